@@ -7,6 +7,8 @@ by oracle/Makefile).  Run in the build container only -- the reference does not 
   <name>.factors.npz L and R after {1, 2, 10, iters} iterations, produced by calling the reference's
                      compiled matrix_factorization() (matFact.c:29) through oracle/_ref/libmatfact_ref.so,
                      plus the reference binary's stdout for cross-checking the .out copy.
+  <name>.in.gz       (LARGE_INPUTS) the reference's larger sample inputs, gzipped, no factors
+  reference_random.npz  seeded random instances and the reference's L, R, B on them (RANDOM_CASES)
 
 Fixtures are data only (inputs and expected outputs); no reference source text is stored.
 """
@@ -61,7 +63,42 @@ def main():
     # the .mats dumps of the three tiny instances (6-decimal prints of L, R, B per iteration)
     for name in ("inst0", "inst1", "inst2"):
         shutil.copyfile(os.path.join(SAMPLES, name + ".mats"), os.path.join(HERE, name + ".mats"))
+    large_inputs()
+    reference_random()
+
+
+# the reference's larger samples, inputs only (the GPU tests compare the backend with the oracle on them); gzip keeps
+# every one under 1 MiB
+LARGE_INPUTS = ["inst50000-5000-100-2-5", "inst400-50000-30-200-500", "inst600-10000-10-40-400"]
+
+# random instances through the reference's own compiled functions (test_oracle_pinned.py: users, items, K per case)
+RANDOM_CASES = [(7, 9, 3), (20, 15, 8), (33, 50, 13), (64, 70, 32)]
+
+
+def large_inputs():
+    for name in LARGE_INPUTS:
+        with open(os.path.join(SAMPLES, name + ".in"), "rb") as f, \
+                gzip.GzipFile(os.path.join(HERE, name + ".in.gz"), "wb", mtime=0) as g:
+            shutil.copyfileobj(f, g)
+
+
+def reference_random():
+    """reference_random.npz: per case the instance (row, col, val) and the reference's L, R and B after its 7
+    iterations (alpha 0.004, user 1 without ratings, user 2 rating every item)."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from conftest import random_instance  # noqa: E402
+    O.build(ref=True)
+    assert O.ref_available(), "oracle/_ref is missing"
+    arrays = {}
+    for seed, (u, i, k) in enumerate(RANDOM_CASES):
+        d = random_instance(100 + seed, u, i, k, density=0.3, iters=7, alpha=0.004, empty_rows=(1,), full_rows=(2,))
+        L, R, B = O.ref_run(O.Instance(**d))
+        arrays.update({"row_%d" % seed: d["row"], "col_%d" % seed: d["col"], "val_%d" % seed: d["val"],
+                       "L_%d" % seed: L, "R_%d" % seed: R, "B_%d" % seed: B})
+    np.savez_compressed(os.path.join(HERE, "reference_random.npz"), **arrays)
 
 
 if __name__ == "__main__":
-    main()
+    # no argument: every fixture; otherwise only the parts named (main, large_inputs, reference_random)
+    for part in sys.argv[1:] or ["main"]:
+        {"main": main, "large_inputs": large_inputs, "reference_random": reference_random}[part]()

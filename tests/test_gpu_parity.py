@@ -453,7 +453,7 @@ def test_two_ranks_one_gpu_sharded_bench(capi):
     from conftest import ROOT
     # no launcher around it: bench.py starts its two ranks itself (child torch.distributed.run before any GPU call)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--config", "twin", "--backend", "gloo", "--check"]
+           "--warmup", "1", "--config", "twin", "--backend", "gloo", "--check", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -463,6 +463,28 @@ def test_two_ranks_one_gpu_sharded_bench(capi):
     assert out["ms_per_step_rank_max"] >= out["ms_per_step_rank_min"] > 0
     assert out["recommend"]["recommended"] > 0 and out["check"]["recommend_differs"] <= 1
     assert out["check"]["L_max_rel"] < 1e-9 and out["check"]["R_max_rel"] < 1e-9, out["check"]
+
+
+def test_bench_dump_outputs_are_the_factors_of_the_timed_steps(orc, tmp_path):
+    """bench.py --dump-outputs: L.npy and R.npy hold the factors after warmup + timed steps, bit for bit the oracle's
+    (ML100k: both factors are written whole); a plain run carries neither the CPU leg nor the recommendation step."""
+    import json
+    import sys
+    from conftest import ROOT
+    dump = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "ml100k", "--steps", "3", "--warmup", "2",
+           "--dump-outputs", str(dump)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["cpu_baseline"] is None and "recommend" not in out
+    L, R = np.load(dump / "L.npy"), np.load(dump / "R.npy")
+    inst = orc.parse_in(golden_in("instML100k"))
+    Lo, Ro = orc.init_factors(inst.users, inst.items, inst.feats)
+    orc.factorize(inst, Lo, Ro, iters=5)
+    assert L.dtype == np.float64 and R.dtype == np.float64
+    assert np.array_equal(L, Lo) and np.array_equal(R, Ro)
 
 
 @pytest.mark.parametrize("impl", ["mfma", "mfma-one-workgroup-per-cu", "mfma-two-per-cu-any-k", "exact"])
@@ -818,13 +840,9 @@ def test_two_live_plans_sharing_a_run_time_k_kernel(capi, orc):
 @pytest.mark.parametrize("name,iters", [("inst50000-5000-100-2-5", 300), ("inst400-50000-30-200-500", 100),
                                          ("inst600-10000-10-40-400", 300)])
 def test_bundled_large_samples_factors_bit_exact(capi, orc, name, iters):
-    """The reference's larger samples (users >> items, items >> users, K = 20 / 30 / 10).  Their `.in` files are too
-    big to commit; samples_local/ holds copies when the tree was prepared in the build container (git-ignored) --
-    skipped otherwise.  Factors after `iters` iterations must equal the oracle's bit for bit."""
-    from conftest import ROOT
-    path = os.path.join(ROOT, "samples_local", name + ".in")
-    if not os.path.exists(path):
-        pytest.skip("samples_local/ not present")
+    """The reference's larger samples (users >> items, items >> users, K = 20 / 30 / 10), gzipped fixtures.  Factors
+    after `iters` iterations must equal the oracle's bit for bit."""
+    path = golden_in(name)
     inst = capi.parse_file(path)
     L, R = capi.init_factors(inst.users, inst.items, inst.feats)
     capi.backend_factorize(inst, L, R, iters=iters)
@@ -909,7 +927,7 @@ def test_four_ranks_one_gpu_grid_bench(capi):
     import sys
     from conftest import ROOT
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "3",
-           "--warmup", "1", "--config", "twin", "--backend", "gloo", "--grid", "2x2", "--check"]
+           "--warmup", "1", "--config", "twin", "--backend", "gloo", "--grid", "2x2", "--check", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

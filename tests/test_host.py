@@ -228,6 +228,21 @@ def test_bench_accounting_and_skewed_generator():
     assert pop.max() > 4 * np.median(pop)                                 # power-law popularity
 
 
+def test_bench_dump_rows_fixed_and_bounded():
+    """--dump-outputs: the same rows in every run, in index order, and L plus R under 64 MB at every configuration."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert 2 * b.DUMP_BYTES + 1024 <= 64e6
+    for cfg in b.CONFIGS.values():
+        for n, seed in ((cfg["users"], 1), (cfg["items"], 2)):
+            rows = b.dump_rows(n, cfg["feats"], seed)
+            assert np.array_equal(rows, b.dump_rows(n, cfg["feats"], seed))
+            assert rows.size * cfg["feats"] * 8 <= b.DUMP_BYTES and np.all(np.diff(rows) > 0) and rows[-1] < n
+    assert np.array_equal(b.dump_rows(943, 30, 1), np.arange(943))        # a small factor is written whole
+
+
 def test_parallel_parser_equals_sequential_semantics(capi, orc, tmp_path):
     """Inputs large enough for the parallel body parser (>= 65536 entries): same entries as the reference
     grammar gives, number forms included; irregular bodies fall back to the sequential parser and its errors."""

@@ -2,7 +2,7 @@
 # bench lines of the other BASELINE-shaped configurations (one JSON line each under gpurun_out/configs/), every one
 # that has a plain single-wave counterpart with --check (bit-identity of the factors against that form)
 R=${GRAFT_REPO_ROOT:-.}; O=$R/gpurun_out/configs; rm -rf $O; mkdir -p $O; cd $R
-b() { name=$1; shift; python3 bench.py "$@" --no-cpu-baseline > $O/$name.json 2> $O/$name.err || { echo "$name failed"; tail -3 $O/$name.err; return 1; }
+b() { name=$1; shift; python3 bench.py "$@" --full --no-cpu-baseline > $O/$name.json 2> $O/$name.err || { echo "$name failed"; tail -3 $O/$name.err; return 1; }
       python3 - $O/$name.json $name <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1]); r = d["roofline"]

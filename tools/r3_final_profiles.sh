@@ -24,7 +24,7 @@ json.dump(t, open(R + "/gpurun_out/final3/pmc_traffic.json", "w"), indent=1)
 print("cfg5 PMC bytes per launch %.4g over algorithmic %.4g = %.3f" % (t["cfg5_n1"]["hbm_bytes_per_launch"], t["cfg5_n1"]["algorithmic_bytes_per_launch"],
                                                                          t["cfg5_n1"]["hbm_bytes_per_launch"] / t["cfg5_n1"]["algorithmic_bytes_per_launch"]))
 PY
-python3 bench.py > $O/cfg4_n1_bench.json 2> $O/cfg4_n1_bench.err || exit 1
+python3 bench.py --full > $O/cfg4_n1_bench.json 2> $O/cfg4_n1_bench.err || exit 1
 python3 - $O/cfg4_n1_bench.json <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1]); r=d["roofline"]; c=d["cpu_baseline"]

@@ -1,10 +1,10 @@
 # Runs on the GPU box: kernel-trace stats, the two PMC passes (separately, as the guide prescribes) and the bench
 # line of the default configuration; raw outputs under gpurun_out/refresh/, summaries copied by the caller.
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/refresh; rm -rf $O; mkdir -p $O; cd /tmp
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline > $O/stats_bench.json 2> $O/stats.err || exit 1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline > $O/stats_bench.json 2> $O/stats.err || exit 1
 timeout -k 10 500 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_fetch.json 2> $O/pmc_fetch.err || exit 1
 timeout -k 10 500 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_write.json 2> $O/pmc_write.err || exit 1
-cd $R && python3 bench.py > $O/bench.json 2> $O/bench.err || exit 1
+cd $R && python3 bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
 python3 - <<PY
 import csv, glob, json
 O = "$O"
