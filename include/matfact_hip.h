@@ -35,7 +35,9 @@ extern "C" {
                                           order-nondeterministic and slower than the owner-computes gather)
                                        4: mf_shard.items_pitch / users_pitch, mf_backend_row_pitch, mf_plan_row_pitch
                                        5: mf_backend_multi_last_counters (one host thread per shard enqueues its
-                                          iterations; MF_MULTI_THREADS=0 keeps the single enqueueing thread) */
+                                          iterations; MF_MULTI_THREADS=0 keeps the single enqueueing thread);
+                                          additive since: top-N recommendations (MF_TOPN_MAX, mf_plan_recommend_topn,
+                                          mf_plan_recommend_topn_info, mf_backend_recommend_topn, mf_backend_run_topn) */
 
 /* == non_zero_entry, datatypes.h:10-15: the (user, item, rating) triple, 16 bytes, array-of-structs */
 typedef struct mf_entry {
@@ -87,6 +89,20 @@ int mf_backend_run(const mf_problem *p, double *L, double *R, int32_t *best, int
 /* The same when only the recommendation list is wanted -- what the reference's main prints (matFact.c:127):
  * the initial factors go in, nothing but best[] comes back (no device-to-host copy of L and R). */
 int mf_backend_run_top1(const mf_problem *p, const double *L0, const double *R0, int32_t *best, int device);
+
+/* Top-N recommendations (an extension: the reference prints one item per user).  items and scores are user_count x n,
+ * row-major; 1 <= n <= MF_TOPN_MAX.  Row i is T_i = print_output's rule applied n times, each pick removed from the set
+ * of unrated items: empty set -> -1; first = its lowest index; B[i][first] NaN -> first; otherwise the arg-max over the
+ * non-NaN scores, the lowest index on ties.  With finite scores that is the n largest in descending order, ties by
+ * ascending index; t_1 is exactly mf_backend_recommend's best[i].  scores[i][r] = B[i][t_r] bit for bit (sequential k,
+ * unfused, mat2d.c:100-113), NaN where t_r = -1.  n < 1 or items == NULL -> MF_ERR_ARGUMENT, n > MF_TOPN_MAX ->
+ * MF_ERR_UNSUPPORTED, both before any HIP call.  scores may be NULL. */
+#define MF_TOPN_MAX 32
+int mf_backend_recommend_topn(const mf_problem *p, const double *L, const double *R, int32_t n, int32_t *items,
+                              double *scores, int device);
+/* factorize + top-N: the twin of mf_backend_run_top1 (no copy-back of the factors) */
+int mf_backend_run_topn(const mf_problem *p, const double *L0, const double *R0, int32_t n, int32_t *items, double *scores,
+                        int device);
 
 /* The same on several GPUs of ONE process: users are cut into ndev contiguous blocks balanced by entry count,
  * L blocks are private, R is replicated and summed after every item sweep (the decomposition of
@@ -191,6 +207,17 @@ void *mf_plan_users_current(mf_plan *plan);
 int mf_plan_recommend(mf_plan *plan, int32_t *best);
 /* users the last mf_plan_recommend sent through the exact pass (-1 when the exact form ran for all) */
 int mf_plan_recommend_info(mf_plan *plan, int64_t *exact_pass_users);
+
+/* Top-N for this shard's users (semantics: mf_backend_recommend_topn).  Default form: the N+1 best matrix-core scores
+ * per user; a user is certified when no non-finite score was seen and a_N - a_{N+1} exceeds the margin of
+ * mf_plan_recommend (or it has at most N unrated items), and its N members are then re-scored exactly and ordered;
+ * everyone else goes through the exact pass.  Matrix-core forms exist for K = 20c <= 100, 16c <= 128 and 256; other K,
+ * and MF_RECOMMEND_IMPL=exact, run the exact pass for every user.  Item indices are block-relative on a 2-D tile. */
+int mf_plan_recommend_topn(mf_plan *plan, int32_t n, int32_t *items, double *scores);
+/* the last mf_plan_recommend_topn: users that went through the exact pass (-1 when the exact form ran for all) and
+ * the form that ran (0 exact for all users, 1 matrix cores at two workgroups per CU, 2 matrix cores at one per CU;
+ * -1 before the first call; 0 and 0 after a call on a plan without users).  Either pointer may be NULL. */
+int mf_plan_recommend_topn_info(mf_plan *plan, int64_t *exact_pass_users, int32_t *mfma_form);
 
 /* Partial result of the sequential scan of print_output (matFact.c:13-23) over this plan's items, in a form
  * that can be combined over the item blocks of a grid row (what MPI_Reduce(max_cmp) does at matFact-mpi.c:98):

@@ -13,6 +13,7 @@
  *                           or balanced by entry count
  *   mf_host_balanced_grid   rows x cols of the 2-D process grid       mpiutil.c:54-88 (create_balanced_grid)
  *   mf_host_write_out       the `.out` writer         matFact.c:24-25
+ *   mf_host_write_topn      its top-N form            (an extension: no reference counterpart)
  *   mf_host_synth_*         deterministic synthetic instances (the reference ships no generator;
  *                           SURVEY.md section 8d defines the shapes)
  */
@@ -91,6 +92,9 @@ int mf_host_balanced_grid(int users, int items, int nproc, int32_t size[2]);
 
 /* one line per user with best >= 0 */
 int mf_host_write_out(FILE *f, const int32_t *best, int users);
+/* top-N form (items: users x n, row-major, from mf_backend_run_topn): one line per user with at least one item >= 0, its
+ * items >= 0 separated by single spaces; with n = 1 byte-identical to mf_host_write_out */
+int mf_host_write_topn(FILE *f, const int32_t *items, int users, int n);
 
 /* ---- iteration checkpoint (the reference has none): a binary file holding the header of the
  * instance it belongs to, the number of iterations already done, and L and R.  Resuming reproduces the

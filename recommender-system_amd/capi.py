@@ -22,6 +22,7 @@ _f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 
 MF_OK = 0
 MF_ERR_ARGUMENT, MF_ERR_NO_DEVICE, MF_ERR_HIP, MF_ERR_NO_MEMORY, MF_ERR_UNSUPPORTED, MF_ERR_STATE = -1, -2, -3, -4, -5, -6
+MF_TOPN_MAX = 32
 
 # every symbol include/matfact_hip.h declares (tests check the library exports each one)
 HIP_SYMBOLS = [
@@ -35,6 +36,7 @@ HIP_SYMBOLS = [
     "mf_plan_recommend_scored_users", "mf_plan_recommend_filter", "mf_backend_recommend_margin",
     "mf_plan_predict", "mf_plan_synchronize",
     "mf_plan_timing", "mf_plan_timing_read", "mf_plan_describe",
+    "mf_backend_recommend_topn", "mf_backend_run_topn", "mf_plan_recommend_topn", "mf_plan_recommend_topn_info",
 ]
 HOST_SYMBOLS = [
     "mf_host_parse_strerror", "mf_host_parse_file", "mf_host_parse_buffer", "mf_host_free_problem",
@@ -42,7 +44,7 @@ HOST_SYMBOLS = [
     "mf_host_srandom", "mf_host_random", "mf_host_init_factors", "mf_host_init_factors_block",
     "mf_host_split_entries", "mf_host_partition_users", "mf_host_balanced_grid", "mf_host_write_out", "mf_host_checkpoint_write",
     "mf_host_checkpoint_read", "mf_host_synth_counts",
-    "mf_host_synth_fill",
+    "mf_host_synth_fill", "mf_host_write_topn",
 ]
 
 
@@ -148,6 +150,10 @@ def hip():
         lib.mf_plan_timing_read.argtypes = [P, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                             C.POINTER(C.c_int64), C.POINTER(C.c_double)]
         lib.mf_plan_describe.argtypes = [P, C.c_char_p, C.c_int]
+        lib.mf_backend_recommend_topn.argtypes = [C.POINTER(Problem), P, P, C.c_int32, P, P, C.c_int]
+        lib.mf_backend_run_topn.argtypes = [C.POINTER(Problem), P, P, C.c_int32, P, P, C.c_int]
+        lib.mf_plan_recommend_topn.argtypes = [P, C.c_int32, P, P]
+        lib.mf_plan_recommend_topn_info.argtypes = [P, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         _hip = lib
     return _hip
 
@@ -180,6 +186,7 @@ def host():
         lib.mf_host_synth_counts.argtypes = [C.POINTER(Synth), C.c_int, C.c_int, _i32p]
         lib.mf_host_synth_counts.restype = C.c_int64
         lib.mf_host_synth_fill.argtypes = [C.POINTER(Synth), C.c_int, C.c_int, _i32p, _i32p, _i32p, _f64p]
+        lib.mf_host_write_topn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         _host = lib
     return _host
 
@@ -412,6 +419,45 @@ def backend_recommend(inst, L, R, device=0):
     return best
 
 
+def _topn(entry, inst, L, R, n, iters=None, device=0):
+    p, keep = _problem(inst, iters)
+    L = np.ascontiguousarray(L, np.float64)
+    R = np.ascontiguousarray(R, np.float64)
+    items = np.empty((inst.users, max(int(n), 0)), np.int32)
+    scores = np.empty((inst.users, max(int(n), 0)), np.float64)
+    _check(getattr(hip(), entry)(C.byref(p), L.ctypes.data, R.ctypes.data, int(n), items.ctypes.data, scores.ctypes.data,
+                                 device), entry)
+    return items, scores
+
+
+def backend_recommend_topn(inst, L, R, n, device=0):
+    """mf_backend_recommend_topn: (items, scores), users x n; item -1 / score NaN past the user's unrated items."""
+    return _topn("mf_backend_recommend_topn", inst, L, R, n, device=device)
+
+
+def backend_run_topn(inst, L0, R0, n, iters=None, device=0):
+    """mf_backend_run_topn: initial factors in, (items, scores) of the top-N lists out (no copy-back of the factors)."""
+    return _topn("mf_backend_run_topn", inst, L0, R0, n, iters=iters, device=device)
+
+
+def write_topn(items):
+    """mf_host_write_topn of an (users x n) int32 array, as bytes."""
+    import tempfile
+    items = np.ascontiguousarray(items, np.int32)
+    libc = C.CDLL(None)
+    libc.fdopen.restype = C.c_void_p
+    libc.fdopen.argtypes = [C.c_int, C.c_char_p]
+    libc.fclose.argtypes = [C.c_void_p]
+    with tempfile.TemporaryFile() as tf:
+        f = libc.fdopen(os.dup(tf.fileno()), b"w")
+        rc = host().mf_host_write_topn(f, items.ctypes.data, items.shape[0], items.shape[1])
+        libc.fclose(f)
+        if rc != 0:
+            raise ValueError("mf_host_write_topn failed")
+        tf.seek(0)
+        return tf.read()
+
+
 # ------------------------------------------------------------------------------------ level 2
 class Plan:
     """mf_plan: one shard resident on one GPU."""
@@ -490,6 +536,21 @@ class Plan:
         best = np.empty(self.user_count, np.int32)
         _check(hip().mf_plan_recommend(self._h, best), "mf_plan_recommend")
         return best
+
+    def recommend_topn(self, n, scores=True):
+        """mf_plan_recommend_topn: (items, scores) of shape (user_count, n), or items alone with scores=False."""
+        items = np.empty((self.user_count, max(int(n), 0)), np.int32)
+        sc = np.empty((self.user_count, max(int(n), 0)), np.float64) if scores else None
+        _check(hip().mf_plan_recommend_topn(self._h, int(n), items.ctypes.data, sc.ctypes.data if scores else None),
+               "mf_plan_recommend_topn")
+        return (items, sc) if scores else items
+
+    def recommend_topn_info(self):
+        """(users of the last recommend_topn that went through the exact pass, or -1 when the exact form ran for all;
+        form: 0 exact, 1 matrix cores at two workgroups per CU, 2 at one per CU)"""
+        n, f = C.c_int64(), C.c_int32()
+        _check(hip().mf_plan_recommend_topn_info(self._h, C.byref(n), C.byref(f)), "mf_plan_recommend_topn_info")
+        return n.value, f.value
 
     def recommend_scored(self):
         """Partial scan state per user (CANDIDATE_DTYPE records); item ids relative to this plan's item block."""

@@ -221,6 +221,15 @@ void mf_plan_destroy(mf_plan *p)
 	(void) hipFree(p->cand_pack);
 	(void) hipFree(p->filt_dev);
 	(void) hipFree(p->part_dev);
+	(void) hipFree(p->topn_items);
+	(void) hipFree(p->topn_scores);
+	(void) hipFree(p->topn_part_v);
+	(void) hipFree(p->topn_part_i);
+	(void) hipFree(p->topn_part_bad);
+#ifdef MF_REC_TOPNGL
+	(void) hipFree(p->topn_glist_v);
+	(void) hipFree(p->topn_glist_i);
+#endif
 	if (!p->r_external) {
 		(void) hipFree(p->Rbuf[0]);
 		(void) hipFree(p->Rbuf[1]);
@@ -742,6 +751,205 @@ int mf_plan_recommend_info(mf_plan *p, int64_t *exact_pass_users)
 	return MF_OK;
 }
 
+}   // extern "C"
+
+// Grows a cached device buffer to at least `count` elements (contents are not kept).
+template <typename T>
+static int topn_grow(T **buf, size_t *cap, size_t count)
+{
+	if (*cap >= count) return MF_OK;
+	(void) hipFree(*buf);
+	*buf = nullptr;
+	*cap = 0;
+	const int rc = dev_alloc(buf, count);
+	if (rc == MF_OK) *cap = count;
+	return rc;
+}
+
+// Top-N on the device: rows of n items / scores per user in p->topn_items / p->topn_scores (nothing copied back).
+// Matrix-core pass (topn_mfma_kernel) with certification and exact re-scoring of the members, the exact pass
+// (topn_exact_kernel) for every user it cannot decide; the exact pass for all users under MF_RECOMMEND_IMPL=exact or
+// when K has no matrix-core form.
+static int launch_topn(mf_plan *p, int n)
+{
+	MF_HIP(hipSetDevice(p->device));
+	{
+		const size_t need = (size_t) p->uc * (size_t) n;
+		size_t cap_s = p->topn_cap;
+		int rc = topn_grow(&p->topn_items, &p->topn_cap, need);
+		if (rc == MF_OK) rc = topn_grow(&p->topn_scores, &cap_s, need);
+		if (rc != MF_OK) {
+			(void) hipFree(p->topn_scores);
+			p->topn_scores = nullptr;
+			(void) hipFree(p->topn_items);
+			p->topn_items = nullptr;
+			p->topn_cap = 0;
+			return rc;
+		}
+	}
+	mf::TopnArgs a;
+	memset(&a, 0, sizeof a);
+	a.users = p->uc;
+	a.items = p->items;
+	a.K = p->K;
+	a.ldl = p->ldl;
+	a.ldr = p->ldr;
+	a.L = p->Lbuf[p->cur];
+	a.R = p->Rbuf[p->cur];
+	a.csr_ptr = p->csr_ptr;
+	a.csr_idx = p->mask_idx ? p->mask_idx : p->csr_idx;
+	a.lnorm = p->lnorm;
+	a.rnorm_max_bits = p->rmax_bits;
+	a.thr_scale = mf_backend_recommend_margin(p->K);
+	a.n = n;
+	a.out_items = p->topn_items;
+	a.out_scores = p->topn_scores;
+	a.olist = p->ulist;
+	a.ocount = p->ucount;
+
+	// the matrix-core shapes of recommend_mfma2_kernel: K = 20 NC <= 100, 16 NC <= 96 (four waves), 112, 128, 256 (eight waves)
+	typedef void (*TopnFn)(mf::TopnArgs);
+	const int K = p->K;
+	const bool fits32 = (unsigned long long) p->items * (unsigned long long) p->ldr * 8ull < (1ull << 32);   // 32-bit row offsets
+	TopnFn fn = nullptr;
+	int qc = 0, waves = 4;
+	if (!p->cfg.rec_exact && fits32 && p->items > 0) {
+		if (K % 20 == 0 && K <= 100) {
+			static const TopnFn f20[5] = {mf::topn_mfma_kernel<1>, mf::topn_mfma_kernel<2>, mf::topn_mfma_kernel<3>,
+			                              mf::topn_mfma_kernel<4>, mf::topn_mfma_kernel<5>};
+			fn = f20[K / 20 - 1];
+			qc = 5;
+		} else if (K % 16 == 0 && K <= 96) {
+			static const TopnFn f16[6] = {mf::topn_mfma_kernel<1, 4>, mf::topn_mfma_kernel<2, 4>, mf::topn_mfma_kernel<3, 4>,
+			                              mf::topn_mfma_kernel<4, 4>, mf::topn_mfma_kernel<5, 4>, mf::topn_mfma_kernel<6, 4>};
+			fn = f16[K / 16 - 1];
+			qc = 4;
+		} else if (K == 112) {   // at 32 users per wave K = 112 and 128 spill (the list walk beside 224 / 256 VGPRs of L operand):
+			fn = mf::topn_mfma_kernel<7, 4, 1, 8>;   // 16 users per wave, eight waves, as K = 256
+			qc = 4;
+			waves = 8;
+		} else if (K == 128) {
+			fn = mf::topn_mfma_kernel<4, 8, 1, 8>;
+			qc = 8;
+			waves = 8;
+		} else if (K == 256) {
+			fn = mf::topn_mfma_kernel<8, 8, 1, 8>;
+			qc = 8;
+			waves = 8;
+		}
+	}
+	if (!fn) {
+		hipLaunchKernelGGL(mf::topn_exact_kernel, dim3(p->uc), dim3(64), 0, p->stream, a);
+		MF_HIP(hipGetLastError());
+		p->last_topn_uncertain = -1;
+		p->topn_form = 0;
+		return MF_OK;
+	}
+
+	MF_HIP(hipMemsetAsync(p->rmax_bits, 0, sizeof(unsigned long long), p->stream));
+	MF_HIP(hipMemsetAsync(p->ucount, 0, sizeof(int), p->stream));
+	hipLaunchKernelGGL(mf::row_norm_kernel, dim3((p->uc + 63) / 64), dim3(64), 0, p->stream, a.L, p->uc, p->K, p->ldl, p->lnorm,
+	                   (unsigned long long *) nullptr);
+	hipLaunchKernelGGL(mf::row_norm_kernel, dim3((p->items + 63) / 64), dim3(64), 0, p->stream, a.R, p->items, p->K, p->ldr,
+	                   (double *) nullptr, p->rmax_bits);
+#ifdef MF_REC_TOPNGL
+	const size_t lds = mf::rec_mfma2_lds(qc);
+#else
+	const size_t lds = mf::rec_mfma2_lds(qc) + mf::topn_list_lds(n);
+#endif
+	MF_HIP(raise_lds_limit((const void *) fn, lds));
+	// two four-wave workgroups per CU while ring + lists + the static arrays (< 3 KB) fit half of the CU's 160 KB
+	const bool two_per_cu = waves == 4 && lds + 3 * 1024 <= 80 * 1024;
+	p->topn_form = two_per_cu ? 1 : 2;
+
+	// item split of small problems: the rule and MF_RECOMMEND_SPLIT of the top-1 pass
+	const int ublocks = (p->uc + mf::kHU - 1) / mf::kHU, tiles = (p->items + mf::kMI - 1) / mf::kMI;
+	const int chip = two_per_cu ? 1024 : 512;
+	int nsplit = 1;
+	if (p->cfg.rec_split != 0 && ublocks < chip * 3 / 8 && tiles >= 2) {
+		nsplit = p->cfg.rec_split > 0 ? p->cfg.rec_split : (chip + ublocks - 1) / ublocks;
+		nsplit = std::max(1, std::min(nsplit, tiles));
+	}
+	if (nsplit > 1) {
+		const int tiles_per = (tiles + nsplit - 1) / nsplit;
+		nsplit = (tiles + tiles_per - 1) / tiles_per;
+		a.split_items = tiles_per * mf::kMI;
+		a.nsplit = nsplit;
+		const size_t nl = (size_t) p->uc * (size_t) (nsplit + 1) * (size_t) (n + 1);
+		size_t cap_i = p->topn_part_cap;
+		int rc = topn_grow(&p->topn_part_v, &p->topn_part_cap, nl);
+		if (rc == MF_OK) rc = topn_grow(&p->topn_part_i, &cap_i, nl);
+		if (rc == MF_OK) rc = topn_grow(&p->topn_part_bad, &p->topn_bad_cap, (size_t) p->uc * (size_t) nsplit);
+		if (rc != MF_OK) {
+			(void) hipFree(p->topn_part_v);
+			(void) hipFree(p->topn_part_i);
+			p->topn_part_v = nullptr;
+			p->topn_part_i = nullptr;
+			p->topn_part_cap = 0;
+			return rc;
+		}
+		a.part_v = p->topn_part_v;
+		a.part_i = p->topn_part_i;
+		a.part_bad = p->topn_part_bad;
+	}
+#ifdef MF_REC_TOPNGL
+	{   // timing build: the lists of every workgroup in global memory (freed with the plan's other top-N buffers)
+		const size_t ng = (size_t) ublocks * (size_t) nsplit * (size_t) mf::kHU * 2 * (size_t) (n + 1);
+		size_t cap_i = p->topn_glist_cap;
+		int rc = topn_grow(&p->topn_glist_v, &p->topn_glist_cap, ng);
+		if (rc == MF_OK) rc = topn_grow(&p->topn_glist_i, &cap_i, ng);
+		if (rc != MF_OK) return rc;
+		a.glist_v = p->topn_glist_v;
+		a.glist_i = p->topn_glist_i;
+	}
+#endif
+	hipLaunchKernelGGL(fn, dim3(ublocks, nsplit), dim3(64 * waves), lds, p->stream, a);
+	MF_HIP(hipGetLastError());
+	if (nsplit > 1) {
+		hipLaunchKernelGGL(mf::topn_merge_kernel, dim3((p->uc + 255) / 256), dim3(256), 0, p->stream, a);
+		MF_HIP(hipGetLastError());
+	}
+	int cnt = 0;
+	MF_HIP(hipMemcpyAsync(&cnt, p->ucount, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+	MF_HIP(hipStreamSynchronize(p->stream));
+	p->last_topn_uncertain = cnt;
+	if (cnt > 0) {
+		a.ulist = p->ulist;
+		hipLaunchKernelGGL(mf::topn_exact_kernel, dim3(cnt), dim3(64), 0, p->stream, a);
+		MF_HIP(hipGetLastError());
+	}
+	return MF_OK;
+}
+
+extern "C" {
+
+int mf_plan_recommend_topn(mf_plan *p, int32_t n, int32_t *items, double *scores)
+{
+	if (!p || n < 1 || !items) return MF_ERR_ARGUMENT;
+	if (n > MF_TOPN_MAX) return MF_ERR_UNSUPPORTED;
+	if (!p->have_factors) return MF_ERR_STATE;
+	if (p->uc == 0) {   // nothing to rank: no pass ran
+		p->last_topn_uncertain = 0;
+		p->topn_form = 0;
+		return MF_OK;
+	}
+	const int rc = launch_topn(p, n);
+	if (rc != MF_OK) return rc;
+	const size_t cnt = (size_t) p->uc * (size_t) n;
+	MF_HIP(hipMemcpyAsync(items, p->topn_items, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
+	if (scores) MF_HIP(hipMemcpyAsync(scores, p->topn_scores, cnt * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+	MF_HIP(hipStreamSynchronize(p->stream));
+	return MF_OK;
+}
+
+int mf_plan_recommend_topn_info(mf_plan *p, int64_t *exact_pass_users, int32_t *mfma_form)
+{
+	if (!p) return MF_ERR_ARGUMENT;
+	if (exact_pass_users) *exact_pass_users = p->last_topn_uncertain;
+	if (mfma_form) *mfma_form = p->topn_form;
+	return MF_OK;
+}
+
 int mf_plan_predict(mf_plan *p, double *B)
 {
 	if (!p || !B) return MF_ERR_ARGUMENT;
@@ -868,6 +1076,35 @@ int mf_backend_run_top1(const mf_problem *pr, const double *L0, const double *R0
 	rc = mf_plan_upload_factors(p, L0, R0);
 	if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
 	if (rc == MF_OK) rc = mf_plan_recommend(p, best);
+	mf_plan_destroy(p);
+	return rc;
+}
+
+int mf_backend_run_topn(const mf_problem *pr, const double *L0, const double *R0, int32_t n, int32_t *items, double *scores,
+                        int device)
+{
+	if (!pr || !L0 || !R0 || n < 1 || !items) return MF_ERR_ARGUMENT;
+	if (n > MF_TOPN_MAX) return MF_ERR_UNSUPPORTED;
+	mf_plan *p = nullptr;
+	int rc = make_single_plan(pr, device, &p);
+	if (rc != MF_OK) return rc;
+	rc = mf_plan_upload_factors(p, L0, R0);
+	if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
+	if (rc == MF_OK) rc = mf_plan_recommend_topn(p, n, items, scores);
+	mf_plan_destroy(p);
+	return rc;
+}
+
+int mf_backend_recommend_topn(const mf_problem *pr, const double *L, const double *R, int32_t n, int32_t *items,
+                              double *scores, int device)
+{
+	if (!pr || !L || !R || n < 1 || !items) return MF_ERR_ARGUMENT;
+	if (n > MF_TOPN_MAX) return MF_ERR_UNSUPPORTED;
+	mf_plan *p = nullptr;
+	int rc = make_single_plan(pr, device, &p);
+	if (rc != MF_OK) return rc;
+	rc = mf_plan_upload_factors(p, L, R);
+	if (rc == MF_OK) rc = mf_plan_recommend_topn(p, n, items, scores);
 	mf_plan_destroy(p);
 	return rc;
 }

@@ -5,4 +5,5 @@
 #include "mf_stream.hip.h"
 #include "mf_resident.hip.h"
 #include "mf_recommend.hip.h"
+#include "mf_topn.hip.h"
 #include "mf_collective.hip.h"

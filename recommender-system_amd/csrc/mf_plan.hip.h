@@ -178,6 +178,20 @@ struct mf_plan {
 	unsigned long long *rmax_bits = nullptr;
 	int *ulist = nullptr, *ucount = nullptr;
 	int64_t last_uncertain = -1;   // users re-scored by the exact pass in the last recommend (-1: exact form ran)
+	// top-N (mf_plan_recommend_topn): output rows and per-split lists, allocated on first use and grown on demand
+	int *topn_items = nullptr;
+	double *topn_scores = nullptr;
+	size_t topn_cap = 0;             // entries of topn_items / topn_scores
+	double *topn_part_v = nullptr;
+	int *topn_part_i = nullptr, *topn_part_bad = nullptr;
+	size_t topn_part_cap = 0, topn_bad_cap = 0;
+	int64_t last_topn_uncertain = -1;   // users of the last top-N call that went through the exact pass (-1: exact form ran)
+	int topn_form = -1;                 // form of the last top-N call (mf_plan_recommend_topn_info)
+#ifdef MF_REC_TOPNGL
+	double *topn_glist_v = nullptr;     // timing build: the matrix-core pass's lists in global memory
+	int *topn_glist_i = nullptr;
+	size_t topn_glist_cap = 0;
+#endif
 
 	SweepVariant sweep{};
 	int nch = 0, stride = 0;

@@ -155,6 +155,18 @@ int main(int argc, char **argv)
 		fprintf(stderr, "Run ./matFact.out file");   /* matFact.c:65 */
 		die("Missing input file name.");
 	}
+	/* MATFACT_TOPN=N (1..MF_TOPN_MAX): N items per user on one line each instead of one (mf_host_write_topn); the single-GPU
+	 * default path only.  Checked before the input is read: a bad value prints nothing. */
+	int topn = 0;
+	const char *topn_env = getenv("MATFACT_TOPN");
+	if (topn_env) {
+		char *stop;
+		const long v = strtol(topn_env, &stop, 10);
+		if (stop == topn_env || *stop || v < 1 || v > MF_TOPN_MAX) die("MATFACT_TOPN: expected a whole number from 1 to 32.");
+		if (getenv("MATFACT_DEVICES") || getenv("MATFACT_MATS") || getenv("MATFACT_CHECKPOINT") || getenv("MATFACT_RESUME"))
+			die("MATFACT_TOPN works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT and MATFACT_RESUME.");
+		topn = (int) v;
+	}
 	const double t0 = now();
 
 	mf_problem prob;
@@ -174,6 +186,12 @@ int main(int argc, char **argv)
 	mf_host_init_factors(prob.users, prob.items, prob.features, L, R);
 	const double t2 = now();
 
+	int32_t *topn_items = NULL;
+	if (topn) {
+		topn_items = malloc(sizeof(int32_t) * (size_t) (prob.users > 0 ? prob.users : 1) * (size_t) topn);
+		if (!topn_items) die("Out of memory.");
+	}
+
 	int device = 0;
 	if (getenv("MATFACT_DEVICE")) device = atoi(getenv("MATFACT_DEVICE"));
 	const char *mats = getenv("MATFACT_MATS");
@@ -183,7 +201,9 @@ int main(int argc, char **argv)
 		if (mf_host_checkpoint_read(getenv("MATFACT_RESUME"), &prob, &start_iter, L, R) != 0)
 			die("MATFACT_RESUME: cannot read the checkpoint or it belongs to another instance.");
 	}
-	if (getenv("MATFACT_CHECKPOINT") || getenv("MATFACT_RESUME")) {
+	if (topn) {
+		rc = mf_backend_run_topn(&prob, L, R, topn, topn_items, NULL, device);
+	} else if (getenv("MATFACT_CHECKPOINT") || getenv("MATFACT_RESUME")) {
 		rc = run_with_checkpoints(&prob, L, R, best, device, start_iter);
 	} else if (mats) {
 		rc = run_with_mats(mats, &prob, L, R, best, device);
@@ -206,13 +226,17 @@ int main(int argc, char **argv)
 	}
 	const double t3 = now();
 
-	mf_host_write_out(stdout, best, prob.users);
+	if (topn)
+		mf_host_write_topn(stdout, topn_items, prob.users, topn);
+	else
+		mf_host_write_out(stdout, best, prob.users);
 	fflush(stdout);
 
 	if (getenv("MATFACT_TIMING"))
 		fprintf(stderr, "parse%s %.6f init %.6f gpu(run) %.6f total %.6f\n", cache_hit ? "(cache)" : "", t1 - t0, t2 - t1,
 		        t3 - t2, now() - t0);
 	free(best);
+	free(topn_items);
 	free(L);
 	free(R);
 	mf_host_free_problem(&prob);

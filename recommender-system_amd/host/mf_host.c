@@ -692,6 +692,21 @@ int mf_host_write_out(FILE *f, const int32_t *best, int users)
 	return 0;
 }
 
+int mf_host_write_topn(FILE *f, const int32_t *items, int users, int n)
+{
+	if (!f || n < 1 || (users > 0 && !items)) return -1;
+	for (int i = 0; i < users; i++) {
+		int put = 0;
+		for (int r = 0; r < n; r++) {
+			const int32_t t = items[(size_t) i * n + r];
+			if (t >= 0 && fprintf(f, put ? " %d" : "%d", t) < 0) return -1;
+			put += t >= 0;
+		}
+		if (put && fputc('\n', f) == EOF) return -1;
+	}
+	return 0;
+}
+
 /* ------------------------------------------------------------------------------------ checkpoint */
 
 int mf_host_checkpoint_write(const char *path, const mf_problem *p, int iters_done, const double *L, const double *R)
