@@ -37,7 +37,9 @@ extern "C" {
                                        5: mf_backend_multi_last_counters (one host thread per shard enqueues its
                                           iterations; MF_MULTI_THREADS=0 keeps the single enqueueing thread);
                                           additive since: top-N recommendations (MF_TOPN_MAX, mf_plan_recommend_topn,
-                                          mf_plan_recommend_topn_info, mf_backend_recommend_topn, mf_backend_run_topn) */
+                                          mf_plan_recommend_topn_info, mf_backend_recommend_topn, mf_backend_run_topn);
+                                          loss (mf_plan_loss, mf_plan_set_heldout, mf_plan_iterate_monitored,
+                                          mf_backend_loss, mf_backend_loss_total) */
 
 /* == non_zero_entry, datatypes.h:10-15: the (user, item, rating) triple, 16 bytes, array-of-structs */
 typedef struct mf_entry {
@@ -253,6 +255,49 @@ typedef struct mf_filter {
 } mf_filter;
 int mf_plan_recommend_filter(mf_plan *plan, mf_filter *out, double *norm, double *rmax);
 double mf_backend_recommend_margin(int features);   /* 8 * (K + 8) * 2^-53 */
+
+/* ---- Loss: the squared error of L R^T over an entry set E -- the plan's training entries or a held-out set -- for the
+ * plan's current factors.  An extension (the reference computes no loss), so the definition is this library's; it fixes
+ * the order of every floating-point operation, and the result is the same bits whatever kernel form, chunk size or
+ * shard count produced it:
+ *   1. p_n = dot(L[i_n], R[j_n]): k ascending from 0.0, multiply and add unfused (mat2d.c:126-139) = B[i][j] of
+ *      mf_plan_predict bit for bit;
+ *   2. d_n = a_n - p_n, q_n = d_n * d_n (no alpha);
+ *   3. row sum s_i = (((0.0 + q_n0) + q_n1) + ...) over the entries of user i in the order the caller gave them
+ *      (0.0 for a user without entries);
+ *   4. users are cut into blocks of MF_LOSS_BLOCK consecutive users counted from GLOBAL user 0; T_b = the s_i of block b
+ *      added in ascending i from 0.0; SSE = the T_b added in ascending b from 0.0;
+ *   5. count = |E|; RMSE = sqrt(SSE / count) in double on the host (NaN when count == 0).
+ * NaN and infinities propagate by these rules (a NaN result is a NaN; which sign and payload it carries is the hardware's
+ * choice, as IEEE 754 leaves it).  A shard's mf_loss.sse is step 4 over ITS users (blocks still cut at
+ * global multiples of MF_LOSS_BLOCK); shard totals cannot be added to the single-plan bits -- concatenate the shards'
+ * row_sse and apply mf_backend_loss_total.  On a 2-D tile the loss is that of the tile's own entries. */
+#define MF_LOSS_BLOCK 1024
+#define MF_LOSS_TRAIN 0
+#define MF_LOSS_HELDOUT 1
+typedef struct mf_loss { double sse; int64_t count; } mf_loss;          /* rmse = sqrt(sse / count) */
+
+/* Held-out set resident in the plan: n triples (GLOBAL user ids inside the shard's range, items inside [0, items), else
+ * MF_ERR_ARGUMENT and nothing changes), bucketed by user stably: inside a user the caller's order is kept; it may be
+ * unsorted and may repeat training pairs.  A new set replaces the old one; n = 0 removes it. */
+int mf_plan_set_heldout(mf_plan *plan, int64_t n, const int32_t *row, const int32_t *col, const double *val);
+/* which = MF_LOSS_TRAIN | MF_LOSS_HELDOUT (no held-out set: MF_ERR_STATE).  row_sse: user_count doubles or NULL. */
+int mf_plan_loss(mf_plan *plan, int which, mf_loss *out, double *row_sse);
+/* step 4 on the host: the same bits as the device total for row sums of `users` consecutive users from user_begin
+ * (plain C++, no HIP call: works without a GPU) */
+int mf_backend_loss_total(const double *row_sse, int32_t user_begin, int32_t users, double *sse);
+
+typedef struct mf_loss_point { int32_t iter; int32_t reserved; mf_loss train, heldout; } mf_loss_point;
+/* Runs up to `iters` iterations.  Evaluates before the first one (iter 0), after every `every`-th and after the last
+ * one run.  Stops after an evaluation at which rmse_prev - rmse <= tol * rmse_prev, rmse being the held-out RMSE
+ * when a set is present and the training RMSE otherwise; with tol > 0 a NaN RMSE also stops; with tol <= 0 nothing
+ * stops the loop.  Without a held-out set a point's heldout is {0.0, 0}.  trace receives at most cap points (NULL/0:
+ * none), *points = points evaluated, *iters_done = iterations run (either may be NULL).  The factors are then those of
+ * mf_plan_iterate(*iters_done) bit for bit. */
+int mf_plan_iterate_monitored(mf_plan *plan, int iters, int every, double tol, mf_loss_point *trace, int cap,
+                              int *points, int *iters_done);
+/* level 1: host buffers in, the training loss of these factors out (factors are not changed) */
+int mf_backend_loss(const mf_problem *p, const double *L, const double *R, mf_loss *out, double *row_sse, int device);
 
 /* Dense predictions of this shard's users, B (user_count x items, row-major) = L R^T exactly as mat2d_prod
  * (mat2d.c:100-113) forms them; for debug dumps of SMALL instances (user_count*items <= 2^26). */

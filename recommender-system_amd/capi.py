@@ -23,6 +23,8 @@ _f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 MF_OK = 0
 MF_ERR_ARGUMENT, MF_ERR_NO_DEVICE, MF_ERR_HIP, MF_ERR_NO_MEMORY, MF_ERR_UNSUPPORTED, MF_ERR_STATE = -1, -2, -3, -4, -5, -6
 MF_TOPN_MAX = 32
+MF_LOSS_BLOCK = 1024
+MF_LOSS_TRAIN, MF_LOSS_HELDOUT = 0, 1
 
 # every symbol include/matfact_hip.h declares (tests check the library exports each one)
 HIP_SYMBOLS = [
@@ -37,6 +39,7 @@ HIP_SYMBOLS = [
     "mf_plan_predict", "mf_plan_synchronize",
     "mf_plan_timing", "mf_plan_timing_read", "mf_plan_describe",
     "mf_backend_recommend_topn", "mf_backend_run_topn", "mf_plan_recommend_topn", "mf_plan_recommend_topn_info",
+    "mf_plan_set_heldout", "mf_plan_loss", "mf_backend_loss_total", "mf_plan_iterate_monitored", "mf_backend_loss",
 ]
 HOST_SYMBOLS = [
     "mf_host_parse_strerror", "mf_host_parse_file", "mf_host_parse_buffer", "mf_host_free_problem",
@@ -78,6 +81,18 @@ class Shard(C.Structure):  # mf_shard
 FILTER_DTYPE = np.dtype([("best", np.float64), ("second", np.float64), ("arg", np.int32), ("nonfinite", np.int32)])
 CANDIDATE_DTYPE = np.dtype([("score", np.float64), ("best", np.int32), ("first", np.int32),
                             ("first_nan", np.int32), ("reserved", np.int32)])
+
+
+class Loss(C.Structure):  # mf_loss
+    _fields_ = [("sse", C.c_double), ("count", C.c_int64)]
+
+    @property
+    def rmse(self):
+        return float(np.sqrt(self.sse / self.count)) if self.count > 0 else float("nan")
+
+
+class LossPoint(C.Structure):  # mf_loss_point
+    _fields_ = [("iter", C.c_int32), ("reserved", C.c_int32), ("train", Loss), ("heldout", Loss)]
 
 
 class Synth(C.Structure):  # mf_synth
@@ -154,6 +169,12 @@ def hip():
         lib.mf_backend_run_topn.argtypes = [C.POINTER(Problem), P, P, C.c_int32, P, P, C.c_int]
         lib.mf_plan_recommend_topn.argtypes = [P, C.c_int32, P, P]
         lib.mf_plan_recommend_topn_info.argtypes = [P, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        lib.mf_plan_set_heldout.argtypes = [P, C.c_int64, P, P, P]
+        lib.mf_plan_loss.argtypes = [P, C.c_int, C.POINTER(Loss), P]
+        lib.mf_backend_loss_total.argtypes = [P, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
+        lib.mf_plan_iterate_monitored.argtypes = [P, C.c_int, C.c_int, C.c_double, C.POINTER(LossPoint), C.c_int,
+                                                  C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.mf_backend_loss.argtypes = [C.POINTER(Problem), P, P, C.POINTER(Loss), P, C.c_int]
         _hip = lib
     return _hip
 
@@ -458,6 +479,27 @@ def write_topn(items):
         return tf.read()
 
 
+def backend_loss(inst, L, R, rows=False, device=0):
+    """mf_backend_loss: the training loss of these factors as a Loss (sse, count, rmse); with rows=True also the row sums."""
+    p, keep = _problem(inst, None)
+    L = np.ascontiguousarray(L, np.float64)
+    R = np.ascontiguousarray(R, np.float64)
+    out = Loss()
+    rs = np.empty(inst.users, np.float64) if rows else None
+    _check(hip().mf_backend_loss(C.byref(p), L.ctypes.data, R.ctypes.data, C.byref(out), rs.ctypes.data if rows else None,
+                                 device), "mf_backend_loss")
+    return (out, rs) if rows else out
+
+
+def loss_total(row_sse, user_begin=0):
+    """mf_backend_loss_total: step 4 of the loss contract over the row sums of consecutive users from user_begin (host only)."""
+    row_sse = np.ascontiguousarray(row_sse, np.float64)
+    sse = C.c_double()
+    _check(hip().mf_backend_loss_total(row_sse.ctypes.data, int(user_begin), int(row_sse.shape[0]), C.byref(sse)),
+           "mf_backend_loss_total")
+    return sse.value
+
+
 # ------------------------------------------------------------------------------------ level 2
 class Plan:
     """mf_plan: one shard resident on one GPU."""
@@ -552,6 +594,33 @@ class Plan:
         _check(hip().mf_plan_recommend_topn_info(self._h, C.byref(n), C.byref(f)), "mf_plan_recommend_topn_info")
         return n.value, f.value
 
+    def set_heldout(self, row, col, val):
+        """mf_plan_set_heldout: the held-out triples (global user ids); empty arrays remove the set."""
+        row = np.ascontiguousarray(row, np.int32)
+        col = np.ascontiguousarray(col, np.int32)
+        val = np.ascontiguousarray(val, np.float64)
+        assert row.shape == col.shape == val.shape and row.ndim == 1
+        _check(hip().mf_plan_set_heldout(self._h, int(row.shape[0]), row.ctypes.data, col.ctypes.data, val.ctypes.data),
+               "mf_plan_set_heldout")
+
+    def loss(self, which="train", rows=False):
+        """mf_plan_loss of the training entries ("train") or the held-out set ("heldout"): a Loss (sse, count, rmse); with
+        rows=True also the user_count row sums."""
+        out = Loss()
+        rs = np.empty(self.user_count, np.float64) if rows else None
+        code = {"train": MF_LOSS_TRAIN, "heldout": MF_LOSS_HELDOUT}.get(which, which)
+        _check(hip().mf_plan_loss(self._h, int(code), C.byref(out), rs.ctypes.data if rows else None), "mf_plan_loss")
+        return (out, rs) if rows else out
+
+    def iterate_monitored(self, iters, every=1, tol=0.0):
+        """mf_plan_iterate_monitored: (iters_done, [LossPoint, ...])."""
+        cap = max(int(iters), 0) // max(int(every), 1) + 2
+        trace = (LossPoint * cap)()
+        npts, done = C.c_int(), C.c_int()
+        _check(hip().mf_plan_iterate_monitored(self._h, int(iters), int(every), float(tol), trace, cap, C.byref(npts),
+                                               C.byref(done)), "mf_plan_iterate_monitored")
+        return done.value, [trace[i] for i in range(min(npts.value, cap))]
+
     def recommend_scored(self):
         """Partial scan state per user (CANDIDATE_DTYPE records); item ids relative to this plan's item block."""
         out = np.zeros(self.user_count, CANDIDATE_DTYPE)
@@ -605,6 +674,6 @@ class Plan:
         return {"item_launches": il.value, "item_ms": ims.value, "user_launches": ul.value, "user_ms": ums.value}
 
     def describe(self):
-        buf = C.create_string_buffer(512)
-        _check(hip().mf_plan_describe(self._h, buf, 512), "mf_plan_describe")
+        buf = C.create_string_buffer(1024)
+        _check(hip().mf_plan_describe(self._h, buf, 1024), "mf_plan_describe")
         return buf.value.decode()

@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <cstdio>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -99,6 +100,7 @@ static int plan_create_impl(mf_plan **out, const mf_shard *s, const mf_entry *ao
 		mf_plan_destroy(p);
 		return code;
 	};
+	if (rc == MF_OK) rc = choose_loss(p);
 	if (rc != MF_OK) return fail(rc);
 
 	if (hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking) != hipSuccess) return fail(MF_ERR_HIP);
@@ -226,6 +228,12 @@ void mf_plan_destroy(mf_plan *p)
 	(void) hipFree(p->topn_part_v);
 	(void) hipFree(p->topn_part_i);
 	(void) hipFree(p->topn_part_bad);
+	(void) hipFree(p->row_sse);
+	(void) hipFree(p->loss_blocks);
+	(void) hipFree(p->loss_total);
+	(void) hipFree(p->ho_ptr);
+	(void) hipFree(p->ho_idx);
+	(void) hipFree(p->ho_val);
 #ifdef MF_REC_TOPNGL
 	(void) hipFree(p->topn_glist_v);
 	(void) hipFree(p->topn_glist_i);
@@ -1026,6 +1034,13 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 			         " iterate=errors+resident-streams(segments=%d x<=%d, %d-column slices of Y in LDS, %d workgroups, lds=%zu/%zu)",
 			         p->es_nseg, p->es_nch, p->res_sw, p->res_nwg, p->es_lds_errors, p->res_lds);
 	}
+	// the row-sum launch of mf_plan_loss: form, chunk sizes (ordinary / few rows) and LDS requests
+	{
+		const size_t at = strlen(buf);
+		if (at + 1 < (size_t) buflen)
+			snprintf(buf + at, (size_t) buflen - at, " loss=%s(nch=%d/%d lds=%zu/%zu)", p->sweep.dma ? "loss_dma_kernel" : "loss_reg_kernel",
+			         p->loss_nch[0], p->loss_nch[1], p->loss_lds[0], p->loss_lds[1]);
+	}
 	// the environment switches this plan was created under, when any differs from its default (mf_config.hip.h)
 	const std::string cfg = p->cfg.describe();
 	const size_t used = strlen(buf);
@@ -1105,6 +1120,188 @@ int mf_backend_recommend_topn(const mf_problem *pr, const double *L, const doubl
 	if (rc != MF_OK) return rc;
 	rc = mf_plan_upload_factors(p, L, R);
 	if (rc == MF_OK) rc = mf_plan_recommend_topn(p, n, items, scores);
+	mf_plan_destroy(p);
+	return rc;
+}
+
+}   // extern "C"
+
+/* ---------------------------------------------------------------------------------------- LOSS (mf_loss.hip.h) */
+
+// Row sums of one entry set (CSR over the plan's users) into p->row_sse, then the block sums and the total, all on the
+// plan's stream.  `order`: optional list of all rows in the order the workgroups take them.
+static int launch_loss(mf_plan *p, const int *ptr, const int *idx, const double *val, const int *order)
+{
+	const int nblocks = p->uc > 0 ? (int) (((long long) p->u0 + p->uc - 1) / mf::kLossBlock - p->u0 / mf::kLossBlock + 1) : 0;
+	if (!p->row_sse) {
+		int rc = dev_alloc(&p->row_sse, (size_t) p->uc);
+		if (rc == MF_OK) rc = dev_alloc(&p->loss_blocks, (size_t) nblocks);
+		if (rc == MF_OK) rc = dev_alloc(&p->loss_total, 1);
+		if (rc != MF_OK) {
+			(void) hipFree(p->row_sse);
+			(void) hipFree(p->loss_blocks);
+			p->row_sse = p->loss_blocks = nullptr;
+			return rc;
+		}
+	}
+	if (p->uc > 0) {
+		mf::LossArgs a;
+		a.nrows = p->uc;
+		a.K = p->K;
+		a.stride = p->stride;
+		a.ldl = p->ldl;
+		a.ldr = p->ldr;
+		a.ptr = ptr;
+		a.idx = idx;
+		a.val = val;
+		a.L = p->Lbuf[p->cur];
+		a.R = p->Rbuf[p->cur];
+		a.row_sse = p->row_sse;
+		a.rowlist = order;
+		const int few = a.nrows < p->cfg.sweep_few ? 1 : 0;
+		a.nch = p->loss_nch[few];
+		void *args[] = {&a};
+		MF_HIP(hipLaunchKernel((const void *) p->loss_fn, dim3(std::min(a.nrows, 1 << 20)), dim3(mf::kWave), args, p->loss_lds[few],
+		                       p->stream));
+		hipLaunchKernelGGL(mf::loss_block_kernel, dim3(nblocks), dim3(mf::kWave), 0, p->stream, p->row_sse, p->u0, p->uc, nblocks,
+		                   p->loss_blocks);
+		MF_HIP(hipGetLastError());
+	}
+	hipLaunchKernelGGL(mf::loss_total_kernel, dim3(1), dim3(mf::kWave), 0, p->stream, p->loss_blocks, nblocks, p->loss_total);
+	MF_HIP(hipGetLastError());
+	return MF_OK;
+}
+
+
+// One evaluation: launches, the total (and the row sums when asked for) back to the host, complete on return.
+static int loss_eval(mf_plan *p, int which, mf_loss *out, double *row_sse)
+{
+	MF_HIP(hipSetDevice(p->device));
+	const bool train = which == MF_LOSS_TRAIN;
+	const int rc = train ? launch_loss(p, p->csr_ptr, p->csr_idx, p->csr_val, p->lpt[1] ? p->short_rows[1] : nullptr)
+	                     : launch_loss(p, p->ho_ptr, p->ho_idx, p->ho_val, nullptr);
+	if (rc != MF_OK) return rc;
+	double sse = 0.0;
+	MF_HIP(hipMemcpyAsync(&sse, p->loss_total, sizeof(double), hipMemcpyDeviceToHost, p->stream));
+	if (row_sse && p->uc > 0)
+		MF_HIP(hipMemcpyAsync(row_sse, p->row_sse, (size_t) p->uc * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+	MF_HIP(hipStreamSynchronize(p->stream));
+	out->sse = sse;
+	out->count = train ? p->nnz : p->ho_nnz;
+	return MF_OK;
+}
+
+static double loss_rmse(const mf_loss &l) { return l.count > 0 ? std::sqrt(l.sse / (double) l.count) : std::nan(""); }
+
+extern "C" {
+
+int mf_backend_loss_total(const double *row_sse, int32_t user_begin, int32_t users, double *sse)
+{
+	if (!sse || user_begin < 0 || users < 0 || (users > 0 && !row_sse)) return MF_ERR_ARGUMENT;
+	double total = 0.0;
+	int64_t i = 0;
+	while (i < users) {   // blocks are cut at global multiples of MF_LOSS_BLOCK
+		const int64_t stop = std::min<int64_t>(users, (((int64_t) user_begin + i) / MF_LOSS_BLOCK + 1) * MF_LOSS_BLOCK - user_begin);
+		double t = 0.0;
+		for (; i < stop; ++i) t = t + row_sse[i];
+		total = total + t;
+	}
+	*sse = total;
+	return MF_OK;
+}
+
+int mf_plan_set_heldout(mf_plan *p, int64_t n, const int32_t *row, const int32_t *col, const double *val)
+{
+	if (!p || n < 0 || n > INT32_MAX - 64 || (n > 0 && (!row || !col || !val))) return MF_ERR_ARGUMENT;
+	for (int64_t i = 0; i < n; ++i)
+		if (row[i] < p->u0 || row[i] >= p->u0 + p->uc || col[i] < 0 || col[i] >= p->items) return MF_ERR_ARGUMENT;
+	MF_HIP(hipSetDevice(p->device));
+	int *nptr = nullptr, *nidx = nullptr;
+	double *nval = nullptr;
+	if (n > 0) {
+		// stable counting sort by user on the host: the caller's order inside a user is the order of the row sum
+		std::vector<int> ptr, idx;
+		std::vector<double> v;
+		try {
+			bucket(n, p->uc, row, p->u0, col, 0, val, ptr, idx, v);
+		} catch (const std::bad_alloc &) {
+			return MF_ERR_NO_MEMORY;
+		}
+		int rc = dev_alloc(&nptr, (size_t) p->uc + 1);
+		if (rc == MF_OK) rc = dev_alloc(&nidx, (size_t) n + 64);
+		if (rc == MF_OK) rc = dev_alloc(&nval, (size_t) n + 64);
+		hipError_t e = hipSuccess;
+		if (rc == MF_OK) e = h2d(p, nptr, ptr.data(), ptr.size() * sizeof(int));
+		if (rc == MF_OK && e == hipSuccess) e = h2d(p, nidx, idx.data(), idx.size() * sizeof(int));
+		if (rc == MF_OK && e == hipSuccess) e = h2d(p, nval, v.data(), v.size() * sizeof(double));
+		if (rc != MF_OK || e != hipSuccess) {
+			(void) hipFree(nptr);
+			(void) hipFree(nidx);
+			(void) hipFree(nval);
+			if (rc != MF_OK) return rc;
+			g_last_hip_error = std::string("mf_plan_set_heldout: ") + hipGetErrorString(e);
+			return e == hipErrorOutOfMemory ? MF_ERR_NO_MEMORY : MF_ERR_HIP;
+		}
+	}
+	MF_HIP(hipStreamSynchronize(p->stream));   // no launch still reads the set that is replaced
+	(void) hipFree(p->ho_ptr);
+	(void) hipFree(p->ho_idx);
+	(void) hipFree(p->ho_val);
+	p->ho_ptr = nptr;
+	p->ho_idx = nidx;
+	p->ho_val = nval;
+	p->ho_nnz = n;
+	p->have_heldout = n > 0;
+	return MF_OK;
+}
+
+int mf_plan_loss(mf_plan *p, int which, mf_loss *out, double *row_sse)
+{
+	if (!p || !out || (which != MF_LOSS_TRAIN && which != MF_LOSS_HELDOUT)) return MF_ERR_ARGUMENT;
+	if (!p->have_factors || (which == MF_LOSS_HELDOUT && !p->have_heldout)) return MF_ERR_STATE;
+	return loss_eval(p, which, out, row_sse);
+}
+
+int mf_plan_iterate_monitored(mf_plan *p, int iters, int every, double tol, mf_loss_point *trace, int cap, int *points,
+                              int *iters_done)
+{
+	if (!p || iters < 0 || every < 1 || cap < 0 || (cap > 0 && !trace)) return MF_ERR_ARGUMENT;
+	if (!p->have_factors) return MF_ERR_STATE;
+	int done = 0, npoints = 0;
+	double prev = 0.0;
+	for (;;) {
+		mf_loss_point pt;
+		memset(&pt, 0, sizeof pt);
+		pt.iter = done;
+		int rc = loss_eval(p, MF_LOSS_TRAIN, &pt.train, nullptr);
+		if (rc == MF_OK && p->have_heldout) rc = loss_eval(p, MF_LOSS_HELDOUT, &pt.heldout, nullptr);
+		if (rc != MF_OK) return rc;
+		if (npoints < cap) trace[npoints] = pt;
+		++npoints;
+		const double rmse = loss_rmse(p->have_heldout ? pt.heldout : pt.train);
+		// the stopping rule (tol > 0 only): a NaN stops; from the second point on, an improvement of at most tol * previous
+		bool stop = done >= iters;
+		if (tol > 0.0 && (std::isnan(rmse) || (npoints > 1 && prev - rmse <= tol * prev))) stop = true;
+		prev = rmse;
+		if (stop) break;
+		const int step = std::min(every, iters - done);
+		rc = mf_plan_iterate(p, step);
+		if (rc != MF_OK) return rc;
+		done += step;
+	}
+	if (points) *points = npoints;
+	if (iters_done) *iters_done = done;
+	return MF_OK;
+}
+
+int mf_backend_loss(const mf_problem *pr, const double *L, const double *R, mf_loss *out, double *row_sse, int device)
+{
+	if (!pr || !L || !R || !out) return MF_ERR_ARGUMENT;
+	mf_plan *p = nullptr;
+	int rc = make_single_plan(pr, device, &p);
+	if (rc != MF_OK) return rc;
+	rc = mf_plan_upload_factors(p, L, R);
+	if (rc == MF_OK) rc = mf_plan_loss(p, MF_LOSS_TRAIN, out, row_sse);
 	mf_plan_destroy(p);
 	return rc;
 }

@@ -6,4 +6,5 @@
 #include "mf_resident.hip.h"
 #include "mf_recommend.hip.h"
 #include "mf_topn.hip.h"
+#include "mf_loss.hip.h"
 #include "mf_collective.hip.h"

@@ -140,6 +140,49 @@ int choose_sweep(mf_plan *p)
 }
 
 
+// Row-sum kernel of mf_plan_loss for this plan's K (the geometry choose_sweep picked) and its chunk sizes.  One tile and
+// no second buffer: the request is the L row plus nch gathered rows.  The chunk rule is the sweeps' (latency hiding
+// against the K steps of phase A per chunk): 16 entries while that stays within a sixth of a CU's LDS, the largest
+// chunk for launches of fewer rows than fill the chip; MF_SWEEP_NCH sets both.
+int choose_loss(mf_plan *p)
+{
+	p->loss_fn = nullptr;
+	if (!p->sweep.dma)
+		p->loss_fn = mf::loss_reg_kernel;
+	else if (p->sweep.kt == 0)
+		p->loss_fn = p->sweep.kpmax == 1 ? mf::loss_dma_kernel<0, 1> : p->sweep.kpmax == 2 ? mf::loss_dma_kernel<0, 2>
+		             : p->sweep.kpmax == 4 ? mf::loss_dma_kernel<0, 4> : mf::loss_dma_kernel<0, 8>;
+	else
+		switch (p->sweep.kt) {
+		case 10: p->loss_fn = mf::loss_dma_kernel<10, mf::DmaGeom<10>::kPasses>; break;
+		case 20: p->loss_fn = mf::loss_dma_kernel<20, mf::DmaGeom<20>::kPasses>; break;
+		case 30: p->loss_fn = mf::loss_dma_kernel<30, mf::DmaGeom<30>::kPasses>; break;
+		case 50: p->loss_fn = mf::loss_dma_kernel<50, mf::DmaGeom<50>::kPasses>; break;
+		case 100: p->loss_fn = mf::loss_dma_kernel<100, mf::DmaGeom<100>::kPasses>; break;
+		case 128: p->loss_fn = mf::loss_dma_kernel<128, mf::DmaGeom<128>::kPasses>; break;
+		case 256: p->loss_fn = mf::loss_dma_kernel<256, mf::DmaGeom<256>::kPasses>; break;
+		default: return MF_ERR_UNSUPPORTED;
+		}
+	const size_t row_bytes = p->sweep.dma ? (size_t) p->sweep.row_bytes : (size_t) p->stride * sizeof(double);
+	const size_t head = p->sweep.dma ? (size_t) p->sweep.xs_bytes : 0;
+	auto fit = [&](size_t budget) {
+		return budget > head ? (int) std::min<size_t>(64, (budget - head) / row_bytes) : 0;
+	};
+	int nch = 16;
+	if (head + (size_t) nch * row_bytes > kLdsPerCu / 6) nch = std::max(12, fit(kLdsPerCu / 6));
+	nch = std::min(nch, fit(kLdsPerCu));
+	if (const int v = p->cfg.sweep_nch; v >= 1 && head + (size_t) v * row_bytes <= kLdsPerCu) nch = v;
+	if (nch < 1) return MF_ERR_UNSUPPORTED;
+	int few = std::max(nch, std::min(64, fit(kLdsPerCu / 2)));
+	if (p->cfg.sweep_nch) few = nch;
+	p->loss_nch[0] = nch;
+	p->loss_nch[1] = few;
+	p->loss_lds[0] = head + (size_t) nch * row_bytes;
+	p->loss_lds[1] = head + (size_t) few * row_bytes;
+	MF_HIP(raise_lds_limit((const void *) p->loss_fn, std::max(p->loss_lds[0], p->loss_lds[1])));
+	return MF_OK;
+}
+
 // defer_join: leave the ordered sums of the extreme rows running on the side stream when the call returns
 // (p->join_pending); the caller joins before anything reads the new generation.
 int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)

@@ -15,6 +15,7 @@ thread_local std::string g_last_hip_error;
 	} while (0)
 
 using SweepFn = void (*)(mf::SweepArgs);
+using LossFn = void (*)(mf::LossArgs);
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is per FUNCTION, not per plan: two live plans that share a kernel
 // instance (the run-time-K forms) but need different tile sizes must never lower each other's limit.
@@ -192,6 +193,17 @@ struct mf_plan {
 	int *topn_glist_i = nullptr;
 	size_t topn_glist_cap = 0;
 #endif
+
+	// loss (mf_plan_loss, mf_loss.hip.h): row sums, block sums and total, allocated on first use; the held-out set as a
+	// second CSR over the shard's users (entries of a user in the caller's order)
+	LossFn loss_fn = nullptr;
+	int loss_nch[2] = {0, 0};        // chunk size of the row-sum launch: [0] ordinary, [1] fewer rows than fill the chip
+	size_t loss_lds[2] = {0, 0};     // its LDS request (the L row + ONE tile)
+	double *row_sse = nullptr, *loss_blocks = nullptr, *loss_total = nullptr;
+	int *ho_ptr = nullptr, *ho_idx = nullptr;
+	double *ho_val = nullptr;
+	int64_t ho_nnz = 0;
+	bool have_heldout = false;
 
 	SweepVariant sweep{};
 	int nch = 0, stride = 0;

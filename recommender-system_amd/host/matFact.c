@@ -11,6 +11,7 @@
 #include "../../include/matfact_hip.h"
 #include "../../include/matfact_host.h"
 
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -135,6 +136,47 @@ static int run_with_checkpoints(const mf_problem *p, double *L, double *R, int32
 	return rc;
 }
 
+/*
+ * MATFACT_LOSS=every[,tol] [MATFACT_HELDOUT=<file.in>]: the single-GPU run through mf_plan_iterate_monitored.  One line per
+ * evaluated point goes to stderr; stdout is the `.out` of the iterations actually run (all of them when tol is absent).
+ */
+static int run_with_loss(const mf_problem *p, const mf_problem *held, const double *L, const double *R, int32_t *best, int device,
+                         int every, double tol)
+{
+	const int64_t nmax = p->nnz > (held ? held->nnz : 0) ? p->nnz : (held ? held->nnz : 0);
+	int32_t *row = malloc(sizeof(int32_t) * (size_t) (nmax ? nmax : 1));
+	int32_t *col = malloc(sizeof(int32_t) * (size_t) (nmax ? nmax : 1));
+	double *val = malloc(sizeof(double) * (size_t) (nmax ? nmax : 1));
+	const int cap = p->iters / every + 2;
+	mf_loss_point *trace = malloc(sizeof(mf_loss_point) * (size_t) cap);
+	if (!row || !col || !val || !trace) return MF_ERR_NO_MEMORY;
+	mf_host_split_entries(p->entries, p->nnz, row, col, val);
+	mf_shard s = {p->users, p->items, p->features, 0, p->users, p->nnz, row, col, val, p->alpha, device, 0, {0, 0}, {0, 0}, 0, 0};
+	mf_plan *plan = NULL;
+	int rc = mf_plan_create(&plan, &s);
+	if (rc == MF_OK) rc = mf_plan_upload_factors(plan, L, R);
+	if (rc == MF_OK && held) {
+		mf_host_split_entries(held->entries, held->nnz, row, col, val);
+		rc = mf_plan_set_heldout(plan, held->nnz, row, col, val);
+	}
+	int points = 0, done = 0;
+	if (rc == MF_OK) rc = mf_plan_iterate_monitored(plan, p->iters, every, tol, trace, cap, &points, &done);
+	for (int i = 0; rc == MF_OK && i < points && i < cap; i++) {
+		fprintf(stderr, "iter %d train_rmse %.17g", trace[i].iter,
+		        trace[i].train.count > 0 ? sqrt(trace[i].train.sse / (double) trace[i].train.count) : NAN);
+		if (held && held->nnz > 0)
+			fprintf(stderr, " heldout_rmse %.17g", sqrt(trace[i].heldout.sse / (double) trace[i].heldout.count));
+		fprintf(stderr, "\n");
+	}
+	if (rc == MF_OK) rc = mf_plan_recommend(plan, best);
+	mf_plan_destroy(plan);
+	free(row);
+	free(col);
+	free(val);
+	free(trace);
+	return rc;
+}
+
 /* util.c:7-10 */
 static void die(const char *error)
 {
@@ -167,6 +209,25 @@ int main(int argc, char **argv)
 			die("MATFACT_TOPN works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT and MATFACT_RESUME.");
 		topn = (int) v;
 	}
+	/* MATFACT_LOSS=every[,tol]: training (and, with MATFACT_HELDOUT=<file.in>, held-out) RMSE every `every` iterations on
+	 * stderr; with tol the run stops by the rule of mf_plan_iterate_monitored.  The single-GPU default path only. */
+	int loss_every = 0;
+	double loss_tol = 0.0;
+	const char *loss_env = getenv("MATFACT_LOSS");
+	if (loss_env) {
+		char *stop;
+		const long v = strtol(loss_env, &stop, 10);
+		if (stop == loss_env || v < 1 || v > 2147483647L || (*stop && *stop != ',')) die("MATFACT_LOSS: expected every[,tol] with every a whole number >= 1.");
+		if (*stop == ',') {
+			char *stop2;
+			loss_tol = strtod(stop + 1, &stop2);
+			if (stop2 == stop + 1 || *stop2) die("MATFACT_LOSS: expected every[,tol] with tol a number.");
+		}
+		if (getenv("MATFACT_DEVICES") || getenv("MATFACT_MATS") || getenv("MATFACT_CHECKPOINT") || getenv("MATFACT_RESUME") || topn)
+			die("MATFACT_LOSS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME and MATFACT_TOPN.");
+		loss_every = (int) v;
+	} else if (getenv("MATFACT_HELDOUT"))
+		die("MATFACT_HELDOUT needs MATFACT_LOSS=every[,tol].");
 	const double t0 = now();
 
 	mf_problem prob;
@@ -175,6 +236,13 @@ int main(int argc, char **argv)
 	int cache_hit = 0;
 	const int prc = mf_host_parse_file_cached(argv[1], getenv("MATFACT_CACHE"), &prob, &cache_hit);
 	if (prc != MF_PARSE_OK) die(mf_host_parse_strerror(prc));
+	mf_problem held;
+	const int have_held = loss_every && getenv("MATFACT_HELDOUT");
+	if (have_held) {
+		const int hrc = mf_host_parse_file(getenv("MATFACT_HELDOUT"), &held);
+		if (hrc != MF_PARSE_OK) die(mf_host_parse_strerror(hrc));
+		if (held.users != prob.users || held.items != prob.items) die(mf_host_parse_strerror(MF_PARSE_THREE_INTS));
+	}
 	const double t1 = now();
 
 	const size_t nl = (size_t) prob.users * (size_t) prob.features;
@@ -201,7 +269,9 @@ int main(int argc, char **argv)
 		if (mf_host_checkpoint_read(getenv("MATFACT_RESUME"), &prob, &start_iter, L, R) != 0)
 			die("MATFACT_RESUME: cannot read the checkpoint or it belongs to another instance.");
 	}
-	if (topn) {
+	if (loss_every) {
+		rc = run_with_loss(&prob, have_held ? &held : NULL, L, R, best, device, loss_every, loss_tol);
+	} else if (topn) {
 		rc = mf_backend_run_topn(&prob, L, R, topn, topn_items, NULL, device);
 	} else if (getenv("MATFACT_CHECKPOINT") || getenv("MATFACT_RESUME")) {
 		rc = run_with_checkpoints(&prob, L, R, best, device, start_iter);
@@ -239,6 +309,7 @@ int main(int argc, char **argv)
 	free(topn_items);
 	free(L);
 	free(R);
+	if (have_held) mf_host_free_problem(&held);
 	mf_host_free_problem(&prob);
 	return 0;
 }
