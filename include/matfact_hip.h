@@ -39,7 +39,9 @@ extern "C" {
                                           additive since: top-N recommendations (MF_TOPN_MAX, mf_plan_recommend_topn,
                                           mf_plan_recommend_topn_info, mf_backend_recommend_topn, mf_backend_run_topn);
                                           loss (mf_plan_loss, mf_plan_set_heldout, mf_plan_iterate_monitored,
-                                          mf_backend_loss, mf_backend_loss_total) */
+                                          mf_backend_loss, mf_backend_loss_total);
+                                          ranks of the held-out entries (mf_plan_rank_heldout, mf_plan_rank_heldout_info,
+                                          mf_backend_rank_metrics) */
 
 /* == non_zero_entry, datatypes.h:10-15: the (user, item, rating) triple, 16 bytes, array-of-structs */
 typedef struct mf_entry {
@@ -298,6 +300,50 @@ int mf_plan_iterate_monitored(mf_plan *plan, int iters, int every, double tol, m
                               int *points, int *iters_done);
 /* level 1: host buffers in, the training loss of these factors out (factors are not changed) */
 int mf_backend_loss(const mf_problem *p, const double *L, const double *R, mf_loss *out, double *row_sse, int device);
+
+/* ---- Ranks of the held-out entries: where each held-out item lands in its user's recommendation order, for the plan's
+ * current factors.  An extension (the reference ranks nothing), so the definition is this library's.  For held-out entry
+ * n = (i, j, a) -- the rating a plays no part --
+ *   C_i      = the items user i has NOT rated in the training entries: exactly the set mf_plan_recommend* choose from
+ *              (block-relative on a 2-D tile, like every other item index: a tile ranks among its own items);
+ *   B[i][.]  = the exact scores (mat2d_prod, mat2d.c:100-113: sequential k from 0.0, multiply and add unfused) --
+ *              mf_plan_predict's bits;
+ *   j not in C_i (the pair is also a training pair)  ->  rank[n] = MF_RANK_MASKED;
+ *   B[i][j] is NaN                                   ->  rank[n] = MF_RANK_NAN;
+ *   otherwise rank[n] = #{ j' in C_i, j' != j : B[i][j'] > B[i][j]  or  (B[i][j'] == B[i][j] and j' < j) },
+ * comparisons as IEEE 754 defines them: a NaN B[i][j'] never counts, +0.0 == -0.0, equal infinities tie.  rank[n] is
+ * 0-based and reported in the order the caller gave the entries to mf_plan_set_heldout.  Other held-out items of the
+ * same user stay candidates; a pair given twice gets the same rank twice.  For a user none of whose candidate scores is
+ * NaN:  rank[n] = r < N  <=>  mf_plan_recommend_topn(N) has items[i][r] == j, for every N <= MF_TOPN_MAX.
+ * Default form: one counting pass over L R^T on the FP64 matrix cores; an entry is certified when no open item's
+ * approximate score lies within the margin of mf_plan_recommend around B[i][j] and none is non-finite, every other entry
+ * is counted again with exact scores, so the result is the definition's in all cases.  Matrix-core forms exist for the K
+ * of mf_plan_recommend_topn; other K, and MF_RECOMMEND_IMPL=exact, count exactly for every entry. */
+#define MF_RANK_MASKED (-1)
+#define MF_RANK_NAN    (-2)
+/* rank: one int32 per held-out entry, the caller's order.  No held-out set or no factors: MF_ERR_STATE; rank == NULL:
+ * MF_ERR_ARGUMENT; both before any HIP call. */
+int mf_plan_rank_heldout(mf_plan *plan, int32_t *rank);
+/* the last mf_plan_rank_heldout: entries that went through the exact pass (-1 when the exact form ran for all) and the
+ * form that ran (0 exact for all, 1 matrix cores at two workgroups per CU, 2 at one per CU; -1 before the first call).
+ * Either pointer may be NULL. */
+int mf_plan_rank_heldout_info(mf_plan *plan, int64_t *exact_pass_entries, int32_t *mfma_form);
+
+typedef struct mf_rank_metrics {
+	int64_t evaluated, masked, nan;   /* rank >= 0, == MF_RANK_MASKED, == MF_RANK_NAN */
+	int64_t users;                    /* users with at least one evaluated entry */
+	int64_t hits;                     /* evaluated entries with rank < cutoff */
+	double hit_rate;                  /* (double) hits / (double) evaluated */
+	double mrr;                       /* (sum over n ascending, from 0.0, of 1.0 / (double) (rank[n] + 1)) / evaluated */
+	double ndcg;                      /* mean over those users, ascending user id, of DCG_i / IDCG_i */
+} mf_rank_metrics;
+/* Hit rate, mean reciprocal rank and NDCG at `cutoff` from a rank vector (plain C++, no HIP call: works without a GPU).
+ * row[n] = the user of entry n (any ids >= 0, any order).  DCG_i = sum, in the caller's order from 0.0, over the user's
+ * evaluated entries with rank < cutoff of 1.0 / log2((double) (rank + 2)); IDCG_i = sum for r = 0 .. min(h_i, cutoff) - 1 of
+ * 1.0 / log2((double) (r + 2)), h_i = the user's evaluated entries.  evaluated == 0: the three doubles are NaN.  cutoff is
+ * not limited by MF_TOPN_MAX.  cutoff < 1, a rank < MF_RANK_NAN or a negative user id: MF_ERR_ARGUMENT.  Ranks of user
+ * shards concatenate: the metrics of the whole are those of the concatenated vectors. */
+int mf_backend_rank_metrics(const int32_t *rank, const int32_t *row, int64_t n, int32_t cutoff, mf_rank_metrics *out);
 
 /* Dense predictions of this shard's users, B (user_count x items, row-major) = L R^T exactly as mat2d_prod
  * (mat2d.c:100-113) forms them; for debug dumps of SMALL instances (user_count*items <= 2^26). */

@@ -25,6 +25,7 @@ MF_ERR_ARGUMENT, MF_ERR_NO_DEVICE, MF_ERR_HIP, MF_ERR_NO_MEMORY, MF_ERR_UNSUPPOR
 MF_TOPN_MAX = 32
 MF_LOSS_BLOCK = 1024
 MF_LOSS_TRAIN, MF_LOSS_HELDOUT = 0, 1
+MF_RANK_MASKED, MF_RANK_NAN = -1, -2
 
 # every symbol include/matfact_hip.h declares (tests check the library exports each one)
 HIP_SYMBOLS = [
@@ -40,6 +41,7 @@ HIP_SYMBOLS = [
     "mf_plan_timing", "mf_plan_timing_read", "mf_plan_describe",
     "mf_backend_recommend_topn", "mf_backend_run_topn", "mf_plan_recommend_topn", "mf_plan_recommend_topn_info",
     "mf_plan_set_heldout", "mf_plan_loss", "mf_backend_loss_total", "mf_plan_iterate_monitored", "mf_backend_loss",
+    "mf_plan_rank_heldout", "mf_plan_rank_heldout_info", "mf_backend_rank_metrics",
 ]
 HOST_SYMBOLS = [
     "mf_host_parse_strerror", "mf_host_parse_file", "mf_host_parse_buffer", "mf_host_free_problem",
@@ -93,6 +95,11 @@ class Loss(C.Structure):  # mf_loss
 
 class LossPoint(C.Structure):  # mf_loss_point
     _fields_ = [("iter", C.c_int32), ("reserved", C.c_int32), ("train", Loss), ("heldout", Loss)]
+
+
+class RankMetrics(C.Structure):  # mf_rank_metrics
+    _fields_ = [("evaluated", C.c_int64), ("masked", C.c_int64), ("nan", C.c_int64), ("users", C.c_int64),
+                ("hits", C.c_int64), ("hit_rate", C.c_double), ("mrr", C.c_double), ("ndcg", C.c_double)]
 
 
 class Synth(C.Structure):  # mf_synth
@@ -175,6 +182,9 @@ def hip():
         lib.mf_plan_iterate_monitored.argtypes = [P, C.c_int, C.c_int, C.c_double, C.POINTER(LossPoint), C.c_int,
                                                   C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.mf_backend_loss.argtypes = [C.POINTER(Problem), P, P, C.POINTER(Loss), P, C.c_int]
+        lib.mf_plan_rank_heldout.argtypes = [P, P]
+        lib.mf_plan_rank_heldout_info.argtypes = [P, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        lib.mf_backend_rank_metrics.argtypes = [P, P, C.c_int64, C.c_int32, C.POINTER(RankMetrics)]
         _hip = lib
     return _hip
 
@@ -500,6 +510,18 @@ def loss_total(row_sse, user_begin=0):
     return sse.value
 
 
+def rank_metrics(rank, row, cutoff):
+    """mf_backend_rank_metrics: hit rate, MRR and NDCG at `cutoff` of a rank vector (Plan.rank_heldout) and the users of its
+    entries, as a RankMetrics (host only)."""
+    rank = np.ascontiguousarray(rank, np.int32)
+    row = np.ascontiguousarray(row, np.int32)
+    assert rank.shape == row.shape and rank.ndim == 1
+    out = RankMetrics()
+    _check(hip().mf_backend_rank_metrics(rank.ctypes.data, row.ctypes.data, int(rank.shape[0]), int(cutoff), C.byref(out)),
+           "mf_backend_rank_metrics")
+    return out
+
+
 # ------------------------------------------------------------------------------------ level 2
 class Plan:
     """mf_plan: one shard resident on one GPU."""
@@ -602,6 +624,21 @@ class Plan:
         assert row.shape == col.shape == val.shape and row.ndim == 1
         _check(hip().mf_plan_set_heldout(self._h, int(row.shape[0]), row.ctypes.data, col.ctypes.data, val.ctypes.data),
                "mf_plan_set_heldout")
+        self._heldout_n = int(row.shape[0])
+
+    def rank_heldout(self):
+        """mf_plan_rank_heldout: the 0-based rank of every held-out entry among its user's unrated items, in the order
+        set_heldout was given them (int32; MF_RANK_MASKED for a training pair, MF_RANK_NAN for a NaN score)."""
+        rank = np.empty(getattr(self, "_heldout_n", 0), np.int32)
+        _check(hip().mf_plan_rank_heldout(self._h, rank.ctypes.data), "mf_plan_rank_heldout")
+        return rank
+
+    def rank_heldout_info(self):
+        """(entries of the last rank_heldout that went through the exact pass, or -1 when the exact form ran for all;
+        form: 0 exact, 1 matrix cores at two workgroups per CU, 2 at one per CU)"""
+        n, f = C.c_int64(), C.c_int32()
+        _check(hip().mf_plan_rank_heldout_info(self._h, C.byref(n), C.byref(f)), "mf_plan_rank_heldout_info")
+        return n.value, f.value
 
     def loss(self, which="train", rows=False):
         """mf_plan_loss of the training entries ("train") or the held-out set ("heldout"): a Loss (sse, count, rmse); with

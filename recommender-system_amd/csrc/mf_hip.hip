@@ -234,6 +234,13 @@ void mf_plan_destroy(mf_plan *p)
 	(void) hipFree(p->ho_ptr);
 	(void) hipFree(p->ho_idx);
 	(void) hipFree(p->ho_val);
+	(void) hipFree(p->ho_user);
+	(void) hipFree(p->rank_score);
+	(void) hipFree(p->rank_state);
+	(void) hipFree(p->rank_out);
+	(void) hipFree(p->rank_above);
+	(void) hipFree(p->rank_band);
+	(void) hipFree(p->rank_list);
 #ifdef MF_REC_TOPNGL
 	(void) hipFree(p->topn_glist_v);
 	(void) hipFree(p->topn_glist_i);
@@ -1191,6 +1198,136 @@ static int loss_eval(mf_plan *p, int which, mf_loss *out, double *row_sse)
 	return MF_OK;
 }
 
+/* ---------------------------------------------------------------------------------------- RANKS (mf_rank.hip.h) */
+
+// Ranks of the held-out entries on the device, in the plan's bucketed order, in p->rank_out (nothing copied back).
+// Thresholds (rank_threshold_kernel), the matrix-core counting pass with launch_topn's shapes, LDS limit, two-per-CU and
+// split rules (rank_mfma_kernel), certification (rank_finish_kernel) and the exact pass (rank_exact_kernel) for the
+// entries it cannot decide; the exact pass for all entries under MF_RECOMMEND_IMPL=exact, when K has no matrix-core form
+// or when R exceeds 32-bit row offsets.
+static int launch_rank(mf_plan *p)
+{
+	MF_HIP(hipSetDevice(p->device));
+	const size_t n = (size_t) p->ho_nnz;
+	if (p->rank_cap < n) {
+		size_t c1 = p->rank_cap, c2 = p->rank_cap, c3 = p->rank_cap, c4 = p->rank_cap, c5 = p->rank_cap;
+		int rc = topn_grow(&p->rank_score, &c1, n);
+		if (rc == MF_OK) rc = topn_grow(&p->rank_state, &c2, n);
+		if (rc == MF_OK) rc = topn_grow(&p->rank_out, &c3, n);
+		if (rc == MF_OK) rc = topn_grow(&p->rank_above, &c4, n);
+		if (rc == MF_OK) rc = topn_grow(&p->rank_band, &c5, n);
+		if (rc == MF_OK) rc = topn_grow(&p->rank_list, &p->rank_cap, n);
+		if (rc != MF_OK) {
+			p->rank_cap = 0;   // the next call allocates all six again
+			return rc;
+		}
+	}
+	mf::RankArgs a;
+	memset(&a, 0, sizeof a);
+	a.rows = (int) n;
+	a.items = p->items;
+	a.K = p->K;
+	a.ldl = p->ldl;
+	a.ldr = p->ldr;
+	a.L = p->Lbuf[p->cur];
+	a.R = p->Rbuf[p->cur];
+	a.csr_ptr = p->csr_ptr;
+	a.csr_idx = p->mask_idx ? p->mask_idx : p->csr_idx;
+	a.ent_user = p->ho_user;
+	a.ent_item = p->ho_idx;
+	a.lnorm = p->lnorm;
+	a.rnorm_max_bits = p->rmax_bits;
+	a.thr_scale = mf_backend_recommend_margin(p->K);
+	a.score = p->rank_score;
+	a.state = p->rank_state;
+	a.rank = p->rank_out;
+	a.above = p->rank_above;
+	a.band = p->rank_band;
+	a.olist = p->rank_list;
+	a.ocount = p->ucount;
+	const unsigned eblocks = (unsigned) ((n + 255) / 256);
+	hipLaunchKernelGGL(mf::rank_threshold_kernel, dim3(eblocks), dim3(256), 0, p->stream, a);
+	MF_HIP(hipGetLastError());
+
+	typedef void (*RankFn)(mf::RankArgs);
+	const int K = p->K;
+	const bool fits32 = (unsigned long long) p->items * (unsigned long long) p->ldr * 8ull < (1ull << 32);   // 32-bit row offsets
+	RankFn fn = nullptr;
+	int qc = 0, waves = 4;
+	if (!p->cfg.rec_exact && fits32) {
+		if (K % 20 == 0 && K <= 100) {
+			static const RankFn f20[5] = {mf::rank_mfma_kernel<1>, mf::rank_mfma_kernel<2>, mf::rank_mfma_kernel<3>,
+			                              mf::rank_mfma_kernel<4>, mf::rank_mfma_kernel<5>};
+			fn = f20[K / 20 - 1];
+			qc = 5;
+		} else if (K % 16 == 0 && K <= 96) {
+			static const RankFn f16[6] = {mf::rank_mfma_kernel<1, 4>, mf::rank_mfma_kernel<2, 4>, mf::rank_mfma_kernel<3, 4>,
+			                              mf::rank_mfma_kernel<4, 4>, mf::rank_mfma_kernel<5, 4>, mf::rank_mfma_kernel<6, 4>};
+			fn = f16[K / 16 - 1];
+			qc = 4;
+		} else if (K == 112) {
+			fn = mf::rank_mfma_kernel<7, 4, 1, 8>;
+			qc = 4;
+			waves = 8;
+		} else if (K == 128) {
+			fn = mf::rank_mfma_kernel<4, 8, 1, 8>;
+			qc = 8;
+			waves = 8;
+		} else if (K == 256) {
+			fn = mf::rank_mfma_kernel<8, 8, 1, 8>;
+			qc = 8;
+			waves = 8;
+		}
+	}
+	if (!fn) {
+		hipLaunchKernelGGL(mf::rank_exact_kernel, dim3((unsigned) n), dim3(64), 0, p->stream, a);
+		MF_HIP(hipGetLastError());
+		p->last_rank_uncertain = -1;
+		p->rank_form = 0;
+		return MF_OK;
+	}
+
+	MF_HIP(hipMemsetAsync(p->rmax_bits, 0, sizeof(unsigned long long), p->stream));
+	MF_HIP(hipMemsetAsync(p->ucount, 0, sizeof(int), p->stream));
+	hipLaunchKernelGGL(mf::row_norm_kernel, dim3((p->uc + 63) / 64), dim3(64), 0, p->stream, a.L, p->uc, p->K, p->ldl, p->lnorm,
+	                   (unsigned long long *) nullptr);
+	hipLaunchKernelGGL(mf::row_norm_kernel, dim3((p->items + 63) / 64), dim3(64), 0, p->stream, a.R, p->items, p->K, p->ldr,
+	                   (double *) nullptr, p->rmax_bits);
+	const size_t lds = mf::rec_mfma2_lds(qc);
+	MF_HIP(raise_lds_limit((const void *) fn, lds));
+	// two four-wave workgroups per CU while the ring + the static arrays (< 4 KB) fit half of the CU's 160 KB
+	const bool two_per_cu = waves == 4 && lds + 4 * 1024 <= 80 * 1024;
+	p->rank_form = two_per_cu ? 1 : 2;
+
+	// item split of small problems: the rule and MF_RECOMMEND_SPLIT of the top-1 pass, over blocks of 64 entries
+	const int rblocks = (int) ((n + mf::kHU - 1) / mf::kHU), tiles = (p->items + mf::kMI - 1) / mf::kMI;
+	const int chip = two_per_cu ? 1024 : 512;
+	int nsplit = 1;
+	if (p->cfg.rec_split != 0 && rblocks < chip * 3 / 8 && tiles >= 2) {
+		nsplit = p->cfg.rec_split > 0 ? p->cfg.rec_split : (chip + rblocks - 1) / rblocks;
+		nsplit = std::max(1, std::min(nsplit, tiles));
+	}
+	if (nsplit > 1) {
+		const int tiles_per = (tiles + nsplit - 1) / nsplit;
+		nsplit = (tiles + tiles_per - 1) / tiles_per;
+		a.split_items = tiles_per * mf::kMI;
+	}
+	hipLaunchKernelGGL(fn, dim3(rblocks, nsplit), dim3(64 * waves), lds, p->stream, a);
+	MF_HIP(hipGetLastError());
+	hipLaunchKernelGGL(mf::rank_finish_kernel, dim3(eblocks), dim3(256), 0, p->stream, a);
+	MF_HIP(hipGetLastError());
+	int cnt = 0;
+	MF_HIP(hipMemcpyAsync(&cnt, p->ucount, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+	MF_HIP(hipStreamSynchronize(p->stream));
+	p->last_rank_uncertain = cnt;
+	if (cnt > 0) {
+		a.elist = p->rank_list;
+		hipLaunchKernelGGL(mf::rank_exact_kernel, dim3(cnt), dim3(64), 0, p->stream, a);
+		MF_HIP(hipGetLastError());
+	}
+	return MF_OK;
+}
+
 static double loss_rmse(const mf_loss &l) { return l.count > 0 ? std::sqrt(l.sse / (double) l.count) : std::nan(""); }
 
 extern "C" {
@@ -1216,28 +1353,34 @@ int mf_plan_set_heldout(mf_plan *p, int64_t n, const int32_t *row, const int32_t
 	for (int64_t i = 0; i < n; ++i)
 		if (row[i] < p->u0 || row[i] >= p->u0 + p->uc || col[i] < 0 || col[i] >= p->items) return MF_ERR_ARGUMENT;
 	MF_HIP(hipSetDevice(p->device));
-	int *nptr = nullptr, *nidx = nullptr;
+	int *nptr = nullptr, *nidx = nullptr, *nuser = nullptr;
 	double *nval = nullptr;
+	std::vector<int> pos;   // bucketed position of the caller's entry n (mf_plan_rank_heldout reports in the caller's order)
 	if (n > 0) {
 		// stable counting sort by user on the host: the caller's order inside a user is the order of the row sum
-		std::vector<int> ptr, idx;
+		std::vector<int> ptr, idx, user;
 		std::vector<double> v;
 		try {
-			bucket(n, p->uc, row, p->u0, col, 0, val, ptr, idx, v);
+			bucket(n, p->uc, row, p->u0, col, 0, val, ptr, idx, v, &pos);
+			user.resize((size_t) n);
+			for (int u = 0; u < p->uc; ++u) std::fill(user.begin() + ptr[(size_t) u], user.begin() + ptr[(size_t) u + 1], u);
 		} catch (const std::bad_alloc &) {
 			return MF_ERR_NO_MEMORY;
 		}
 		int rc = dev_alloc(&nptr, (size_t) p->uc + 1);
 		if (rc == MF_OK) rc = dev_alloc(&nidx, (size_t) n + 64);
 		if (rc == MF_OK) rc = dev_alloc(&nval, (size_t) n + 64);
+		if (rc == MF_OK) rc = dev_alloc(&nuser, (size_t) n);
 		hipError_t e = hipSuccess;
 		if (rc == MF_OK) e = h2d(p, nptr, ptr.data(), ptr.size() * sizeof(int));
 		if (rc == MF_OK && e == hipSuccess) e = h2d(p, nidx, idx.data(), idx.size() * sizeof(int));
 		if (rc == MF_OK && e == hipSuccess) e = h2d(p, nval, v.data(), v.size() * sizeof(double));
+		if (rc == MF_OK && e == hipSuccess) e = h2d(p, nuser, user.data(), user.size() * sizeof(int));
 		if (rc != MF_OK || e != hipSuccess) {
 			(void) hipFree(nptr);
 			(void) hipFree(nidx);
 			(void) hipFree(nval);
+			(void) hipFree(nuser);
 			if (rc != MF_OK) return rc;
 			g_last_hip_error = std::string("mf_plan_set_heldout: ") + hipGetErrorString(e);
 			return e == hipErrorOutOfMemory ? MF_ERR_NO_MEMORY : MF_ERR_HIP;
@@ -1247,9 +1390,12 @@ int mf_plan_set_heldout(mf_plan *p, int64_t n, const int32_t *row, const int32_t
 	(void) hipFree(p->ho_ptr);
 	(void) hipFree(p->ho_idx);
 	(void) hipFree(p->ho_val);
+	(void) hipFree(p->ho_user);
 	p->ho_ptr = nptr;
 	p->ho_idx = nidx;
 	p->ho_val = nval;
+	p->ho_user = nuser;
+	p->ho_pos.swap(pos);
 	p->ho_nnz = n;
 	p->have_heldout = n > 0;
 	return MF_OK;
@@ -1260,6 +1406,83 @@ int mf_plan_loss(mf_plan *p, int which, mf_loss *out, double *row_sse)
 	if (!p || !out || (which != MF_LOSS_TRAIN && which != MF_LOSS_HELDOUT)) return MF_ERR_ARGUMENT;
 	if (!p->have_factors || (which == MF_LOSS_HELDOUT && !p->have_heldout)) return MF_ERR_STATE;
 	return loss_eval(p, which, out, row_sse);
+}
+
+int mf_plan_rank_heldout(mf_plan *p, int32_t *rank)
+{
+	if (!p || !rank) return MF_ERR_ARGUMENT;
+	if (!p->have_factors || !p->have_heldout) return MF_ERR_STATE;
+	const int rc = launch_rank(p);
+	if (rc != MF_OK) return rc;
+	const size_t n = (size_t) p->ho_nnz;
+	std::vector<int> bucketed;
+	try {
+		bucketed.resize(n);
+	} catch (const std::bad_alloc &) {
+		return MF_ERR_NO_MEMORY;
+	}
+	MF_HIP(hipMemcpyAsync(bucketed.data(), p->rank_out, n * sizeof(int), hipMemcpyDeviceToHost, p->stream));
+	MF_HIP(hipStreamSynchronize(p->stream));
+	for (size_t i = 0; i < n; ++i) rank[i] = bucketed[(size_t) p->ho_pos[i]];
+	return MF_OK;
+}
+
+int mf_plan_rank_heldout_info(mf_plan *p, int64_t *exact_pass_entries, int32_t *mfma_form)
+{
+	if (!p) return MF_ERR_ARGUMENT;
+	if (exact_pass_entries) *exact_pass_entries = p->last_rank_uncertain;
+	if (mfma_form) *mfma_form = p->rank_form;
+	return MF_OK;
+}
+
+int mf_backend_rank_metrics(const int32_t *rank, const int32_t *row, int64_t n, int32_t cutoff, mf_rank_metrics *out)
+{
+	if (!out || n < 0 || cutoff < 1 || (n > 0 && (!rank || !row))) return MF_ERR_ARGUMENT;
+	for (int64_t i = 0; i < n; ++i)
+		if (rank[i] < MF_RANK_NAN || row[i] < 0) return MF_ERR_ARGUMENT;
+	mf_rank_metrics m;
+	memset(&m, 0, sizeof m);
+	double rr = 0.0;
+	std::map<int32_t, std::pair<int64_t, double>> per_user;   // user -> (evaluated entries, DCG), ascending user id
+	try {
+		for (int64_t i = 0; i < n; ++i) {
+			const int32_t r = rank[i];
+			if (r == MF_RANK_MASKED) {
+				++m.masked;
+			} else if (r == MF_RANK_NAN) {
+				++m.nan;
+			} else {
+				++m.evaluated;
+				rr = rr + 1.0 / (double) ((int64_t) r + 1);
+				std::pair<int64_t, double> &u = per_user[row[i]];
+				++u.first;
+				if (r < cutoff) {
+					++m.hits;
+					u.second = u.second + 1.0 / std::log2((double) ((int64_t) r + 2));
+				}
+			}
+		}
+	} catch (const std::bad_alloc &) {
+		return MF_ERR_NO_MEMORY;
+	}
+	m.users = (int64_t) per_user.size();
+	if (m.evaluated == 0) {
+		m.hit_rate = m.mrr = m.ndcg = std::nan("");
+	} else {
+		m.hit_rate = (double) m.hits / (double) m.evaluated;
+		m.mrr = rr / (double) m.evaluated;
+		// the ideal DCG depends on min(h, cutoff) only: a running prefix sum serves every user
+		std::vector<double> ideal(1, 0.0);
+		double total = 0.0;
+		for (const auto &kv : per_user) {
+			const int64_t h = std::min<int64_t>(kv.second.first, cutoff);
+			while ((int64_t) ideal.size() <= h) ideal.push_back(ideal.back() + 1.0 / std::log2((double) (ideal.size() + 1)));
+			total = total + kv.second.second / ideal[(size_t) h];
+		}
+		m.ndcg = total / (double) m.users;
+	}
+	*out = m;
+	return MF_OK;
 }
 
 int mf_plan_iterate_monitored(mf_plan *p, int iters, int every, double tol, mf_loss_point *trace, int cap, int *points,

@@ -204,6 +204,15 @@ struct mf_plan {
 	double *ho_val = nullptr;
 	int64_t ho_nnz = 0;
 	bool have_heldout = false;
+	// ranks of the held-out entries (mf_plan_rank_heldout, mf_rank.hip.h): the local user of every bucketed entry, the
+	// bucketed position of every entry the caller gave (host), and the pass's buffers, allocated on first use per set
+	int *ho_user = nullptr;
+	std::vector<int> ho_pos;
+	double *rank_score = nullptr;
+	int *rank_state = nullptr, *rank_out = nullptr, *rank_above = nullptr, *rank_band = nullptr, *rank_list = nullptr;
+	size_t rank_cap = 0;                // entries of each of the six
+	int64_t last_rank_uncertain = -1;   // entries of the last rank call that went through the exact pass (-1: exact form ran)
+	int rank_form = -1;                 // form of the last rank call (mf_plan_rank_heldout_info)
 
 	SweepVariant sweep{};
 	int nch = 0, stride = 0;

@@ -141,7 +141,7 @@ static int run_with_checkpoints(const mf_problem *p, double *L, double *R, int32
  * evaluated point goes to stderr; stdout is the `.out` of the iterations actually run (all of them when tol is absent).
  */
 static int run_with_loss(const mf_problem *p, const mf_problem *held, const double *L, const double *R, int32_t *best, int device,
-                         int every, double tol)
+                         int every, double tol, int rank_cutoff)
 {
 	const int64_t nmax = p->nnz > (held ? held->nnz : 0) ? p->nnz : (held ? held->nnz : 0);
 	int32_t *row = malloc(sizeof(int32_t) * (size_t) (nmax ? nmax : 1));
@@ -167,6 +167,19 @@ static int run_with_loss(const mf_problem *p, const mf_problem *held, const doub
 		if (held && held->nnz > 0)
 			fprintf(stderr, " heldout_rmse %.17g", sqrt(trace[i].heldout.sse / (double) trace[i].heldout.count));
 		fprintf(stderr, "\n");
+	}
+	if (rc == MF_OK && rank_cutoff && held && held->nnz > 0) {
+		/* row still holds the users of the held-out entries in the caller's order; col is free to take the ranks */
+		rc = mf_plan_rank_heldout(plan, col);
+		mf_rank_metrics m;
+		if (rc == MF_OK) rc = mf_backend_rank_metrics(col, row, held->nnz, rank_cutoff, &m);
+		if (rc == MF_OK)
+			fprintf(stderr, "heldout_rank cutoff %d evaluated %lld masked %lld nan %lld users %lld hits %lld hit_rate %.17g mrr %.17g ndcg %.17g\n",
+			        rank_cutoff, (long long) m.evaluated, (long long) m.masked, (long long) m.nan, (long long) m.users,
+			        (long long) m.hits, m.hit_rate, m.mrr, m.ndcg);
+	} else if (rc == MF_OK && rank_cutoff) {
+		fprintf(stderr, "heldout_rank cutoff %d evaluated 0 masked 0 nan 0 users 0 hits 0 hit_rate %.17g mrr %.17g ndcg %.17g\n", rank_cutoff,
+		        NAN, NAN, NAN);
 	}
 	if (rc == MF_OK) rc = mf_plan_recommend(plan, best);
 	mf_plan_destroy(plan);
@@ -228,6 +241,17 @@ int main(int argc, char **argv)
 		loss_every = (int) v;
 	} else if (getenv("MATFACT_HELDOUT"))
 		die("MATFACT_HELDOUT needs MATFACT_LOSS=every[,tol].");
+	/* MATFACT_RANK=N (N >= 1) with MATFACT_LOSS and MATFACT_HELDOUT: after the monitored loop one more stderr line with the
+	 * hit rate, MRR and NDCG at N of the held-out entries' ranks (mf_plan_rank_heldout, mf_backend_rank_metrics) */
+	int rank_cutoff = 0;
+	const char *rank_env = getenv("MATFACT_RANK");
+	if (rank_env) {
+		char *stop;
+		const long v = strtol(rank_env, &stop, 10);
+		if (stop == rank_env || *stop || v < 1 || v > 2147483647L) die("MATFACT_RANK: expected a whole number >= 1.");
+		if (!loss_every || !getenv("MATFACT_HELDOUT")) die("MATFACT_RANK needs MATFACT_HELDOUT=<file.in>.");
+		rank_cutoff = (int) v;
+	}
 	const double t0 = now();
 
 	mf_problem prob;
@@ -270,7 +294,7 @@ int main(int argc, char **argv)
 			die("MATFACT_RESUME: cannot read the checkpoint or it belongs to another instance.");
 	}
 	if (loss_every) {
-		rc = run_with_loss(&prob, have_held ? &held : NULL, L, R, best, device, loss_every, loss_tol);
+		rc = run_with_loss(&prob, have_held ? &held : NULL, L, R, best, device, loss_every, loss_tol, rank_cutoff);
 	} else if (topn) {
 		rc = mf_backend_run_topn(&prob, L, R, topn, topn_items, NULL, device);
 	} else if (getenv("MATFACT_CHECKPOINT") || getenv("MATFACT_RESUME")) {
