@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 			nextcol = cur < cend ? a.csr_idx[cur] : INT32_MAX;
 			nextcol2 = cur + 1 < cend ? a.csr_idx[cur + 1] : INT32_MAX;
 			const double ln = a.lnorm[u];
-			const double thr = a.thr_scale * ln * __longlong_as_double((long long) *a.rnorm_max_bits) + 1e-300;
+			const double thr = a.thr_scale * (ln * __longlong_as_double((long long) *a.rnorm_max_bits)) + 1e-300;
 			const double t = a.score[e];
 			lo = t - thr;
 			hi = t + thr;

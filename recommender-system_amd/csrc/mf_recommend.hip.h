@@ -237,13 +237,31 @@ __global__ void __launch_bounds__(kWave) row_norm_kernel(const double *__restric
                                                           unsigned long long *__restrict__ max_bits)
 {
 	const int r = blockIdx.x * kWave + threadIdx.x;
-	double s = 0.0;
+	double s = 0.0, m = 0.0;
 	if (r < rows)
 		for (int k = 0; k < K; ++k) {
 			const double v = X[(size_t) r * ld + k];
 			s += v * v;
+			m = fmax(m, fabs(v));   // a NaN entry is skipped here and still makes s NaN
 		}
 	s = sqrt(s);
+	// The certification needs norm >= the true norm (an overestimate only sends more users to the exact pass).  The plain
+	// sum is within (K + 2) * 2^-53 of the truth while the largest square is far above the subnormals: the squares that
+	// underflow lose at most K * 2^-1075 in all, against a sum >= 2^-960.  A row whose largest entry is below 2^-480 is
+	// summed again scaled by that entry's exponent (exact powers of two), and the result is scaled back rounding UP, so
+	// a norm in the subnormal range is not rounded below the truth either.  Overflow needs nothing: an infinite norm
+	// certifies nobody.
+	if (r < rows && m > 0.0 && m < 0x1p-480) {
+		const int e = ilogb(m);
+		double t = 0.0;
+		for (int k = 0; k < K; ++k) {
+			const double v = ldexp(X[(size_t) r * ld + k], -e);
+			t += v * v;
+		}
+		t = sqrt(t);
+		s = ldexp(t, e);
+		if (ldexp(s, -e) < t) s = __longlong_as_double(__double_as_longlong(s) + 1);
+	}
 	if (r < rows && norm) norm[r] = s;
 	if (max_bits) {
 		// NaN compares as a huge unsigned pattern: it poisons the maximum, which sends every user to pass 2
@@ -660,7 +678,7 @@ __global__ void __launch_bounds__(kMThreads) recommend_mfma_kernel(RecMfmaArgs a
 			return;
 		}
 		const double rmax = __longlong_as_double((long long) *a.rnorm_max_bits);
-		const double thr = a.thr_scale * a.lnorm[i0 + tid] * rmax + 1e-300;
+		const double thr = a.thr_scale * (a.lnorm[i0 + tid] * rmax) + 1e-300;
 		const bool certain = !bd && (t.i1 < 0 || (t.b1 - t.b2) > thr);
 		if (certain) {
 			a.best[i0 + tid] = t.i1;
@@ -1001,7 +1019,7 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 			return;
 		}
 		const double rmax = __longlong_as_double((long long) *a.rnorm_max_bits);
-		const double thr = a.thr_scale * a.lnorm[i0 + tid] * rmax + 1e-300;
+		const double thr = a.thr_scale * (a.lnorm[i0 + tid] * rmax) + 1e-300;
 		const bool certain = !bd && (t.i1 < 0 || (t.b1 - t.b2) > thr);
 		if (certain) {
 			a.best[i0 + tid] = t.i1;
@@ -1031,7 +1049,7 @@ __global__ void __launch_bounds__(256) merge_splits_kernel(RecMfmaArgs a, int ns
 		return;
 	}
 	const double rmax = __longlong_as_double((long long) *a.rnorm_max_bits);
-	const double thr = a.thr_scale * a.lnorm[i] * rmax + 1e-300;
+	const double thr = a.thr_scale * (a.lnorm[i] * rmax) + 1e-300;
 	const bool certain = !bd && (t.i1 < 0 || (t.b1 - t.b2) > thr);
 	if (certain) {
 		a.best[i] = t.i1;

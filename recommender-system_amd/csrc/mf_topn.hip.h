@@ -81,7 +81,7 @@ __device__ bool topn_finish(const TopnArgs &a, int u, double *v, int *it, int ba
 	int valid = 0;
 	for (int r = 0; r <= N; ++r) valid += it[r] >= 0;
 	const double ln = a.lnorm[u];
-	const double thr = a.thr_scale * ln * rmax + 1e-300;
+	const double thr = a.thr_scale * (ln * rmax) + 1e-300;
 	if (bad || !(ln * rmax <= 1e300) || (valid > N && !((v[N - 1] - v[N]) > thr))) return false;
 	const int n = min(valid, N);
 	const double *l = a.L + (size_t) u * a.ldl;

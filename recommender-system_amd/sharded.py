@@ -180,7 +180,7 @@ def certify_filters(filters, norm, rmax, margin):
     runner = np.maximum(np.stack([f["second"] for f in filters])[w, cols], others.max(axis=0))
     arg = np.stack([f["arg"] for f in filters])[w, cols]
     bad = np.stack([f["nonfinite"] for f in filters]).any(axis=0)
-    thr = margin * norm * rmax + 1e-300
+    thr = margin * (norm * rmax) + 1e-300
     with np.errstate(invalid="ignore"):
         gap_ok = (b1 - runner) > thr                        # False for NaN thresholds and for -inf - -inf
     none = np.stack([f["arg"] for f in filters]).max(axis=0) < 0
