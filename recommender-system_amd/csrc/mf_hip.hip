@@ -1032,6 +1032,10 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 	else
 		n = snprintf(buf, (size_t) buflen, "sweep_kernel<KT=%d,KPMAX=%d> K=%d nch=%d stride=%d lds=%zu",
 		             p->sweep.kt, p->sweep.kpmax, p->K, p->nch, p->stride, p->lds_bytes);
+	// accumulate form of the single-wave launch of the item / user sweep (the rule of launch_sweep, mf_launch.hip.h)
+	if (n > 0 && n < buflen)
+		n += snprintf(buf + n, (size_t) (buflen - n), " accumulate=%s/%s", single_wave_pipelined(p, 0) ? "pf" : "plain",
+		              single_wave_pipelined(p, 1) ? "pf" : "plain");
 	// how mf_plan_iterate runs an iteration: the two sweeps above, or errors + streams (mf_stream.hip.h)
 	if (n > 0 && n < buflen) {
 		if (!p->es_mode)

@@ -183,6 +183,21 @@ int choose_loss(mf_plan *p)
 	return MF_OK;
 }
 
+// Accumulate form of the single-wave launch of one side (kind 0: items, 1: users): true for the form with the pipelined
+// phases (sweep.pf), false for the plain one (sweep.fn).  Up to kPfRows rows: the form whose phases keep their LDS reads
+// in flight and whose gather issue is lean -- what a wave walking a long row alone is bound by (cfg3 uniform 0.224 ->
+// 0.201 ms, power-law 0.367 -> 0.350, a lone 5993-entry row 1.02 -> 0.78 ms).  Larger launches of one-pass rows
+// (K <= 128) are never bound by one wave and keep round 2's form (cfg4 user sweep, 1e6 rows: 11.45 vs 11.60 ms).
+// Two-pass rows (K = 256) take it at every size: their phase A is a 256-deep chain per chunk that the six resident
+// workgroups of a CU do not hide, and keeping its LDS reads in flight shortens it (cfg5: 346.6 -> 327.9 ms, 0.745 ->
+// 0.787).  launch_sweep chooses by it and mf_plan_describe prints it (accumulate=<items>/<users>).
+bool single_wave_pipelined(const mf_plan *p, int kind)
+{
+	const int nrows = kind == 0 ? p->items : p->uc;
+	const int kPfRows = p->cfg.pf_rows > 0 ? p->cfg.pf_rows : (p->K > 128 ? INT_MAX : 262144);
+	return p->sweep.pf && p->n_short[kind] <= kPfRows && nrows <= kPfRows;
+}
+
 // defer_join: leave the ordered sums of the extreme rows running on the side stream when the call returns
 // (p->join_pending); the caller joins before anything reads the new generation.
 int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
@@ -232,14 +247,7 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	if (db) a.nch = p->nch_db;
 	if (pair) a.nch = trio ? p->nch_trio : p->nch_pair;
 	const size_t lds = coop ? p->lds_bytes_coop : db ? p->lds_bytes_db : trio ? p->lds_bytes_trio : pair ? p->lds_bytes_pair : (few_rows ? p->lds_bytes_few : p->lds_bytes);
-	// Accumulate form of the single-wave launch.  Up to kPfRows rows: the form whose phases keep their LDS reads in flight
-	// and whose gather issue is lean -- what a wave walking a long row alone is bound by (cfg3 uniform 0.224 -> 0.201 ms,
-	// power-law 0.367 -> 0.350, a lone 5993-entry row 1.02 -> 0.78 ms).  Larger launches of one-pass rows (K <= 128) are
-	// never bound by one wave and keep round 2's form (cfg4 user sweep, 1e6 rows: 11.45 vs 11.60 ms).  Two-pass rows
-	// (K = 256) take it at every size: their phase A is a 256-deep chain per chunk that the six resident workgroups of a
-	// CU do not hide, and keeping its LDS reads in flight shortens it (cfg5: 346.6 -> 327.9 ms, 0.745 -> 0.787).
-	const int kPfRows = p->cfg.pf_rows > 0 ? p->cfg.pf_rows : (p->K > 128 ? INT_MAX : 262144);
-	const SweepFn single = p->sweep.pf && p->n_short[kind] <= kPfRows && a.nrows <= kPfRows ? p->sweep.pf : p->sweep.fn;
+	const SweepFn single = single_wave_pipelined(p, kind) ? p->sweep.pf : p->sweep.fn;   // accumulate form of the single-wave launch
 	const SweepFn fn = coop ? p->sweep.coop : db ? p->sweep.db : trio ? p->sweep.trio : pair ? p->sweep.pair : single;
 	const int block = coop ? mf::kCoopWaves * mf::kWave : trio ? 3 * mf::kWave : pair ? p->pair_waves * mf::kWave : mf::kWave;
 	const int grid = std::min(a.nrows, 1 << 20);

@@ -9,6 +9,9 @@ by oracle/Makefile).  Run in the build container only -- the reference does not 
                      plus the reference binary's stdout for cross-checking the .out copy.
   <name>.in.gz       (LARGE_INPUTS) the reference's larger sample inputs, gzipped, no factors
   reference_random.npz  seeded random instances and the reference's L, R, B on them (RANDOM_CASES)
+  reference_special.npz signed ratings, three diverging step sizes and one that converges: the reference's L, R, B
+                        after 1, 2, 3, 5, 6, 7 and 8 iterations (inf and NaN included)
+  instDiverge.in/.out   one of the diverging instances as an input file, and the reference binary's stdout on it
 
 Fixtures are data only (inputs and expected outputs); no reference source text is stored.
 """
@@ -65,6 +68,7 @@ def main():
         shutil.copyfile(os.path.join(SAMPLES, name + ".mats"), os.path.join(HERE, name + ".mats"))
     large_inputs()
     reference_random()
+    reference_special()
 
 
 # the reference's larger samples, inputs only (the GPU tests compare the backend with the oracle on them); gzip keeps
@@ -98,7 +102,52 @@ def reference_random():
     np.savez_compressed(os.path.join(HERE, "reference_random.npz"), **arrays)
 
 
+# instances with ratings in [-5, 5] (multiples of 0.5): three step sizes at which the run diverges to inf and then NaN
+# within a few iterations, and one at which it does not (tests/test_sweep_edges.py)
+SPECIAL_SHAPE = (40, 30, 6)
+SPECIAL_ALPHAS = [0.5, 0.05, 3.0, 0.002]
+SPECIAL_ITERS = [1, 2, 3, 5, 6, 7, 8]   # 6 and 7: where inf and NaN first appear at alpha 0.5 and 3.0
+DIVERGE = 0   # the instance written out as instDiverge.in / .out (its header asks for SPECIAL_ITERS[-1] iterations)
+
+
+def special_instance(n):
+    """Instance n of reference_special.npz (shared with tests/test_sweep_edges.py, which rebuilds it from the seed)."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from conftest import random_instance  # noqa: E402
+    u, i, k = SPECIAL_SHAPE
+    d = random_instance(700 + n, u, i, k, density=0.3, iters=SPECIAL_ITERS[-1], alpha=SPECIAL_ALPHAS[n], empty_rows=(1,),
+                        full_rows=(2,))
+    d["val"] = np.random.default_rng(800 + n).integers(-10, 11, len(d["row"])) / 2.0
+    return d
+
+
+def reference_special():
+    """reference_special.npz: per instance (row, col, val) and the reference's own L, R, B after 1, 2, 3, 5, 6, 7 and 8
+    iterations (NaN as the reference's machine wrote it); instDiverge.in / .out: one diverging instance as a file and the reference
+    binary's stdout on it."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from conftest import to_text  # noqa: E402
+    O.build(ref=True)
+    assert O.ref_available(), "oracle/_ref is missing"
+    arrays = {}
+    with np.errstate(all="ignore"):
+        for n in range(len(SPECIAL_ALPHAS)):
+            d = special_instance(n)
+            arrays.update({"row_%d" % n: d["row"], "col_%d" % n: d["col"], "val_%d" % n: d["val"]})
+            for it in SPECIAL_ITERS:
+                L, R, B = O.ref_run(O.Instance(**d), iters=it)
+                arrays.update({"L_%d_%d" % (n, it): L, "R_%d_%d" % (n, it): R, "B_%d_%d" % (n, it): B})
+            print("special", n, "alpha", d["alpha"], "NaN in L after", SPECIAL_ITERS[-1], "iterations:", int(np.isnan(L).sum()), flush=True)
+    np.savez_compressed(os.path.join(HERE, "reference_special.npz"), **arrays)
+    path = os.path.join(HERE, "instDiverge.in")
+    with open(path, "w") as f:
+        f.write(to_text(special_instance(DIVERGE)))
+    with open(os.path.join(HERE, "instDiverge.out"), "w") as f:
+        f.write(O.ref_cli(path, "serial"))
+
+
 if __name__ == "__main__":
-    # no argument: every fixture; otherwise only the parts named (main, large_inputs, reference_random)
+    # no argument: every fixture; otherwise only the parts named (main, large_inputs, reference_random, reference_special)
     for part in sys.argv[1:] or ["main"]:
-        {"main": main, "large_inputs": large_inputs, "reference_random": reference_random}[part]()
+        {"main": main, "large_inputs": large_inputs, "reference_random": reference_random,
+         "reference_special": reference_special}[part]()
