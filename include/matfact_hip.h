@@ -41,7 +41,9 @@ extern "C" {
                                           loss (mf_plan_loss, mf_plan_set_heldout, mf_plan_iterate_monitored,
                                           mf_backend_loss, mf_backend_loss_total);
                                           ranks of the held-out entries (mf_plan_rank_heldout, mf_plan_rank_heldout_info,
-                                          mf_backend_rank_metrics) */
+                                          mf_backend_rank_metrics);
+                                          similar items (mf_plan_similar_items, mf_plan_similar_items_info,
+                                          mf_backend_similar_items) */
 
 /* == non_zero_entry, datatypes.h:10-15: the (user, item, rating) triple, 16 bytes, array-of-structs */
 typedef struct mf_entry {
@@ -222,6 +224,40 @@ int mf_plan_recommend_topn(mf_plan *plan, int32_t n, int32_t *items, double *sco
  * the form that ran (0 exact for all users, 1 matrix cores at two workgroups per CU, 2 matrix cores at one per CU;
  * -1 before the first call; 0 and 0 after a call on a plan without users).  Either pointer may be NULL. */
 int mf_plan_recommend_topn_info(mf_plan *plan, int64_t *exact_pass_users, int32_t *mfma_form);
+
+/* ---- Similar items: the top-N neighbours of an item's row of R among the OTHER items, by dot product or by cosine ("people
+ * who liked X also liked ...").  An extension (the reference has no such query), so the definition is this library's; it
+ * fixes the order of every floating-point operation.  The operand matrix Q (items x K) comes from the plan's current R:
+ *   MF_SIMILAR_DOT     Q = R;
+ *   MF_SIMILAR_COSINE  s_j = ((0.0 + R[j][0]*R[j][0]) + R[j][1]*R[j][1]) + ..., k ascending, multiply and add unfused;
+ *                      n_j = sqrt(s_j), correctly rounded; Q[j][k] = R[j][k] / n_j, correctly rounded IEEE division.  Nothing
+ *                      is special-cased: a zero row gives 0/0 = NaN, an infinite norm 0 or NaN, a sum that underflows to 0
+ *                      +-inf; the rule below says what happens to NaN scores.
+ * Scores S[j][j'] = dot(Q[j], Q[j']), sequential k from 0.0, unfused: mf_plan_predict's bits for L = R = Q.  The candidates
+ * of item j are C_j = { j' in [0, items) : j' != j }.  Row t of the result belongs to query[t] and is the rule of
+ * mf_backend_recommend_topn applied to S[query[t]][.] over C_query[t]: print_output's rule n times, each pick removed --
+ * empty set -> -1; first = its lowest index; S[.][first] NaN -> first; otherwise the arg-max over the non-NaN scores, the
+ * lowest index on ties -- and scores[t][r] = S[query[t]][items[t][r]] bit for bit, NaN where the item is -1.
+ * query == NULL: all items in ascending order, nq must equal the plan's item count; otherwise nq item ids in any order,
+ * repeats allowed, each with a row of its own.  items and scores are nq x n, row-major; 1 <= n <= MF_TOPN_MAX; scores may
+ * be NULL.  Before any HIP call: NULL items, n < 1, an unknown metric, nq < 0, a query id out of range or query == NULL
+ * with nq != items -> MF_ERR_ARGUMENT; n > MF_TOPN_MAX -> MF_ERR_UNSUPPORTED; no factors uploaded -> MF_ERR_STATE.  nq == 0:
+ * MF_OK and nothing is written.  On a 2-D tile the query works among the tile's own items, like every other item index; a
+ * user shard holds the whole of R, so any shard answers.
+ * Default form: mf_plan_recommend_topn's passes on other operands -- the rows of Q (or the gathered query rows) against
+ * Q under a mask of one item per row, the query itself; the margin is mf_backend_recommend_margin(K) * ||Q_j|| * max ||Q||.
+ * Q is formed again on every call. */
+#define MF_SIMILAR_DOT    0
+#define MF_SIMILAR_COSINE 1
+int mf_plan_similar_items(mf_plan *plan, int metric, const int32_t *query, int32_t nq, int32_t n, int32_t *items,
+                          double *scores);
+/* the last mf_plan_similar_items: queries that went through the exact pass (-1 when the exact form ran for all) and the
+ * form that ran (0 exact for all, 1 matrix cores at two workgroups per CU, 2 at one per CU; -1 before the first call; 0 and
+ * 0 after a call with nq == 0).  Independent of mf_plan_recommend_topn_info.  Either pointer may be NULL. */
+int mf_plan_similar_items_info(mf_plan *plan, int64_t *exact_pass_queries, int32_t *mfma_form);
+/* level 1: host R (items x features, row-major) in, the rows out, on a throw-away plan without entries */
+int mf_backend_similar_items(const double *R, int32_t items, int32_t features, int metric, const int32_t *query, int32_t nq,
+                             int32_t n, int32_t *out_items, double *out_scores, int device);
 
 /* Partial result of the sequential scan of print_output (matFact.c:13-23) over this plan's items, in a form
  * that can be combined over the item blocks of a grid row (what MPI_Reduce(max_cmp) does at matFact-mpi.c:98):

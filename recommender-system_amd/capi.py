@@ -26,6 +26,8 @@ MF_TOPN_MAX = 32
 MF_LOSS_BLOCK = 1024
 MF_LOSS_TRAIN, MF_LOSS_HELDOUT = 0, 1
 MF_RANK_MASKED, MF_RANK_NAN = -1, -2
+MF_SIMILAR_DOT, MF_SIMILAR_COSINE = 0, 1
+SIMILAR_METRICS = {"dot": MF_SIMILAR_DOT, "cosine": MF_SIMILAR_COSINE}
 
 # every symbol include/matfact_hip.h declares (tests check the library exports each one)
 HIP_SYMBOLS = [
@@ -42,6 +44,7 @@ HIP_SYMBOLS = [
     "mf_backend_recommend_topn", "mf_backend_run_topn", "mf_plan_recommend_topn", "mf_plan_recommend_topn_info",
     "mf_plan_set_heldout", "mf_plan_loss", "mf_backend_loss_total", "mf_plan_iterate_monitored", "mf_backend_loss",
     "mf_plan_rank_heldout", "mf_plan_rank_heldout_info", "mf_backend_rank_metrics",
+    "mf_plan_similar_items", "mf_plan_similar_items_info", "mf_backend_similar_items",
 ]
 HOST_SYMBOLS = [
     "mf_host_parse_strerror", "mf_host_parse_file", "mf_host_parse_buffer", "mf_host_free_problem",
@@ -185,6 +188,9 @@ def hip():
         lib.mf_plan_rank_heldout.argtypes = [P, P]
         lib.mf_plan_rank_heldout_info.argtypes = [P, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         lib.mf_backend_rank_metrics.argtypes = [P, P, C.c_int64, C.c_int32, C.POINTER(RankMetrics)]
+        lib.mf_plan_similar_items.argtypes = [P, C.c_int, P, C.c_int32, C.c_int32, P, P]
+        lib.mf_plan_similar_items_info.argtypes = [P, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        lib.mf_backend_similar_items.argtypes = [P, C.c_int32, C.c_int32, C.c_int, P, C.c_int32, C.c_int32, P, P, C.c_int]
         _hip = lib
     return _hip
 
@@ -522,6 +528,29 @@ def rank_metrics(rank, row, cutoff):
     return out
 
 
+def _similar_query(query, items):
+    """(contiguous int32 query or None, its pointer, nq) of a similar-items call"""
+    if query is None:
+        return None, None, int(items)
+    query = np.ascontiguousarray(query, np.int32)
+    assert query.ndim == 1
+    return query, query.ctypes.data, int(query.shape[0])
+
+
+def backend_similar_items(R, n, metric="cosine", query=None, device=0):
+    """mf_backend_similar_items: (items, scores), one row of n per query item (all items in ascending order with
+    query=None); item -1 / score NaN past the other items.  metric: "cosine", "dot" or one of the MF_SIMILAR_* codes."""
+    R = np.ascontiguousarray(R, np.float64)
+    assert R.ndim == 2
+    query, qptr, nq = _similar_query(query, R.shape[0])
+    items = np.empty((nq, max(int(n), 0)), np.int32)
+    scores = np.empty((nq, max(int(n), 0)), np.float64)
+    _check(hip().mf_backend_similar_items(R.ctypes.data, R.shape[0], R.shape[1], int(SIMILAR_METRICS.get(metric, metric)), qptr,
+                                          nq, int(n), items.ctypes.data, scores.ctypes.data, device),
+           "mf_backend_similar_items")
+    return items, scores
+
+
 # ------------------------------------------------------------------------------------ level 2
 class Plan:
     """mf_plan: one shard resident on one GPU."""
@@ -614,6 +643,24 @@ class Plan:
         form: 0 exact, 1 matrix cores at two workgroups per CU, 2 at one per CU)"""
         n, f = C.c_int64(), C.c_int32()
         _check(hip().mf_plan_recommend_topn_info(self._h, C.byref(n), C.byref(f)), "mf_plan_recommend_topn_info")
+        return n.value, f.value
+
+    def similar_items(self, n, metric="cosine", query=None, scores=True):
+        """mf_plan_similar_items: the n nearest other items of every query item (all items in ascending order with
+        query=None) by "cosine" or "dot" of the rows of the current R: (items, scores) of shape (nq, n), or items alone
+        with scores=False."""
+        query, qptr, nq = _similar_query(query, self.items)
+        items = np.empty((nq, max(int(n), 0)), np.int32)
+        sc = np.empty((nq, max(int(n), 0)), np.float64) if scores else None
+        _check(hip().mf_plan_similar_items(self._h, int(SIMILAR_METRICS.get(metric, metric)), qptr, nq, int(n),
+                                           items.ctypes.data, sc.ctypes.data if scores else None), "mf_plan_similar_items")
+        return (items, sc) if scores else items
+
+    def similar_items_info(self):
+        """(queries of the last similar_items that went through the exact pass, or -1 when the exact form ran for all;
+        form: 0 exact, 1 matrix cores at two workgroups per CU, 2 at one per CU)"""
+        n, f = C.c_int64(), C.c_int32()
+        _check(hip().mf_plan_similar_items_info(self._h, C.byref(n), C.byref(f)), "mf_plan_similar_items_info")
         return n.value, f.value
 
     def set_heldout(self, row, col, val):

@@ -223,11 +223,24 @@ void mf_plan_destroy(mf_plan *p)
 	(void) hipFree(p->cand_pack);
 	(void) hipFree(p->filt_dev);
 	(void) hipFree(p->part_dev);
-	(void) hipFree(p->topn_items);
-	(void) hipFree(p->topn_scores);
-	(void) hipFree(p->topn_part_v);
-	(void) hipFree(p->topn_part_i);
-	(void) hipFree(p->topn_part_bad);
+	for (topn_buffers *b : {&p->topn, &p->sim}) {
+		(void) hipFree(b->items);
+		(void) hipFree(b->scores);
+		(void) hipFree(b->part_v);
+		(void) hipFree(b->part_i);
+		(void) hipFree(b->part_bad);
+#ifdef MF_REC_TOPNGL
+		(void) hipFree(b->glist_v);
+		(void) hipFree(b->glist_i);
+#endif
+	}
+	(void) hipFree(p->sim_q);
+	(void) hipFree(p->sim_block);
+	(void) hipFree(p->sim_lnorm);
+	(void) hipFree(p->sim_query);
+	(void) hipFree(p->sim_ptr);
+	(void) hipFree(p->sim_idx);
+	(void) hipFree(p->sim_ulist);
 	(void) hipFree(p->row_sse);
 	(void) hipFree(p->loss_blocks);
 	(void) hipFree(p->loss_total);
@@ -241,10 +254,6 @@ void mf_plan_destroy(mf_plan *p)
 	(void) hipFree(p->rank_above);
 	(void) hipFree(p->rank_band);
 	(void) hipFree(p->rank_list);
-#ifdef MF_REC_TOPNGL
-	(void) hipFree(p->topn_glist_v);
-	(void) hipFree(p->topn_glist_i);
-#endif
 	if (!p->r_external) {
 		(void) hipFree(p->Rbuf[0]);
 		(void) hipFree(p->Rbuf[1]);
@@ -781,54 +790,57 @@ static int topn_grow(T **buf, size_t *cap, size_t count)
 	return rc;
 }
 
-// Top-N on the device: rows of n items / scores per user in p->topn_items / p->topn_scores (nothing copied back).
-// Matrix-core pass (topn_mfma_kernel) with certification and exact re-scoring of the members, the exact pass
-// (topn_exact_kernel) for every user it cannot decide; the exact pass for all users under MF_RECOMMEND_IMPL=exact or
-// when K has no matrix-core form.
-static int launch_topn(mf_plan *p, int n)
+// Top-N on the device: rows of n items / scores per row of the operands' L in o.out->items / scores (nothing copied
+// back).  Matrix-core pass (topn_mfma_kernel) with certification and exact re-scoring of the members, the exact pass
+// (topn_exact_kernel) for every row it cannot decide; the exact pass for all rows under MF_RECOMMEND_IMPL=exact or
+// when K has no matrix-core form.  The plan gives the device, the stream, K and the environment switches only: what is
+// ranked against what, under which mask and into which buffers is the operands' (mf_plan_recommend_topn: the users
+// against the items under the rated mask; mf_plan_similar_items: items against items under the self mask).
+static int launch_topn_core(mf_plan *p, const topn_operands &o, int n)
 {
 	MF_HIP(hipSetDevice(p->device));
+	topn_buffers &b = *o.out;
 	{
-		const size_t need = (size_t) p->uc * (size_t) n;
-		size_t cap_s = p->topn_cap;
-		int rc = topn_grow(&p->topn_items, &p->topn_cap, need);
-		if (rc == MF_OK) rc = topn_grow(&p->topn_scores, &cap_s, need);
+		const size_t need = (size_t) o.rows * (size_t) n;
+		size_t cap_s = b.cap;
+		int rc = topn_grow(&b.items, &b.cap, need);
+		if (rc == MF_OK) rc = topn_grow(&b.scores, &cap_s, need);
 		if (rc != MF_OK) {
-			(void) hipFree(p->topn_scores);
-			p->topn_scores = nullptr;
-			(void) hipFree(p->topn_items);
-			p->topn_items = nullptr;
-			p->topn_cap = 0;
+			(void) hipFree(b.scores);
+			b.scores = nullptr;
+			(void) hipFree(b.items);
+			b.items = nullptr;
+			b.cap = 0;
 			return rc;
 		}
 	}
 	mf::TopnArgs a;
 	memset(&a, 0, sizeof a);
-	a.users = p->uc;
-	a.items = p->items;
+	a.users = o.rows;
+	a.items = o.items;
 	a.K = p->K;
-	a.ldl = p->ldl;
-	a.ldr = p->ldr;
-	a.L = p->Lbuf[p->cur];
-	a.R = p->Rbuf[p->cur];
-	a.csr_ptr = p->csr_ptr;
-	a.csr_idx = p->mask_idx ? p->mask_idx : p->csr_idx;
-	a.lnorm = p->lnorm;
-	a.rnorm_max_bits = p->rmax_bits;
+	a.ldl = o.ldl;
+	a.ldr = o.ldr;
+	a.L = o.L;
+	a.R = o.R;
+	a.csr_ptr = o.mask_ptr;
+	a.csr_idx = o.mask_idx;
+	a.lnorm = o.lnorm;
+	a.rnorm_max_bits = o.rmax_bits;
 	a.thr_scale = mf_backend_recommend_margin(p->K);
 	a.n = n;
-	a.out_items = p->topn_items;
-	a.out_scores = p->topn_scores;
-	a.olist = p->ulist;
-	a.ocount = p->ucount;
+	a.out_items = b.items;
+	a.out_scores = b.scores;
+	a.olist = o.ulist;
+	a.ocount = o.ucount;
 
 	// the matrix-core shapes of recommend_mfma2_kernel: K = 20 NC <= 100, 16 NC <= 96 (four waves), 112, 128, 256 (eight waves)
 	typedef void (*TopnFn)(mf::TopnArgs);
 	const int K = p->K;
-	const bool fits32 = (unsigned long long) p->items * (unsigned long long) p->ldr * 8ull < (1ull << 32);   // 32-bit row offsets
+	const bool fits32 = (unsigned long long) o.items * (unsigned long long) o.ldr * 8ull < (1ull << 32);   // 32-bit row offsets
 	TopnFn fn = nullptr;
 	int qc = 0, waves = 4;
-	if (!p->cfg.rec_exact && fits32 && p->items > 0) {
+	if (!p->cfg.rec_exact && fits32 && o.items > 0) {
 		if (K % 20 == 0 && K <= 100) {
 			static const TopnFn f20[5] = {mf::topn_mfma_kernel<1>, mf::topn_mfma_kernel<2>, mf::topn_mfma_kernel<3>,
 			                              mf::topn_mfma_kernel<4>, mf::topn_mfma_kernel<5>};
@@ -854,19 +866,19 @@ static int launch_topn(mf_plan *p, int n)
 		}
 	}
 	if (!fn) {
-		hipLaunchKernelGGL(mf::topn_exact_kernel, dim3(p->uc), dim3(64), 0, p->stream, a);
+		hipLaunchKernelGGL(mf::topn_exact_kernel, dim3(o.rows), dim3(64), 0, p->stream, a);
 		MF_HIP(hipGetLastError());
-		p->last_topn_uncertain = -1;
-		p->topn_form = 0;
+		b.last_uncertain = -1;
+		b.form = 0;
 		return MF_OK;
 	}
 
-	MF_HIP(hipMemsetAsync(p->rmax_bits, 0, sizeof(unsigned long long), p->stream));
-	MF_HIP(hipMemsetAsync(p->ucount, 0, sizeof(int), p->stream));
-	hipLaunchKernelGGL(mf::row_norm_kernel, dim3((p->uc + 63) / 64), dim3(64), 0, p->stream, a.L, p->uc, p->K, p->ldl, p->lnorm,
+	MF_HIP(hipMemsetAsync(o.rmax_bits, 0, sizeof(unsigned long long), p->stream));
+	MF_HIP(hipMemsetAsync(o.ucount, 0, sizeof(int), p->stream));
+	hipLaunchKernelGGL(mf::row_norm_kernel, dim3((o.rows + 63) / 64), dim3(64), 0, p->stream, a.L, o.rows, p->K, o.ldl, o.lnorm,
 	                   (unsigned long long *) nullptr);
-	hipLaunchKernelGGL(mf::row_norm_kernel, dim3((p->items + 63) / 64), dim3(64), 0, p->stream, a.R, p->items, p->K, p->ldr,
-	                   (double *) nullptr, p->rmax_bits);
+	hipLaunchKernelGGL(mf::row_norm_kernel, dim3((o.items + 63) / 64), dim3(64), 0, p->stream, a.R, o.items, p->K, o.ldr,
+	                   (double *) nullptr, o.rmax_bits);
 #ifdef MF_REC_TOPNGL
 	const size_t lds = mf::rec_mfma2_lds(qc);
 #else
@@ -875,10 +887,10 @@ static int launch_topn(mf_plan *p, int n)
 	MF_HIP(raise_lds_limit((const void *) fn, lds));
 	// two four-wave workgroups per CU while ring + lists + the static arrays (< 3 KB) fit half of the CU's 160 KB
 	const bool two_per_cu = waves == 4 && lds + 3 * 1024 <= 80 * 1024;
-	p->topn_form = two_per_cu ? 1 : 2;
+	b.form = two_per_cu ? 1 : 2;
 
 	// item split of small problems: the rule and MF_RECOMMEND_SPLIT of the top-1 pass
-	const int ublocks = (p->uc + mf::kHU - 1) / mf::kHU, tiles = (p->items + mf::kMI - 1) / mf::kMI;
+	const int ublocks = (o.rows + mf::kHU - 1) / mf::kHU, tiles = (o.items + mf::kMI - 1) / mf::kMI;
 	const int chip = two_per_cu ? 1024 : 512;
 	int nsplit = 1;
 	if (p->cfg.rec_split != 0 && ublocks < chip * 3 / 8 && tiles >= 2) {
@@ -890,50 +902,114 @@ static int launch_topn(mf_plan *p, int n)
 		nsplit = (tiles + tiles_per - 1) / tiles_per;
 		a.split_items = tiles_per * mf::kMI;
 		a.nsplit = nsplit;
-		const size_t nl = (size_t) p->uc * (size_t) (nsplit + 1) * (size_t) (n + 1);
-		size_t cap_i = p->topn_part_cap;
-		int rc = topn_grow(&p->topn_part_v, &p->topn_part_cap, nl);
-		if (rc == MF_OK) rc = topn_grow(&p->topn_part_i, &cap_i, nl);
-		if (rc == MF_OK) rc = topn_grow(&p->topn_part_bad, &p->topn_bad_cap, (size_t) p->uc * (size_t) nsplit);
+		const size_t nl = (size_t) o.rows * (size_t) (nsplit + 1) * (size_t) (n + 1);
+		size_t cap_i = b.part_cap;
+		int rc = topn_grow(&b.part_v, &b.part_cap, nl);
+		if (rc == MF_OK) rc = topn_grow(&b.part_i, &cap_i, nl);
+		if (rc == MF_OK) rc = topn_grow(&b.part_bad, &b.bad_cap, (size_t) o.rows * (size_t) nsplit);
 		if (rc != MF_OK) {
-			(void) hipFree(p->topn_part_v);
-			(void) hipFree(p->topn_part_i);
-			p->topn_part_v = nullptr;
-			p->topn_part_i = nullptr;
-			p->topn_part_cap = 0;
+			(void) hipFree(b.part_v);
+			(void) hipFree(b.part_i);
+			b.part_v = nullptr;
+			b.part_i = nullptr;
+			b.part_cap = 0;
 			return rc;
 		}
-		a.part_v = p->topn_part_v;
-		a.part_i = p->topn_part_i;
-		a.part_bad = p->topn_part_bad;
+		a.part_v = b.part_v;
+		a.part_i = b.part_i;
+		a.part_bad = b.part_bad;
 	}
 #ifdef MF_REC_TOPNGL
 	{   // timing build: the lists of every workgroup in global memory (freed with the plan's other top-N buffers)
 		const size_t ng = (size_t) ublocks * (size_t) nsplit * (size_t) mf::kHU * 2 * (size_t) (n + 1);
-		size_t cap_i = p->topn_glist_cap;
-		int rc = topn_grow(&p->topn_glist_v, &p->topn_glist_cap, ng);
-		if (rc == MF_OK) rc = topn_grow(&p->topn_glist_i, &cap_i, ng);
+		size_t cap_i = b.glist_cap;
+		int rc = topn_grow(&b.glist_v, &b.glist_cap, ng);
+		if (rc == MF_OK) rc = topn_grow(&b.glist_i, &cap_i, ng);
 		if (rc != MF_OK) return rc;
-		a.glist_v = p->topn_glist_v;
-		a.glist_i = p->topn_glist_i;
+		a.glist_v = b.glist_v;
+		a.glist_i = b.glist_i;
 	}
 #endif
 	hipLaunchKernelGGL(fn, dim3(ublocks, nsplit), dim3(64 * waves), lds, p->stream, a);
 	MF_HIP(hipGetLastError());
 	if (nsplit > 1) {
-		hipLaunchKernelGGL(mf::topn_merge_kernel, dim3((p->uc + 255) / 256), dim3(256), 0, p->stream, a);
+		hipLaunchKernelGGL(mf::topn_merge_kernel, dim3((o.rows + 255) / 256), dim3(256), 0, p->stream, a);
 		MF_HIP(hipGetLastError());
 	}
 	int cnt = 0;
-	MF_HIP(hipMemcpyAsync(&cnt, p->ucount, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+	MF_HIP(hipMemcpyAsync(&cnt, o.ucount, sizeof(int), hipMemcpyDeviceToHost, p->stream));
 	MF_HIP(hipStreamSynchronize(p->stream));
-	p->last_topn_uncertain = cnt;
+	b.last_uncertain = cnt;
 	if (cnt > 0) {
-		a.ulist = p->ulist;
+		a.ulist = o.ulist;
 		hipLaunchKernelGGL(mf::topn_exact_kernel, dim3(cnt), dim3(64), 0, p->stream, a);
 		MF_HIP(hipGetLastError());
 	}
 	return MF_OK;
+}
+
+// mf_plan_recommend_topn's operands: this shard's users against the items under the rated mask
+static int launch_topn(mf_plan *p, int n)
+{
+	topn_operands o;
+	o.rows = p->uc;
+	o.items = p->items;
+	o.L = p->Lbuf[p->cur];
+	o.R = p->Rbuf[p->cur];
+	o.ldl = p->ldl;
+	o.ldr = p->ldr;
+	o.mask_ptr = p->csr_ptr;
+	o.mask_idx = p->mask_idx ? p->mask_idx : p->csr_idx;
+	o.lnorm = p->lnorm;
+	o.rmax_bits = p->rmax_bits;
+	o.ulist = p->ulist;
+	o.ucount = p->ucount;
+	o.out = &p->topn;
+	return launch_topn_core(p, o, n);
+}
+
+// mf_plan_similar_items on the device: Q (cosine: similar_normalize_kernel into the plan's buffer; dot: R itself), the
+// self mask and, for a listed query, the gathered rows (similar_gather_kernel), then the top-N pass on those operands.
+// Rows of n items / scores per query in p->sim.items / p->sim.scores.
+static int launch_similar(mf_plan *p, int metric, const int32_t *query, int nq, int n)
+{
+	MF_HIP(hipSetDevice(p->device));
+	const double *Q = p->Rbuf[p->cur];
+	if (metric == MF_SIMILAR_COSINE) {
+		const int rc = topn_grow(&p->sim_q, &p->sim_q_cap, (size_t) p->items * (size_t) p->ldr);
+		if (rc != MF_OK) return rc;
+		hipLaunchKernelGGL(mf::similar_normalize_kernel, dim3((p->items + mf::kSimRows - 1) / mf::kSimRows), dim3(mf::kSimThreads), 0,
+		                   p->stream, p->Rbuf[p->cur], p->items, p->K, p->ldr, p->sim_q);
+		MF_HIP(hipGetLastError());
+		Q = p->sim_q;
+	}
+	const int ldb = row_pitch(p->cfg, p->K, p->sweep.dma != 0);   // the pitch the plan gives an L buffer of its own
+	int rc = topn_grow(&p->sim_ptr, &p->sim_ptr_cap, (size_t) nq + 1);
+	if (rc == MF_OK) rc = topn_grow(&p->sim_idx, &p->sim_idx_cap, (size_t) nq);
+	if (rc == MF_OK) rc = topn_grow(&p->sim_lnorm, &p->sim_lnorm_cap, (size_t) nq);
+	if (rc == MF_OK) rc = topn_grow(&p->sim_ulist, &p->sim_ulist_cap, (size_t) nq);
+	if (rc == MF_OK && query) rc = topn_grow(&p->sim_query, &p->sim_query_cap, (size_t) nq);
+	if (rc == MF_OK && query) rc = topn_grow(&p->sim_block, &p->sim_block_cap, (size_t) nq * (size_t) ldb);
+	if (rc != MF_OK) return rc;
+	if (query) MF_HIP(hipMemcpyAsync(p->sim_query, query, (size_t) nq * sizeof(int32_t), hipMemcpyHostToDevice, p->stream));
+	hipLaunchKernelGGL(mf::similar_gather_kernel, dim3((nq + 63) / 64), dim3(64), 0, p->stream, Q, p->ldr, p->K,
+	                   query ? p->sim_query : (const int *) nullptr, nq, p->sim_block, ldb, p->sim_ptr, p->sim_idx);
+	MF_HIP(hipGetLastError());
+	topn_operands o;
+	o.rows = nq;
+	o.items = p->items;
+	o.L = query ? p->sim_block : Q;
+	o.R = Q;
+	o.ldl = query ? ldb : p->ldr;
+	o.ldr = p->ldr;
+	o.mask_ptr = p->sim_ptr;
+	o.mask_idx = p->sim_idx;
+	o.lnorm = p->sim_lnorm;
+	o.rmax_bits = p->rmax_bits;   // one word each, reset by every pass that uses them
+	o.ulist = p->sim_ulist;
+	o.ucount = p->ucount;
+	o.out = &p->sim;
+	return launch_topn_core(p, o, n);
 }
 
 extern "C" {
@@ -944,15 +1020,15 @@ int mf_plan_recommend_topn(mf_plan *p, int32_t n, int32_t *items, double *scores
 	if (n > MF_TOPN_MAX) return MF_ERR_UNSUPPORTED;
 	if (!p->have_factors) return MF_ERR_STATE;
 	if (p->uc == 0) {   // nothing to rank: no pass ran
-		p->last_topn_uncertain = 0;
-		p->topn_form = 0;
+		p->topn.last_uncertain = 0;
+		p->topn.form = 0;
 		return MF_OK;
 	}
 	const int rc = launch_topn(p, n);
 	if (rc != MF_OK) return rc;
 	const size_t cnt = (size_t) p->uc * (size_t) n;
-	MF_HIP(hipMemcpyAsync(items, p->topn_items, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
-	if (scores) MF_HIP(hipMemcpyAsync(scores, p->topn_scores, cnt * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+	MF_HIP(hipMemcpyAsync(items, p->topn.items, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
+	if (scores) MF_HIP(hipMemcpyAsync(scores, p->topn.scores, cnt * sizeof(double), hipMemcpyDeviceToHost, p->stream));
 	MF_HIP(hipStreamSynchronize(p->stream));
 	return MF_OK;
 }
@@ -960,8 +1036,48 @@ int mf_plan_recommend_topn(mf_plan *p, int32_t n, int32_t *items, double *scores
 int mf_plan_recommend_topn_info(mf_plan *p, int64_t *exact_pass_users, int32_t *mfma_form)
 {
 	if (!p) return MF_ERR_ARGUMENT;
-	if (exact_pass_users) *exact_pass_users = p->last_topn_uncertain;
-	if (mfma_form) *mfma_form = p->topn_form;
+	if (exact_pass_users) *exact_pass_users = p->topn.last_uncertain;
+	if (mfma_form) *mfma_form = p->topn.form;
+	return MF_OK;
+}
+
+// the argument rules of the two similar-items entry points, checked before any HIP call
+static int similar_check(int32_t items_total, int metric, const int32_t *query, int32_t nq, int32_t n, const int32_t *out_items)
+{
+	if (!out_items || n < 1 || nq < 0 || (metric != MF_SIMILAR_DOT && metric != MF_SIMILAR_COSINE)) return MF_ERR_ARGUMENT;
+	if (!query && nq != items_total) return MF_ERR_ARGUMENT;
+	if (query)
+		for (int32_t t = 0; t < nq; ++t)
+			if (query[t] < 0 || query[t] >= items_total) return MF_ERR_ARGUMENT;
+	if (n > MF_TOPN_MAX) return MF_ERR_UNSUPPORTED;
+	return MF_OK;
+}
+
+int mf_plan_similar_items(mf_plan *p, int metric, const int32_t *query, int32_t nq, int32_t n, int32_t *items, double *scores)
+{
+	if (!p) return MF_ERR_ARGUMENT;
+	const int chk = similar_check(p->items, metric, query, nq, n, items);
+	if (chk != MF_OK) return chk;
+	if (!p->have_factors) return MF_ERR_STATE;
+	if (nq == 0) {   // nothing to rank: no pass ran
+		p->sim.last_uncertain = 0;
+		p->sim.form = 0;
+		return MF_OK;
+	}
+	const int rc = launch_similar(p, metric, query, nq, n);
+	if (rc != MF_OK) return rc;
+	const size_t cnt = (size_t) nq * (size_t) n;
+	MF_HIP(hipMemcpyAsync(items, p->sim.items, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
+	if (scores) MF_HIP(hipMemcpyAsync(scores, p->sim.scores, cnt * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+	MF_HIP(hipStreamSynchronize(p->stream));
+	return MF_OK;
+}
+
+int mf_plan_similar_items_info(mf_plan *p, int64_t *exact_pass_queries, int32_t *mfma_form)
+{
+	if (!p) return MF_ERR_ARGUMENT;
+	if (exact_pass_queries) *exact_pass_queries = p->sim.last_uncertain;
+	if (mfma_form) *mfma_form = p->sim.form;
 	return MF_OK;
 }
 
@@ -1131,6 +1247,29 @@ int mf_backend_recommend_topn(const mf_problem *pr, const double *L, const doubl
 	if (rc != MF_OK) return rc;
 	rc = mf_plan_upload_factors(p, L, R);
 	if (rc == MF_OK) rc = mf_plan_recommend_topn(p, n, items, scores);
+	mf_plan_destroy(p);
+	return rc;
+}
+
+int mf_backend_similar_items(const double *R, int32_t items, int32_t features, int metric, const int32_t *query, int32_t nq,
+                             int32_t n, int32_t *out_items, double *out_scores, int device)
+{
+	if (items < 0 || features < 1 || (!R && items > 0)) return MF_ERR_ARGUMENT;
+	const int chk = similar_check(items, metric, query, nq, n, out_items);
+	if (chk != MF_OK) return chk;
+	// a throw-away plan of one user without entries: the query reads nothing of it but R
+	mf_shard s;
+	memset(&s, 0, sizeof s);
+	s.users_total = s.user_count = 1;
+	s.items = items;
+	s.features = features;
+	s.device = device;
+	mf_plan *p = nullptr;
+	int rc = mf_plan_create(&p, &s);
+	if (rc != MF_OK) return rc;
+	const std::vector<double> l0((size_t) features, 0.0);
+	rc = mf_plan_upload_factors(p, l0.data(), R);
+	if (rc == MF_OK) rc = mf_plan_similar_items(p, metric, query, nq, n, out_items, out_scores);
 	mf_plan_destroy(p);
 	return rc;
 }

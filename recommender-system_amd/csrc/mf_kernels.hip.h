@@ -7,5 +7,6 @@
 #include "mf_recommend.hip.h"
 #include "mf_topn.hip.h"
 #include "mf_rank.hip.h"
+#include "mf_similar.hip.h"
 #include "mf_loss.hip.h"
 #include "mf_collective.hip.h"

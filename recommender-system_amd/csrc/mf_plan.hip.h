@@ -126,6 +126,38 @@ struct TimedLaunch {
 	bool shared_start;   // t0 is the previous record's t1 (not owned)
 };
 
+// What a top-N pass (launch_topn_core, mf_hip.hip) writes and reports: the output rows (rows x n), the per-split lists of
+// an item split, and the last call's exact-pass count and form.  All device buffers are allocated on first use and grown
+// on demand; one instance per entry point, so the report of one is not disturbed by a call of the other.
+struct topn_buffers {
+	int *items = nullptr;
+	double *scores = nullptr;
+	size_t cap = 0;                  // entries of items / scores
+	double *part_v = nullptr;
+	int *part_i = nullptr, *part_bad = nullptr;
+	size_t part_cap = 0, bad_cap = 0;
+	int64_t last_uncertain = -1;     // rows of the last call that went through the exact pass (-1: exact form ran)
+	int form = -1;                   // form of the last call (mf_plan_recommend_topn_info)
+#ifdef MF_REC_TOPNGL
+	double *glist_v = nullptr;       // timing build: the matrix-core pass's lists in global memory
+	int *glist_i = nullptr;
+	size_t glist_cap = 0;
+#endif
+};
+
+// The operands of a top-N pass: `rows` rows of L (pitch ldl) are ranked against the `items` rows of R (pitch ldr), row i
+// choosing among the items its mask (a CSR over the rows: item ids ascending within a row) leaves open.
+struct topn_operands {
+	int rows = 0, items = 0;
+	const double *L = nullptr, *R = nullptr;
+	int ldl = 0, ldr = 0;
+	const int *mask_ptr = nullptr, *mask_idx = nullptr;
+	double *lnorm = nullptr;                    // scratch: the norm of every row of L (rows doubles)
+	unsigned long long *rmax_bits = nullptr;    // scratch: the largest norm of a row of R
+	int *ulist = nullptr, *ucount = nullptr;    // scratch: the rows that need the exact pass (rows ints) and their number
+	topn_buffers *out = nullptr;
+};
+
 }  // namespace
 
 struct mf_plan {
@@ -179,20 +211,15 @@ struct mf_plan {
 	unsigned long long *rmax_bits = nullptr;
 	int *ulist = nullptr, *ucount = nullptr;
 	int64_t last_uncertain = -1;   // users re-scored by the exact pass in the last recommend (-1: exact form ran)
-	// top-N (mf_plan_recommend_topn): output rows and per-split lists, allocated on first use and grown on demand
-	int *topn_items = nullptr;
-	double *topn_scores = nullptr;
-	size_t topn_cap = 0;             // entries of topn_items / topn_scores
-	double *topn_part_v = nullptr;
-	int *topn_part_i = nullptr, *topn_part_bad = nullptr;
-	size_t topn_part_cap = 0, topn_bad_cap = 0;
-	int64_t last_topn_uncertain = -1;   // users of the last top-N call that went through the exact pass (-1: exact form ran)
-	int topn_form = -1;                 // form of the last top-N call (mf_plan_recommend_topn_info)
-#ifdef MF_REC_TOPNGL
-	double *topn_glist_v = nullptr;     // timing build: the matrix-core pass's lists in global memory
-	int *topn_glist_i = nullptr;
-	size_t topn_glist_cap = 0;
-#endif
+	// top-N (mf_plan_recommend_topn) and similar items (mf_plan_similar_items): each its own output rows, per-split lists
+	// and report of the last call
+	topn_buffers topn, sim;
+	// similar items, allocated on first use and grown on demand: Q (the rows of R divided by their norms, R's pitch), the
+	// gathered rows of a listed query with the device copy of the list, the self mask, and the pass's scratch by query row
+	double *sim_q = nullptr, *sim_block = nullptr, *sim_lnorm = nullptr;
+	int *sim_query = nullptr, *sim_ptr = nullptr, *sim_idx = nullptr, *sim_ulist = nullptr;
+	size_t sim_q_cap = 0, sim_block_cap = 0, sim_lnorm_cap = 0, sim_query_cap = 0, sim_ptr_cap = 0, sim_idx_cap = 0,
+	       sim_ulist_cap = 0;
 
 	// loss (mf_plan_loss, mf_loss.hip.h): row sums, block sums and total, allocated on first use; the held-out set as a
 	// second CSR over the shard's users (entries of a user in the caller's order)

@@ -190,6 +190,42 @@ static int run_with_loss(const mf_problem *p, const mf_problem *held, const doub
 	return rc;
 }
 
+/*
+ * MATFACT_SIMILAR=N[,dot|cosine] MATFACT_SIMILAR_OUT=<path>: after training, the N nearest other items of every item by
+ * that metric (mf_plan_similar_items on the trained R) go to <path>, one line per item in mf_host_write_topn's format;
+ * stdout is the usual `.out`.
+ */
+static int run_with_similar(const mf_problem *p, const double *L, const double *R, int32_t *best, int device, int n, int metric,
+                            const char *out_path)
+{
+	int32_t *row = malloc(sizeof(int32_t) * (size_t) (p->nnz ? p->nnz : 1));
+	int32_t *col = malloc(sizeof(int32_t) * (size_t) (p->nnz ? p->nnz : 1));
+	double *val = malloc(sizeof(double) * (size_t) (p->nnz ? p->nnz : 1));
+	int32_t *near = malloc(sizeof(int32_t) * (size_t) (p->items > 0 ? p->items : 1) * (size_t) n);
+	mf_plan *plan = NULL;
+	int rc = row && col && val && near ? MF_OK : MF_ERR_NO_MEMORY;
+	if (rc == MF_OK) {
+		mf_host_split_entries(p->entries, p->nnz, row, col, val);
+		mf_shard s = {p->users, p->items, p->features, 0, p->users, p->nnz, row, col, val, p->alpha, device, 0, {0, 0}, {0, 0}, 0, 0};
+		rc = mf_plan_create(&plan, &s);
+	}
+	if (rc == MF_OK) rc = mf_plan_upload_factors(plan, L, R);
+	if (rc == MF_OK) rc = mf_plan_iterate(plan, p->iters);
+	if (rc == MF_OK) rc = mf_plan_recommend(plan, best);
+	if (rc == MF_OK) rc = mf_plan_similar_items(plan, metric, NULL, p->items, n, near, NULL);
+	if (rc == MF_OK) {
+		FILE *f = fopen(out_path, "w");
+		if (!f || mf_host_write_topn(f, near, p->items, n) != 0) rc = MF_ERR_ARGUMENT;
+		if (f && fclose(f) == EOF) rc = MF_ERR_ARGUMENT;
+	}
+	mf_plan_destroy(plan);
+	free(row);
+	free(col);
+	free(val);
+	free(near);
+	return rc;
+}
+
 /* util.c:7-10 */
 static void die(const char *error)
 {
@@ -252,6 +288,26 @@ int main(int argc, char **argv)
 		if (!loss_every || !getenv("MATFACT_HELDOUT")) die("MATFACT_RANK needs MATFACT_HELDOUT=<file.in>.");
 		rank_cutoff = (int) v;
 	}
+	/* MATFACT_SIMILAR=N[,dot|cosine] (1..MF_TOPN_MAX, default cosine) with MATFACT_SIMILAR_OUT=<path>: the N nearest other
+	 * items of every item, one line per item, to <path>; stdout is unchanged.  The single-GPU default path only. */
+	int similar = 0, similar_metric = MF_SIMILAR_COSINE;
+	const char *similar_env = getenv("MATFACT_SIMILAR");
+	if (similar_env) {
+		char *stop;
+		const long v = strtol(similar_env, &stop, 10);
+		if (stop == similar_env || v < 1 || v > MF_TOPN_MAX || (*stop && *stop != ','))
+			die("MATFACT_SIMILAR: expected N[,dot|cosine] with N a whole number from 1 to 32.");
+		if (*stop == ',') {
+			if (!strcmp(stop + 1, "dot")) similar_metric = MF_SIMILAR_DOT;
+			else if (strcmp(stop + 1, "cosine")) die("MATFACT_SIMILAR: expected N[,dot|cosine] with N a whole number from 1 to 32.");
+		}
+		if (!getenv("MATFACT_SIMILAR_OUT") || !*getenv("MATFACT_SIMILAR_OUT")) die("MATFACT_SIMILAR needs MATFACT_SIMILAR_OUT=<path>.");
+		if (getenv("MATFACT_DEVICES") || getenv("MATFACT_MATS") || getenv("MATFACT_CHECKPOINT") || getenv("MATFACT_RESUME"))
+			die("MATFACT_SIMILAR works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT and MATFACT_RESUME.");
+		if (topn || loss_every) die("MATFACT_SIMILAR cannot be combined with MATFACT_TOPN or MATFACT_LOSS.");
+		similar = (int) v;
+	} else if (getenv("MATFACT_SIMILAR_OUT"))
+		die("MATFACT_SIMILAR_OUT needs MATFACT_SIMILAR=N[,dot|cosine].");
 	const double t0 = now();
 
 	mf_problem prob;
@@ -297,6 +353,8 @@ int main(int argc, char **argv)
 		rc = run_with_loss(&prob, have_held ? &held : NULL, L, R, best, device, loss_every, loss_tol, rank_cutoff);
 	} else if (topn) {
 		rc = mf_backend_run_topn(&prob, L, R, topn, topn_items, NULL, device);
+	} else if (similar) {
+		rc = run_with_similar(&prob, L, R, best, device, similar, similar_metric, getenv("MATFACT_SIMILAR_OUT"));
 	} else if (getenv("MATFACT_CHECKPOINT") || getenv("MATFACT_RESUME")) {
 		rc = run_with_checkpoints(&prob, L, R, best, device, start_iter);
 	} else if (mats) {
