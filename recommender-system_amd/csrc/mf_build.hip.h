@@ -23,14 +23,6 @@ inline hipError_t h2d(mf_plan *p, void *dst, const void *src, size_t bytes)
 	} while (0)
 #define MF_TRY_HIP(call) MF_HIP(call)
 
-template <typename T>
-int dev_alloc(T **out, size_t count)
-{
-	*out = nullptr;
-	MF_HIP(hipMalloc((void **) out, std::max<size_t>(count, 1) * sizeof(T)));
-	return MF_OK;
-}
-
 // stable counting sort of the entries by `key` into (ptr, idx, val)
 void bucket(int64_t nnz, int nkeys, const int32_t *key, int32_t key_off, const int32_t *other,
             int32_t other_off, const double *val, std::vector<int> &ptr, std::vector<int> &idx,
@@ -138,12 +130,13 @@ int bits_for(int nkeys)
 }
 
 struct DevTmp {   // frees its buffers on scope exit
-	std::vector<void *> bufs;
-	~DevTmp() { for (void *b : bufs) (void) hipFree(b); }
+	std::vector<dev_buf<char>> bufs;
 	template <typename T> int get(T **out, size_t count)
 	{
-		const int rc = dev_alloc(out, count);
-		if (rc == MF_OK) bufs.push_back(*out);
+		dev_buf<char> b;
+		const int rc = b.alloc(std::max<size_t>(count, 1) * sizeof(T));
+		*out = (T *) b.get();
+		if (rc == MF_OK) bufs.push_back(std::move(b));
 		return rc;
 	}
 };
@@ -168,12 +161,12 @@ int build_on_device(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swa
 	const int64_t nnz = s->nnz;
 	const size_t nz = (size_t) nnz;
 	hipStream_t st = p->stream;
-	MF_HIP(dev_alloc(&p->csr_ptr, (size_t) p->uc + 1) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
-	MF_HIP(dev_alloc(&p->csc_ptr, (size_t) p->items + 1) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
-	MF_HIP(dev_alloc(&p->csr_idx, nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
-	MF_HIP(dev_alloc(&p->csr_val, nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
-	MF_HIP(dev_alloc(&p->csc_idx, nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
-	MF_HIP(dev_alloc(&p->csc_val, nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
+	MF_HIP(p->csr_ptr.alloc((size_t) p->uc + 1) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
+	MF_HIP(p->csc_ptr.alloc((size_t) p->items + 1) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
+	MF_HIP(p->csr_idx.alloc(nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
+	MF_HIP(p->csr_val.alloc(nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
+	MF_HIP(p->csc_idx.alloc(nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
+	MF_HIP(p->csc_val.alloc(nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
 	csr_ptr_host.assign((size_t) p->uc + 1, 0);
 	csc_ptr_host.assign((size_t) p->items + 1, 0);
 	if (nnz == 0) {
@@ -269,7 +262,7 @@ int build_on_device(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swa
 		unsigned *mk_in = nullptr, *mk_out = nullptr, *mv_out = nullptr;
 		if ((rc = tmp.get(&mk_in, nz)) != MF_OK || (rc = tmp.get(&mk_out, nz)) != MF_OK || (rc = tmp.get(&mv_out, nz)) != MF_OK)
 			return rc;
-		MF_HIP(dev_alloc(&p->mask_idx, nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
+		MF_HIP(p->mask_idx.alloc(nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
 		hipLaunchKernelGGL(copy_keys_kernel, dim3(grid), dim3(256), 0, st, p->csc_idx, nnz, mk_in, perm_in);
 		size_t need2 = 0;
 		MF_HIP(rocprim::radix_sort_pairs(nullptr, need2, mk_in, mk_out, key_out, mv_out, nz, 0, bits_for(p->uc), st));
@@ -279,7 +272,7 @@ int build_on_device(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swa
 		MF_HIP(hipMemcpyAsync(p->mask_idx, mv_out, nz * sizeof(int), hipMemcpyDeviceToDevice, st));
 	}
 	if (p->want_map) {
-		MF_HIP(dev_alloc(&p->csr2csc, nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
+		MF_HIP(p->csr2csc.alloc(nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
 		hipLaunchKernelGGL(csr2csc_kernel, dim3(grid), dim3(256), 0, st, perm_out, nnz, file2csr, p->csr2csc);
 	}
 	MF_HIP(hipGetLastError());
@@ -330,9 +323,9 @@ int build_sparse(mf_plan *p, const mf_shard *s_in, const mf_entry *aos, bool swa
 		} catch (const std::bad_alloc &) {
 			return MF_ERR_NO_MEMORY;
 		}
-		MF_TRY(dev_alloc(&p->csr_ptr, (size_t) p->uc + 1));
-		MF_TRY(dev_alloc(&p->csr_idx, nz + 64));
-		MF_TRY(dev_alloc(&p->csr_val, nz + 64));
+		MF_TRY(p->csr_ptr.alloc((size_t) p->uc + 1));
+		MF_TRY(p->csr_idx.alloc(nz + 64));
+		MF_TRY(p->csr_val.alloc(nz + 64));
 		MF_TRY_HIP(h2d(p, p->csr_ptr, rptr.data(), ((size_t) p->uc + 1) * sizeof(int)));
 		{
 			// mask ids ascending inside every row (see build_on_device) when the file order is not
@@ -342,7 +335,7 @@ int build_sparse(mf_plan *p, const mf_shard *s_in, const mf_entry *aos, bool swa
 			if (!ascending) {
 				std::vector<int> mk(idx);
 				for (int u = 0; u < p->uc; ++u) std::sort(mk.begin() + rptr[(size_t) u], mk.begin() + rptr[(size_t) u + 1]);
-				MF_TRY(dev_alloc(&p->mask_idx, nz + 64));
+				MF_TRY(p->mask_idx.alloc(nz + 64));
 				MF_TRY_HIP(h2d(p, p->mask_idx, mk.data(), nz * sizeof(int)));
 			}
 		}
@@ -355,9 +348,9 @@ int build_sparse(mf_plan *p, const mf_shard *s_in, const mf_entry *aos, bool swa
 		} catch (const std::bad_alloc &) {
 			return MF_ERR_NO_MEMORY;
 		}
-		MF_TRY(dev_alloc(&p->csc_ptr, (size_t) p->items + 1));
-		MF_TRY(dev_alloc(&p->csc_idx, nz + 64));
-		MF_TRY(dev_alloc(&p->csc_val, nz + 64));
+		MF_TRY(p->csc_ptr.alloc((size_t) p->items + 1));
+		MF_TRY(p->csc_idx.alloc(nz + 64));
+		MF_TRY(p->csc_val.alloc(nz + 64));
 		MF_TRY_HIP(h2d(p, p->csc_ptr, cptr.data(), ((size_t) p->items + 1) * sizeof(int)));
 		if (nz) {
 			MF_TRY_HIP(h2d(p, p->csc_idx, idx.data(), nz * sizeof(int)));
@@ -366,7 +359,7 @@ int build_sparse(mf_plan *p, const mf_shard *s_in, const mf_entry *aos, bool swa
 		if (p->want_map) {
 			std::vector<int> map(nz + 1);
 			for (size_t n = 0; n < nz; ++n) map[(size_t) pos_r[n]] = pos_c[n];
-			MF_TRY(dev_alloc(&p->csr2csc, nz + 64));
+			MF_TRY(p->csr2csc.alloc(nz + 64));
 			if (nz) MF_TRY_HIP(h2d(p, p->csr2csc, map.data(), nz * sizeof(int)));
 		}
 	} else {
@@ -493,12 +486,12 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 				std::stable_sort(lg.begin(), lg.end(), by_len);
 			}
 			if (!md.empty()) {
-				MF_TRY(dev_alloc(&p->mid_rows[kind], md.size()));
+				MF_TRY(p->mid_rows[kind].alloc(md.size()));
 				MF_TRY_HIP(h2d(p, p->mid_rows[kind], md.data(), md.size() * sizeof(int)));
 				p->n_mid[kind] = (int) md.size();
 			}
-			MF_TRY(dev_alloc(&p->long_rows[kind], lg.size()));
-			MF_TRY(dev_alloc(&p->short_rows[kind], sh.size()));
+			MF_TRY(p->long_rows[kind].alloc(lg.size()));
+			MF_TRY(p->short_rows[kind].alloc(sh.size()));
 			MF_TRY_HIP(h2d(p, p->long_rows[kind], lg.data(), lg.size() * sizeof(int)));
 			if (!sh.empty())
 				MF_TRY_HIP(h2d(p, p->short_rows[kind], sh.data(), sh.size() * sizeof(int)));
@@ -527,12 +520,12 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 			}
 			scratch_entries = std::max(scratch_entries, off);
 			p->n_seg[kind] = (int) srow.size();
-			MF_TRY(dev_alloc(&p->seg_row[kind], srow.size()));
-			MF_TRY(dev_alloc(&p->seg_beg[kind], srow.size()));
-			MF_TRY(dev_alloc(&p->seg_end[kind], srow.size()));
-			MF_TRY(dev_alloc(&p->seg_out[kind], srow.size()));
-			MF_TRY(dev_alloc(&p->lr_sbeg[kind], lg.size()));
-			MF_TRY(dev_alloc(&p->lr_cnt[kind], lg.size()));
+			MF_TRY(p->seg_row[kind].alloc(srow.size()));
+			MF_TRY(p->seg_beg[kind].alloc(srow.size()));
+			MF_TRY(p->seg_end[kind].alloc(srow.size()));
+			MF_TRY(p->seg_out[kind].alloc(srow.size()));
+			MF_TRY(p->lr_sbeg[kind].alloc(lg.size()));
+			MF_TRY(p->lr_cnt[kind].alloc(lg.size()));
 			MF_TRY_HIP(h2d(p, p->seg_row[kind], srow.data(), srow.size() * sizeof(int)));
 			MF_TRY_HIP(h2d(p, p->seg_beg[kind], sbeg.data(), srow.size() * sizeof(int)));
 			MF_TRY_HIP(h2d(p, p->seg_end[kind], send.data(), srow.size() * sizeof(int)));
@@ -558,7 +551,7 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 			MF_TRY_HIP(raise_lds_limit(cfg.os_dpp ? (const void *) mf::ordered_sum_kernel<true> : (const void *) mf::ordered_sum_kernel<false>, p->lds_bytes_osum));
 			// [slice][entry][kSliceCols doubles]; one block of padding per slice: the last block of a row is read whole
 			p->scratch_entries = (size_t) scratch_entries + mf::kBlockEntries;
-			MF_TRY(dev_alloc(&p->scratch, p->scratch_entries * mf::kSliceCols *
+			MF_TRY(p->scratch.alloc(p->scratch_entries * mf::kSliceCols *
 			                                  (size_t) ((p->K + mf::kSliceCols - 1) / mf::kSliceCols)));
 			int prio_lo = 0, prio_hi = 0;
 			MF_TRY_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
@@ -657,7 +650,7 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 				std::stable_sort(head.begin(), head.end(), longer);
 				order.insert(order.begin(), head.begin(), head.end());
 			}
-			MF_TRY(dev_alloc(&p->short_rows[kind], order.size()));
+			MF_TRY(p->short_rows[kind].alloc(order.size()));
 			MF_TRY_HIP(h2d(p, p->short_rows[kind], order.data(), order.size() * sizeof(int)));
 			p->lpt[kind] = true;
 		}
@@ -690,11 +683,11 @@ int plan_es_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vector
 	}
 	p->es_nseg = (int) srow.size();
 	if (p->es_nseg == 0 || p->res_sw <= 0) return MF_OK;
-	MF_TRY(dev_alloc(&p->es_seg_row, srow.size()));
-	MF_TRY(dev_alloc(&p->es_seg_beg, srow.size()));
-	MF_TRY(dev_alloc(&p->es_seg_end, srow.size()));
-	MF_TRY(dev_alloc(&p->rec_csr, (size_t) p->nnz + 64));
-	MF_TRY(dev_alloc(&p->rec_csc, (size_t) p->nnz + 64));
+	MF_TRY(p->es_seg_row.alloc(srow.size()));
+	MF_TRY(p->es_seg_beg.alloc(srow.size()));
+	MF_TRY(p->es_seg_end.alloc(srow.size()));
+	MF_TRY(p->rec_csr.alloc((size_t) p->nnz + 64));
+	MF_TRY(p->rec_csc.alloc((size_t) p->nnz + 64));
 	MF_TRY_HIP(h2d(p, p->es_seg_row, srow.data(), srow.size() * sizeof(int)));
 	MF_TRY_HIP(h2d(p, p->es_seg_beg, sbeg.data(), srow.size() * sizeof(int)));
 	MF_TRY_HIP(h2d(p, p->es_seg_end, send.data(), srow.size() * sizeof(int)));
@@ -763,7 +756,7 @@ int plan_es_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vector
 		p->res_nwg = (int) wgs.size();
 		p->res_lds = (size_t) std::max(p->uc, p->items) * sw * 8 + mf::kResidentWaves * mf::kResidentWaveLds;
 		if (p->res_nwg > 0) {
-			MF_TRY(dev_alloc(&p->res_wg, wgs.size()));
+			MF_TRY(p->res_wg.alloc(wgs.size()));
 			MF_TRY_HIP(h2d(p, p->res_wg, wgs.data(), wgs.size() * sizeof(mf::SliceWg)));
 			const void *fn = sw == 8   ? (const void *) mf::stream_resident_kernel<8>
 			                 : sw == 4 ? (const void *) mf::stream_resident_kernel<4>

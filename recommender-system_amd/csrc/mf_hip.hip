@@ -19,9 +19,12 @@
 #include <vector>
 
 #include "mf_config.hip.h"
+#include "mf_device.hip.h"
 #include "mf_plan.hip.h"
 #include "mf_launch.hip.h"
 #include "mf_build.hip.h"
+#include "mf_certified.hip.h"
+#include "mf_loss_host.hip.h"
 
 extern "C" {
 
@@ -142,8 +145,10 @@ static int plan_create_impl(mf_plan **out, const mf_shard *s, const mf_entry *ao
 		p->Lbuf[0] = (double *) s->users_ext[0];
 		p->Lbuf[1] = (double *) s->users_ext[1];
 	} else {
-		MF_TRY(dev_alloc(&p->Lbuf[0], nl));
-		MF_TRY(dev_alloc(&p->Lbuf[1], nl));
+		MF_TRY(p->Lown[0].alloc(nl));
+		MF_TRY(p->Lown[1].alloc(nl));
+		p->Lbuf[0] = p->Lown[0];
+		p->Lbuf[1] = p->Lown[1];
 		if (p->ldl != p->K) {   // the padding is never read by a kernel, but it is summed by the multi-GPU reducers
 			MF_TRY_HIP(hipMemsetAsync(p->Lbuf[0], 0, std::max<size_t>(nl, 1) * sizeof(double), p->stream));
 			MF_TRY_HIP(hipMemsetAsync(p->Lbuf[1], 0, std::max<size_t>(nl, 1) * sizeof(double), p->stream));
@@ -154,19 +159,21 @@ static int plan_create_impl(mf_plan **out, const mf_shard *s, const mf_entry *ao
 		p->Rbuf[0] = (double *) s->items_ext[0];
 		p->Rbuf[1] = (double *) s->items_ext[1];
 	} else {
-		MF_TRY(dev_alloc(&p->Rbuf[0], nr));
-		MF_TRY(dev_alloc(&p->Rbuf[1], nr));
+		MF_TRY(p->Rown[0].alloc(nr));
+		MF_TRY(p->Rown[1].alloc(nr));
+		p->Rbuf[0] = p->Rown[0];
+		p->Rbuf[1] = p->Rown[1];
 		if (p->ldr != p->K) {
 			MF_TRY_HIP(hipMemsetAsync(p->Rbuf[0], 0, std::max<size_t>(nr, 1) * sizeof(double), p->stream));
 			MF_TRY_HIP(hipMemsetAsync(p->Rbuf[1], 0, std::max<size_t>(nr, 1) * sizeof(double), p->stream));
 		}
 	}
 	MF_TRY_HIP(hipStreamSynchronize(p->stream));   // the plan is complete when the call returns
-	MF_TRY(dev_alloc(&p->best_dev, (size_t) p->uc));
-	MF_TRY(dev_alloc(&p->lnorm, (size_t) p->uc));
-	MF_TRY(dev_alloc(&p->rmax_bits, 1));
-	MF_TRY(dev_alloc(&p->ulist, (size_t) p->uc));
-	MF_TRY(dev_alloc(&p->ucount, 1));
+	MF_TRY(p->best_dev.alloc((size_t) p->uc));
+	MF_TRY(p->lnorm.alloc((size_t) p->uc));
+	MF_TRY(p->rmax_bits.alloc(1));
+	MF_TRY(p->ulist.alloc((size_t) p->uc));
+	MF_TRY(p->ucount.alloc(1));
 #undef MF_TRY
 #undef MF_TRY_HIP
 	*out = p;
@@ -201,87 +208,13 @@ void mf_plan_destroy(mf_plan *p)
 		if (!t.shared_start) (void) hipEventDestroy(t.t0);
 		(void) hipEventDestroy(t.t1);
 	}
-	(void) hipFree(p->csr2csc);
-	(void) hipFree(p->mask_idx);
-	(void) hipFree(p->rec_csr);
-	(void) hipFree(p->rec_csc);
-	(void) hipFree(p->es_seg_row);
-	(void) hipFree(p->es_seg_beg);
-	(void) hipFree(p->es_seg_end);
-	(void) hipFree(p->res_wg);
-	(void) hipFree(p->csr_ptr);
-	(void) hipFree(p->csr_idx);
-	(void) hipFree(p->csr_val);
-	(void) hipFree(p->csc_ptr);
-	(void) hipFree(p->csc_idx);
-	(void) hipFree(p->csc_val);
-	if (!p->l_external) {
-		(void) hipFree(p->Lbuf[0]);
-		(void) hipFree(p->Lbuf[1]);
-	}
-	(void) hipFree(p->cand_dev);
-	(void) hipFree(p->cand_pack);
-	(void) hipFree(p->filt_dev);
-	(void) hipFree(p->part_dev);
-	for (topn_buffers *b : {&p->topn, &p->sim}) {
-		(void) hipFree(b->items);
-		(void) hipFree(b->scores);
-		(void) hipFree(b->part_v);
-		(void) hipFree(b->part_i);
-		(void) hipFree(b->part_bad);
-#ifdef MF_REC_TOPNGL
-		(void) hipFree(b->glist_v);
-		(void) hipFree(b->glist_i);
-#endif
-	}
-	(void) hipFree(p->sim_q);
-	(void) hipFree(p->sim_block);
-	(void) hipFree(p->sim_lnorm);
-	(void) hipFree(p->sim_query);
-	(void) hipFree(p->sim_ptr);
-	(void) hipFree(p->sim_idx);
-	(void) hipFree(p->sim_ulist);
-	(void) hipFree(p->row_sse);
-	(void) hipFree(p->loss_blocks);
-	(void) hipFree(p->loss_total);
-	(void) hipFree(p->ho_ptr);
-	(void) hipFree(p->ho_idx);
-	(void) hipFree(p->ho_val);
-	(void) hipFree(p->ho_user);
-	(void) hipFree(p->rank_score);
-	(void) hipFree(p->rank_state);
-	(void) hipFree(p->rank_out);
-	(void) hipFree(p->rank_above);
-	(void) hipFree(p->rank_band);
-	(void) hipFree(p->rank_list);
-	if (!p->r_external) {
-		(void) hipFree(p->Rbuf[0]);
-		(void) hipFree(p->Rbuf[1]);
-	}
-	(void) hipFree(p->best_dev);
-	for (int k = 0; k < 2; ++k) {
-		(void) hipFree(p->long_rows[k]);
-		(void) hipFree(p->mid_rows[k]);
-		(void) hipFree(p->short_rows[k]);
-		(void) hipFree(p->seg_row[k]);
-		(void) hipFree(p->seg_beg[k]);
-		(void) hipFree(p->seg_end[k]);
-		(void) hipFree(p->seg_out[k]);
-		(void) hipFree(p->lr_sbeg[k]);
-		(void) hipFree(p->lr_cnt[k]);
-	}
-	(void) hipFree(p->scratch);
 	if (p->side_stream) (void) hipStreamDestroy(p->side_stream);
 	if (p->mid_stream) (void) hipStreamDestroy(p->mid_stream);
 	if (p->ev_mid_join) (void) hipEventDestroy(p->ev_mid_join);
 	if (p->ev_fork) (void) hipEventDestroy(p->ev_fork);
 	if (p->ev_join) (void) hipEventDestroy(p->ev_join);
-	(void) hipFree(p->lnorm);
-	(void) hipFree(p->rmax_bits);
-	(void) hipFree(p->ulist);
-	(void) hipFree(p->ucount);
 	if (p->own_stream) (void) hipStreamDestroy(p->own_stream);
-	delete p;
+	delete p;   // frees the device memory: every buffer is a dev_buf member
 }
 
 int mf_plan_set_stream(mf_plan *p, void *hip_stream)
@@ -467,163 +400,6 @@ int mf_plan_iterate(mf_plan *p, int iters)
 	return iterate_eager(p, iters);
 }
 
-}   // extern "C"
-
-// Pass 1 of the recommendation: row norms + recommend_mfma_kernel.  filt == nullptr: the kernel certifies per user
-// against THIS plan's items (best / list of uncertain users); filt != nullptr: it only reports (best, second, arg,
-// non-finite flag) per user, for a certification over several item blocks by the caller (2-D tiles).
-static int launch_recommend_pass1(mf_plan *p, mf_filter *filt)
-{
-	const double *Lc = p->Lbuf[p->cur], *Rc = p->Rbuf[p->cur];
-	// pass 1: scores on the FP64 matrix cores + certification margin; pass 2: exact re-scoring of the rest
-	MF_HIP(hipMemsetAsync(p->rmax_bits, 0, sizeof(unsigned long long), p->stream));
-	MF_HIP(hipMemsetAsync(p->ucount, 0, sizeof(int), p->stream));
-	hipLaunchKernelGGL(mf::row_norm_kernel, dim3((p->uc + 63) / 64), dim3(64), 0, p->stream, Lc, p->uc,
-	                   p->K, p->ldl, p->lnorm, (unsigned long long *) nullptr);
-	if (p->items > 0)
-		hipLaunchKernelGGL(mf::row_norm_kernel, dim3((p->items + 63) / 64), dim3(64), 0, p->stream, Rc,
-		                   p->items, p->K, p->ldr, (double *) nullptr, p->rmax_bits);
-	mf::RecMfmaArgs m;
-	m.users = p->uc;
-	m.items = p->items;
-	m.K = p->K;
-	m.ldl = p->ldl;
-	m.ldr = p->ldr;
-	m.L = Lc;
-	m.R = Rc;
-	m.csr_ptr = p->csr_ptr;
-	m.csr_idx = p->mask_idx ? p->mask_idx : p->csr_idx;
-	m.lnorm = p->lnorm;
-	m.rnorm_max_bits = p->rmax_bits;
-	m.thr_scale = mf_backend_recommend_margin(p->K);
-	m.best = p->best_dev;
-	m.ulist = p->ulist;
-	m.ucount = p->ucount;
-	m.filt = filt;
-	// Form.  The L block's image stays resident in LDS (it is the same for every item tile) whenever it fits
-	// beside the two R buffers, and the R chunks then go global -> LDS by LDS-DMA (even K): K <= 64 with 32-deep
-	// chunks, up to K = 100 with 24- or 20-deep ones -- the depth with the fewest chunks wins, an exact divisor
-	// of K on ties (K=100: 5 x 20 instead of 32+32+32+4).  Larger K: both operands staged through registers.
-	// Measured on 1e6 x 1e5 (profiles/r01/recommend_resident_L_ab.txt): K=100 55.4 vs 48.9 TFLOP/s, K=64 54.3
-	// vs 50.2, K=30 41.1 vs 37.7.
-	typedef void (*RecFn)(mf::RecMfmaArgs);
-	const bool vec = (p->K & 1) == 0;
-	const bool allow = p->cfg.rec_ares;              // MF_RECOMMEND_ARES=0 disables the resident-L form (tests, A/B)
-	const bool allow_dma = vec && p->cfg.rec_bdma;   // MF_RECOMMEND_BDMA=0: stage R chunks through registers (A/B)
-	const size_t static_lds = 8 * 1024, cu_lds = 160 * 1024;   // masks + merge arrays, rounded up
-	int kc = 32;
-	bool ares = false;
-	if (allow) {
-		int best_nch = 1 << 30;
-		for (int cand : {32, 24, 20}) {
-			if (cand == 24 && !allow_dma) continue;                    // 24 exists in the DMA form only
-			if (cand == 20 && p->K % 20 != 0 && !allow_dma) continue;   // register form: exact multiples only
-			if (mf::rec_mfma_lds(p->K, cand, true) + static_lds > cu_lds) continue;
-			const int nch = (p->K + cand - 1) / cand;
-			if (nch < best_nch || (nch == best_nch && p->K % cand == 0 && p->K % kc != 0)) {
-				best_nch = nch;
-				kc = cand;
-				ares = true;
-			}
-		}
-	}
-	const bool bdma = ares && allow_dma;
-	RecFn fn;
-	if (kc == 24)
-		fn = mf::recommend_mfma_kernel<true, 24, true, true>;
-	else if (kc == 20)   // even K here
-		fn = bdma ? mf::recommend_mfma_kernel<true, 20, true, true> : mf::recommend_mfma_kernel<true, 20, true, false>;
-	else if (bdma)
-		fn = mf::recommend_mfma_kernel<true, 32, true, true>;
-	else
-		fn = ares ? (vec ? mf::recommend_mfma_kernel<true, 32, true> : mf::recommend_mfma_kernel<false, 32, true>)
-		          : (vec ? mf::recommend_mfma_kernel<true, 32, false> : mf::recommend_mfma_kernel<false, 32, false>);
-	size_t lds = mf::rec_mfma_lds(p->K, kc, ares);
-	// K = 20, 40, .. 100 (a wave's L operand fits its registers; whole 20-deep chunks): workgroups of 64 users, two per CU,
-	// whose barriers / arg-max steps / mask walks overlap each other's matrix instructions, with a gapless matrix stream
-	// per wave.  K=100: 64.7 vs 57.6 TFLOP/s on the 131072 x 100000 probe, K=80 64.3 vs 57.4, K=40 57.7 vs 52.1, K=20 49.7 vs
-	// 45.0.  Its general form (any even K <= 100, MF_RECOMMEND_HALF=all) has branches on K in the tile body that defeat
-	// hipcc's s_waitcnt placement and is slower than the 128-user kernel (K=64: 51.7 vs 58.5): not chosen by the rule.
-	// The same kernel with 16-deep chunks for K = 16, 32, .. 128 (two per CU as well) and, for K = 256, with 16 users per
-	// wave and eight waves per workgroup (one per CU): DESIGN.md 5.8.
-	const bool fits32 = (unsigned long long) p->items * (unsigned long long) p->ldr * 8ull < (1ull << 32);   // 32-bit row offsets
-	RecFn hfn = nullptr;
-	int hqc = 0, hwaves = 4;
-	if (vec && allow_dma && p->cfg.rec_half && fits32) {
-		const int K = p->K;
-		if (K % 20 == 0 && K <= mf::kHKmax) {
-			static const RecFn f20[5] = {mf::recommend_mfma2_kernel<1>, mf::recommend_mfma2_kernel<2>, mf::recommend_mfma2_kernel<3>,
-			                             mf::recommend_mfma2_kernel<4>, mf::recommend_mfma2_kernel<5>};
-			hfn = f20[K / 20 - 1];
-			hqc = 5;
-		} else if (K % 16 == 0 && K <= 128) {
-			static const RecFn f16[8] = {mf::recommend_mfma2_kernel<1, 4>, mf::recommend_mfma2_kernel<2, 4>, mf::recommend_mfma2_kernel<3, 4>,
-			                             mf::recommend_mfma2_kernel<4, 4>, mf::recommend_mfma2_kernel<5, 4>, mf::recommend_mfma2_kernel<6, 4>,
-			                             mf::recommend_mfma2_kernel<7, 4>, mf::recommend_mfma2_kernel<8, 4>};
-			hfn = f16[K / 16 - 1];
-			hqc = 4;
-		} else if (K == 256) {
-			hfn = mf::recommend_mfma2_kernel<8, 8, 1, 8>;
-			hqc = 8;
-			hwaves = 8;
-		}
-		if (K == 128 && p->cfg.rec_wide) {   // MF_RECOMMEND_WIDE (experiments build): K=128 in the eight-wave shape of K=256
-			hfn = mf::recommend_mfma2_kernel<4, 8, 1, 8>;
-			hqc = 8;
-			hwaves = 8;
-		}
-		if (!hfn && p->cfg.rec_half == 2 && K <= mf::kHKmax) {
-			hfn = mf::recommend_mfma2_kernel<0>;
-			hqc = 5;
-		}
-	}
-	const bool half = hfn != nullptr;
-	int block_users = mf::kMU, threads = mf::kMThreads;
-	if (half) {
-		fn = hfn;
-		lds = mf::rec_mfma2_lds(hqc);
-		block_users = mf::kHU;
-		threads = 64 * hwaves;
-	}
-	p->rec_half_used = half;
-	MF_HIP(raise_lds_limit((const void *) fn, lds));
-	// Small problems: a workgroup owns 128 (64) users and ALL items, so few users leave most of the chip idle (cfg3: 48
-	// workgroups on 256 CUs).  The items are then split over gridDim.y -- whole 128-item tiles, about two workgroups per
-	// CU in all (four of the half-size ones) -- and the per-split top-2 reports merged and certified by merge_splits_kernel.
-	const int ublocks = (p->uc + block_users - 1) / block_users, tiles = (p->items + mf::kMI - 1) / mf::kMI;
-	const int chip = half && hwaves == 4 ? 1024 : 512;   // workgroups the chip holds at once, times two
-	int nsplit = 1;
-	if (p->cfg.rec_split != 0 && ublocks < chip * 3 / 8 && tiles >= 2) {
-		nsplit = p->cfg.rec_split > 0 ? p->cfg.rec_split : (chip + ublocks - 1) / ublocks;
-		nsplit = std::max(1, std::min(nsplit, tiles));
-	}
-	m.split_items = 0;
-	m.part = nullptr;
-	if (nsplit > 1) {
-		const int tiles_per = (tiles + nsplit - 1) / nsplit;
-		nsplit = (tiles + tiles_per - 1) / tiles_per;
-		m.split_items = tiles_per * mf::kMI;
-		if (p->part_cap < nsplit) {
-			(void) hipFree(p->part_dev);
-			p->part_dev = nullptr;
-			p->part_cap = 0;
-			const int rc = dev_alloc(&p->part_dev, (size_t) nsplit * (size_t) p->uc);
-			if (rc != MF_OK) return rc;
-			p->part_cap = nsplit;
-		}
-		m.part = p->part_dev;
-	}
-	hipLaunchKernelGGL(fn, dim3(ublocks, nsplit), dim3(threads), lds, p->stream, m);
-	MF_HIP(hipGetLastError());
-	if (nsplit > 1) {
-		hipLaunchKernelGGL(mf::merge_splits_kernel, dim3((p->uc + 255) / 256), dim3(256), 0, p->stream, m, nsplit);
-		MF_HIP(hipGetLastError());
-	}
-	return MF_OK;
-}
-
-extern "C" {
-
 int mf_plan_recommend(mf_plan *p, int32_t *best)
 {
 	if (!p || (!best && p->uc > 0)) return MF_ERR_ARGUMENT;
@@ -631,19 +407,7 @@ int mf_plan_recommend(mf_plan *p, int32_t *best)
 	MF_HIP(hipSetDevice(p->device));
 	if (p->uc == 0) return MF_OK;
 	const bool use_mfma = !p->cfg.rec_exact;   // MF_RECOMMEND_IMPL=mfma (default) | exact
-	mf::RecArgs ex;
-	ex.users = p->uc;
-	ex.items = p->items;
-	ex.K = p->K;
-	ex.ldl = p->ldl;
-	ex.ldr = p->ldr;
-	ex.L = p->Lbuf[p->cur];
-	ex.R = p->Rbuf[p->cur];
-	ex.csr_ptr = p->csr_ptr;
-	ex.csr_idx = p->mask_idx ? p->mask_idx : p->csr_idx;
-	ex.best = p->best_dev;
-	ex.ulist = nullptr;
-	ex.cand = nullptr;
+	mf::RecArgs ex = exact_args(p, p->uc, nullptr, nullptr);
 	if (!use_mfma) {
 		const int grid = (p->uc + mf::kRT - 1) / mf::kRT;
 		hipLaunchKernelGGL(mf::recommend_kernel, dim3(grid), dim3(256), 0, p->stream, ex);
@@ -679,23 +443,11 @@ int mf_plan_recommend_scored(mf_plan *p, mf_candidate *out)
 	if (!p->have_factors) return MF_ERR_STATE;
 	MF_HIP(hipSetDevice(p->device));
 	if (p->uc == 0) return MF_OK;
-	if (!p->cand_dev) {
-		const int rc = dev_alloc(&p->cand_dev, (size_t) p->uc);
+	{
+		const int rc = p->cand_dev.grow((size_t) p->uc);
 		if (rc != MF_OK) return rc;
 	}
-	mf::RecArgs ex;
-	ex.users = p->uc;
-	ex.items = p->items;
-	ex.K = p->K;
-	ex.ldl = p->ldl;
-	ex.ldr = p->ldr;
-	ex.L = p->Lbuf[p->cur];
-	ex.R = p->Rbuf[p->cur];
-	ex.csr_ptr = p->csr_ptr;
-	ex.csr_idx = p->mask_idx ? p->mask_idx : p->csr_idx;
-	ex.best = p->best_dev;
-	ex.ulist = nullptr;
-	ex.cand = p->cand_dev;
+	const mf::RecArgs ex = exact_args(p, p->uc, nullptr, p->cand_dev);
 	hipLaunchKernelGGL(mf::recommend_kernel, dim3((p->uc + mf::kRT - 1) / mf::kRT), dim3(256), 0, p->stream, ex);
 	MF_HIP(hipGetLastError());
 	MF_HIP(hipMemcpyAsync(out, p->cand_dev, (size_t) p->uc * sizeof(mf_candidate), hipMemcpyDeviceToHost, p->stream));
@@ -711,29 +463,17 @@ int mf_plan_recommend_scored_users(mf_plan *p, const int32_t *users, int32_t n, 
 		if (users[t] < 0 || users[t] >= p->uc) return MF_ERR_ARGUMENT;
 	MF_HIP(hipSetDevice(p->device));
 	if (n == 0) return MF_OK;
-	if (!p->cand_dev) {
-		const int rc = dev_alloc(&p->cand_dev, (size_t) p->uc);
+	{
+		const int rc = p->cand_dev.grow((size_t) p->uc);
 		if (rc != MF_OK) return rc;
 	}
 	MF_HIP(hipMemcpyAsync(p->ulist, users, (size_t) n * sizeof(int), hipMemcpyHostToDevice, p->stream));
-	mf::RecArgs ex;
-	ex.users = n;
-	ex.items = p->items;
-	ex.K = p->K;
-	ex.ldl = p->ldl;
-	ex.ldr = p->ldr;
-	ex.L = p->Lbuf[p->cur];
-	ex.R = p->Rbuf[p->cur];
-	ex.csr_ptr = p->csr_ptr;
-	ex.csr_idx = p->mask_idx ? p->mask_idx : p->csr_idx;
-	ex.best = p->best_dev;
-	ex.ulist = p->ulist;
-	ex.cand = p->cand_dev;   // written at the user's own index
+	const mf::RecArgs ex = exact_args(p, n, p->ulist, p->cand_dev);   // cand is written at the user's own index
 	hipLaunchKernelGGL(mf::recommend_kernel, dim3((n + mf::kRT - 1) / mf::kRT), dim3(256), 0, p->stream, ex);
 	MF_HIP(hipGetLastError());
 	// only the n requested records travel: packed on the device in list order
-	if (!p->cand_pack) {
-		const int rc = dev_alloc(&p->cand_pack, (size_t) p->uc);
+	{
+		const int rc = p->cand_pack.grow((size_t) p->uc);
 		if (rc != MF_OK) return rc;
 	}
 	hipLaunchKernelGGL(mf::pack_candidates_kernel, dim3((n + 255) / 256), dim3(256), 0, p->stream, p->cand_dev, p->ulist,
@@ -753,11 +493,8 @@ int mf_plan_recommend_filter(mf_plan *p, mf_filter *out, double *norm, double *r
 	MF_HIP(hipSetDevice(p->device));
 	*rmax = 0.0;
 	if (p->uc == 0) return MF_OK;
-	if (!p->filt_dev) {
-		const int rc = dev_alloc(&p->filt_dev, (size_t) p->uc);
-		if (rc != MF_OK) return rc;
-	}
-	const int rc = launch_recommend_pass1(p, p->filt_dev);
+	int rc = p->filt_dev.grow((size_t) p->uc);
+	if (rc == MF_OK) rc = launch_recommend_pass1(p, p->filt_dev);
 	if (rc != MF_OK) return rc;
 	unsigned long long bits = 0;
 	MF_HIP(hipMemcpyAsync(out, p->filt_dev, (size_t) p->uc * sizeof(mf_filter), hipMemcpyDeviceToHost, p->stream));
@@ -774,245 +511,6 @@ int mf_plan_recommend_info(mf_plan *p, int64_t *exact_pass_users)
 	*exact_pass_users = p->last_uncertain;
 	return MF_OK;
 }
-
-}   // extern "C"
-
-// Grows a cached device buffer to at least `count` elements (contents are not kept).
-template <typename T>
-static int topn_grow(T **buf, size_t *cap, size_t count)
-{
-	if (*cap >= count) return MF_OK;
-	(void) hipFree(*buf);
-	*buf = nullptr;
-	*cap = 0;
-	const int rc = dev_alloc(buf, count);
-	if (rc == MF_OK) *cap = count;
-	return rc;
-}
-
-// Top-N on the device: rows of n items / scores per row of the operands' L in o.out->items / scores (nothing copied
-// back).  Matrix-core pass (topn_mfma_kernel) with certification and exact re-scoring of the members, the exact pass
-// (topn_exact_kernel) for every row it cannot decide; the exact pass for all rows under MF_RECOMMEND_IMPL=exact or
-// when K has no matrix-core form.  The plan gives the device, the stream, K and the environment switches only: what is
-// ranked against what, under which mask and into which buffers is the operands' (mf_plan_recommend_topn: the users
-// against the items under the rated mask; mf_plan_similar_items: items against items under the self mask).
-static int launch_topn_core(mf_plan *p, const topn_operands &o, int n)
-{
-	MF_HIP(hipSetDevice(p->device));
-	topn_buffers &b = *o.out;
-	{
-		const size_t need = (size_t) o.rows * (size_t) n;
-		size_t cap_s = b.cap;
-		int rc = topn_grow(&b.items, &b.cap, need);
-		if (rc == MF_OK) rc = topn_grow(&b.scores, &cap_s, need);
-		if (rc != MF_OK) {
-			(void) hipFree(b.scores);
-			b.scores = nullptr;
-			(void) hipFree(b.items);
-			b.items = nullptr;
-			b.cap = 0;
-			return rc;
-		}
-	}
-	mf::TopnArgs a;
-	memset(&a, 0, sizeof a);
-	a.users = o.rows;
-	a.items = o.items;
-	a.K = p->K;
-	a.ldl = o.ldl;
-	a.ldr = o.ldr;
-	a.L = o.L;
-	a.R = o.R;
-	a.csr_ptr = o.mask_ptr;
-	a.csr_idx = o.mask_idx;
-	a.lnorm = o.lnorm;
-	a.rnorm_max_bits = o.rmax_bits;
-	a.thr_scale = mf_backend_recommend_margin(p->K);
-	a.n = n;
-	a.out_items = b.items;
-	a.out_scores = b.scores;
-	a.olist = o.ulist;
-	a.ocount = o.ucount;
-
-	// the matrix-core shapes of recommend_mfma2_kernel: K = 20 NC <= 100, 16 NC <= 96 (four waves), 112, 128, 256 (eight waves)
-	typedef void (*TopnFn)(mf::TopnArgs);
-	const int K = p->K;
-	const bool fits32 = (unsigned long long) o.items * (unsigned long long) o.ldr * 8ull < (1ull << 32);   // 32-bit row offsets
-	TopnFn fn = nullptr;
-	int qc = 0, waves = 4;
-	if (!p->cfg.rec_exact && fits32 && o.items > 0) {
-		if (K % 20 == 0 && K <= 100) {
-			static const TopnFn f20[5] = {mf::topn_mfma_kernel<1>, mf::topn_mfma_kernel<2>, mf::topn_mfma_kernel<3>,
-			                              mf::topn_mfma_kernel<4>, mf::topn_mfma_kernel<5>};
-			fn = f20[K / 20 - 1];
-			qc = 5;
-		} else if (K % 16 == 0 && K <= 96) {
-			static const TopnFn f16[6] = {mf::topn_mfma_kernel<1, 4>, mf::topn_mfma_kernel<2, 4>, mf::topn_mfma_kernel<3, 4>,
-			                              mf::topn_mfma_kernel<4, 4>, mf::topn_mfma_kernel<5, 4>, mf::topn_mfma_kernel<6, 4>};
-			fn = f16[K / 16 - 1];
-			qc = 4;
-		} else if (K == 112) {   // at 32 users per wave K = 112 and 128 spill (the list walk beside 224 / 256 VGPRs of L operand):
-			fn = mf::topn_mfma_kernel<7, 4, 1, 8>;   // 16 users per wave, eight waves, as K = 256
-			qc = 4;
-			waves = 8;
-		} else if (K == 128) {
-			fn = mf::topn_mfma_kernel<4, 8, 1, 8>;
-			qc = 8;
-			waves = 8;
-		} else if (K == 256) {
-			fn = mf::topn_mfma_kernel<8, 8, 1, 8>;
-			qc = 8;
-			waves = 8;
-		}
-	}
-	if (!fn) {
-		hipLaunchKernelGGL(mf::topn_exact_kernel, dim3(o.rows), dim3(64), 0, p->stream, a);
-		MF_HIP(hipGetLastError());
-		b.last_uncertain = -1;
-		b.form = 0;
-		return MF_OK;
-	}
-
-	MF_HIP(hipMemsetAsync(o.rmax_bits, 0, sizeof(unsigned long long), p->stream));
-	MF_HIP(hipMemsetAsync(o.ucount, 0, sizeof(int), p->stream));
-	hipLaunchKernelGGL(mf::row_norm_kernel, dim3((o.rows + 63) / 64), dim3(64), 0, p->stream, a.L, o.rows, p->K, o.ldl, o.lnorm,
-	                   (unsigned long long *) nullptr);
-	hipLaunchKernelGGL(mf::row_norm_kernel, dim3((o.items + 63) / 64), dim3(64), 0, p->stream, a.R, o.items, p->K, o.ldr,
-	                   (double *) nullptr, o.rmax_bits);
-#ifdef MF_REC_TOPNGL
-	const size_t lds = mf::rec_mfma2_lds(qc);
-#else
-	const size_t lds = mf::rec_mfma2_lds(qc) + mf::topn_list_lds(n);
-#endif
-	MF_HIP(raise_lds_limit((const void *) fn, lds));
-	// two four-wave workgroups per CU while ring + lists + the static arrays (< 3 KB) fit half of the CU's 160 KB
-	const bool two_per_cu = waves == 4 && lds + 3 * 1024 <= 80 * 1024;
-	b.form = two_per_cu ? 1 : 2;
-
-	// item split of small problems: the rule and MF_RECOMMEND_SPLIT of the top-1 pass
-	const int ublocks = (o.rows + mf::kHU - 1) / mf::kHU, tiles = (o.items + mf::kMI - 1) / mf::kMI;
-	const int chip = two_per_cu ? 1024 : 512;
-	int nsplit = 1;
-	if (p->cfg.rec_split != 0 && ublocks < chip * 3 / 8 && tiles >= 2) {
-		nsplit = p->cfg.rec_split > 0 ? p->cfg.rec_split : (chip + ublocks - 1) / ublocks;
-		nsplit = std::max(1, std::min(nsplit, tiles));
-	}
-	if (nsplit > 1) {
-		const int tiles_per = (tiles + nsplit - 1) / nsplit;
-		nsplit = (tiles + tiles_per - 1) / tiles_per;
-		a.split_items = tiles_per * mf::kMI;
-		a.nsplit = nsplit;
-		const size_t nl = (size_t) o.rows * (size_t) (nsplit + 1) * (size_t) (n + 1);
-		size_t cap_i = b.part_cap;
-		int rc = topn_grow(&b.part_v, &b.part_cap, nl);
-		if (rc == MF_OK) rc = topn_grow(&b.part_i, &cap_i, nl);
-		if (rc == MF_OK) rc = topn_grow(&b.part_bad, &b.bad_cap, (size_t) o.rows * (size_t) nsplit);
-		if (rc != MF_OK) {
-			(void) hipFree(b.part_v);
-			(void) hipFree(b.part_i);
-			b.part_v = nullptr;
-			b.part_i = nullptr;
-			b.part_cap = 0;
-			return rc;
-		}
-		a.part_v = b.part_v;
-		a.part_i = b.part_i;
-		a.part_bad = b.part_bad;
-	}
-#ifdef MF_REC_TOPNGL
-	{   // timing build: the lists of every workgroup in global memory (freed with the plan's other top-N buffers)
-		const size_t ng = (size_t) ublocks * (size_t) nsplit * (size_t) mf::kHU * 2 * (size_t) (n + 1);
-		size_t cap_i = b.glist_cap;
-		int rc = topn_grow(&b.glist_v, &b.glist_cap, ng);
-		if (rc == MF_OK) rc = topn_grow(&b.glist_i, &cap_i, ng);
-		if (rc != MF_OK) return rc;
-		a.glist_v = b.glist_v;
-		a.glist_i = b.glist_i;
-	}
-#endif
-	hipLaunchKernelGGL(fn, dim3(ublocks, nsplit), dim3(64 * waves), lds, p->stream, a);
-	MF_HIP(hipGetLastError());
-	if (nsplit > 1) {
-		hipLaunchKernelGGL(mf::topn_merge_kernel, dim3((o.rows + 255) / 256), dim3(256), 0, p->stream, a);
-		MF_HIP(hipGetLastError());
-	}
-	int cnt = 0;
-	MF_HIP(hipMemcpyAsync(&cnt, o.ucount, sizeof(int), hipMemcpyDeviceToHost, p->stream));
-	MF_HIP(hipStreamSynchronize(p->stream));
-	b.last_uncertain = cnt;
-	if (cnt > 0) {
-		a.ulist = o.ulist;
-		hipLaunchKernelGGL(mf::topn_exact_kernel, dim3(cnt), dim3(64), 0, p->stream, a);
-		MF_HIP(hipGetLastError());
-	}
-	return MF_OK;
-}
-
-// mf_plan_recommend_topn's operands: this shard's users against the items under the rated mask
-static int launch_topn(mf_plan *p, int n)
-{
-	topn_operands o;
-	o.rows = p->uc;
-	o.items = p->items;
-	o.L = p->Lbuf[p->cur];
-	o.R = p->Rbuf[p->cur];
-	o.ldl = p->ldl;
-	o.ldr = p->ldr;
-	o.mask_ptr = p->csr_ptr;
-	o.mask_idx = p->mask_idx ? p->mask_idx : p->csr_idx;
-	o.lnorm = p->lnorm;
-	o.rmax_bits = p->rmax_bits;
-	o.ulist = p->ulist;
-	o.ucount = p->ucount;
-	o.out = &p->topn;
-	return launch_topn_core(p, o, n);
-}
-
-// mf_plan_similar_items on the device: Q (cosine: similar_normalize_kernel into the plan's buffer; dot: R itself), the
-// self mask and, for a listed query, the gathered rows (similar_gather_kernel), then the top-N pass on those operands.
-// Rows of n items / scores per query in p->sim.items / p->sim.scores.
-static int launch_similar(mf_plan *p, int metric, const int32_t *query, int nq, int n)
-{
-	MF_HIP(hipSetDevice(p->device));
-	const double *Q = p->Rbuf[p->cur];
-	if (metric == MF_SIMILAR_COSINE) {
-		const int rc = topn_grow(&p->sim_q, &p->sim_q_cap, (size_t) p->items * (size_t) p->ldr);
-		if (rc != MF_OK) return rc;
-		hipLaunchKernelGGL(mf::similar_normalize_kernel, dim3((p->items + mf::kSimRows - 1) / mf::kSimRows), dim3(mf::kSimThreads), 0,
-		                   p->stream, p->Rbuf[p->cur], p->items, p->K, p->ldr, p->sim_q);
-		MF_HIP(hipGetLastError());
-		Q = p->sim_q;
-	}
-	const int ldb = row_pitch(p->cfg, p->K, p->sweep.dma != 0);   // the pitch the plan gives an L buffer of its own
-	int rc = topn_grow(&p->sim_ptr, &p->sim_ptr_cap, (size_t) nq + 1);
-	if (rc == MF_OK) rc = topn_grow(&p->sim_idx, &p->sim_idx_cap, (size_t) nq);
-	if (rc == MF_OK) rc = topn_grow(&p->sim_lnorm, &p->sim_lnorm_cap, (size_t) nq);
-	if (rc == MF_OK) rc = topn_grow(&p->sim_ulist, &p->sim_ulist_cap, (size_t) nq);
-	if (rc == MF_OK && query) rc = topn_grow(&p->sim_query, &p->sim_query_cap, (size_t) nq);
-	if (rc == MF_OK && query) rc = topn_grow(&p->sim_block, &p->sim_block_cap, (size_t) nq * (size_t) ldb);
-	if (rc != MF_OK) return rc;
-	if (query) MF_HIP(hipMemcpyAsync(p->sim_query, query, (size_t) nq * sizeof(int32_t), hipMemcpyHostToDevice, p->stream));
-	hipLaunchKernelGGL(mf::similar_gather_kernel, dim3((nq + 63) / 64), dim3(64), 0, p->stream, Q, p->ldr, p->K,
-	                   query ? p->sim_query : (const int *) nullptr, nq, p->sim_block, ldb, p->sim_ptr, p->sim_idx);
-	MF_HIP(hipGetLastError());
-	topn_operands o;
-	o.rows = nq;
-	o.items = p->items;
-	o.L = query ? p->sim_block : Q;
-	o.R = Q;
-	o.ldl = query ? ldb : p->ldr;
-	o.ldr = p->ldr;
-	o.mask_ptr = p->sim_ptr;
-	o.mask_idx = p->sim_idx;
-	o.lnorm = p->sim_lnorm;
-	o.rmax_bits = p->rmax_bits;   // one word each, reset by every pass that uses them
-	o.ulist = p->sim_ulist;
-	o.ucount = p->ucount;
-	o.out = &p->sim;
-	return launch_topn_core(p, o, n);
-}
-
-extern "C" {
 
 int mf_plan_recommend_topn(mf_plan *p, int32_t n, int32_t *items, double *scores)
 {
@@ -1089,14 +587,16 @@ int mf_plan_predict(mf_plan *p, double *B)
 	if (n > ((size_t) 1 << 26)) return MF_ERR_UNSUPPORTED;
 	if (n == 0) return MF_OK;
 	MF_HIP(hipSetDevice(p->device));
-	double *dB = nullptr;
-	MF_HIP(hipMalloc((void **) &dB, n * sizeof(double)));
+	dev_buf<double> dB;
+	{
+		const int rc = dB.alloc(n);
+		if (rc != MF_OK) return rc;
+	}
 	hipLaunchKernelGGL(mf::predict_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, p->stream,
 	                   p->Lbuf[p->cur], p->Rbuf[p->cur], p->uc, p->items, p->K, p->ldl, p->ldr, dB);
 	hipError_t e = hipGetLastError();
 	if (e == hipSuccess) e = hipMemcpyAsync(B, dB, n * sizeof(double), hipMemcpyDeviceToHost, p->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-	(void) hipFree(dB);
 	if (e != hipSuccess) {
 		g_last_hip_error = std::string("mf_plan_predict: ") + hipGetErrorString(e);
 		return MF_ERR_HIP;
@@ -1175,6 +675,8 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 	return MF_OK;
 }
 
+}   // extern "C"
+
 /* ---------------------------------------------------------------------------------------- LEVEL 1 */
 
 static int make_single_plan(const mf_problem *pr, int device, mf_plan **out)
@@ -1195,31 +697,40 @@ static int make_single_plan(const mf_problem *pr, int device, mf_plan **out)
 	return plan_create_impl(out, &s, pr->entries);
 }
 
-int mf_backend_run(const mf_problem *pr, double *L, double *R, int32_t *best, int device)
+// The level-1 sequence: a plan over the whole problem, the factors up, `work(plan)`, the plan destroyed.  Every entry
+// point checks its own arguments first.
+template <class Work>
+static int with_single_plan(const mf_problem *pr, int device, const double *L, const double *R, Work work)
 {
-	if (!pr || !L || !R) return MF_ERR_ARGUMENT;   // L and R carry the initial factors in
 	mf_plan *p = nullptr;
 	int rc = make_single_plan(pr, device, &p);
 	if (rc != MF_OK) return rc;
 	rc = mf_plan_upload_factors(p, L, R);
-	if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
-	if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
-	if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
+	if (rc == MF_OK) rc = work(p);
 	mf_plan_destroy(p);
 	return rc;
+}
+
+extern "C" {
+
+int mf_backend_run(const mf_problem *pr, double *L, double *R, int32_t *best, int device)
+{
+	if (!pr || !L || !R) return MF_ERR_ARGUMENT;   // L and R carry the initial factors in
+	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
+		int rc = mf_plan_iterate(p, pr->iters);
+		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
+		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
+		return rc;
+	});
 }
 
 int mf_backend_run_top1(const mf_problem *pr, const double *L0, const double *R0, int32_t *best, int device)
 {
 	if (!pr || !L0 || !R0 || (!best && pr->users > 0)) return MF_ERR_ARGUMENT;
-	mf_plan *p = nullptr;
-	int rc = make_single_plan(pr, device, &p);
-	if (rc != MF_OK) return rc;
-	rc = mf_plan_upload_factors(p, L0, R0);
-	if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
-	if (rc == MF_OK) rc = mf_plan_recommend(p, best);
-	mf_plan_destroy(p);
-	return rc;
+	return with_single_plan(pr, device, L0, R0, [&](mf_plan *p) {
+		const int rc = mf_plan_iterate(p, pr->iters);
+		return rc == MF_OK ? mf_plan_recommend(p, best) : rc;
+	});
 }
 
 int mf_backend_run_topn(const mf_problem *pr, const double *L0, const double *R0, int32_t n, int32_t *items, double *scores,
@@ -1227,14 +738,10 @@ int mf_backend_run_topn(const mf_problem *pr, const double *L0, const double *R0
 {
 	if (!pr || !L0 || !R0 || n < 1 || !items) return MF_ERR_ARGUMENT;
 	if (n > MF_TOPN_MAX) return MF_ERR_UNSUPPORTED;
-	mf_plan *p = nullptr;
-	int rc = make_single_plan(pr, device, &p);
-	if (rc != MF_OK) return rc;
-	rc = mf_plan_upload_factors(p, L0, R0);
-	if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
-	if (rc == MF_OK) rc = mf_plan_recommend_topn(p, n, items, scores);
-	mf_plan_destroy(p);
-	return rc;
+	return with_single_plan(pr, device, L0, R0, [&](mf_plan *p) {
+		const int rc = mf_plan_iterate(p, pr->iters);
+		return rc == MF_OK ? mf_plan_recommend_topn(p, n, items, scores) : rc;
+	});
 }
 
 int mf_backend_recommend_topn(const mf_problem *pr, const double *L, const double *R, int32_t n, int32_t *items,
@@ -1242,13 +749,7 @@ int mf_backend_recommend_topn(const mf_problem *pr, const double *L, const doubl
 {
 	if (!pr || !L || !R || n < 1 || !items) return MF_ERR_ARGUMENT;
 	if (n > MF_TOPN_MAX) return MF_ERR_UNSUPPORTED;
-	mf_plan *p = nullptr;
-	int rc = make_single_plan(pr, device, &p);
-	if (rc != MF_OK) return rc;
-	rc = mf_plan_upload_factors(p, L, R);
-	if (rc == MF_OK) rc = mf_plan_recommend_topn(p, n, items, scores);
-	mf_plan_destroy(p);
-	return rc;
+	return with_single_plan(pr, device, L, R, [&](mf_plan *p) { return mf_plan_recommend_topn(p, n, items, scores); });
 }
 
 int mf_backend_similar_items(const double *R, int32_t items, int32_t features, int metric, const int32_t *query, int32_t nq,
@@ -1276,201 +777,6 @@ int mf_backend_similar_items(const double *R, int32_t items, int32_t features, i
 
 }   // extern "C"
 
-/* ---------------------------------------------------------------------------------------- LOSS (mf_loss.hip.h) */
-
-// Row sums of one entry set (CSR over the plan's users) into p->row_sse, then the block sums and the total, all on the
-// plan's stream.  `order`: optional list of all rows in the order the workgroups take them.
-static int launch_loss(mf_plan *p, const int *ptr, const int *idx, const double *val, const int *order)
-{
-	const int nblocks = p->uc > 0 ? (int) (((long long) p->u0 + p->uc - 1) / mf::kLossBlock - p->u0 / mf::kLossBlock + 1) : 0;
-	if (!p->row_sse) {
-		int rc = dev_alloc(&p->row_sse, (size_t) p->uc);
-		if (rc == MF_OK) rc = dev_alloc(&p->loss_blocks, (size_t) nblocks);
-		if (rc == MF_OK) rc = dev_alloc(&p->loss_total, 1);
-		if (rc != MF_OK) {
-			(void) hipFree(p->row_sse);
-			(void) hipFree(p->loss_blocks);
-			p->row_sse = p->loss_blocks = nullptr;
-			return rc;
-		}
-	}
-	if (p->uc > 0) {
-		mf::LossArgs a;
-		a.nrows = p->uc;
-		a.K = p->K;
-		a.stride = p->stride;
-		a.ldl = p->ldl;
-		a.ldr = p->ldr;
-		a.ptr = ptr;
-		a.idx = idx;
-		a.val = val;
-		a.L = p->Lbuf[p->cur];
-		a.R = p->Rbuf[p->cur];
-		a.row_sse = p->row_sse;
-		a.rowlist = order;
-		const int few = a.nrows < p->cfg.sweep_few ? 1 : 0;
-		a.nch = p->loss_nch[few];
-		void *args[] = {&a};
-		MF_HIP(hipLaunchKernel((const void *) p->loss_fn, dim3(std::min(a.nrows, 1 << 20)), dim3(mf::kWave), args, p->loss_lds[few],
-		                       p->stream));
-		hipLaunchKernelGGL(mf::loss_block_kernel, dim3(nblocks), dim3(mf::kWave), 0, p->stream, p->row_sse, p->u0, p->uc, nblocks,
-		                   p->loss_blocks);
-		MF_HIP(hipGetLastError());
-	}
-	hipLaunchKernelGGL(mf::loss_total_kernel, dim3(1), dim3(mf::kWave), 0, p->stream, p->loss_blocks, nblocks, p->loss_total);
-	MF_HIP(hipGetLastError());
-	return MF_OK;
-}
-
-
-// One evaluation: launches, the total (and the row sums when asked for) back to the host, complete on return.
-static int loss_eval(mf_plan *p, int which, mf_loss *out, double *row_sse)
-{
-	MF_HIP(hipSetDevice(p->device));
-	const bool train = which == MF_LOSS_TRAIN;
-	const int rc = train ? launch_loss(p, p->csr_ptr, p->csr_idx, p->csr_val, p->lpt[1] ? p->short_rows[1] : nullptr)
-	                     : launch_loss(p, p->ho_ptr, p->ho_idx, p->ho_val, nullptr);
-	if (rc != MF_OK) return rc;
-	double sse = 0.0;
-	MF_HIP(hipMemcpyAsync(&sse, p->loss_total, sizeof(double), hipMemcpyDeviceToHost, p->stream));
-	if (row_sse && p->uc > 0)
-		MF_HIP(hipMemcpyAsync(row_sse, p->row_sse, (size_t) p->uc * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-	MF_HIP(hipStreamSynchronize(p->stream));
-	out->sse = sse;
-	out->count = train ? p->nnz : p->ho_nnz;
-	return MF_OK;
-}
-
-/* ---------------------------------------------------------------------------------------- RANKS (mf_rank.hip.h) */
-
-// Ranks of the held-out entries on the device, in the plan's bucketed order, in p->rank_out (nothing copied back).
-// Thresholds (rank_threshold_kernel), the matrix-core counting pass with launch_topn's shapes, LDS limit, two-per-CU and
-// split rules (rank_mfma_kernel), certification (rank_finish_kernel) and the exact pass (rank_exact_kernel) for the
-// entries it cannot decide; the exact pass for all entries under MF_RECOMMEND_IMPL=exact, when K has no matrix-core form
-// or when R exceeds 32-bit row offsets.
-static int launch_rank(mf_plan *p)
-{
-	MF_HIP(hipSetDevice(p->device));
-	const size_t n = (size_t) p->ho_nnz;
-	if (p->rank_cap < n) {
-		size_t c1 = p->rank_cap, c2 = p->rank_cap, c3 = p->rank_cap, c4 = p->rank_cap, c5 = p->rank_cap;
-		int rc = topn_grow(&p->rank_score, &c1, n);
-		if (rc == MF_OK) rc = topn_grow(&p->rank_state, &c2, n);
-		if (rc == MF_OK) rc = topn_grow(&p->rank_out, &c3, n);
-		if (rc == MF_OK) rc = topn_grow(&p->rank_above, &c4, n);
-		if (rc == MF_OK) rc = topn_grow(&p->rank_band, &c5, n);
-		if (rc == MF_OK) rc = topn_grow(&p->rank_list, &p->rank_cap, n);
-		if (rc != MF_OK) {
-			p->rank_cap = 0;   // the next call allocates all six again
-			return rc;
-		}
-	}
-	mf::RankArgs a;
-	memset(&a, 0, sizeof a);
-	a.rows = (int) n;
-	a.items = p->items;
-	a.K = p->K;
-	a.ldl = p->ldl;
-	a.ldr = p->ldr;
-	a.L = p->Lbuf[p->cur];
-	a.R = p->Rbuf[p->cur];
-	a.csr_ptr = p->csr_ptr;
-	a.csr_idx = p->mask_idx ? p->mask_idx : p->csr_idx;
-	a.ent_user = p->ho_user;
-	a.ent_item = p->ho_idx;
-	a.lnorm = p->lnorm;
-	a.rnorm_max_bits = p->rmax_bits;
-	a.thr_scale = mf_backend_recommend_margin(p->K);
-	a.score = p->rank_score;
-	a.state = p->rank_state;
-	a.rank = p->rank_out;
-	a.above = p->rank_above;
-	a.band = p->rank_band;
-	a.olist = p->rank_list;
-	a.ocount = p->ucount;
-	const unsigned eblocks = (unsigned) ((n + 255) / 256);
-	hipLaunchKernelGGL(mf::rank_threshold_kernel, dim3(eblocks), dim3(256), 0, p->stream, a);
-	MF_HIP(hipGetLastError());
-
-	typedef void (*RankFn)(mf::RankArgs);
-	const int K = p->K;
-	const bool fits32 = (unsigned long long) p->items * (unsigned long long) p->ldr * 8ull < (1ull << 32);   // 32-bit row offsets
-	RankFn fn = nullptr;
-	int qc = 0, waves = 4;
-	if (!p->cfg.rec_exact && fits32) {
-		if (K % 20 == 0 && K <= 100) {
-			static const RankFn f20[5] = {mf::rank_mfma_kernel<1>, mf::rank_mfma_kernel<2>, mf::rank_mfma_kernel<3>,
-			                              mf::rank_mfma_kernel<4>, mf::rank_mfma_kernel<5>};
-			fn = f20[K / 20 - 1];
-			qc = 5;
-		} else if (K % 16 == 0 && K <= 96) {
-			static const RankFn f16[6] = {mf::rank_mfma_kernel<1, 4>, mf::rank_mfma_kernel<2, 4>, mf::rank_mfma_kernel<3, 4>,
-			                              mf::rank_mfma_kernel<4, 4>, mf::rank_mfma_kernel<5, 4>, mf::rank_mfma_kernel<6, 4>};
-			fn = f16[K / 16 - 1];
-			qc = 4;
-		} else if (K == 112) {
-			fn = mf::rank_mfma_kernel<7, 4, 1, 8>;
-			qc = 4;
-			waves = 8;
-		} else if (K == 128) {
-			fn = mf::rank_mfma_kernel<4, 8, 1, 8>;
-			qc = 8;
-			waves = 8;
-		} else if (K == 256) {
-			fn = mf::rank_mfma_kernel<8, 8, 1, 8>;
-			qc = 8;
-			waves = 8;
-		}
-	}
-	if (!fn) {
-		hipLaunchKernelGGL(mf::rank_exact_kernel, dim3((unsigned) n), dim3(64), 0, p->stream, a);
-		MF_HIP(hipGetLastError());
-		p->last_rank_uncertain = -1;
-		p->rank_form = 0;
-		return MF_OK;
-	}
-
-	MF_HIP(hipMemsetAsync(p->rmax_bits, 0, sizeof(unsigned long long), p->stream));
-	MF_HIP(hipMemsetAsync(p->ucount, 0, sizeof(int), p->stream));
-	hipLaunchKernelGGL(mf::row_norm_kernel, dim3((p->uc + 63) / 64), dim3(64), 0, p->stream, a.L, p->uc, p->K, p->ldl, p->lnorm,
-	                   (unsigned long long *) nullptr);
-	hipLaunchKernelGGL(mf::row_norm_kernel, dim3((p->items + 63) / 64), dim3(64), 0, p->stream, a.R, p->items, p->K, p->ldr,
-	                   (double *) nullptr, p->rmax_bits);
-	const size_t lds = mf::rec_mfma2_lds(qc);
-	MF_HIP(raise_lds_limit((const void *) fn, lds));
-	// two four-wave workgroups per CU while the ring + the static arrays (< 4 KB) fit half of the CU's 160 KB
-	const bool two_per_cu = waves == 4 && lds + 4 * 1024 <= 80 * 1024;
-	p->rank_form = two_per_cu ? 1 : 2;
-
-	// item split of small problems: the rule and MF_RECOMMEND_SPLIT of the top-1 pass, over blocks of 64 entries
-	const int rblocks = (int) ((n + mf::kHU - 1) / mf::kHU), tiles = (p->items + mf::kMI - 1) / mf::kMI;
-	const int chip = two_per_cu ? 1024 : 512;
-	int nsplit = 1;
-	if (p->cfg.rec_split != 0 && rblocks < chip * 3 / 8 && tiles >= 2) {
-		nsplit = p->cfg.rec_split > 0 ? p->cfg.rec_split : (chip + rblocks - 1) / rblocks;
-		nsplit = std::max(1, std::min(nsplit, tiles));
-	}
-	if (nsplit > 1) {
-		const int tiles_per = (tiles + nsplit - 1) / nsplit;
-		nsplit = (tiles + tiles_per - 1) / tiles_per;
-		a.split_items = tiles_per * mf::kMI;
-	}
-	hipLaunchKernelGGL(fn, dim3(rblocks, nsplit), dim3(64 * waves), lds, p->stream, a);
-	MF_HIP(hipGetLastError());
-	hipLaunchKernelGGL(mf::rank_finish_kernel, dim3(eblocks), dim3(256), 0, p->stream, a);
-	MF_HIP(hipGetLastError());
-	int cnt = 0;
-	MF_HIP(hipMemcpyAsync(&cnt, p->ucount, sizeof(int), hipMemcpyDeviceToHost, p->stream));
-	MF_HIP(hipStreamSynchronize(p->stream));
-	p->last_rank_uncertain = cnt;
-	if (cnt > 0) {
-		a.elist = p->rank_list;
-		hipLaunchKernelGGL(mf::rank_exact_kernel, dim3(cnt), dim3(64), 0, p->stream, a);
-		MF_HIP(hipGetLastError());
-	}
-	return MF_OK;
-}
-
 static double loss_rmse(const mf_loss &l) { return l.count > 0 ? std::sqrt(l.sse / (double) l.count) : std::nan(""); }
 
 extern "C" {
@@ -1496,8 +802,8 @@ int mf_plan_set_heldout(mf_plan *p, int64_t n, const int32_t *row, const int32_t
 	for (int64_t i = 0; i < n; ++i)
 		if (row[i] < p->u0 || row[i] >= p->u0 + p->uc || col[i] < 0 || col[i] >= p->items) return MF_ERR_ARGUMENT;
 	MF_HIP(hipSetDevice(p->device));
-	int *nptr = nullptr, *nidx = nullptr, *nuser = nullptr;
-	double *nval = nullptr;
+	dev_buf<int> nptr, nidx, nuser;
+	dev_buf<double> nval;
 	std::vector<int> pos;   // bucketed position of the caller's entry n (mf_plan_rank_heldout reports in the caller's order)
 	if (n > 0) {
 		// stable counting sort by user on the host: the caller's order inside a user is the order of the row sum
@@ -1510,34 +816,25 @@ int mf_plan_set_heldout(mf_plan *p, int64_t n, const int32_t *row, const int32_t
 		} catch (const std::bad_alloc &) {
 			return MF_ERR_NO_MEMORY;
 		}
-		int rc = dev_alloc(&nptr, (size_t) p->uc + 1);
-		if (rc == MF_OK) rc = dev_alloc(&nidx, (size_t) n + 64);
-		if (rc == MF_OK) rc = dev_alloc(&nval, (size_t) n + 64);
-		if (rc == MF_OK) rc = dev_alloc(&nuser, (size_t) n);
-		hipError_t e = hipSuccess;
-		if (rc == MF_OK) e = h2d(p, nptr, ptr.data(), ptr.size() * sizeof(int));
-		if (rc == MF_OK && e == hipSuccess) e = h2d(p, nidx, idx.data(), idx.size() * sizeof(int));
-		if (rc == MF_OK && e == hipSuccess) e = h2d(p, nval, v.data(), v.size() * sizeof(double));
-		if (rc == MF_OK && e == hipSuccess) e = h2d(p, nuser, user.data(), user.size() * sizeof(int));
-		if (rc != MF_OK || e != hipSuccess) {
-			(void) hipFree(nptr);
-			(void) hipFree(nidx);
-			(void) hipFree(nval);
-			(void) hipFree(nuser);
-			if (rc != MF_OK) return rc;
+		int rc = nptr.alloc((size_t) p->uc + 1);
+		if (rc == MF_OK) rc = nidx.alloc((size_t) n + 64);
+		if (rc == MF_OK) rc = nval.alloc((size_t) n + 64);
+		if (rc == MF_OK) rc = nuser.alloc((size_t) n);
+		if (rc != MF_OK) return rc;
+		hipError_t e = h2d(p, nptr, ptr.data(), ptr.size() * sizeof(int));
+		if (e == hipSuccess) e = h2d(p, nidx, idx.data(), idx.size() * sizeof(int));
+		if (e == hipSuccess) e = h2d(p, nval, v.data(), v.size() * sizeof(double));
+		if (e == hipSuccess) e = h2d(p, nuser, user.data(), user.size() * sizeof(int));
+		if (e != hipSuccess) {
 			g_last_hip_error = std::string("mf_plan_set_heldout: ") + hipGetErrorString(e);
 			return e == hipErrorOutOfMemory ? MF_ERR_NO_MEMORY : MF_ERR_HIP;
 		}
 	}
 	MF_HIP(hipStreamSynchronize(p->stream));   // no launch still reads the set that is replaced
-	(void) hipFree(p->ho_ptr);
-	(void) hipFree(p->ho_idx);
-	(void) hipFree(p->ho_val);
-	(void) hipFree(p->ho_user);
-	p->ho_ptr = nptr;
-	p->ho_idx = nidx;
-	p->ho_val = nval;
-	p->ho_user = nuser;
+	p->ho_ptr = std::move(nptr);   // the set that is replaced is freed here
+	p->ho_idx = std::move(nidx);
+	p->ho_val = std::move(nval);
+	p->ho_user = std::move(nuser);
 	p->ho_pos.swap(pos);
 	p->ho_nnz = n;
 	p->have_heldout = n > 0;
@@ -1663,13 +960,7 @@ int mf_plan_iterate_monitored(mf_plan *p, int iters, int every, double tol, mf_l
 int mf_backend_loss(const mf_problem *pr, const double *L, const double *R, mf_loss *out, double *row_sse, int device)
 {
 	if (!pr || !L || !R || !out) return MF_ERR_ARGUMENT;
-	mf_plan *p = nullptr;
-	int rc = make_single_plan(pr, device, &p);
-	if (rc != MF_OK) return rc;
-	rc = mf_plan_upload_factors(p, L, R);
-	if (rc == MF_OK) rc = mf_plan_loss(p, MF_LOSS_TRAIN, out, row_sse);
-	mf_plan_destroy(p);
-	return rc;
+	return with_single_plan(pr, device, L, R, [&](mf_plan *p) { return mf_plan_loss(p, MF_LOSS_TRAIN, out, row_sse); });
 }
 
 int mf_backend_factorize(const mf_problem *pr, double *L, double *R, int device)
@@ -1680,13 +971,7 @@ int mf_backend_factorize(const mf_problem *pr, double *L, double *R, int device)
 int mf_backend_recommend(const mf_problem *pr, const double *L, const double *R, int32_t *best, int device)
 {
 	if (!pr || !L || !R || (!best && pr->users > 0)) return MF_ERR_ARGUMENT;
-	mf_plan *p = nullptr;
-	int rc = make_single_plan(pr, device, &p);
-	if (rc != MF_OK) return rc;
-	rc = mf_plan_upload_factors(p, L, R);
-	if (rc == MF_OK) rc = mf_plan_recommend(p, best);
-	mf_plan_destroy(p);
-	return rc;
+	return with_single_plan(pr, device, L, R, [&](mf_plan *p) { return mf_plan_recommend(p, best); });
 }
 
 #ifdef MF_OS_DIAG

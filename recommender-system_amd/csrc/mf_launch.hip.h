@@ -380,8 +380,8 @@ int launch_es_iteration(mf_plan *p)
 	a.seg_row = p->es_seg_row;
 	a.seg_beg = p->es_seg_beg;
 	a.seg_end = p->es_seg_end;
-	a.err_a = reinterpret_cast<double *>(p->rec_csr);
-	a.err_b = reinterpret_cast<double *>(p->rec_csc);
+	a.err_a = reinterpret_cast<double *>(p->rec_csr.get());
+	a.err_b = reinterpret_cast<double *>(p->rec_csc.get());
 	a.map = p->csr2csc;
 	mf::SliceArgs ra;
 	ra.K = p->K;

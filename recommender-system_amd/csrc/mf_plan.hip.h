@@ -1,18 +1,8 @@
-// mf_plan.hip.h -- error macro, kernel variant tables and the resident plan (struct mf_plan).
+// mf_plan.hip.h -- kernel variant tables, the buffers and operands of a top-N pass and the resident plan (struct mf_plan).
+// The plan owns its device memory through dev_buf members (mf_device.hip.h): deleting the plan frees it.
 #pragma once
 
 namespace {
-
-thread_local std::string g_last_hip_error;
-
-#define MF_HIP(call)                                                                        \
-	do {                                                                                    \
-		hipError_t _e = (call);                                                             \
-		if (_e != hipSuccess) {                                                             \
-			g_last_hip_error = std::string(#call) + ": " + hipGetErrorString(_e);           \
-			return _e == hipErrorOutOfMemory ? MF_ERR_NO_MEMORY : MF_ERR_HIP;               \
-		}                                                                                   \
-	} while (0)
 
 using SweepFn = void (*)(mf::SweepArgs);
 using LossFn = void (*)(mf::LossArgs);
@@ -126,22 +116,19 @@ struct TimedLaunch {
 	bool shared_start;   // t0 is the previous record's t1 (not owned)
 };
 
-// What a top-N pass (launch_topn_core, mf_hip.hip) writes and reports: the output rows (rows x n), the per-split lists of
+// What a top-N pass (launch_topn_core, mf_certified.hip.h) writes and reports: the output rows (rows x n), the per-split lists of
 // an item split, and the last call's exact-pass count and form.  All device buffers are allocated on first use and grown
 // on demand; one instance per entry point, so the report of one is not disturbed by a call of the other.
 struct topn_buffers {
-	int *items = nullptr;
-	double *scores = nullptr;
-	size_t cap = 0;                  // entries of items / scores
-	double *part_v = nullptr;
-	int *part_i = nullptr, *part_bad = nullptr;
-	size_t part_cap = 0, bad_cap = 0;
+	dev_buf<int> items;              // items / scores share a capacity, part_v / part_i another
+	dev_buf<double> scores;
+	dev_buf<double> part_v;
+	dev_buf<int> part_i, part_bad;
 	int64_t last_uncertain = -1;     // rows of the last call that went through the exact pass (-1: exact form ran)
 	int form = -1;                   // form of the last call (mf_plan_recommend_topn_info)
 #ifdef MF_REC_TOPNGL
-	double *glist_v = nullptr;       // timing build: the matrix-core pass's lists in global memory
-	int *glist_i = nullptr;
-	size_t glist_cap = 0;
+	dev_buf<double> glist_v;         // timing build: the matrix-core pass's lists in global memory
+	dev_buf<int> glist_i;
 #endif
 };
 
@@ -173,71 +160,69 @@ struct mf_plan {
 	hipStream_t stream = nullptr;
 
 	// CSR over the shard's users (idx = item id) and CSC over items (idx = LOCAL user id)
-	int *csr_ptr = nullptr, *csr_idx = nullptr;
-	double *csr_val = nullptr;
-	int *csc_ptr = nullptr, *csc_idx = nullptr;
-	double *csc_val = nullptr;
-	int *mask_idx = nullptr;   // item ids ascending inside every user's row, only when the file order is not (recommend mask)
+	dev_buf<int> csr_ptr, csr_idx;
+	dev_buf<double> csr_val;
+	dev_buf<int> csc_ptr, csc_idx;
+	dev_buf<double> csc_val;
+	dev_buf<int> mask_idx;   // item ids ascending inside every user's row, only when the file order is not (recommend mask)
 	// errors + streams iteration (mf_stream.hip.h): CSR position -> CSC position, the {idx, e_n} records in both orders, the segment table
 	// of the errors launch and the task list (both factors' rows, longest first) of the streams launch
 	bool want_map = false, es_mode = false;
-	int *csr2csc = nullptr;
-	mf::StreamRec *rec_csr = nullptr, *rec_csc = nullptr;
+	dev_buf<int> csr2csc;
+	dev_buf<mf::StreamRec> rec_csr, rec_csc;
 	int es_nseg = 0, es_nch = 0;
 	size_t es_lds_errors = 0;
-	int *es_seg_row = nullptr, *es_seg_beg = nullptr, *es_seg_end = nullptr;
+	dev_buf<int> es_seg_row, es_seg_beg, es_seg_end;
 	// streams launch with a column slice of Y resident in LDS (mf_resident.hip.h): small factor matrices only
 	int res_sw = 0, res_nwg = 0;
 	size_t res_lds = 0;
-	mf::SliceWg *res_wg = nullptr;
+	dev_buf<mf::SliceWg> res_wg;
 
-	double *Lbuf[2] = {nullptr, nullptr};
+	double *Lbuf[2] = {nullptr, nullptr};   // the two generations: the plan's own buffers or the caller's
 	double *Rbuf[2] = {nullptr, nullptr};
+	dev_buf<double> Lown[2], Rown[2];       // the plan's own, empty when l_external / r_external
 	int ldl = 0, ldr = 0;   // row pitch of the L and R buffers in doubles (K, or K padded to whole 128-byte lines)
 	bool r_external = false;
 	bool l_external = false;
 	bool join_pending = false;          // ordered sums of the last item sweep still run on the side stream
-	mf_candidate *cand_dev = nullptr;   // recommend_scored output, allocated on first use
-	mf_candidate *cand_pack = nullptr;  // the listed users' records in list order (recommend_scored_users)
-	mf_filter *filt_dev = nullptr;      // recommend_filter output, allocated on first use
-	mf_filter *part_dev = nullptr;      // per-split reports of a small recommendation (nsplit x users), allocated on first use
-	int part_cap = 0;
+	dev_buf<mf_candidate> cand_dev;     // recommend_scored output, allocated on first use
+	dev_buf<mf_candidate> cand_pack;    // the listed users' records in list order (recommend_scored_users)
+	dev_buf<mf_filter> filt_dev;        // recommend_filter output, allocated on first use
+	dev_buf<mf_filter> part_dev;        // per-split reports of a small recommendation (nsplit x users), grown on demand
 	bool rec_half_used = false;   // the last MFMA pass ran as 64-user workgroups, two per CU (recommend_mfma2_kernel)
 	int cur = 0;            // generation index of the current factors
 	bool have_factors = false;
-	int *best_dev = nullptr;
+	dev_buf<int> best_dev;
 	// MFMA recommend scratch
-	double *lnorm = nullptr;
-	unsigned long long *rmax_bits = nullptr;
-	int *ulist = nullptr, *ucount = nullptr;
+	dev_buf<double> lnorm;
+	dev_buf<unsigned long long> rmax_bits;
+	dev_buf<int> ulist, ucount;
 	int64_t last_uncertain = -1;   // users re-scored by the exact pass in the last recommend (-1: exact form ran)
 	// top-N (mf_plan_recommend_topn) and similar items (mf_plan_similar_items): each its own output rows, per-split lists
 	// and report of the last call
 	topn_buffers topn, sim;
 	// similar items, allocated on first use and grown on demand: Q (the rows of R divided by their norms, R's pitch), the
 	// gathered rows of a listed query with the device copy of the list, the self mask, and the pass's scratch by query row
-	double *sim_q = nullptr, *sim_block = nullptr, *sim_lnorm = nullptr;
-	int *sim_query = nullptr, *sim_ptr = nullptr, *sim_idx = nullptr, *sim_ulist = nullptr;
-	size_t sim_q_cap = 0, sim_block_cap = 0, sim_lnorm_cap = 0, sim_query_cap = 0, sim_ptr_cap = 0, sim_idx_cap = 0,
-	       sim_ulist_cap = 0;
+	dev_buf<double> sim_q, sim_block, sim_lnorm;
+	dev_buf<int> sim_query, sim_ptr, sim_idx, sim_ulist;
 
 	// loss (mf_plan_loss, mf_loss.hip.h): row sums, block sums and total, allocated on first use; the held-out set as a
 	// second CSR over the shard's users (entries of a user in the caller's order)
 	LossFn loss_fn = nullptr;
 	int loss_nch[2] = {0, 0};        // chunk size of the row-sum launch: [0] ordinary, [1] fewer rows than fill the chip
 	size_t loss_lds[2] = {0, 0};     // its LDS request (the L row + ONE tile)
-	double *row_sse = nullptr, *loss_blocks = nullptr, *loss_total = nullptr;
-	int *ho_ptr = nullptr, *ho_idx = nullptr;
-	double *ho_val = nullptr;
+	dev_buf<double> row_sse, loss_blocks, loss_total;
+	dev_buf<int> ho_ptr, ho_idx;
+	dev_buf<double> ho_val;
 	int64_t ho_nnz = 0;
 	bool have_heldout = false;
 	// ranks of the held-out entries (mf_plan_rank_heldout, mf_rank.hip.h): the local user of every bucketed entry, the
-	// bucketed position of every entry the caller gave (host), and the pass's buffers, allocated on first use per set
-	int *ho_user = nullptr;
+	// bucketed position of every entry the caller gave (host), and the pass's six buffers, which share a capacity and grow
+	// on demand
+	dev_buf<int> ho_user;
 	std::vector<int> ho_pos;
-	double *rank_score = nullptr;
-	int *rank_state = nullptr, *rank_out = nullptr, *rank_above = nullptr, *rank_band = nullptr, *rank_list = nullptr;
-	size_t rank_cap = 0;                // entries of each of the six
+	dev_buf<double> rank_score;
+	dev_buf<int> rank_state, rank_out, rank_above, rank_band, rank_list;
 	int64_t last_rank_uncertain = -1;   // entries of the last rank call that went through the exact pass (-1: exact form ran)
 	int rank_form = -1;                 // form of the last rank call (mf_plan_rank_heldout_info)
 
@@ -261,7 +246,7 @@ struct mf_plan {
 	// double-buffered form with a LARGE chunk on a second side stream -- a wave that keeps 48 rows in flight gets a
 	// matching share of its CU's gather rate instead of 1/11 of it, so the walk of the longest remaining row no longer
 	// sets the sweep's time
-	int *mid_rows[2] = {nullptr, nullptr};
+	dev_buf<int> mid_rows[2];
 	int n_mid[2] = {0, 0};
 	int nch_mid = 0;
 	size_t lds_bytes_mid = 0;
@@ -272,16 +257,16 @@ struct mf_plan {
 	int prio_len[2] = {0, 0};    // rows at least this long run at raised wave priority in the single-wave launch (0: none)
 	// skew-aware split of a sweep with many rows: rows whose serial walk would dominate the launch go to the
 	// row-cooperative kernel on a side stream, the others stay on the single-wave kernel
-	int *long_rows[2] = {nullptr, nullptr}, *short_rows[2] = {nullptr, nullptr};
+	dev_buf<int> long_rows[2], short_rows[2];
 	bool lpt[2] = {false, false};   // short_rows[kind] = ALL rows, longest first: the order of a sweep without extreme rows
 	int n_long[2] = {0, 0}, n_short[2] = {0, 0};
 	int long_len[2] = {0, 0};   // a row at least this long is on the extreme-row path (when n_long > 0)
 	// extreme rows of LARGE sweeps: 256-entry segments -> scaled rows in `scratch` -> ordered sum
 	int n_seg[2] = {0, 0};
-	int *seg_row[2] = {nullptr, nullptr}, *seg_beg[2] = {nullptr, nullptr}, *seg_end[2] = {nullptr, nullptr};
-	long long *seg_out[2] = {nullptr, nullptr}, *lr_sbeg[2] = {nullptr, nullptr};
-	int *lr_cnt[2] = {nullptr, nullptr};
-	double *scratch = nullptr;
+	dev_buf<int> seg_row[2], seg_beg[2], seg_end[2];
+	dev_buf<long long> seg_out[2], lr_sbeg[2];
+	dev_buf<int> lr_cnt[2];
+	dev_buf<double> scratch;
 	size_t scratch_entries = 0;
 	// tiny sweeps (a few us of data): ONE cooperative launch over all rows; a fork/join costs more than it saves
 	int nch_coop = 0;

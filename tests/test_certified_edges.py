@@ -46,7 +46,7 @@ KS_DISPATCHED = [16, 20, 32, 40, 48, 60, 64, 80, 96, 100, 112, 128, 256]     # t
 
 
 def shape_of(K):
-    """(k-steps per chunk, waves) of the instance K is dispatched to (mf_hip.hip: K % 20 is tested before K % 16)."""
+    """(k-steps per chunk, waves) of the instance K is dispatched to (certified_shape, mf_certified.hip.h: K % 20 is tested before K % 16)."""
     if K % 20 == 0 and K <= 100:
         return 5, 4
     if K % 16 == 0 and K <= 96:
