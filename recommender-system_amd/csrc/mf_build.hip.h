@@ -446,8 +446,8 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 			if (est_us < 50.0 && nrows < 4096 && !cfg.sweep_long_set && cfg.sweep_long_kind[kind] <= 0) {
 				if (p->sweep.coop && (nc >= 8 || cfg.sweep_nch)) {
 					p->coop_all[kind] = true;
-					p->nch_coop = cfg.sweep_nch ? nl : nc;
-					p->lds_bytes_coop = head + (size_t) p->nch_coop * per_entry;
+					const int n = cfg.sweep_nch ? nl : nc;
+					p->coop = SweepForm{p->sweep.coop, n, head + (size_t) n * per_entry, mf::kCoopWaves * mf::kWave};
 				}
 				continue;
 			}
@@ -468,27 +468,17 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 				t_eff *= 2;
 			}
 			if (p->max_row_len[kind] < t_eff) continue;
-			std::vector<int> lg, sh, md;
-			// mid-length rows: at least t_mid entries (default: a quarter of the extreme threshold, never below 4x the mean)
-			const int t_mid = !p->sweep.db || cfg.sweep_mid == 0 ? t_eff
-			                  : cfg.sweep_mid > 0            ? std::min(cfg.sweep_mid, t_eff)
-			                                                 : std::min(t_eff, std::max(t_eff / 4, (int) std::min<long long>(4 * (long long) (p->nnz / std::max(nrows, 1)), 1 << 30)));
+			std::vector<int> lg, sh;
 			for (int r = 0; r < nrows; ++r) {
 				const int len = pt[(size_t) r + 1] - pt[r];
-				(len >= t_eff ? lg : len >= t_mid ? md : sh).push_back(r);
+				(len >= t_eff ? lg : sh).push_back(r);
 			}
 			// longest first: workgroups are dispatched in list order as slots free up, so the long walks start
 			// at once and the short rows fill in behind them (longest-processing-time-first scheduling)
 			auto by_len = [&](int x, int y) { return pt[(size_t) x + 1] - pt[x] > pt[(size_t) y + 1] - pt[y]; };
 			if (!cfg.nosort) {
 				std::stable_sort(sh.begin(), sh.end(), by_len);
-				std::stable_sort(md.begin(), md.end(), by_len);
 				std::stable_sort(lg.begin(), lg.end(), by_len);
-			}
-			if (!md.empty()) {
-				MF_TRY(p->mid_rows[kind].alloc(md.size()));
-				MF_TRY_HIP(h2d(p, p->mid_rows[kind], md.data(), md.size() * sizeof(int)));
-				p->n_mid[kind] = (int) md.size();
 			}
 			MF_TRY(p->long_rows[kind].alloc(lg.size()));
 			MF_TRY(p->short_rows[kind].alloc(sh.size()));
@@ -534,20 +524,14 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 			MF_TRY_HIP(h2d(p, p->lr_cnt[kind], lcnt.data(), lg.size() * sizeof(int)));
 		}
 		if (p->coop_all[0] || p->coop_all[1])
-			MF_TRY_HIP(raise_lds_limit((const void *) p->sweep.coop, p->lds_bytes_coop));
+			MF_TRY_HIP(raise_lds_limit((const void *) p->coop.fn, p->coop.lds));
 		if (p->n_long[0] || p->n_long[1]) {
-			if (cfg.rest_coop && p->sweep.coop) {
-				p->rest_coop = true;
-				p->nch_coop = cfg.sweep_nch ? nl : nc;
-				p->lds_bytes_coop = head + (size_t) p->nch_coop * per_entry;
-				MF_TRY_HIP(raise_lds_limit((const void *) p->sweep.coop, p->lds_bytes_coop));
-			}
-			p->nch_prod = p->nch;
-			if (const int v = cfg.sweep_pnch; v >= 1 && v <= 64 && (size_t) p->sweep.xs_bytes + (size_t) v * p->sweep.row_bytes <= kLdsPerCu) p->nch_prod = v;
-			p->lds_bytes_prod = (size_t) p->sweep.xs_bytes + (size_t) p->nch_prod * p->sweep.row_bytes;
+			int npr = p->single.nch;
+			if (const int v = cfg.sweep_pnch; v >= 1 && v <= 64 && head + (size_t) v * p->sweep.row_bytes <= kLdsPerCu) npr = v;
+			p->prod = SweepForm{p->sweep.prod, npr, head + (size_t) npr * p->sweep.row_bytes, mf::kWave};
 			p->lds_bytes_osum = mf::kOrderedSumLds;
 			if (cfg.os_lds) p->lds_bytes_osum = std::min<size_t>(kLdsPerCu, std::max<size_t>(p->lds_bytes_osum, cfg.os_lds));
-			MF_TRY_HIP(raise_lds_limit((const void *) p->sweep.prod, p->lds_bytes_prod));
+			MF_TRY_HIP(raise_lds_limit((const void *) p->prod.fn, p->prod.lds));
 			MF_TRY_HIP(raise_lds_limit(cfg.os_dpp ? (const void *) mf::ordered_sum_kernel<true> : (const void *) mf::ordered_sum_kernel<false>, p->lds_bytes_osum));
 			// [slice][entry][kSliceCols doubles]; one block of padding per slice: the last block of a row is read whole
 			p->scratch_entries = (size_t) scratch_entries + mf::kBlockEntries;
@@ -563,25 +547,6 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 			MF_TRY_HIP(hipStreamCreateWithPriority(&p->side_stream, hipStreamNonBlocking, side_low ? prio_lo : prio_hi));
 			MF_TRY_HIP(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
 			MF_TRY_HIP(hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming));
-			if (p->n_mid[0] || p->n_mid[1]) {
-				// two tiles of nch_mid rows: as many as fit a third of a CU's LDS (K=100: 32 rows, 53 KB, three per CU)
-				const size_t rb = (size_t) p->sweep.row_bytes, hd = (size_t) p->sweep.xs_bytes;
-				int nm = cfg.mid_nch > 0 ? cfg.mid_nch : 32;
-				while (nm > 4 && hd + 2 * (size_t) nm * rb > kLdsPerCu / (cfg.mid_nch > 0 ? 1 : 3)) --nm;
-				p->nch_mid = std::min(nm, 64);
-				p->lds_bytes_mid = hd + 2 * (size_t) p->nch_mid * rb;
-				p->mid_coop = cfg.mid_coop && p->sweep.coop;
-				if (p->mid_coop) {   // 2 buffers x 7 producers x nch rows
-					int nc2 = cfg.mid_nch > 0 ? cfg.mid_nch : 13;
-					while (nc2 > 1 && hd + (size_t) nc2 * per_entry > kLdsPerCu - 2048) --nc2;
-					p->nch_mid = nc2;
-					p->lds_bytes_mid = hd + (size_t) nc2 * per_entry;
-					MF_TRY_HIP(raise_lds_limit((const void *) p->sweep.coop, p->lds_bytes_mid));
-				} else
-				MF_TRY_HIP(raise_lds_limit((const void *) p->sweep.db, p->lds_bytes_mid));
-				MF_TRY_HIP(hipStreamCreateWithPriority(&p->mid_stream, hipStreamNonBlocking, prio_hi));
-				MF_TRY_HIP(hipEventCreateWithFlags(&p->ev_mid_join, hipEventDisableTiming));
-			}
 		}
 	}
 	// ---- wave priority for the long rows of the single-wave launch (what the launch ends on): when the launch is skewed
@@ -608,21 +573,14 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 	// ---- double-buffered single-wave form for the WHOLE single-wave launch: measured slower than the single-buffered form
 	// whenever the launch has more rows than double-tile workgroups fit the chip (cfg3 uniform 0.222 -> 0.429 ms: the
 	// second tile halves the resident workgroups and the CU's gather rate is shared by fewer requests in flight), so it
-	// is off unless forced (MF_SWEEP_DB=1) or the launch is below MF_SWEEP_DB_ROWS rows (experiments build).  Its use is
-	// the mid-length rows' launch above.
+	// is off unless forced (MF_SWEEP_DB=1) or the launch is below MF_SWEEP_DB_ROWS rows (experiments build).
 	for (int kind = 0; kind < 2; ++kind) {
 		const int nrows = kind == 0 ? p->items : p->uc;
 		const int launch_rows = p->n_long[kind] > 0 ? p->n_short[kind] : nrows;
 		const int limit = p->cfg.db_rows;
-		p->use_db[kind] = p->sweep.db && !p->coop_all[kind] && !p->rest_coop && launch_rows > 0 &&
+		p->use_db[kind] = p->sweep.db && !p->coop_all[kind] && launch_rows > 0 &&
 		                  (p->cfg.sweep_db == 1 || (p->cfg.sweep_db < 0 && launch_rows <= limit));
-		p->use_pair[kind] = !p->coop_all[kind] && !p->rest_coop && !p->use_db[kind] && launch_rows > 0 && pair_wanted(p, kind);
-		// Trios (loader / phase-A / phase-B waves, mf_sweep.hip.h): experiments build only, MF_SWEEP_TRIO=1 (every side that
-		// runs pairs) or MF_SWEEP_TRIO_U=1 (the user side alone).  No rule chooses them: on the one side they were meant for --
-		// cfg3 power-law users, not split, longest row 2324 entries = 128 us of walk against 112 us of bytes -- the trio alone
-		// is slower than the pair (0.1447 vs 0.1378 ms with the items on pairs; the 0.121 of the all-trio run was the item
-		// side's ordered sums no longer overlapping the user sweep), and every throughput-bound side loses to the third tile.
-		p->use_trio[kind] = p->use_pair[kind] && p->sweep.trio && (p->cfg.sweep_trio == 1 || (kind == 1 && p->cfg.sweep_trio == 2));
+		p->use_pair[kind] = !p->coop_all[kind] && !p->use_db[kind] && launch_rows > 0 && pair_wanted(p, kind);
 	}
 	// ---- a sweep of a few thousand rows is a handful of rounds of workgroups: in index order its tail is whatever
 	// long rows happen to start last.  Longest first (workgroups are dispatched in list order) the tail is made of the

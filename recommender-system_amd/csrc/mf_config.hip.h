@@ -49,8 +49,6 @@ struct mf_config {
 	bool sum_under = false;           // MF_SWEEP_SUM_ORDER=under
 	bool no_defer = false;            // MF_SWEEP_NO_DEFER
 	bool nosort = false;              // MF_SWEEP_NOSORT
-	bool rest_coop = false;           // MF_SWEEP_REST=coop
-	int sweep_trio = 0;               // MF_SWEEP_TRIO=1 / MF_SWEEP_TRIO_U=1: the pair form's compute wave split into a phase-A and a phase-B wave wherever pairs run / on the user side
 	int sweep_pair_kind[2] = {-1, -1};  // MF_SWEEP_PAIR_I / MF_SWEEP_PAIR_U = 0|1: the wave-pair form of the item / user sweep alone
 	int es_row_cost = 0;              // MF_ES_ROW_COST: entries a row end counts for when the streams launch cuts its runs (0: rule)
 	int es_active = 0;                // MF_ES_ACTIVE=1..8: waves per workgroup of the streams launch that own rows (0: rule)
@@ -60,14 +58,10 @@ struct mf_config {
 	int side_prio = -1;               // MF_SIDE_PRIO=0|1: the side stream of the extreme-row path at low / high priority (-1: rule)
 	bool rec_wide = false;            // MF_RECOMMEND_WIDE: K=128 in the eight-wave, 16-users-per-wave shape of K=256
 	int pf_rows = 0;                  // MF_SWEEP_PF_ROWS: launches of up to this many rows take the pipelined-phases form (0: 262144)
-	int pair_loaders = 0;             // MF_SWEEP_PAIR_LOADERS=1|2: loader waves of the wave-pair form (0: rule)
 	int pair_nch = 0;                 // MF_SWEEP_PAIR_NCH: chunk size of the wave-pair form (0: 32)
 	int db_nch = 0;                   // MF_SWEEP_DB_NCH: its chunk size (0: 16)
 	bool sweep_pf = true;             // MF_SWEEP_PF=0: phases A / B as hipcc schedules them (two steps per LDS round trip)
 	int sweep_prio = -1;              // MF_SWEEP_PRIO: rows at least this long run at raised wave priority (0: none, -1: rule)
-	int sweep_mid = 0;                // MF_SWEEP_MID: rows at least this long (and below the extreme threshold) get their own launch (0: none, -1: a quarter of the threshold)
-	bool mid_coop = false;            // MF_SWEEP_MID_KERNEL=coop: the mid-length rows through the row-cooperative kernel
-	int mid_nch = 0;                  // MF_SWEEP_MID_NCH: its chunk size (0: 32 or what fits a third of the LDS)
 
 	static bool is0(const char *v) { return v && v[0] == '0'; }
 	static bool eq(const char *v, const char *s) { return v && strcmp(v, s) == 0; }
@@ -112,18 +106,14 @@ struct mf_config {
 		c.sum_under = eq(getenv("MF_SWEEP_SUM_ORDER"), "under");
 		c.no_defer = getenv("MF_SWEEP_NO_DEFER") != nullptr;
 		c.nosort = getenv("MF_SWEEP_NOSORT") != nullptr;
-		c.rest_coop = eq(getenv("MF_SWEEP_REST"), "coop");
 		if ((v = getenv("MF_ES_NCH"))) c.es_nch = atoi(v);
 		if ((v = getenv("MF_ES_ACTIVE"))) c.es_active = atoi(v);
 		if ((v = getenv("MF_ES_ROW_COST"))) c.es_row_cost = atoi(v);
-		if ((v = getenv("MF_SWEEP_TRIO"))) c.sweep_trio = is0(v) ? 0 : 1;
-		if ((v = getenv("MF_SWEEP_TRIO_U")) && !is0(v)) c.sweep_trio = 2;
 		if ((v = getenv("MF_SWEEP_PAIR_I"))) c.sweep_pair_kind[0] = is0(v) ? 0 : 1;
 		if ((v = getenv("MF_SWEEP_PAIR_U"))) c.sweep_pair_kind[1] = is0(v) ? 0 : 1;
 		if ((v = getenv("MF_SWEEP_DB_ROWS"))) c.db_rows = atoi(v);
 		if ((v = getenv("MF_SWEEP_DB_NCH"))) c.db_nch = atoi(v);
 		if ((v = getenv("MF_SWEEP_PAIR_NCH"))) c.pair_nch = atoi(v);
-		if ((v = getenv("MF_SWEEP_PAIR_LOADERS"))) c.pair_loaders = atoi(v);
 		if ((v = getenv("MF_SWEEP_PF_ROWS"))) c.pf_rows = atoi(v);
 		c.rec_wide = getenv("MF_RECOMMEND_WIDE") != nullptr;
 		if ((v = getenv("MF_SWEEP_LONG_I"))) c.sweep_long_kind[0] = atoi(v);
@@ -131,9 +121,6 @@ struct mf_config {
 		if ((v = getenv("MF_SIDE_PRIO"))) c.side_prio = is0(v) ? 0 : 1;
 		if ((v = getenv("MF_SWEEP_PF"))) c.sweep_pf = !is0(v);
 		if ((v = getenv("MF_SWEEP_PRIO"))) c.sweep_prio = atoi(v);
-		if ((v = getenv("MF_SWEEP_MID"))) c.sweep_mid = atoi(v);
-		if ((v = getenv("MF_SWEEP_MID_NCH"))) c.mid_nch = atoi(v);
-		c.mid_coop = eq(getenv("MF_SWEEP_MID_KERNEL"), "coop");
 #endif
 		return c;
 	}
@@ -173,17 +160,14 @@ struct mf_config {
 		if (sum_under) add("MF_SWEEP_SUM_ORDER", "under");
 		if (no_defer) add("MF_SWEEP_NO_DEFER", "1");
 		if (nosort) add("MF_SWEEP_NOSORT", "1");
-		if (rest_coop) add("MF_SWEEP_REST", "coop");
 		if (es_nch) add("MF_ES_NCH", std::to_string(es_nch));
 		if (es_active) add("MF_ES_ACTIVE", std::to_string(es_active));
 		if (es_row_cost) add("MF_ES_ROW_COST", std::to_string(es_row_cost));
-		if (sweep_trio) add(sweep_trio == 2 ? "MF_SWEEP_TRIO_U" : "MF_SWEEP_TRIO", "1");
 		if (sweep_pair_kind[0] >= 0) add("MF_SWEEP_PAIR_I", std::to_string(sweep_pair_kind[0]));
 		if (sweep_pair_kind[1] >= 0) add("MF_SWEEP_PAIR_U", std::to_string(sweep_pair_kind[1]));
 		if (db_rows) add("MF_SWEEP_DB_ROWS", std::to_string(db_rows));
 		if (db_nch) add("MF_SWEEP_DB_NCH", std::to_string(db_nch));
 		if (pair_nch) add("MF_SWEEP_PAIR_NCH", std::to_string(pair_nch));
-		if (pair_loaders) add("MF_SWEEP_PAIR_LOADERS", std::to_string(pair_loaders));
 		if (pf_rows) add("MF_SWEEP_PF_ROWS", std::to_string(pf_rows));
 		if (rec_wide) add("MF_RECOMMEND_WIDE", "1");
 		if (sweep_long_kind[0]) add("MF_SWEEP_LONG_I", std::to_string(sweep_long_kind[0]));
@@ -191,9 +175,6 @@ struct mf_config {
 		if (side_prio >= 0) add("MF_SIDE_PRIO", std::to_string(side_prio));
 		if (!sweep_pf) add("MF_SWEEP_PF", "0");
 		if (sweep_prio >= 0) add("MF_SWEEP_PRIO", std::to_string(sweep_prio));
-		if (sweep_mid != 0) add("MF_SWEEP_MID", std::to_string(sweep_mid));
-		if (mid_nch) add("MF_SWEEP_MID_NCH", std::to_string(mid_nch));
-		if (mid_coop) add("MF_SWEEP_MID_KERNEL", "coop");
 		return s;
 	}
 };

@@ -209,8 +209,6 @@ void mf_plan_destroy(mf_plan *p)
 		(void) hipEventDestroy(t.t1);
 	}
 	if (p->side_stream) (void) hipStreamDestroy(p->side_stream);
-	if (p->mid_stream) (void) hipStreamDestroy(p->mid_stream);
-	if (p->ev_mid_join) (void) hipEventDestroy(p->ev_mid_join);
 	if (p->ev_fork) (void) hipEventDestroy(p->ev_fork);
 	if (p->ev_join) (void) hipEventDestroy(p->ev_join);
 	if (p->own_stream) (void) hipStreamDestroy(p->own_stream);
@@ -641,13 +639,13 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 	int n;
 	if (p->sweep.dma)
 		n = snprintf(buf, (size_t) buflen,
-		             "sweep_dma_kernel<KT=%d,NPASS=%d> K=%d pitch=%d/%d nch=%d row_bytes=%d lds=%zu long_rows=%d/%d coop_nch=%d double_buffered=%d/%d(nch=%d) mid_rows=%d/%d(nch=%d) wave_pair=%d/%d(nch=%d) trio=%d/%d",
-		             p->sweep.kt, p->sweep.kt ? (p->K / 2 + 63) / 64 : p->sweep.kpmax, p->K, p->ldl, p->ldr, p->nch, p->sweep.row_bytes,
-		             p->lds_bytes, p->n_long[0] + (p->coop_all[0] ? p->items : 0), p->n_long[1] + (p->coop_all[1] ? p->uc : 0),
-		             p->coop_all[0] || p->coop_all[1] ? p->nch_coop : 0, (int) p->use_db[0], (int) p->use_db[1], p->nch_db, p->n_mid[0], p->n_mid[1], p->nch_mid, (int) p->use_pair[0], (int) p->use_pair[1], p->nch_pair, (int) p->use_trio[0], (int) p->use_trio[1]);
+		             "sweep_dma_kernel<KT=%d,NPASS=%d> K=%d pitch=%d/%d nch=%d row_bytes=%d lds=%zu long_rows=%d/%d coop_nch=%d double_buffered=%d/%d(nch=%d) wave_pair=%d/%d(nch=%d)",
+		             p->sweep.kt, p->sweep.kt ? mf::dma_passes(p->K) : p->sweep.kpmax, p->K, p->ldl, p->ldr, p->single.nch, p->sweep.row_bytes,
+		             p->single.lds, p->n_long[0] + (p->coop_all[0] ? p->items : 0), p->n_long[1] + (p->coop_all[1] ? p->uc : 0),
+		             p->coop_all[0] || p->coop_all[1] ? p->coop.nch : 0, (int) p->use_db[0], (int) p->use_db[1], p->db.nch, (int) p->use_pair[0], (int) p->use_pair[1], p->pair.nch);
 	else
 		n = snprintf(buf, (size_t) buflen, "sweep_kernel<KT=%d,KPMAX=%d> K=%d nch=%d stride=%d lds=%zu",
-		             p->sweep.kt, p->sweep.kpmax, p->K, p->nch, p->stride, p->lds_bytes);
+		             p->sweep.kt, p->sweep.kpmax, p->K, p->single.nch, p->stride, p->single.lds);
 	// accumulate form of the single-wave launch of the item / user sweep (the rule of launch_sweep, mf_launch.hip.h)
 	if (n > 0 && n < buflen)
 		n += snprintf(buf + n, (size_t) (buflen - n), " accumulate=%s/%s", single_wave_pipelined(p, 0) ? "pf" : "plain",

@@ -38,10 +38,43 @@ bool sweep_is_dma(const mf_config &cfg, int K)
 	return !cfg.sweep_reg && (K & 1) == 0 && K >= 2 && K <= 128 * 8;
 }
 
+// Entries per chunk of a single-wave launch: {nch, nch_few}, or {0, 0} when not even one row fits.  `head` = LDS bytes in
+// front of the tile, `row_bytes` = tile row stride.
+// Chunk size = latency hiding vs fixed cost.  Each single-wave workgroup alternates "gather a chunk"
+// and "compute on it", so the bytes in flight per CU come from OTHER resident workgroups: small tiles
+// (~13 KB -> ~11 workgroups per CU) beat big ones (measured on cfg4, K=100: nch 64/32/16/8 ->
+// 37.1/29.3/24.1/25.5 ms per iteration); phase A costs K steps per chunk whatever its size, which is
+// what stops the trend below ~12 entries.
+// K=256: nch 8/12/16/24 -> 71/66/78/82 ms (12 rows = 6 workgroups per CU); K=30: nch 16..32 best.
+// nch_few: a sweep over FEW rows (ML100k: 943 x 1682) cannot fill 256 CUs whatever the chunk size; its time is the
+// longest row's serial chain of chunks, so use the largest chunk there (737 entries: 47 -> 12 chunks).
+// MF_SWEEP_NCH sets both.
+struct ChunkSizes {
+	int nch, nch_few;
+};
+ChunkSizes chunk_rule(size_t head, size_t row_bytes, const mf_config &cfg)
+{
+	auto fit = [&](size_t budget) {
+		return budget > head ? (int) std::min<size_t>(64, (budget - head) / row_bytes) : 0;
+	};
+	int nch = 16;
+	if (head + (size_t) nch * row_bytes > kLdsPerCu / 6) nch = std::max(12, fit(kLdsPerCu / 6));
+	nch = std::min(nch, fit(kLdsPerCu));
+	if (const int v = cfg.sweep_nch; v >= 1 && head + (size_t) v * row_bytes <= kLdsPerCu) nch = v;
+	if (nch < 1) return {0, 0};
+	int few = std::max(nch, std::min(64, fit(kLdsPerCu / 2)));
+	if (cfg.sweep_nch) few = nch;
+	return {nch, few};
+}
+
+// LDS tile row stride and the bytes in front of the tile, for the form choose_sweep picked
+size_t tile_row_bytes(const mf_plan *p) { return p->sweep.dma ? (size_t) p->sweep.row_bytes : (size_t) p->stride * sizeof(double); }
+size_t tile_head_bytes(const mf_plan *p) { return p->sweep.dma ? (size_t) p->sweep.xs_bytes : 0; }
+
 int choose_sweep(mf_plan *p)
 {
 	const int K = p->K;
-	p->sweep = SweepVariant{nullptr, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+	p->sweep = SweepVariant{};
 	const bool allow_dma = !p->cfg.sweep_reg;   // MF_SWEEP_IMPL=dma (default) | reg: register-staged form only
 	if (allow_dma)
 		for (const auto &v : kDma)
@@ -50,8 +83,8 @@ int choose_sweep(mf_plan *p)
 		for (const auto &v : kDmaGeneric)
 			if (K <= 128 * v.kpmax && !p->sweep.fn) {
 				p->sweep = v;
-				p->sweep.row_bytes = 16 * ((K / 2) | 1);
-				p->sweep.xs_bytes = ((K * 8 + 255) / 256) * 256;
+				p->sweep.row_bytes = mf::dma_row_stride(K);
+				p->sweep.xs_bytes = mf::dma_xs_bytes(K);
 			}
 	if (!p->sweep.fn)
 		for (const auto &v : kSpecialised)
@@ -65,62 +98,29 @@ int choose_sweep(mf_plan *p)
 	if (!p->sweep.fn) return MF_ERR_UNSUPPORTED;
 	if (!p->cfg.sweep_pf) p->sweep.pf = nullptr;   // MF_SWEEP_PF=0 (experiments build): round 2's accumulate form everywhere
 
-	p->stride = K | 1;
-	const size_t row_bytes = p->sweep.dma ? (size_t) p->sweep.row_bytes : (size_t) p->stride * sizeof(double);
-	const size_t head = p->sweep.dma ? (size_t) p->sweep.xs_bytes : 0;
-	auto fit = [&](size_t budget) {
-		return budget > head ? (int) std::min<size_t>(64, (budget - head) / row_bytes) : 0;
+	p->stride = mf::reg_row_stride(K);
+	const size_t row_bytes = tile_row_bytes(p), head = tile_head_bytes(p);
+	const ChunkSizes cs = chunk_rule(head, row_bytes, p->cfg);
+	if (cs.nch < 1) return MF_ERR_UNSUPPORTED;
+	p->single = SweepForm{nullptr, cs.nch, head + (size_t) cs.nch * row_bytes, mf::kWave};
+	p->few = SweepForm{nullptr, cs.nch_few, head + (size_t) cs.nch_few * row_bytes, mf::kWave};
+	MF_HIP(raise_lds_limit((const void *) p->sweep.fn, std::max(p->single.lds, p->few.lds)));
+	if (p->sweep.pf) MF_HIP(raise_lds_limit((const void *) p->sweep.pf, std::max(p->single.lds, p->few.lds)));
+	// the two-tile forms: `dflt` entries per chunk (MF_SWEEP_NCH overrides) while two tiles stay within half a CU's LDS
+	auto two_tiles = [&](SweepFn fn, int dflt, int block) {
+		int n = p->cfg.sweep_nch ? p->cfg.sweep_nch : dflt;
+		while (n > 1 && head + 2 * (size_t) n * row_bytes > kLdsPerCu / 2) --n;
+		return SweepForm{fn, n, head + 2 * (size_t) n * row_bytes, block};
 	};
-	// Chunk size = latency hiding vs fixed cost.  Each single-wave workgroup alternates "gather a chunk"
-	// and "compute on it", so the bytes in flight per CU come from OTHER resident workgroups: small tiles
-	// (~13 KB -> ~11 workgroups per CU) beat big ones (measured on cfg4, K=100: nch 64/32/16/8 ->
-	// 37.1/29.3/24.1/25.5 ms per iteration); phase A costs K steps per chunk whatever its size, which is
-	// what stops the trend below ~12 entries.
-	// K=256: nch 8/12/16/24 -> 71/66/78/82 ms (12 rows = 6 workgroups per CU); K=30: nch 16..32 best.
-	int nch = 16;
-	if (head + (size_t) nch * row_bytes > kLdsPerCu / 6) nch = std::max(12, fit(kLdsPerCu / 6));
-	nch = std::min(nch, fit(kLdsPerCu));
-	if (const int v = p->cfg.sweep_nch; v >= 1 && head + (size_t) v * row_bytes <= kLdsPerCu) nch = v;
-	if (nch < 1) return MF_ERR_UNSUPPORTED;
-	p->nch = nch;
-	p->lds_bytes = head + (size_t) nch * row_bytes;
-	// A sweep over FEW rows (ML100k: 943 x 1682) cannot fill 256 CUs whatever the chunk size; its time is the
-	// longest row's serial chain of chunks, so use the largest chunk there (737 entries: 47 -> 12 chunks).
-	int few = std::max(nch, std::min(64, fit(kLdsPerCu / 2)));
-	if (p->cfg.sweep_nch) few = nch;
-	p->nch_few = few;
-	p->lds_bytes_few = head + (size_t) few * row_bytes;
-	MF_HIP(raise_lds_limit((const void *) p->sweep.fn, (size_t) (std::max(p->lds_bytes, p->lds_bytes_few))));
-	if (p->sweep.pf) MF_HIP(raise_lds_limit((const void *) p->sweep.pf, (size_t) (std::max(p->lds_bytes, p->lds_bytes_few))));
-	if (p->sweep.pair) {   // wave-pair form: two tiles
+	if (p->sweep.pair) {   // wave-pair form
 		// 32-entry chunks: the loader's ~90 cycles per gathered row are what a pair is bound by, the K steps of phase A are
 		// paid per chunk -- a lone 5993-entry row: 0.526 ms at 16, 0.332 at 32; cfg3 power-law 0.311 / 0.268 / 0.314 at 24 / 32 / 40
-		int npr = p->cfg.pair_nch > 0 ? p->cfg.pair_nch : 32;
-		if (p->cfg.sweep_nch) npr = p->cfg.sweep_nch;
-		while (npr > 1 && head + 2 * (size_t) npr * row_bytes > kLdsPerCu / 2) --npr;
-		p->nch_pair = npr;
-		p->lds_bytes_pair = head + 2 * (size_t) npr * row_bytes;
-		p->pair_loaders = p->cfg.pair_loaders == 2 && p->sweep.pair2 ? 2 : 1;
-		if (p->pair_loaders == 2) p->sweep.pair = p->sweep.pair2;
-		p->pair_waves = p->pair_loaders + 1;
-		MF_HIP(raise_lds_limit((const void *) p->sweep.pair, p->lds_bytes_pair));
-		if (p->sweep.trio) {   // loader / phase-A / phase-B waves: three tiles + the errors of two chunks
-			int ntr = p->cfg.pair_nch > 0 ? p->cfg.pair_nch : 32;
-			if (p->cfg.sweep_nch) ntr = p->cfg.sweep_nch;
-			while (ntr > 1 && head + 1024 + 3 * (size_t) ntr * row_bytes > kLdsPerCu / 2) --ntr;
-			p->nch_trio = ntr;
-			p->lds_bytes_trio = head + 1024 + 3 * (size_t) ntr * row_bytes;
-			MF_HIP(raise_lds_limit((const void *) p->sweep.trio, p->lds_bytes_trio));
-		}
+		p->pair = two_tiles(p->sweep.pair, p->cfg.pair_nch > 0 ? p->cfg.pair_nch : 32, 2 * mf::kWave);
+		MF_HIP(raise_lds_limit((const void *) p->pair.fn, p->pair.lds));
 	}
-	// double-buffered form (few rows per CU: the wave hides its own gather): two tiles of nch_db rows
-	if (p->sweep.db) {
-		int ndb = p->cfg.db_nch > 0 ? p->cfg.db_nch : 16;
-		if (p->cfg.sweep_nch) ndb = p->cfg.sweep_nch;
-		while (ndb > 1 && head + 2 * (size_t) ndb * row_bytes > kLdsPerCu / 2) --ndb;
-		p->nch_db = ndb;
-		p->lds_bytes_db = head + 2 * (size_t) ndb * row_bytes;
-		MF_HIP(raise_lds_limit((const void *) p->sweep.db, p->lds_bytes_db));
+	if (p->sweep.db) {   // double-buffered form (few rows per CU: the wave hides its own gather)
+		p->db = two_tiles(p->sweep.db, p->cfg.db_nch > 0 ? p->cfg.db_nch : 16, mf::kWave);
+		MF_HIP(raise_lds_limit((const void *) p->db.fn, p->db.lds));
 	}
 	// ---- errors + streams iteration (mf_stream.hip.h) for instances whose factors stay in L2 / Infinity Cache: the
 	// two sweeps are then bound by the latency of one wave walking a row chunk by chunk, not by bandwidth.  It costs a
@@ -139,46 +139,19 @@ int choose_sweep(mf_plan *p)
 	return MF_OK;
 }
 
-
 // Row-sum kernel of mf_plan_loss for this plan's K (the geometry choose_sweep picked) and its chunk sizes.  One tile and
-// no second buffer: the request is the L row plus nch gathered rows.  The chunk rule is the sweeps' (latency hiding
-// against the K steps of phase A per chunk): 16 entries while that stays within a sixth of a CU's LDS, the largest
-// chunk for launches of fewer rows than fill the chip; MF_SWEEP_NCH sets both.
+// no second buffer: the request is the L row plus nch gathered rows, at the sweeps' chunk rule (chunk_rule).
 int choose_loss(mf_plan *p)
 {
-	p->loss_fn = nullptr;
-	if (!p->sweep.dma)
-		p->loss_fn = mf::loss_reg_kernel;
-	else if (p->sweep.kt == 0)
-		p->loss_fn = p->sweep.kpmax == 1 ? mf::loss_dma_kernel<0, 1> : p->sweep.kpmax == 2 ? mf::loss_dma_kernel<0, 2>
-		             : p->sweep.kpmax == 4 ? mf::loss_dma_kernel<0, 4> : mf::loss_dma_kernel<0, 8>;
-	else
-		switch (p->sweep.kt) {
-		case 10: p->loss_fn = mf::loss_dma_kernel<10, mf::DmaGeom<10>::kPasses>; break;
-		case 20: p->loss_fn = mf::loss_dma_kernel<20, mf::DmaGeom<20>::kPasses>; break;
-		case 30: p->loss_fn = mf::loss_dma_kernel<30, mf::DmaGeom<30>::kPasses>; break;
-		case 50: p->loss_fn = mf::loss_dma_kernel<50, mf::DmaGeom<50>::kPasses>; break;
-		case 100: p->loss_fn = mf::loss_dma_kernel<100, mf::DmaGeom<100>::kPasses>; break;
-		case 128: p->loss_fn = mf::loss_dma_kernel<128, mf::DmaGeom<128>::kPasses>; break;
-		case 256: p->loss_fn = mf::loss_dma_kernel<256, mf::DmaGeom<256>::kPasses>; break;
-		default: return MF_ERR_UNSUPPORTED;
-		}
-	const size_t row_bytes = p->sweep.dma ? (size_t) p->sweep.row_bytes : (size_t) p->stride * sizeof(double);
-	const size_t head = p->sweep.dma ? (size_t) p->sweep.xs_bytes : 0;
-	auto fit = [&](size_t budget) {
-		return budget > head ? (int) std::min<size_t>(64, (budget - head) / row_bytes) : 0;
-	};
-	int nch = 16;
-	if (head + (size_t) nch * row_bytes > kLdsPerCu / 6) nch = std::max(12, fit(kLdsPerCu / 6));
-	nch = std::min(nch, fit(kLdsPerCu));
-	if (const int v = p->cfg.sweep_nch; v >= 1 && head + (size_t) v * row_bytes <= kLdsPerCu) nch = v;
-	if (nch < 1) return MF_ERR_UNSUPPORTED;
-	int few = std::max(nch, std::min(64, fit(kLdsPerCu / 2)));
-	if (p->cfg.sweep_nch) few = nch;
-	p->loss_nch[0] = nch;
-	p->loss_nch[1] = few;
-	p->loss_lds[0] = head + (size_t) nch * row_bytes;
-	p->loss_lds[1] = head + (size_t) few * row_bytes;
+	p->loss_fn = p->sweep.dma ? p->sweep.loss : mf::loss_reg_kernel;
+	if (!p->loss_fn) return MF_ERR_UNSUPPORTED;
+	const size_t row_bytes = tile_row_bytes(p), head = tile_head_bytes(p);
+	const ChunkSizes cs = chunk_rule(head, row_bytes, p->cfg);
+	if (cs.nch < 1) return MF_ERR_UNSUPPORTED;
+	p->loss_nch[0] = cs.nch;
+	p->loss_nch[1] = cs.nch_few;
+	p->loss_lds[0] = head + (size_t) cs.nch * row_bytes;
+	p->loss_lds[1] = head + (size_t) cs.nch_few * row_bytes;
 	MF_HIP(raise_lds_limit((const void *) p->loss_fn, std::max(p->loss_lds[0], p->loss_lds[1])));
 	return MF_OK;
 }
@@ -198,13 +171,32 @@ bool single_wave_pipelined(const mf_plan *p, int kind)
 	return p->sweep.pf && p->n_short[kind] <= kPfRows && nrows <= kPfRows;
 }
 
+// The form of the main launch of one side (kind 0: items, 1: users): the cooperative launch of a tiny sweep, the
+// double-buffered or the wave-pair form where plan_row_schedule chose one, else the single-wave form -- plain or
+// pipelined by single_wave_pipelined, at the large chunk when `few_rows`.
+SweepForm main_form(const mf_plan *p, int kind, bool few_rows)
+{
+	if (p->coop_all[kind]) {
+		// A cooperative launch of sweep_few rows or more runs at the single-wave chunk size with the cooperative LDS request,
+		// as it always has.  Known and left for a change of its own, with a test: at K = 30 and K = 50 that request is sized
+		// for fewer rows (14 and 8) than the 16 of the single-wave chunk.
+		SweepForm f = p->coop;
+		if (!few_rows) f.nch = p->single.nch;
+		return f;
+	}
+	if (p->use_db[kind]) return p->db;
+	if (p->use_pair[kind]) return p->pair;
+	SweepForm f = few_rows ? p->few : p->single;
+	f.fn = single_wave_pipelined(p, kind) ? p->sweep.pf : p->sweep.fn;
+	return f;
+}
+
 // defer_join: leave the ordered sums of the extreme rows running on the side stream when the call returns
 // (p->join_pending); the caller joins before anything reads the new generation.
 int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 {
 	mf::SweepArgs a;
 	a.K = p->K;
-	a.nch = p->nch;
 	a.stride = p->stride;
 	a.seed = seed;
 	a.prio_len = p->prio_len[kind];
@@ -235,22 +227,13 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	a.scratch = nullptr;
 	a.scratch_entries = 0;
 	if (a.nrows <= 0) return MF_OK;
+	const bool extreme = p->n_long[kind] > 0;
 	// "few rows": the launch cannot fill the chip whatever the chunk size, its time is the longest row's serial chain
 	// of chunks -> the largest chunk.  Only below ~2048 rows: at 3952 rows (the cfg3 item sweep) the large chunk's LDS
-	// footprint cost more occupancy than it saved (item sweep 0.189 -> 0.123 ms with the ordinary chunk).
-	const bool few_rows = a.nrows < p->cfg.sweep_few;
-	const bool coop = p->coop_all[kind];
-	const bool db = !coop && p->use_db[kind];
-	const bool pair = !coop && !db && p->use_pair[kind];
-	const bool trio = pair && p->use_trio[kind] && p->sweep.trio;
-	if (few_rows) a.nch = coop ? p->nch_coop : p->nch_few;
-	if (db) a.nch = p->nch_db;
-	if (pair) a.nch = trio ? p->nch_trio : p->nch_pair;
-	const size_t lds = coop ? p->lds_bytes_coop : db ? p->lds_bytes_db : trio ? p->lds_bytes_trio : pair ? p->lds_bytes_pair : (few_rows ? p->lds_bytes_few : p->lds_bytes);
-	const SweepFn single = single_wave_pipelined(p, kind) ? p->sweep.pf : p->sweep.fn;   // accumulate form of the single-wave launch
-	const SweepFn fn = coop ? p->sweep.coop : db ? p->sweep.db : trio ? p->sweep.trio : pair ? p->sweep.pair : single;
-	const int block = coop ? mf::kCoopWaves * mf::kWave : trio ? 3 * mf::kWave : pair ? p->pair_waves * mf::kWave : mf::kWave;
-	const int grid = std::min(a.nrows, 1 << 20);
+	// footprint cost more occupancy than it saved (item sweep 0.189 -> 0.123 ms with the ordinary chunk).  Never beside
+	// the extreme-row path: with the extreme rows gone the occupancy-friendly chunk size is right again.
+	const SweepForm f = main_form(p, kind, !extreme && a.nrows < p->cfg.sweep_few);
+	a.nch = f.nch;
 	TimedLaunch t{};
 	if (p->timing) {
 		MF_HIP(hipEventCreate(&t.t0));
@@ -259,14 +242,14 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 		MF_HIP(hipEventRecord(t.t0, p->stream));
 	}
 	void *args[] = {&a};
-	if (p->n_long[kind] > 0) {
+	if (extreme) {
 		// extreme rows: products kernel over their 256-entry segments -> ordered sum per (row, column slice),
 		// beside the sweep of the other rows (schedule below)
 		mf::SweepArgs b = a;
 		b.nrows = p->n_seg[kind];
 		b.prio_len = 0;
 		b.rowlist = nullptr;
-		b.nch = p->nch_prod;
+		b.nch = p->prod.nch;
 		b.seg_row = p->seg_row[kind];
 		b.seg_beg = p->seg_beg[kind];
 		b.seg_end = p->seg_end[kind];
@@ -299,8 +282,7 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 			MF_HIP(hipEventRecord(p->ev_fork, p->stream));
 			MF_HIP(hipStreamWaitEvent(p->side_stream, p->ev_fork, 0));
 		}
-		MF_HIP(hipLaunchKernel((const void *) p->sweep.prod, dim3(b.nrows), dim3(mf::kWave), bargs, p->lds_bytes_prod,
-		                       prod_stream));
+		MF_HIP(hipLaunchKernel((const void *) p->prod.fn, dim3(b.nrows), dim3(p->prod.block), bargs, p->prod.lds, prod_stream));
 		if (under) {
 			MF_HIP(hipEventRecord(p->ev_fork, p->stream));
 			MF_HIP(hipStreamWaitEvent(p->side_stream, p->ev_fork, 0));
@@ -309,45 +291,16 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 		                       dim3(o.nrows * o.nslices), dim3(mf::kWave), oargs,
 		                       p->lds_bytes_osum, p->side_stream));
 		MF_HIP(hipEventRecord(p->ev_join, p->side_stream));
-		if (p->n_mid[kind] > 0) {
-			// mid-length rows: double-buffered form with the large chunk, on its own stream beside everything else
-			mf::SweepArgs m = a;
-			m.nrows = p->n_mid[kind];
-			m.rowlist = p->mid_rows[kind];
-			m.nch = p->nch_mid;
-			void *margs[] = {&m};
-			MF_HIP(hipStreamWaitEvent(p->mid_stream, p->ev_fork, 0));
-			if (p->mid_coop)
-				MF_HIP(hipLaunchKernel((const void *) p->sweep.coop, dim3(m.nrows), dim3(mf::kCoopWaves * mf::kWave), margs, p->lds_bytes_mid, p->mid_stream));
-			else
-			MF_HIP(hipLaunchKernel((const void *) p->sweep.db, dim3(m.nrows), dim3(mf::kWave), margs, p->lds_bytes_mid, p->mid_stream));
-			MF_HIP(hipEventRecord(p->ev_mid_join, p->mid_stream));
-		}
 		a.nrows = p->n_short[kind];
 		a.rowlist = p->short_rows[kind];
-		a.nch = p->nch;   // the extreme rows are gone: the occupancy-friendly chunk size is right again
-		if (a.nrows > 0 && p->rest_coop) {
-			a.nch = p->nch_coop;
-			MF_HIP(hipLaunchKernel((const void *) p->sweep.coop, dim3(std::min(a.nrows, 1 << 20)),
-			                       dim3(mf::kCoopWaves * mf::kWave), args, p->lds_bytes_coop, p->stream));
-		} else if (a.nrows > 0 && pair) {
-			a.nch = trio ? p->nch_trio : p->nch_pair;
-			MF_HIP(hipLaunchKernel((const void *) (trio ? p->sweep.trio : p->sweep.pair), dim3(std::min(a.nrows, 1 << 20)),
-			                       dim3((trio ? 3 : p->pair_waves) * mf::kWave), args, trio ? p->lds_bytes_trio : p->lds_bytes_pair, p->stream));
-		} else if (a.nrows > 0 && db) {
-			a.nch = p->nch_db;
-			MF_HIP(hipLaunchKernel((const void *) p->sweep.db, dim3(std::min(a.nrows, 1 << 20)), dim3(mf::kWave), args,
-			                       p->lds_bytes_db, p->stream));
-		} else if (a.nrows > 0)
-			MF_HIP(hipLaunchKernel((const void *) single, dim3(std::min(a.nrows, 1 << 20)), dim3(mf::kWave), args,
-			                       p->lds_bytes, p->stream));
-		if (p->n_mid[kind] > 0) MF_HIP(hipStreamWaitEvent(p->stream, p->ev_mid_join, 0));
+	}
+	if (a.nrows > 0)
+		MF_HIP(hipLaunchKernel((const void *) f.fn, dim3(std::min(a.nrows, 1 << 20)), dim3(f.block), args, f.lds, p->stream));
+	if (extreme) {
 		if (defer_join)
 			p->join_pending = true;
 		else
 			MF_HIP(hipStreamWaitEvent(p->stream, p->ev_join, 0));
-	} else {
-		MF_HIP(hipLaunchKernel((const void *) fn, dim3(grid), dim3(block), args, lds, p->stream));
 	}
 	if (p->timing) {
 		MF_HIP(hipEventRecord(t.t1, p->stream));

@@ -67,10 +67,10 @@ template <int KT, int NPASS>
 __global__ void __launch_bounds__(kWave) loss_dma_kernel(LossArgs a)
 {
 	const int K = KT > 0 ? KT : a.K;
-	const int P = K >> 1;                                   // 16-B pieces per row
-	constexpr int NP = NPASS;                               // DMA instructions per row
-	const int S = 16 * (P | 1);                             // tile row stride, odd multiple of 16 B
-	const int xs_bytes = ((K * 8 + 255) / 256) * 256;
+	const int P = dma_pieces(K);
+	constexpr int NP = NPASS;
+	const int S = dma_row_stride(K);
+	const int xs_bytes = dma_xs_bytes(K);
 	extern __shared__ __attribute__((aligned(16))) char lds[];
 	double2 *xs = reinterpret_cast<double2 *>(lds);
 	char *tile = lds + xs_bytes;
@@ -106,68 +106,40 @@ __global__ void __launch_bounds__(kWave) loss_dma_kernel(LossArgs a)
 				nx_idx = a.idx[c + nch + lane];
 				nx_val = a.val[c + nch + lane];
 			}
-			// ---- stage (sweep_dma_kernel): short rows several per instruction, the others one instruction per row and pass
-			constexpr bool kMultiRow = KT > 0 && ((KT / 2) | 1) <= 32;
-			if constexpr (kMultiRow) {
-				constexpr int PP = KT / 2, PS = PP | 1, RPI = kWave / PS;   // pieces, stride in pieces, rows per instruction
-				const int rr = lane / PS, piece = lane - rr * PS;
-				for (int n0 = 0; n0 < cnt; n0 += RPI) {
-					const int n = n0 + rr;
-					const int j = __shfl(my_idx, n < cnt ? n : 0);
-					const char *src = reinterpret_cast<const char *>(ybase) + (size_t) (unsigned) j * ybytes + 16 * piece;
-					if (rr < RPI && piece < PP && n < cnt)
-						__builtin_amdgcn_global_load_lds((mf_gvoid *) src, (mf_lvoid *) (tile + n0 * S), 16, 0, 0);
-				}
-			} else
-			for (int n = 0; n < cnt; ++n) {
-				const int j = __builtin_amdgcn_readlane(my_idx, n);
-				unsigned long long base = ybase + (unsigned long long) (unsigned) j * (unsigned long long) ybytes;
-				asm volatile("" : "+s"(base));   // keep the row base scalar
-#pragma unroll
-				for (int p = 0; p < NP; ++p) {
-					const char *src = reinterpret_cast<const char *>(base) + voff + 1024u * p;
-					if (lane + kWave * p < P)
-						__builtin_amdgcn_global_load_lds((mf_gvoid *) src, (mf_lvoid *) (tile + n * S + 1024 * p), 16, 0, 0);
-				}
-			}
+			// ---- stage (as sweep_dma_kernel): short rows several per instruction, the others one instruction per row and pass
+			if constexpr (KT > 0 && dma_multi_row(KT))
+				gather_multi_row<KT>(ybase, ybytes, my_idx, cnt, lane, tile);
+			else
+				gather_rows<NP>(ybase, ybytes, my_idx, cnt, lane, voff, P, S, tile);
 			__syncthreads();   // single-wave workgroup: this is the vmcnt(0)/lgkmcnt(0) that retires the DMA
 			// ---- phase A (lanes beyond the tile re-read row 0; lanes >= cnt produce garbage that never enters the chain)
-			double q;
-			{
-				const double2 *t2 = reinterpret_cast<const double2 *>(tile + (lane < nch ? lane : 0) * S);
-				double dot = 0.0;
-				if (KT > 0) {
+			const double2 *t2 = reinterpret_cast<const double2 *>(tile + (lane < nch ? lane : 0) * S);
+			double dot = 0.0;
+			if constexpr (KT > 0) {
+				dot = phase_a_dot<KT>(t2, xs);
+			} else {
+				int i = 0;
+				for (; i + 4 <= P; i += 4) {
+					double2 t[4], x[4];
 #pragma unroll
-					for (int i = 0; i < KT / 2; ++i) {
-						const double2 t = t2[i];
-						const double2 x = xs[i];
-						dot = dot + x.x * t.x;
-						dot = dot + x.y * t.y;
+					for (int u = 0; u < 4; ++u) {
+						t[u] = t2[i + u];
+						x[u] = xs[i + u];
 					}
-				} else {
-					int i = 0;
-					for (; i + 4 <= P; i += 4) {
-						double2 t[4], x[4];
 #pragma unroll
-						for (int u = 0; u < 4; ++u) {
-							t[u] = t2[i + u];
-							x[u] = xs[i + u];
-						}
-#pragma unroll
-						for (int u = 0; u < 4; ++u) {
-							dot = dot + x[u].x * t[u].x;
-							dot = dot + x[u].y * t[u].y;
-						}
-					}
-					for (; i < P; ++i) {
-						const double2 t = t2[i];
-						const double2 x = xs[i];
-						dot = dot + x.x * t.x;
-						dot = dot + x.y * t.y;
+					for (int u = 0; u < 4; ++u) {
+						dot = dot + x[u].x * t[u].x;
+						dot = dot + x[u].y * t[u].y;
 					}
 				}
-				q = loss_square(my_val, dot);
+				for (; i < P; ++i) {
+					const double2 t = t2[i];
+					const double2 x = xs[i];
+					dot = dot + x.x * t.x;
+					dot = dot + x.y * t.y;
+				}
 			}
+			const double q = loss_square(my_val, dot);
 			s = loss_chain(s, q, cnt);
 			__syncthreads();   // tile is overwritten by the next chunk's DMA
 		}

@@ -23,42 +23,38 @@ inline hipError_t raise_lds_limit(const void *fn, size_t bytes)
 	return e;
 }
 
+// One K's kernels.  Filled by name: a form a K does not have stays null.
 struct SweepVariant {
-	SweepFn fn;
-	int kt;         // compile-time K, 0 = runtime K
-	int kpmax;      // 64-column groups held in registers (register-staged form)
-	int dma;        // 1: LDS-DMA form
-	int row_bytes;  // LDS tile row stride in bytes (DMA form)
-	int xs_bytes;   // LDS bytes in front of the tile (DMA form)
-	SweepFn coop;   // row-cooperative form for tiny sweeps (compile-time-K DMA variants only)
-	SweepFn prod;   // products form for segments of extreme rows (all DMA variants)
-	SweepFn errs;   // errors form: e_n per entry of a segment (all DMA variants; mf_stream.hip.h)
-	SweepFn db;     // intra-wave double-buffered form for launches of few rows (all DMA variants)
-	SweepFn pf;     // accumulate form with the LDS reads of phases A / B kept in flight (compile-time-K DMA variants)
-	SweepFn pair;   // wave-pair form (loader + compute) for launches that end on long rows (64 <= K <= 128, compile-time K)
-	SweepFn pair2;  // ... with two loader waves
-	SweepFn trio = nullptr;   // ... with the compute wave split into a phase-A and a phase-B wave (three waves per row)
+	SweepFn fn = nullptr;
+	int kt = 0;         // compile-time K, 0 = runtime K
+	int kpmax = 0;      // 64-column groups held in registers (register-staged form) / DMA passes per row (run-time-K DMA form)
+	int dma = 0;        // 1: LDS-DMA form
+	int row_bytes = 0;  // LDS tile row stride in bytes (DMA form)
+	int xs_bytes = 0;   // LDS bytes in front of the tile (DMA form)
+	SweepFn coop = nullptr;   // row-cooperative form for tiny sweeps (compile-time-K DMA variants only)
+	SweepFn prod = nullptr;   // products form for segments of extreme rows (all DMA variants)
+	SweepFn errs = nullptr;   // errors form: e_n per entry of a segment (all DMA variants; mf_stream.hip.h)
+	SweepFn db = nullptr;     // intra-wave double-buffered form for launches of few rows (all DMA variants)
+	SweepFn pf = nullptr;     // accumulate form with the LDS reads of phases A / B kept in flight (compile-time-K DMA variants)
+	SweepFn pair = nullptr;   // wave-pair form (loader + compute) for launches that end on long rows (64 <= K <= 128, compile-time K)
+	LossFn loss = nullptr;    // row sums of mf_plan_loss in the same geometry (all DMA variants; the others use loss_reg_kernel)
 };
 
 template <int KT, int KP>
 constexpr SweepVariant variant()
 {
-	return SweepVariant{mf::sweep_kernel<KT, KP>, KT, KP, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+	SweepVariant v;
+	v.fn = mf::sweep_kernel<KT, KP>;
+	v.kt = KT;
+	v.kpmax = KP;
+	return v;
 }
 
-template <int KT, int NL>
+template <int KT>
 constexpr SweepFn pair_fn()
 {
-	if constexpr (mf::DmaGeom<KT>::kPasses == 1 && (mf::DmaGeom<KT>::kPieces | 1) > 32)
-		return mf::sweep_pair_kernel<KT, NL>;
-	else
-		return nullptr;
-}
-template <int KT>
-constexpr SweepFn trio_fn()
-{
-	if constexpr (mf::DmaGeom<KT>::kPasses == 1 && (mf::DmaGeom<KT>::kPieces | 1) > 32)
-		return mf::sweep_trio_kernel<KT>;
+	if constexpr (mf::DmaGeom<KT>::kOnePassWide)
+		return mf::sweep_pair_kernel<KT, 1>;
 	else
 		return nullptr;
 }
@@ -66,29 +62,45 @@ constexpr SweepFn trio_fn()
 template <int KT>
 constexpr SweepVariant dma_variant()
 {
-	return SweepVariant{mf::sweep_dma_kernel<KT, mf::DmaGeom<KT>::kPasses>, KT, 0, 1, mf::DmaGeom<KT>::kStride,
-	                    mf::DmaGeom<KT>::kXsBytes, mf::sweep_coop_kernel<KT>,
-	                    mf::sweep_dma_kernel<KT, mf::DmaGeom<KT>::kPasses, mf::kSweepProducts>,
-	                    mf::sweep_dma_kernel<KT, mf::DmaGeom<KT>::kPasses, mf::kSweepErrors>,
-	                    mf::sweep_db_kernel<KT, mf::DmaGeom<KT>::kPasses>,
-	                    mf::sweep_dma_kernel<KT, mf::DmaGeom<KT>::kPasses, mf::kSweepAccumulate, 8>, pair_fn<KT, 1>(),
-#ifdef MF_EXPERIMENTS
-	                    pair_fn<KT, 2>(),   // two loader waves: measured within noise of one (the compute wave is the bound)
-	                    trio_fn<KT>()       // loader / phase-A / phase-B waves: measured slower wherever it was tried
-#else
-	                    nullptr, nullptr
-#endif
-	};
+	constexpr int NP = mf::DmaGeom<KT>::kPasses;
+	SweepVariant v;
+	v.fn = mf::sweep_dma_kernel<KT, NP>;
+	v.kt = KT;
+	v.dma = 1;
+	v.row_bytes = mf::DmaGeom<KT>::kStride;
+	v.xs_bytes = mf::DmaGeom<KT>::kXsBytes;
+	v.coop = mf::sweep_coop_kernel<KT>;
+	v.prod = mf::sweep_dma_kernel<KT, NP, mf::kSweepProducts>;
+	v.errs = mf::sweep_dma_kernel<KT, NP, mf::kSweepErrors>;
+	v.db = mf::sweep_db_kernel<KT, NP>;
+	v.pf = mf::sweep_dma_kernel<KT, NP, mf::kSweepAccumulate, 8>;
+	v.pair = pair_fn<KT>();
+	v.loss = mf::loss_dma_kernel<KT, NP>;
+	return v;
 }
 
 // run-time even K <= 128 * NPASS through the LDS-DMA kernel (row_bytes / xs_bytes filled in per plan)
 template <int NPASS>
 constexpr SweepVariant dma_generic_variant()
 {
-	return SweepVariant{mf::sweep_dma_kernel<0, NPASS>, 0, NPASS, 1, 0, 0, nullptr,
-	                    mf::sweep_dma_kernel<0, NPASS, mf::kSweepProducts>, mf::sweep_dma_kernel<0, NPASS, mf::kSweepErrors>,
-	                    mf::sweep_db_kernel<0, NPASS>, nullptr, nullptr, nullptr};
+	SweepVariant v;
+	v.fn = mf::sweep_dma_kernel<0, NPASS>;
+	v.kpmax = NPASS;
+	v.dma = 1;
+	v.prod = mf::sweep_dma_kernel<0, NPASS, mf::kSweepProducts>;
+	v.errs = mf::sweep_dma_kernel<0, NPASS, mf::kSweepErrors>;
+	v.db = mf::sweep_db_kernel<0, NPASS>;
+	v.loss = mf::loss_dma_kernel<0, NPASS>;
+	return v;
 }
+
+// One launchable form of a sweep: its kernel, entries per chunk, LDS request and workgroup size.
+struct SweepForm {
+	SweepFn fn = nullptr;
+	int nch = 0;
+	size_t lds = 0;
+	int block = mf::kWave;
+};
 
 // K-specialised instances for the K of the bundled samples and of the BASELINE configs, then generic ones.
 const SweepVariant kSpecialised[] = {
@@ -227,32 +239,17 @@ struct mf_plan {
 	int rank_form = -1;                 // form of the last rank call (mf_plan_rank_heldout_info)
 
 	SweepVariant sweep{};
-	int nch = 0, stride = 0;
-	size_t lds_bytes = 0;
-	int nch_few = 0;            // chunk size when a sweep has too few rows to fill the chip (see choose_sweep)
-	size_t lds_bytes_few = 0;
-	int nch_db = 0;             // chunk size and LDS request (two tiles) of the double-buffered form
-	size_t lds_bytes_db = 0;
+	int stride = 0;             // register-staged form: LDS row stride in doubles
+	// the forms of a sweep's main launch (launch_sweep: main_form); `single` and `few` leave fn to the side (plain or
+	// pipelined accumulate form, single_wave_pipelined)
+	SweepForm single;           // single-wave form at the chunk size of choose_sweep
+	SweepForm few;              // ... at the chunk size for a sweep of too few rows to fill the chip
+	SweepForm db;               // double-buffered form (two tiles)
+	SweepForm pair;             // wave-pair form (two tiles, two waves per row)
+	SweepForm coop;             // tiny sweeps (a few us of data): ONE cooperative launch over all rows; a fork/join costs more than it saves
+	SweepForm prod;             // products launch over the segments of the extreme rows
 	bool use_db[2] = {false, false};   // the sweep's single-wave launch takes the double-buffered form (plan_row_schedule)
 	bool use_pair[2] = {false, false}; // ... or the wave-pair form
-	int nch_pair = 0;
-	int pair_waves = 2;   // waves per row of the pair form in use: 2 (loader + compute), 3 with two loaders
-	bool use_trio[2] = {false, false};   // ... that side's pairs as loader / phase-A / phase-B trios (three tiles)
-	int nch_trio = 0;
-	size_t lds_bytes_trio = 0;
-	int pair_loaders = 1;   // loader waves of the wave-pair form
-	size_t lds_bytes_pair = 0;
-	// mid-length rows of a skewed sweep (below the extreme threshold, far above the mean): their own launch of the
-	// double-buffered form with a LARGE chunk on a second side stream -- a wave that keeps 48 rows in flight gets a
-	// matching share of its CU's gather rate instead of 1/11 of it, so the walk of the longest remaining row no longer
-	// sets the sweep's time
-	dev_buf<int> mid_rows[2];
-	int n_mid[2] = {0, 0};
-	int nch_mid = 0;
-	size_t lds_bytes_mid = 0;
-	bool mid_coop = false;   // the mid-length rows go through the row-cooperative kernel (8 waves per row) instead
-	hipStream_t mid_stream = nullptr;
-	hipEvent_t ev_mid_join = nullptr;
 	int max_row_len[2] = {0, 0}; // longest column (item sweep) / longest user row (user sweep)
 	int prio_len[2] = {0, 0};    // rows at least this long run at raised wave priority in the single-wave launch (0: none)
 	// skew-aware split of a sweep with many rows: rows whose serial walk would dominate the launch go to the
@@ -268,13 +265,7 @@ struct mf_plan {
 	dev_buf<int> lr_cnt[2];
 	dev_buf<double> scratch;
 	size_t scratch_entries = 0;
-	// tiny sweeps (a few us of data): ONE cooperative launch over all rows; a fork/join costs more than it saves
-	int nch_coop = 0;
-	bool rest_coop = false;     // rows beside the extreme ones go through the cooperative kernel (experiment)
-	int nch_prod = 0;           // chunk size of the products launch (extreme rows)
-	size_t lds_bytes_prod = 0;
 	size_t lds_bytes_osum = 0;  // LDS request of ordered_sum_kernel (ring + padding that bounds the waves per CU)
-	size_t lds_bytes_coop = 0;
 	bool coop_all[2] = {false, false};
 	hipStream_t side_stream = nullptr;
 	hipEvent_t ev_fork = nullptr, ev_join = nullptr;

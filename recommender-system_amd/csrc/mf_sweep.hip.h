@@ -67,12 +67,15 @@ __device__ __forceinline__ double readlane_f64(double v, int lane)
 	return __hiloint2double(hi, lo);
 }
 
+// LDS row stride of the register-staged form in doubles: odd, so both access patterns are bank-conflict-free
+__host__ __device__ constexpr int reg_row_stride(int K) { return K | 1; }
+
 template <int KT, int KPMAX>
 __global__ void __launch_bounds__(kWave) sweep_kernel(SweepArgs a)
 {
 	extern __shared__ double tile[];
 	const int K = KT > 0 ? KT : a.K;
-	const int stride = KT > 0 ? (KT | 1) : a.stride;
+	const int stride = KT > 0 ? reg_row_stride(KT) : a.stride;
 	const int nch = a.nch;
 	const int lane = threadIdx.x;
 
@@ -147,28 +150,29 @@ __global__ void __launch_bounds__(kWave) sweep_kernel(SweepArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Sweep kernel, LDS-DMA form (the production kernel for even, compile-time K).
-// Same arithmetic, same order, as sweep_kernel above; what changes is how the bytes move:
-//   stage   one `global_load_lds_dwordx4` per gathered row (K/2 lanes x 16 B, per-lane source address,
-//           wave-uniform LDS row base): the whole chunk -- up to 64 rows, 51 KB at K=100 -- is in flight
-//           at once with no VGPR staging and no ds_write; one vmcnt(0) retires it.
-//   tile    row stride = 16 B x (odd), so phase A's ds_read_b128 (lane n -> row n, 16-lane groups) is
-//           bank-conflict-free while every row stays 16-B aligned for the DMA.
-//   phase A lane n: 16 B of its row + 16 B of x (LDS broadcast) per step, two sequential mul/add pairs.
-//   phase B lane l owns columns 2l, 2l+1 (+128 per pass): one ds_read_b128 per entry and pass, entries
-//           in order, e_n broadcast through v_readlane into a scalar operand.
-// LDS: [ x row: XS bytes ][ tile: nch rows x S bytes ].
+// The LDS-DMA forms: their tile geometry, the pieces they share, then the kernels.
 // ------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(1))) const void mf_gvoid;
 typedef __attribute__((address_space(3))) void mf_lvoid;
 
+// ---- Tile geometry of the LDS-DMA forms for an even K, on the host and on the device, at compile time or at run
+// time.  These functions are the only place the formulas are written.
+__host__ __device__ constexpr int dma_pieces(int K) { return K >> 1; }                                  // 16-B pieces per row
+__host__ __device__ constexpr int dma_passes(int K) { return (dma_pieces(K) + kWave - 1) / kWave; }     // DMA instructions per row
+__host__ __device__ constexpr int dma_stride_pieces(int K) { return dma_pieces(K) | 1; }                // tile row stride in pieces: odd
+__host__ __device__ constexpr int dma_row_stride_of(int pieces) { return 16 * (pieces | 1); }           // tile row stride in bytes: odd multiple of 16
+__host__ __device__ constexpr int dma_row_stride(int K) { return dma_row_stride_of(dma_pieces(K)); }
+__host__ __device__ constexpr int dma_xs_bytes(int K) { return ((K * 8 + 255) / 256) * 256; }           // the x row in front of the tile
+__host__ __device__ constexpr bool dma_multi_row(int K) { return dma_stride_pieces(K) <= 32; }          // K <= 62: several rows fit one instruction
+
 template <int KT>
 struct DmaGeom {
 	static_assert(KT % 2 == 0 && KT >= 2, "LDS-DMA sweep needs an even K");
-	static constexpr int kPieces = KT / 2;                        // 16-B pieces per row
-	static constexpr int kPasses = (kPieces + kWave - 1) / kWave; // DMA instructions per row
-	static constexpr int kStride = 16 * (kPieces | 1);            // bytes, odd multiple of 16
-	static constexpr int kXsBytes = ((KT * 8 + 255) / 256) * 256;
+	static constexpr int kPieces = dma_pieces(KT);
+	static constexpr int kPasses = dma_passes(KT);
+	static constexpr int kStride = dma_row_stride(KT);
+	static constexpr int kXsBytes = dma_xs_bytes(KT);
+	static constexpr bool kOnePassWide = kPasses == 1 && !dma_multi_row(KT);   // one LDS-DMA instruction per gathered row (64 <= K <= 128)
 };
 
 // Extreme-row scratch geometry: the scaled rows are stored [slice of kSliceCols columns][entry][kSliceCols doubles];
@@ -182,10 +186,163 @@ constexpr int kSliceShift = kSliceCols == 8 ? 3 : 4;  // log2(kSliceCols)
 constexpr int kPieceShift = kSliceShift - 1;
 static_assert(kSliceCols == 8 || kSliceCols == 16, "slice width");
 
+// ------------------------------------------------------------------------------------------------
+// Pieces of the LDS-DMA kernels, each stated once, all __forceinline__: the row prologue and write-out, the gathers,
+// phase A for a compile-time K and phase B.  sweep_dma_kernel, sweep_db_kernel, sweep_pair_kernel, sweep_coop_kernel and
+// loss_dma_kernel (mf_loss.hip.h) are assembled from them.  Three things stay written in the single-wave kernels that have
+// them, because hipcc optimises a helper before it inlines it and these came out with other VECTOR code: the run-time-K
+// phase A (one more v_mov_b64 and a branch in every <0, NPASS> instance), the row prologue of sweep_dma_kernel and
+// sweep_db_kernel (the accumulators by reference: another register allocation) and the one-chunk-ahead load of (idx, val)
+// (an s_waitcnt moves into the chunk loop).  profiles/sweep_parts/README.md has the comparison with the code before.
+// ------------------------------------------------------------------------------------------------
+
+// Row prologue: the owned X row goes to `xs` (phase A reads it as an LDS broadcast) and seeds the accumulators (zero
+// without `seed`, and in the lanes beyond the row).
+template <int NP>
+__device__ __forceinline__ void load_x_row(const double2 *__restrict__ xrow2, double2 *xs, int lane, int P, int seed, double2 (&acc)[NP])
+{
+#pragma unroll
+	for (int p = 0; p < NP; ++p) {
+		const int q = lane + kWave * p;
+		double2 v = make_double2(0.0, 0.0);
+		if (q < P) {
+			v = xrow2[q];
+			xs[q] = v;
+		}
+		acc[p] = seed ? v : make_double2(0.0, 0.0);
+	}
+}
+
+// Write-out: lane l holds columns 2l, 2l+1 (+128 per pass) of the new row.
+template <int NP>
+__device__ __forceinline__ void store_x_row(double2 *__restrict__ out2, int lane, int P, const double2 (&acc)[NP])
+{
+#pragma unroll
+	for (int p = 0; p < NP; ++p) {
+		const int q = lane + kWave * p;
+		if (q < P) out2[q] = acc[p];
+	}
+}
+
+// ---- The gathers: rows idx_0 .. idx_{cnt-1} of Y (lane n holds idx_n) -> rows 0 .. cnt-1 of an LDS tile.
+// gather_multi_row and gather_rows issue the transfer as the builtin: hipcc tracks it and waits for it in front of
+// whatever may read the tile.  With M0 = true (sweep_db_kernel) they issue it through lds_dma_m0, and gather_lean always
+// does: from inline asm with the LDS row base in M0 (a reserved register: hipcc re-loads it before each of its own uses).
+// hipcc knows NOTHING of such a transfer, so it does not drain vmcnt in front of every LDS read that might alias it, and
+// the kernel waits by hand.
+__device__ __forceinline__ unsigned lds_address(const char *p)
+{
+	return (unsigned) (unsigned long long) (__attribute__((address_space(3))) const char *) p;
+}
+
+__device__ __forceinline__ void lds_dma_m0(const char *src, unsigned m0)
+{
+	asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(m0) : "memory");
+}
+
+// Several rows per instruction, for short rows (K <= 62): lane -> (row lane / PS, piece lane % PS) with PS = the tile row
+// stride in pieces (P, or P + 1 when P is even: that lane is the padding and stays off), 12 rows at K=10, 5 at K=20 --
+// instead of one instruction with five active lanes per row.
+template <int KT, bool M0 = false>
+__device__ __forceinline__ void gather_multi_row(unsigned long long ybase, size_t ybytes, int idx, int cnt, int lane, char *tile)
+{
+	constexpr int PP = dma_pieces(KT), PS = dma_stride_pieces(KT), RPI = kWave / PS, S = dma_row_stride(KT);   // pieces, stride in pieces, rows per instruction
+	const int rr = lane / PS, piece = lane - rr * PS;
+	for (int n0 = 0; n0 < cnt; n0 += RPI) {
+		const int n = n0 + rr;
+		const int j = __shfl(idx, n < cnt ? n : 0);
+		const char *src = reinterpret_cast<const char *>(ybase) + (size_t) (unsigned) j * ybytes + 16 * piece;
+		if constexpr (M0) {
+			const unsigned m0 = __builtin_amdgcn_readfirstlane(lds_address(tile) + (unsigned) (n0 * S));
+			if (rr < RPI && piece < PP && n < cnt) lds_dma_m0(src, m0);
+		} else if (rr < RPI && piece < PP && n < cnt)
+			__builtin_amdgcn_global_load_lds((mf_gvoid *) src, (mf_lvoid *) (tile + n0 * S), 16, 0, 0);
+	}
+}
+
+// One row per group of NP instructions (P pieces of 16 B, 64 per instruction): v_readlane of the index, the row base
+// as a scalar pair, the lane's 16-byte offset as the vector part.
+template <int NP, bool M0 = false>
+__device__ __forceinline__ void gather_rows(unsigned long long ybase, unsigned long long ybytes, int idx, int cnt, int lane, unsigned voff, int P, int S, char *tile)
+{
+	for (int n = 0; n < cnt; ++n) {
+		const int j = __builtin_amdgcn_readlane(idx, n);
+		unsigned long long base = ybase + (unsigned long long) (unsigned) j * ybytes;
+		asm volatile("" : "+s"(base));   // keep the row base scalar
+#pragma unroll
+		for (int p = 0; p < NP; ++p) {
+			const char *src = reinterpret_cast<const char *>(base) + voff + 1024u * p;
+			if constexpr (M0) {
+				const unsigned m0 = __builtin_amdgcn_readfirstlane(lds_address(tile) + (unsigned) (n * S + 1024 * p));
+				if (lane + kWave * p < P) lds_dma_m0(src, m0);
+			} else if (lane + kWave * p < P)
+				__builtin_amdgcn_global_load_lds((mf_gvoid *) src, (mf_lvoid *) (tile + n * S + 1024 * p), 16, 0, 0);
+		}
+	}
+}
+
+// Lean issue (a wave walking a long row alone is bound by its own instruction stream, ~17 instructions per gathered row
+// in gather_rows): every lane forms the address of ITS entry's row once per chunk (one 64-bit multiply-add per chunk
+// instead of four scalar multiplies per row); per row two v_readlane give the row base as a scalar pair and the transfer
+// takes it as its scalar address with the lane's 16-byte offset as the vector part.  The asm opens with s_nop 4: an SGPR
+// written by v_readlane needs five wait states before a VMEM instruction reads it as its address, and hipcc pads nothing
+// inside an asm statement.
+// TWO (K = 256: two 1-KiB instructions per row, all lanes active in both): the second one is the first with offset:1024
+// -- the instruction offset of an LDS-DMA load moves the LDS side as well as the global one
+// (tools/micro/lds_dma_offset.hip), so neither M0 nor the base is touched between the two.
+// hipcc knows nothing of these transfers: the caller waits for them (s_waitcnt vmcnt(0)) by hand.
+template <bool TWO>
+__device__ __forceinline__ void lds_dma_lean(unsigned long long base, unsigned dst, unsigned voff)
+{
+	if constexpr (TWO)
+		asm volatile("s_nop 4\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %0\n\t"
+		             "global_load_lds_dwordx4 %2, %0 offset:1024"
+		             :
+		             : "s"(base), "s"(dst), "v"(voff)
+		             : "memory");
+	else
+		asm volatile("s_nop 4\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %0"
+		             :
+		             : "s"(base), "s"(dst), "v"(voff)
+		             : "memory");
+}
+
+// Rows first, first + step, ... in groups of four (the eight v_readlane of a group in front of its four transfers), and
+// the last, partial group of four row by row: it belongs to the caller it falls to (one loader: first = 0, step = 4).
+// `active`: this lane holds a piece of the row.
+template <bool TWO>
+__device__ __forceinline__ void gather_lean(unsigned long long ybase, unsigned long long ybytes, int idx, int first, int step, int cnt,
+                                            bool active, unsigned tile_lds, int S, unsigned voff)
+{
+	const unsigned long long rowaddr = ybase + (unsigned long long) (unsigned) idx * ybytes;
+	const int alo = (int) (unsigned) rowaddr, ahi = (int) (unsigned) (rowaddr >> 32);
+	auto row_base = [&](int n) {
+		return ((unsigned long long) (unsigned) __builtin_amdgcn_readlane(ahi, n) << 32) |
+		       (unsigned long long) (unsigned) __builtin_amdgcn_readlane(alo, n);
+	};
+	int n = first;
+	for (; n + 4 <= cnt; n += step) {
+		unsigned long long b[4];
+#pragma unroll
+		for (int u = 0; u < 4; ++u) b[u] = row_base(n + u);
+		if (active) {
+#pragma unroll
+			for (int u = 0; u < 4; ++u) lds_dma_lean<TWO>(b[u], tile_lds + (unsigned) ((n + u) * S), voff);
+		}
+	}
+	for (int m = n; m < min(n + 4, cnt); ++m) {
+		const unsigned long long b = row_base(m);
+		if (active) lds_dma_lean<TWO>(b, tile_lds + (unsigned) (m * S), voff);
+	}
+}
+
+// ---- Phase A.  Lane n walks row n of the tile (t2) against the x row (xs, an LDS broadcast): 16 B of each per step,
+// two sequential multiply/add pairs.  Every form below is the same operations in the same order: same bits.
+//
 // Phase A / phase B with the LDS reads kept IN FLIGHT (PF steps / PB entries ahead) instead of the two steps per round
 // trip hipcc schedules by itself (it aims at 64 registers): one wave walking a long row alone -- the tail of every launch of
 // a few thousand rows -- is bound by the LDS latency of these reads, 25 round trips per chunk at K=100, not by the chain of
-// dependent adds.  Same operations in the same order: same bits.  Empty asm statements with a memory clobber keep the reads where they
+// dependent adds.  Empty asm statements with a memory clobber keep the reads where they
 // are written (a sched_barrier does not: the loads are hoisted above it before the machine scheduler runs).
 template <int Q, int PF>
 __device__ __forceinline__ double phase_a_dot_pipelined(const double2 *t2, const double2 *xs)
@@ -212,6 +369,146 @@ __device__ __forceinline__ double phase_a_dot_pipelined(const double2 *t2, const
 	return dot;
 }
 
+template <int Q, int PF>
+__device__ __forceinline__ double phase_a_dot_ahead(const double2 *t2, const double2 *xs)
+{
+	// as phase_a_dot_pipelined, and the two products of step q+1 are formed before the two adds of step q: the chain of
+	// dependent adds never waits for a multiply
+	double2 t[PF], x[PF];
+#pragma unroll
+	for (int i = 0; i < PF; ++i)
+		if (i < Q) {
+			t[i] = t2[i];
+			x[i] = xs[i];
+		}
+	double dot = 0.0;
+	double px = x[0].x * t[0].x, py = x[0].y * t[0].y;
+#pragma unroll
+	for (int q = 0; q < Q; ++q) {
+		double nx = 0.0, ny = 0.0;
+		if (q + 1 < Q) {
+			nx = x[(q + 1) % PF].x * t[(q + 1) % PF].x;
+			ny = x[(q + 1) % PF].y * t[(q + 1) % PF].y;
+		}
+		if (q + PF < Q) {
+			t[q % PF] = t2[q + PF];
+			x[q % PF] = xs[q + PF];
+		}
+		// (pinning the multiplies of step q+1 between the adds of steps q-1 and q with register operands on this statement
+		// was measured SLOWER -- a lone 5993-entry row 0.327 -> 0.347 ms --: hipcc's own placement, each multiply in front
+		// of its add, stays)
+		asm volatile("" ::: "memory");
+		dot = dot + px;
+		dot = dot + py;
+		px = nx;
+		py = ny;
+	}
+	return dot;
+}
+
+// The dot of a tile row with xs for a compile-time K, fully unrolled: plain (PF = 0), with PF steps' reads in flight, or
+// with the products formed one step ahead as well (AHEAD).  The run-time-K form (P pieces, by four, then a tail) stays
+// written in the three kernels that have run-time-K instances (see the head of this section).
+template <int KT, int PF = 0, bool AHEAD = false>
+__device__ __forceinline__ double phase_a_dot(const double2 *t2, const double2 *xs)
+{
+	static_assert(KT > 0, "compile-time K");
+	if constexpr (AHEAD) {
+		return phase_a_dot_ahead<KT / 2, PF>(t2, xs);
+	} else if constexpr (PF > 0) {
+		return phase_a_dot_pipelined<KT / 2, PF>(t2, xs);
+	} else {
+		double dot = 0.0;
+#pragma unroll
+		for (int q = 0; q < KT / 2; ++q) {
+			const double2 t = t2[q];
+			const double2 x = xs[q];
+			dot = dot + x.x * t.x;
+			dot = dot + x.y * t.y;
+		}
+		return dot;
+	}
+}
+
+// ---- Phase B.  Lane l owns columns 2l, 2l+1 (+128 per pass); tb = the tile + this lane's 16 bytes; entries in order,
+// e_n broadcast through v_readlane into a scalar operand: acc = acc + e_n * tile[n].  Each helper takes the entries from
+// n on that it can and returns the first one it left.
+//
+// Sixteen entries' reads in flight at once (one pass per row).  GUARD: lanes beyond the row (`active` false) read nothing
+// and add zeros; without it every lane reads (the caller points those lanes at piece 0: no branch masks).
+template <bool GUARD>
+__device__ __forceinline__ int phase_b_sixteen(const char *tb, int S, double e, int n, int cnt, bool active, double2 &acc)
+{
+	for (; n + 16 <= cnt; n += 16) {
+		double2 t[16];
+#pragma unroll
+		for (int u = 0; u < 16; ++u)
+			t[u] = (!GUARD || active) ? *reinterpret_cast<const double2 *>(tb + (n + u) * S) : make_double2(0.0, 0.0);
+		asm volatile("" ::: "memory");   // pins the issue order: the reads above go out before the arithmetic below
+#pragma unroll
+		for (int u = 0; u < 16; ++u) {
+			const double en = readlane_f64(e, n + u);
+			acc.x = acc.x + en * t[u].x;
+			acc.y = acc.y + en * t[u].y;
+		}
+	}
+	return n;
+}
+
+// Four entries at a time, every pass of each: the reads of a group in front of its arithmetic.
+template <int NP>
+__device__ __forceinline__ int phase_b_four(const char *tb, int S, double e, int n, int cnt, int lane, int P, double2 (&acc)[NP])
+{
+	for (; n + 4 <= cnt; n += 4) {
+		double2 t[4][NP];
+		double en[4];
+#pragma unroll
+		for (int u = 0; u < 4; ++u) {
+			en[u] = readlane_f64(e, n + u);
+#pragma unroll
+			for (int p = 0; p < NP; ++p)
+				t[u][p] = (lane + kWave * p < P) ? *reinterpret_cast<const double2 *>(tb + (n + u) * S + 1024 * p) : make_double2(0.0, 0.0);
+		}
+#pragma unroll
+		for (int u = 0; u < 4; ++u)
+#pragma unroll
+			for (int p = 0; p < NP; ++p) {
+				acc[p].x = acc[p].x + en[u] * t[u][p].x;
+				acc[p].y = acc[p].y + en[u] * t[u][p].y;
+			}
+	}
+	return n;
+}
+
+// The tail, entry by entry.
+template <int NP, bool GUARD>
+__device__ __forceinline__ void phase_b_tail(const char *tb, int S, double e, int n, int cnt, int lane, int P, double2 (&acc)[NP])
+{
+	for (; n < cnt; ++n) {
+		const double en = readlane_f64(e, n);
+#pragma unroll
+		for (int p = 0; p < NP; ++p)
+			if (!GUARD || lane + kWave * p < P) {
+				const double2 t = *reinterpret_cast<const double2 *>(tb + n * S + 1024 * p);
+				acc[p].x = acc[p].x + en * t.x;
+				acc[p].y = acc[p].y + en * t.y;
+			}
+	}
+}
+
+// ------------------------------------------------------------------------------------------------
+// Sweep kernel, LDS-DMA form (the production kernel for even K).
+// Same arithmetic, same order, as sweep_kernel above; what changes is how the bytes move:
+//   stage   one `global_load_lds_dwordx4` per gathered row (K/2 lanes x 16 B, per-lane source address,
+//           wave-uniform LDS row base): the whole chunk -- up to 64 rows, 51 KB at K=100 -- is in flight
+//           at once with no VGPR staging and no ds_write; one vmcnt(0) retires it.
+//   tile    row stride = 16 B x (odd), so phase A's ds_read_b128 (lane n -> row n, 16-lane groups) is
+//           bank-conflict-free while every row stays 16-B aligned for the DMA.
+//   phase A lane n: 16 B of its row + 16 B of x (LDS broadcast) per step, two sequential mul/add pairs.
+//   phase B lane l owns columns 2l, 2l+1 (+128 per pass): one ds_read_b128 per entry and pass, entries
+//           in order, e_n broadcast through v_readlane into a scalar operand.
+// LDS: [ x row: XS bytes ][ tile: nch rows x S bytes ].
+//
 // KT > 0: K is a compile-time constant (phase A fully unrolled).  KT == 0: any even K up to 128*NPASS at run
 // time (phase A unrolled by four) -- same data movement, so an unusual K does not fall back to the
 // register-staged kernel.
@@ -220,6 +517,8 @@ __device__ __forceinline__ double phase_a_dot_pipelined(const double2 *t2, const
 // entry order, and ordered_sum_kernel adds them up in that order afterwards.  Thousands of segments run in
 // parallel, so a row rated by every user costs a chip-wide pass plus one serial chain of adds.
 // MODE: 0 accumulate (the sweep), 1 products (extreme rows), 2 errors (first half of the errors + streams iteration)
+// PF > 0: phases A and B keep their LDS reads in flight and the gather issue is lean.
+// ------------------------------------------------------------------------------------------------
 constexpr int kSweepAccumulate = 0, kSweepProducts = 1, kSweepErrors = 2;
 #ifdef MF_STAMPS
 // diagnostic build only (tools/stamps.py): shader-clock totals of the phases of the rows of at least 1024 entries --
@@ -235,10 +534,10 @@ __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 {
 	constexpr bool PRODUCTS = MODE == kSweepProducts, ERRORS = MODE == kSweepErrors, SEGMENTS = MODE != kSweepAccumulate;
 	const int K = KT > 0 ? KT : a.K;
-	const int P = K >> 1;                                   // 16-B pieces per row
+	const int P = dma_pieces(K);
 	constexpr int NP = NPASS;                               // DMA instructions per row
-	const int S = 16 * (P | 1);                             // tile row stride, odd multiple of 16 B
-	const int xs_bytes = ((K * 8 + 255) / 256) * 256;
+	const int S = dma_row_stride_of(P);
+	const int xs_bytes = dma_xs_bytes(K);
 	extern __shared__ __attribute__((aligned(16))) char lds[];
 	double2 *xs = reinterpret_cast<double2 *>(lds);
 	char *tile = lds + xs_bytes;
@@ -297,74 +596,13 @@ __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 				nx_val = a.val[c + nch + lane];
 				if (ERRORS) nx_map = a.map[c + nch + lane];
 			}
-			// ---- stage.  Short rows (K <= 62) are gathered SEVERAL per instruction: lane -> (row lane / PS, piece
-			// lane % PS) with PS = the tile row stride in pieces (P, or P + 1 when P is even: that lane is the padding
-			// and stays off), 12 rows at K=10, 5 at K=20 -- instead of one instruction with five active lanes per row.
+			// ---- stage: short rows several per instruction, K <= 128 and K = 256 with PF by the lean issue, the others one
+			// group of NP instructions per row
 			MF_STAMP(t_s0);
-			constexpr bool kMultiRow = KT > 0 && ((KT / 2) | 1) <= 32;
-			if constexpr (kMultiRow) {
-				constexpr int PP = KT / 2, PS = PP | 1, RPI = kWave / PS;   // pieces, stride in pieces, rows per instruction
-				const int rr = lane / PS, piece = lane - rr * PS;
-				for (int n0 = 0; n0 < cnt; n0 += RPI) {
-					const int n = n0 + rr;
-					const int j = __shfl(my_idx, n < cnt ? n : 0);
-					const char *src = reinterpret_cast<const char *>(ybase) + (size_t) (unsigned) j * ybytes + 16 * piece;
-					if (rr < RPI && piece < PP && n < cnt)
-						__builtin_amdgcn_global_load_lds((mf_gvoid *) src, (mf_lvoid *) (tile + n0 * S), 16, 0, 0);
-				}
+			if constexpr (KT > 0 && dma_multi_row(KT)) {
+				gather_multi_row<KT>(ybase, ybytes, my_idx, cnt, lane, tile);
 			} else if constexpr (PF > 0 && (NP == 1 || KT == 256)) {
-				// Lean issue (a wave walking a long row alone is bound by its own instruction stream, ~17 instructions per
-				// gathered row in the loop below): every lane forms the address of ITS entry's row once per chunk (one
-				// 64-bit multiply-add per chunk instead of four scalar multiplies per row); per row two v_readlane give the
-				// row base as a scalar pair and the transfer takes it as its scalar address with the lane's 16-byte offset
-				// as the vector part.  The asm opens with s_nop 4: an SGPR written by v_readlane needs five wait states
-				// before a VMEM instruction reads it as its address, and hipcc pads nothing inside an asm statement.
-				// K = 256 (two 1-KiB instructions per row, all lanes active in both): the second one is the first with
-				// offset:1024 -- the instruction offset of an LDS-DMA load moves the LDS side as well as the global one
-				// (tools/micro/lds_dma_offset.hip), so neither M0 nor the base is touched between the two.
-				const unsigned long long rowaddr = ybase + (unsigned long long) (unsigned) my_idx * (unsigned long long) ybytes;
-				const int alo = (int) (unsigned) rowaddr, ahi = (int) (unsigned) (rowaddr >> 32);
-				const unsigned tile_lds = (unsigned) (unsigned long long) (__attribute__((address_space(3))) char *) tile;
-				int n = 0;
-				for (; n + 4 <= cnt; n += 4) {
-					unsigned long long b[4];
-#pragma unroll
-					for (int u = 0; u < 4; ++u)
-						b[u] = ((unsigned long long) (unsigned) __builtin_amdgcn_readlane(ahi, n + u) << 32) |
-						       (unsigned long long) (unsigned) __builtin_amdgcn_readlane(alo, n + u);
-					if (lane < P) {
-#pragma unroll
-						for (int u = 0; u < 4; ++u)
-							if constexpr (NP == 2)
-								asm volatile("s_nop 4\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %0\n\t"
-								             "global_load_lds_dwordx4 %2, %0 offset:1024"
-								             :
-								             : "s"(b[u]), "s"(tile_lds + (unsigned) ((n + u) * S)), "v"(voff)
-								             : "memory");
-							else
-								asm volatile("s_nop 4\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %0"
-								             :
-								             : "s"(b[u]), "s"(tile_lds + (unsigned) ((n + u) * S)), "v"(voff)
-								             : "memory");
-					}
-				}
-				for (; n < cnt; ++n) {
-					const unsigned long long b = ((unsigned long long) (unsigned) __builtin_amdgcn_readlane(ahi, n) << 32) |
-					                             (unsigned long long) (unsigned) __builtin_amdgcn_readlane(alo, n);
-					if (lane < P) {
-						if constexpr (NP == 2)
-							asm volatile("s_nop 4\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %0\n\t"
-							             "global_load_lds_dwordx4 %2, %0 offset:1024"
-							             :
-							             : "s"(b), "s"(tile_lds + (unsigned) (n * S)), "v"(voff)
-							             : "memory");
-						else
-							asm volatile("s_nop 4\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %0"
-							             :
-							             : "s"(b), "s"(tile_lds + (unsigned) (n * S)), "v"(voff)
-							             : "memory");
-					}
-				}
+				gather_lean<NP == 2>(ybase, ybytes, my_idx, 0, 4, cnt, lane < P, lds_address(tile), S, voff);
 				// hipcc knows nothing of these transfers: the barrier below would not wait for them
 				MF_STAMP(t_s1);
 				asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -372,18 +610,8 @@ __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 				st_issue += t_s1 - t_s0;
 				st_wait += __builtin_amdgcn_s_memtime() - t_s1;
 #endif
-			} else
-			for (int n = 0; n < cnt; ++n) {
-				const int j = __builtin_amdgcn_readlane(my_idx, n);
-				unsigned long long base = ybase + (unsigned long long) (unsigned) j * (unsigned long long) ybytes;
-				asm volatile("" : "+s"(base));   // keep the row base scalar
-#pragma unroll
-				for (int p = 0; p < NP; ++p) {
-					const char *src = reinterpret_cast<const char *>(base) + voff + 1024u * p;
-					if (lane + kWave * p < P)
-						__builtin_amdgcn_global_load_lds((mf_gvoid *) src, (mf_lvoid *) (tile + n * S + 1024 * p),
-						                                 16, 0, 0);
-				}
+			} else {
+				gather_rows<NP>(ybase, ybytes, my_idx, cnt, lane, voff, P, S, tile);
 			}
 			__syncthreads();   // single-wave workgroup: this is the vmcnt(0)/lgkmcnt(0) that retires the DMA
 			MF_STAMP(t_a0);
@@ -464,51 +692,9 @@ __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 			// ---- phase B
 			const char *tb = tile + voff;
 			int n = 0;
-			if constexpr (PF > 0 && NP == 1) {   // sixteen entries' reads in flight at once
-				for (; n + 16 <= cnt; n += 16) {
-					double2 t[16];
-#pragma unroll
-					for (int u = 0; u < 16; ++u)
-						t[u] = (lane < P) ? *reinterpret_cast<const double2 *>(tb + (n + u) * S) : make_double2(0.0, 0.0);
-					asm volatile("" ::: "memory");   // pins the issue order: the reads above go out before the arithmetic below
-#pragma unroll
-					for (int u = 0; u < 16; ++u) {
-						const double en = readlane_f64(e, n + u);
-						acc[0].x = acc[0].x + en * t[u].x;
-						acc[0].y = acc[0].y + en * t[u].y;
-					}
-				}
-			}
-			for (; n + 4 <= cnt; n += 4) {
-				double2 t[4][NP];
-				double en[4];
-#pragma unroll
-				for (int u = 0; u < 4; ++u) {
-					en[u] = readlane_f64(e, n + u);
-#pragma unroll
-					for (int p = 0; p < NP; ++p)
-						t[u][p] = (lane + kWave * p < P)
-						              ? *reinterpret_cast<const double2 *>(tb + (n + u) * S + 1024 * p)
-						              : make_double2(0.0, 0.0);
-				}
-#pragma unroll
-				for (int u = 0; u < 4; ++u)
-#pragma unroll
-					for (int p = 0; p < NP; ++p) {
-						acc[p].x = acc[p].x + en[u] * t[u][p].x;
-						acc[p].y = acc[p].y + en[u] * t[u][p].y;
-					}
-			}
-			for (; n < cnt; ++n) {
-				const double en = readlane_f64(e, n);
-#pragma unroll
-				for (int p = 0; p < NP; ++p)
-					if (lane + kWave * p < P) {
-						const double2 t = *reinterpret_cast<const double2 *>(tb + n * S + 1024 * p);
-						acc[p].x = acc[p].x + en * t.x;
-						acc[p].y = acc[p].y + en * t.y;
-					}
-			}
+			if constexpr (PF > 0 && NP == 1) n = phase_b_sixteen<true>(tb, S, e, n, cnt, lane < P, acc[0]);
+			n = phase_b_four<NP>(tb, S, e, n, cnt, lane, P, acc);
+			phase_b_tail<NP, true>(tb, S, e, n, cnt, lane, P, acc);
 			__syncthreads();   // tile is overwritten by the next chunk's DMA
 #ifdef MF_STAMPS
 			st_a += t_a1 - t_a0;
@@ -556,16 +742,15 @@ template <int KT, int NPASS>
 __global__ void __launch_bounds__(kWave) sweep_db_kernel(SweepArgs a)
 {
 	const int K = KT > 0 ? KT : a.K;
-	const int P = K >> 1;
+	const int P = dma_pieces(K);
 	constexpr int NP = NPASS;
-	const int S = 16 * (P | 1);
-	const int xs_bytes = ((K * 8 + 255) / 256) * 256;
+	const int S = dma_row_stride_of(P);
+	const int xs_bytes = dma_xs_bytes(K);
 	extern __shared__ __attribute__((aligned(16))) char lds[];
 	double2 *xs = reinterpret_cast<double2 *>(lds);
 	const int nch = a.nch;
 	const int tile_bytes = nch * S;
 	char *tile0 = lds + xs_bytes;
-	const unsigned tile0_lds = (unsigned) (unsigned long long) (__attribute__((address_space(3))) char *) tile0;
 	const int lane = threadIdx.x;
 	const unsigned voff = (unsigned) lane * 16u;
 	const unsigned long long ybase = (unsigned long long) a.Y_old;
@@ -573,32 +758,11 @@ __global__ void __launch_bounds__(kWave) sweep_db_kernel(SweepArgs a)
 
 	// gather of one chunk into tile `buf`: the rows of lanes 0..cnt-1 of `idx`
 	auto stage = [&](int idx, int cnt, int buf) {
-		const unsigned tb = tile0_lds + (unsigned) (buf * tile_bytes);
-		constexpr bool kMultiRow = KT > 0 && ((KT / 2) | 1) <= 32;
-		if constexpr (kMultiRow) {
-			constexpr int PP = KT / 2, PS = PP | 1, RPI = kWave / PS;
-			const int rr = lane / PS, piece = lane - rr * PS;
-			for (int n0 = 0; n0 < cnt; n0 += RPI) {
-				const int n = n0 + rr;
-				const int j = __shfl(idx, n < cnt ? n : 0);
-				const char *src = reinterpret_cast<const char *>(ybase) + (size_t) (unsigned) j * ybytes + 16 * piece;
-				const unsigned m0 = __builtin_amdgcn_readfirstlane(tb + (unsigned) (n0 * S));
-				if (rr < RPI && piece < PP && n < cnt)
-					asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(m0) : "memory");
-			}
-		} else
-			for (int n = 0; n < cnt; ++n) {
-				const int j = __builtin_amdgcn_readlane(idx, n);
-				unsigned long long base = ybase + (unsigned long long) (unsigned) j * (unsigned long long) ybytes;
-				asm volatile("" : "+s"(base));
-#pragma unroll
-				for (int p = 0; p < NP; ++p) {
-					const char *src = reinterpret_cast<const char *>(base) + voff + 1024u * p;
-					const unsigned m0 = __builtin_amdgcn_readfirstlane(tb + (unsigned) (n * S + 1024 * p));
-					if (lane + kWave * p < P)
-						asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(m0) : "memory");
-				}
-			}
+		char *tile = tile0 + buf * tile_bytes;
+		if constexpr (KT > 0 && dma_multi_row(KT))
+			gather_multi_row<KT, true>(ybase, ybytes, idx, cnt, lane, tile);
+		else
+			gather_rows<NP, true>(ybase, ybytes, idx, cnt, lane, voff, P, S, tile);
 	};
 
 	for (int it = blockIdx.x; it < a.nrows; it += gridDim.x) {
@@ -655,14 +819,6 @@ __global__ void __launch_bounds__(kWave) sweep_db_kernel(SweepArgs a)
 				double dot = 0.0;
 				if constexpr (KT > 0) {
 					dot = phase_a_dot_pipelined<KT / 2, 8>(t2, xs);
-				} else if (KT > 0) {
-#pragma unroll
-					for (int q = 0; q < KT / 2; ++q) {
-						const double2 t = t2[q];
-						const double2 x = xs[q];
-						dot = dot + x.x * t.x;
-						dot = dot + x.y * t.y;
-					}
 				} else {
 					int q = 0;
 					for (; q + 4 <= P; q += 4) {
@@ -690,50 +846,9 @@ __global__ void __launch_bounds__(kWave) sweep_db_kernel(SweepArgs a)
 			// ---- phase B
 			const char *tb = tile + voff;
 			int n = 0;
-			if constexpr (NP == 1) {   // sixteen entries' reads in flight at once
-				for (; n + 16 <= cnt; n += 16) {
-					double2 t[16];
-#pragma unroll
-					for (int u = 0; u < 16; ++u)
-						t[u] = (lane < P) ? *reinterpret_cast<const double2 *>(tb + (n + u) * S) : make_double2(0.0, 0.0);
-					asm volatile("" ::: "memory");   // pins the issue order: the reads above go out before the arithmetic below
-#pragma unroll
-					for (int u = 0; u < 16; ++u) {
-						const double en = readlane_f64(e, n + u);
-						acc[0].x = acc[0].x + en * t[u].x;
-						acc[0].y = acc[0].y + en * t[u].y;
-					}
-				}
-			}
-			for (; n + 4 <= cnt; n += 4) {
-				double2 t[4][NP];
-				double en[4];
-#pragma unroll
-				for (int u = 0; u < 4; ++u) {
-					en[u] = readlane_f64(e, n + u);
-#pragma unroll
-					for (int p = 0; p < NP; ++p)
-						t[u][p] = (lane + kWave * p < P) ? *reinterpret_cast<const double2 *>(tb + (n + u) * S + 1024 * p)
-						                                 : make_double2(0.0, 0.0);
-				}
-#pragma unroll
-				for (int u = 0; u < 4; ++u)
-#pragma unroll
-					for (int p = 0; p < NP; ++p) {
-						acc[p].x = acc[p].x + en[u] * t[u][p].x;
-						acc[p].y = acc[p].y + en[u] * t[u][p].y;
-					}
-			}
-			for (; n < cnt; ++n) {
-				const double en = readlane_f64(e, n);
-#pragma unroll
-				for (int p = 0; p < NP; ++p)
-					if (lane + kWave * p < P) {
-						const double2 t = *reinterpret_cast<const double2 *>(tb + n * S + 1024 * p);
-						acc[p].x = acc[p].x + en * t.x;
-						acc[p].y = acc[p].y + en * t.y;
-					}
-			}
+			if constexpr (NP == 1) n = phase_b_sixteen<true>(tb, S, e, n, cnt, lane < P, acc[0]);
+			n = phase_b_four<NP>(tb, S, e, n, cnt, lane, P, acc);
+			phase_b_tail<NP, true>(tb, S, e, n, cnt, lane, P, acc);
 			// all LDS reads of this tile are complete before a later iteration's transfer may land in it
 			asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 		}
@@ -759,59 +874,23 @@ __global__ void __launch_bounds__(kWave) sweep_db_kernel(SweepArgs a)
 // consumed".  The row's walk costs max(issue + landing, A + B) per chunk instead of their sum, and the arithmetic is
 // wave 1's alone, in the order of sweep_dma_kernel: same bits.  Compile-time K with one DMA instruction per row
 // (64 <= K <= 128).
+// NL loader waves + one compute wave; loader w takes the groups of four rows w, w + NL, ... of a chunk.  Only NL = 1 is
+// built: a second loader was measured within noise of one (the compute wave is the bound), and so
+// was splitting the compute wave into a phase-A and a phase-B wave (profiles/r03/trio_ab.txt).
 // ------------------------------------------------------------------------------------------------
-template <int Q, int PF>
-__device__ __forceinline__ double phase_a_dot_ahead(const double2 *t2, const double2 *xs)
-{
-	// as phase_a_dot_pipelined, and the two products of step q+1 are formed before the two adds of step q: the chain of
-	// dependent adds never waits for a multiply
-	double2 t[PF], x[PF];
-#pragma unroll
-	for (int i = 0; i < PF; ++i)
-		if (i < Q) {
-			t[i] = t2[i];
-			x[i] = xs[i];
-		}
-	double dot = 0.0;
-	double px = x[0].x * t[0].x, py = x[0].y * t[0].y;
-#pragma unroll
-	for (int q = 0; q < Q; ++q) {
-		double nx = 0.0, ny = 0.0;
-		if (q + 1 < Q) {
-			nx = x[(q + 1) % PF].x * t[(q + 1) % PF].x;
-			ny = x[(q + 1) % PF].y * t[(q + 1) % PF].y;
-		}
-		if (q + PF < Q) {
-			t[q % PF] = t2[q + PF];
-			x[q % PF] = xs[q + PF];
-		}
-		// (pinning the multiplies of step q+1 between the adds of steps q-1 and q with register operands on this statement
-		// was measured SLOWER -- a lone 5993-entry row 0.327 -> 0.347 ms --: hipcc's own placement, each multiply in front
-		// of its add, stays)
-		asm volatile("" ::: "memory");
-		dot = dot + px;
-		dot = dot + py;
-		px = nx;
-		py = ny;
-	}
-	return dot;
-}
-
-// NL loader waves + one compute wave.  NL = 2: the two loaders issue alternate groups of four rows of a chunk, so the
-// ~90 cycles per gathered row -- what a pair is bound by -- are paid in parallel and the walk becomes bound by the compute
-// wave (phases A + B).
 template <int KT, int NL = 1>
 __global__ void __launch_bounds__((NL + 1) * kWave) sweep_pair_kernel(SweepArgs a)
 {
 	using G = DmaGeom<KT>;
-	static_assert(G::kPasses == 1 && (G::kPieces | 1) > 32, "one LDS-DMA instruction per gathered row");
+	static_assert(G::kOnePassWide, "one LDS-DMA instruction per gathered row");
+	static_assert(NL == 1, "one loader wave");
 	constexpr int P = G::kPieces, S = G::kStride;
 	extern __shared__ __attribute__((aligned(16))) char lds[];
 	double2 *xs = reinterpret_cast<double2 *>(lds);
 	char *tile0 = lds + G::kXsBytes;
 	const int nch = a.nch;
 	const int tile_bytes = nch * S;
-	const unsigned tile0_lds = (unsigned) (unsigned long long) (__attribute__((address_space(3))) char *) tile0;
+	const unsigned tile0_lds = lds_address(tile0);
 	const int lane = threadIdx.x & 63;
 	const int wave = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));   // scalar: the two roles never share a branch mask
 	const unsigned voff = (unsigned) lane * 16u;
@@ -825,7 +904,7 @@ __global__ void __launch_bounds__((NL + 1) * kWave) sweep_pair_kernel(SweepArgs 
 		// arbitrated by priority, then age) beside the waves of short rows on the same SIMDs
 		const bool long_row = a.prio_len > 0 && end - beg >= a.prio_len;
 		if (wave < NL) {
-			// ---------------- loader(s): chunk c -> tile c & 1, then "landed" = barrier c
+			// ---------------- loader: chunk c -> tile c & 1, then "landed" = barrier c
 			if (long_row)
 				__builtin_amdgcn_s_setprio(3);
 			else
@@ -839,34 +918,7 @@ __global__ void __launch_bounds__((NL + 1) * kWave) sweep_pair_kernel(SweepArgs 
 				asm volatile("" : "+v"(my_idx));   // hipcc's wait for this load stays here, outside the loops below
 				nx_idx = 0;
 				if (c + nch + lane < min(end, c + 2 * nch)) nx_idx = a.idx[c + nch + lane];
-				const unsigned long long rowaddr = ybase + (unsigned long long) (unsigned) my_idx * ybytes;
-				const int alo = (int) (unsigned) rowaddr, ahi = (int) (unsigned) (rowaddr >> 32);
-				const unsigned tb = tile0_lds + (unsigned) (buf * tile_bytes);
-				int n = 4 * wave;   // loader w takes the groups of four rows w, w + NL, ...
-				for (; n + 4 <= cnt; n += 4 * NL) {
-					unsigned long long b[4];
-#pragma unroll
-					for (int u = 0; u < 4; ++u)
-						b[u] = ((unsigned long long) (unsigned) __builtin_amdgcn_readlane(ahi, n + u) << 32) |
-						       (unsigned long long) (unsigned) __builtin_amdgcn_readlane(alo, n + u);
-					if (lane < P) {
-#pragma unroll
-						for (int u = 0; u < 4; ++u)
-							asm volatile("s_nop 4\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %0"
-							             :
-							             : "s"(b[u]), "s"(tb + (unsigned) ((n + u) * S)), "v"(voff)
-							             : "memory");
-					}
-				}
-				for (int m = n; m < min(n + 4, cnt); ++m) {   // the last, partial group of four belongs to the loader it falls to
-					const unsigned long long b = ((unsigned long long) (unsigned) __builtin_amdgcn_readlane(ahi, m) << 32) |
-					                             (unsigned long long) (unsigned) __builtin_amdgcn_readlane(alo, m);
-					if (lane < P)
-						asm volatile("s_nop 4\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %0"
-						             :
-						             : "s"(b), "s"(tb + (unsigned) (m * S)), "v"(voff)
-						             : "memory");
-				}
+				gather_lean<false>(ybase, ybytes, my_idx, 4 * wave, 4 * NL, cnt, lane < P, tile0_lds + (unsigned) (buf * tile_bytes), S, voff);
 				// landed (this also retires the index load of the next chunk, issued in front of the transfers)
 				asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
 			}
@@ -878,12 +930,8 @@ __global__ void __launch_bounds__((NL + 1) * kWave) sweep_pair_kernel(SweepArgs 
 			else
 				__builtin_amdgcn_s_setprio(0);
 			const double2 *__restrict__ xrow2 = reinterpret_cast<const double2 *>(a.X_old + (size_t) r * a.ldx);
-			double2 acc = make_double2(0.0, 0.0);
-			if (lane < P) {
-				const double2 v = xrow2[lane];
-				xs[lane] = v;
-				if (a.seed) acc = v;
-			}
+			double2 acc[1];
+			load_x_row<1>(xrow2, xs, lane, P, a.seed, acc);
 			double nx_val = 0.0;
 			if (beg + lane < min(end, beg + nch)) nx_val = a.val[beg + lane];
 			const unsigned boff = (unsigned) (lane < P ? lane : 0) * 16u;   // lanes beyond the row re-read piece 0: no branch masks in phase B
@@ -896,183 +944,14 @@ __global__ void __launch_bounds__((NL + 1) * kWave) sweep_pair_kernel(SweepArgs 
 				asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : "+v"(my_val)::"memory");   // chunk c has landed
 				const char *tile = tile0 + buf * tile_bytes;
 				const double2 *t2 = reinterpret_cast<const double2 *>(tile + (lane < nch ? lane : 0) * S);
-				const double dot = phase_a_dot_ahead<KT / 2, 8>(t2, xs);
-				const double e = a.c2 * (my_val - dot);
+				const double e = a.c2 * (my_val - phase_a_dot<KT, 8, true>(t2, xs));
 				const char *tb = tile + boff;
-				int n = 0;
-				for (; n + 16 <= cnt; n += 16) {
-					double2 t[16];
-#pragma unroll
-					for (int u = 0; u < 16; ++u) t[u] = *reinterpret_cast<const double2 *>(tb + (n + u) * S);
-					asm volatile("" ::: "memory");
-#pragma unroll
-					for (int u = 0; u < 16; ++u) {
-						const double en = readlane_f64(e, n + u);
-						acc.x = acc.x + en * t[u].x;
-						acc.y = acc.y + en * t[u].y;
-					}
-				}
-				for (; n < cnt; ++n) {
-					const double en = readlane_f64(e, n);
-					const double2 t = *reinterpret_cast<const double2 *>(tb + n * S);
-					acc.x = acc.x + en * t.x;
-					acc.y = acc.y + en * t.y;
-				}
+				const int n = phase_b_sixteen<false>(tb, S, e, 0, cnt, true, acc[0]);
+				phase_b_tail<1, false>(tb, S, e, n, cnt, lane, P, acc);
 			}
-			if (lane < P) reinterpret_cast<double2 *>(a.X_new + (size_t) r * a.ldx)[lane] = acc;
+			store_x_row<1>(reinterpret_cast<double2 *>(a.X_new + (size_t) r * a.ldx), lane, P, acc);
 			// row end: every read of the last tile and of xs is complete before the loader refills / xs is rewritten
 			asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-		}
-	}
-}
-
-// Three waves per row: loader, phase A, phase B -- the pair's compute wave split in two.  A pair walks a row at
-// max(issue + landing, A + B) per chunk and is bound by A + B (clocks of a lone long row, tools/stamps.py: per 16 entries
-// issue 1430 / landing 370 / phase A 1770 / phase B 1100 cycles; phase A costs the same for 32 entries, lane = entry); with
-// the phases on separate waves, one chunk apart, the walk costs max(issue + landing, A, B).  Lockstep pipeline, ONE barrier
-// per step s: the loader fills tile s % 3 with chunk s, the A wave forms the errors of chunk s-1 (tile (s-1) % 3) and parks
-// them in ebuf[(s-1) & 1], the B wave accumulates chunk s-2 (tile (s-2) % 3, errors from ebuf[s & 1]).  The barrier that ends
-// step s says: chunk s has landed, the errors of chunk s-1 are in LDS, tile (s-2) % 3 = (s+1) % 3 is consumed.  The
-// arithmetic is that of the pair's compute wave, in the same order => same bits.
-// Measured (tools/r3_trio_ab.sh, profiles/r03/trio_ab.txt; experiments build, MF_SWEEP_TRIO=1): the side whose time IS its
-// longest row gains -- cfg3 power-law users 0.138 -> 0.121 ms -- but every throughput-bound side loses to the third tile
-// (fewer workgroups per CU): cfg3 power-law items 0.115 -> 0.151, Netflix-shape items 9.97 -> 10.48 ms, cfg4 items 11.84 ->
-// 12.68.  And the users' gain was the item side's ordered sums no longer overlapping the user sweep: with trios on the user
-// side ALONE (MF_SWEEP_TRIO_U=1) it is 0.1447 against 0.1378 ms.  Not chosen by any rule; experiments build only.
-template <int KT>
-__global__ void __launch_bounds__(3 * kWave) sweep_trio_kernel(SweepArgs a)
-{
-	using G = DmaGeom<KT>;
-	static_assert(G::kPasses == 1 && (G::kPieces | 1) > 32, "one LDS-DMA instruction per gathered row");
-	constexpr int P = G::kPieces, S = G::kStride;
-	extern __shared__ __attribute__((aligned(16))) char lds[];
-	double2 *xs = reinterpret_cast<double2 *>(lds);
-	double *ebuf = reinterpret_cast<double *>(lds + G::kXsBytes);   // 2 x 64 errors
-	char *tile0 = lds + G::kXsBytes + 1024;
-	const int nch = a.nch;
-	const int tile_bytes = nch * S;
-	const unsigned tile0_lds = (unsigned) (unsigned long long) (__attribute__((address_space(3))) char *) tile0;
-	const int lane = threadIdx.x & 63;
-	const int wave = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));   // scalar: the roles never share a branch mask
-	const unsigned voff = (unsigned) lane * 16u;
-	const unsigned long long ybase = (unsigned long long) a.Y_old;
-	const unsigned long long ybytes = (unsigned long long) a.ldy * 8ull;
-
-	for (int it = blockIdx.x; it < a.nrows; it += gridDim.x) {
-		const int r = a.rowlist ? a.rowlist[it] : it;
-		const int beg = a.ptr[r], end = a.ptr[r + 1];
-		const int nchunks = (end - beg + nch - 1) / nch;
-		const bool long_row = a.prio_len > 0 && end - beg >= a.prio_len;
-		if (long_row)
-			__builtin_amdgcn_s_setprio(3);
-		else if (wave == 0)
-			__builtin_amdgcn_s_setprio(1);   // its few instructions gate the two other waves
-		else
-			__builtin_amdgcn_s_setprio(0);
-		if (wave == 0) {
-			// ---------------- loader: chunk s -> tile s % 3
-			int nx_idx = 0;
-			if (beg + lane < min(end, beg + nch)) nx_idx = a.idx[beg + lane];
-			int ti = 0;
-			for (int s = 0; s < nchunks + 2; ++s) {
-				if (s < nchunks) {
-					const int c = beg + s * nch;
-					const int cnt = min(nch, end - c);
-					int my_idx = nx_idx;
-					asm volatile("" : "+v"(my_idx));   // hipcc's wait for this load stays here, outside the loops below
-					nx_idx = 0;
-					if (c + nch + lane < min(end, c + 2 * nch)) nx_idx = a.idx[c + nch + lane];
-					const unsigned long long rowaddr = ybase + (unsigned long long) (unsigned) my_idx * ybytes;
-					const int alo = (int) (unsigned) rowaddr, ahi = (int) (unsigned) (rowaddr >> 32);
-					const unsigned tb = tile0_lds + (unsigned) (ti * tile_bytes);
-					int n = 0;
-					for (; n + 4 <= cnt; n += 4) {
-						unsigned long long b[4];
-#pragma unroll
-						for (int u = 0; u < 4; ++u)
-							b[u] = ((unsigned long long) (unsigned) __builtin_amdgcn_readlane(ahi, n + u) << 32) |
-							       (unsigned long long) (unsigned) __builtin_amdgcn_readlane(alo, n + u);
-						if (lane < P) {
-#pragma unroll
-							for (int u = 0; u < 4; ++u)
-								asm volatile("s_nop 4\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %0"
-								             :
-								             : "s"(b[u]), "s"(tb + (unsigned) ((n + u) * S)), "v"(voff)
-								             : "memory");
-						}
-					}
-					for (; n < cnt; ++n) {
-						const unsigned long long b = ((unsigned long long) (unsigned) __builtin_amdgcn_readlane(ahi, n) << 32) |
-						                             (unsigned long long) (unsigned) __builtin_amdgcn_readlane(alo, n);
-						if (lane < P)
-							asm volatile("s_nop 4\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %0"
-							             :
-							             : "s"(b), "s"(tb + (unsigned) (n * S)), "v"(voff)
-							             : "memory");
-					}
-				}
-				// landed (this also retires the index load of the next chunk, issued in front of the transfers)
-				asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-				ti = ti == 2 ? 0 : ti + 1;
-			}
-		} else if (wave == 1) {
-			// ---------------- phase A of chunk s - 1 at step s: the errors, parked in ebuf[(s - 1) & 1]
-			const double2 *__restrict__ xrow2 = reinterpret_cast<const double2 *>(a.X_old + (size_t) r * a.ldx);
-			if (lane < P) xs[lane] = xrow2[lane];
-			double nx_val = 0.0;
-			if (beg + lane < min(end, beg + nch)) nx_val = a.val[beg + lane];
-			int ti = 0;   // tile of chunk s - 1
-			for (int s = 0; s < nchunks + 2; ++s) {
-				if (s >= 1 && s <= nchunks) {
-					const int c = beg + (s - 1) * nch;
-					const double my_val = nx_val;
-					nx_val = 0.0;
-					if (c + nch + lane < min(end, c + 2 * nch)) nx_val = a.val[c + nch + lane];
-					const char *tile = tile0 + ti * tile_bytes;
-					const double2 *t2 = reinterpret_cast<const double2 *>(tile + (lane < nch ? lane : 0) * S);
-					const double dot = phase_a_dot_ahead<KT / 2, 8>(t2, xs);
-					ebuf[((s - 1) & 1) * kWave + lane] = a.c2 * (my_val - dot);
-					ti = ti == 2 ? 0 : ti + 1;
-				}
-				asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" : "+v"(nx_val)::"memory");
-			}
-		} else {
-			// ---------------- phase B of chunk s - 2 at step s
-			const double2 *__restrict__ xrow2 = reinterpret_cast<const double2 *>(a.X_old + (size_t) r * a.ldx);
-			double2 acc = make_double2(0.0, 0.0);
-			if (lane < P && a.seed) acc = xrow2[lane];
-			const unsigned boff = (unsigned) (lane < P ? lane : 0) * 16u;   // lanes beyond the row re-read piece 0: no branch masks
-			int ti = 0;   // tile of chunk s - 2
-			for (int s = 0; s < nchunks + 2; ++s) {
-				if (s >= 2) {
-					const int c = beg + (s - 2) * nch;
-					const int cnt = min(nch, end - c);
-					const double e = ebuf[(s & 1) * kWave + lane];
-					const char *tb = tile0 + ti * tile_bytes + boff;
-					int n = 0;
-					for (; n + 16 <= cnt; n += 16) {
-						double2 t[16];
-#pragma unroll
-						for (int u = 0; u < 16; ++u) t[u] = *reinterpret_cast<const double2 *>(tb + (n + u) * S);
-						asm volatile("" ::: "memory");
-#pragma unroll
-						for (int u = 0; u < 16; ++u) {
-							const double en = readlane_f64(e, n + u);
-							acc.x = acc.x + en * t[u].x;
-							acc.y = acc.y + en * t[u].y;
-						}
-					}
-					for (; n < cnt; ++n) {
-						const double en = readlane_f64(e, n);
-						const double2 t = *reinterpret_cast<const double2 *>(tb + n * S);
-						acc.x = acc.x + en * t.x;
-						acc.y = acc.y + en * t.y;
-					}
-					ti = ti == 2 ? 0 : ti + 1;
-				}
-				asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" : "+v"(acc.x), "+v"(acc.y)::"memory");
-			}
-			if (lane < P) reinterpret_cast<double2 *>(a.X_new + (size_t) r * a.ldx)[lane] = acc;
 		}
 	}
 }
@@ -1722,7 +1601,7 @@ __global__ void __launch_bounds__(kCoopWaves *kWave) sweep_coop_kernel(SweepArgs
 		double2 acc[NP];
 #pragma unroll
 		for (int p = 0; p < NP; ++p) acc[p] = make_double2(0.0, 0.0);
-		if (wave == 0) {
+		if (wave == 0) {   // load_x_row, for the accumulator wave alone (the other waves' acc stays zero and unused)
 #pragma unroll
 			for (int p = 0; p < NP; ++p) {
 				const int q = lane + kWave * p;
@@ -1748,33 +1627,12 @@ __global__ void __launch_bounds__(kCoopWaves *kWave) sweep_coop_kernel(SweepArgs
 						my_idx = a.idx[c + lane];
 						my_val = a.val[c + lane];
 					}
-					for (int n = 0; n < cnt; ++n) {
-						const int j = __builtin_amdgcn_readlane(my_idx, n);
-						unsigned long long base = ybase + (unsigned long long) (unsigned) j * (unsigned long long) a.ldy * 8ull;
-						asm volatile("" : "+s"(base));
-#pragma unroll
-						for (int p = 0; p < NP; ++p) {
-							const char *src = reinterpret_cast<const char *>(base) + voff + 1024u * p;
-							if (lane + kWave * p < P)
-								__builtin_amdgcn_global_load_lds((mf_gvoid *) src,
-								                                 (mf_lvoid *) (tile + n * S + 1024 * p), 16, 0, 0);
-						}
-					}
+					gather_rows<NP>(ybase, (unsigned long long) a.ldy * 8ull, my_idx, cnt, lane, voff, P, S, tile);
 					__builtin_amdgcn_s_waitcnt(0);          // vmcnt(0): the DMA has landed (single wave owns the tile)
 					__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-					double e;
-					{
-						const double2 *t2 = reinterpret_cast<const double2 *>(tile + (lane < nch ? lane : 0) * S);   // lanes beyond the tile re-read row 0
-						double dot = 0.0;
-#pragma unroll
-						for (int q = 0; q < P; ++q) {
-							const double2 t = t2[q];
-							const double2 x = xs[q];
-							dot = dot + x.x * t.x;
-							dot = dot + x.y * t.y;
-						}
-						e = a.c2 * (my_val - dot);
-					}
+					// lanes beyond the tile re-read row 0
+					const double2 *t2 = reinterpret_cast<const double2 *>(tile + (lane < nch ? lane : 0) * S);
+					const double e = a.c2 * (my_val - phase_a_dot<KT>(t2, xs));
 					// scale in place: p_n[k] = e_n * y_n[k]
 					char *tb = tile + voff;
 					for (int n = 0; n < cnt; ++n) {
@@ -1791,7 +1649,8 @@ __global__ void __launch_bounds__(kCoopWaves *kWave) sweep_coop_kernel(SweepArgs
 					}
 				}
 			} else if (round > 0) {
-				// ---- accumulator: the tiles of round-1, producers in order, entries in order
+				// ---- accumulator: the tiles of round-1, producers in order, entries in order (an add-only walk: the
+				// products are in the tile already)
 				const int base_c = beg + (round - 1) * per_round;
 				for (int pw = 0; pw < kCoopProducers; ++pw) {
 					const int cnt = max(0, min(nch, end - (base_c + pw * nch)));
