@@ -11,7 +11,7 @@
 // load the same L row).  Matrix-core form: the K families of topn_mfma_kernel; every other K runs the exact form.
 #pragma once
 #include "mf_common.hip.h"
-#include "mf_recommend.hip.h"   // kHU, kHNB, kMI, mf_d4
+#include "mf_ring.hip.h"
 #include "mf_topn.hip.h"        // topn_exact_score
 
 namespace mf {
@@ -69,10 +69,10 @@ __global__ void __launch_bounds__(256) rank_threshold_kernel(RankArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Matrix-core counting pass.  The operand path and item masks of topn_mfma_kernel (L in registers, a ring of three R
-// chunks by LDS-DMA, fragment reads one k-step ahead, 128-item tiles); the epilogue of a tile counts.  Every approximate
-// score s' of an open item is within thr / 2 of B[i][j'] (thr = thr_scale * ||L_i|| * max ||R_j|| + 1e-300, as in
-// topn_finish), and the threshold t is exact, so
+// Matrix-core counting pass.  The operand path (RRing: L in registers, a ring of three R chunks by LDS-DMA, fragment reads
+// one k-step ahead, 128-item tiles) and item masks of topn_mfma_kernel; the epilogue of a tile counts.  Every approximate
+// score s' of an open item is within thr / 2 of B[i][j'] (thr = cert_margin, as in topn_finish), and the threshold t is
+// exact, so
 //   s' > t + thr  =>  B[i][j'] > t: counted in `above`;      s' < t - thr  =>  B[i][j'] < t: not counted;
 //   anything else (NaN included) sets `band`: the entry goes to the exact pass.
 // Item j itself is closed through the row's mask.  The counts live per lane in VGPRs and are summed over the 16 lanes and
@@ -81,11 +81,9 @@ __global__ void __launch_bounds__(256) rank_threshold_kernel(RankArgs a)
 template <int NC, int QC = 5, int TU = 2, int WAVES = 4>
 __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2))) rank_mfma_kernel(RankArgs a)
 {
-	static_assert(NC > 0 && 16 * TU * (WAVES / 2) == kHU && (2 * QC) % (WAVES / 2) == 0 && (2 * QC) / (WAVES / 2) <= 5, "shape");
-	constexpr int kHThreads = 64 * WAVES, kHKC = 4 * QC, kHPC = 2 * QC, kHQ = QC, kHChunkD2 = kHPC * kMI;
-	constexpr int NCH = NC, KSTEPS = NCH * kHQ;
+	static_assert(NC > 0, "compile-time K only");
+	using Ring = RRing<NC, QC, TU, WAVES>;
 	extern __shared__ double2 rec_lds[];   // ring of kHNB R chunks: [k-pair][128 items]
-	const int K = a.K;
 	__shared__ unsigned long long maskw[2][kHU][2];   // [tile parity][row][item half]
 	__shared__ double sh_lo[kHU], sh_hi[kHU];
 	__shared__ int red_above[kHU], red_band[kHU];
@@ -113,7 +111,7 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 			nextcol = cur < cend ? a.csr_idx[cur] : INT32_MAX;
 			nextcol2 = cur + 1 < cend ? a.csr_idx[cur + 1] : INT32_MAX;
 			const double ln = a.lnorm[u];
-			const double thr = a.thr_scale * (ln * __longlong_as_double((long long) *a.rnorm_max_bits)) + 1e-300;
+			const double thr = cert_margin(a.thr_scale, ln, rnorm_max(a.rnorm_max_bits));
 			const double t = a.score[e];
 			lo = t - thr;
 			hi = t + thr;
@@ -123,22 +121,19 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 		sh_hi[tid] = hi;
 		red_above[tid] = 0;
 		red_band[tid] = 0;
-		for (int d = 32; d >= 1; d >>= 1) {
-			const unsigned long long o = __shfl_xor(b, d);
-			b = o > b ? o : b;
-		}
+		b = wave_max_bits(b);
 		if (lane == 0) lmax_bits = b;
 	}
-	for (int sl = tid; sl < kHNB * kHChunkD2; sl += kHThreads) rec_lds[sl] = make_double2(0.0, 0.0);
-	double fa[KSTEPS][TU];
+	Ring::clear(rec_lds, tid);
+	double fa[Ring::KSTEPS][TU];
 #pragma unroll
 	for (int tu = 0; tu < TU; ++tu) {
 		const int row = e0 + 16 * TU * wr + 16 * tu + lr;
 		const double *l = a.L + (size_t) (row < a.rows ? a.ent_user[row] : 0) * a.ldl;
 #pragma unroll
-		for (int ks = 0; ks < KSTEPS; ++ks) {
+		for (int ks = 0; ks < Ring::KSTEPS; ++ks) {
 			const int k = 4 * ks + lq;
-			fa[ks][tu] = row < a.rows && k < K ? l[k] : 0.0;
+			fa[ks][tu] = row < a.rows && k < a.K ? l[k] : 0.0;
 		}
 	}
 	__syncthreads();
@@ -155,70 +150,12 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 			above[tu * 4 + r] = 0;
 		}
 
-	const unsigned bs_lds = (unsigned) (unsigned long long) (__attribute__((address_space(3))) char *) rec_lds;
-	unsigned voff = 0;
-	auto set_rows = [&](int jt) {
-		const int item = ((lane >> 4) & 1) * 64 + (2 * wc + (lane >> 5)) * 16 + (lane & 15);
-		const int row = min(jt + item, a.items - 1);
-		voff = (unsigned) row * (unsigned) (a.ldr * 8);   // the host admits R below 4 GB only
-	};
-	auto dma_chunk = [&](int kc, int slot) -> int {
-		int n = 0;
-#pragma unroll
-		for (int h = 0; h < kHPC / (WAVES / 2); ++h) {
-			const int pr = wr + (WAVES / 2) * h, k = kc + 2 * pr;
-			if (k < K) {   // wave-uniform
-				const char *sbase = reinterpret_cast<const char *>(a.R + k);
-				const unsigned m0 = bs_lds + (unsigned) ((slot * kHChunkD2 + pr * kMI + 64 * wc) * 16);
-				asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(m0));
-				++n;
-			}
-		}
-		return n;
-	};
-	auto wait_vm = [&](int n) {
-		switch (n) {
-		case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-		case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-		case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-		case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-		case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-		default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-		}
-	};
-
 	const int j_first = a.split_items ? (int) blockIdx.y * a.split_items : 0;
 	const int j_end = a.split_items ? min(a.items, j_first + a.split_items) : a.items;
-	int pj = j_first, pk = 0, pslot = 0;
-	auto issue_next = [&]() -> int {
-		if (pj >= j_end) return 0;
-		if (pk == 0) set_rows(pj);
-		const int n = dma_chunk(pk, pslot);
-		pk += kHKC;
-		if (pk >= K) {
-			pk = 0;
-			pj += kMI;
-		}
-		pslot = pslot == kHNB - 1 ? 0 : pslot + 1;
-		return n;
-	};
-	issue_next();
-	wait_vm(issue_next());
-	__syncthreads();
-	bool all_finite;
-	{
-		const double bound = __longlong_as_double((long long) lmax_bits) * __longlong_as_double((long long) *a.rnorm_max_bits);
-		all_finite = bound <= 1e300;   // false for NaN
-	}
-	const int boff = (lq >> 1) * (kMI * 2) + wc * 32 + lr * 2 + (lq & 1);
-	auto frag = [&](int s, int q, double (&f)[4]) {
-		const double *Bb = reinterpret_cast<const double *>(rec_lds) + s * (kHChunkD2 * 2) + boff;
-#pragma unroll
-		for (int ti = 0; ti < 4; ++ti) f[ti] = Bb[(8 * q + ti) * 64];
-	};
-	double fc[4];
-	frag(0, 0, fc);
-	int slot = 0, pending = 0;
+	Ring ring(rec_lds, a, j_first, j_end, lane, wave);
+	ring.issue_next();
+	ring.prime();
+	const bool all_finite = all_scores_finite(lmax_bits, a.rnorm_max_bits);
 	for (int j0 = j_first; j0 < j_end; j0 += kMI) {
 		mf_d4 acc[TU][4];
 
@@ -251,36 +188,7 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 			maskw[par][tid][1] = m1;
 		}
 
-#pragma unroll
-		for (int c = 0; c < NCH; ++c) {
-			const int nslot = slot == kHNB - 1 ? 0 : slot + 1;
-#pragma unroll
-			for (int q = 0; q < kHQ; ++q) {
-				double fn[4];
-				if (q == kHQ - 1) {
-					wait_vm(pending);
-					pending = 0;
-					__syncthreads();
-					frag(nslot, 0, fn);
-				} else {
-					frag(slot, q + 1, fn);
-				}
-				__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-				for (int tu = 0; tu < TU; ++tu)
-#pragma unroll
-					for (int ti = 0; ti < 4; ++ti)
-						acc[tu][ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[c * kHQ + q][tu], fc[ti],
-						                                                   c + q == 0 ? mf_d4{0.0, 0.0, 0.0, 0.0} : acc[tu][ti], 0, 0, 0);
-				if (q == 0) {
-					const int n = issue_next();
-					if (q != kHQ - 1) pending = n;
-				}
-#pragma unroll
-				for (int ti = 0; ti < 4; ++ti) fc[ti] = fn[ti];
-			}
-			slot = nslot;
-		}
+		ring.tile(fa, acc);
 
 		// counting epilogue: the lane's four scores of each of its rows against the row's t -/+ thr
 #pragma unroll
@@ -336,7 +244,7 @@ __global__ void __launch_bounds__(256) rank_finish_kernel(RankArgs a)
 {
 	const int e = blockIdx.x * 256 + threadIdx.x;
 	if (e >= a.rows || a.state[e] != 0) return;
-	const double bound = a.lnorm[a.ent_user[e]] * __longlong_as_double((long long) *a.rnorm_max_bits);
+	const double bound = a.lnorm[a.ent_user[e]] * rnorm_max(a.rnorm_max_bits);
 	const double t = a.score[e];
 	if (a.band[e] == 0 && bound <= 1e300 && t == t)
 		a.rank[e] = a.above[e];

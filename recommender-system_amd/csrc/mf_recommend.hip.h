@@ -2,6 +2,7 @@
 // dense predictions for the debug dump.
 #pragma once
 #include "mf_common.hip.h"
+#include "mf_ring.hip.h"
 #include "../../include/matfact_hip.h"   // mf_candidate
 
 namespace mf {
@@ -274,7 +275,7 @@ __global__ void __launch_bounds__(kWave) row_norm_kernel(const double *__restric
 	}
 }
 
-constexpr int kMU = 128, kMI = 128;
+constexpr int kMU = 128;   // users per workgroup; the item tile is kMI
 // LDS image of a chunk: [k-pair][row] of double2 {x[row][2p], x[row][2p+1]}, 130 rows per k-pair.
 //   fragment read (ds_read_b64): lanes 0..31 = 16 rows x (k, k+1) of one pair -> 256 contiguous bytes;
 //   staging store (ds_write_b128): an 8-lane group = consecutive k-pairs of a row, pair stride 130*16 B = 8 banks
@@ -288,24 +289,6 @@ constexpr size_t rec_mfma_lds(int K, int KC, bool ares)
 	const size_t nch = (size_t) ((K + KC - 1) / KC);
 	return (ares ? nch * chunk : 2 * chunk) + 2 * chunk;
 }
-
-struct Top2 {
-	double b1, b2;
-	int i1;
-};
-
-// b1 = -inf / i1 = -1 encode "no candidate"; all values are finite or -inf, so plain comparisons suffice
-__device__ __forceinline__ void top2_merge(Top2 &a, const Top2 &b)
-{
-	const bool take = b.b1 > a.b1;
-	const double lo1 = take ? a.b1 : b.b1;          // the smaller of the two bests
-	const double hi2 = take ? b.b2 : a.b2;          // the winner's own runner-up
-	a.b2 = lo1 > hi2 ? lo1 : hi2;
-	a.b1 = take ? b.b1 : a.b1;
-	a.i1 = take ? b.i1 : a.i1;
-}
-
-typedef double mf_d4 __attribute__((ext_vector_type(4)));
 
 #ifdef MF_STAMPS
 // diagnostic build only (tools/rec_stamps.py): shader-clock totals of wave 0 (slots 0..15) and wave 7 (16..31) of workgroup 0 --
@@ -418,7 +401,7 @@ __global__ void __launch_bounds__(kMThreads) recommend_mfma_kernel(RecMfmaArgs a
 	};
 	// LDS-DMA staging of an R chunk: instruction t (t = wave, wave + 8, ...) covers k-pair t/2, rows 64*(t%2)..+63
 	const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-	const unsigned bs_lds = (unsigned) (unsigned long long) (__attribute__((address_space(3))) char *) Bs0;
+	const unsigned bs_lds = lds_address(reinterpret_cast<const char *>(Bs0));
 	auto dma_image = [&](const double *__restrict__ X, int ld, int first_row, int last_row, unsigned lds_base, int kc, int buf) {
 #pragma unroll
 		for (int t0 = 0; t0 < 2 * PC; t0 += 8) {
@@ -428,7 +411,7 @@ __global__ void __launch_bounds__(kMThreads) recommend_mfma_kernel(RecMfmaArgs a
 				const int row = min(first_row + rb + lane, last_row);   // rows beyond the matrix are masked / never stored
 				const char *g = reinterpret_cast<const char *>(X + (size_t) row * ld + k);
 				const unsigned m0 = __builtin_amdgcn_readfirstlane(lds_base + (unsigned) ((buf * kChunkD2 + pr * kMLD2 + rb) * 16));
-				asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(m0) : "memory");
+				lds_dma_m0(g, m0);
 			}
 		}
 	};
@@ -448,17 +431,10 @@ __global__ void __launch_bounds__(kMThreads) recommend_mfma_kernel(RecMfmaArgs a
 		}
 	}
 
-	// Can a score of this workgroup be non-finite at all?  |score| <= ||L[i]|| * ||R[j]|| (Cauchy-Schwarz): when the
-	// largest of its 128 user norms times the largest item norm is a finite number well below the overflow threshold,
-	// every partial sum of every score is finite and the arg-max step needs no NaN / inf screening.  A NaN or inf
-	// anywhere in the rows involved makes a norm NaN or inf (compared as bit patterns, a NaN is the largest value).
+	// the largest of the 128 user norms, for all_scores_finite() below
 	__shared__ unsigned long long lmax_bits[2];
 	if (tid < kMU) {
-		unsigned long long b = i0 + tid < a.users ? (unsigned long long) __double_as_longlong(a.lnorm[i0 + tid]) : 0ull;
-		for (int d = 32; d >= 1; d >>= 1) {
-			const unsigned long long o = __shfl_xor(b, d);
-			b = o > b ? o : b;
-		}
+		const unsigned long long b = wave_max_bits(i0 + tid < a.users ? (unsigned long long) __double_as_longlong(a.lnorm[i0 + tid]) : 0ull);
 		if (lane == 0) lmax_bits[wave] = b;
 	}
 
@@ -478,12 +454,7 @@ __global__ void __launch_bounds__(kMThreads) recommend_mfma_kernel(RecMfmaArgs a
 		stage(0);
 	}
 	__syncthreads();
-	bool all_finite;
-	{
-		const unsigned long long lb = lmax_bits[0] > lmax_bits[1] ? lmax_bits[0] : lmax_bits[1];
-		const double bound = __longlong_as_double((long long) lb) * __longlong_as_double((long long) *a.rnorm_max_bits);
-		all_finite = bound <= 1e300;   // false for NaN
-	}
+	const bool all_finite = all_scores_finite(lmax_bits[0] > lmax_bits[1] ? lmax_bits[0] : lmax_bits[1], a.rnorm_max_bits);
 	for (int j0 = j_first; j0 < j_end; j0 += kMI) {
 		mf_d4 acc[2][4];
 #pragma unroll
@@ -579,35 +550,9 @@ __global__ void __launch_bounds__(kMThreads) recommend_mfma_kernel(RecMfmaArgs a
 		}
 		MF_RSTAMP(rt_e0);
 
-		// Cheap reject: after the first tiles almost no score beats its row's runner-up.  One compare per score register,
-		// masks not even looked at: the 32 lane masks land in scalar registers and are OR-ed there, one scalar branch decides
-		// (fmax() would add a canonicalising v_max per operand, a ballot two more vector instructions per row -- and every
-		// vector instruction of this step waits for the matrix pipe of its SIMD).  !(v <= thr) is also true for a NaN.  Only
-		// when the norms do not rule out non-finite scores (all_finite) a sum per row is formed as well: it is non-finite
-		// whenever a score is NaN or +-inf (a sum that merely overflows only costs the slow path).
-		constexpr int kUGT = 10;   // llvm::FCmpInst::FCMP_UGT: unordered or greater than
+		// cheap reject (32 compares), then the slow path for the rows with a survivor
 		unsigned long long rowm[8];
-		unsigned long long anym = 0;
-#pragma unroll
-		for (int tu = 0; tu < 2; ++tu)
-#pragma unroll
-			for (int r = 0; r < 4; ++r) {
-				const int x = tu * 4 + r;
-				rowm[x] = __builtin_amdgcn_fcmp(acc[tu][0][r], thr2[x], kUGT) | __builtin_amdgcn_fcmp(acc[tu][1][r], thr2[x], kUGT) |
-				          __builtin_amdgcn_fcmp(acc[tu][2][r], thr2[x], kUGT) | __builtin_amdgcn_fcmp(acc[tu][3][r], thr2[x], kUGT);
-				anym |= rowm[x];
-			}
-		if (!all_finite) {
-#pragma unroll
-			for (int tu = 0; tu < 2; ++tu)
-#pragma unroll
-				for (int r = 0; r < 4; ++r) {
-					const double sum = (acc[tu][0][r] + acc[tu][1][r]) + (acc[tu][2][r] + acc[tu][3][r]);
-					rowm[tu * 4 + r] |= __builtin_amdgcn_fcmp(fabs(sum), 1.7976931348623157e308, kUGT);
-					anym |= rowm[tu * 4 + r];
-				}
-		}
-		if (anym != 0)
+		if (cheap_reject(acc, thr2, all_finite, rowm))
 #pragma unroll
 		for (int tu = 0; tu < 2; ++tu)
 #pragma unroll
@@ -677,15 +622,7 @@ __global__ void __launch_bounds__(kMThreads) recommend_mfma_kernel(RecMfmaArgs a
 			a.filt[i0 + tid] = mf_filter{t.b1, t.b2, t.i1, bd};
 			return;
 		}
-		const double rmax = __longlong_as_double((long long) *a.rnorm_max_bits);
-		const double thr = a.thr_scale * (a.lnorm[i0 + tid] * rmax) + 1e-300;
-		const bool certain = !bd && (t.i1 < 0 || (t.b1 - t.b2) > thr);
-		if (certain) {
-			a.best[i0 + tid] = t.i1;
-		} else {
-			a.best[i0 + tid] = -2;
-			a.ulist[atomicAdd(a.ucount, 1)] = i0 + tid;
-		}
+		top1_certify(a, i0 + tid, t, bd);
 	}
 }
 
@@ -706,28 +643,19 @@ __global__ void __launch_bounds__(kMThreads) recommend_mfma_kernel(RecMfmaArgs a
 // contiguous per instruction; the fragment read of 32 lanes is 256 contiguous bytes).  R streams from L2 twice as often
 // (64 users per pass instead of 128): 3.8 TB/s of L2 -> LDS at cfg4, HBM traffic unchanged (the workgroups of an XCD
 // walk R = 80 MB in step).  Masks, top-2 bookkeeping and certification are those of recommend_mfma_kernel.
+// The ring, its transfers and the primed start are RRing (mf_ring.hip.h), shared with rank_mfma_kernel.
 // ------------------------------------------------------------------------------------------------
-constexpr int kHU = 64, kHNB = 3, kHKmax = 100;
-constexpr size_t kHStaticLds = 2 * kHU * 2 * 8 + kHU * 2 * (8 + 8 + 4 + 4) + 64;
-// dynamic LDS: the ring of kHNB chunks of QC k-steps (2 QC k-pairs x 128 items x 16 B each)
-inline size_t rec_mfma2_lds(int qc) { return (size_t) kHNB * (2 * qc) * kMI * sizeof(double2); }
-
-// NC > 0: K == 20 * NC exactly -- every chunk whole, no branch of the tile body depends on K (hipcc's s_waitcnt placement
-// follows the fragment pipeline only through straight-line code); NC == 0: any even K <= 100.
-// The same kernel at other shapes: QC = k-steps per chunk (5: the 20-deep chunks above; 4 for K = 16 NC up to 128, two per
-// CU as well; 8 for K = 256), TU = 16-user tiles per wave, WAVES = 4 (two workgroups per CU) or 8.  K = 256 does not fit the
-// registers of a wave at 32 users (256 VGPRs for the L operand alone): there a wave owns 16 users x 64 items (TU = 1: 128
-// VGPRs of L, 32 accumulators, 4 matrix instructions per k-step) and EIGHT waves form the 64-user workgroup, one per CU --
-// the two waves of a SIMD then share their barriers, which costs little once each keeps the pipe full alone (ablation above).
+// NC, QC: K = 4 QC NC, or NC == 0 for any even K <= 100 (RRing).  The same kernel at other shapes: QC = k-steps per chunk (5:
+// the 20-deep chunks above; 4 for K = 16 NC up to 128, two per CU as well; 8 for K = 256), TU = 16-user tiles per wave,
+// WAVES = 4 (two workgroups per CU) or 8.  K = 256 does not fit the registers of a wave at 32 users (256 VGPRs for the L
+// operand alone): there a wave owns 16 users x 64 items (TU = 1: 128 VGPRs of L, 32 accumulators, 4 matrix instructions per
+// k-step) and EIGHT waves form the 64-user workgroup, one per CU -- the two waves of a SIMD then share their barriers, which
+// costs little once each keeps the pipe full alone (ablation above).
 template <int NC, int QC = 5, int TU = 2, int WAVES = 4>
 __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2, 2))) recommend_mfma2_kernel(RecMfmaArgs a)
 {
-	static_assert(16 * TU * (WAVES / 2) == kHU && (2 * QC) % (WAVES / 2) == 0 && (2 * QC) / (WAVES / 2) <= 5, "shape");
-	static_assert(NC > 0 || (QC == 5 && TU == 2 && WAVES == 4), "the general form exists for the 20-deep chunks only");
-	constexpr int kHThreads = 64 * WAVES, kHKC = 4 * QC, kHPC = 2 * QC, kHQ = QC, kHChunkD2 = kHPC * kMI;
-	constexpr int NCH = NC ? NC : kHKmax / kHKC, KSTEPS = NCH * kHQ;
+	using Ring = RRing<NC, QC, TU, WAVES>;
 	extern __shared__ double2 rec_lds[];   // ring of kHNB R chunks: [k-pair][128 items]
-	const int K = a.K;
 	__shared__ unsigned long long maskw[2][kHU][2];   // [tile parity][user][item half]
 	__shared__ double red_b1[kHU][2], red_b2[kHU][2];
 	__shared__ int red_i1[kHU][2], red_bad[kHU][2];
@@ -759,106 +687,29 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 			red_i1[tid][h] = -1;
 			red_bad[tid][h] = 0;
 		}
-		unsigned long long b = i0 + tid < a.users ? (unsigned long long) __double_as_longlong(a.lnorm[i0 + tid]) : 0ull;
-		for (int d = 32; d >= 1; d >>= 1) {
-			const unsigned long long o = __shfl_xor(b, d);
-			b = o > b ? o : b;
-		}
+		const unsigned long long b = wave_max_bits(i0 + tid < a.users ? (unsigned long long) __double_as_longlong(a.lnorm[i0 + tid]) : 0ull);
 		if (lane == 0) lmax_bits = b;
 	}
-	// pairs beyond K are never transferred: the ring holds zeros there at first, not NaN patterns
-	for (int sl = tid; sl < kHNB * kHChunkD2; sl += kHThreads) rec_lds[sl] = make_double2(0.0, 0.0);
-	// the wave's L operand, once: k-step ks, user tile tu -> A[32*wr + 16*tu + lr][4*ks + lq] (zero beyond K / the last user)
-	double fa[KSTEPS][TU];
+	Ring::clear(rec_lds, tid);
+	// the wave's L operand, once: k-step ks, user tile tu -> A[16*TU*wr + 16*tu + lr][4*ks + lq]
+	double fa[Ring::KSTEPS][TU];
 #pragma unroll
-	for (int ks = 0; ks < KSTEPS; ++ks)
+	for (int ks = 0; ks < Ring::KSTEPS; ++ks)
 #pragma unroll
 		for (int tu = 0; tu < TU; ++tu) {
 			const int row = i0 + 16 * TU * wr + 16 * tu + lr, k = 4 * ks + lq;
-			fa[ks][tu] = row < a.users && k < K ? a.L[(size_t) row * a.ldl + k] : 0.0;
+			fa[ks][tu] = row < a.users && k < a.K ? a.L[(size_t) row * a.ldl + k] : 0.0;
 		}
 	__syncthreads();
-
-	// LDS-DMA of one R chunk (k offset kc of the tile `voff` points into) into ring slot `slot`: 20 instructions of 64
-	// rows x 16 B, five per wave (k-pair wr + 2h, rows 64*wc..+63).  Scalar base + per-lane row offset: no vector
-	// arithmetic per transfer -- every VALU instruction of a wave waits for the matrix pipe of its SIMD to drain
-	// (tools/micro/valu_under_mfma.hip).  Returns how many this wave issued (pairs beyond K: none).
-	const unsigned bs_lds = (unsigned) (unsigned long long) (__attribute__((address_space(3))) char *) rec_lds;
-	unsigned voff = 0;
-	auto set_rows = [&](int jt) {
-		// lane i of a transfer lands at byte 16 i of window w = wc of its k-pair's row: the item the chunk image keeps there
-		const int item = ((lane >> 4) & 1) * 64 + (2 * wc + (lane >> 5)) * 16 + (lane & 15);
-		const int row = min(jt + item, a.items - 1);      // rows beyond the matrix are masked
-		voff = (unsigned) row * (unsigned) (a.ldr * 8);   // the host admits R below 4 GB only
-	};
-	auto dma_chunk = [&](int kc, int slot) -> int {
-		int n = 0;
-#pragma unroll
-		for (int h = 0; h < kHPC / (WAVES / 2); ++h) {
-			const int pr = wr + (WAVES / 2) * h, k = kc + 2 * pr;
-			if (k < K) {   // wave-uniform
-				const char *sbase = reinterpret_cast<const char *>(a.R + k);
-				const unsigned m0 = bs_lds + (unsigned) ((slot * kHChunkD2 + pr * kMI + 64 * wc) * 16);
-				asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(m0));
-				++n;
-			}
-		}
-		return n;
-	};
-	// at most n of this wave's transfers still in flight (hipcc does not count the asm transfers)
-	auto wait_vm = [&](int n) {
-		switch (n) {
-		case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-		case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-		case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-		case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-		case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-		default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-		}
-	};
-
 	const int j_first = a.split_items ? (int) blockIdx.y * a.split_items : 0;
 	const int j_end = a.split_items ? min(a.items, j_first + a.split_items) : a.items;
-	// the chunk sequence: tiles in ascending order, k-chunks within; (pj, pk, pslot) = the next chunk to transfer
-	int pj = j_first, pk = 0, pslot = 0;
-	auto issue_next = [&]() -> int {
-		if (pj >= j_end) return 0;
-		if (pk == 0) set_rows(pj);
-		const int n = dma_chunk(pk, pslot);
-		pk += kHKC;
-		if (pk >= K) {
-			pk = 0;
-			pj += kMI;
-		}
-		pslot = pslot == kHNB - 1 ? 0 : pslot + 1;
-		return n;
-	};
-	issue_next();
-	wait_vm(issue_next());   // chunk 0 has landed; chunk 1 may still be in flight
-	__syncthreads();
-	bool all_finite;
-	{
-		const double bound = __longlong_as_double((long long) lmax_bits) * __longlong_as_double((long long) *a.rnorm_max_bits);
-		all_finite = bound <= 1e300;   // false for NaN
-	}
-	// R fragment of k-step q of the chunk in ring slot s: k = 4q + lq -> pair 2q + (lq >> 1), half lq & 1.  Within the 2 KB
-	// row of a k-pair, item 64 wc + 16 ti + lr sits at byte 512 ti + 256 wc + 16 lr: a wave's four fragments of a k-step are
-	// 512 B apart, the k-steps 4 KB, the slots 20 KB -- all multiples of 512, so every fragment read of a chunk is one base
-	// register plus an immediate (ds_read2st64_b64) and the k-loop holds no vector arithmetic at all.
-	const int boff = (lq >> 1) * (kMI * 2) + wc * 32 + lr * 2 + (lq & 1);
-	auto frag = [&](int s, int q, double (&f)[4]) {
-		const double *Bb = reinterpret_cast<const double *>(rec_lds) + s * (kHChunkD2 * 2) + boff;
+	Ring ring(rec_lds, a, j_first, j_end, lane, wave);
+	ring.issue_next();
+	ring.prime();
+	double fc[4];   // this kernel's own copy of the R fragment of the next k-step: its chunk loop is written out below
 #pragma unroll
-		for (int ti = 0; ti < 4; ++ti) f[ti] = Bb[(8 * q + ti) * 64];
-	};
-	// The matrix stream of a wave has no gap of its own: the fragment of the NEXT k-step -- of this chunk, of the next
-	// chunk, of the next tile -- is read in front of the matrix instructions of the current one.  For that the barrier
-	// that publishes chunk s+1 stands in front of the LAST k-step of chunk s (whose transfer, issued under the first k-step
-	// of chunk s-1, has had almost two chunk times), and the transfer of chunk s+2 goes into the slot of chunk s-1 -- whose
-	// last fragment every wave had read before it passed that barrier one chunk ago.
-	double fc[4];
-	frag(0, 0, fc);
-	int slot = 0, pending = 0;   // pending: this wave's transfers issued AFTER those of the chunk the next barrier publishes
+	for (int ti = 0; ti < 4; ++ti) fc[ti] = ring.fc[ti];
+	const bool all_finite = all_scores_finite(lmax_bits, a.rnorm_max_bits);
 	for (int j0 = j_first; j0 < j_end; j0 += kMI) {
 		mf_d4 acc[TU][4];
 
@@ -888,86 +739,61 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 			maskw[par][tid][1] = m1;
 		}
 
+		// RRing::tile written out: as a call it moved registers and waits of this kernel's epilogue (profiles/certified_parts)
 #pragma unroll
-		for (int c = 0; c < NCH; ++c) {
-			const int kc = c * kHKC;
-			if (NC || kc < K) {   // wave-uniform
-				const int nq = NC ? kHQ : min(kHQ, (K - kc + 3) >> 2);   // k-steps of this chunk (only the last chunk can be short)
-				const int nslot = slot == kHNB - 1 ? 0 : slot + 1;
+		for (int c = 0; c < Ring::NCH; ++c) {
+			const int kc = c * Ring::kKC;
+			if (NC || kc < a.K) {   // wave-uniform
+				const int nq = NC ? QC : min(QC, (a.K - kc + 3) >> 2);   // k-steps of this chunk (only the last chunk can be short)
+				const int nslot = ring.slot == kHNB - 1 ? 0 : ring.slot + 1;
 #pragma unroll
-				for (int q = 0; q < kHQ; ++q) {
+				for (int q = 0; q < QC; ++q) {
 					if (q < nq) {   // wave-uniform
 						double fn[4];
 						if (q == nq - 1) {
-							wait_vm(pending);   // chunk s+1 has landed ...
-							pending = 0;
+							ring.wait_vm(ring.pending);   // chunk s+1 has landed ...
+							ring.pending = 0;
 #ifndef MF_REC_NOBAR
 							__syncthreads();    // ... for every wave
 #endif
-							frag(nslot, 0, fn);
+							ring.frag(nslot, 0, fn);
 						} else {
-							frag(slot, q + 1, fn);
+							ring.frag(ring.slot, q + 1, fn);
 						}
-						// the reads stay in front of the matrix instructions (the scheduler would sink them behind the last
-						// use of the current fragment's registers to save eight VGPRs -- and expose the LDS latency per k-step)
 						__builtin_amdgcn_sched_barrier(0);
 #pragma unroll
 						for (int tu = 0; tu < TU; ++tu)
 #pragma unroll
 							for (int ti = 0; ti < 4; ++ti)
-								acc[tu][ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[c * kHQ + q][tu], fc[ti],
+								acc[tu][ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[c * QC + q][tu], fc[ti],
 								                                                   c + q == 0 ? mf_d4{0.0, 0.0, 0.0, 0.0} : acc[tu][ti], 0, 0, 0);
 						if (q == 0) {   // chunk s+2 under the matrix instructions just issued
-							const int n = issue_next();
-							if (q != nq - 1) pending = n;
+							const int n = ring.issue_next();
+							if (q != nq - 1) ring.pending = n;
 						}
 #pragma unroll
 						for (int ti = 0; ti < 4; ++ti) fc[ti] = fn[ti];
 					}
 				}
-				slot = nslot;
+				ring.slot = nslot;
 			}
 		}
 
-		// Cheap reject: after the first tiles almost no score beats its row's runner-up.  Every vector instruction of this
-		// step costs matrix-pipe time (nothing else of the SIMD runs while an FP64 matrix instruction executes, and vice
-		// versa), so the common case is ONE compare per score register -- 32 v_cmp whose lane masks land in scalar registers
-		// and are OR-ed there -- and one scalar branch; fmax() would add a canonicalising v_max per operand and a ballot two
-		// more instructions per row.  (!(v <= thr) is also true for a NaN.)  Only when the norms do not rule out non-finite
-		// scores a sum per row is formed as well: it is non-finite whenever a score is NaN or +-inf.
-		constexpr int kUGT = 10;   // llvm::FCmpInst::FCMP_UGT: unordered or greater than
 		unsigned long long rowm[4 * TU];
-		unsigned long long anym = 0;
-#pragma unroll
-		for (int tu = 0; tu < TU; ++tu)
-#pragma unroll
-			for (int r = 0; r < 4; ++r) {
-				const int x = tu * 4 + r;
-				rowm[x] = __builtin_amdgcn_fcmp(acc[tu][0][r], thr2[x], kUGT) | __builtin_amdgcn_fcmp(acc[tu][1][r], thr2[x], kUGT) |
-				          __builtin_amdgcn_fcmp(acc[tu][2][r], thr2[x], kUGT) | __builtin_amdgcn_fcmp(acc[tu][3][r], thr2[x], kUGT);
-				anym |= rowm[x];
-			}
-		if (!all_finite) {
-#pragma unroll
-			for (int tu = 0; tu < TU; ++tu)
-#pragma unroll
-				for (int r = 0; r < 4; ++r) {
-					const double sum = (acc[tu][0][r] + acc[tu][1][r]) + (acc[tu][2][r] + acc[tu][3][r]);
-					rowm[tu * 4 + r] |= __builtin_amdgcn_fcmp(fabs(sum), 1.7976931348623157e308, kUGT);
-					anym |= rowm[tu * 4 + r];
-				}
-		}
+		const bool any = cheap_reject(acc, thr2, all_finite, rowm);
 #ifdef MF_REC_NOEPI
 		if (j0 + kMI >= j_end)
 #endif
-		if (anym != 0)
+		if (any)
 #pragma unroll
 		for (int tu = 0; tu < TU; ++tu)
 #pragma unroll
 			for (int r = 0; r < 4; ++r) {
 				const int x = tu * 4 + r;
-				// slow path exactly as in recommend_mfma_kernel
 				if (rowm[x] != 0) {
+					// slow path (the whole wave, a few dozen times per row over the kernel): the lane's top-2 of the
+					// row among its unrated items, merged over the 16 lanes that share the row, folded into the
+					// row's state in LDS by the first of them, and the new runner-up handed back to all 16
 					const int row = 16 * TU * wr + 16 * tu + lq + 4 * r;
 					const unsigned long long m = maskw[par][row][wc] >> lr;
 					Top2 t{ninf, ninf, -1};
@@ -1018,15 +844,7 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 			a.filt[i0 + tid] = mf_filter{t.b1, t.b2, t.i1, bd};
 			return;
 		}
-		const double rmax = __longlong_as_double((long long) *a.rnorm_max_bits);
-		const double thr = a.thr_scale * (a.lnorm[i0 + tid] * rmax) + 1e-300;
-		const bool certain = !bd && (t.i1 < 0 || (t.b1 - t.b2) > thr);
-		if (certain) {
-			a.best[i0 + tid] = t.i1;
-		} else {
-			a.best[i0 + tid] = -2;
-			a.ulist[atomicAdd(a.ucount, 1)] = i0 + tid;
-		}
+		top1_certify(a, i0 + tid, t, bd);
 	}
 }
 
@@ -1048,15 +866,7 @@ __global__ void __launch_bounds__(256) merge_splits_kernel(RecMfmaArgs a, int ns
 		a.filt[i] = mf_filter{t.b1, t.b2, t.i1, bd};
 		return;
 	}
-	const double rmax = __longlong_as_double((long long) *a.rnorm_max_bits);
-	const double thr = a.thr_scale * (a.lnorm[i] * rmax) + 1e-300;
-	const bool certain = !bd && (t.i1 < 0 || (t.b1 - t.b2) > thr);
-	if (certain) {
-		a.best[i] = t.i1;
-	} else {
-		a.best[i] = -2;
-		a.ulist[atomicAdd(a.ucount, 1)] = i;
-	}
+	top1_certify(a, i, t, bd);
 }
 
 }  // namespace mf

@@ -230,16 +230,7 @@ __device__ __forceinline__ void store_x_row(double2 *__restrict__ out2, int lane
 // does: from inline asm with the LDS row base in M0 (a reserved register: hipcc re-loads it before each of its own uses).
 // hipcc knows NOTHING of such a transfer, so it does not drain vmcnt in front of every LDS read that might alias it, and
 // the kernel waits by hand.
-__device__ __forceinline__ unsigned lds_address(const char *p)
-{
-	return (unsigned) (unsigned long long) (__attribute__((address_space(3))) const char *) p;
-}
-
-__device__ __forceinline__ void lds_dma_m0(const char *src, unsigned m0)
-{
-	asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(m0) : "memory");
-}
-
+// (lds_address and lds_dma_m0 are in mf_common.hip.h: the certified passes use them too)
 // Several rows per instruction, for short rows (K <= 62): lane -> (row lane / PS, piece lane % PS) with PS = the tile row
 // stride in pieces (P, or P + 1 when P is even: that lane is the padding and stays off), 12 rows at K=10, 5 at K=20 --
 // instead of one instruction with five active lanes per row.

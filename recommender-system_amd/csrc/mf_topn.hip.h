@@ -11,7 +11,7 @@
 // K runs the exact form for all users (mf_plan_recommend_topn_info reports which form ran).
 #pragma once
 #include "mf_common.hip.h"
-#include "mf_recommend.hip.h"   // kHU, kHNB, kMI, mf_d4, rec_mfma2_lds
+#include "mf_ring.hip.h"        // kHU, kHNB, kMI, mf_d4, rec_mfma2_lds, cert_margin
 
 namespace mf {
 
@@ -81,7 +81,7 @@ __device__ bool topn_finish(const TopnArgs &a, int u, double *v, int *it, int ba
 	int valid = 0;
 	for (int r = 0; r <= N; ++r) valid += it[r] >= 0;
 	const double ln = a.lnorm[u];
-	const double thr = a.thr_scale * (ln * rmax) + 1e-300;
+	const double thr = cert_margin(a.thr_scale, ln, rmax);
 	if (bad || !(ln * rmax <= 1e300) || (valid > N && !((v[N - 1] - v[N]) > thr))) return false;
 	const int n = min(valid, N);
 	const double *l = a.L + (size_t) u * a.ldl;
@@ -115,6 +115,9 @@ __device__ bool topn_finish(const TopnArgs &a, int u, double *v, int *it, int ba
 // candidate lanes (the lowest first, all four lane groups of the wave at once) and inserts each score that still beats the
 // bar, the 16 lanes of the group shifting the list in one step.  After the last tile the two halves are merged, then
 // certified and re-scored (topn_finish) -- or, under an item split, written to the user's part slot for topn_merge_kernel.
+// This kernel does NOT use RRing of mf_ring.hip.h: with the ring's state in that struct hipcc addressed the lists below with
+// other instructions in all 14 instances and took two more VGPRs in the eight-wave ones (profiles/certified_parts).  Its
+// ring text is a copy of RRing's: a change to either is a change to both.
 // ------------------------------------------------------------------------------------------------
 constexpr size_t topn_list_lds(int n) { return (size_t) kHU * 2 * (size_t) (n + 1) * (sizeof(double) + sizeof(int)); }
 
@@ -163,11 +166,7 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 	}
 	if (tid < kHU) {
 		red_bad[tid][0] = red_bad[tid][1] = 0;
-		unsigned long long b = i0 + tid < a.users ? (unsigned long long) __double_as_longlong(a.lnorm[i0 + tid]) : 0ull;
-		for (int d = 32; d >= 1; d >>= 1) {
-			const unsigned long long o = __shfl_xor(b, d);
-			b = o > b ? o : b;
-		}
+		const unsigned long long b = wave_max_bits(i0 + tid < a.users ? (unsigned long long) __double_as_longlong(a.lnorm[i0 + tid]) : 0ull);
 		if (lane == 0) lmax_bits = b;
 	}
 	for (int sl = tid; sl < kHNB * kHChunkD2; sl += kHThreads) rec_lds[sl] = make_double2(0.0, 0.0);
@@ -231,11 +230,7 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 	issue_next();
 	wait_vm(issue_next());
 	__syncthreads();
-	bool all_finite;
-	{
-		const double bound = __longlong_as_double((long long) lmax_bits) * __longlong_as_double((long long) *a.rnorm_max_bits);
-		all_finite = bound <= 1e300;   // false for NaN
-	}
+	const bool all_finite = all_scores_finite(lmax_bits, a.rnorm_max_bits);
 	const int boff = (lq >> 1) * (kMI * 2) + wc * 32 + lr * 2 + (lq & 1);
 	auto frag = [&](int s, int q, double (&f)[4]) {
 		const double *Bb = reinterpret_cast<const double *>(rec_lds) + s * (kHChunkD2 * 2) + boff;
@@ -281,7 +276,9 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 				if (q == kHQ - 1) {
 					wait_vm(pending);
 					pending = 0;
+#ifndef MF_REC_NOBAR
 					__syncthreads();
+#endif
 					frag(nslot, 0, fn);
 				} else {
 					frag(slot, q + 1, fn);

@@ -3,6 +3,9 @@
 Used by tests/test_isa.py (the hand-written ISA invariants of the kernels, checked on the CPU) and as a command:
     python tools/isa.py [lib.so]                 per-kernel instruction census
     python tools/isa.py [lib.so] <symbol part>   the instructions of every kernel whose demangled name contains the part
+    python tools/isa.py --compare PARENT.so NEW.so [name part]
+                                                 per kernel `same`, `ok` or `MISS` (compare() below) with what differs:
+                                                 the table a refactor of the kernels is judged by
 Nothing here is on the product path."""
 import os
 import re
@@ -107,8 +110,82 @@ def census(body):
     return c
 
 
+# scalar ALU, compare and branch, and the s_nop padding hipcc places itself: free to move in a refactor
+_SCALAR_FREE = re.compile(r"s_(nop|branch|cbranch|cmp|cmpk|cselect|cmov|mov|movk|add|addc|addk|sub|subb|mul|mulk|and|andn\d|or|orn\d|xor|"
+                          r"xnor|nand|nor|not|lshl|lshr|ashr|bfe|bfm|min|max|abs|sext|ff[01]|flbit|bcnt|brev|bitset|bitcmp|wqm|"
+                          r"quadmask|pack|getpc|setpc|swappc)(_|$)")
+_FIXED_HEAD = re.compile(r"(global_|flat_|buffer_|scratch_|ds_|s_load|s_buffer_load|s_waitcnt|s_barrier)")
+_META = (".vgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
+
+
+def _int_or_move(op):
+    return op.startswith("v_") and not op.startswith("v_mfma") and not re.search(r"_(f16|bf16|f32|f64)", op)
+
+
+def compare(pbody, pmeta, nbody, nmeta):
+    """('same' | 'ok' | 'MISS', [what differs]) of one kernel, parent against new.
+    same: equal instruction list and metadata.
+    ok:   VGPR, spill, scratch and LDS figures equal, SGPR count no higher; from the first v_mfma to the end (reported as
+          `stream` up to the last v_mfma and `tail` behind it) every opcode count equal but for scalar ALU / compare /
+          branch and s_nop; before it (`head`: once per workgroup; the whole body of a kernel without matrix instructions)
+          memory, LDS, wait and barrier counts equal, only integer arithmetic and move opcodes differ otherwise, and at
+          most 4 vector instructions more than the parent."""
+    if pbody == nbody and pmeta == nmeta:
+        return "same", []
+    notes, ok = [], True
+    for k in _META + (".sgpr_count",):
+        a, b = pmeta.get(k), nmeta.get(k)
+        if a != b:
+            notes.append("%s %s -> %s" % (k, a, b))
+            ok &= k == ".sgpr_count" and b <= a
+    def spans(body):   # before the first matrix instruction, up to the last one, behind it (a tile's epilogue and the kernel's end)
+        mf = [i for i, x in enumerate(body) if x.startswith("v_mfma")]
+        return (body, [], []) if not mf else (body[:mf[0]], body[mf[0]:mf[-1] + 1], body[mf[-1] + 1:])
+    for span, pb, nb in zip(("head", "stream", "tail"), spans(pbody), spans(nbody)):
+        pc, nc = census(pb), census(nb)
+        for op in sorted(set(pc) | set(nc)):
+            a, b = pc.get(op, 0), nc.get(op, 0)
+            if a == b or not op[0].isalpha():   # "...": padding the disassembler skips
+                continue
+            notes.append("%s %s %d -> %d" % (span, op, a, b))
+            if _SCALAR_FREE.match(op):
+                continue
+            ok &= span == "head" and not _FIXED_HEAD.match(op) and _int_or_move(op)
+        if span == "head":
+            pv, nv = (sum(n for op, n in c.items() if op.startswith("v_")) for c in (pc, nc))
+            if nv > pv + 4:
+                notes.append("head vector instructions %d -> %d" % (pv, nv))
+                ok = False
+    if not notes:
+        notes.append("equal opcode counts and metadata; operands or order differ")
+    return ("ok" if ok else "MISS"), notes
+
+
+def _compare_main(parent, new, part):
+    pk, nk, pm, nm = disassemble(parent), disassemble(new), metadata(parent), metadata(new)
+    print("kernels: %d in %s, %d in %s" % (len(pk), parent, len(nk), new))
+    only = sorted(set(pk) ^ set(nk))
+    for n in only:
+        print("ONLY IN %s: %s" % ("PARENT" if n in pk else "NEW", n))
+    tally = {}
+    for name in sorted(set(pk) & set(nk)):
+        if part and part not in name:
+            continue
+        verdict, notes = compare(pk[name], pm.get(name, {}), nk[name], nm.get(name, {}))
+        tally[verdict] = tally.get(verdict, 0) + 1
+        if verdict != "same" or part:
+            print("%-5s %s" % (verdict, name))
+            for x in notes:
+                print("        " + x)
+    print("total: " + ", ".join("%d %s" % (tally[v], v) for v in ("same", "ok", "MISS") if v in tally) +
+          (", %d on one side only" % len(only) if only else ""))
+    return 1 if tally.get("MISS") or only else 0
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
+    if args and args[0] == "--compare":
+        sys.exit(_compare_main(args[1], args[2], args[3] if len(args) > 3 else None))
     lib = DEFAULT_LIB
     if args and args[0].endswith(".so"):
         lib = args.pop(0)
