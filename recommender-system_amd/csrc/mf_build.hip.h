@@ -375,8 +375,8 @@ int build_sparse(mf_plan *p, const mf_shard *s_in, const mf_entry *aos, bool swa
 //          11.77 vs 12.19 ms, three alternating runs on one box).  On a skewed side of that kind (the Netflix shape's 17770
 //          items of 3770 entries, cfg4-Zipf's) the extreme-row threshold moves up 2.7x with the pairs (plan_row_schedule),
 //          the scratch round trip shrinks and the side stream no longer eats into the other sweep: Netflix shape 19.7 ->
-//          17.1 ms, cfg4-Zipf 35.5 -> 31.2 (tools/r3_pair_nflx.sh; at the single-wave threshold the pairs LOSE there, 20.0
-//          vs 19.7); or
+//          17.1 ms, cfg4-Zipf 35.5 -> 31.2 (profiles/r03/pair_long_rows_ab.txt; at the single-wave threshold the pairs LOSE
+//          there, 20.0 vs 19.7); or
 //   small and skewed: at most 65536 rows and ~2 ms of bytes, the longest row at least four times the mean -- such a launch
 //          ENDS on its long rows, which a pair walks 2.4x faster than one wave (cfg3 power-law).
 // Short equally long rows stay on the single-wave form (cfg3 uniform, 253 / 166 entries per row: 0.207 vs 0.222 ms), and so
@@ -390,7 +390,6 @@ bool pair_wanted(const mf_plan *p, int kind)
 {
 	if (!p->sweep.pair || p->cfg.sweep_pair == 0) return false;
 	if (p->cfg.sweep_pair == 1) return true;
-	if (p->cfg.sweep_pair_kind[kind] >= 0) return p->cfg.sweep_pair_kind[kind] == 1;   // MF_SWEEP_PAIR_I / _U (experiments build)
 	const int nrows = kind == 0 ? p->items : p->uc;
 	if (nrows < 512 || p->nnz <= 0) return false;
 	if (pair_long_rows(p, kind)) return true;
@@ -434,16 +433,16 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 			// cfg4-Zipf 32.6 / 31.2 / 31.2 / 39.9 at 120 / 160 / 220 / 400 thousand, the rule gives 160 000)
 			const bool pairs_long = pair_wanted(p, kind) && pair_long_rows(p, kind) && p->cfg.sweep_pair != 1;
 			const int t_side = pairs_long ? std::max(128, (int) std::min(16e-6 * (double) p->nnz * (double) p->K, 2e9)) : t_long;
-			const int t_kind = cfg.sweep_long_kind[kind] > 0 ? cfg.sweep_long_kind[kind] : cfg.sweep_long_set ? t_long : std::max(t_side, (int) std::min<long long>(4 * (long long) (p->nnz / std::max(nrows, 1)), 2000000000ll));
+			const long long mean4 = std::min<long long>(4 * (long long) (p->nnz / std::max(nrows, 1)), 2000000000ll);
+			const int t_kind = cfg.sweep_long_set ? t_long : std::max(t_side, (int) mean4);
 			if (p->max_row_len[kind] < t_kind) continue;
 			// With the wave-pair form a long row is walked at ~0.055 us per entry at K=100 (a lone single wave: 0.13): when
 			// even the longest row's walk fits the sweep's bandwidth time the split buys nothing and costs the scratch
 			// round trip and a fork/join (cfg3 power-law users, longest row 2324: 0.160 -> 0.139 ms without the split).
-			const bool forced_thr = cfg.sweep_long_set || cfg.sweep_long_kind[kind] > 0;
-			if (pair_wanted(p, kind) && !forced_thr && est_us >= 50.0 &&
+			if (pair_wanted(p, kind) && !cfg.sweep_long_set && est_us >= 50.0 &&
 			    (double) p->max_row_len[kind] * 0.055 * p->K / 100.0 <= 1.3 * est_us)
 				continue;
-			if (est_us < 50.0 && nrows < 4096 && !cfg.sweep_long_set && cfg.sweep_long_kind[kind] <= 0) {
+			if (est_us < 50.0 && nrows < 4096 && !cfg.sweep_long_set) {
 				if (p->sweep.coop && (nc >= 8 || cfg.sweep_nch)) {
 					p->coop_all[kind] = true;
 					const int n = cfg.sweep_nch ? nl : nc;
@@ -476,10 +475,8 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 			// longest first: workgroups are dispatched in list order as slots free up, so the long walks start
 			// at once and the short rows fill in behind them (longest-processing-time-first scheduling)
 			auto by_len = [&](int x, int y) { return pt[(size_t) x + 1] - pt[x] > pt[(size_t) y + 1] - pt[y]; };
-			if (!cfg.nosort) {
-				std::stable_sort(sh.begin(), sh.end(), by_len);
-				std::stable_sort(lg.begin(), lg.end(), by_len);
-			}
+			std::stable_sort(sh.begin(), sh.end(), by_len);
+			std::stable_sort(lg.begin(), lg.end(), by_len);
 			MF_TRY(p->long_rows[kind].alloc(lg.size()));
 			MF_TRY(p->short_rows[kind].alloc(sh.size()));
 			MF_TRY_HIP(h2d(p, p->long_rows[kind], lg.data(), lg.size() * sizeof(int)));
@@ -488,11 +485,11 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 			p->n_long[kind] = (int) lg.size();
 			p->long_len[kind] = t_eff;
 			p->n_short[kind] = (int) sh.size();
-			// segments of 256 entries; scratch offsets in entry units, rows back to back
+			// segments of kSeg entries; scratch offsets in entry units, rows back to back
 			// entries per segment of the products launch: one wave walks a segment chunk by chunk (~2.5 us per 16 entries
 			// of exposed latency), so short segments finish sooner and there are more of them to overlap
 			// (cfg3 power-law: 256 -> 64 entries 0.452 -> 0.421 ms per iteration; Netflix-shaped 21.6 -> 21.4 ms)
-			const int kSeg = cfg.sweep_seg;
+			constexpr int kSeg = 64;
 			std::vector<int> srow, sbeg, send, lcnt;
 			std::vector<long long> sout, lbeg;
 			long long off = 0;
@@ -526,11 +523,9 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 		if (p->coop_all[0] || p->coop_all[1])
 			MF_TRY_HIP(raise_lds_limit((const void *) p->coop.fn, p->coop.lds));
 		if (p->n_long[0] || p->n_long[1]) {
-			int npr = p->single.nch;
-			if (const int v = cfg.sweep_pnch; v >= 1 && v <= 64 && head + (size_t) v * p->sweep.row_bytes <= kLdsPerCu) npr = v;
+			const int npr = p->single.nch;
 			p->prod = SweepForm{p->sweep.prod, npr, head + (size_t) npr * p->sweep.row_bytes, mf::kWave};
 			p->lds_bytes_osum = mf::kOrderedSumLds;
-			if (cfg.os_lds) p->lds_bytes_osum = std::min<size_t>(kLdsPerCu, std::max<size_t>(p->lds_bytes_osum, cfg.os_lds));
 			MF_TRY_HIP(raise_lds_limit((const void *) p->prod.fn, p->prod.lds));
 			MF_TRY_HIP(raise_lds_limit(cfg.os_dpp ? (const void *) mf::ordered_sum_kernel<true> : (const void *) mf::ordered_sum_kernel<false>, p->lds_bytes_osum));
 			// [slice][entry][kSliceCols doubles]; one block of padding per slice: the last block of a row is read whole
@@ -542,8 +537,8 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 			// beside the single-wave form: high priority -- the ordered sums are few, latency-bound waves that must get their
 			// slots ahead of the thousands of workgroups of the sweep they run under.  Beside the wave-pair form: LOW
 			// priority -- there the launch ends on the pairs of the long rows, which must be dispatched at once, and the
-			// side path has the whole other sweep to hide under (cfg3 power-law 0.304 -> 0.268 ms).  MF_SIDE_PRIO=0|1.
-			const bool side_low = cfg.side_prio >= 0 ? cfg.side_prio == 0 : (pair_wanted(p, 0) || pair_wanted(p, 1));
+			// side path has the whole other sweep to hide under (cfg3 power-law 0.304 -> 0.268 ms).
+			const bool side_low = pair_wanted(p, 0) || pair_wanted(p, 1);
 			MF_TRY_HIP(hipStreamCreateWithPriority(&p->side_stream, hipStreamNonBlocking, side_low ? prio_lo : prio_hi));
 			MF_TRY_HIP(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
 			MF_TRY_HIP(hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming));
@@ -565,21 +560,17 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 		}
 		const long long mean = rows ? ent / rows : 0;
 		p->prio_len[kind] = 0;
-		if (p->cfg.sweep_prio > 0)
-			p->prio_len[kind] = p->cfg.sweep_prio;
-		else if (p->cfg.sweep_prio < 0 && rows > 256 && longest >= 4 * std::max<long long>(mean, 1))
+		if (rows > 256 && longest >= 4 * std::max<long long>(mean, 1))
 			p->prio_len[kind] = (int) std::max<long long>(64, 2 * mean);
 	}
 	// ---- double-buffered single-wave form for the WHOLE single-wave launch: measured slower than the single-buffered form
 	// whenever the launch has more rows than double-tile workgroups fit the chip (cfg3 uniform 0.222 -> 0.429 ms: the
 	// second tile halves the resident workgroups and the CU's gather rate is shared by fewer requests in flight), so it
-	// is off unless forced (MF_SWEEP_DB=1) or the launch is below MF_SWEEP_DB_ROWS rows (experiments build).
+	// is off unless forced (MF_SWEEP_DB=1).
 	for (int kind = 0; kind < 2; ++kind) {
 		const int nrows = kind == 0 ? p->items : p->uc;
 		const int launch_rows = p->n_long[kind] > 0 ? p->n_short[kind] : nrows;
-		const int limit = p->cfg.db_rows;
-		p->use_db[kind] = p->sweep.db && !p->coop_all[kind] && launch_rows > 0 &&
-		                  (p->cfg.sweep_db == 1 || (p->cfg.sweep_db < 0 && launch_rows <= limit));
+		p->use_db[kind] = p->sweep.db && !p->coop_all[kind] && launch_rows > 0 && p->cfg.sweep_db == 1;
 		p->use_pair[kind] = !p->coop_all[kind] && !p->use_db[kind] && launch_rows > 0 && pair_wanted(p, kind);
 	}
 	// ---- a sweep of a few thousand rows is a handful of rounds of workgroups: in index order its tail is whatever
@@ -587,31 +578,30 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 	// shortest rows.  cfg3 uniform (3952 / 6040 rows of 50..311 entries): see DESIGN 5.1.  Large sweeps keep the index
 	// order (the tail is a negligible part of them and neighbouring rows share lines of the entry arrays) except for rows
 	// several times longer than the average, which lead the list.
-	if (!p->cfg.nosort)
-		for (int kind = 0; kind < 2; ++kind) {
-			const std::vector<int> &pt = kind == 0 ? cptr : rptr;
-			const int nrows = kind == 0 ? p->items : p->uc;
-			if (p->n_long[kind] > 0 || p->coop_all[kind] || nrows < 512) continue;
-			auto len = [&](int r) { return pt[(size_t) r + 1] - pt[r]; };
-			auto longer = [&](int x, int y) { return len(x) > len(y); };
-			std::vector<int> order;
-			order.reserve((size_t) nrows);
-			if (nrows <= (1 << 15)) {   // a dozen rounds of workgroups at most: the tail matters, the order of the row reads does not
-				for (int r = 0; r < nrows; ++r) order.push_back(r);
-				std::stable_sort(order.begin(), order.end(), longer);
-			} else {
-				// a large sweep with a few very long rows (power-law users): only those move to the front
-				const long long mean = p->nnz / nrows;
-				if ((long long) p->max_row_len[kind] < 8 * std::max<long long>(mean, 1)) continue;
-				std::vector<int> head;
-				for (int r = 0; r < nrows; ++r) (len(r) >= 4 * mean ? head : order).push_back(r);
-				std::stable_sort(head.begin(), head.end(), longer);
-				order.insert(order.begin(), head.begin(), head.end());
-			}
-			MF_TRY(p->short_rows[kind].alloc(order.size()));
-			MF_TRY_HIP(h2d(p, p->short_rows[kind], order.data(), order.size() * sizeof(int)));
-			p->lpt[kind] = true;
+	for (int kind = 0; kind < 2; ++kind) {
+		const std::vector<int> &pt = kind == 0 ? cptr : rptr;
+		const int nrows = kind == 0 ? p->items : p->uc;
+		if (p->n_long[kind] > 0 || p->coop_all[kind] || nrows < 512) continue;
+		auto len = [&](int r) { return pt[(size_t) r + 1] - pt[r]; };
+		auto longer = [&](int x, int y) { return len(x) > len(y); };
+		std::vector<int> order;
+		order.reserve((size_t) nrows);
+		if (nrows <= (1 << 15)) {   // a dozen rounds of workgroups at most: the tail matters, the order of the row reads does not
+			for (int r = 0; r < nrows; ++r) order.push_back(r);
+			std::stable_sort(order.begin(), order.end(), longer);
+		} else {
+			// a large sweep with a few very long rows (power-law users): only those move to the front
+			const long long mean = p->nnz / nrows;
+			if ((long long) p->max_row_len[kind] < 8 * std::max<long long>(mean, 1)) continue;
+			std::vector<int> head;
+			for (int r = 0; r < nrows; ++r) (len(r) >= 4 * mean ? head : order).push_back(r);
+			std::stable_sort(head.begin(), head.end(), longer);
+			order.insert(order.begin(), head.begin(), head.end());
 		}
+		MF_TRY(p->short_rows[kind].alloc(order.size()));
+		MF_TRY_HIP(h2d(p, p->short_rows[kind], order.data(), order.size() * sizeof(int)));
+		p->lpt[kind] = true;
+	}
 	return MF_OK;
 }
 
@@ -622,8 +612,7 @@ int plan_es_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vector
 	p->es_mode = false;
 	if (!p->want_map || !p->csr2csc) return MF_OK;
 	const size_t row_bytes = (size_t) p->sweep.row_bytes, head = (size_t) p->sweep.xs_bytes;
-	int nch = (int) std::min<size_t>(64, (kLdsPerCu / 3 - head) / row_bytes);
-	if (const int v = p->cfg.es_nch; v >= 1 && v <= 64 && head + (size_t) v * row_bytes <= kLdsPerCu) nch = v;
+	const int nch = (int) std::min<size_t>(64, (kLdsPerCu / 3 - head) / row_bytes);
 	if (nch < 1) return MF_OK;
 	p->es_nch = nch;
 	p->es_lds_errors = head + (size_t) nch * row_bytes;
@@ -667,8 +656,7 @@ int plan_es_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vector
 	{
 		const int sw = p->res_sw, nsl = (p->K + sw - 1) / sw;
 		const int per = std::max(1, ncu / (2 * nsl));
-		// waves of a workgroup that own rows (the others only help with the slice copy): MF_ES_ACTIVE
-		const int aw = p->cfg.es_active >= 1 && p->cfg.es_active <= mf::kResidentWaves ? p->cfg.es_active : mf::kResidentWaves;
+		constexpr int aw = mf::kResidentWaves;   // every wave of a workgroup owns rows
 		std::vector<mf::SliceWg> wgs;
 		for (int side = 0; side < 2; ++side) {
 			const std::vector<int> &pt = side == 0 ? cptr : rptr;
@@ -679,7 +667,7 @@ int plan_es_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vector
 			std::vector<int> cut(1, 0);
 			{
 				const int target_runs = per * aw;
-				const double row_cost = p->cfg.es_row_cost > 0 ? (double) p->cfg.es_row_cost : 16.0;   // entries a row end is worth
+				constexpr double row_cost = 16.0;   // entries a row end is worth
 				const double total_cost = (double) pt[(size_t) nrows] + row_cost * nrows;
 				double acc_cost = 0, done = 0;
 				int in_run = 0;
@@ -705,7 +693,7 @@ int plan_es_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vector
 					g.side = side;
 					g.slice = sl;
 					for (int i = 0; i <= mf::kResidentWaves; ++i) {
-						g.row_beg[i] = cut[(size_t) (w * aw + std::min(i, aw))];
+						g.row_beg[i] = cut[(size_t) (w * aw + i)];
 						g.ent_beg[i] = pt[(size_t) g.row_beg[i]];
 					}
 					if (g.row_beg[mf::kResidentWaves] > g.row_beg[0]) wgs.push_back(g);

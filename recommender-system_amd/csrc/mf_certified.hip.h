@@ -228,9 +228,8 @@ int launch_recommend_pass1(mf_plan *p, mf_filter *filt)
 	mfma_shape hs;
 	if (vec && allow_dma && p->cfg.rec_half && fits32(p->items, p->ldr)) {
 		hs = certified_shape(p->K, top1_family::kWide);
-		if (p->K == 128 && p->cfg.rec_wide) hs = {4, 8, 8};   // MF_RECOMMEND_WIDE (experiments build): K=128 in the eight-wave shape of K=256
 		if (hs.waves)
-			hfn = hs.nc == 4 && hs.qc == 8 ? mf::recommend_mfma2_kernel<4, 8, 1, 8> : certified_kernel<top1_family>(hs);
+			hfn = certified_kernel<top1_family>(hs);
 		else if (p->cfg.rec_half == 2 && p->K <= mf::kHKmax) {
 			hfn = mf::recommend_mfma2_kernel<0>;
 			hs = {0, 5, 4};
@@ -313,11 +312,7 @@ int launch_topn_core(mf_plan *p, const topn_operands &o, int n)
 
 	int rc = certified_norms(p, a.L, o.rows, o.ldl, o.lnorm, a.R, o.items, o.ldr, o.rmax_bits, o.ucount);
 	if (rc != MF_OK) return rc;
-#ifdef MF_REC_TOPNGL
-	const size_t lds = mf::rec_mfma2_lds(s.qc);
-#else
 	const size_t lds = mf::rec_mfma2_lds(s.qc) + mf::topn_list_lds(n);   // the lists sit beside the ring
-#endif
 	MF_HIP(raise_lds_limit((const void *) fn, lds));
 	constexpr size_t kStaticLds = 3 * 1024;   // topn_mfma_kernel's static arrays, rounded up
 	const bool two = two_per_cu(s.waves, lds, kStaticLds);
@@ -335,13 +330,6 @@ int launch_topn_core(mf_plan *p, const topn_operands &o, int n)
 		a.part_i = b.part_i;
 		a.part_bad = b.part_bad;
 	}
-#ifdef MF_REC_TOPNGL
-	// timing build: the lists of every workgroup in global memory
-	rc = grow_all((size_t) ublocks * (size_t) sp.nsplit * (size_t) mf::kHU * 2 * (size_t) (n + 1), b.glist_v, b.glist_i);
-	if (rc != MF_OK) return rc;
-	a.glist_v = b.glist_v;
-	a.glist_i = b.glist_i;
-#endif
 	hipLaunchKernelGGL(fn, dim3(ublocks, sp.nsplit), dim3(64 * s.waves), lds, p->stream, a);
 	MF_HIP(hipGetLastError());
 	if (sp.nsplit > 1) {

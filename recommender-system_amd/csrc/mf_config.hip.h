@@ -2,11 +2,8 @@
 // mf_backend_run_multi) into a struct the plan keeps.  Nothing reads the environment per launch or per iteration, so a
 // plan's behaviour is fixed at its creation and mf_plan_describe prints the switches that differ from their defaults.
 //
-// Two classes:
-//   * documented switches select between forms the library SHIPS -- the tests
-//     force each form through them and bench.py --check uses them for its reference run; always honoured;
-//   * experiment switches tune constants inside one form (chunk and segment sizes, schedules).  They are compiled in only
-//     with -DMF_EXPERIMENTS (make EXPERIMENTS=1; tools/ scripts build their own copy): the shipped library ignores them.
+// Every switch is documented and selects between forms the library SHIPS: the
+// tests force each form through them and bench.py --check uses them for its reference run.
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -15,7 +12,6 @@
 namespace {
 
 struct mf_config {
-	// ---- documented
 	enum IterMode { kIterAuto, kIterSweeps, kIterEs };
 	IterMode iter_mode = kIterAuto;   // MF_ITER_MODE=auto|sweeps|es: two sweeps or errors + resident streams
 	bool sweep_reg = false;           // MF_SWEEP_IMPL=reg: register-staged sweep only
@@ -41,27 +37,6 @@ struct mf_config {
 	bool multi_force = false;         // MF_MULTI_FORCE=1: sharded path even with one shard
 	bool multi_rccl = false;          // MF_MULTI_REDUCE=rccl|peer
 	bool multi_threads = true;        // MF_MULTI_THREADS=0: all shards enqueued from the calling thread
-	// ---- experiments (-DMF_EXPERIMENTS)
-	int sweep_few = 2048;             // MF_SWEEP_FEW: row count below which a sweep takes the large chunk
-	int sweep_seg = 64;               // MF_SWEEP_SEG: entries per segment of the products launch
-	int sweep_pnch = 0;               // MF_SWEEP_PNCH: chunk size of the products launch (0: the sweep's)
-	size_t os_lds = 0;                // MF_OS_LDS: LDS request of the ordered sums (bounds their waves per CU)
-	bool sum_under = false;           // MF_SWEEP_SUM_ORDER=under
-	bool no_defer = false;            // MF_SWEEP_NO_DEFER
-	bool nosort = false;              // MF_SWEEP_NOSORT
-	int sweep_pair_kind[2] = {-1, -1};  // MF_SWEEP_PAIR_I / MF_SWEEP_PAIR_U = 0|1: the wave-pair form of the item / user sweep alone
-	int es_row_cost = 0;              // MF_ES_ROW_COST: entries a row end counts for when the streams launch cuts its runs (0: rule)
-	int es_active = 0;                // MF_ES_ACTIVE=1..8: waves per workgroup of the streams launch that own rows (0: rule)
-	int es_nch = 0;                   // MF_ES_NCH: segment size of the errors launch
-	int db_rows = 0;                  // MF_SWEEP_DB_ROWS: row count below which the double-buffered sweep is chosen (0: rule)
-	int sweep_long_kind[2] = {0, 0};  // MF_SWEEP_LONG_I / MF_SWEEP_LONG_U: the extreme-row threshold of the item / user sweep alone
-	int side_prio = -1;               // MF_SIDE_PRIO=0|1: the side stream of the extreme-row path at low / high priority (-1: rule)
-	bool rec_wide = false;            // MF_RECOMMEND_WIDE: K=128 in the eight-wave, 16-users-per-wave shape of K=256
-	int pf_rows = 0;                  // MF_SWEEP_PF_ROWS: launches of up to this many rows take the pipelined-phases form (0: 262144)
-	int pair_nch = 0;                 // MF_SWEEP_PAIR_NCH: chunk size of the wave-pair form (0: 32)
-	int db_nch = 0;                   // MF_SWEEP_DB_NCH: its chunk size (0: 16)
-	bool sweep_pf = true;             // MF_SWEEP_PF=0: phases A / B as hipcc schedules them (two steps per LDS round trip)
-	int sweep_prio = -1;              // MF_SWEEP_PRIO: rows at least this long run at raised wave priority (0: none, -1: rule)
 
 	static bool is0(const char *v) { return v && v[0] == '0'; }
 	static bool eq(const char *v, const char *s) { return v && strcmp(v, s) == 0; }
@@ -98,30 +73,6 @@ struct mf_config {
 		c.multi_force = eq(getenv("MF_MULTI_FORCE"), "1");
 		c.multi_rccl = eq(getenv("MF_MULTI_REDUCE"), "rccl");
 		c.multi_threads = !is0(getenv("MF_MULTI_THREADS"));
-#ifdef MF_EXPERIMENTS
-		if ((v = getenv("MF_SWEEP_FEW"))) c.sweep_few = atoi(v);
-		if ((v = getenv("MF_SWEEP_SEG"))) c.sweep_seg = atoi(v) > 16 ? atoi(v) : 16;
-		if ((v = getenv("MF_SWEEP_PNCH"))) c.sweep_pnch = atoi(v);
-		if ((v = getenv("MF_OS_LDS"))) c.os_lds = (size_t) atoll(v);
-		c.sum_under = eq(getenv("MF_SWEEP_SUM_ORDER"), "under");
-		c.no_defer = getenv("MF_SWEEP_NO_DEFER") != nullptr;
-		c.nosort = getenv("MF_SWEEP_NOSORT") != nullptr;
-		if ((v = getenv("MF_ES_NCH"))) c.es_nch = atoi(v);
-		if ((v = getenv("MF_ES_ACTIVE"))) c.es_active = atoi(v);
-		if ((v = getenv("MF_ES_ROW_COST"))) c.es_row_cost = atoi(v);
-		if ((v = getenv("MF_SWEEP_PAIR_I"))) c.sweep_pair_kind[0] = is0(v) ? 0 : 1;
-		if ((v = getenv("MF_SWEEP_PAIR_U"))) c.sweep_pair_kind[1] = is0(v) ? 0 : 1;
-		if ((v = getenv("MF_SWEEP_DB_ROWS"))) c.db_rows = atoi(v);
-		if ((v = getenv("MF_SWEEP_DB_NCH"))) c.db_nch = atoi(v);
-		if ((v = getenv("MF_SWEEP_PAIR_NCH"))) c.pair_nch = atoi(v);
-		if ((v = getenv("MF_SWEEP_PF_ROWS"))) c.pf_rows = atoi(v);
-		c.rec_wide = getenv("MF_RECOMMEND_WIDE") != nullptr;
-		if ((v = getenv("MF_SWEEP_LONG_I"))) c.sweep_long_kind[0] = atoi(v);
-		if ((v = getenv("MF_SWEEP_LONG_U"))) c.sweep_long_kind[1] = atoi(v);
-		if ((v = getenv("MF_SIDE_PRIO"))) c.side_prio = is0(v) ? 0 : 1;
-		if ((v = getenv("MF_SWEEP_PF"))) c.sweep_pf = !is0(v);
-		if ((v = getenv("MF_SWEEP_PRIO"))) c.sweep_prio = atoi(v);
-#endif
 		return c;
 	}
 
@@ -153,28 +104,6 @@ struct mf_config {
 		if (multi_force) add("MF_MULTI_FORCE", "1");
 		if (multi_rccl) add("MF_MULTI_REDUCE", "rccl");
 		if (!multi_threads) add("MF_MULTI_THREADS", "0");
-		if (sweep_few != d.sweep_few) add("MF_SWEEP_FEW", std::to_string(sweep_few));
-		if (sweep_seg != d.sweep_seg) add("MF_SWEEP_SEG", std::to_string(sweep_seg));
-		if (sweep_pnch) add("MF_SWEEP_PNCH", std::to_string(sweep_pnch));
-		if (os_lds) add("MF_OS_LDS", std::to_string(os_lds));
-		if (sum_under) add("MF_SWEEP_SUM_ORDER", "under");
-		if (no_defer) add("MF_SWEEP_NO_DEFER", "1");
-		if (nosort) add("MF_SWEEP_NOSORT", "1");
-		if (es_nch) add("MF_ES_NCH", std::to_string(es_nch));
-		if (es_active) add("MF_ES_ACTIVE", std::to_string(es_active));
-		if (es_row_cost) add("MF_ES_ROW_COST", std::to_string(es_row_cost));
-		if (sweep_pair_kind[0] >= 0) add("MF_SWEEP_PAIR_I", std::to_string(sweep_pair_kind[0]));
-		if (sweep_pair_kind[1] >= 0) add("MF_SWEEP_PAIR_U", std::to_string(sweep_pair_kind[1]));
-		if (db_rows) add("MF_SWEEP_DB_ROWS", std::to_string(db_rows));
-		if (db_nch) add("MF_SWEEP_DB_NCH", std::to_string(db_nch));
-		if (pair_nch) add("MF_SWEEP_PAIR_NCH", std::to_string(pair_nch));
-		if (pf_rows) add("MF_SWEEP_PF_ROWS", std::to_string(pf_rows));
-		if (rec_wide) add("MF_RECOMMEND_WIDE", "1");
-		if (sweep_long_kind[0]) add("MF_SWEEP_LONG_I", std::to_string(sweep_long_kind[0]));
-		if (sweep_long_kind[1]) add("MF_SWEEP_LONG_U", std::to_string(sweep_long_kind[1]));
-		if (side_prio >= 0) add("MF_SIDE_PRIO", std::to_string(side_prio));
-		if (!sweep_pf) add("MF_SWEEP_PF", "0");
-		if (sweep_prio >= 0) add("MF_SWEEP_PRIO", std::to_string(sweep_prio));
 		return s;
 	}
 };

@@ -301,7 +301,7 @@ static int iterate_eager(mf_plan *p, int iters)
 		// Both sweeps read only the frozen generation (matFact.c:38-39), so the ordered sums of the item sweep's
 		// extreme rows may run on the side stream UNDER the whole user sweep; they are joined before the flip.
 		// Not when the user sweep has extreme rows of its own: it would reuse the scratch buffer.
-		int rc = launch_sweep(p, 0, 1, /*defer_join=*/p->n_long[1] == 0 && !p->cfg.no_defer);
+		int rc = launch_sweep(p, 0, 1, /*defer_join=*/p->n_long[1] == 0);
 		if (rc != MF_OK) return rc;
 		rc = launch_sweep(p, 1, 1);
 		if (rc != MF_OK) return rc;
@@ -971,19 +971,6 @@ int mf_backend_recommend(const mf_problem *pr, const double *L, const double *R,
 	if (!pr || !L || !R || (!best && pr->users > 0)) return MF_ERR_ARGUMENT;
 	return with_single_plan(pr, device, L, R, [&](mf_plan *p) { return mf_plan_recommend(p, best); });
 }
-
-#ifdef MF_OS_DIAG
-// diagnostic build only: read and clear the records of ordered_sum_task_diag (tools/os_diag.py)
-int mf_debug_read_os_diag(unsigned long long *out, int words)
-{
-	static unsigned long long zero[2 + 8 * 32];
-	if (words > (int) (sizeof zero / sizeof zero[0])) words = (int) (sizeof zero / sizeof zero[0]);
-	MF_HIP(hipDeviceSynchronize());
-	MF_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(mf::mf_os_diag), sizeof(unsigned long long) * (size_t) words));
-	MF_HIP(hipMemcpyToSymbol(HIP_SYMBOL(mf::mf_os_diag), zero, sizeof zero));
-	return MF_OK;
-}
-#endif
 
 #ifdef MF_STAMPS
 // diagnostic build only: read and clear the phase clocks of sweep_dma_kernel (tools/stamps.py)

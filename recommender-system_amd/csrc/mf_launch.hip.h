@@ -52,6 +52,11 @@ bool sweep_is_dma(const mf_config &cfg, int K)
 struct ChunkSizes {
 	int nch, nch_few;
 };
+// "Few rows": the launch cannot fill the chip whatever the chunk size, its time is the longest row's serial chain of
+// chunks -> the largest chunk.  Only below ~2048 rows: at 3952 rows (the cfg3 item sweep) the large chunk's LDS
+// footprint cost more occupancy than it saved (item sweep 0.189 -> 0.123 ms with the ordinary chunk).  The sweeps
+// (launch_sweep) and the loss (launch_loss) share the bound.
+constexpr int kSweepFewRows = 2048;
 ChunkSizes chunk_rule(size_t head, size_t row_bytes, const mf_config &cfg)
 {
 	auto fit = [&](size_t budget) {
@@ -96,7 +101,6 @@ int choose_sweep(mf_plan *p)
 				break;
 			}
 	if (!p->sweep.fn) return MF_ERR_UNSUPPORTED;
-	if (!p->cfg.sweep_pf) p->sweep.pf = nullptr;   // MF_SWEEP_PF=0 (experiments build): round 2's accumulate form everywhere
 
 	p->stride = mf::reg_row_stride(K);
 	const size_t row_bytes = tile_row_bytes(p), head = tile_head_bytes(p);
@@ -115,17 +119,17 @@ int choose_sweep(mf_plan *p)
 	if (p->sweep.pair) {   // wave-pair form
 		// 32-entry chunks: the loader's ~90 cycles per gathered row are what a pair is bound by, the K steps of phase A are
 		// paid per chunk -- a lone 5993-entry row: 0.526 ms at 16, 0.332 at 32; cfg3 power-law 0.311 / 0.268 / 0.314 at 24 / 32 / 40
-		p->pair = two_tiles(p->sweep.pair, p->cfg.pair_nch > 0 ? p->cfg.pair_nch : 32, 2 * mf::kWave);
+		p->pair = two_tiles(p->sweep.pair, 32, 2 * mf::kWave);
 		MF_HIP(raise_lds_limit((const void *) p->pair.fn, p->pair.lds));
 	}
 	if (p->sweep.db) {   // double-buffered form (few rows per CU: the wave hides its own gather)
-		p->db = two_tiles(p->sweep.db, p->cfg.db_nch > 0 ? p->cfg.db_nch : 16, mf::kWave);
+		p->db = two_tiles(p->sweep.db, 16, mf::kWave);
 		MF_HIP(raise_lds_limit((const void *) p->db.fn, p->db.lds));
 	}
 	// ---- errors + streams iteration (mf_stream.hip.h) for instances whose factors stay in L2 / Infinity Cache: the
 	// two sweeps are then bound by the latency of one wave walking a row chunk by chunk, not by bandwidth.  It costs a
 	// third gather of every entry's row, so it is only chosen while the factors are cache-resident; MF_ITER_MODE=es |
-	// sweeps overrides, MF_ES_MAX_MB moves the limit.
+	// sweeps overrides.
 	p->want_map = false;
 	p->res_sw = resident_slice_width(p->cfg, K, std::max(p->uc, p->items));
 	if (p->sweep.errs && p->nnz > 0) {
@@ -167,7 +171,7 @@ int choose_loss(mf_plan *p)
 bool single_wave_pipelined(const mf_plan *p, int kind)
 {
 	const int nrows = kind == 0 ? p->items : p->uc;
-	const int kPfRows = p->cfg.pf_rows > 0 ? p->cfg.pf_rows : (p->K > 128 ? INT_MAX : 262144);
+	const int kPfRows = p->K > 128 ? INT_MAX : 262144;
 	return p->sweep.pf && p->n_short[kind] <= kPfRows && nrows <= kPfRows;
 }
 
@@ -177,7 +181,7 @@ bool single_wave_pipelined(const mf_plan *p, int kind)
 SweepForm main_form(const mf_plan *p, int kind, bool few_rows)
 {
 	if (p->coop_all[kind]) {
-		// A cooperative launch of sweep_few rows or more runs at the single-wave chunk size with the cooperative LDS request,
+		// A cooperative launch of kSweepFewRows rows or more runs at the single-wave chunk size with the cooperative LDS request,
 		// as it always has.  Known and left for a change of its own, with a test: at K = 30 and K = 50 that request is sized
 		// for fewer rows (14 and 8) than the 16 of the single-wave chunk.
 		SweepForm f = p->coop;
@@ -228,11 +232,9 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	a.scratch_entries = 0;
 	if (a.nrows <= 0) return MF_OK;
 	const bool extreme = p->n_long[kind] > 0;
-	// "few rows": the launch cannot fill the chip whatever the chunk size, its time is the longest row's serial chain
-	// of chunks -> the largest chunk.  Only below ~2048 rows: at 3952 rows (the cfg3 item sweep) the large chunk's LDS
-	// footprint cost more occupancy than it saved (item sweep 0.189 -> 0.123 ms with the ordinary chunk).  Never beside
-	// the extreme-row path: with the extreme rows gone the occupancy-friendly chunk size is right again.
-	const SweepForm f = main_form(p, kind, !extreme && a.nrows < p->cfg.sweep_few);
+	// the large chunk below kSweepFewRows rows.  Never beside the extreme-row path: with the extreme rows gone the
+	// occupancy-friendly chunk size is right again.
+	const SweepForm f = main_form(p, kind, !extreme && a.nrows < kSweepFewRows);
 	a.nch = f.nch;
 	TimedLaunch t{};
 	if (p->timing) {
@@ -273,20 +275,10 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 		o.stamps = nullptr;
 		o.max_cnt = p->max_row_len[kind];
 		void *oargs[] = {&o};
-		// Schedule (MF_SWEEP_SUM_ORDER): "after" (default) -- products kernel and ordered sums on the side stream
-		// while the remaining rows run on the main stream; "under" -- products first on the main stream, then the
-		// ordered sums on the side stream under the sweep of the remaining rows.
-		const bool under = p->cfg.sum_under;
-		hipStream_t prod_stream = under ? p->stream : p->side_stream;
-		if (!under) {
-			MF_HIP(hipEventRecord(p->ev_fork, p->stream));
-			MF_HIP(hipStreamWaitEvent(p->side_stream, p->ev_fork, 0));
-		}
-		MF_HIP(hipLaunchKernel((const void *) p->prod.fn, dim3(b.nrows), dim3(p->prod.block), bargs, p->prod.lds, prod_stream));
-		if (under) {
-			MF_HIP(hipEventRecord(p->ev_fork, p->stream));
-			MF_HIP(hipStreamWaitEvent(p->side_stream, p->ev_fork, 0));
-		}
+		// Schedule: products kernel and ordered sums on the side stream while the remaining rows run on the main stream.
+		MF_HIP(hipEventRecord(p->ev_fork, p->stream));
+		MF_HIP(hipStreamWaitEvent(p->side_stream, p->ev_fork, 0));
+		MF_HIP(hipLaunchKernel((const void *) p->prod.fn, dim3(b.nrows), dim3(p->prod.block), bargs, p->prod.lds, p->side_stream));
 		MF_HIP(hipLaunchKernel(p->cfg.os_dpp ? (const void *) mf::ordered_sum_kernel<true> : (const void *) mf::ordered_sum_kernel<false>,
 		                       dim3(o.nrows * o.nslices), dim3(mf::kWave), oargs,
 		                       p->lds_bytes_osum, p->side_stream));

@@ -31,7 +31,7 @@ int launch_loss(mf_plan *p, const int *ptr, const int *idx, const double *val, c
 		a.R = p->Rbuf[p->cur];
 		a.row_sse = p->row_sse;
 		a.rowlist = order;
-		const int few = a.nrows < p->cfg.sweep_few ? 1 : 0;
+		const int few = a.nrows < kSweepFewRows ? 1 : 0;
 		a.nch = p->loss_nch[few];
 		void *args[] = {&a};
 		MF_HIP(hipLaunchKernel((const void *) p->loss_fn, dim3(std::min(a.nrows, 1 << 20)), dim3(mf::kWave), args, p->loss_lds[few],

@@ -138,10 +138,6 @@ struct topn_buffers {
 	dev_buf<int> part_i, part_bad;
 	int64_t last_uncertain = -1;     // rows of the last call that went through the exact pass (-1: exact form ran)
 	int form = -1;                   // form of the last call (mf_plan_recommend_topn_info)
-#ifdef MF_REC_TOPNGL
-	dev_buf<double> glist_v;         // timing build: the matrix-core pass's lists in global memory
-	dev_buf<int> glist_i;
-#endif
 };
 
 // The operands of a top-N pass: `rows` rows of L (pitch ldl) are ranked against the `items` rows of R (pitch ldr), row i

@@ -753,9 +753,7 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 						if (q == nq - 1) {
 							ring.wait_vm(ring.pending);   // chunk s+1 has landed ...
 							ring.pending = 0;
-#ifndef MF_REC_NOBAR
 							__syncthreads();    // ... for every wave
-#endif
 							ring.frag(nslot, 0, fn);
 						} else {
 							ring.frag(ring.slot, q + 1, fn);
@@ -781,9 +779,6 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 
 		unsigned long long rowm[4 * TU];
 		const bool any = cheap_reject(acc, thr2, all_finite, rowm);
-#ifdef MF_REC_NOEPI
-		if (j0 + kMI >= j_end)
-#endif
 		if (any)
 #pragma unroll
 		for (int tu = 0; tu < TU; ++tu)

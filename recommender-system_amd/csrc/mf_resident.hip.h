@@ -21,9 +21,6 @@
 #include "mf_common.hip.h"
 #include <type_traits>
 #include "mf_stream.hip.h"
-#ifndef MF_ES_ABLATE
-#define MF_ES_ABLATE 0   // diagnostic builds only (results wrong, timing valid): 1 no read-back, 2 no y gather, 3 no add chain
-#endif
 
 namespace mf {
 
@@ -215,28 +212,15 @@ __global__ void __launch_bounds__(kResidentThreads) stream_resident_kernel(Slice
 			constexpr int PAR = decltype(par_c)::value;
 			const int s0 = sidx * G;
 			const StreamRec my3 = recbuf[s0 + 3 * G + g];            // records of step sidx + 3 (padding past the chunk)
-#if MF_ES_ABLATE == 2
-			const double y2 = (double) my2.idx;                      // ablation: no gather of y from the LDS slice
-#else
 			const double y2 = ys[(size_t) my2.idx * SW + c];         // y of step sidx + 2
-#endif
 			prod[(PAR ^ 1) * kWave + lane] = my1.err * y1;           // products of step sidx + 1 ...
 			// ... back into registers (every lane group reads them: masking the read-back to the one group that stores
 			// the row was measured 6 % slower -- the LDS cost of an instruction does not shrink with its active lanes)
-#if MF_ES_ABLATE == 1
-#pragma unroll
-			for (int u = 0; u < G; ++u) pr[PAR ^ 1][u] = my1.err * (double) u;   // ablation: no read-back of the products
-#else
 #pragma unroll
 			for (int u = 0; u < G; ++u) pr[PAR ^ 1][u] = prod[(PAR ^ 1) * kWave + u * SW + c];
-#endif
 			if (inside) {
-#if MF_ES_ABLATE == 3
-				acc = acc + ((pr[PAR][0] + pr[PAR][1]) + (pr[PAR][G - 2] + pr[PAR][G - 1]));   // ablation: no chain of G dependent adds
-#else
 #pragma unroll
 				for (int u = 0; u < G; ++u) acc = acc + pr[PAR][u];
-#endif
 			} else {
 				const int m = min(G, cnt - s0), pos0 = c0 + s0;
 #pragma unroll

@@ -250,9 +250,7 @@ struct RRing {
 						if (last) {
 							wait_vm(pending);   // chunk s+1 has landed ...
 							pending = 0;
-#ifndef MF_REC_NOBAR
 							__syncthreads();    // ... for every wave
-#endif
 							frag(nslot, 0, fn);
 						} else {
 							frag(slot, q + 1, fn);

@@ -974,8 +974,8 @@ __global__ void __launch_bounds__((NL + 1) * kWave) sweep_pair_kernel(SweepArgs 
 // Why: round 2 shipped, for a while, a two-register software pipeline -- the read of block b+1 issued from an asm statement
 // before the chain of block b, `s_waitcnt lgkmcnt(0)` in another asm statement at the top of the next step -- that gave one
 // wrong sum per ~1e8 blocks, only beside another kernel on a busy chip, and was blamed on the hardware (DPP beside a
-// returning LDS read).  It was a SOFTWARE bug, settled in round 3 from the builds kept in tools/micro/alt and with the
-// diagnostic build below (tools/os_diag.py): the loop's odd tail step ended in `cur = nxt;` in front of `landed(cur)`, and
+// returning LDS read).  It was a SOFTWARE bug, settled in round 3 from the builds kept in tools/micro/alt and with a
+// diagnostic build of that loop: the loop's odd tail step ended in `cur = nxt;` in front of `landed(cur)`, and
 // hipcc -- for which an asm output is written when the statement ends -- emitted that copy as two v_mov_b64 of the PENDING
 // quad in front of the wait (libmatfact_hip_base.so: ds_read_b128 v[24:27] ... v_mov_b64 v[6:7], v[24:25] / v[8:9],
 // v[26:27] ... s_waitcnt lgkmcnt(0), in all three depth classes).  Whenever the read took longer than the chain in between
@@ -1189,204 +1189,6 @@ __device__ __forceinline__ void ordered_sum_task(const char *src, unsigned ring_
 	if (b == 0) read_seed();
 	for (; b < nblk; ++b) add_block(b, min(EB, cnt - EB * b), std::integral_constant<int, -1>{}, -1);
 }
-#ifdef MF_OS_DIAG
-// Diagnostic builds only (make csrc/libmatfact_hip_osdiag<level>.so; tools/os_diag.py): ROUND 2'S LOOP -- the LDS read of
-// block b+1 issued before the v_fmac_f64_dpp chain of block b and waited for after it, two registers swapping roles, the
-// odd tail step ending in `cur = nxt` -- with two checks after every chain, written to tell the candidate causes apart:
-//   bit 0  the register the chain consumed differs from what the block's LDS slot holds NOW (re-read after the chain):
-//          the read returned before the transfer had landed, or returned something else than the slot's bytes;
-//   bit 1  the chain's result differs from the same 16 adds formed without DPP from the SAME register (lane e of the
-//          row fetched by ds_bpermute): the DPP chain mis-executed.
-// Neither bit set on a launch whose result is wrong: the slot itself held wrong bytes (the scratch as this wave's
-// transfers saw it).  mf_os_diag: [0] blocks checked, [1] records, then 8 words per record.
-// What the levels showed (tenth-scale Netflix shape, MF_SWEEP_LONG=3000, 1500 lockstep iterations each): level 1 (the old
-// loop, no checks) 93 wrong iterations; level 4 (the transfer issued before the chain) 131; levels 2, 3 and 5 (a check --
-// hence an `s_waitcnt lgkmcnt(0)` -- after the chain, in front of or behind the transfer) none, no record.  The checks
-// cured what they were looking for: the wait they add sits in front of the compiler's copy of the pending quad (the
-// `cur = nxt` of the tail step, see the ISA of level 1: v_mov_b64 v[8:9], v[26:27] / v[10:11], v[28:29] ahead of the
-// lgkmcnt(0)).  Cause = that copy; neither DPP nor the transfers.
-__device__ unsigned long long mf_os_diag[2 + 8 * 32];
-
-template <int D>
-__device__ __forceinline__ void ordered_sum_task_diag(const char *src, unsigned ring_base, unsigned my, int cnt,
-                                                      const double *seed_ptr, double &ax, double &ay, double one, int task)
-{
-	constexpr int EB = kBlockEntries;
-	const int nblk = (cnt + EB - 1) / EB;
-	const int lane = threadIdx.x;
-	auto slot_of = [&](int b) { return (unsigned) (b & (kRing - 1)) * 1024u; };
-	auto issue = [&](int b) {
-		const char *g = src + (size_t) b * 1024;
-		const unsigned m0 = __builtin_amdgcn_readfirstlane(ring_base + slot_of(b));
-		asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(m0) : "memory");
-	};
-	auto read_block = [&](int b, v2d &v) {
-		const unsigned addr = my + slot_of(b);
-		asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-	};
-	auto landed = [&](v2d &v) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v)::"memory"); };
-	auto add16 = [&](const v2d &v) {
-		MF_FMAC_BCAST(0); MF_FMAC_BCAST(1); MF_FMAC_BCAST(2); MF_FMAC_BCAST(3);
-		MF_FMAC_BCAST(4); MF_FMAC_BCAST(5); MF_FMAC_BCAST(6); MF_FMAC_BCAST(7);
-		MF_FMAC_BCAST(8); MF_FMAC_BCAST(9); MF_FMAC_BCAST(10); MF_FMAC_BCAST(11);
-		MF_FMAC_BCAST(12); MF_FMAC_BCAST(13); MF_FMAC_BCAST(14); MF_FMAC_BCAST(15);
-	};
-	auto checked_add16 = [&](int blk, const v2d &v) {
-		// MF_OS_DIAG = 1: the old order alone (does it still fail beside this round's kernels?), 2: + the re-read check,
-		// 3: + the DPP-free recomputation (32 ds_bpermute per block: it changes the timing the most)
-		const double bx = ax, by = ay;
-		add16(v);
-		double px = ax, py = ay;
-		v2d chk = v;
-#if MF_OS_DIAG >= 3
-		// (bit 1) the same sixteen adds without DPP, from the same register
-		px = bx;
-		py = by;
-#pragma unroll
-		for (int e = 0; e < 16; ++e) {
-			px = px + __shfl(v.x, (lane & ~15) + e);
-			py = py + __shfl(v.y, (lane & ~15) + e);
-		}
-#else
-		(void) bx;
-		(void) by;
-#endif
-#if MF_OS_DIAG >= 2
-		// (bit 0) the slot again, now that the chain is over (it is refilled one step later at the earliest)
-		{
-			const unsigned addr = my + slot_of(blk);
-			asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(chk) : "v"(addr) : "memory");
-		}
-#endif
-		int flags = 0;
-		if (__double_as_longlong(chk.x) != __double_as_longlong(v.x) || __double_as_longlong(chk.y) != __double_as_longlong(v.y)) flags |= 1;
-		if (__double_as_longlong(px) != __double_as_longlong(ax) || __double_as_longlong(py) != __double_as_longlong(ay)) flags |= 2;
-#if MF_OS_DIAG >= 2
-		if (lane == 0) atomicAdd(&mf_os_diag[0], 1ull);
-#endif
-		if (flags) {
-			const unsigned long long slot = atomicAdd(&mf_os_diag[1], 1ull);
-			if (slot < 32) {
-				unsigned long long *r = mf_os_diag + 2 + 8 * slot;
-				r[0] = (unsigned long long) task;
-				r[1] = (unsigned long long) blk | ((unsigned long long) nblk << 32);
-				r[2] = (unsigned long long) lane | ((unsigned long long) flags << 32) | ((unsigned long long) D << 40);
-				r[3] = (unsigned long long) __double_as_longlong(v.x);
-				r[4] = (unsigned long long) __double_as_longlong(chk.x);
-				r[5] = (unsigned long long) __double_as_longlong(ax);
-				r[6] = (unsigned long long) __double_as_longlong(px);
-				r[7] = (unsigned long long) __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
-			}
-		}
-	};
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	if (seed_ptr) {
-		const unsigned m0 = __builtin_amdgcn_readfirstlane(ring_base + (unsigned) kRing * 1024u);
-		asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(seed_ptr), "s"(m0) : "memory");
-	}
-	auto read_seed = [&]() {
-		v2d sv = {0.0, 0.0};
-		if (seed_ptr) {
-			const unsigned addr = my + (unsigned) kRing * 1024u;
-			asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(sv) : "v"(addr) : "memory");
-		}
-		ax = sv.x;
-		ay = sv.y;
-	};
-	const int ahead = min(nblk, D - 1);
-	for (int b = 0; b < ahead; ++b) issue(b);
-	int b = 0;
-	if (nblk > D - 1) {
-		v2d cur, nxt;
-		asm volatile("s_waitcnt vmcnt(%0)" ::"n"(D - 2) : "memory");
-		read_seed();
-		read_block(0, cur);
-		auto step = [&](int blk, v2d &have, v2d &want) {   // round 2's failing order
-			landed(have);
-			asm volatile("s_waitcnt vmcnt(%0)" ::"n"(D - 3) : "memory");
-			read_block(blk + 1, want);   // in flight under the chain below
-#if MF_OS_DIAG == 4
-			issue(blk + D - 1);          // 4: the transfer issued BEFORE the chain instead of after it
-			add16(have);
-#elif MF_OS_DIAG == 5
-			// 5: the failing sequence untouched -- read, chain, transfer -- and the checks only AFTER the transfer is out
-			const double bx = ax, by = ay;
-			add16(have);
-			issue(blk + D - 1);
-			{
-				double px = bx, py = by;
-#pragma unroll
-				for (int e = 0; e < 16; ++e) {
-					px = px + __shfl(have.x, (lane & ~15) + e);
-					py = py + __shfl(have.y, (lane & ~15) + e);
-				}
-				v2d chk;
-				const unsigned addr = my + slot_of(blk);
-				asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(chk) : "v"(addr) : "memory");
-				int flags = 0;
-				if (__double_as_longlong(chk.x) != __double_as_longlong(have.x) || __double_as_longlong(chk.y) != __double_as_longlong(have.y)) flags |= 1;
-				if (__double_as_longlong(px) != __double_as_longlong(ax) || __double_as_longlong(py) != __double_as_longlong(ay)) flags |= 2;
-				if (lane == 0) atomicAdd(&mf_os_diag[0], 1ull);
-				if (flags) {
-					const unsigned long long slot = atomicAdd(&mf_os_diag[1], 1ull);
-					if (slot < 32) {
-						unsigned long long *r = mf_os_diag + 2 + 8 * slot;
-						r[0] = (unsigned long long) task;
-						r[1] = (unsigned long long) blk | ((unsigned long long) nblk << 32);
-						r[2] = (unsigned long long) lane | ((unsigned long long) flags << 32) | ((unsigned long long) D << 40);
-						r[3] = (unsigned long long) __double_as_longlong(have.x);
-						r[4] = (unsigned long long) __double_as_longlong(chk.x);
-						r[5] = (unsigned long long) __double_as_longlong(ax);
-						r[6] = (unsigned long long) __double_as_longlong(px);
-						r[7] = (unsigned long long) __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
-					}
-				}
-			}
-#else
-			checked_add16(blk, have);
-			issue(blk + D - 1);
-#endif
-		};
-		for (; b + D < nblk; b += 2) {
-			step(b, cur, nxt);
-			step(b + 1, nxt, cur);
-		}
-		if (b + (D - 1) < nblk) {
-			step(b, cur, nxt);
-			cur = nxt;
-			++b;
-		}
-		landed(cur);
-		add16(cur);
-		++b;
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	} else {
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		read_seed();
-	}
-	for (; b < nblk; ++b) {
-		v2d v;
-		asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(my + slot_of(b)) : "memory");
-		const int n = min(EB, cnt - EB * b);
-		if (n > 0) MF_FMAC_BCAST(0);
-		if (n > 1) MF_FMAC_BCAST(1);
-		if (n > 2) MF_FMAC_BCAST(2);
-		if (n > 3) MF_FMAC_BCAST(3);
-		if (n > 4) MF_FMAC_BCAST(4);
-		if (n > 5) MF_FMAC_BCAST(5);
-		if (n > 6) MF_FMAC_BCAST(6);
-		if (n > 7) MF_FMAC_BCAST(7);
-		if (n > 8) MF_FMAC_BCAST(8);
-		if (n > 9) MF_FMAC_BCAST(9);
-		if (n > 10) MF_FMAC_BCAST(10);
-		if (n > 11) MF_FMAC_BCAST(11);
-		if (n > 12) MF_FMAC_BCAST(12);
-		if (n > 13) MF_FMAC_BCAST(13);
-		if (n > 14) MF_FMAC_BCAST(14);
-		if (n > 15) MF_FMAC_BCAST(15);
-	}
-}
-#endif
 #undef MF_FMAC_BCAST
 
 template <bool DPP>
@@ -1416,16 +1218,6 @@ __global__ void __launch_bounds__(kWave) ordered_sum_kernel(OrderedSumArgs a)
 		// every lane a valid address (the dead lanes of the last slice fetch column 0; they never store)
 		const double *seed_ptr = a.seed ? a.X_old + (size_t) r * a.ldx + (live ? k0 : 0) : nullptr;
 		double ax = 0.0, ay = 0.0;
-#ifdef MF_OS_DIAG
-		if constexpr (DPP) {
-			if (4 * (long long) cnt >= 2 * (long long) a.max_cnt)
-				ordered_sum_task_diag<kRing>(src, ring_base, my, cnt, seed_ptr, ax, ay, one, it);
-			else if (4 * (long long) cnt >= (long long) a.max_cnt)
-				ordered_sum_task_diag<kRing / 2>(src, ring_base, my, cnt, seed_ptr, ax, ay, one, it);
-			else
-				ordered_sum_task_diag<kRing / 4>(src, ring_base, my, cnt, seed_ptr, ax, ay, one, it);
-		} else
-#endif
 		// in flight: all of the ring for the longest rows, a half or a quarter of it for the shorter ones
 		if (4 * (long long) cnt >= 2 * (long long) a.max_cnt)
 			ordered_sum_task<kRing, DPP>(src, ring_base, my, cnt, seed_ptr, ax, ay, one, t_issued);

@@ -39,12 +39,6 @@ struct TopnArgs {
 	double *__restrict__ part_v;               // users x (nsplit + 1) x (n + 1); slot nsplit is the merge's scratch
 	int *__restrict__ part_i;
 	int *__restrict__ part_bad;                // users x nsplit
-#ifdef MF_REC_TOPNGL
-	// timing build only (make csrc/libmatfact_hip_ablate_TOPNGL.so): the lists in global memory instead of LDS,
-	// 64 x 2 x (n + 1) entries per workgroup, so that two workgroups per CU fit at every N
-	double *glist_v;
-	int *glist_i;
-#endif
 };
 
 // B[i][j] exactly as mat2d_prod forms it (mat2d.c:100-113): sequential k from 0.0, separate multiply and add
@@ -131,14 +125,8 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 	const int K = a.K;
 	const int M = a.n + 1;
 	// lists: [user][half][M] scores, then the same of items
-#ifdef MF_REC_TOPNGL
-	const size_t wg_slice = ((size_t) blockIdx.y * gridDim.x + blockIdx.x) * (size_t) (kHU * 2 * M);
-	double *const lst_v = a.glist_v + wg_slice;
-	int *const lst_i = a.glist_i + wg_slice;
-#else
 	double *const lst_v = reinterpret_cast<double *>(rec_lds + kHNB * kHChunkD2);
 	int *const lst_i = reinterpret_cast<int *>(lst_v + kHU * 2 * M);
-#endif
 	__shared__ unsigned long long maskw[2][kHU][2];   // [tile parity][user][item half]
 	__shared__ int red_bad[kHU][2];
 	__shared__ unsigned long long lmax_bits;
@@ -276,9 +264,7 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 				if (q == kHQ - 1) {
 					wait_vm(pending);
 					pending = 0;
-#ifndef MF_REC_NOBAR
 					__syncthreads();
-#endif
 					frag(nslot, 0, fn);
 				} else {
 					frag(slot, q + 1, fn);
@@ -394,9 +380,6 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 											li[e] = j0 + 64 * wc + 16 * ti + (src & 15);
 										}
 									}
-#ifdef MF_REC_TOPNGL
-									__threadfence_block();   // the stores of the other lanes before the next read of the list
-#endif
 									t = lv[M - 1];
 								}
 							}

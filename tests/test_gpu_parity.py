@@ -293,8 +293,8 @@ def test_wave_pair_rule_and_extreme_rows_beside_it(capi, orc, monkeypatch):
 
 def test_switches_are_read_once_per_plan_and_experiments_are_not_in_the_shipped_library(capi, monkeypatch):
     """csrc/mf_config.hip.h: a plan's behaviour is fixed when it is created (a switch set afterwards changes nothing),
-    mf_plan_describe names every documented switch that differs from its default, and the shipped library ignores the
-    experiment-only ones (they exist in the -DMF_EXPERIMENTS build only)."""
+    mf_plan_describe names every documented switch that differs from its default, and the library ignores the names of
+    the retired experiment switches: they are gone from the sources, not compiled out (DESIGN.md 8b lists them)."""
     d = random_instance(3, 120, 90, 100, density=0.3)
     for k in ("MF_ITER_MODE", "MF_SWEEP_DB", "MF_SWEEP_NCH", "MF_SWEEP_SEG", "MF_SWEEP_PNCH", "MF_ES_NCH", "MF_SWEEP_FEW"):
         monkeypatch.delenv(k, raising=False)
@@ -306,8 +306,11 @@ def test_switches_are_read_once_per_plan_and_experiments_are_not_in_the_shipped_
     assert "config{MF_SWEEP_NCH=7}" in later.describe() and " nch=7 " in later.describe(), later.describe()
     monkeypatch.delenv("MF_SWEEP_NCH")
     for k, v in (("MF_SWEEP_SEG", "32"), ("MF_SWEEP_PNCH", "8"), ("MF_ES_NCH", "8"), ("MF_SWEEP_FEW", "1"), ("MF_SWEEP_PF", "0"),
-                 ("MF_ES_ACTIVE", "4"), ("MF_ES_ROW_COST", "40"), ("MF_SWEEP_PAIR_I", "1"), ("MF_SWEEP_TRIO", "1"), ("MF_SWEEP_PF_ROWS", "5"), ("MF_RECOMMEND_WIDE", "1")):
-        monkeypatch.setenv(k, v)                        # experiments: not compiled into the shipped library
+                 ("MF_ES_ACTIVE", "4"), ("MF_ES_ROW_COST", "40"), ("MF_SWEEP_PAIR_I", "1"), ("MF_SWEEP_TRIO", "1"), ("MF_SWEEP_PF_ROWS", "5"), ("MF_RECOMMEND_WIDE", "1"),
+                 ("MF_OS_LDS", "65536"), ("MF_SWEEP_SUM_ORDER", "under"), ("MF_SWEEP_NO_DEFER", "1"), ("MF_SWEEP_NOSORT", "1"),
+                 ("MF_SWEEP_PAIR_U", "1"), ("MF_SWEEP_DB_ROWS", "1000"), ("MF_SWEEP_DB_NCH", "8"), ("MF_SWEEP_PAIR_NCH", "8"),
+                 ("MF_SWEEP_LONG_I", "40"), ("MF_SWEEP_LONG_U", "40"), ("MF_SIDE_PRIO", "0"), ("MF_SWEEP_PRIO", "64")):
+        monkeypatch.setenv(k, v)                        # retired experiment switches: no build reads them
     exp = capi.Plan(120, 90, 100, 0.01, d["row"], d["col"], d["val"])
     assert exp.describe() == plain.describe(), (exp.describe(), plain.describe())
     for p in (plain, later, exp):

@@ -388,3 +388,26 @@ def test_binary_cache_header_only_instance_and_many_open_problems(capi, tmp_path
         assert p.nnz == 2 and p.entries[1].value == n + 0.5
         h.mf_host_free_problem(C.byref(p))
         assert not p.entries
+
+
+def test_every_switch_the_library_reads_is_documented():
+    """One class of switches: the MF_* names the HIP sources read from the environment are exactly those of the
+    "Documented" table of DESIGN.md 8b (MF_HIP_LIB apart: the Python binding reads it), and mf_config::describe() can
+    name each of them."""
+    import glob
+    csrc = os.path.join(ROOT, "recommender-system_amd", "csrc")
+    read = set()
+    for path in glob.glob(os.path.join(csrc, "*.hip*")):
+        read |= set(re.findall(r'getenv\("(MF_\w+)"\)', open(path).read()))
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    table = design[design.index("*Documented*"):]
+    rows = re.search(r"\n\n((?:\|[^\n]*\n)+)", table).group(1).splitlines()[2:]
+    documented = set()
+    for row in rows:
+        documented |= set(re.findall(r"`(MF_[A-Z0-9_]+)", row.split(" | ")[0]))
+    assert len(rows) > 5 and "MF_HIP_LIB" in documented
+    assert read == documented - {"MF_HIP_LIB"}, (sorted(read - documented), sorted(documented - read))
+    config = open(os.path.join(csrc, "mf_config.hip.h")).read()
+    describe = config[config.index("std::string describe() const"):]
+    named = set(re.findall(r'add\("(MF_\w+)"', describe))
+    assert read == named, sorted(read ^ named)
