@@ -15,14 +15,6 @@ inline hipError_t h2d(mf_plan *p, void *dst, const void *src, size_t bytes)
 }
 
 
-// inside helpers that return a status directly
-#define MF_TRY(x)                       \
-	do {                                \
-		int _rc = (x);                  \
-		if (_rc != MF_OK) return _rc;   \
-	} while (0)
-#define MF_TRY_HIP(call) MF_HIP(call)
-
 // stable counting sort of the entries by `key` into (ptr, idx, val)
 void bucket(int64_t nnz, int nkeys, const int32_t *key, int32_t key_off, const int32_t *other,
             int32_t other_off, const double *val, std::vector<int> &ptr, std::vector<int> &idx,
@@ -161,12 +153,12 @@ int build_on_device(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swa
 	const int64_t nnz = s->nnz;
 	const size_t nz = (size_t) nnz;
 	hipStream_t st = p->stream;
-	MF_HIP(p->csr_ptr.alloc((size_t) p->uc + 1) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
-	MF_HIP(p->csc_ptr.alloc((size_t) p->items + 1) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
-	MF_HIP(p->csr_idx.alloc(nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
-	MF_HIP(p->csr_val.alloc(nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
-	MF_HIP(p->csc_idx.alloc(nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
-	MF_HIP(p->csc_val.alloc(nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
+	MF_TRY(p->csr_ptr.alloc((size_t) p->uc + 1));
+	MF_TRY(p->csc_ptr.alloc((size_t) p->items + 1));
+	MF_TRY(p->csr_idx.alloc(nz + 64));
+	MF_TRY(p->csr_val.alloc(nz + 64));
+	MF_TRY(p->csc_idx.alloc(nz + 64));
+	MF_TRY(p->csc_val.alloc(nz + 64));
 	csr_ptr_host.assign((size_t) p->uc + 1, 0);
 	csc_ptr_host.assign((size_t) p->items + 1, 0);
 	if (nnz == 0) {
@@ -262,7 +254,7 @@ int build_on_device(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swa
 		unsigned *mk_in = nullptr, *mk_out = nullptr, *mv_out = nullptr;
 		if ((rc = tmp.get(&mk_in, nz)) != MF_OK || (rc = tmp.get(&mk_out, nz)) != MF_OK || (rc = tmp.get(&mv_out, nz)) != MF_OK)
 			return rc;
-		MF_HIP(p->mask_idx.alloc(nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
+		MF_TRY(p->mask_idx.alloc(nz + 64));
 		hipLaunchKernelGGL(copy_keys_kernel, dim3(grid), dim3(256), 0, st, p->csc_idx, nnz, mk_in, perm_in);
 		size_t need2 = 0;
 		MF_HIP(rocprim::radix_sort_pairs(nullptr, need2, mk_in, mk_out, key_out, mv_out, nz, 0, bits_for(p->uc), st));
@@ -272,7 +264,7 @@ int build_on_device(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swa
 		MF_HIP(hipMemcpyAsync(p->mask_idx, mv_out, nz * sizeof(int), hipMemcpyDeviceToDevice, st));
 	}
 	if (p->want_map) {
-		MF_HIP(p->csr2csc.alloc(nz + 64) == MF_OK ? hipSuccess : hipErrorOutOfMemory);
+		MF_TRY(p->csr2csc.alloc(nz + 64));
 		hipLaunchKernelGGL(csr2csc_kernel, dim3(grid), dim3(256), 0, st, perm_out, nnz, file2csr, p->csr2csc);
 	}
 	MF_HIP(hipGetLastError());
@@ -326,7 +318,7 @@ int build_sparse(mf_plan *p, const mf_shard *s_in, const mf_entry *aos, bool swa
 		MF_TRY(p->csr_ptr.alloc((size_t) p->uc + 1));
 		MF_TRY(p->csr_idx.alloc(nz + 64));
 		MF_TRY(p->csr_val.alloc(nz + 64));
-		MF_TRY_HIP(h2d(p, p->csr_ptr, rptr.data(), ((size_t) p->uc + 1) * sizeof(int)));
+		MF_HIP(h2d(p, p->csr_ptr, rptr.data(), ((size_t) p->uc + 1) * sizeof(int)));
 		{
 			// mask ids ascending inside every row (see build_on_device) when the file order is not
 			bool ascending = true;
@@ -336,12 +328,12 @@ int build_sparse(mf_plan *p, const mf_shard *s_in, const mf_entry *aos, bool swa
 				std::vector<int> mk(idx);
 				for (int u = 0; u < p->uc; ++u) std::sort(mk.begin() + rptr[(size_t) u], mk.begin() + rptr[(size_t) u + 1]);
 				MF_TRY(p->mask_idx.alloc(nz + 64));
-				MF_TRY_HIP(h2d(p, p->mask_idx, mk.data(), nz * sizeof(int)));
+				MF_HIP(h2d(p, p->mask_idx, mk.data(), nz * sizeof(int)));
 			}
 		}
 		if (nz) {
-			MF_TRY_HIP(h2d(p, p->csr_idx, idx.data(), nz * sizeof(int)));
-			MF_TRY_HIP(h2d(p, p->csr_val, val.data(), nz * sizeof(double)));
+			MF_HIP(h2d(p, p->csr_idx, idx.data(), nz * sizeof(int)));
+			MF_HIP(h2d(p, p->csr_val, val.data(), nz * sizeof(double)));
 		}
 		try {
 			bucket(s->nnz, p->items, s->col, 0, s->row, p->u0, s->val, cptr, idx, val, p->want_map ? &pos_c : nullptr);
@@ -351,16 +343,16 @@ int build_sparse(mf_plan *p, const mf_shard *s_in, const mf_entry *aos, bool swa
 		MF_TRY(p->csc_ptr.alloc((size_t) p->items + 1));
 		MF_TRY(p->csc_idx.alloc(nz + 64));
 		MF_TRY(p->csc_val.alloc(nz + 64));
-		MF_TRY_HIP(h2d(p, p->csc_ptr, cptr.data(), ((size_t) p->items + 1) * sizeof(int)));
+		MF_HIP(h2d(p, p->csc_ptr, cptr.data(), ((size_t) p->items + 1) * sizeof(int)));
 		if (nz) {
-			MF_TRY_HIP(h2d(p, p->csc_idx, idx.data(), nz * sizeof(int)));
-			MF_TRY_HIP(h2d(p, p->csc_val, val.data(), nz * sizeof(double)));
+			MF_HIP(h2d(p, p->csc_idx, idx.data(), nz * sizeof(int)));
+			MF_HIP(h2d(p, p->csc_val, val.data(), nz * sizeof(double)));
 		}
 		if (p->want_map) {
 			std::vector<int> map(nz + 1);
 			for (size_t n = 0; n < nz; ++n) map[(size_t) pos_r[n]] = pos_c[n];
 			MF_TRY(p->csr2csc.alloc(nz + 64));
-			if (nz) MF_TRY_HIP(h2d(p, p->csr2csc, map.data(), nz * sizeof(int)));
+			if (nz) MF_HIP(h2d(p, p->csr2csc, map.data(), nz * sizeof(int)));
 		}
 	} else {
 		MF_TRY(build_on_device(p, s_in, aos, swap, rptr, cptr));
@@ -368,353 +360,138 @@ int build_sparse(mf_plan *p, const mf_shard *s_in, const mf_entry *aos, bool swa
 	return MF_OK;
 }
 
-// Does the single-wave launch of this sweep take the wave-pair form (mf_sweep.hip.h: loader + compute wave per row)?  Where
-// the kernel exists (64 <= K <= 128, compile-time K) and the side is
-//   made of long rows: 512 entries per row or more on average, skewed or not -- a wave spends its life inside rows, where
-//          the pair overlaps the gather of chunk c+1 with the arithmetic of chunk c (cfg4's 1e5 items of 1000 entries:
-//          11.77 vs 12.19 ms, three alternating runs on one box).  On a skewed side of that kind (the Netflix shape's 17770
-//          items of 3770 entries, cfg4-Zipf's) the extreme-row threshold moves up 2.7x with the pairs (plan_row_schedule),
-//          the scratch round trip shrinks and the side stream no longer eats into the other sweep: Netflix shape 19.7 ->
-//          17.1 ms, cfg4-Zipf 35.5 -> 31.2 (profiles/r03/pair_long_rows_ab.txt; at the single-wave threshold the pairs LOSE
-//          there, 20.0 vs 19.7); or
-//   small and skewed: at most 65536 rows and ~2 ms of bytes, the longest row at least four times the mean -- such a launch
-//          ENDS on its long rows, which a pair walks 2.4x faster than one wave (cfg3 power-law).
-// Short equally long rows stay on the single-wave form (cfg3 uniform, 253 / 166 entries per row: 0.207 vs 0.222 ms), and so
-// does a large side of short rows (users of the Netflix shape 8.2 vs 6.8 ms, of cfg4 12.9 vs 11.4).  MF_SWEEP_PAIR=0|1 overrides.
-static bool pair_long_rows(const mf_plan *p, int kind)
+// The inputs of the schedule rules (mf_schedule.h): what the chosen variant can do, the kernel constants, the switches.
+mf_sched::Caps schedule_caps(const mf_plan *p)
 {
-	const int nrows = kind == 0 ? p->items : p->uc;
-	return nrows >= 512 && p->nnz / nrows >= 512;
+	mf_sched::Caps c;
+	c.prod = p->sweep.prod, c.pf = p->sweep.pf, c.pair = p->sweep.pair, c.coop = p->sweep.coop, c.db = p->sweep.db;
+	c.row_bytes = p->sweep.row_bytes, c.xs_bytes = p->sweep.xs_bytes, c.single_nch = p->single.nch;
+	c.coop_producers = mf::kCoopProducers, c.coop_waves = mf::kCoopWaves, c.slice_cols = mf::kSliceCols;
+	c.block_entries = mf::kBlockEntries, c.wave = mf::kWave, c.lds_per_cu = kLdsPerCu;
+	return c;
 }
-bool pair_wanted(const mf_plan *p, int kind)
+mf_sched::Switches schedule_switches(const mf_config &cfg)
 {
-	if (!p->sweep.pair || p->cfg.sweep_pair == 0) return false;
-	if (p->cfg.sweep_pair == 1) return true;
-	const int nrows = kind == 0 ? p->items : p->uc;
-	if (nrows < 512 || p->nnz <= 0) return false;
-	if (pair_long_rows(p, kind)) return true;
-	if ((long long) p->max_row_len[kind] < 4 * std::max<long long>(p->nnz / nrows, 1)) return false;
-	return nrows <= 65536 && (double) p->nnz * 8.0 * p->K / 6e12 * 1e6 <= 2000.0;
+	mf_sched::Switches w;
+	w.skew = cfg.skew, w.sweep_nch = cfg.sweep_nch, w.sweep_long_set = cfg.sweep_long_set, w.sweep_long = cfg.sweep_long;
+	w.sweep_pair = cfg.sweep_pair, w.sweep_db = cfg.sweep_db;
+	return w;
 }
 
-// Schedule of the two sweeps from the row lengths: which rows count as long, whether a tiny sweep runs as ONE
-// cooperative launch, and the segment tables + scratch buffer of the extreme-row path.
+// device copy of a host table (h2d: on the plan's stream, complete on return)
+template <class T>
+int upload(mf_plan *p, dev_buf<T> &dst, const std::vector<T> &src)
+{
+	MF_TRY(dst.alloc(src.size()));
+	MF_HIP(h2d(p, dst, src.data(), src.size() * sizeof(T)));
+	return MF_OK;
+}
+
+// Schedule of the two sweeps from the row lengths, by the rules of mf_schedule.h: which rows
+// count as long, whether a tiny sweep runs as ONE cooperative launch, the segment tables + scratch buffer of the
+// extreme-row path, the wave priority, the form of the main launch and the dispatch order.
 int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vector<int> &cptr)
 {
-	for (int u = 0; u < p->uc; ++u) p->max_row_len[1] = std::max(p->max_row_len[1], rptr[(size_t) u + 1] - rptr[u]);
-	for (int j = 0; j < p->items; ++j) p->max_row_len[0] = std::max(p->max_row_len[0], cptr[(size_t) j + 1] - cptr[j]);
-	// ---- long / short row lists.  A row is "long" when its serial walk would exceed a good part of the bandwidth time
-	// of the whole sweep (nnz * 8K bytes at ~7 TB/s): len > 4e-6 (6e-6) * nnz * K, and never below 128 entries.  cfg4
-	// has none; a power-law instance a few.
-	const mf_config &cfg = p->cfg;
-	if (p->sweep.prod && cfg.skew) {   // MF_SWEEP_SKEW=0 disables the split
-		const size_t per_entry = 2 * (size_t) mf::kCoopProducers * (size_t) p->sweep.row_bytes;
-		const size_t head = (size_t) p->sweep.xs_bytes;
-		int nl = (int) std::min<size_t>(32, (kLdsPerCu - 4096 - head) / per_entry);
-		if (const int v = cfg.sweep_nch; v >= 1 && head + (size_t) v * per_entry <= kLdsPerCu) nl = v;
-		// (6e-6 where the accumulate form with the pipelined phases exists: its lone wave walks 0.13 us per entry at K=100
-		// instead of 0.17, so fewer rows need the scratch round trip -- Netflix shape 21.05 -> 19.68 ms at 40000 instead of
-		// 26800 entries, cfg4-Zipf 34.5 -> 33.9; round 2's 4e-6 otherwise)
-		double thr = (p->sweep.pf ? 6e-6 : 4e-6) * (double) p->nnz * (double) p->K;
-		if (cfg.sweep_long_set) thr = cfg.sweep_long;
-		const int t_long = std::max(128, (int) std::min(thr, 2e9));
-		// estimated bandwidth time of one sweep; below ~50 us the two-stream fork/join (tens of us on the 6000
-		// launches of ML100k) costs more than the split saves: use one cooperative launch for all rows there
-		const double est_us = (double) p->nnz * 8.0 * p->K / 6e12 * 1e6;
-		const int nc = (int) std::min<size_t>(32, (48 * 1024) / per_entry);
-		long long scratch_entries = 0;
-		for (int kind = 0; kind < 2; ++kind) {
-			const std::vector<int> &pt = kind == 0 ? cptr : rptr;
-			const int nrows = kind == 0 ? p->items : p->uc;
-			// ... and only rows well above the average count as long: when every row is equally long (the cfg4
-			// twin: 1000 items x 1000 entries) there is no skew to fix and the single-wave kernel is the faster one
-			// (a side of long rows walked by wave pairs -- 0.055 us per entry instead of 0.13 --: 16e-6 nnz K.  Netflix shape,
-			// pairs on the item side: 18.5 / 17.9 / 17.1 / 18.6 ms at 60 / 80 / 100 / 160 thousand entries, the rule gives 107 000;
-			// cfg4-Zipf 32.6 / 31.2 / 31.2 / 39.9 at 120 / 160 / 220 / 400 thousand, the rule gives 160 000)
-			const bool pairs_long = pair_wanted(p, kind) && pair_long_rows(p, kind) && p->cfg.sweep_pair != 1;
-			const int t_side = pairs_long ? std::max(128, (int) std::min(16e-6 * (double) p->nnz * (double) p->K, 2e9)) : t_long;
-			const long long mean4 = std::min<long long>(4 * (long long) (p->nnz / std::max(nrows, 1)), 2000000000ll);
-			const int t_kind = cfg.sweep_long_set ? t_long : std::max(t_side, (int) mean4);
-			if (p->max_row_len[kind] < t_kind) continue;
-			// With the wave-pair form a long row is walked at ~0.055 us per entry at K=100 (a lone single wave: 0.13): when
-			// even the longest row's walk fits the sweep's bandwidth time the split buys nothing and costs the scratch
-			// round trip and a fork/join (cfg3 power-law users, longest row 2324: 0.160 -> 0.139 ms without the split).
-			if (pair_wanted(p, kind) && !cfg.sweep_long_set && est_us >= 50.0 &&
-			    (double) p->max_row_len[kind] * 0.055 * p->K / 100.0 <= 1.3 * est_us)
-				continue;
-			if (est_us < 50.0 && nrows < 4096 && !cfg.sweep_long_set) {
-				if (p->sweep.coop && (nc >= 8 || cfg.sweep_nch)) {
-					p->coop_all[kind] = true;
-					const int n = cfg.sweep_nch ? nl : nc;
-					p->coop = SweepForm{p->sweep.coop, n, head + (size_t) n * per_entry, mf::kCoopWaves * mf::kWave};
-				}
-				continue;
-			}
-			// the scratch buffer holds K doubles per entry of every extreme row: keep it under a quarter of the free
-			// memory by raising the threshold (on Netflix-like data most entries sit in long columns)
-			size_t free_b = 0, total_b = 0;
-			(void) hipMemGetInfo(&free_b, &total_b);
-			const size_t nsl = (size_t) ((p->K + mf::kSliceCols - 1) / mf::kSliceCols);
-			const size_t cap_entries = std::max<size_t>(free_b / 4 / (nsl * mf::kSliceCols * 8), 1);
-			int t_eff = t_kind;
-			for (;;) {
-				size_t ent = 0;
-				for (int r = 0; r < nrows; ++r) {
-					const int len = pt[(size_t) r + 1] - pt[r];
-					if (len >= t_eff) ent += (size_t) len;
-				}
-				if (ent <= cap_entries || t_eff > (1 << 29)) break;
-				t_eff *= 2;
-			}
-			if (p->max_row_len[kind] < t_eff) continue;
-			std::vector<int> lg, sh;
-			for (int r = 0; r < nrows; ++r) {
-				const int len = pt[(size_t) r + 1] - pt[r];
-				(len >= t_eff ? lg : sh).push_back(r);
-			}
-			// longest first: workgroups are dispatched in list order as slots free up, so the long walks start
-			// at once and the short rows fill in behind them (longest-processing-time-first scheduling)
-			auto by_len = [&](int x, int y) { return pt[(size_t) x + 1] - pt[x] > pt[(size_t) y + 1] - pt[y]; };
-			std::stable_sort(sh.begin(), sh.end(), by_len);
-			std::stable_sort(lg.begin(), lg.end(), by_len);
-			MF_TRY(p->long_rows[kind].alloc(lg.size()));
-			MF_TRY(p->short_rows[kind].alloc(sh.size()));
-			MF_TRY_HIP(h2d(p, p->long_rows[kind], lg.data(), lg.size() * sizeof(int)));
-			if (!sh.empty())
-				MF_TRY_HIP(h2d(p, p->short_rows[kind], sh.data(), sh.size() * sizeof(int)));
-			p->n_long[kind] = (int) lg.size();
-			p->long_len[kind] = t_eff;
-			p->n_short[kind] = (int) sh.size();
-			// segments of kSeg entries; scratch offsets in entry units, rows back to back
-			// entries per segment of the products launch: one wave walks a segment chunk by chunk (~2.5 us per 16 entries
-			// of exposed latency), so short segments finish sooner and there are more of them to overlap
-			// (cfg3 power-law: 256 -> 64 entries 0.452 -> 0.421 ms per iteration; Netflix-shaped 21.6 -> 21.4 ms)
-			constexpr int kSeg = 64;
-			std::vector<int> srow, sbeg, send, lcnt;
-			std::vector<long long> sout, lbeg;
-			long long off = 0;
-			for (int r : lg) {
-				const int b = pt[r], e = pt[(size_t) r + 1];
-				lbeg.push_back(off);
-				lcnt.push_back(e - b);
-				for (int c = b; c < e; c += kSeg) {
-					srow.push_back(r);
-					sbeg.push_back(c);
-					send.push_back(std::min(e, c + kSeg));
-					sout.push_back(off + (c - b));
-				}
-				off += e - b;
-			}
-			scratch_entries = std::max(scratch_entries, off);
-			p->n_seg[kind] = (int) srow.size();
-			MF_TRY(p->seg_row[kind].alloc(srow.size()));
-			MF_TRY(p->seg_beg[kind].alloc(srow.size()));
-			MF_TRY(p->seg_end[kind].alloc(srow.size()));
-			MF_TRY(p->seg_out[kind].alloc(srow.size()));
-			MF_TRY(p->lr_sbeg[kind].alloc(lg.size()));
-			MF_TRY(p->lr_cnt[kind].alloc(lg.size()));
-			MF_TRY_HIP(h2d(p, p->seg_row[kind], srow.data(), srow.size() * sizeof(int)));
-			MF_TRY_HIP(h2d(p, p->seg_beg[kind], sbeg.data(), srow.size() * sizeof(int)));
-			MF_TRY_HIP(h2d(p, p->seg_end[kind], send.data(), srow.size() * sizeof(int)));
-			MF_TRY_HIP(h2d(p, p->seg_out[kind], sout.data(), srow.size() * sizeof(long long)));
-			MF_TRY_HIP(h2d(p, p->lr_sbeg[kind], lbeg.data(), lg.size() * sizeof(long long)));
-			MF_TRY_HIP(h2d(p, p->lr_cnt[kind], lcnt.data(), lg.size() * sizeof(int)));
-		}
-		if (p->coop_all[0] || p->coop_all[1])
-			MF_TRY_HIP(raise_lds_limit((const void *) p->coop.fn, p->coop.lds));
-		if (p->n_long[0] || p->n_long[1]) {
-			const int npr = p->single.nch;
-			p->prod = SweepForm{p->sweep.prod, npr, head + (size_t) npr * p->sweep.row_bytes, mf::kWave};
-			p->lds_bytes_osum = mf::kOrderedSumLds;
-			MF_TRY_HIP(raise_lds_limit((const void *) p->prod.fn, p->prod.lds));
-			MF_TRY_HIP(raise_lds_limit(cfg.os_dpp ? (const void *) mf::ordered_sum_kernel<true> : (const void *) mf::ordered_sum_kernel<false>, p->lds_bytes_osum));
-			// [slice][entry][kSliceCols doubles]; one block of padding per slice: the last block of a row is read whole
-			p->scratch_entries = (size_t) scratch_entries + mf::kBlockEntries;
-			MF_TRY(p->scratch.alloc(p->scratch_entries * mf::kSliceCols *
-			                                  (size_t) ((p->K + mf::kSliceCols - 1) / mf::kSliceCols)));
-			int prio_lo = 0, prio_hi = 0;
-			MF_TRY_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-			// beside the single-wave form: high priority -- the ordered sums are few, latency-bound waves that must get their
-			// slots ahead of the thousands of workgroups of the sweep they run under.  Beside the wave-pair form: LOW
-			// priority -- there the launch ends on the pairs of the long rows, which must be dispatched at once, and the
-			// side path has the whole other sweep to hide under (cfg3 power-law 0.304 -> 0.268 ms).
-			const bool side_low = pair_wanted(p, 0) || pair_wanted(p, 1);
-			MF_TRY_HIP(hipStreamCreateWithPriority(&p->side_stream, hipStreamNonBlocking, side_low ? prio_lo : prio_hi));
-			MF_TRY_HIP(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
-			MF_TRY_HIP(hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming));
-		}
-	}
-	// ---- wave priority for the long rows of the single-wave launch (what the launch ends on): when the launch is skewed
-	// (its longest row at least four times its mean), rows of at least twice the mean run at raised priority
+	// ---- the inputs
+	const mf_sched::Caps caps = schedule_caps(p);
+	const mf_sched::Switches sw = schedule_switches(p->cfg);
+	const mf_sched::Rows rows[2] = {{cptr.data(), p->items}, {rptr.data(), p->uc}};
+	mf_sched::Problem pb;
+	pb.K = p->K;
+	pb.nnz = p->nnz;
+	pb.free_bytes = [] {
+		size_t free_b = 0, total_b = 0;
+		(void) hipMemGetInfo(&free_b, &total_b);
+		return free_b;
+	};
+	// ---- the decision
+	const mf_sched::Sweeps s = mf_sched::sweep_schedule(pb, caps, sw, rows);
+	// ---- its tables on the device
 	for (int kind = 0; kind < 2; ++kind) {
-		const std::vector<int> &pt = kind == 0 ? cptr : rptr;
-		const int nrows = kind == 0 ? p->items : p->uc;
-		long long ent = 0, rows = 0;
-		int longest = 0;
-		for (int r = 0; r < nrows; ++r) {
-			const int len = pt[(size_t) r + 1] - pt[r];
-			if (p->n_long[kind] > 0 && len >= p->long_len[kind]) continue;   // on the extreme-row path
-			ent += len;
-			++rows;
-			longest = std::max(longest, len);
-		}
-		const long long mean = rows ? ent / rows : 0;
-		p->prio_len[kind] = 0;
-		if (rows > 256 && longest >= 4 * std::max<long long>(mean, 1))
-			p->prio_len[kind] = (int) std::max<long long>(64, 2 * mean);
+		const mf_sched::Side &h = s.side[kind];
+		SweepSide &d = p->side[kind];
+		d.max_row_len = h.max_row_len, d.prio_len = h.prio_len, d.long_len = h.long_len;
+		d.coop_all = h.coop_all, d.lpt = h.lpt, d.use_db = h.use_db, d.use_pair = h.use_pair;
+		if (h.lpt) MF_TRY(upload(p, d.short_rows, h.short_rows));
+		if (h.long_rows.empty()) continue;
+		d.n_long = (int) h.long_rows.size(), d.n_short = (int) h.short_rows.size(), d.n_seg = (int) h.seg_row.size();
+		MF_TRY(upload(p, d.long_rows, h.long_rows));
+		MF_TRY(upload(p, d.short_rows, h.short_rows));
+		MF_TRY(upload(p, d.seg_row, h.seg_row));
+		MF_TRY(upload(p, d.seg_beg, h.seg_beg));
+		MF_TRY(upload(p, d.seg_end, h.seg_end));
+		MF_TRY(upload(p, d.seg_out, h.seg_out));
+		MF_TRY(upload(p, d.lr_sbeg, h.lr_sbeg));
+		MF_TRY(upload(p, d.lr_cnt, h.lr_cnt));
 	}
-	// ---- double-buffered single-wave form for the WHOLE single-wave launch: measured slower than the single-buffered form
-	// whenever the launch has more rows than double-tile workgroups fit the chip (cfg3 uniform 0.222 -> 0.429 ms: the
-	// second tile halves the resident workgroups and the CU's gather rate is shared by fewer requests in flight), so it
-	// is off unless forced (MF_SWEEP_DB=1).
-	for (int kind = 0; kind < 2; ++kind) {
-		const int nrows = kind == 0 ? p->items : p->uc;
-		const int launch_rows = p->n_long[kind] > 0 ? p->n_short[kind] : nrows;
-		p->use_db[kind] = p->sweep.db && !p->coop_all[kind] && launch_rows > 0 && p->cfg.sweep_db == 1;
-		p->use_pair[kind] = !p->coop_all[kind] && !p->use_db[kind] && launch_rows > 0 && pair_wanted(p, kind);
+	// ---- LDS limits, the scratch, the side stream and its events
+	if (s.coop.nch) {
+		p->coop = SweepForm{p->sweep.coop, s.coop.nch, s.coop.lds, mf::kCoopWaves * mf::kWave};
+		MF_HIP(raise_lds_limit((const void *) p->coop.fn, p->coop.lds));
 	}
-	// ---- a sweep of a few thousand rows is a handful of rounds of workgroups: in index order its tail is whatever
-	// long rows happen to start last.  Longest first (workgroups are dispatched in list order) the tail is made of the
-	// shortest rows.  cfg3 uniform (3952 / 6040 rows of 50..311 entries): see DESIGN 5.1.  Large sweeps keep the index
-	// order (the tail is a negligible part of them and neighbouring rows share lines of the entry arrays) except for rows
-	// several times longer than the average, which lead the list.
-	for (int kind = 0; kind < 2; ++kind) {
-		const std::vector<int> &pt = kind == 0 ? cptr : rptr;
-		const int nrows = kind == 0 ? p->items : p->uc;
-		if (p->n_long[kind] > 0 || p->coop_all[kind] || nrows < 512) continue;
-		auto len = [&](int r) { return pt[(size_t) r + 1] - pt[r]; };
-		auto longer = [&](int x, int y) { return len(x) > len(y); };
-		std::vector<int> order;
-		order.reserve((size_t) nrows);
-		if (nrows <= (1 << 15)) {   // a dozen rounds of workgroups at most: the tail matters, the order of the row reads does not
-			for (int r = 0; r < nrows; ++r) order.push_back(r);
-			std::stable_sort(order.begin(), order.end(), longer);
-		} else {
-			// a large sweep with a few very long rows (power-law users): only those move to the front
-			const long long mean = p->nnz / nrows;
-			if ((long long) p->max_row_len[kind] < 8 * std::max<long long>(mean, 1)) continue;
-			std::vector<int> head;
-			for (int r = 0; r < nrows; ++r) (len(r) >= 4 * mean ? head : order).push_back(r);
-			std::stable_sort(head.begin(), head.end(), longer);
-			order.insert(order.begin(), head.begin(), head.end());
-		}
-		MF_TRY(p->short_rows[kind].alloc(order.size()));
-		MF_TRY_HIP(h2d(p, p->short_rows[kind], order.data(), order.size() * sizeof(int)));
-		p->lpt[kind] = true;
+	if (s.extreme) {
+		p->prod = SweepForm{p->sweep.prod, s.prod_nch, s.prod_lds, mf::kWave};
+		p->lds_bytes_osum = mf::kOrderedSumLds;
+		MF_HIP(raise_lds_limit((const void *) p->prod.fn, p->prod.lds));
+		MF_HIP(raise_lds_limit(ordered_sum_fn(p->cfg), p->lds_bytes_osum));
+		p->scratch_entries = s.scratch_entries;
+		MF_TRY(p->scratch.alloc(p->scratch_entries * mf::kSliceCols * mf_sched::slice_count(p->K, mf::kSliceCols)));
+		int prio_lo = 0, prio_hi = 0;
+		MF_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+		MF_HIP(hipStreamCreateWithPriority(&p->side_stream, hipStreamNonBlocking, s.side_low ? prio_lo : prio_hi));
+		MF_HIP(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
+		MF_HIP(hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming));
 	}
 	return MF_OK;
 }
 
-// Tables of the errors + streams iteration (mf_stream.hip.h): the CSR rows cut into segments of at most es_nch
-// entries (one wave each in the errors launch) and the workgroup table of the streams launch (mf_resident.hip.h).
+// Tables of the errors + streams iteration (mf_stream.hip.h), cut by mf_schedule.h: the CSR rows in segments of at most
+// es_nch entries (one wave each in the errors launch) and the workgroup table of the streams launch (mf_resident.hip.h).
 int plan_es_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vector<int> &cptr)
 {
 	p->es_mode = false;
 	if (!p->want_map || !p->csr2csc) return MF_OK;
-	const size_t row_bytes = (size_t) p->sweep.row_bytes, head = (size_t) p->sweep.xs_bytes;
-	const int nch = (int) std::min<size_t>(64, (kLdsPerCu / 3 - head) / row_bytes);
-	if (nch < 1) return MF_OK;
-	p->es_nch = nch;
-	p->es_lds_errors = head + (size_t) nch * row_bytes;
-	std::vector<int> srow, sbeg, send;
-	for (int u = 0; u < p->uc; ++u)
-		for (int c = rptr[(size_t) u]; c < rptr[(size_t) u + 1]; c += nch) {
-			srow.push_back(u);
-			sbeg.push_back(c);
-			send.push_back(std::min(rptr[(size_t) u + 1], c + nch));
-		}
+	const mf_sched::Rows rows[2] = {{cptr.data(), p->items}, {rptr.data(), p->uc}};
+	const mf_sched::EsErrors e = mf_sched::es_errors(schedule_caps(p), rows[1]);
+	if (e.nch < 1) return MF_OK;
+	p->es_nch = e.nch;
+	p->es_lds_errors = e.lds;
+	p->es_nseg = (int) e.seg_row.size();
+	if (p->es_nseg == 0 || p->res_sw <= 0) return MF_OK;
+	MF_TRY(upload(p, p->es_seg_row, e.seg_row));
+	MF_TRY(upload(p, p->es_seg_beg, e.seg_beg));
+	MF_TRY(upload(p, p->es_seg_end, e.seg_end));
+	MF_TRY(p->rec_csr.alloc((size_t) p->nnz + 64));
+	MF_TRY(p->rec_csc.alloc((size_t) p->nnz + 64));
+	// records = {idx (fixed), pad, err (rewritten every iteration)}; the 64 entries of slack behind the last one are
+	// read (never used) by the streams launch's 64-wide chunk loads
+	// on the plan's own stream: it is a non-blocking stream, NOT ordered with the null stream a plain hipMemset runs on
+	MF_HIP(hipMemsetAsync(p->rec_csr, 0, ((size_t) p->nnz + 64) * sizeof(mf::StreamRec), p->stream));
+	MF_HIP(hipMemsetAsync(p->rec_csc, 0, ((size_t) p->nnz + 64) * sizeof(mf::StreamRec), p->stream));
+	{
+		const unsigned grid = (unsigned) ((p->nnz + 255) / 256);
+		hipLaunchKernelGGL(fill_records_kernel, dim3(grid), dim3(256), 0, p->stream, p->csr_idx, p->nnz, p->rec_csr);
+		hipLaunchKernelGGL(fill_records_kernel, dim3(grid), dim3(256), 0, p->stream, p->csc_idx, p->nnz, p->rec_csc);
+		MF_HIP(hipGetLastError());
+		MF_HIP(hipStreamSynchronize(p->stream));
+	}
+	MF_HIP(raise_lds_limit((const void *) p->sweep.errs, p->es_lds_errors));
+	// ---- LDS-resident streams (mf_resident.hip.h): ~one workgroup per CU
 	int ncu = 256;
 	{
 		hipDeviceProp_t prop;
 		if (hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
 	}
-	p->es_nseg = (int) srow.size();
-	if (p->es_nseg == 0 || p->res_sw <= 0) return MF_OK;
-	MF_TRY(p->es_seg_row.alloc(srow.size()));
-	MF_TRY(p->es_seg_beg.alloc(srow.size()));
-	MF_TRY(p->es_seg_end.alloc(srow.size()));
-	MF_TRY(p->rec_csr.alloc((size_t) p->nnz + 64));
-	MF_TRY(p->rec_csc.alloc((size_t) p->nnz + 64));
-	MF_TRY_HIP(h2d(p, p->es_seg_row, srow.data(), srow.size() * sizeof(int)));
-	MF_TRY_HIP(h2d(p, p->es_seg_beg, sbeg.data(), srow.size() * sizeof(int)));
-	MF_TRY_HIP(h2d(p, p->es_seg_end, send.data(), srow.size() * sizeof(int)));
-	// records = {idx (fixed), pad, err (rewritten every iteration)}; the 64 entries of slack behind the last one are
-	// read (never used) by the streams launch's 64-wide chunk loads
-	// on the plan's own stream: it is a non-blocking stream, NOT ordered with the null stream a plain hipMemset runs on
-	MF_TRY_HIP(hipMemsetAsync(p->rec_csr, 0, ((size_t) p->nnz + 64) * sizeof(mf::StreamRec), p->stream));
-	MF_TRY_HIP(hipMemsetAsync(p->rec_csc, 0, ((size_t) p->nnz + 64) * sizeof(mf::StreamRec), p->stream));
-	{
-		const unsigned grid = (unsigned) ((p->nnz + 255) / 256);
-		hipLaunchKernelGGL(fill_records_kernel, dim3(grid), dim3(256), 0, p->stream, p->csr_idx, p->nnz, p->rec_csr);
-		hipLaunchKernelGGL(fill_records_kernel, dim3(grid), dim3(256), 0, p->stream, p->csc_idx, p->nnz, p->rec_csc);
-		MF_TRY_HIP(hipGetLastError());
-		MF_TRY_HIP(hipStreamSynchronize(p->stream));
-	}
-	MF_TRY_HIP(raise_lds_limit((const void *) p->sweep.errs, p->es_lds_errors));
-	// ---- LDS-resident streams (mf_resident.hip.h): ~one workgroup per CU; every (side, slice) gets `per` workgroups
-	// of eight waves, and the side's rows are cut into per * 8 runs of consecutive rows balanced by cost
-	{
-		const int sw = p->res_sw, nsl = (p->K + sw - 1) / sw;
-		const int per = std::max(1, ncu / (2 * nsl));
-		constexpr int aw = mf::kResidentWaves;   // every wave of a workgroup owns rows
-		std::vector<mf::SliceWg> wgs;
-		for (int side = 0; side < 2; ++side) {
-			const std::vector<int> &pt = side == 0 ? cptr : rptr;
-			const int nrows = side == 0 ? p->items : p->uc;
-			// run boundaries: greedy on cost = entries + 16 per row; a run never splits a row and never holds more than
-			// kResidentRows rows (its row pointers live in one register), so a side of many short rows gets more
-			// workgroups than one per CU and slice
-			std::vector<int> cut(1, 0);
-			{
-				const int target_runs = per * aw;
-				constexpr double row_cost = 16.0;   // entries a row end is worth
-				const double total_cost = (double) pt[(size_t) nrows] + row_cost * nrows;
-				double acc_cost = 0, done = 0;
-				int in_run = 0;
-				for (int r = 0; r < nrows; ++r) {
-					acc_cost += (pt[(size_t) r + 1] - pt[(size_t) r]) + row_cost;
-					++in_run;
-					const int left = target_runs - (int) cut.size();
-					const bool share = left > 0 && acc_cost >= (total_cost - done) / (left + 1);
-					if (r + 1 < nrows && (share || in_run == mf::kResidentRows)) {
-						cut.push_back(r + 1);
-						done += acc_cost;
-						acc_cost = 0;
-						in_run = 0;
-					}
-				}
-				cut.push_back(nrows);
-				while (((int) cut.size() - 1) % aw != 0) cut.push_back(nrows);
-			}
-			const int nwg_side = ((int) cut.size() - 1) / aw;
-			for (int sl = 0; sl < nsl; ++sl)
-				for (int w = 0; w < nwg_side; ++w) {
-					mf::SliceWg g;
-					g.side = side;
-					g.slice = sl;
-					for (int i = 0; i <= mf::kResidentWaves; ++i) {
-						g.row_beg[i] = cut[(size_t) (w * aw + i)];
-						g.ent_beg[i] = pt[(size_t) g.row_beg[i]];
-					}
-					if (g.row_beg[mf::kResidentWaves] > g.row_beg[0]) wgs.push_back(g);
-				}
-		}
-		p->res_nwg = (int) wgs.size();
-		p->res_lds = (size_t) std::max(p->uc, p->items) * sw * 8 + mf::kResidentWaves * mf::kResidentWaveLds;
-		if (p->res_nwg > 0) {
-			MF_TRY(p->res_wg.alloc(wgs.size()));
-			MF_TRY_HIP(h2d(p, p->res_wg, wgs.data(), wgs.size() * sizeof(mf::SliceWg)));
-			const void *fn = sw == 8   ? (const void *) mf::stream_resident_kernel<8>
-			                 : sw == 4 ? (const void *) mf::stream_resident_kernel<4>
-			                           : (const void *) mf::stream_resident_kernel<2>;
-			MF_TRY_HIP(raise_lds_limit(fn, p->res_lds));
-		}
+	const std::vector<mf::SliceWg> wgs =
+	    mf_sched::es_workgroups<mf::SliceWg, mf::kResidentWaves>(rows, p->K, p->res_sw, ncu, mf::kResidentRows);
+	p->res_nwg = (int) wgs.size();
+	p->res_lds = mf_sched::es_resident_lds(std::max(p->uc, p->items), p->res_sw, mf::kResidentWaves, mf::kResidentWaveLds);
+	if (p->res_nwg > 0) {
+		MF_TRY(upload(p, p->res_wg, wgs));
+		MF_HIP(raise_lds_limit(stream_resident_fn(p->res_sw), p->res_lds));
 	}
 	p->es_mode = true;
 	return MF_OK;
 }
-
-#undef MF_TRY
-#undef MF_TRY_HIP
 
 }  // namespace

@@ -15,6 +15,13 @@ thread_local std::string g_last_hip_error;
 		}                                                                                   \
 	} while (0)
 
+// inside functions that return a status: pass a failure on
+#define MF_TRY(x)                     \
+	do {                              \
+		int _rc = (x);                \
+		if (_rc != MF_OK) return _rc; \
+	} while (0)
+
 template <typename T>
 int dev_alloc(T **out, size_t count)
 {

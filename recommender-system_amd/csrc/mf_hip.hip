@@ -21,6 +21,7 @@
 #include "mf_config.hip.h"
 #include "mf_device.hip.h"
 #include "mf_plan.hip.h"
+#include "mf_schedule.h"
 #include "mf_launch.hip.h"
 #include "mf_build.hip.h"
 #include "mf_certified.hip.h"
@@ -59,6 +60,55 @@ int mf_backend_device_count(void)
 
 }   // extern "C"
 
+// One factor's two generations: the caller's buffers at the caller's pitch, or the plan's own at the padded pitch `own`.
+// Row pitch of the buffers the plan owns: rows of 8K bytes are gathered in whole 128-byte lines, so when 8K
+// is not a multiple of 128 a row costs a line more than its bytes wherever it happens to start (80-byte rows:
+// 1.5 lines on average instead of 1; 240-byte rows: 2.75 instead of 2).  The plan pads its own rows to whole
+// lines where that saves at least a tenth of the lines; caller-owned buffers keep the caller's pitch K.
+static int factor_buffers(mf_plan *p, void *const ext[2], int ext_pitch, int own, int rows, double *buf[2], dev_buf<double> mine[2],
+                          int *ld, bool *external)
+{
+	*external = ext[0] && ext[1];
+	*ld = *external ? (ext_pitch ? ext_pitch : p->K) : own;
+	for (int g = 0; g < 2; ++g) {
+		if (*external) {
+			buf[g] = (double *) ext[g];
+			continue;
+		}
+		const size_t n = (size_t) rows * *ld;
+		MF_TRY(mine[g].alloc(n));
+		buf[g] = mine[g];
+		if (*ld != p->K)   // the padding is never read by a kernel, but it is summed by the multi-GPU reducers
+			MF_HIP(hipMemsetAsync(buf[g], 0, std::max<size_t>(n, 1) * sizeof(double), p->stream));
+	}
+	return MF_OK;
+}
+
+// everything of a new plan that can fail: the caller destroys the plan when it does
+static int plan_fill(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swap)
+{
+	MF_TRY(choose_sweep(p));
+	MF_TRY(choose_loss(p));
+	if (hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking) != hipSuccess) return MF_ERR_HIP;
+	p->stream = p->own_stream;
+	{
+		std::vector<int> rptr, cptr;
+		MF_TRY(build_sparse(p, s, aos, swap, rptr, cptr));
+		MF_TRY(plan_row_schedule(p, rptr, cptr));
+		MF_TRY(plan_es_schedule(p, rptr, cptr));
+	}
+	const int own = row_pitch(p->cfg, p->K, p->sweep.dma != 0);
+	MF_TRY(factor_buffers(p, s->users_ext, s->users_pitch, own, p->uc, p->Lbuf, p->Lown, &p->ldl, &p->l_external));
+	MF_TRY(factor_buffers(p, s->items_ext, s->items_pitch, own, p->items, p->Rbuf, p->Rown, &p->ldr, &p->r_external));
+	MF_HIP(hipStreamSynchronize(p->stream));   // the plan is complete when the call returns
+	MF_TRY(p->best_dev.alloc((size_t) p->uc));
+	MF_TRY(p->lnorm.alloc((size_t) p->uc));
+	MF_TRY(p->rmax_bits.alloc(1));
+	MF_TRY(p->ulist.alloc((size_t) p->uc));
+	MF_TRY(p->ucount.alloc(1));
+	return MF_OK;
+}
+
 // `aos` (optional): the entries as the reference's array of (row, col, value) structs; they are then uploaded as they
 // are and split into the three arrays on the device (the level-1 entry points: no host-side copy of 1e8 entries).
 // `swap`: read the structs with row and col exchanged (the item-cut form of mf_backend_run_multi).
@@ -93,91 +143,33 @@ static int plan_create_impl(mf_plan **out, const mf_shard *s, const mf_entry *ao
 	p->K = s->features;
 	p->u0 = s->user_begin;
 	p->uc = s->user_count;
+	p->side[0].nrows = p->items;
+	p->side[1].nrows = p->uc;
 	p->nnz = s->nnz;
 	p->alpha = s->alpha;
 	p->flags = s->flags;
 	p->cfg = mf_config::from_env();
-
-	int rc = choose_sweep(p);
-	auto fail = [&](int code) {
+	const int rc = plan_fill(p, s, aos, swap);
+	if (rc != MF_OK) {
 		mf_plan_destroy(p);
-		return code;
-	};
-	if (rc == MF_OK) rc = choose_loss(p);
-	if (rc != MF_OK) return fail(rc);
-
-	if (hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking) != hipSuccess) return fail(MF_ERR_HIP);
-	p->stream = p->own_stream;
-
-#define MF_TRY(x)                       \
-	do {                                \
-		int _rc = (x);                  \
-		if (_rc != MF_OK) return fail(_rc); \
-	} while (0)
-#define MF_TRY_HIP(call)                                                              \
-	do {                                                                              \
-		hipError_t _e = (call);                                                       \
-		if (_e != hipSuccess) {                                                       \
-			g_last_hip_error = std::string(#call) + ": " + hipGetErrorString(_e);     \
-			return fail(_e == hipErrorOutOfMemory ? MF_ERR_NO_MEMORY : MF_ERR_HIP);   \
-		}                                                                             \
-	} while (0)
-	{
-		std::vector<int> rptr, cptr;
-		MF_TRY(build_sparse(p, s, aos, swap, rptr, cptr));
-		MF_TRY(plan_row_schedule(p, rptr, cptr));
-		MF_TRY(plan_es_schedule(p, rptr, cptr));
+		return rc;
 	}
-
-	// Row pitch of the factor buffers the plan owns: rows of 8K bytes are gathered in whole 128-byte lines, so when 8K
-	// is not a multiple of 128 a row costs a line more than its bytes wherever it happens to start (80-byte rows:
-	// 1.5 lines on average instead of 1; 240-byte rows: 2.75 instead of 2).  The plan pads its own rows to whole
-	// lines where that saves at least a tenth of the lines; caller-owned buffers keep the caller's pitch K.
-	p->ldl = p->ldr = p->K;
-	{
-		const int own = row_pitch(p->cfg, p->K, p->sweep.dma != 0);
-		p->ldl = s->users_ext[0] && s->users_ext[1] ? (s->users_pitch ? s->users_pitch : p->K) : own;
-		p->ldr = s->items_ext[0] && s->items_ext[1] ? (s->items_pitch ? s->items_pitch : p->K) : own;
-	}
-	const size_t nl = (size_t) p->uc * p->ldl, nr = (size_t) p->items * p->ldr;
-	if (s->users_ext[0] && s->users_ext[1]) {
-		p->l_external = true;
-		p->Lbuf[0] = (double *) s->users_ext[0];
-		p->Lbuf[1] = (double *) s->users_ext[1];
-	} else {
-		MF_TRY(p->Lown[0].alloc(nl));
-		MF_TRY(p->Lown[1].alloc(nl));
-		p->Lbuf[0] = p->Lown[0];
-		p->Lbuf[1] = p->Lown[1];
-		if (p->ldl != p->K) {   // the padding is never read by a kernel, but it is summed by the multi-GPU reducers
-			MF_TRY_HIP(hipMemsetAsync(p->Lbuf[0], 0, std::max<size_t>(nl, 1) * sizeof(double), p->stream));
-			MF_TRY_HIP(hipMemsetAsync(p->Lbuf[1], 0, std::max<size_t>(nl, 1) * sizeof(double), p->stream));
-		}
-	}
-	if (s->items_ext[0] && s->items_ext[1]) {
-		p->r_external = true;
-		p->Rbuf[0] = (double *) s->items_ext[0];
-		p->Rbuf[1] = (double *) s->items_ext[1];
-	} else {
-		MF_TRY(p->Rown[0].alloc(nr));
-		MF_TRY(p->Rown[1].alloc(nr));
-		p->Rbuf[0] = p->Rown[0];
-		p->Rbuf[1] = p->Rown[1];
-		if (p->ldr != p->K) {
-			MF_TRY_HIP(hipMemsetAsync(p->Rbuf[0], 0, std::max<size_t>(nr, 1) * sizeof(double), p->stream));
-			MF_TRY_HIP(hipMemsetAsync(p->Rbuf[1], 0, std::max<size_t>(nr, 1) * sizeof(double), p->stream));
-		}
-	}
-	MF_TRY_HIP(hipStreamSynchronize(p->stream));   // the plan is complete when the call returns
-	MF_TRY(p->best_dev.alloc((size_t) p->uc));
-	MF_TRY(p->lnorm.alloc((size_t) p->uc));
-	MF_TRY(p->rmax_bits.alloc(1));
-	MF_TRY(p->ulist.alloc((size_t) p->uc));
-	MF_TRY(p->ucount.alloc(1));
-#undef MF_TRY
-#undef MF_TRY_HIP
 	*out = p;
 	return MF_OK;
+}
+
+// a shard that is the whole problem: every user, no caller-owned buffers
+static mf_shard whole_shard(int32_t users, int32_t items, int32_t features, int64_t nnz, double alpha, int device)
+{
+	mf_shard s;
+	memset(&s, 0, sizeof s);
+	s.users_total = s.user_count = users;
+	s.items = items;
+	s.features = features;
+	s.nnz = nnz;
+	s.alpha = alpha;
+	s.device = device;
+	return s;
 }
 
 extern "C" {
@@ -301,7 +293,7 @@ static int iterate_eager(mf_plan *p, int iters)
 		// Both sweeps read only the frozen generation (matFact.c:38-39), so the ordered sums of the item sweep's
 		// extreme rows may run on the side stream UNDER the whole user sweep; they are joined before the flip.
 		// Not when the user sweep has extreme rows of its own: it would reuse the scratch buffer.
-		int rc = launch_sweep(p, 0, 1, /*defer_join=*/p->n_long[1] == 0);
+		int rc = launch_sweep(p, 0, 1, /*defer_join=*/p->side[1].n_long == 0);
 		if (rc != MF_OK) return rc;
 		rc = launch_sweep(p, 1, 1);
 		if (rc != MF_OK) return rc;
@@ -367,8 +359,8 @@ int mf_plan_iterate(mf_plan *p, int iters)
 			return MF_OK;
 		}
 	}
-	const bool small = (double) p->nnz * p->K < p->cfg.graph_max && !p->timing && p->n_long[0] == 0 &&
-	                   p->n_long[1] == 0;
+	const bool small = (double) p->nnz * p->K < p->cfg.graph_max && !p->timing && p->side[0].n_long == 0 &&
+	                   p->side[1].n_long == 0;
 	constexpr int kGraphIters = 32;
 	if (small && iters >= 4 * kGraphIters && p->cfg.graph) {
 		hipGraph_t graph = nullptr;
@@ -637,12 +629,13 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 {
 	if (!p || !buf || buflen <= 0) return MF_ERR_ARGUMENT;
 	int n;
+	const SweepSide &it = p->side[0], &us = p->side[1];
 	if (p->sweep.dma)
 		n = snprintf(buf, (size_t) buflen,
 		             "sweep_dma_kernel<KT=%d,NPASS=%d> K=%d pitch=%d/%d nch=%d row_bytes=%d lds=%zu long_rows=%d/%d coop_nch=%d double_buffered=%d/%d(nch=%d) wave_pair=%d/%d(nch=%d)",
 		             p->sweep.kt, p->sweep.kt ? mf::dma_passes(p->K) : p->sweep.kpmax, p->K, p->ldl, p->ldr, p->single.nch, p->sweep.row_bytes,
-		             p->single.lds, p->n_long[0] + (p->coop_all[0] ? p->items : 0), p->n_long[1] + (p->coop_all[1] ? p->uc : 0),
-		             p->coop_all[0] || p->coop_all[1] ? p->coop.nch : 0, (int) p->use_db[0], (int) p->use_db[1], p->db.nch, (int) p->use_pair[0], (int) p->use_pair[1], p->pair.nch);
+		             p->single.lds, it.n_long + (it.coop_all ? it.nrows : 0), us.n_long + (us.coop_all ? us.nrows : 0),
+		             it.coop_all || us.coop_all ? p->coop.nch : 0, (int) it.use_db, (int) us.use_db, p->db.nch, (int) it.use_pair, (int) us.use_pair, p->pair.nch);
 	else
 		n = snprintf(buf, (size_t) buflen, "sweep_kernel<KT=%d,KPMAX=%d> K=%d nch=%d stride=%d lds=%zu",
 		             p->sweep.kt, p->sweep.kpmax, p->K, p->single.nch, p->stride, p->single.lds);
@@ -682,16 +675,7 @@ static int make_single_plan(const mf_problem *pr, int device, mf_plan **out)
 	if (!pr || pr->users < 0 || pr->items < 0 || pr->features < 1 || pr->nnz < 0 || pr->iters < 0 ||
 	    (pr->nnz > 0 && !pr->entries))
 		return MF_ERR_ARGUMENT;
-	mf_shard s;
-	memset(&s, 0, sizeof s);
-	s.users_total = pr->users;
-	s.items = pr->items;
-	s.features = pr->features;
-	s.user_begin = 0;
-	s.user_count = pr->users;
-	s.nnz = pr->nnz;
-	s.alpha = pr->alpha;
-	s.device = device;
+	const mf_shard s = whole_shard(pr->users, pr->items, pr->features, pr->nnz, pr->alpha, device);
 	return plan_create_impl(out, &s, pr->entries);
 }
 
@@ -757,12 +741,7 @@ int mf_backend_similar_items(const double *R, int32_t items, int32_t features, i
 	const int chk = similar_check(items, metric, query, nq, n, out_items);
 	if (chk != MF_OK) return chk;
 	// a throw-away plan of one user without entries: the query reads nothing of it but R
-	mf_shard s;
-	memset(&s, 0, sizeof s);
-	s.users_total = s.user_count = 1;
-	s.items = items;
-	s.features = features;
-	s.device = device;
+	const mf_shard s = whole_shard(1, items, features, 0, 0.0, device);
 	mf_plan *p = nullptr;
 	int rc = mf_plan_create(&p, &s);
 	if (rc != MF_OK) return rc;

@@ -76,6 +76,35 @@ ChunkSizes chunk_rule(size_t head, size_t row_bytes, const mf_config &cfg)
 size_t tile_row_bytes(const mf_plan *p) { return p->sweep.dma ? (size_t) p->sweep.row_bytes : (size_t) p->stride * sizeof(double); }
 size_t tile_head_bytes(const mf_plan *p) { return p->sweep.dma ? (size_t) p->sweep.xs_bytes : 0; }
 
+// What a side's update reads and writes: side 0 (items) has X = R, Y = L and walks the CSC; side 1 (users) has X = L,
+// Y = R and walks the CSR.  X_new is the next generation of X.
+struct SideOperands {
+	const int *ptr, *idx;
+	const double *val;
+	const mf::StreamRec *rec;   // the side's {idx, e_n} records (errors + streams iteration)
+	const double *X_old, *Y_old;
+	double *X_new;
+	int ldx, ldy;   // row pitch of X and of Y in doubles
+	int yrows;      // rows of Y
+};
+SideOperands side_operands(const mf_plan *p, int kind)
+{
+	const int cur = p->cur, nxt = p->cur ^ 1;
+	if (kind == 0)
+		return {p->csc_ptr, p->csc_idx, p->csc_val, p->rec_csc, p->Rbuf[cur], p->Lbuf[cur], p->Rbuf[nxt], p->ldr, p->ldl, p->uc};
+	return {p->csr_ptr, p->csr_idx, p->csr_val, p->rec_csr, p->Lbuf[cur], p->Rbuf[cur], p->Lbuf[nxt], p->ldl, p->ldr, p->items};
+}
+
+// the ordered-sum kernel (MF_OS_DPP) and the resident streams kernel of a slice width
+const void *ordered_sum_fn(const mf_config &cfg)
+{
+	return cfg.os_dpp ? (const void *) mf::ordered_sum_kernel<true> : (const void *) mf::ordered_sum_kernel<false>;
+}
+const void *stream_resident_fn(int sw)
+{
+	return sw == 8 ? (const void *) mf::stream_resident_kernel<8> : sw == 4 ? (const void *) mf::stream_resident_kernel<4> : (const void *) mf::stream_resident_kernel<2>;
+}
+
 int choose_sweep(mf_plan *p)
 {
 	const int K = p->K;
@@ -170,9 +199,8 @@ int choose_loss(mf_plan *p)
 // 0.787).  launch_sweep chooses by it and mf_plan_describe prints it (accumulate=<items>/<users>).
 bool single_wave_pipelined(const mf_plan *p, int kind)
 {
-	const int nrows = kind == 0 ? p->items : p->uc;
 	const int kPfRows = p->K > 128 ? INT_MAX : 262144;
-	return p->sweep.pf && p->n_short[kind] <= kPfRows && nrows <= kPfRows;
+	return p->sweep.pf && p->side[kind].n_short <= kPfRows && p->side[kind].nrows <= kPfRows;
 }
 
 // The form of the main launch of one side (kind 0: items, 1: users): the cooperative launch of a tiny sweep, the
@@ -180,7 +208,8 @@ bool single_wave_pipelined(const mf_plan *p, int kind)
 // pipelined by single_wave_pipelined, at the large chunk when `few_rows`.
 SweepForm main_form(const mf_plan *p, int kind, bool few_rows)
 {
-	if (p->coop_all[kind]) {
+	const SweepSide &sd = p->side[kind];
+	if (sd.coop_all) {
 		// A cooperative launch of kSweepFewRows rows or more runs at the single-wave chunk size with the cooperative LDS request,
 		// as it always has.  Known and left for a change of its own, with a test: at K = 30 and K = 50 that request is sized
 		// for fewer rows (14 and 8) than the 16 of the single-wave chunk.
@@ -188,8 +217,8 @@ SweepForm main_form(const mf_plan *p, int kind, bool few_rows)
 		if (!few_rows) f.nch = p->single.nch;
 		return f;
 	}
-	if (p->use_db[kind]) return p->db;
-	if (p->use_pair[kind]) return p->pair;
+	if (sd.use_db) return p->db;
+	if (sd.use_pair) return p->pair;
 	SweepForm f = few_rows ? p->few : p->single;
 	f.fn = single_wave_pipelined(p, kind) ? p->sweep.pf : p->sweep.fn;
 	return f;
@@ -199,39 +228,30 @@ SweepForm main_form(const mf_plan *p, int kind, bool few_rows)
 // (p->join_pending); the caller joins before anything reads the new generation.
 int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 {
+	const SweepSide &sd = p->side[kind];
+	const SideOperands x = side_operands(p, kind);
 	mf::SweepArgs a;
 	a.K = p->K;
 	a.stride = p->stride;
 	a.seed = seed;
-	a.prio_len = p->prio_len[kind];
+	a.prio_len = sd.prio_len;
 	a.c2 = p->alpha * 2;
-	const int nxt = p->cur ^ 1;
-	a.ldx = kind == 0 ? p->ldr : p->ldl;
-	a.ldy = kind == 0 ? p->ldl : p->ldr;
-	if (kind == 0) {   // item sweep: X = R, Y = L, CSC
-		a.nrows = p->items;
-		a.ptr = p->csc_ptr;
-		a.idx = p->csc_idx;
-		a.val = p->csc_val;
-		a.X_old = p->Rbuf[p->cur];
-		a.Y_old = p->Lbuf[p->cur];
-		a.X_new = p->Rbuf[nxt];
-	} else {           // user sweep: X = L, Y = R, CSR
-		a.nrows = p->uc;
-		a.ptr = p->csr_ptr;
-		a.idx = p->csr_idx;
-		a.val = p->csr_val;
-		a.X_old = p->Lbuf[p->cur];
-		a.Y_old = p->Rbuf[p->cur];
-		a.X_new = p->Lbuf[nxt];
-	}
-	a.rowlist = p->lpt[kind] ? p->short_rows[kind] : nullptr;
+	a.ldx = x.ldx;
+	a.ldy = x.ldy;
+	a.nrows = sd.nrows;
+	a.ptr = x.ptr;
+	a.idx = x.idx;
+	a.val = x.val;
+	a.X_old = x.X_old;
+	a.Y_old = x.Y_old;
+	a.X_new = x.X_new;
+	a.rowlist = sd.lpt ? sd.short_rows.get() : nullptr;
 	a.seg_row = a.seg_beg = a.seg_end = nullptr;
 	a.seg_out = nullptr;
 	a.scratch = nullptr;
 	a.scratch_entries = 0;
 	if (a.nrows <= 0) return MF_OK;
-	const bool extreme = p->n_long[kind] > 0;
+	const bool extreme = sd.n_long > 0;
 	// the large chunk below kSweepFewRows rows.  Never beside the extreme-row path: with the extreme rows gone the
 	// occupancy-friendly chunk size is right again.
 	const SweepForm f = main_form(p, kind, !extreme && a.nrows < kSweepFewRows);
@@ -245,46 +265,44 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	}
 	void *args[] = {&a};
 	if (extreme) {
-		// extreme rows: products kernel over their 256-entry segments -> ordered sum per (row, column slice),
+		// extreme rows: products kernel over their 64-entry segments -> ordered sum per (row, column slice),
 		// beside the sweep of the other rows (schedule below)
 		mf::SweepArgs b = a;
-		b.nrows = p->n_seg[kind];
+		b.nrows = sd.n_seg;
 		b.prio_len = 0;
 		b.rowlist = nullptr;
 		b.nch = p->prod.nch;
-		b.seg_row = p->seg_row[kind];
-		b.seg_beg = p->seg_beg[kind];
-		b.seg_end = p->seg_end[kind];
-		b.seg_out = p->seg_out[kind];
+		b.seg_row = sd.seg_row;
+		b.seg_beg = sd.seg_beg;
+		b.seg_end = sd.seg_end;
+		b.seg_out = sd.seg_out;
 		b.scratch = p->scratch;
 		b.scratch_entries = p->scratch_entries;
 		void *bargs[] = {&b};
 		mf::OrderedSumArgs o;
-		o.nrows = p->n_long[kind];
+		o.nrows = sd.n_long;
 		o.K = p->K;
 		o.ldx = a.ldx;
 		o.seed = seed;
-		o.nslices = (p->K + mf::kSliceCols - 1) / mf::kSliceCols;
-		o.row = p->long_rows[kind];
-		o.sbeg = p->lr_sbeg[kind];
-		o.cnt = p->lr_cnt[kind];
+		o.nslices = (int) mf_sched::slice_count(p->K, mf::kSliceCols);
+		o.row = sd.long_rows;
+		o.sbeg = sd.lr_sbeg;
+		o.cnt = sd.lr_cnt;
 		o.scratch = p->scratch;
 		o.scratch_entries = p->scratch_entries;
 		o.X_old = a.X_old;
 		o.X_new = a.X_new;
 		o.stamps = nullptr;
-		o.max_cnt = p->max_row_len[kind];
+		o.max_cnt = sd.max_row_len;
 		void *oargs[] = {&o};
 		// Schedule: products kernel and ordered sums on the side stream while the remaining rows run on the main stream.
 		MF_HIP(hipEventRecord(p->ev_fork, p->stream));
 		MF_HIP(hipStreamWaitEvent(p->side_stream, p->ev_fork, 0));
 		MF_HIP(hipLaunchKernel((const void *) p->prod.fn, dim3(b.nrows), dim3(p->prod.block), bargs, p->prod.lds, p->side_stream));
-		MF_HIP(hipLaunchKernel(p->cfg.os_dpp ? (const void *) mf::ordered_sum_kernel<true> : (const void *) mf::ordered_sum_kernel<false>,
-		                       dim3(o.nrows * o.nslices), dim3(mf::kWave), oargs,
-		                       p->lds_bytes_osum, p->side_stream));
+		MF_HIP(hipLaunchKernel(ordered_sum_fn(p->cfg), dim3(o.nrows * o.nslices), dim3(mf::kWave), oargs, p->lds_bytes_osum, p->side_stream));
 		MF_HIP(hipEventRecord(p->ev_join, p->side_stream));
-		a.nrows = p->n_short[kind];
-		a.rowlist = p->short_rows[kind];
+		a.nrows = sd.n_short;
+		a.rowlist = sd.short_rows;
 	}
 	if (a.nrows > 0)
 		MF_HIP(hipLaunchKernel((const void *) f.fn, dim3(std::min(a.nrows, 1 << 20)), dim3(f.block), args, f.lds, p->stream));
@@ -305,22 +323,22 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 // ONE streams launch that adds up both factors' rows (timed as kind 0 / kind 1 like the two sweeps).
 int launch_es_iteration(mf_plan *p)
 {
-	const int nxt = p->cur ^ 1;
+	const SideOperands items = side_operands(p, 0), users = side_operands(p, 1);
 	mf::SweepArgs a;
 	memset(&a, 0, sizeof a);
 	a.nrows = p->es_nseg;
 	a.K = p->K;
 	a.nch = p->es_nch;
 	a.stride = p->stride;
-	a.ldx = p->ldl;
-	a.ldy = p->ldr;
+	a.ldx = users.ldx;   // the errors launch walks the CSR
+	a.ldy = users.ldy;
 	a.seed = 1;
 	a.c2 = p->alpha * 2;
-	a.ptr = p->csr_ptr;
-	a.idx = p->csr_idx;
-	a.val = p->csr_val;
-	a.X_old = p->Lbuf[p->cur];
-	a.Y_old = p->Rbuf[p->cur];
+	a.ptr = users.ptr;
+	a.idx = users.idx;
+	a.val = users.val;
+	a.X_old = users.X_old;
+	a.Y_old = users.Y_old;
 	a.X_new = nullptr;
 	a.seg_row = p->es_seg_row;
 	a.seg_beg = p->es_seg_beg;
@@ -331,16 +349,14 @@ int launch_es_iteration(mf_plan *p)
 	mf::SliceArgs ra;
 	ra.K = p->K;
 	ra.wg = p->res_wg;
-	ra.ptr[0] = p->csc_ptr;
-	ra.ptr[1] = p->csr_ptr;
-	ra.side[0] = mf::StreamSide{p->rec_csc, p->Rbuf[p->cur], p->Lbuf[p->cur], p->Rbuf[nxt]};
-	ra.side[1] = mf::StreamSide{p->rec_csr, p->Lbuf[p->cur], p->Rbuf[p->cur], p->Lbuf[nxt]};
-	ra.yrows[0] = p->uc;
-	ra.yrows[1] = p->items;
-	ra.ldx[0] = p->ldr;   // side 0: X = R, Y = L
-	ra.ldy[0] = p->ldl;
-	ra.ldx[1] = p->ldl;
-	ra.ldy[1] = p->ldr;
+	for (int side = 0; side < 2; ++side) {
+		const SideOperands &x = side == 0 ? items : users;
+		ra.ptr[side] = x.ptr;
+		ra.side[side] = mf::StreamSide{x.rec, x.X_old, x.Y_old, x.X_new};
+		ra.yrows[side] = x.yrows;
+		ra.ldx[side] = x.ldx;
+		ra.ldy[side] = x.ldy;
+	}
 	TimedLaunch t0{}, t1{};
 	if (p->timing) {
 		MF_HIP(hipEventCreate(&t0.t0));
@@ -356,10 +372,7 @@ int launch_es_iteration(mf_plan *p)
 	if (p->timing) MF_HIP(hipEventRecord(t0.t1, p->stream));
 	{
 		void *rargs[] = {&ra};
-		const void *fn = p->res_sw == 8   ? (const void *) mf::stream_resident_kernel<8>
-		                 : p->res_sw == 4 ? (const void *) mf::stream_resident_kernel<4>
-		                                  : (const void *) mf::stream_resident_kernel<2>;
-		MF_HIP(hipLaunchKernel(fn, dim3(p->res_nwg), dim3(mf::kResidentThreads), rargs, p->res_lds, p->stream));
+		MF_HIP(hipLaunchKernel(stream_resident_fn(p->res_sw), dim3(p->res_nwg), dim3(mf::kResidentThreads), rargs, p->res_lds, p->stream));
 	}
 	if (p->timing) {
 		MF_HIP(hipEventRecord(t1.t1, p->stream));

@@ -50,7 +50,7 @@ int loss_eval(mf_plan *p, int which, mf_loss *out, double *row_sse)
 {
 	MF_HIP(hipSetDevice(p->device));
 	const bool train = which == MF_LOSS_TRAIN;
-	const int rc = train ? launch_loss(p, p->csr_ptr, p->csr_idx, p->csr_val, p->lpt[1] ? p->short_rows[1] : nullptr)
+	const int rc = train ? launch_loss(p, p->csr_ptr, p->csr_idx, p->csr_val, p->side[1].lpt ? p->side[1].short_rows.get() : nullptr)
 	                     : launch_loss(p, p->ho_ptr, p->ho_idx, p->ho_val, nullptr);
 	if (rc != MF_OK) return rc;
 	double sse = 0.0;

@@ -467,16 +467,9 @@ int mf_backend_run_multi(const mf_problem *pr, double *L, double *R, int32_t *be
 	ss.ev_red.assign((size_t) ndev, nullptr);
 	ss.comm.assign((size_t) ndev, nullptr);
 	rc = for_each_shard(ndev, [&](int g) -> int {
-		mf_shard s;
-		memset(&s, 0, sizeof s);
-		s.users_total = nrows_a;
-		s.items = nrows_b;
-		s.features = K;
+		mf_shard s = whole_shard(nrows_a, nrows_b, K, sl.off[(size_t) g + 1] - sl.off[(size_t) g], pr->alpha, devices[g]);
 		s.user_begin = begin[(size_t) g];
 		s.user_count = begin[(size_t) g + 1] - begin[(size_t) g];
-		s.nnz = sl.off[(size_t) g + 1] - sl.off[(size_t) g];
-		s.alpha = pr->alpha;
-		s.device = devices[g];
 		int r = plan_create_impl(&ss.plan[(size_t) g], &s, sl.base + sl.off[(size_t) g], cut_items);
 		if (r != MF_OK) return r;
 		r = mf_plan_upload_factors(ss.plan[(size_t) g], A + (size_t) begin[(size_t) g] * K, B);
@@ -538,16 +531,9 @@ int mf_backend_run_multi(const mf_problem *pr, double *L, double *R, int32_t *be
 		rc = for_each_shard(ndev, [&](int g) -> int {
 			const int b0 = ubegin[(size_t) g], b1 = ubegin[(size_t) g + 1];
 			if (b1 == b0) return MF_OK;
-			mf_shard s;
-			memset(&s, 0, sizeof s);
-			s.users_total = U;
-			s.items = I;
-			s.features = K;
+			mf_shard s = whole_shard(U, I, K, usl.off[(size_t) g + 1] - usl.off[(size_t) g], pr->alpha, devices[g]);
 			s.user_begin = b0;
 			s.user_count = b1 - b0;
-			s.nnz = usl.off[(size_t) g + 1] - usl.off[(size_t) g];
-			s.alpha = pr->alpha;
-			s.device = devices[g];
 			mf_plan *plan = nullptr;
 			int r = plan_create_impl(&plan, &s, usl.base + usl.off[(size_t) g], false);
 			if (r == MF_OK) r = mf_plan_upload_factors(plan, L + (size_t) b0 * K, R);

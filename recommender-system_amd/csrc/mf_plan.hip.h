@@ -122,6 +122,27 @@ const SweepVariant kGeneric[] = {
 
 constexpr size_t kLdsPerCu = 160 * 1024;
 
+// One side of an iteration (0 = items / CSC, 1 = users / CSR): its rows and what plan_row_schedule decided for its sweep by
+// the rules of mf_schedule.h.
+struct SweepSide {
+	int nrows = 0;           // items / the shard's users
+	bool use_db = false;     // the sweep's main launch takes the double-buffered form
+	bool use_pair = false;   // ... or the wave-pair form
+	bool coop_all = false;   // ... or is ONE cooperative launch over all rows (tiny sweeps)
+	int max_row_len = 0;     // longest column (item sweep) / longest user row (user sweep)
+	int prio_len = 0;        // rows at least this long run at raised wave priority in the single-wave launch (0: none)
+	// skew-aware split of a sweep with many rows: rows whose serial walk would dominate the launch go to the extreme-row
+	// path on a side stream (products over their segments -> ordered sums), the others stay on the main launch
+	dev_buf<int> long_rows, short_rows;
+	bool lpt = false;        // short_rows = ALL rows in dispatch order: a sweep without extreme rows
+	int n_long = 0, n_short = 0;
+	int long_len = 0;        // a row at least this long is on the extreme-row path (when n_long > 0)
+	int n_seg = 0;
+	dev_buf<int> seg_row, seg_beg, seg_end;
+	dev_buf<long long> seg_out, lr_sbeg;
+	dev_buf<int> lr_cnt;
+};
+
 struct TimedLaunch {
 	hipEvent_t t0, t1;
 	int kind;            // 0 item sweep / errors launch, 1 user sweep / streams launch
@@ -244,25 +265,11 @@ struct mf_plan {
 	SweepForm pair;             // wave-pair form (two tiles, two waves per row)
 	SweepForm coop;             // tiny sweeps (a few us of data): ONE cooperative launch over all rows; a fork/join costs more than it saves
 	SweepForm prod;             // products launch over the segments of the extreme rows
-	bool use_db[2] = {false, false};   // the sweep's single-wave launch takes the double-buffered form (plan_row_schedule)
-	bool use_pair[2] = {false, false}; // ... or the wave-pair form
-	int max_row_len[2] = {0, 0}; // longest column (item sweep) / longest user row (user sweep)
-	int prio_len[2] = {0, 0};    // rows at least this long run at raised wave priority in the single-wave launch (0: none)
-	// skew-aware split of a sweep with many rows: rows whose serial walk would dominate the launch go to the
-	// row-cooperative kernel on a side stream, the others stay on the single-wave kernel
-	dev_buf<int> long_rows[2], short_rows[2];
-	bool lpt[2] = {false, false};   // short_rows[kind] = ALL rows, longest first: the order of a sweep without extreme rows
-	int n_long[2] = {0, 0}, n_short[2] = {0, 0};
-	int long_len[2] = {0, 0};   // a row at least this long is on the extreme-row path (when n_long > 0)
-	// extreme rows of LARGE sweeps: 256-entry segments -> scaled rows in `scratch` -> ordered sum
-	int n_seg[2] = {0, 0};
-	dev_buf<int> seg_row[2], seg_beg[2], seg_end[2];
-	dev_buf<long long> seg_out[2], lr_sbeg[2];
-	dev_buf<int> lr_cnt[2];
+	SweepSide side[2];          // 0 = items / CSC, 1 = users / CSR
+	// extreme rows: 64-entry segments -> scaled rows in `scratch` -> ordered sum
 	dev_buf<double> scratch;
 	size_t scratch_entries = 0;
 	size_t lds_bytes_osum = 0;  // LDS request of ordered_sum_kernel (ring + padding that bounds the waves per CU)
-	bool coop_all[2] = {false, false};
 	hipStream_t side_stream = nullptr;
 	hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 
