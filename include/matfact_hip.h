@@ -43,7 +43,9 @@ extern "C" {
                                           ranks of the held-out entries (mf_plan_rank_heldout, mf_plan_rank_heldout_info,
                                           mf_backend_rank_metrics);
                                           similar items (mf_plan_similar_items, mf_plan_similar_items_info,
-                                          mf_backend_similar_items) */
+                                          mf_backend_similar_items);
+                                          L2 regularisation (mf_plan_set_regularization, mf_plan_get_regularization,
+                                          mf_plan_penalty, mf_backend_run_reg) */
 
 /* == non_zero_entry, datatypes.h:10-15: the (user, item, rating) triple, 16 bytes, array-of-structs */
 typedef struct mf_entry {
@@ -336,6 +338,37 @@ int mf_plan_iterate_monitored(mf_plan *plan, int iters, int every, double tol, m
                               int *points, int *iters_done);
 /* level 1: host buffers in, the training loss of these factors out (factors are not changed) */
 int mf_backend_loss(const mf_problem *p, const double *L, const double *R, mf_loss *out, double *row_sse, int device);
+
+/* ---- L2 regularisation (weight decay): the update rule for the objective SSE + lambda_users ||L||^2 + lambda_items ||R||^2.
+ * An extension (the reference has none), so the definition is this library's; it fixes every rounding.  Per side, lambda
+ * is finite and >= 0 and defaults to 0.  On the host, in double:
+ *   c2 = alpha * 2;   d_side = 1.0 - c2 * lambda_side   (two roundings: the product, then the subtraction).
+ * A seeded sweep of side X over the frozen X_old, Y_old:
+ *   e_n         = c2 * (val_n - dot_n)        unchanged: dot_n from the UNshrunk X_old and Y_old
+ *   X_new[r][k] = (...((X_old[r][k] * d_side) + e_0*Y[idx_0][k]) + e_1*Y[idx_1][k]) + ...
+ * -- one more rounded multiply, unfused with the add that follows; the entries in the order of the plain sweep.  An
+ * unseeded sweep (seed_from_old = 0) starts from 0.0 as before: in a sharded or tiled run the decay is applied once, by
+ * the root that seeds.  Nothing is special-cased: a d below 0 is the caller's business; inf * 0, NaN and subnormals follow
+ * IEEE 754.  lambda = 0 gives d = 1.0 (whatever alpha is, a non-finite one included) and x * 1.0 is x bit for bit: with
+ * both at 0 every result is that of the plain rule.
+ * mf_plan_set_regularization: NaN, infinite or negative lambda -> MF_ERR_ARGUMENT before any HIP call and nothing
+ * changes; legal at any time, before the upload too; in force from the next sweep or mf_plan_iterate* call on, for
+ * every way the plan iterates (mf_plan_iterate, mf_plan_iterate_monitored, mf_plan_sweep_items, mf_plan_sweep_users[_seeded]).
+ * mf_backend_run_multi does not regularise.  mf_plan_describe appends lambda=<users>/<items> when either is non-zero. */
+int mf_plan_set_regularization(mf_plan *plan, double lambda_users, double lambda_items);
+int mf_plan_get_regularization(mf_plan *plan, double *lambda_users, double *lambda_items);   /* either may be NULL */
+/* The penalty's two norms for the current factors, next to mf_plan_loss: users_sq = ||L_block||_F^2, items_sq = ||R||_F^2,
+ * in a fixed order.  Row sums s_r = ((0.0 + x_0*x_0) + x_1*x_1) + ..., k ascending, unfused (the s_j of
+ * MF_SIMILAR_COSINE); rows -> total by step 4 of the loss: blocks of MF_LOSS_BLOCK rows cut at global multiples (the
+ * GLOBAL user index for L, the item index for R), T_b summed in ascending order from 0.0, the total over ascending b --
+ * mf_backend_loss_total is the host twin (user_begin = 0 for the items).  user_rows: user_count doubles, item_rows: items
+ * doubles; any pointer may be NULL.  No factors: MF_ERR_STATE.  The objective is then
+ * sse + lambda_users * users_sq + lambda_items * items_sq in whatever order the caller chooses. */
+int mf_plan_penalty(mf_plan *plan, double *users_sq, double *items_sq, double *user_rows, double *item_rows);
+/* level 1: mf_backend_run under regularisation -- L0 / R0 go in as L and R, the final factors come back; best == NULL: no
+ * recommendation.  A bad lambda -> MF_ERR_ARGUMENT before any HIP call. */
+int mf_backend_run_reg(const mf_problem *p, double *L, double *R, int32_t *best, double lambda_users, double lambda_items,
+                       int device);
 
 /* ---- Ranks of the held-out entries: where each held-out item lands in its user's recommendation order, for the plan's
  * current factors.  An extension (the reference ranks nothing), so the definition is this library's.  For held-out entry

@@ -45,6 +45,7 @@ HIP_SYMBOLS = [
     "mf_plan_set_heldout", "mf_plan_loss", "mf_backend_loss_total", "mf_plan_iterate_monitored", "mf_backend_loss",
     "mf_plan_rank_heldout", "mf_plan_rank_heldout_info", "mf_backend_rank_metrics",
     "mf_plan_similar_items", "mf_plan_similar_items_info", "mf_backend_similar_items",
+    "mf_plan_set_regularization", "mf_plan_get_regularization", "mf_plan_penalty", "mf_backend_run_reg",
 ]
 HOST_SYMBOLS = [
     "mf_host_parse_strerror", "mf_host_parse_file", "mf_host_parse_buffer", "mf_host_free_problem",
@@ -191,6 +192,10 @@ def hip():
         lib.mf_plan_similar_items.argtypes = [P, C.c_int, P, C.c_int32, C.c_int32, P, P]
         lib.mf_plan_similar_items_info.argtypes = [P, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         lib.mf_backend_similar_items.argtypes = [P, C.c_int32, C.c_int32, C.c_int, P, C.c_int32, C.c_int32, P, P, C.c_int]
+        lib.mf_plan_set_regularization.argtypes = [P, C.c_double, C.c_double]
+        lib.mf_plan_get_regularization.argtypes = [P, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        lib.mf_plan_penalty.argtypes = [P, C.POINTER(C.c_double), C.POINTER(C.c_double), P, P]
+        lib.mf_backend_run_reg.argtypes = [C.POINTER(Problem), _f64p, _f64p, P, C.c_double, C.c_double, C.c_int]
         _hip = lib
     return _hip
 
@@ -412,6 +417,17 @@ def backend_run(inst, L, R, iters=None, device=0):
     return best
 
 
+def backend_run_reg(inst, L, R, lambda_users, lambda_items=None, iters=None, device=0, recommend=True):
+    """mf_backend_run_reg: backend_run under L2 regularisation (one value means both sides); L, R updated in place,
+    returns best[users], or None with recommend=False."""
+    p, keep = _problem(inst, iters)
+    li = lambda_users if lambda_items is None else lambda_items
+    best = np.empty(inst.users, np.int32) if recommend else None
+    _check(hip().mf_backend_run_reg(C.byref(p), L, R, best.ctypes.data if recommend else None, float(lambda_users), float(li),
+                                    device), "mf_backend_run_reg")
+    return best
+
+
 def backend_run_multi(inst, L, R, devices, iters=None):
     """mf_backend_run_multi: one process, len(devices) shards (ordinals may repeat)."""
     p, keep = _problem(inst, iters)
@@ -603,6 +619,28 @@ class Plan:
 
     def iterate(self, iters):
         _check(hip().mf_plan_iterate(self._h, int(iters)), "mf_plan_iterate")
+
+    def set_regularization(self, users, items=None):
+        """mf_plan_set_regularization: the L2 weights of the user and the item side (one value means both), in force from
+        the next sweep or iterate call."""
+        _check(hip().mf_plan_set_regularization(self._h, float(users), float(users if items is None else items)),
+               "mf_plan_set_regularization")
+
+    def regularization(self):
+        """(lambda_users, lambda_items) in force"""
+        u, i = C.c_double(), C.c_double()
+        _check(hip().mf_plan_get_regularization(self._h, C.byref(u), C.byref(i)), "mf_plan_get_regularization")
+        return u.value, i.value
+
+    def penalty(self, rows=False):
+        """mf_plan_penalty: (||L_block||^2, ||R||^2) of the current factors; with rows=True also the user_count and the
+        items row sums of squares."""
+        u, i = C.c_double(), C.c_double()
+        ur = np.empty(self.user_count, np.float64) if rows else None
+        ir = np.empty(self.items, np.float64) if rows else None
+        _check(hip().mf_plan_penalty(self._h, C.byref(u), C.byref(i), ur.ctypes.data if rows else None,
+                                     ir.ctypes.data if rows else None), "mf_plan_penalty")
+        return (u.value, i.value, ur, ir) if rows else (u.value, i.value)
 
     def sweep_items(self, seed_from_old=True):
         _check(hip().mf_plan_sweep_items(self._h, 1 if seed_from_old else 0), "mf_plan_sweep_items")

@@ -333,6 +333,8 @@ int mf_plan_iterate(mf_plan *p, int iters)
 			ra.ldr = p->ldr;
 			ra.iters = iters;
 			ra.c2 = p->alpha * 2;
+			ra.d_users = side_decay(p, 1);
+			ra.d_items = side_decay(p, 0);
 			ra.csr_ptr = p->csr_ptr;
 			ra.csr_idx = p->csr_idx;
 			ra.csr_val = p->csr_val;
@@ -388,6 +390,33 @@ int mf_plan_iterate(mf_plan *p, int iters)
 		}
 	}
 	return iterate_eager(p, iters);
+}
+
+// a regularisation weight is finite and >= 0 (a NaN fails both comparisons' complement)
+static bool lambda_ok(double v) { return std::isfinite(v) && v >= 0.0; }
+
+int mf_plan_set_regularization(mf_plan *p, double lambda_users, double lambda_items)
+{
+	if (!p || !lambda_ok(lambda_users) || !lambda_ok(lambda_items)) return MF_ERR_ARGUMENT;
+	// read by side_decay at every launch (the graph path captures per call): nothing is cached from an earlier value
+	p->lambda[1] = lambda_users;
+	p->lambda[0] = lambda_items;
+	return MF_OK;
+}
+
+int mf_plan_get_regularization(mf_plan *p, double *lambda_users, double *lambda_items)
+{
+	if (!p) return MF_ERR_ARGUMENT;
+	if (lambda_users) *lambda_users = p->lambda[1];
+	if (lambda_items) *lambda_items = p->lambda[0];
+	return MF_OK;
+}
+
+int mf_plan_penalty(mf_plan *p, double *users_sq, double *items_sq, double *user_rows, double *item_rows)
+{
+	if (!p) return MF_ERR_ARGUMENT;
+	if (!p->have_factors) return MF_ERR_STATE;
+	return penalty_eval(p, users_sq, items_sq, user_rows, item_rows);
 }
 
 int mf_plan_recommend(mf_plan *p, int32_t *best)
@@ -659,6 +688,11 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 			snprintf(buf + at, (size_t) buflen - at, " loss=%s(nch=%d/%d lds=%zu/%zu)", p->sweep.dma ? "loss_dma_kernel" : "loss_reg_kernel",
 			         p->loss_nch[0], p->loss_nch[1], p->loss_lds[0], p->loss_lds[1]);
 	}
+	// the regularisation in force, when there is any
+	if (p->lambda[0] != 0.0 || p->lambda[1] != 0.0) {
+		const size_t at = strlen(buf);
+		if (at + 1 < (size_t) buflen) snprintf(buf + at, (size_t) buflen - at, " lambda=%g/%g", p->lambda[1], p->lambda[0]);
+	}
 	// the environment switches this plan was created under, when any differs from its default (mf_config.hip.h)
 	const std::string cfg = p->cfg.describe();
 	const size_t used = strlen(buf);
@@ -700,6 +734,19 @@ int mf_backend_run(const mf_problem *pr, double *L, double *R, int32_t *best, in
 	if (!pr || !L || !R) return MF_ERR_ARGUMENT;   // L and R carry the initial factors in
 	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
 		int rc = mf_plan_iterate(p, pr->iters);
+		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
+		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
+		return rc;
+	});
+}
+
+int mf_backend_run_reg(const mf_problem *pr, double *L, double *R, int32_t *best, double lambda_users, double lambda_items,
+                       int device)
+{
+	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items)) return MF_ERR_ARGUMENT;
+	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
+		int rc = mf_plan_set_regularization(p, lambda_users, lambda_items);
+		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
 		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
 		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
 		return rc;

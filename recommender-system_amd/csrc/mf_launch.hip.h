@@ -139,6 +139,8 @@ int choose_sweep(mf_plan *p)
 	p->few = SweepForm{nullptr, cs.nch_few, head + (size_t) cs.nch_few * row_bytes, mf::kWave};
 	MF_HIP(raise_lds_limit((const void *) p->sweep.fn, std::max(p->single.lds, p->few.lds)));
 	if (p->sweep.pf) MF_HIP(raise_lds_limit((const void *) p->sweep.pf, std::max(p->single.lds, p->few.lds)));
+	if (p->sweep.fn_decay) MF_HIP(raise_lds_limit((const void *) p->sweep.fn_decay, std::max(p->single.lds, p->few.lds)));
+	if (p->sweep.pf_decay) MF_HIP(raise_lds_limit((const void *) p->sweep.pf_decay, std::max(p->single.lds, p->few.lds)));
 	// the two-tile forms: `dflt` entries per chunk (MF_SWEEP_NCH overrides) while two tiles stay within half a CU's LDS
 	auto two_tiles = [&](SweepFn fn, int dflt, int block) {
 		int n = p->cfg.sweep_nch ? p->cfg.sweep_nch : dflt;
@@ -206,7 +208,7 @@ bool single_wave_pipelined(const mf_plan *p, int kind)
 // The form of the main launch of one side (kind 0: items, 1: users): the cooperative launch of a tiny sweep, the
 // double-buffered or the wave-pair form where plan_row_schedule chose one, else the single-wave form -- plain or
 // pipelined by single_wave_pipelined, at the large chunk when `few_rows`.
-SweepForm main_form(const mf_plan *p, int kind, bool few_rows)
+SweepForm main_form(const mf_plan *p, int kind, bool few_rows, bool decay)
 {
 	const SweepSide &sd = p->side[kind];
 	if (sd.coop_all) {
@@ -220,8 +222,24 @@ SweepForm main_form(const mf_plan *p, int kind, bool few_rows)
 	if (sd.use_db) return p->db;
 	if (sd.use_pair) return p->pair;
 	SweepForm f = few_rows ? p->few : p->single;
-	f.fn = single_wave_pipelined(p, kind) ? p->sweep.pf : p->sweep.fn;
+	// the LDS-DMA single-wave form multiplies the seed only in its decay instances (the register-staged form always does);
+	// a missing one leaves fn null and launch_sweep refuses, rather than run without the decay
+	const bool pf = single_wave_pipelined(p, kind);
+	if (decay && p->sweep.dma)
+		f.fn = pf ? p->sweep.pf_decay : p->sweep.fn_decay;
+	else
+		f.fn = pf ? p->sweep.pf : p->sweep.fn;
 	return f;
+}
+
+// Weight decay of a side's seed (kind 0: items, 1: users): d = 1.0 - (alpha * 2) * lambda, two roundings in double -- the
+// product, then the subtraction.  Read at every launch, so a change of lambda holds from the next sweep on; lambda = 0
+// is 1.0 whatever alpha is (a non-finite alpha times 0 would be NaN), and x * 1.0 is x bit for bit.
+double side_decay(const mf_plan *p, int kind)
+{
+	if (p->lambda[kind] == 0.0) return 1.0;
+	const double t = (p->alpha * 2) * p->lambda[kind];
+	return 1.0 - t;
 }
 
 // defer_join: leave the ordered sums of the extreme rows running on the side stream when the call returns
@@ -236,6 +254,7 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	a.seed = seed;
 	a.prio_len = sd.prio_len;
 	a.c2 = p->alpha * 2;
+	a.d = side_decay(p, kind);
 	a.ldx = x.ldx;
 	a.ldy = x.ldy;
 	a.nrows = sd.nrows;
@@ -254,7 +273,8 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	const bool extreme = sd.n_long > 0;
 	// the large chunk below kSweepFewRows rows.  Never beside the extreme-row path: with the extreme rows gone the
 	// occupancy-friendly chunk size is right again.
-	const SweepForm f = main_form(p, kind, !extreme && a.nrows < kSweepFewRows);
+	const SweepForm f = main_form(p, kind, !extreme && a.nrows < kSweepFewRows, a.d != 1.0);
+	if (!f.fn) return MF_ERR_UNSUPPORTED;
 	a.nch = f.nch;
 	TimedLaunch t{};
 	if (p->timing) {
@@ -284,6 +304,7 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 		o.K = p->K;
 		o.ldx = a.ldx;
 		o.seed = seed;
+		o.d = a.d;
 		o.nslices = (int) mf_sched::slice_count(p->K, mf::kSliceCols);
 		o.row = sd.long_rows;
 		o.sbeg = sd.lr_sbeg;
@@ -334,6 +355,7 @@ int launch_es_iteration(mf_plan *p)
 	a.ldy = users.ldy;
 	a.seed = 1;
 	a.c2 = p->alpha * 2;
+	a.d = 1.0;           // the errors launch seeds nothing: e_n does not see the decay
 	a.ptr = users.ptr;
 	a.idx = users.idx;
 	a.val = users.val;
@@ -356,6 +378,7 @@ int launch_es_iteration(mf_plan *p)
 		ra.yrows[side] = x.yrows;
 		ra.ldx[side] = x.ldx;
 		ra.ldy[side] = x.ldy;
+		ra.d[side] = side_decay(p, side);
 	}
 	TimedLaunch t0{}, t1{};
 	if (p->timing) {

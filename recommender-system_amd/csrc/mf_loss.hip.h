@@ -228,4 +228,38 @@ __global__ void __launch_bounds__(kWave) loss_total_kernel(const double *__restr
 	if (lane == 0) total[0] = t;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Penalty (mf_plan_penalty): the squared Frobenius norm of a factor in a fixed order.  Row sums of squares
+//   s_r = ((0.0 + X[r][0]*X[r][0]) + X[r][1]*X[r][1]) + ...   k ascending, multiply and add unfused
+// (the s_j of MF_SIMILAR_COSINE, staged the way similar_normalize_kernel stages them: coalesced runs of a row into LDS,
+// the serial sum of row r formed by lane r), then loss_block_kernel and loss_total_kernel over them: step 4 of the loss.
+// ------------------------------------------------------------------------------------------------
+constexpr int kPenRows = 16;      // rows of a workgroup (one wave)
+constexpr int kPenKC = 32;        // columns staged per step; the LDS pitch kPenKC + 1 keeps the row walk conflict-free
+
+__global__ void __launch_bounds__(kWave) penalty_rows_kernel(const double *__restrict__ X, int rows, int K, int ld,
+                                                              double *__restrict__ row_sq)
+{
+	__shared__ double tile[kPenRows][kPenKC + 1];
+	const int lane = threadIdx.x;
+	const int r0 = blockIdx.x * kPenRows;
+	const int n = min(kPenRows, rows - r0);
+	double s = 0.0;
+	for (int k0 = 0; k0 < K; k0 += kPenKC) {
+		const int kc = min(kPenKC, K - k0);
+		for (int e = lane; e < n * kPenKC; e += kWave) {
+			const int r = e / kPenKC, k = e % kPenKC;
+			if (k < kc) tile[r][k] = X[(size_t) (r0 + r) * ld + k0 + k];
+		}
+		__syncthreads();
+		if (lane < n)
+			for (int k = 0; k < kc; ++k) {
+				const double v = tile[lane][k];
+				s = s + v * v;   // unfused: the library is built with -ffp-contract=off
+			}
+		__syncthreads();
+	}
+	if (lane < n) row_sq[r0 + lane] = s;
+}
+
 }  // namespace mf

@@ -3,11 +3,17 @@
 
 namespace {
 
+// blocks of kLossBlock rows, cut at global multiples, that `rows` rows from global row `begin` touch
+int blocks_touched(int begin, int rows)
+{
+	return rows > 0 ? (int) (((long long) begin + rows - 1) / mf::kLossBlock - begin / mf::kLossBlock + 1) : 0;
+}
+
 // Row sums of one entry set (CSR over the plan's users) into p->row_sse, then the block sums and the total, all on the
 // plan's stream.  `order`: optional list of all rows in the order the workgroups take them.
 int launch_loss(mf_plan *p, const int *ptr, const int *idx, const double *val, const int *order)
 {
-	const int nblocks = p->uc > 0 ? (int) (((long long) p->u0 + p->uc - 1) / mf::kLossBlock - p->u0 / mf::kLossBlock + 1) : 0;
+	const int nblocks = blocks_touched(p->u0, p->uc);
 	if (!p->row_sse) {   // the three are allocated together; row_sse marks them
 		int rc = p->row_sse.alloc((size_t) p->uc);
 		if (rc == MF_OK) rc = p->loss_blocks.alloc((size_t) nblocks);
@@ -60,6 +66,52 @@ int loss_eval(mf_plan *p, int which, mf_loss *out, double *row_sse)
 	MF_HIP(hipStreamSynchronize(p->stream));
 	out->sse = sse;
 	out->count = train ? p->nnz : p->ho_nnz;
+	return MF_OK;
+}
+
+// The penalty of one factor: row sums of squares into `rows_out`, block sums (blocks cut at global multiples of
+// kLossBlock counted from `begin`) into `blocks_out`, the total into `total_out`, all on the plan's stream.
+int launch_penalty_side(mf_plan *p, const double *X, int begin, int rows, int ld, double *rows_out, double *blocks_out, double *total_out)
+{
+	const int nblocks = blocks_touched(begin, rows);
+	if (rows > 0) {
+		hipLaunchKernelGGL(mf::penalty_rows_kernel, dim3((rows + mf::kPenRows - 1) / mf::kPenRows), dim3(mf::kWave), 0, p->stream, X, rows,
+		                   p->K, ld, rows_out);
+		MF_HIP(hipGetLastError());
+		hipLaunchKernelGGL(mf::loss_block_kernel, dim3(nblocks), dim3(mf::kWave), 0, p->stream, rows_out, begin, rows, nblocks, blocks_out);
+		MF_HIP(hipGetLastError());
+	}
+	hipLaunchKernelGGL(mf::loss_total_kernel, dim3(1), dim3(mf::kWave), 0, p->stream, blocks_out, nblocks, total_out);
+	MF_HIP(hipGetLastError());
+	return MF_OK;
+}
+
+// ||L_block||^2 and ||R||^2 of the current factors: launches and read-back, complete on return.
+int penalty_eval(mf_plan *p, double *users_sq, double *items_sq, double *user_rows, double *item_rows)
+{
+	MF_HIP(hipSetDevice(p->device));
+	const int nbu = blocks_touched(p->u0, p->uc), nbi = blocks_touched(0, p->items);
+	if (!p->pen_total) {   // the three are allocated together; pen_total marks them
+		int rc = p->pen_rows.alloc((size_t) p->uc + (size_t) p->items);
+		if (rc == MF_OK) rc = p->pen_blocks.alloc((size_t) nbu + (size_t) nbi);
+		if (rc == MF_OK) rc = p->pen_total.alloc(2);
+		if (rc != MF_OK) {
+			p->pen_total.reset();
+			return rc;
+		}
+	}
+	double *rows_u = p->pen_rows, *rows_i = rows_u + p->uc;
+	double *blocks_u = p->pen_blocks, *blocks_i = blocks_u + nbu;
+	double *total = p->pen_total;
+	MF_TRY(launch_penalty_side(p, p->Lbuf[p->cur], p->u0, p->uc, p->ldl, rows_u, blocks_u, total));
+	MF_TRY(launch_penalty_side(p, p->Rbuf[p->cur], 0, p->items, p->ldr, rows_i, blocks_i, total + 1));
+	double t[2] = {0.0, 0.0};
+	MF_HIP(hipMemcpyAsync(t, total, sizeof t, hipMemcpyDeviceToHost, p->stream));
+	if (user_rows && p->uc > 0) MF_HIP(hipMemcpyAsync(user_rows, rows_u, (size_t) p->uc * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+	if (item_rows && p->items > 0) MF_HIP(hipMemcpyAsync(item_rows, rows_i, (size_t) p->items * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+	MF_HIP(hipStreamSynchronize(p->stream));
+	if (users_sq) *users_sq = t[0];
+	if (items_sq) *items_sq = t[1];
 	return MF_OK;
 }
 

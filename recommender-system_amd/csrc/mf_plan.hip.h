@@ -36,6 +36,7 @@ struct SweepVariant {
 	SweepFn errs = nullptr;   // errors form: e_n per entry of a segment (all DMA variants; mf_stream.hip.h)
 	SweepFn db = nullptr;     // intra-wave double-buffered form for launches of few rows (all DMA variants)
 	SweepFn pf = nullptr;     // accumulate form with the LDS reads of phases A / B kept in flight (compile-time-K DMA variants)
+	SweepFn fn_decay = nullptr, pf_decay = nullptr;   // fn and pf with the seed times the decay factor (DMA variants; the other forms multiply always)
 	SweepFn pair = nullptr;   // wave-pair form (loader + compute) for launches that end on long rows (64 <= K <= 128, compile-time K)
 	LossFn loss = nullptr;    // row sums of mf_plan_loss in the same geometry (all DMA variants; the others use loss_reg_kernel)
 };
@@ -74,6 +75,9 @@ constexpr SweepVariant dma_variant()
 	v.errs = mf::sweep_dma_kernel<KT, NP, mf::kSweepErrors>;
 	v.db = mf::sweep_db_kernel<KT, NP>;
 	v.pf = mf::sweep_dma_kernel<KT, NP, mf::kSweepAccumulate, 8>;
+	// two-pass rows (K = 256) take the pipelined form at every size (single_wave_pipelined): no plain decay instance
+	if constexpr (KT <= 128) v.fn_decay = mf::sweep_dma_kernel<KT, NP, mf::kSweepDecay>;
+	v.pf_decay = mf::sweep_dma_kernel<KT, NP, mf::kSweepDecay, 8>;
 	v.pair = pair_fn<KT>();
 	v.loss = mf::loss_dma_kernel<KT, NP>;
 	return v;
@@ -90,6 +94,7 @@ constexpr SweepVariant dma_generic_variant()
 	v.prod = mf::sweep_dma_kernel<0, NPASS, mf::kSweepProducts>;
 	v.errs = mf::sweep_dma_kernel<0, NPASS, mf::kSweepErrors>;
 	v.db = mf::sweep_db_kernel<0, NPASS>;
+	v.fn_decay = mf::sweep_dma_kernel<0, NPASS, mf::kSweepDecay>;
 	v.loss = mf::loss_dma_kernel<0, NPASS>;
 	return v;
 }
@@ -183,6 +188,7 @@ struct mf_plan {
 	int u0 = 0, uc = 0;
 	int64_t nnz = 0;
 	double alpha = 0.0;
+	double lambda[2] = {0.0, 0.0};   // L2 regularisation per side (0 = items, 1 = users), mf_plan_set_regularization
 	int flags = 0;
 
 	hipStream_t own_stream = nullptr;
@@ -241,6 +247,9 @@ struct mf_plan {
 	int loss_nch[2] = {0, 0};        // chunk size of the row-sum launch: [0] ordinary, [1] fewer rows than fill the chip
 	size_t loss_lds[2] = {0, 0};     // its LDS request (the L row + ONE tile)
 	dev_buf<double> row_sse, loss_blocks, loss_total;
+	// penalty (mf_plan_penalty), allocated on first use: the row sums of squares [users | items], their block sums
+	// [user blocks | item blocks] and the two totals
+	dev_buf<double> pen_rows, pen_blocks, pen_total;
 	dev_buf<int> ho_ptr, ho_idx;
 	dev_buf<double> ho_val;
 	int64_t ho_nnz = 0;

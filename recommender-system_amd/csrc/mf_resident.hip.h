@@ -44,6 +44,7 @@ struct SliceArgs {
 	StreamSide side[2];
 	int yrows[2];                     // rows of Y per side
 	int ldx[2], ldy[2];               // row pitch of X and of Y per side, in doubles (>= K)
+	double d[2];                      // weight decay per side: a row's seed is X_old * d (SweepArgs::d)
 };
 
 #ifdef MF_STAMPS
@@ -70,6 +71,7 @@ __global__ void __launch_bounds__(kResidentThreads) stream_resident_kernel(Slice
 	const int *__restrict__ ptr = a.ptr[side];
 	const int yrows = a.yrows[side];
 	const size_t ldx = (size_t) a.ldx[side], ldy = (size_t) a.ldy[side];
+	const double d = a.d[side];
 	const int col0 = me.slice * SW, ncol = min(SW, K - col0);
 	const double *ys = reinterpret_cast<const double *>(lds);
 	const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -89,14 +91,14 @@ __global__ void __launch_bounds__(kResidentThreads) stream_resident_kernel(Slice
 	StreamRec r0 = ld(eb), r1 = ld(eb + 64), r2 = ld(eb + 128), r3 = ld(eb + 192);
 	// row pointers of the wave's rows (at most kResidentRows of them): lane l holds ptr[rb + l]
 	const int pv = ptr[min(rb + lane, re)];
-	// seeds of all its rows: register b, lane (g, c) holds X_old[rb + b * G + g][col0 + c].  Nothing but the record
+	// seeds of all its rows, decay applied: register b, lane (g, c) holds X_old[rb + b * G + g][col0 + c] * d.  Nothing but the record
 	// prefetch and the X_new stores touches memory once the stream runs: a load inside it would make hipcc drain the
 	// prefetched chunks (s_waitcnt vmcnt(0) at every join of its branch).
 	constexpr int NSEED = kWave / G;
 	double sv[NSEED];
 #pragma unroll
 	for (int b = 0; b < NSEED; ++b)
-		sv[b] = rb + b * G + g < re ? sd.X_old[(size_t) (rb + b * G + g) * ldx + col0 + cc] : 0.0;
+		sv[b] = rb + b * G + g < re ? sd.X_old[(size_t) (rb + b * G + g) * ldx + col0 + cc] * d : 0.0;
 
 	// ---- the slice of every row of Y -> LDS (16-byte pieces, SW/2 per row).  All of a thread's loads are issued
 	// before the first LDS write (one memory latency for the whole copy, not one per piece): at most kPieces per thread.
@@ -145,7 +147,7 @@ __global__ void __launch_bounds__(kResidentThreads) stream_resident_kernel(Slice
 	// ---- the stream.  cur = the row being added up, row_end = its last entry + 1, acc = its running sum.
 	int cur = rb;
 	auto ptr_of = [&](int q) { return __builtin_amdgcn_readlane(pv, q - rb); };   // ptr[q], rb <= q <= re
-	auto seed_of = [&](int q) {    // X_old[q][col0 + c] in every lane group
+	auto seed_of = [&](int q) {    // X_old[q][col0 + c] * d in every lane group
 		const int b = (q - rb) / G, gg = (q - rb) - b * G;
 		double x = sv[0];
 #pragma unroll

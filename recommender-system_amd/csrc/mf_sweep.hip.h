@@ -19,8 +19,9 @@ namespace mf {
 //   dot_n = sum_k X_old[r][k] * Y_old[idx_n][k]      sequential k, from 0.0       (mat2d.c:126-139)
 //   e_n   = (alpha*2) * (val_n - dot_n)                                            (matFact.c:45)
 //   X_new[r][k] = (...((seed + e_0*Y[idx_0][k]) + e_1*Y[idx_1][k]) + ...)          (matFact.c:47-51)
-// where seed = X_old[r][k], or 0 for the non-root contribution of a sharded item sweep
-// (matFact-mpi.c:187).  Mapping onto the wave, per chunk of <= nch entries of the row:
+// where seed = X_old[r][k] * d (d = 1.0 - c2 * lambda, the side's L2 weight decay: one rounded multiply, unfused with
+// the add that follows; d = 1.0 leaves the bits of X_old), or 0 for the non-root contribution of a sharded item sweep
+// (matFact-mpi.c:187): the decay is applied where the seed is taken, once.  Mapping onto the wave, per chunk of <= nch entries of the row:
 //   stage   the nch gathered Y rows are copied, coalesced (16 B per lane), into an LDS tile whose row
 //           stride is odd in doubles, so both access patterns below are bank-conflict-free;
 //   phase A lane n walks row n of the tile and forms dot_n sequentially in k (the serial order) with
@@ -58,6 +59,9 @@ struct SweepArgs {
 	double *__restrict__ err_a;
 	double *__restrict__ err_b;
 	const int *__restrict__ map;
+	// weight decay: a seeded row starts from X_old[r][k] * d, d = 1.0 - c2 * lambda of the side (1.0: no decay).  Last, so
+	// that the layout in front of it -- all that the products, errors and plain accumulate instances read -- stays as it was
+	double d;
 };
 
 __device__ __forceinline__ double readlane_f64(double v, int lane)
@@ -88,7 +92,7 @@ __global__ void __launch_bounds__(kWave) sweep_kernel(SweepArgs a)
 #pragma unroll
 		for (int kk = 0; kk < KPMAX; ++kk) {
 			const int k = lane + kWave * kk;
-			acc[kk] = (a.seed && k < K) ? xrow[k] : 0.0;
+			acc[kk] = (a.seed && k < K) ? xrow[k] * a.d : 0.0;
 		}
 
 		for (int c = beg; c < end; c += nch) {
@@ -196,10 +200,10 @@ static_assert(kSliceCols == 8 || kSliceCols == 16, "slice width");
 // (an s_waitcnt moves into the chunk loop).  profiles/sweep_parts/README.md has the comparison with the code before.
 // ------------------------------------------------------------------------------------------------
 
-// Row prologue: the owned X row goes to `xs` (phase A reads it as an LDS broadcast) and seeds the accumulators (zero
-// without `seed`, and in the lanes beyond the row).
+// Row prologue: the owned X row goes to `xs` (phase A reads it as an LDS broadcast: the dots see it unshrunk) and, times
+// the decay factor `d`, seeds the accumulators (zero without `seed`, and in the lanes beyond the row).
 template <int NP>
-__device__ __forceinline__ void load_x_row(const double2 *__restrict__ xrow2, double2 *xs, int lane, int P, int seed, double2 (&acc)[NP])
+__device__ __forceinline__ void load_x_row(const double2 *__restrict__ xrow2, double2 *xs, int lane, int P, int seed, double d, double2 (&acc)[NP])
 {
 #pragma unroll
 	for (int p = 0; p < NP; ++p) {
@@ -209,7 +213,7 @@ __device__ __forceinline__ void load_x_row(const double2 *__restrict__ xrow2, do
 			v = xrow2[q];
 			xs[q] = v;
 		}
-		acc[p] = seed ? v : make_double2(0.0, 0.0);
+		acc[p] = seed ? make_double2(v.x * d, v.y * d) : make_double2(0.0, 0.0);
 	}
 }
 
@@ -507,10 +511,12 @@ __device__ __forceinline__ void phase_b_tail(const char *tb, int S, double e, in
 // scaled rows p_n[k] = e_n * y_n[k] (the rounded product the serial loop adds) are stored to a scratch buffer in
 // entry order, and ordered_sum_kernel adds them up in that order afterwards.  Thousands of segments run in
 // parallel, so a row rated by every user costs a chip-wide pass plus one serial chain of adds.
-// MODE: 0 accumulate (the sweep), 1 products (extreme rows), 2 errors (first half of the errors + streams iteration)
+// MODE: 0 accumulate (the sweep), 1 products (extreme rows), 2 errors (first half of the errors + streams iteration),
+// 3 accumulate with the seed multiplied by the decay factor a.d -- launch_sweep picks it when d != 1.0, so the instances
+// of mode 0, the timed path of an unregularised run, keep their code
 // PF > 0: phases A and B keep their LDS reads in flight and the gather issue is lean.
 // ------------------------------------------------------------------------------------------------
-constexpr int kSweepAccumulate = 0, kSweepProducts = 1, kSweepErrors = 2;
+constexpr int kSweepAccumulate = 0, kSweepProducts = 1, kSweepErrors = 2, kSweepDecay = 3;
 #ifdef MF_STAMPS
 // diagnostic build only (tools/stamps.py): shader-clock totals of the phases of the rows of at least 1024 entries --
 // [0] rows, [1] chunks, [2] gather issue, [3] landing wait, [4] phase A, [5] phase B, [6] whole row
@@ -523,7 +529,7 @@ __device__ unsigned long long mf_stamp_buf[8];
 template <int KT, int NPASS, int MODE = kSweepAccumulate, int PF = 0>
 __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 {
-	constexpr bool PRODUCTS = MODE == kSweepProducts, ERRORS = MODE == kSweepErrors, SEGMENTS = MODE != kSweepAccumulate;
+	constexpr bool PRODUCTS = MODE == kSweepProducts, ERRORS = MODE == kSweepErrors, SEGMENTS = PRODUCTS || ERRORS, DECAY = MODE == kSweepDecay;
 	const int K = KT > 0 ? KT : a.K;
 	const int P = dma_pieces(K);
 	constexpr int NP = NPASS;                               // DMA instructions per row
@@ -566,7 +572,10 @@ __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 				v = xrow2[q];
 				xs[q] = v;
 			}
-			acc[p] = a.seed ? v : make_double2(0.0, 0.0);
+			if constexpr (DECAY)
+				acc[p] = a.seed ? make_double2(v.x * a.d, v.y * a.d) : make_double2(0.0, 0.0);
+			else
+				acc[p] = a.seed ? v : make_double2(0.0, 0.0);
 		}
 
 		// (idx, val) of a chunk are loaded one chunk ahead, so the gather of chunk c never waits on them
@@ -769,7 +778,7 @@ __global__ void __launch_bounds__(kWave) sweep_db_kernel(SweepArgs a)
 				v = xrow2[q];
 				xs[q] = v;
 			}
-			acc[p] = a.seed ? v : make_double2(0.0, 0.0);
+			acc[p] = a.seed ? make_double2(v.x * a.d, v.y * a.d) : make_double2(0.0, 0.0);
 		}
 		// chunk c's (idx, val) in cur_*, chunk c+1's in nx_*; the gather of chunk c is issued one iteration ahead
 		int cur_idx = 0, nx_idx = 0;
@@ -922,7 +931,7 @@ __global__ void __launch_bounds__((NL + 1) * kWave) sweep_pair_kernel(SweepArgs 
 				__builtin_amdgcn_s_setprio(0);
 			const double2 *__restrict__ xrow2 = reinterpret_cast<const double2 *>(a.X_old + (size_t) r * a.ldx);
 			double2 acc[1];
-			load_x_row<1>(xrow2, xs, lane, P, a.seed, acc);
+			load_x_row<1>(xrow2, xs, lane, P, a.seed, a.d, acc);
 			double nx_val = 0.0;
 			if (beg + lane < min(end, beg + nch)) nx_val = a.val[beg + lane];
 			const unsigned boff = (unsigned) (lane < P ? lane : 0) * 16u;   // lanes beyond the row re-read piece 0: no branch masks in phase B
@@ -991,6 +1000,7 @@ struct OrderedSumArgs {
 	int nrows, K, seed, nslices;
 	int ldx;                              // row pitch of X in doubles
 	int max_cnt;                          // entries of the longest row of the launch
+	double d;                             // weight decay of the seed (SweepArgs::d)
 	const int *__restrict__ row;          // extreme row ids
 	const long long *__restrict__ sbeg;   // first scratch entry of the row
 	const int *__restrict__ cnt;          // entries of the row
@@ -1013,12 +1023,12 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 	             : "v"(v.x), "v"(v.y), "v"(one))
 
 // One (row, slice) task with D-1 blocks in flight.  `src` = this lane's 16 bytes of block 0 (piece lane >> 4 of entry
-// lane & 15), `my` = its 16 bytes of ring slot 0, `seed_ptr` = its two columns of X_old (null: start from zero).
+// lane & 15), `my` = its 16 bytes of ring slot 0, `seed_ptr` = its two columns of X_old (null: start from zero), `d` = the factor the seed is multiplied by.
 // DPP = false: the plain form -- every lane reads the 16 entries of its piece (LDS broadcast reads) and adds them with
 // v_add_f64; same DMA image, same order, same bits.
 template <int D, bool DPP>
 __device__ __forceinline__ void ordered_sum_task(const char *src, unsigned ring_base, unsigned my, int cnt,
-                                                 const double *seed_ptr, double &ax, double &ay, double one,
+                                                 const double *seed_ptr, double d, double &ax, double &ay, double one,
                                                  unsigned long long &t_issued)
 {
 	static_assert(D >= 4 && D <= kRing, "depth");
@@ -1120,6 +1130,8 @@ __device__ __forceinline__ void ordered_sum_task(const char *src, unsigned ring_
 		if (seed_ptr) {
 			const unsigned addr = my + (unsigned) kRing * 1024u;
 			asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(sv) : "v"(addr) : "memory");
+			sv.x = sv.x * d;   // the decay, on landed data; without a seed the sum starts from 0.0 itself
+			sv.y = sv.y * d;
 		}
 		ax = sv.x;
 		ay = sv.y;
@@ -1220,11 +1232,11 @@ __global__ void __launch_bounds__(kWave) ordered_sum_kernel(OrderedSumArgs a)
 		double ax = 0.0, ay = 0.0;
 		// in flight: all of the ring for the longest rows, a half or a quarter of it for the shorter ones
 		if (4 * (long long) cnt >= 2 * (long long) a.max_cnt)
-			ordered_sum_task<kRing, DPP>(src, ring_base, my, cnt, seed_ptr, ax, ay, one, t_issued);
+			ordered_sum_task<kRing, DPP>(src, ring_base, my, cnt, seed_ptr, a.d, ax, ay, one, t_issued);
 		else if (4 * (long long) cnt >= (long long) a.max_cnt)
-			ordered_sum_task<kRing / 2, DPP>(src, ring_base, my, cnt, seed_ptr, ax, ay, one, t_issued);
+			ordered_sum_task<kRing / 2, DPP>(src, ring_base, my, cnt, seed_ptr, a.d, ax, ay, one, t_issued);
 		else
-			ordered_sum_task<kRing / 4, DPP>(src, ring_base, my, cnt, seed_ptr, ax, ay, one, t_issued);
+			ordered_sum_task<kRing / 4, DPP>(src, ring_base, my, cnt, seed_ptr, a.d, ax, ay, one, t_issued);
 		if (live && ent == 0) *reinterpret_cast<double2 *>(a.X_new + (size_t) r * a.ldx + k0) = make_double2(ax, ay);
 		if (stamp) {
 			stamp[0] = t_start;
@@ -1246,6 +1258,7 @@ struct ResidentArgs {
 	int users, items, K, iters;
 	int ldl, ldr;                               // row pitch of L and of R in global memory (doubles)
 	double c2;                                  // alpha * 2
+	double d_users, d_items;                    // weight decay of a user / an item row's seed (SweepArgs::d)
 	const int *__restrict__ csr_ptr;            // users + 1
 	const int *__restrict__ csr_idx;            // item ids
 	const double *__restrict__ csr_val;
@@ -1300,6 +1313,7 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 	const int end = owner ? (user ? ptr[r + 1] : nnz + ptr[U + 1 + r + 1]) : 0;
 	const int xoff = (user ? r : U + r) * K;    // my row inside a generation
 	const int ybase = user ? U * K : 0;         // the other factor inside a generation
+	const double d = user ? a.d_users : a.d_items;
 	double *cur = gen0, *nxt = gen1;
 	for (int it = 0; it < a.iters; ++it) {
 		if (owner && KMAX > 0) {
@@ -1308,7 +1322,7 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 #pragma unroll
 			for (int k = 0; k < KM; ++k) {
 				xr[k] = k < K ? cur[xoff + k] : 0.0;
-				acc[k] = xr[k];
+				acc[k] = xr[k] * d;
 			}
 			for (int n = beg; n < end; ++n) {
 				const double *y = cur + ybase + idx[n] * K;
@@ -1330,7 +1344,7 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 		} else if (owner) {
 			const double *x = cur + xoff;
 			double *xn = nxt + xoff;
-			for (int k = 0; k < K; ++k) xn[k] = x[k];
+			for (int k = 0; k < K; ++k) xn[k] = x[k] * d;
 			for (int n = beg; n < end; ++n) {
 				const double *y = cur + ybase + idx[n] * K;
 				double dot = 0.0;
@@ -1391,7 +1405,7 @@ __global__ void __launch_bounds__(kCoopWaves *kWave) sweep_coop_kernel(SweepArgs
 				if (q < P) {
 					const double2 v = xrow2[q];
 					xs[q] = v;
-					if (a.seed) acc[p] = v;
+					if (a.seed) acc[p] = make_double2(v.x * a.d, v.y * a.d);
 				}
 			}
 		}

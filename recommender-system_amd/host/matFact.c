@@ -139,9 +139,11 @@ static int run_with_checkpoints(const mf_problem *p, double *L, double *R, int32
 /*
  * MATFACT_LOSS=every[,tol] [MATFACT_HELDOUT=<file.in>]: the single-GPU run through mf_plan_iterate_monitored.  One line per
  * evaluated point goes to stderr; stdout is the `.out` of the iterations actually run (all of them when tol is absent).
+ * With MATFACT_LAMBDA the loop runs regularised, and one more stderr line after it carries ||L||^2, ||R||^2
+ * (mf_plan_penalty) and the objective SSE + lambda_users ||L||^2 + lambda_items ||R||^2 of the final factors.
  */
 static int run_with_loss(const mf_problem *p, const mf_problem *held, const double *L, const double *R, int32_t *best, int device,
-                         int every, double tol, int rank_cutoff)
+                         int every, double tol, int rank_cutoff, int regularised, double lambda_users, double lambda_items)
 {
 	const int64_t nmax = p->nnz > (held ? held->nnz : 0) ? p->nnz : (held ? held->nnz : 0);
 	int32_t *row = malloc(sizeof(int32_t) * (size_t) (nmax ? nmax : 1));
@@ -160,6 +162,7 @@ static int run_with_loss(const mf_problem *p, const mf_problem *held, const doub
 		rc = mf_plan_set_heldout(plan, held->nnz, row, col, val);
 	}
 	int points = 0, done = 0;
+	if (rc == MF_OK && regularised) rc = mf_plan_set_regularization(plan, lambda_users, lambda_items);
 	if (rc == MF_OK) rc = mf_plan_iterate_monitored(plan, p->iters, every, tol, trace, cap, &points, &done);
 	for (int i = 0; rc == MF_OK && i < points && i < cap; i++) {
 		fprintf(stderr, "iter %d train_rmse %.17g", trace[i].iter,
@@ -167,6 +170,16 @@ static int run_with_loss(const mf_problem *p, const mf_problem *held, const doub
 		if (held && held->nnz > 0)
 			fprintf(stderr, " heldout_rmse %.17g", sqrt(trace[i].heldout.sse / (double) trace[i].heldout.count));
 		fprintf(stderr, "\n");
+	}
+	if (rc == MF_OK && regularised) {
+		/* MATFACT_LAMBDA: the penalty's norms of the final factors and the objective at them */
+		double lsq = 0.0, rsq = 0.0;
+		mf_loss fin;
+		rc = mf_plan_penalty(plan, &lsq, &rsq, NULL, NULL);
+		if (rc == MF_OK) rc = mf_plan_loss(plan, MF_LOSS_TRAIN, &fin, NULL);
+		if (rc == MF_OK)
+			fprintf(stderr, "penalty lambda %.17g %.17g users_sq %.17g items_sq %.17g objective %.17g\n", lambda_users, lambda_items, lsq,
+			        rsq, (fin.sse + lambda_users * lsq) + lambda_items * rsq);
 	}
 	if (rc == MF_OK && rank_cutoff && held && held->nnz > 0) {
 		/* row still holds the users of the held-out entries in the caller's order; col is free to take the ranks */
@@ -308,6 +321,26 @@ int main(int argc, char **argv)
 		similar = (int) v;
 	} else if (getenv("MATFACT_SIMILAR_OUT"))
 		die("MATFACT_SIMILAR_OUT needs MATFACT_SIMILAR=N[,dot|cosine].");
+	/* MATFACT_LAMBDA=l[,li]: L2 regularisation, one number for both sides or users,items (mf_plan_set_regularization's
+	 * rule: finite and >= 0).  The single-GPU default path (mf_backend_run_reg) and the MATFACT_LOSS path only. */
+	int regularised = 0;
+	double lambda_users = 0.0, lambda_items = 0.0;
+	const char *lambda_env = getenv("MATFACT_LAMBDA");
+	if (lambda_env) {
+		char *stop;
+		lambda_users = lambda_items = strtod(lambda_env, &stop);
+		if (stop == lambda_env || (*stop && *stop != ',')) die("MATFACT_LAMBDA: expected l[,li] with l and li numbers >= 0.");
+		if (*stop == ',') {
+			char *stop2;
+			lambda_items = strtod(stop + 1, &stop2);
+			if (stop2 == stop + 1 || *stop2) die("MATFACT_LAMBDA: expected l[,li] with l and li numbers >= 0.");
+		}
+		if (!isfinite(lambda_users) || !isfinite(lambda_items) || lambda_users < 0.0 || lambda_items < 0.0)
+			die("MATFACT_LAMBDA: expected l[,li] with l and li numbers >= 0.");
+		if (getenv("MATFACT_DEVICES") || getenv("MATFACT_MATS") || getenv("MATFACT_CHECKPOINT") || getenv("MATFACT_RESUME") || topn || similar)
+			die("MATFACT_LAMBDA works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR.");
+		regularised = 1;
+	}
 	const double t0 = now();
 
 	mf_problem prob;
@@ -350,7 +383,10 @@ int main(int argc, char **argv)
 			die("MATFACT_RESUME: cannot read the checkpoint or it belongs to another instance.");
 	}
 	if (loss_every) {
-		rc = run_with_loss(&prob, have_held ? &held : NULL, L, R, best, device, loss_every, loss_tol, rank_cutoff);
+		rc = run_with_loss(&prob, have_held ? &held : NULL, L, R, best, device, loss_every, loss_tol, rank_cutoff, regularised,
+		                   lambda_users, lambda_items);
+	} else if (regularised) {
+		rc = mf_backend_run_reg(&prob, L, R, best, lambda_users, lambda_items, device);
 	} else if (topn) {
 		rc = mf_backend_run_topn(&prob, L, R, topn, topn_items, NULL, device);
 	} else if (similar) {

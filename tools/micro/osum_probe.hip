@@ -84,6 +84,7 @@ int main(int argc, char **argv)
 	o.nrows = nrows;
 	o.K = K;
 	o.seed = 1;
+	o.d = 1.0;
 	o.nslices = nsl;
 	o.ldx = ld;
 	o.row = drow;
