@@ -45,7 +45,10 @@ extern "C" {
                                           similar items (mf_plan_similar_items, mf_plan_similar_items_info,
                                           mf_backend_similar_items);
                                           L2 regularisation (mf_plan_set_regularization, mf_plan_get_regularization,
-                                          mf_plan_penalty, mf_backend_run_reg) */
+                                          mf_plan_penalty, mf_backend_run_reg);
+                                          frozen factor columns and biases (mf_plan_set_frozen_columns,
+                                          mf_plan_get_frozen_columns, mf_backend_bias_mean, mf_backend_bias_pack,
+                                          mf_backend_bias_unpack, mf_backend_run_biased) */
 
 /* == non_zero_entry, datatypes.h:10-15: the (user, item, rating) triple, 16 bytes, array-of-structs */
 typedef struct mf_entry {
@@ -369,6 +372,42 @@ int mf_plan_penalty(mf_plan *plan, double *users_sq, double *items_sq, double *u
  * recommendation.  A bad lambda -> MF_ERR_ARGUMENT before any HIP call. */
 int mf_backend_run_reg(const mf_problem *p, double *L, double *R, int32_t *best, double lambda_users, double lambda_items,
                        int device);
+
+/* ---- Frozen factor columns: a column of a factor matrix that a sweep leaves alone.  An extension (the reference has
+ * none), so the definition is this library's; it fixes every bit.  Each side has one frozen column index, or -1 for none
+ * (the default).  For a sweep of side X with frozen column f >= 0, for every row r of the launch, bit for bit:
+ *   X_new[r][f] = seed_from_old ? X_old[r][f] : 0.0
+ * -- whatever e_n, Y and d are: a NaN or infinite e_n does not reach the column, the weight decay is not applied to it, and a
+ * row without entries obeys it too.  Every other column is exactly what it is without a frozen column, decay included, and
+ * dot_n reads the frozen column like any other.  The unseeded form writes 0.0, so the caller's sum over shards or tiles
+ * gives back X_old -- with one exception: a frozen -0.0 comes back as +0.0 from a sum with an unseeded shard ((-0.0) + 0.0).
+ * mf_plan_set_frozen_columns: a column < -1 or >= features -> MF_ERR_ARGUMENT before any HIP call and nothing changes;
+ * legal at any time, before the upload too; in force from the next sweep or mf_plan_iterate* call on, for every way the
+ * plan iterates (read at every launch, like the decay).  mf_backend_run_multi does not freeze.  mf_plan_describe appends
+ * frozen=<users>/<items> when either is >= 0.
+ *
+ * Biases on top.  With K = F + 2 columns,
+ *   L' = [ L (F columns) | b_user | 1.0 ]   users' column F+1 frozen
+ *   R' = [ R (F columns) | 1.0    | b_item ] items' column F   frozen
+ * the sequential dot is ((dot_F + b_u*1.0) + 1.0*b_i) and the bias column's update is b*d + sum e_n*1.0 (e_n*1.0 is e_n):
+ * the model a ~ mu + b_user + b_item + l.r on values centred by mu, and every pass that reads L.R^T (recommend, top-N,
+ * ranks, loss, predict) works on it unchanged.  The bias columns decay with their side's lambda, like any free column. */
+int mf_plan_set_frozen_columns(mf_plan *plan, int32_t users_col, int32_t items_col);
+int mf_plan_get_frozen_columns(mf_plan *plan, int32_t *users_col, int32_t *items_col);   /* either may be NULL */
+/* Host helpers (no HIP call).  mf_backend_bias_mean: s = ((0.0 + v_0) + v_1) + ... in the given order, mu = s / (double) n;
+ * n == 0 gives 0.0.  mf_backend_bias_pack: out is rows x (F+2), packed; side 1 (users) writes [X | bias | 1.0], side 0
+ * (items) writes [X | 1.0 | bias]; bias == NULL means zeros.  mf_backend_bias_unpack is the inverse; either of X and bias
+ * may be NULL. */
+int mf_backend_bias_mean(const double *val, int64_t n, double *mu);
+int mf_backend_bias_pack(const double *X, const double *bias, int32_t rows, int32_t F, int side, double *out);
+int mf_backend_bias_unpack(const double *in, int32_t rows, int32_t F, int side, double *X, double *bias);
+/* level 1: the biased model.  p->features = F is the latent count; L, R, user_bias and item_bias go in as the initial values
+ * and come back final; *mu goes out.  The run is mf_backend_run_reg on K = F + 2 with the values a_n - mu (one rounding
+ * each), the packed factors and the frozen columns F+1 (users) and F (items); best is mf_plan_recommend on that plan
+ * (NULL: no recommendation).  Bad lambdas or NULL factors, biases or mu -> MF_ERR_ARGUMENT before any HIP call; F + 2 beyond
+ * the largest supported K (4096) -> MF_ERR_UNSUPPORTED. */
+int mf_backend_run_biased(const mf_problem *p, double *L, double *R, double *user_bias, double *item_bias, double *mu,
+                          int32_t *best, double lambda_users, double lambda_items, int device);
 
 /* ---- Ranks of the held-out entries: where each held-out item lands in its user's recommendation order, for the plan's
  * current factors.  An extension (the reference ranks nothing), so the definition is this library's.  For held-out entry

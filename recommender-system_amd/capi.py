@@ -46,6 +46,8 @@ HIP_SYMBOLS = [
     "mf_plan_rank_heldout", "mf_plan_rank_heldout_info", "mf_backend_rank_metrics",
     "mf_plan_similar_items", "mf_plan_similar_items_info", "mf_backend_similar_items",
     "mf_plan_set_regularization", "mf_plan_get_regularization", "mf_plan_penalty", "mf_backend_run_reg",
+    "mf_plan_set_frozen_columns", "mf_plan_get_frozen_columns", "mf_backend_bias_mean", "mf_backend_bias_pack",
+    "mf_backend_bias_unpack", "mf_backend_run_biased",
 ]
 HOST_SYMBOLS = [
     "mf_host_parse_strerror", "mf_host_parse_file", "mf_host_parse_buffer", "mf_host_free_problem",
@@ -196,6 +198,13 @@ def hip():
         lib.mf_plan_get_regularization.argtypes = [P, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         lib.mf_plan_penalty.argtypes = [P, C.POINTER(C.c_double), C.POINTER(C.c_double), P, P]
         lib.mf_backend_run_reg.argtypes = [C.POINTER(Problem), _f64p, _f64p, P, C.c_double, C.c_double, C.c_int]
+        lib.mf_plan_set_frozen_columns.argtypes = [P, C.c_int32, C.c_int32]
+        lib.mf_plan_get_frozen_columns.argtypes = [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        lib.mf_backend_bias_mean.argtypes = [P, C.c_int64, C.POINTER(C.c_double)]
+        lib.mf_backend_bias_pack.argtypes = [P, P, C.c_int32, C.c_int32, C.c_int, P]
+        lib.mf_backend_bias_unpack.argtypes = [P, C.c_int32, C.c_int32, C.c_int, P, P]
+        lib.mf_backend_run_biased.argtypes = [C.POINTER(Problem), _f64p, _f64p, _f64p, _f64p, C.POINTER(C.c_double), P,
+                                              C.c_double, C.c_double, C.c_int]
         _hip = lib
     return _hip
 
@@ -428,6 +437,52 @@ def backend_run_reg(inst, L, R, lambda_users, lambda_items=None, iters=None, dev
     return best
 
 
+def bias_mean(val):
+    """mf_backend_bias_mean: the mean of `val` summed in the given order from 0.0; 0.0 for an empty array."""
+    v = np.ascontiguousarray(val, np.float64)
+    mu = C.c_double()
+    _check(hip().mf_backend_bias_mean(v.ctypes.data, v.size, C.byref(mu)), "mf_backend_bias_mean")
+    return mu.value
+
+
+def bias_pack(X, bias, side):
+    """mf_backend_bias_pack: rows x (F+2) -- side 1 (users) [X | bias | 1.0], side 0 (items) [X | 1.0 | bias]; bias=None
+    means zeros."""
+    X = np.ascontiguousarray(X, np.float64)
+    rows, F = X.shape
+    b = None if bias is None else np.ascontiguousarray(bias, np.float64)
+    if b is not None and b.shape != (rows,):
+        raise ValueError("bias_pack: bias must have one element per row")
+    out = np.empty((rows, F + 2), np.float64)
+    _check(hip().mf_backend_bias_pack(X.ctypes.data, None if b is None else b.ctypes.data, rows, F, int(side), out.ctypes.data),
+           "mf_backend_bias_pack")
+    return out
+
+
+def bias_unpack(packed, side):
+    """mf_backend_bias_unpack: (X, bias) of a packed rows x (F+2) factor."""
+    p = np.ascontiguousarray(packed, np.float64)
+    rows, K = p.shape
+    X, b = np.empty((rows, K - 2), np.float64), np.empty(rows, np.float64)
+    _check(hip().mf_backend_bias_unpack(p.ctypes.data, rows, K - 2, int(side), X.ctypes.data, b.ctypes.data),
+           "mf_backend_bias_unpack")
+    return X, b
+
+
+def backend_run_biased(inst, L, R, user_bias, item_bias, lambda_users=0.0, lambda_items=None, iters=None, device=0,
+                       recommend=True):
+    """mf_backend_run_biased: the model a ~ mu + b_user + b_item + l.r; L, R (inst.feats latent columns), user_bias and
+    item_bias are updated in place.  Returns (mu, best), best None with recommend=False."""
+    p, keep = _problem(inst, iters)
+    li = lambda_users if lambda_items is None else lambda_items
+    best = np.empty(inst.users, np.int32) if recommend else None
+    mu = C.c_double()
+    _check(hip().mf_backend_run_biased(C.byref(p), L, R, user_bias, item_bias, C.byref(mu),
+                                       best.ctypes.data if recommend else None, float(lambda_users), float(li), device),
+           "mf_backend_run_biased")
+    return mu.value, best
+
+
 def backend_run_multi(inst, L, R, devices, iters=None):
     """mf_backend_run_multi: one process, len(devices) shards (ordinals may repeat)."""
     p, keep = _problem(inst, iters)
@@ -630,6 +685,17 @@ class Plan:
         """(lambda_users, lambda_items) in force"""
         u, i = C.c_double(), C.c_double()
         _check(hip().mf_plan_get_regularization(self._h, C.byref(u), C.byref(i)), "mf_plan_get_regularization")
+        return u.value, i.value
+
+    def set_frozen_columns(self, users, items):
+        """mf_plan_set_frozen_columns: the column of L and of R that the sweeps leave alone (-1: none), in force from the
+        next sweep or iterate call."""
+        _check(hip().mf_plan_set_frozen_columns(self._h, int(users), int(items)), "mf_plan_set_frozen_columns")
+
+    def frozen_columns(self):
+        """(users' column, items' column) in force; -1: none"""
+        u, i = C.c_int32(), C.c_int32()
+        _check(hip().mf_plan_get_frozen_columns(self._h, C.byref(u), C.byref(i)), "mf_plan_get_frozen_columns")
         return u.value, i.value
 
     def penalty(self, rows=False):

@@ -335,6 +335,8 @@ int mf_plan_iterate(mf_plan *p, int iters)
 			ra.c2 = p->alpha * 2;
 			ra.d_users = side_decay(p, 1);
 			ra.d_items = side_decay(p, 0);
+			ra.frozen_users = p->frozen[1];
+			ra.frozen_items = p->frozen[0];
 			ra.csr_ptr = p->csr_ptr;
 			ra.csr_idx = p->csr_idx;
 			ra.csr_val = p->csr_val;
@@ -409,6 +411,23 @@ int mf_plan_get_regularization(mf_plan *p, double *lambda_users, double *lambda_
 	if (!p) return MF_ERR_ARGUMENT;
 	if (lambda_users) *lambda_users = p->lambda[1];
 	if (lambda_items) *lambda_items = p->lambda[0];
+	return MF_OK;
+}
+
+int mf_plan_set_frozen_columns(mf_plan *p, int32_t users_col, int32_t items_col)
+{
+	if (!p || users_col < -1 || items_col < -1 || users_col >= p->K || items_col >= p->K) return MF_ERR_ARGUMENT;
+	// read at every launch, like the decay: the graph path captures per call, so no replay sees an earlier value
+	p->frozen[1] = users_col;
+	p->frozen[0] = items_col;
+	return MF_OK;
+}
+
+int mf_plan_get_frozen_columns(mf_plan *p, int32_t *users_col, int32_t *items_col)
+{
+	if (!p) return MF_ERR_ARGUMENT;
+	if (users_col) *users_col = p->frozen[1];
+	if (items_col) *items_col = p->frozen[0];
 	return MF_OK;
 }
 
@@ -693,6 +712,11 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 		const size_t at = strlen(buf);
 		if (at + 1 < (size_t) buflen) snprintf(buf + at, (size_t) buflen - at, " lambda=%g/%g", p->lambda[1], p->lambda[0]);
 	}
+	// the frozen columns in force, when there is one
+	if (p->frozen[0] >= 0 || p->frozen[1] >= 0) {
+		const size_t at = strlen(buf);
+		if (at + 1 < (size_t) buflen) snprintf(buf + at, (size_t) buflen - at, " frozen=%d/%d", p->frozen[1], p->frozen[0]);
+	}
 	// the environment switches this plan was created under, when any differs from its default (mf_config.hip.h)
 	const std::string cfg = p->cfg.describe();
 	const size_t used = strlen(buf);
@@ -751,6 +775,83 @@ int mf_backend_run_reg(const mf_problem *pr, double *L, double *R, int32_t *best
 		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
 		return rc;
 	});
+}
+
+// ---- biases on frozen columns: a ~ mu + b_user + b_item + l.r as the K = F + 2 product of
+//   L' = [ L | b_user | 1.0 ] (users' column F+1 frozen)  and  R' = [ R | 1.0 | b_item ] (items' column F frozen)
+int mf_backend_bias_mean(const double *val, int64_t n, double *mu)
+{
+	if (!mu || n < 0 || (n > 0 && !val)) return MF_ERR_ARGUMENT;
+	double s = 0.0;
+	for (int64_t i = 0; i < n; ++i) s = s + val[i];
+	*mu = n > 0 ? s / (double) n : 0.0;
+	return MF_OK;
+}
+
+int mf_backend_bias_pack(const double *X, const double *bias, int32_t rows, int32_t F, int side, double *out)
+{
+	if (rows < 0 || F < 1 || (side != 0 && side != 1) || (rows > 0 && (!X || !out))) return MF_ERR_ARGUMENT;
+	const size_t K = (size_t) F + 2;
+	for (int32_t r = 0; r < rows; ++r) {
+		double *o = out + (size_t) r * K;
+		for (int32_t k = 0; k < F; ++k) o[k] = X[(size_t) r * F + k];
+		const double b = bias ? bias[r] : 0.0;
+		o[F] = side == 1 ? b : 1.0;
+		o[F + 1] = side == 1 ? 1.0 : b;
+	}
+	return MF_OK;
+}
+
+int mf_backend_bias_unpack(const double *in, int32_t rows, int32_t F, int side, double *X, double *bias)
+{
+	if (rows < 0 || F < 1 || (side != 0 && side != 1) || (rows > 0 && !in)) return MF_ERR_ARGUMENT;
+	const size_t K = (size_t) F + 2;
+	for (int32_t r = 0; r < rows; ++r) {
+		const double *i = in + (size_t) r * K;
+		if (X)
+			for (int32_t k = 0; k < F; ++k) X[(size_t) r * F + k] = i[k];
+		if (bias) bias[r] = i[side == 1 ? F : F + 1];
+	}
+	return MF_OK;
+}
+
+int mf_backend_run_biased(const mf_problem *pr, double *L, double *R, double *user_bias, double *item_bias, double *mu,
+                          int32_t *best, double lambda_users, double lambda_items, int device)
+{
+	if (!pr || !L || !R || !user_bias || !item_bias || !mu || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) ||
+	    pr->users < 0 || pr->items < 0 || pr->features < 1 || pr->nnz < 0 || pr->iters < 0 || (pr->nnz > 0 && !pr->entries))
+		return MF_ERR_ARGUMENT;
+	if (pr->features > kLargestK - 2) return MF_ERR_UNSUPPORTED;
+	const int32_t F = pr->features, K = F + 2;
+	// mu in the entries' order, then every value centred with one rounding
+	std::vector<mf_entry> ent((size_t) pr->nnz);
+	{
+		std::vector<double> v((size_t) pr->nnz);
+		for (int64_t n = 0; n < pr->nnz; ++n) v[(size_t) n] = pr->entries[n].value;
+		(void) mf_backend_bias_mean(v.data(), pr->nnz, mu);
+		for (int64_t n = 0; n < pr->nnz; ++n) {
+			ent[(size_t) n] = pr->entries[n];
+			ent[(size_t) n].value = v[(size_t) n] - *mu;
+		}
+	}
+	std::vector<double> Lp((size_t) pr->users * K), Rp((size_t) pr->items * K);
+	(void) mf_backend_bias_pack(L, user_bias, pr->users, F, 1, Lp.data());
+	(void) mf_backend_bias_pack(R, item_bias, pr->items, F, 0, Rp.data());
+	mf_problem q = *pr;
+	q.features = K;
+	q.entries = ent.data();
+	const int rc = with_single_plan(&q, device, Lp.data(), Rp.data(), [&](mf_plan *p) {
+		int rc = mf_plan_set_regularization(p, lambda_users, lambda_items);
+		if (rc == MF_OK) rc = mf_plan_set_frozen_columns(p, F + 1, F);
+		if (rc == MF_OK) rc = mf_plan_iterate(p, q.iters);
+		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
+		if (rc == MF_OK) rc = mf_plan_download_factors(p, Lp.data(), Rp.data());
+		return rc;
+	});
+	if (rc != MF_OK) return rc;
+	(void) mf_backend_bias_unpack(Lp.data(), pr->users, F, 1, L, user_bias);
+	(void) mf_backend_bias_unpack(Rp.data(), pr->items, F, 0, R, item_bias);
+	return MF_OK;
 }
 
 int mf_backend_run_top1(const mf_problem *pr, const double *L0, const double *R0, int32_t *best, int device)

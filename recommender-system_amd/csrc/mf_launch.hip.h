@@ -222,8 +222,9 @@ SweepForm main_form(const mf_plan *p, int kind, bool few_rows, bool decay)
 	if (sd.use_db) return p->db;
 	if (sd.use_pair) return p->pair;
 	SweepForm f = few_rows ? p->few : p->single;
-	// the LDS-DMA single-wave form multiplies the seed only in its decay instances (the register-staged form always does);
-	// a missing one leaves fn null and launch_sweep refuses, rather than run without the decay
+	// the LDS-DMA single-wave form multiplies the seed, and keeps a frozen column, only in its decay instances (the
+	// register-staged form always does) -- `decay` is "d != 1.0 or the side has a frozen column", x * 1.0 being x; a
+	// missing one leaves fn null and launch_sweep refuses, rather than run without the decay or the frozen column
 	const bool pf = single_wave_pipelined(p, kind);
 	if (decay && p->sweep.dma)
 		f.fn = pf ? p->sweep.pf_decay : p->sweep.fn_decay;
@@ -255,6 +256,7 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	a.prio_len = sd.prio_len;
 	a.c2 = p->alpha * 2;
 	a.d = side_decay(p, kind);
+	a.frozen = p->frozen[kind];   // read at every launch, like the decay: a captured graph is built per call
 	a.ldx = x.ldx;
 	a.ldy = x.ldy;
 	a.nrows = sd.nrows;
@@ -273,7 +275,7 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	const bool extreme = sd.n_long > 0;
 	// the large chunk below kSweepFewRows rows.  Never beside the extreme-row path: with the extreme rows gone the
 	// occupancy-friendly chunk size is right again.
-	const SweepForm f = main_form(p, kind, !extreme && a.nrows < kSweepFewRows, a.d != 1.0);
+	const SweepForm f = main_form(p, kind, !extreme && a.nrows < kSweepFewRows, a.d != 1.0 || a.frozen >= 0);
 	if (!f.fn) return MF_ERR_UNSUPPORTED;
 	a.nch = f.nch;
 	TimedLaunch t{};
@@ -305,6 +307,7 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 		o.ldx = a.ldx;
 		o.seed = seed;
 		o.d = a.d;
+		o.frozen = a.frozen;
 		o.nslices = (int) mf_sched::slice_count(p->K, mf::kSliceCols);
 		o.row = sd.long_rows;
 		o.sbeg = sd.lr_sbeg;
@@ -356,6 +359,7 @@ int launch_es_iteration(mf_plan *p)
 	a.seed = 1;
 	a.c2 = p->alpha * 2;
 	a.d = 1.0;           // the errors launch seeds nothing: e_n does not see the decay
+	a.frozen = -1;       // and stores no factor row
 	a.ptr = users.ptr;
 	a.idx = users.idx;
 	a.val = users.val;
@@ -379,6 +383,7 @@ int launch_es_iteration(mf_plan *p)
 		ra.ldx[side] = x.ldx;
 		ra.ldy[side] = x.ldy;
 		ra.d[side] = side_decay(p, side);
+		ra.frozen[side] = p->frozen[side];
 	}
 	TimedLaunch t0{}, t1{};
 	if (p->timing) {

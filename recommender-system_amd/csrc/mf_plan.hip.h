@@ -36,7 +36,7 @@ struct SweepVariant {
 	SweepFn errs = nullptr;   // errors form: e_n per entry of a segment (all DMA variants; mf_stream.hip.h)
 	SweepFn db = nullptr;     // intra-wave double-buffered form for launches of few rows (all DMA variants)
 	SweepFn pf = nullptr;     // accumulate form with the LDS reads of phases A / B kept in flight (compile-time-K DMA variants)
-	SweepFn fn_decay = nullptr, pf_decay = nullptr;   // fn and pf with the seed times the decay factor (DMA variants; the other forms multiply always)
+	SweepFn fn_decay = nullptr, pf_decay = nullptr;   // fn and pf with the seed times the decay factor and the frozen column kept (DMA variants; the other forms do both always)
 	SweepFn pair = nullptr;   // wave-pair form (loader + compute) for launches that end on long rows (64 <= K <= 128, compile-time K)
 	LossFn loss = nullptr;    // row sums of mf_plan_loss in the same geometry (all DMA variants; the others use loss_reg_kernel)
 };
@@ -125,6 +125,8 @@ const SweepVariant kGeneric[] = {
     variant<0, 16>(), variant<0, 32>(), variant<0, 64>(),
 };
 
+constexpr int kLargestK = 64 * mf::kWave;   // the widest row of kGeneric: choose_sweep refuses a larger K
+
 constexpr size_t kLdsPerCu = 160 * 1024;
 
 // One side of an iteration (0 = items / CSC, 1 = users / CSR): its rows and what plan_row_schedule decided for its sweep by
@@ -189,6 +191,7 @@ struct mf_plan {
 	int64_t nnz = 0;
 	double alpha = 0.0;
 	double lambda[2] = {0.0, 0.0};   // L2 regularisation per side (0 = items, 1 = users), mf_plan_set_regularization
+	int frozen[2] = {-1, -1};        // frozen column per side (0 = items, 1 = users) or -1, mf_plan_set_frozen_columns
 	int flags = 0;
 
 	hipStream_t own_stream = nullptr;

@@ -45,6 +45,7 @@ struct SliceArgs {
 	int yrows[2];                     // rows of Y per side
 	int ldx[2], ldy[2];               // row pitch of X and of Y per side, in doubles (>= K)
 	double d[2];                      // weight decay per side: a row's seed is X_old * d (SweepArgs::d)
+	int frozen[2];                    // frozen column per side, or -1 (SweepArgs::frozen)
 };
 
 #ifdef MF_STAMPS
@@ -80,6 +81,9 @@ __global__ void __launch_bounds__(kResidentThreads) stream_resident_kernel(Slice
 	double *prod = reinterpret_cast<double *>(wbuf + kResidentWaveLds - 1024);   // two steps' products
 	const int g = lane / SW, c = lane - g * SW;
 	const int cc = c < ncol ? c : 0;
+	// the lanes of the side's frozen column: their seeds stay unshrunk (x * 1.0 is x) and a closed row stores its seed
+	const bool frz = c < ncol && col0 + c == a.frozen[side];
+	const double dl = frz ? 1.0 : d;
 
 	const int rb = me.row_beg[wave], re = me.row_beg[wave + 1];
 	const int eb = me.ent_beg[wave], ee = me.ent_beg[wave + 1];
@@ -91,14 +95,14 @@ __global__ void __launch_bounds__(kResidentThreads) stream_resident_kernel(Slice
 	StreamRec r0 = ld(eb), r1 = ld(eb + 64), r2 = ld(eb + 128), r3 = ld(eb + 192);
 	// row pointers of the wave's rows (at most kResidentRows of them): lane l holds ptr[rb + l]
 	const int pv = ptr[min(rb + lane, re)];
-	// seeds of all its rows, decay applied: register b, lane (g, c) holds X_old[rb + b * G + g][col0 + c] * d.  Nothing but the record
+	// seeds of all its rows, decay applied: register b, lane (g, c) holds X_old[rb + b * G + g][col0 + c] * d (the frozen column's lanes: * 1.0).  Nothing but the record
 	// prefetch and the X_new stores touches memory once the stream runs: a load inside it would make hipcc drain the
 	// prefetched chunks (s_waitcnt vmcnt(0) at every join of its branch).
 	constexpr int NSEED = kWave / G;
 	double sv[NSEED];
 #pragma unroll
 	for (int b = 0; b < NSEED; ++b)
-		sv[b] = rb + b * G + g < re ? sd.X_old[(size_t) (rb + b * G + g) * ldx + col0 + cc] * d : 0.0;
+		sv[b] = rb + b * G + g < re ? sd.X_old[(size_t) (rb + b * G + g) * ldx + col0 + cc] * dl : 0.0;
 
 	// ---- the slice of every row of Y -> LDS (16-byte pieces, SW/2 per row).  All of a thread's loads are issued
 	// before the first LDS write (one memory latency for the whole copy, not one per piece): at most kPieces per thread.
@@ -155,6 +159,7 @@ __global__ void __launch_bounds__(kResidentThreads) stream_resident_kernel(Slice
 		return __shfl(x, gg * SW + cc);
 	};
 	double acc = seed_of(rb);
+	double sc = acc;   // the seed of row `cur`: what its frozen column stores
 	int row_end = ptr_of(cur + 1);
 	// A finished row is stored from an asm statement: a store hipcc knows of inside the stream makes it drain the
 	// prefetched chunks at every chunk (vmcnt(0) at the loop head).  Unknown to its bookkeeping the store only makes
@@ -163,11 +168,13 @@ __global__ void __launch_bounds__(kResidentThreads) stream_resident_kernel(Slice
 		while (pos == row_end && cur < re) {
 			if (g == 0 && c < ncol) {
 				double *dst = sd.X_new + (size_t) cur * ldx + col0 + c;
-				asm volatile("global_store_dwordx2 %0, %1, off" ::"v"(dst), "v"(acc) : "memory");
+				const double out = frz ? sc : acc;   // a select on the result: no e_n reaches the frozen column
+				asm volatile("global_store_dwordx2 %0, %1, off" ::"v"(dst), "v"(out) : "memory");
 			}
 			++cur;
 			if (cur < re) {
 				acc = seed_of(cur);
+				sc = acc;
 				row_end = ptr_of(cur + 1);
 			}
 		}

@@ -62,6 +62,9 @@ struct SweepArgs {
 	// weight decay: a seeded row starts from X_old[r][k] * d, d = 1.0 - c2 * lambda of the side (1.0: no decay).  Last, so
 	// that the layout in front of it -- all that the products, errors and plain accumulate instances read -- stays as it was
 	double d;
+	// frozen column of the side, or -1: X_new[r][frozen] = seed ? X_old[r][frozen] : 0.0 whatever was added up -- a select on
+	// the finished row where it is stored, in the instances that multiply by d (main_form picks those for a frozen side too)
+	int frozen;
 };
 
 __device__ __forceinline__ double readlane_f64(double v, int lane)
@@ -144,11 +147,19 @@ __global__ void __launch_bounds__(kWave) sweep_kernel(SweepArgs a)
 			}
 			__syncthreads();
 		}
+		// the frozen column keeps its old bits (0.0 without a seed): a select on the result, so no e_n reaches it.  Its
+		// register is a scalar compare and its lane one mask (-1: register -1, which no kk is).  The empty asm keeps hipcc
+		// from forming KPMAX lane masks in front of the row loop and holding them across it.
+		int fk = a.frozen >> 6;
+		asm volatile("" : "+s"(fk));
+		const bool flane = lane == (a.frozen & (kWave - 1));
 #pragma unroll
 		for (int kk = 0; kk < KPMAX; ++kk) {
 			const int k = lane + kWave * kk;
-			if (k < K)
+			if (k < K) {
+				if (kk == fk && flane) acc[kk] = a.seed ? xrow[k] : 0.0;
 				a.X_new[(size_t) r * a.ldx + k] = acc[kk];
+			}
 		}
 	}
 }
@@ -214,6 +225,29 @@ __device__ __forceinline__ void load_x_row(const double2 *__restrict__ xrow2, do
 			xs[q] = v;
 		}
 		acc[p] = seed ? make_double2(v.x * d, v.y * d) : make_double2(0.0, 0.0);
+	}
+}
+
+// Frozen column `frozen` (-1: none, and no piece matches) of a finished row: the lane that owns its piece takes the
+// element back from `xs`, which holds the old row unshrunk until the next row's prologue -- 0.0 without a seed.  A select
+// on the result: whatever was added up (a NaN e_n, the decay) does not reach the column.
+template <int NP>
+__device__ __forceinline__ void freeze_column(const double2 *xs, int lane, int seed, int frozen, double2 (&acc)[NP])
+{
+	int fq = frozen >> 1;                             // its piece; pass fq >> 6 (a scalar compare), lane fq & 63 (one mask)
+	asm volatile("" : "+s"(fq));                      // per row: hipcc would hold NP masks across the row loop otherwise
+	const bool flane = lane == (fq & (kWave - 1));
+#pragma unroll
+	for (int p = 0; p < NP; ++p) {
+		const int q = lane + kWave * p;
+		if (p == fq >> 6 && flane) {
+			const double2 x = xs[q];
+			const double f = seed ? ((frozen & 1) ? x.y : x.x) : 0.0;
+			if (frozen & 1)
+				acc[p].y = f;
+			else
+				acc[p].x = f;
+		}
 	}
 }
 
@@ -513,7 +547,8 @@ __device__ __forceinline__ void phase_b_tail(const char *tb, int S, double e, in
 // parallel, so a row rated by every user costs a chip-wide pass plus one serial chain of adds.
 // MODE: 0 accumulate (the sweep), 1 products (extreme rows), 2 errors (first half of the errors + streams iteration),
 // 3 accumulate with the seed multiplied by the decay factor a.d -- launch_sweep picks it when d != 1.0, so the instances
-// of mode 0, the timed path of an unregularised run, keep their code
+// of mode 0, the timed path of an unregularised run, keep their code.  Mode 3 also carries the frozen column (a.frozen):
+// launch_sweep picks it for a frozen side at d = 1.0 too, x * 1.0 being x
 // PF > 0: phases A and B keep their LDS reads in flight and the gather issue is lean.
 // ------------------------------------------------------------------------------------------------
 constexpr int kSweepAccumulate = 0, kSweepProducts = 1, kSweepErrors = 2, kSweepDecay = 3;
@@ -714,6 +749,7 @@ __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 		}
 #endif
 		if (!SEGMENTS) {
+			if constexpr (DECAY) freeze_column<NP>(xs, lane, a.seed, a.frozen, acc);
 			double2 *__restrict__ out2 = reinterpret_cast<double2 *>(a.X_new + (size_t) r * a.ldx);
 #pragma unroll
 			for (int p = 0; p < NP; ++p) {
@@ -853,6 +889,7 @@ __global__ void __launch_bounds__(kWave) sweep_db_kernel(SweepArgs a)
 			asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 		}
 		{
+			freeze_column<NP>(xs, lane, a.seed, a.frozen, acc);
 			double2 *__restrict__ out2 = reinterpret_cast<double2 *>(a.X_new + (size_t) r * a.ldx);
 #pragma unroll
 			for (int p = 0; p < NP; ++p) {
@@ -949,6 +986,7 @@ __global__ void __launch_bounds__((NL + 1) * kWave) sweep_pair_kernel(SweepArgs 
 				const int n = phase_b_sixteen<false>(tb, S, e, 0, cnt, true, acc[0]);
 				phase_b_tail<1, false>(tb, S, e, n, cnt, lane, P, acc);
 			}
+			freeze_column<1>(xs, lane, a.seed, a.frozen, acc);
 			store_x_row<1>(reinterpret_cast<double2 *>(a.X_new + (size_t) r * a.ldx), lane, P, acc);
 			// row end: every read of the last tile and of xs is complete before the loader refills / xs is rewritten
 			asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -1001,6 +1039,7 @@ struct OrderedSumArgs {
 	int ldx;                              // row pitch of X in doubles
 	int max_cnt;                          // entries of the longest row of the launch
 	double d;                             // weight decay of the seed (SweepArgs::d)
+	int frozen;                           // frozen column or -1 (SweepArgs::frozen)
 	const int *__restrict__ row;          // extreme row ids
 	const long long *__restrict__ sbeg;   // first scratch entry of the row
 	const int *__restrict__ cnt;          // entries of the row
@@ -1237,6 +1276,19 @@ __global__ void __launch_bounds__(kWave) ordered_sum_kernel(OrderedSumArgs a)
 			ordered_sum_task<kRing / 2, DPP>(src, ring_base, my, cnt, seed_ptr, a.d, ax, ay, one, t_issued);
 		else
 			ordered_sum_task<kRing / 4, DPP>(src, ring_base, my, cnt, seed_ptr, a.d, ax, ay, one, t_issued);
+		// the frozen column: its two-column piece takes the element back from the seed's slot -- landed with block 0 and
+		// rewritten by no block -- or 0.0 without a seed; read and waited for in one statement like every read of the ring
+		if (live && (a.frozen >> 1 << 1) == k0) {
+			v2d sv = {0.0, 0.0};
+			if (a.seed) {
+				const unsigned addr = my + (unsigned) kRing * 1024u;
+				asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(sv) : "v"(addr) : "memory");
+			}
+			if (a.frozen & 1)
+				ay = sv.y;
+			else
+				ax = sv.x;
+		}
 		if (live && ent == 0) *reinterpret_cast<double2 *>(a.X_new + (size_t) r * a.ldx + k0) = make_double2(ax, ay);
 		if (stamp) {
 			stamp[0] = t_start;
@@ -1259,6 +1311,7 @@ struct ResidentArgs {
 	int ldl, ldr;                               // row pitch of L and of R in global memory (doubles)
 	double c2;                                  // alpha * 2
 	double d_users, d_items;                    // weight decay of a user / an item row's seed (SweepArgs::d)
+	int frozen_users, frozen_items;             // frozen column of a user / an item row, or -1 (SweepArgs::frozen)
 	const int *__restrict__ csr_ptr;            // users + 1
 	const int *__restrict__ csr_idx;            // item ids
 	const double *__restrict__ csr_val;
@@ -1314,6 +1367,7 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 	const int xoff = (user ? r : U + r) * K;    // my row inside a generation
 	const int ybase = user ? U * K : 0;         // the other factor inside a generation
 	const double d = user ? a.d_users : a.d_items;
+	const int frozen = user ? a.frozen_users : a.frozen_items;
 	double *cur = gen0, *nxt = gen1;
 	for (int it = 0; it < a.iters; ++it) {
 		if (owner && KMAX > 0) {
@@ -1324,6 +1378,9 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 				xr[k] = k < K ? cur[xoff + k] : 0.0;
 				acc[k] = xr[k] * d;
 			}
+			// the frozen column's old element, read beside the row (a select over xr[] would keep KMAX lane masks alive
+			// across the iteration loop)
+			const double fold = frozen >= 0 ? cur[xoff + frozen] : 0.0;
 			for (int n = beg; n < end; ++n) {
 				const double *y = cur + ybase + idx[n] * K;
 				double yr[KM];
@@ -1341,6 +1398,7 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 #pragma unroll
 			for (int k = 0; k < KM; ++k)
 				if (k < K) nxt[xoff + k] = acc[k];
+			if (frozen >= 0) nxt[xoff + frozen] = fold;   // whatever was added: no e_n reaches the frozen column
 		} else if (owner) {
 			const double *x = cur + xoff;
 			double *xn = nxt + xoff;
@@ -1352,6 +1410,7 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 				const double e = a.c2 * (val[n] - dot);
 				for (int k = 0; k < K; ++k) xn[k] = xn[k] + e * y[k];
 			}
+			if (frozen >= 0) xn[frozen] = x[frozen];
 		}
 		__syncthreads();
 		double *sw = cur;
@@ -1483,6 +1542,7 @@ __global__ void __launch_bounds__(kCoopWaves *kWave) sweep_coop_kernel(SweepArgs
 			__syncthreads();
 		}
 		if (wave == 0) {
+			freeze_column<NP>(xs, lane, a.seed, a.frozen, acc);
 			double2 *__restrict__ out2 = reinterpret_cast<double2 *>(a.X_new + (size_t) r * a.ldx);
 #pragma unroll
 			for (int p = 0; p < NP; ++p) {

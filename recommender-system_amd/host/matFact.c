@@ -141,9 +141,12 @@ static int run_with_checkpoints(const mf_problem *p, double *L, double *R, int32
  * evaluated point goes to stderr; stdout is the `.out` of the iterations actually run (all of them when tol is absent).
  * With MATFACT_LAMBDA the loop runs regularised, and one more stderr line after it carries ||L||^2, ||R||^2
  * (mf_plan_penalty) and the objective SSE + lambda_users ||L||^2 + lambda_items ||R||^2 of the final factors.
+ * With MATFACT_BIAS (`biased`) the caller hands in the packed problem of K = F + 2 -- values centred with the training mean
+ * `mu`, the held-out ones too, factors packed by mf_backend_bias_pack --, the loop runs with the users' column K-1 and the
+ * items' column K-2 frozen, and one more stderr line behind the points carries mu.
  */
 static int run_with_loss(const mf_problem *p, const mf_problem *held, const double *L, const double *R, int32_t *best, int device,
-                         int every, double tol, int rank_cutoff, int regularised, double lambda_users, double lambda_items)
+                         int every, double tol, int rank_cutoff, int regularised, double lambda_users, double lambda_items, int biased, double mu)
 {
 	const int64_t nmax = p->nnz > (held ? held->nnz : 0) ? p->nnz : (held ? held->nnz : 0);
 	int32_t *row = malloc(sizeof(int32_t) * (size_t) (nmax ? nmax : 1));
@@ -163,6 +166,7 @@ static int run_with_loss(const mf_problem *p, const mf_problem *held, const doub
 	}
 	int points = 0, done = 0;
 	if (rc == MF_OK && regularised) rc = mf_plan_set_regularization(plan, lambda_users, lambda_items);
+	if (rc == MF_OK && biased) rc = mf_plan_set_frozen_columns(plan, p->features - 1, p->features - 2);
 	if (rc == MF_OK) rc = mf_plan_iterate_monitored(plan, p->iters, every, tol, trace, cap, &points, &done);
 	for (int i = 0; rc == MF_OK && i < points && i < cap; i++) {
 		fprintf(stderr, "iter %d train_rmse %.17g", trace[i].iter,
@@ -171,6 +175,7 @@ static int run_with_loss(const mf_problem *p, const mf_problem *held, const doub
 			fprintf(stderr, " heldout_rmse %.17g", sqrt(trace[i].heldout.sse / (double) trace[i].heldout.count));
 		fprintf(stderr, "\n");
 	}
+	if (rc == MF_OK && biased) fprintf(stderr, "bias mu %.17g\n", mu);
 	if (rc == MF_OK && regularised) {
 		/* MATFACT_LAMBDA: the penalty's norms of the final factors and the objective at them */
 		double lsq = 0.0, rsq = 0.0;
@@ -244,6 +249,55 @@ static void die(const char *error)
 {
 	fprintf(stderr, "Error: %s\n", error);
 	exit(-1);
+}
+
+/* MATFACT_BIAS: a copy of `p` with K = F + 2 and every value centred with `mu` (one rounding each); NULL when out of memory */
+static mf_entry *centred_entries(const mf_problem *p, double mu)
+{
+	mf_entry *e = malloc(sizeof(mf_entry) * (size_t) (p->nnz ? p->nnz : 1));
+	for (int64_t n = 0; e && n < p->nnz; n++) {
+		e[n] = p->entries[n];
+		e[n].value = p->entries[n].value - mu;
+	}
+	return e;
+}
+
+/*
+ * MATFACT_BIAS=1 with MATFACT_LOSS: the monitored loop on the packed plan.  L and R hold the reference's initialisation for
+ * K = F; the biases start at 0.0; the held-out values are centred with the TRAINING mean.
+ */
+static int run_biased_with_loss(const mf_problem *p, const mf_problem *held, const double *L, const double *R, int32_t *best, int device,
+                                int every, double tol, int rank_cutoff, int regularised, double lambda_users, double lambda_items)
+{
+	const int32_t F = p->features, K = F + 2;
+	double mu = 0.0;
+	double *val = malloc(sizeof(double) * (size_t) (p->nnz ? p->nnz : 1));
+	double *Lp = malloc(sizeof(double) * ((size_t) p->users * (size_t) K + 1));
+	double *Rp = malloc(sizeof(double) * ((size_t) p->items * (size_t) K + 1));
+	if (!val || !Lp || !Rp) return MF_ERR_NO_MEMORY;
+	for (int64_t n = 0; n < p->nnz; n++) val[n] = p->entries[n].value;
+	int rc = mf_backend_bias_mean(val, p->nnz, &mu);
+	free(val);
+	mf_problem q = *p, h;
+	q.features = K;
+	mf_entry *qe = centred_entries(p, mu), *he = NULL;
+	q.entries = qe;
+	if (held) {
+		h = *held;
+		h.features = K;
+		he = centred_entries(held, mu);
+		h.entries = he;
+	}
+	if (!qe || (held && !he)) rc = MF_ERR_NO_MEMORY;
+	if (rc == MF_OK) rc = mf_backend_bias_pack(L, NULL, p->users, F, 1, Lp);
+	if (rc == MF_OK) rc = mf_backend_bias_pack(R, NULL, p->items, F, 0, Rp);
+	if (rc == MF_OK)
+		rc = run_with_loss(&q, held ? &h : NULL, Lp, Rp, best, device, every, tol, rank_cutoff, regularised, lambda_users, lambda_items, 1, mu);
+	free(qe);
+	free(he);
+	free(Lp);
+	free(Rp);
+	return rc;
 }
 
 static double now(void)
@@ -341,6 +395,16 @@ int main(int argc, char **argv)
 			die("MATFACT_LAMBDA works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR.");
 		regularised = 1;
 	}
+	/* MATFACT_BIAS=1: the biased model a ~ mu + b_user + b_item + l.r on frozen columns (mf_backend_run_biased); the file's K
+	 * is the latent count F.  The single-GPU default path and the MATFACT_LOSS path only, with or without MATFACT_LAMBDA. */
+	int biased = 0;
+	const char *bias_env = getenv("MATFACT_BIAS");
+	if (bias_env) {
+		if (strcmp(bias_env, "1")) die("MATFACT_BIAS: expected 1.");
+		if (getenv("MATFACT_DEVICES") || getenv("MATFACT_MATS") || getenv("MATFACT_CHECKPOINT") || getenv("MATFACT_RESUME") || topn || similar)
+			die("MATFACT_BIAS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR.");
+		biased = 1;
+	}
 	const double t0 = now();
 
 	mf_problem prob;
@@ -382,9 +446,21 @@ int main(int argc, char **argv)
 		if (mf_host_checkpoint_read(getenv("MATFACT_RESUME"), &prob, &start_iter, L, R) != 0)
 			die("MATFACT_RESUME: cannot read the checkpoint or it belongs to another instance.");
 	}
-	if (loss_every) {
+	if (biased && loss_every) {
+		rc = run_biased_with_loss(&prob, have_held ? &held : NULL, L, R, best, device, loss_every, loss_tol, rank_cutoff, regularised,
+		                          lambda_users, lambda_items);
+	} else if (biased) {
+		/* biases start at 0.0; L and R took the reference's random() stream for K = F above */
+		double mu = 0.0;
+		double *bu = calloc((size_t) (prob.users > 0 ? prob.users : 1), sizeof(double));
+		double *bi = calloc((size_t) (prob.items > 0 ? prob.items : 1), sizeof(double));
+		if (!bu || !bi) die("Out of memory.");
+		rc = mf_backend_run_biased(&prob, L, R, bu, bi, &mu, best, lambda_users, lambda_items, device);
+		free(bu);
+		free(bi);
+	} else if (loss_every) {
 		rc = run_with_loss(&prob, have_held ? &held : NULL, L, R, best, device, loss_every, loss_tol, rank_cutoff, regularised,
-		                   lambda_users, lambda_items);
+		                   lambda_users, lambda_items, 0, 0.0);
 	} else if (regularised) {
 		rc = mf_backend_run_reg(&prob, L, R, best, lambda_users, lambda_items, device);
 	} else if (topn) {

@@ -85,6 +85,7 @@ int main(int argc, char **argv)
 	o.K = K;
 	o.seed = 1;
 	o.d = 1.0;
+	o.frozen = -1;
 	o.nslices = nsl;
 	o.ldx = ld;
 	o.row = drow;
