@@ -6,6 +6,9 @@
  * stdout carries ONLY the recommendations (one index per line), byte-identical to the reference's `.out`
  * files; timing goes to stderr and only when MATFACT_TIMING is set (the root-dir reference build appends a
  * `time : %f` line to stdout, benchmark.h:23; the hand-in build prints none).
+ *
+ * Top down: the options (one record, filled from the environment by one function; the combination rules are two tables),
+ * the plan session (the one place a resident plan is opened and closed) with the stages that run over it, main().
  */
 #define _POSIX_C_SOURCE 200809L
 #include "../../include/matfact_hip.h"
@@ -17,106 +20,202 @@
 #include <string.h>
 #include <time.h>
 
-/*
- * MATFACT_MATS=<path>: also write the reference's debug dump format (samples/inst{0,1,2}.mats): the dense
- * rating matrix, then L, R (printed K x I, i.e. un-transposed) and B = L R^T with "%f " per element -- initially,
- * after each of the first MATFACT_MATS_ITERS iterations (default 0; inst0.mats holds 5) and at the end.
- * Uses the resident-plan API so that every number printed comes from the GPU path.
- */
-static void mats_matrix(FILE *f, const char *title, const double *m, int rows, int cols, int transposed)
+/* Every MATFACT_* variable the program reads: the mode options in the order they are examined, the path options, and the
+ * accessories, which take part in no rule. */
+enum { V_TOPN, V_LOSS, V_HELDOUT, V_RANK, V_SIMILAR, V_SIMILAR_OUT, V_LAMBDA, V_BIAS, V_DEVICES, V_MATS, V_CHECKPOINT, V_RESUME,
+       V_DEVICE, V_MATS_ITERS, V_CHECKPOINT_EVERY, V_CACHE, V_TIMING, V_COUNT };
+static const char *const cli_names[V_COUNT] = {
+	"MATFACT_TOPN", "MATFACT_LOSS", "MATFACT_HELDOUT", "MATFACT_RANK", "MATFACT_SIMILAR", "MATFACT_SIMILAR_OUT", "MATFACT_LAMBDA",
+	"MATFACT_BIAS", "MATFACT_DEVICES", "MATFACT_MATS", "MATFACT_CHECKPOINT", "MATFACT_RESUME", "MATFACT_DEVICE",
+	"MATFACT_MATS_ITERS", "MATFACT_CHECKPOINT_EVERY", "MATFACT_CACHE", "MATFACT_TIMING"};
+
+struct cli_options {
+	/* the variable's text, NULL when unset.  Used as they are: the paths MATFACT_HELDOUT=<file.in> (a second file with the
+	 * same users and items), _SIMILAR_OUT, _MATS, _CHECKPOINT, _RESUME, and _CACHE=<dir> (binary cache of parsed inputs keyed
+	 * by the file's content; util.c:30-34 re-parses every run); MATFACT_TIMING only has to be set */
+	const char *value[V_COUNT];
+	int topn;             /* MATFACT_TOPN=N (1..MF_TOPN_MAX): N items per user on one line each instead of one (mf_host_write_topn) */
+	int loss_every;       /* MATFACT_LOSS=every[,tol]: training (with MATFACT_HELDOUT also held-out) RMSE every `every` iterations */
+	double loss_tol;      /* on stderr; with tol the run stops by the rule of mf_plan_iterate_monitored */
+	int rank_cutoff;      /* MATFACT_RANK=N (>= 1): one more stderr line with hit rate, MRR and NDCG at N of the held-out entries */
+	int similar;          /* MATFACT_SIMILAR=N[,dot|cosine] (1..MF_TOPN_MAX): the N nearest other items of every item, one line per */
+	int similar_metric;   /* item, to MATFACT_SIMILAR_OUT; cosine unless said */
+	int regularised;      /* MATFACT_LAMBDA=l[,li]: L2 regularisation, one number for both sides or users,items (finite, >= 0); */
+	double lambda_users, lambda_items;   /* with MATFACT_LOSS one more stderr line: ||L||^2, ||R||^2, the objective at the end */
+	int biased;           /* MATFACT_BIAS=1: a ~ mu + b_user + b_item + l.r on frozen columns; the file's K is the latent count F */
+	int device;           /* MATFACT_DEVICE=n: the GPU of a single-GPU run, default 0 */
+	int devs[16], ndev;   /* MATFACT_DEVICES=0,1,...: row-shard over these GPUs of the process, at most 16 */
+	const char *devices_error;   /* a non-number in it: said only where that path runs, after the input was read, as ever */
+	int mats_iters;       /* MATFACT_MATS_ITERS=n: the dump also holds the state after each of the first n iterations, default 0 */
+	int checkpoint_every; /* MATFACT_CHECKPOINT_EVERY=n: default 1000 */
+};
+
+/* a whole number from 1 to `max` at s, followed by the end of the text or by `sep`; *rest is where the number ended */
+static int whole(const char *s, long max, char sep, const char **rest, int *out)
 {
-	fprintf(f, "%s\n", title);
-	for (int i = 0; i < rows; i++) {
-		for (int j = 0; j < cols; j++)
-			fprintf(f, "%f ", transposed ? m[(size_t) j * rows + i] : m[(size_t) i * cols + j]);
-		fprintf(f, "\n");
-	}
+	char *stop;
+	const long v = strtol(s, &stop, 10);
+	*rest = stop;
+	if (stop == s || v < 1 || v > max || (*stop && *stop != sep)) return 0;
+	*out = (int) v;
+	return 1;
 }
 
-static int mats_state(FILE *f, mf_plan *plan, const mf_problem *p, double *L, double *R, double *B, int initial)
+static int number(const char *s, char sep, const char **rest, double *out)
 {
-	int rc = mf_plan_download_factors(plan, L, R);
-	if (rc == MF_OK) rc = mf_plan_predict(plan, B);
-	if (rc != MF_OK) return rc;
-	mats_matrix(f, initial ? "Initial matrix L" : "Matrix L", L, p->users, p->features, 0);
-	mats_matrix(f, initial ? "Initial matrix R" : "Matrix R", R, p->features, p->items, 1);
-	mats_matrix(f, initial ? "Initial matrix B" : "Matrix B", B, p->users, p->items, 0);
+	char *stop;
+	*out = strtod(s, &stop);
+	*rest = stop;
+	return stop != s && (!*stop || *stop == sep);
+}
+
+/* The value format of mode option `v`: fills its fields of `o` and returns NULL, or returns the message. */
+static const char *cli_value(int v, const char *s, struct cli_options *o)
+{
+	const char *rest, *bad;
+	int ok;
+	switch (v) {
+	case V_TOPN:
+		return whole(s, MF_TOPN_MAX, 0, &rest, &o->topn) ? NULL : "MATFACT_TOPN: expected a whole number from 1 to 32.";
+	case V_LOSS:
+		if (!whole(s, 2147483647L, ',', &rest, &o->loss_every)) return "MATFACT_LOSS: expected every[,tol] with every a whole number >= 1.";
+		return !*rest || number(rest + 1, 0, &rest, &o->loss_tol) ? NULL : "MATFACT_LOSS: expected every[,tol] with tol a number.";
+	case V_RANK:
+		return whole(s, 2147483647L, 0, &rest, &o->rank_cutoff) ? NULL : "MATFACT_RANK: expected a whole number >= 1.";
+	case V_SIMILAR:
+		bad = "MATFACT_SIMILAR: expected N[,dot|cosine] with N a whole number from 1 to 32.";
+		if (!whole(s, MF_TOPN_MAX, ',', &rest, &o->similar)) return bad;
+		o->similar_metric = *rest && !strcmp(rest + 1, "dot") ? MF_SIMILAR_DOT : MF_SIMILAR_COSINE;
+		return *rest && o->similar_metric == MF_SIMILAR_COSINE && strcmp(rest + 1, "cosine") ? bad : NULL;
+	case V_LAMBDA:
+		ok = number(s, ',', &rest, &o->lambda_users);
+		o->lambda_items = o->lambda_users;
+		if (ok && *rest) ok = number(rest + 1, 0, &rest, &o->lambda_items);
+		o->regularised = ok && isfinite(o->lambda_users) && isfinite(o->lambda_items) && o->lambda_users >= 0.0 && o->lambda_items >= 0.0;
+		return o->regularised ? NULL : "MATFACT_LAMBDA: expected l[,li] with l and li numbers >= 0.";
+	case V_BIAS:
+		o->biased = !strcmp(s, "1");
+		return o->biased ? NULL : "MATFACT_BIAS: expected 1.";
+	}
+	return NULL;   /* MATFACT_HELDOUT, MATFACT_SIMILAR_OUT: any text */
+}
+
+/* The combination rules.  A mode option is examined only when it is set, in the order of the enum: its value format first,
+ * then its rows of cli_needs, then its rows of cli_clashes, each in table order.  The first failure is the message. */
+#define BIT(v) (1u << (v))
+#define PATHS (BIT(V_DEVICES) | BIT(V_MATS) | BIT(V_CHECKPOINT) | BIT(V_RESUME))
+#define COUNT(a) (sizeof(a) / sizeof((a)[0]))
+struct cli_rule {
+	int var;
+	unsigned others;
+	const char *message;
+};
+/* `var` needs every one of `others` (MATFACT_SIMILAR_OUT counts only when it is not empty) */
+static const struct cli_rule cli_needs[] = {
+	{V_HELDOUT, BIT(V_LOSS), "MATFACT_HELDOUT needs MATFACT_LOSS=every[,tol]."},
+	{V_RANK, BIT(V_LOSS) | BIT(V_HELDOUT), "MATFACT_RANK needs MATFACT_HELDOUT=<file.in>."},
+	{V_SIMILAR, BIT(V_SIMILAR_OUT), "MATFACT_SIMILAR needs MATFACT_SIMILAR_OUT=<path>."},
+	{V_SIMILAR_OUT, BIT(V_SIMILAR), "MATFACT_SIMILAR_OUT needs MATFACT_SIMILAR=N[,dot|cosine]."},
+};
+/* `var` cannot be combined with any one of `others` (MATFACT_SIMILAR has two rows: it says two different things) */
+static const struct cli_rule cli_clashes[] = {
+	{V_TOPN, PATHS, "MATFACT_TOPN works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT and MATFACT_RESUME."},
+	{V_LOSS, PATHS | BIT(V_TOPN), "MATFACT_LOSS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME and MATFACT_TOPN."},
+	{V_SIMILAR, PATHS, "MATFACT_SIMILAR works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT and MATFACT_RESUME."},
+	{V_SIMILAR, BIT(V_TOPN) | BIT(V_LOSS), "MATFACT_SIMILAR cannot be combined with MATFACT_TOPN or MATFACT_LOSS."},
+	{V_LAMBDA, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_LAMBDA works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
+	{V_BIAS, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_BIAS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
+};
+
+/* Fills `o` from the environment -- it opens no file and makes no GPU call -- and returns NULL, or the message to die with. */
+static const char *cli_parse(struct cli_options *o)
+{
+	unsigned set = 0;
+	memset(o, 0, sizeof(*o));
+	for (int v = 0; v < V_COUNT; v++)
+		if ((o->value[v] = getenv(cli_names[v])) != NULL) set |= BIT(v);
+	const unsigned usable = o->value[V_SIMILAR_OUT] && !*o->value[V_SIMILAR_OUT] ? set & ~BIT(V_SIMILAR_OUT) : set;
+	for (int v = V_TOPN; v <= V_BIAS; v++) {
+		const char *message = set & BIT(v) ? cli_value(v, o->value[v], o) : NULL;
+		if (message) return message;
+		if (!(set & BIT(v))) continue;
+		for (size_t r = 0; r < COUNT(cli_needs); r++)
+			if (cli_needs[r].var == v && (usable & cli_needs[r].others) != cli_needs[r].others) return cli_needs[r].message;
+		for (size_t r = 0; r < COUNT(cli_clashes); r++)
+			if (cli_clashes[r].var == v && (set & cli_clashes[r].others)) return cli_clashes[r].message;
+	}
+	/* the accessories parse leniently */
+	o->device = o->value[V_DEVICE] ? atoi(o->value[V_DEVICE]) : 0;
+	o->mats_iters = o->value[V_MATS_ITERS] ? atoi(o->value[V_MATS_ITERS]) : 0;
+	o->checkpoint_every = o->value[V_CHECKPOINT_EVERY] ? atoi(o->value[V_CHECKPOINT_EVERY]) : 1000;
+	if (o->checkpoint_every < 1) o->checkpoint_every = 1;
+	for (const char *c = o->value[V_DEVICES]; c && *c && o->ndev < 16 && !o->devices_error;) {
+		char *stop;
+		o->devs[o->ndev++] = (int) strtol(c, &stop, 10);
+		if (stop == c) o->devices_error = "MATFACT_DEVICES: expected a comma-separated list of device ordinals.";
+		c = *stop == ',' ? stop + 1 : stop;
+	}
+	return NULL;
+}
+
+/* One resident single-GPU plan over a whole problem and the host buffers it reads: the only place that splits entries into
+ * SoA form, fills an mf_shard and creates a plan.  session_close releases everything, whatever was acquired.
+ * MATFACT_BIAS (here always next to MATFACT_LOSS) is a preparation in front of the plan: the values are centred with the
+ * training mean `mu` (one rounding each; the held-out ones later with the SAME mean), L and R -- the reference's
+ * initialisation for K = F -- are packed to K = F + 2 by mf_backend_bias_pack with the biases at 0.0. */
+struct session {
+	mf_plan *plan;
+	int32_t *row, *col, *hrow, *hcol;   /* the training entries; the held-out ones, in buffers of their own */
+	double *val, *hval;
+	double *Lp, *Rp, mu;                /* MATFACT_BIAS: the packed initial factors and the mean */
+};
+
+static int split_entries(const mf_problem *p, int32_t **row, int32_t **col, double **val)
+{
+	const size_t n = (size_t) (p->nnz ? p->nnz : 1);
+	*row = malloc(sizeof(int32_t) * n);
+	*col = malloc(sizeof(int32_t) * n);
+	*val = malloc(sizeof(double) * n);
+	if (!*row || !*col || !*val) return MF_ERR_NO_MEMORY;
+	mf_host_split_entries(p->entries, p->nnz, *row, *col, *val);
 	return MF_OK;
 }
 
-static int run_with_mats(const char *path, const mf_problem *p, double *L, double *R, int32_t *best, int device)
+static int session_open(struct session *s, const struct cli_options *o, const mf_problem *p, const double *L, const double *R)
 {
-	/* the dense A and B of the dump exist only for small instances (mf_plan_predict refuses more than 2^26 elements);
-	 * indices are checked BEFORE A is filled: the parser does not range-check them, only the device build does */
-	const size_t nb = (size_t) p->users * (size_t) p->items;
-	if (p->users < 0 || p->items < 0 || nb > ((size_t) 1 << 26)) return MF_ERR_UNSUPPORTED;
-	for (int64_t n = 0; n < p->nnz; n++)
-		if (p->entries[n].row < 0 || p->entries[n].row >= p->users || p->entries[n].col < 0 ||
-		    p->entries[n].col >= p->items)
-			return MF_ERR_ARGUMENT;
-	int rc = MF_OK;
-	FILE *f = fopen(path, "w");
-	double *B = calloc(nb ? nb : 1, sizeof(double));
-	int32_t *row = malloc(sizeof(int32_t) * (size_t) (p->nnz ? p->nnz : 1));
-	int32_t *col = malloc(sizeof(int32_t) * (size_t) (p->nnz ? p->nnz : 1));
-	double *val = malloc(sizeof(double) * (size_t) (p->nnz ? p->nnz : 1));
-	mf_plan *plan = NULL;
-	if (!f) rc = MF_ERR_ARGUMENT;
-	if (rc == MF_OK && (!B || !row || !col || !val)) rc = MF_ERR_NO_MEMORY;
-	if (rc != MF_OK) goto done;
-	mf_host_split_entries(p->entries, p->nnz, row, col, val);
-	for (int64_t n = 0; n < p->nnz; n++) B[(size_t) row[n] * p->items + col[n]] = val[n];
-	mats_matrix(f, "Initial matrix A", B, p->users, p->items, 0);
-
-	mf_shard s = {p->users, p->items, p->features, 0, p->users, p->nnz, row, col, val, p->alpha, device, 0, {0, 0}, {0, 0}, 0, 0};
-	rc = mf_plan_create(&plan, &s);
-	if (rc == MF_OK) rc = mf_plan_upload_factors(plan, L, R);
-	if (rc == MF_OK) rc = mats_state(f, plan, p, L, R, B, 1);
-	int shown = getenv("MATFACT_MATS_ITERS") ? atoi(getenv("MATFACT_MATS_ITERS")) : 0;
-	if (shown > p->iters) shown = p->iters;
-	for (int it = 0; rc == MF_OK && it < shown; it++) {
-		rc = mf_plan_iterate(plan, 1);
-		if (rc == MF_OK) {
-			fprintf(f, "Iter=%d\n", it);
-			rc = mats_state(f, plan, p, L, R, B, 0);
-		}
+	const int32_t F = p->features, K = o->biased ? F + 2 : F;
+	memset(s, 0, sizeof(*s));
+	int rc = split_entries(p, &s->row, &s->col, &s->val);
+	if (rc == MF_OK && o->biased) {
+		s->Lp = malloc(sizeof(double) * ((size_t) p->users * (size_t) K + 1));
+		s->Rp = malloc(sizeof(double) * ((size_t) p->items * (size_t) K + 1));
+		rc = s->Lp && s->Rp ? mf_backend_bias_mean(s->val, p->nnz, &s->mu) : MF_ERR_NO_MEMORY;
+		for (int64_t i = 0; rc == MF_OK && i < p->nnz; i++) s->val[i] -= s->mu;
+		if (rc == MF_OK) rc = mf_backend_bias_pack(L, NULL, p->users, F, 1, s->Lp);
+		if (rc == MF_OK) rc = mf_backend_bias_pack(R, NULL, p->items, F, 0, s->Rp);
 	}
-	if (rc == MF_OK) rc = mf_plan_iterate(plan, p->iters - shown);
-	if (rc == MF_OK) {
-		fprintf(f, "Final:\n");
-		rc = mats_state(f, plan, p, L, R, B, 0);
-	}
-	if (rc == MF_OK) rc = mf_plan_recommend(plan, best);
-done:   /* the one way out: everything that was acquired is released, whatever failed */
-	mf_plan_destroy(plan);
-	free(B);
-	free(row);
-	free(col);
-	free(val);
-	if (f && fclose(f) == EOF && rc == MF_OK) rc = MF_ERR_ARGUMENT;
+	const mf_shard shard = {.users_total = p->users, .items = p->items, .features = K, .user_begin = 0, .user_count = p->users,
+	                        .nnz = p->nnz, .row = s->row, .col = s->col, .val = s->val, .alpha = p->alpha, .device = o->device,
+	                        .flags = MF_PLAN_DEFAULT};
+	if (rc == MF_OK) rc = mf_plan_create(&s->plan, &shard);
+	if (rc == MF_OK) rc = mf_plan_upload_factors(s->plan, o->biased ? s->Lp : L, o->biased ? s->Rp : R);
 	return rc;
 }
 
-/*
- * MATFACT_CHECKPOINT=<path> [MATFACT_CHECKPOINT_EVERY=n, default 1000]: write (L, R, iterations done) every n
- * iterations; MATFACT_RESUME=<path>: start from such a file instead of the random initial factors.  The final
- * factors and recommendations are bit-identical to an uninterrupted run.
- */
-static int run_with_checkpoints(const mf_problem *p, double *L, double *R, int32_t *best, int device, int start_iter)
+static void session_close(struct session *s)
 {
-	const char *ck = getenv("MATFACT_CHECKPOINT");
-	int every = getenv("MATFACT_CHECKPOINT_EVERY") ? atoi(getenv("MATFACT_CHECKPOINT_EVERY")) : 1000;
-	if (every < 1) every = 1;
-	int32_t *row = malloc(sizeof(int32_t) * (size_t) (p->nnz ? p->nnz : 1));
-	int32_t *col = malloc(sizeof(int32_t) * (size_t) (p->nnz ? p->nnz : 1));
-	double *val = malloc(sizeof(double) * (size_t) (p->nnz ? p->nnz : 1));
-	if (!row || !col || !val) return MF_ERR_NO_MEMORY;
-	mf_host_split_entries(p->entries, p->nnz, row, col, val);
-	mf_shard s = {p->users, p->items, p->features, 0, p->users, p->nnz, row, col, val, p->alpha, device, 0, {0, 0}, {0, 0}, 0, 0};
-	mf_plan *plan = NULL;
-	int rc = mf_plan_create(&plan, &s);
-	if (rc == MF_OK) rc = mf_plan_upload_factors(plan, L, R);
-	int done = start_iter;
+	void *const owned[] = {s->row, s->col, s->val, s->hrow, s->hcol, s->hval, s->Lp, s->Rp};
+	mf_plan_destroy(s->plan);
+	for (size_t i = 0; i < COUNT(owned); i++) free(owned[i]);
+}
+
+/* MATFACT_CHECKPOINT / MATFACT_RESUME: steps that end on the multiples of checkpoint_every, (L, R, iterations done) written
+ * after each but the last.  The final factors and recommendations are bit-identical to an uninterrupted run. */
+static int loop_checkpointed(mf_plan *plan, const struct cli_options *o, const mf_problem *p, double *L, double *R, int done)
+{
+	const char *ck = o->value[V_CHECKPOINT];
+	const int every = o->checkpoint_every;
+	int rc = MF_OK;
 	while (rc == MF_OK && done < p->iters) {
 		int step = p->iters - done;
 		if (ck && step > every - done % every) step = every - done % every;
@@ -127,120 +226,165 @@ static int run_with_checkpoints(const mf_problem *p, double *L, double *R, int32
 			if (rc == MF_OK && mf_host_checkpoint_write(ck, p, done, L, R) != 0) rc = MF_ERR_ARGUMENT;
 		}
 	}
-	if (rc == MF_OK) rc = mf_plan_recommend(plan, best);
-	if (rc == MF_OK) rc = mf_plan_download_factors(plan, L, R);
-	mf_plan_destroy(plan);
-	free(row);
-	free(col);
-	free(val);
 	return rc;
 }
 
-/*
- * MATFACT_LOSS=every[,tol] [MATFACT_HELDOUT=<file.in>]: the single-GPU run through mf_plan_iterate_monitored.  One line per
- * evaluated point goes to stderr; stdout is the `.out` of the iterations actually run (all of them when tol is absent).
- * With MATFACT_LAMBDA the loop runs regularised, and one more stderr line after it carries ||L||^2, ||R||^2
- * (mf_plan_penalty) and the objective SSE + lambda_users ||L||^2 + lambda_items ||R||^2 of the final factors.
- * With MATFACT_BIAS (`biased`) the caller hands in the packed problem of K = F + 2 -- values centred with the training mean
- * `mu`, the held-out ones too, factors packed by mf_backend_bias_pack --, the loop runs with the users' column K-1 and the
- * items' column K-2 frozen, and one more stderr line behind the points carries mu.
- */
-static int run_with_loss(const mf_problem *p, const mf_problem *held, const double *L, const double *R, int32_t *best, int device,
-                         int every, double tol, int rank_cutoff, int regularised, double lambda_users, double lambda_items, int biased, double mu)
+/* MATFACT_MATS: the reference's debug dump format: the dense rating matrix, then L, R (printed K x I, i.e. un-transposed)
+ * and B = L R^T with "%f " per element -- initially, after each of the first MATFACT_MATS_ITERS iterations (inst0.mats
+ * holds 5) and at the end.  Every number printed comes from the GPU path. */
+struct dump {
+	FILE *f;
+	double *B;   /* users x items */
+};
+
+static void mats_matrix(FILE *f, const char *title, const double *m, int rows, int cols, int transposed)
 {
-	const int64_t nmax = p->nnz > (held ? held->nnz : 0) ? p->nnz : (held ? held->nnz : 0);
-	int32_t *row = malloc(sizeof(int32_t) * (size_t) (nmax ? nmax : 1));
-	int32_t *col = malloc(sizeof(int32_t) * (size_t) (nmax ? nmax : 1));
-	double *val = malloc(sizeof(double) * (size_t) (nmax ? nmax : 1));
-	const int cap = p->iters / every + 2;
-	mf_loss_point *trace = malloc(sizeof(mf_loss_point) * (size_t) cap);
-	if (!row || !col || !val || !trace) return MF_ERR_NO_MEMORY;
-	mf_host_split_entries(p->entries, p->nnz, row, col, val);
-	mf_shard s = {p->users, p->items, p->features, 0, p->users, p->nnz, row, col, val, p->alpha, device, 0, {0, 0}, {0, 0}, 0, 0};
-	mf_plan *plan = NULL;
-	int rc = mf_plan_create(&plan, &s);
-	if (rc == MF_OK) rc = mf_plan_upload_factors(plan, L, R);
-	if (rc == MF_OK && held) {
-		mf_host_split_entries(held->entries, held->nnz, row, col, val);
-		rc = mf_plan_set_heldout(plan, held->nnz, row, col, val);
+	fprintf(f, "%s\n", title);
+	for (int i = 0; i < rows; i++) {
+		for (int j = 0; j < cols; j++)
+			fprintf(f, "%f ", transposed ? m[(size_t) j * rows + i] : m[(size_t) i * cols + j]);
+		fprintf(f, "\n");
 	}
-	int points = 0, done = 0;
-	if (rc == MF_OK && regularised) rc = mf_plan_set_regularization(plan, lambda_users, lambda_items);
-	if (rc == MF_OK && biased) rc = mf_plan_set_frozen_columns(plan, p->features - 1, p->features - 2);
-	if (rc == MF_OK) rc = mf_plan_iterate_monitored(plan, p->iters, every, tol, trace, cap, &points, &done);
+}
+
+static int mats_state(const struct dump *d, mf_plan *plan, const mf_problem *p, double *L, double *R, int initial)
+{
+	int rc = mf_plan_download_factors(plan, L, R);
+	if (rc == MF_OK) rc = mf_plan_predict(plan, d->B);
+	if (rc != MF_OK) return rc;
+	mats_matrix(d->f, initial ? "Initial matrix L" : "Matrix L", L, p->users, p->features, 0);
+	mats_matrix(d->f, initial ? "Initial matrix R" : "Matrix R", R, p->features, p->items, 1);
+	mats_matrix(d->f, initial ? "Initial matrix B" : "Matrix B", d->B, p->users, p->items, 0);
+	return MF_OK;
+}
+
+static int loop_dumped(mf_plan *plan, const struct cli_options *o, const mf_problem *p, double *L, double *R, const struct dump *d)
+{
+	const int shown = o->mats_iters > p->iters ? p->iters : o->mats_iters;
+	int rc = mats_state(d, plan, p, L, R, 1);
+	for (int it = 0; rc == MF_OK && it < shown; it++) {
+		rc = mf_plan_iterate(plan, 1);
+		if (rc == MF_OK) {
+			fprintf(d->f, "Iter=%d\n", it);
+			rc = mats_state(d, plan, p, L, R, 0);
+		}
+	}
+	if (rc == MF_OK) rc = mf_plan_iterate(plan, p->iters - shown);
+	if (rc == MF_OK) {
+		fprintf(d->f, "Final:\n");
+		rc = mats_state(d, plan, p, L, R, 0);
+	}
+	return rc;
+}
+
+/* MATFACT_LAMBDA with MATFACT_LOSS: the penalty's norms of the final factors and the objective at them */
+static int report_penalty(mf_plan *plan, const struct cli_options *o)
+{
+	double lsq = 0.0, rsq = 0.0;
+	mf_loss fin;
+	int rc = mf_plan_penalty(plan, &lsq, &rsq, NULL, NULL);
+	if (rc == MF_OK) rc = mf_plan_loss(plan, MF_LOSS_TRAIN, &fin, NULL);
+	if (rc == MF_OK)
+		fprintf(stderr, "penalty lambda %.17g %.17g users_sq %.17g items_sq %.17g objective %.17g\n", o->lambda_users, o->lambda_items,
+		        lsq, rsq, (fin.sse + o->lambda_users * lsq) + o->lambda_items * rsq);
+	return rc;
+}
+
+/* MATFACT_RANK: the metrics at `cutoff` of the held-out entries' ranks; `users` are their users in the caller's order */
+static int report_ranks(mf_plan *plan, int cutoff, const int32_t *users, int64_t n)
+{
+	mf_rank_metrics m = {.hit_rate = NAN, .mrr = NAN, .ndcg = NAN};   /* an empty held-out file: nothing is evaluated */
+	int rc = MF_OK;
+	if (n > 0) {
+		int32_t *ranks = malloc(sizeof(int32_t) * (size_t) n);
+		rc = ranks ? mf_plan_rank_heldout(plan, ranks) : MF_ERR_NO_MEMORY;
+		if (rc == MF_OK) rc = mf_backend_rank_metrics(ranks, users, n, cutoff, &m);
+		free(ranks);
+	}
+	if (rc == MF_OK)
+		fprintf(stderr, "heldout_rank cutoff %d evaluated %lld masked %lld nan %lld users %lld hits %lld hit_rate %.17g mrr %.17g ndcg %.17g\n",
+		        cutoff, (long long) m.evaluated, (long long) m.masked, (long long) m.nan, (long long) m.users, (long long) m.hits,
+		        m.hit_rate, m.mrr, m.ndcg);
+	return rc;
+}
+
+/* MATFACT_SIMILAR: the neighbours of every item by the trained R, to MATFACT_SIMILAR_OUT */
+static int write_similar(mf_plan *plan, const struct cli_options *o, int32_t items)
+{
+	int32_t *near = malloc(sizeof(int32_t) * (size_t) (items > 0 ? items : 1) * (size_t) o->similar);
+	int rc = near ? mf_plan_similar_items(plan, o->similar_metric, NULL, items, o->similar, near, NULL) : MF_ERR_NO_MEMORY;
+	if (rc == MF_OK) {
+		FILE *f = fopen(o->value[V_SIMILAR_OUT], "w");
+		if (!f || mf_host_write_topn(f, near, items, o->similar) != 0) rc = MF_ERR_ARGUMENT;
+		if (f && fclose(f) == EOF) rc = MF_ERR_ARGUMENT;
+	}
+	free(near);
+	return rc;
+}
+
+/* Every mode that needs a resident plan, as stages over one session: configure, exactly one loop, the reports on stderr,
+ * the outputs.  `d` is the open dump of MATFACT_MATS or NULL; `done` counts the iterations a checkpoint already holds. */
+static int run_session(const struct cli_options *o, const mf_problem *p, const mf_problem *held, double *L, double *R, int32_t *best,
+                       int done, const struct dump *d)
+{
+	struct session s;
+	const int cap = o->loss_every ? p->iters / o->loss_every + 2 : 0;
+	mf_loss_point *trace = cap ? malloc(sizeof(mf_loss_point) * (size_t) cap) : NULL;
+	const int checkpointed = o->value[V_CHECKPOINT] || o->value[V_RESUME];
+	int points = 0;
+	int rc = session_open(&s, o, p, L, R);
+	if (rc == MF_OK && cap && !trace) rc = MF_ERR_NO_MEMORY;
+	/* configure: the held-out set, regularisation, the frozen columns of the biases */
+	if (rc == MF_OK && held) rc = split_entries(held, &s.hrow, &s.hcol, &s.hval);
+	for (int64_t i = 0; rc == MF_OK && held && o->biased && i < held->nnz; i++) s.hval[i] -= s.mu;
+	if (rc == MF_OK && held) rc = mf_plan_set_heldout(s.plan, held->nnz, s.hrow, s.hcol, s.hval);
+	if (rc == MF_OK && o->regularised) rc = mf_plan_set_regularization(s.plan, o->lambda_users, o->lambda_items);
+	if (rc == MF_OK && o->biased) rc = mf_plan_set_frozen_columns(s.plan, p->features + 1, p->features);
+	/* loop */
+	if (rc == MF_OK) {
+		if (o->loss_every) rc = mf_plan_iterate_monitored(s.plan, p->iters, o->loss_every, o->loss_tol, trace, cap, &points, &done);
+		else if (checkpointed) rc = loop_checkpointed(s.plan, o, p, L, R, done);
+		else if (d) rc = loop_dumped(s.plan, o, p, L, R, d);
+		else rc = mf_plan_iterate(s.plan, p->iters);
+	}
+	/* report: the rules allow MATFACT_BIAS, MATFACT_LAMBDA and MATFACT_RANK in a session only next to MATFACT_LOSS */
 	for (int i = 0; rc == MF_OK && i < points && i < cap; i++) {
 		fprintf(stderr, "iter %d train_rmse %.17g", trace[i].iter,
 		        trace[i].train.count > 0 ? sqrt(trace[i].train.sse / (double) trace[i].train.count) : NAN);
-		if (held && held->nnz > 0)
-			fprintf(stderr, " heldout_rmse %.17g", sqrt(trace[i].heldout.sse / (double) trace[i].heldout.count));
+		if (held && held->nnz > 0) fprintf(stderr, " heldout_rmse %.17g", sqrt(trace[i].heldout.sse / (double) trace[i].heldout.count));
 		fprintf(stderr, "\n");
 	}
-	if (rc == MF_OK && biased) fprintf(stderr, "bias mu %.17g\n", mu);
-	if (rc == MF_OK && regularised) {
-		/* MATFACT_LAMBDA: the penalty's norms of the final factors and the objective at them */
-		double lsq = 0.0, rsq = 0.0;
-		mf_loss fin;
-		rc = mf_plan_penalty(plan, &lsq, &rsq, NULL, NULL);
-		if (rc == MF_OK) rc = mf_plan_loss(plan, MF_LOSS_TRAIN, &fin, NULL);
-		if (rc == MF_OK)
-			fprintf(stderr, "penalty lambda %.17g %.17g users_sq %.17g items_sq %.17g objective %.17g\n", lambda_users, lambda_items, lsq,
-			        rsq, (fin.sse + lambda_users * lsq) + lambda_items * rsq);
-	}
-	if (rc == MF_OK && rank_cutoff && held && held->nnz > 0) {
-		/* row still holds the users of the held-out entries in the caller's order; col is free to take the ranks */
-		rc = mf_plan_rank_heldout(plan, col);
-		mf_rank_metrics m;
-		if (rc == MF_OK) rc = mf_backend_rank_metrics(col, row, held->nnz, rank_cutoff, &m);
-		if (rc == MF_OK)
-			fprintf(stderr, "heldout_rank cutoff %d evaluated %lld masked %lld nan %lld users %lld hits %lld hit_rate %.17g mrr %.17g ndcg %.17g\n",
-			        rank_cutoff, (long long) m.evaluated, (long long) m.masked, (long long) m.nan, (long long) m.users,
-			        (long long) m.hits, m.hit_rate, m.mrr, m.ndcg);
-	} else if (rc == MF_OK && rank_cutoff) {
-		fprintf(stderr, "heldout_rank cutoff %d evaluated 0 masked 0 nan 0 users 0 hits 0 hit_rate %.17g mrr %.17g ndcg %.17g\n", rank_cutoff,
-		        NAN, NAN, NAN);
-	}
-	if (rc == MF_OK) rc = mf_plan_recommend(plan, best);
-	mf_plan_destroy(plan);
-	free(row);
-	free(col);
-	free(val);
+	if (rc == MF_OK && o->biased) fprintf(stderr, "bias mu %.17g\n", s.mu);
+	if (rc == MF_OK && o->regularised) rc = report_penalty(s.plan, o);
+	if (rc == MF_OK && o->rank_cutoff) rc = report_ranks(s.plan, o->rank_cutoff, s.hrow, held->nnz);
+	/* outputs */
+	if (rc == MF_OK) rc = mf_plan_recommend(s.plan, best);
+	if (rc == MF_OK && o->similar) rc = write_similar(s.plan, o, p->items);
+	if (rc == MF_OK && checkpointed) rc = mf_plan_download_factors(s.plan, L, R);
+	session_close(&s);
 	free(trace);
 	return rc;
 }
 
-/*
- * MATFACT_SIMILAR=N[,dot|cosine] MATFACT_SIMILAR_OUT=<path>: after training, the N nearest other items of every item by
- * that metric (mf_plan_similar_items on the trained R) go to <path>, one line per item in mf_host_write_topn's format;
- * stdout is the usual `.out`.
- */
-static int run_with_similar(const mf_problem *p, const double *L, const double *R, int32_t *best, int device, int n, int metric,
-                            const char *out_path)
+/* MATFACT_MATS around the session: the dump file, its dense B and the rating matrix A, written before the plan exists */
+static int run_with_mats(const struct cli_options *o, const mf_problem *p, double *L, double *R, int32_t *best)
 {
-	int32_t *row = malloc(sizeof(int32_t) * (size_t) (p->nnz ? p->nnz : 1));
-	int32_t *col = malloc(sizeof(int32_t) * (size_t) (p->nnz ? p->nnz : 1));
-	double *val = malloc(sizeof(double) * (size_t) (p->nnz ? p->nnz : 1));
-	int32_t *near = malloc(sizeof(int32_t) * (size_t) (p->items > 0 ? p->items : 1) * (size_t) n);
-	mf_plan *plan = NULL;
-	int rc = row && col && val && near ? MF_OK : MF_ERR_NO_MEMORY;
+	/* the dense A and B of the dump exist only for small instances (mf_plan_predict refuses more than 2^26 elements);
+	 * indices are checked BEFORE A is filled: the parser does not range-check them, only the device build does */
+	const size_t nb = (size_t) p->users * (size_t) p->items;
+	if (p->users < 0 || p->items < 0 || nb > ((size_t) 1 << 26)) return MF_ERR_UNSUPPORTED;
+	for (int64_t n = 0; n < p->nnz; n++)
+		if (p->entries[n].row < 0 || p->entries[n].row >= p->users || p->entries[n].col < 0 || p->entries[n].col >= p->items)
+			return MF_ERR_ARGUMENT;
+	struct dump d = {fopen(o->value[V_MATS], "w"), calloc(nb ? nb : 1, sizeof(double))};
+	int rc = !d.f ? MF_ERR_ARGUMENT : !d.B ? MF_ERR_NO_MEMORY : MF_OK;
 	if (rc == MF_OK) {
-		mf_host_split_entries(p->entries, p->nnz, row, col, val);
-		mf_shard s = {p->users, p->items, p->features, 0, p->users, p->nnz, row, col, val, p->alpha, device, 0, {0, 0}, {0, 0}, 0, 0};
-		rc = mf_plan_create(&plan, &s);
+		for (int64_t n = 0; n < p->nnz; n++) d.B[(size_t) p->entries[n].row * p->items + p->entries[n].col] = p->entries[n].value;
+		mats_matrix(d.f, "Initial matrix A", d.B, p->users, p->items, 0);
+		rc = run_session(o, p, NULL, L, R, best, 0, &d);
 	}
-	if (rc == MF_OK) rc = mf_plan_upload_factors(plan, L, R);
-	if (rc == MF_OK) rc = mf_plan_iterate(plan, p->iters);
-	if (rc == MF_OK) rc = mf_plan_recommend(plan, best);
-	if (rc == MF_OK) rc = mf_plan_similar_items(plan, metric, NULL, p->items, n, near, NULL);
-	if (rc == MF_OK) {
-		FILE *f = fopen(out_path, "w");
-		if (!f || mf_host_write_topn(f, near, p->items, n) != 0) rc = MF_ERR_ARGUMENT;
-		if (f && fclose(f) == EOF) rc = MF_ERR_ARGUMENT;
-	}
-	mf_plan_destroy(plan);
-	free(row);
-	free(col);
-	free(val);
-	free(near);
+	free(d.B);
+	if (d.f && fclose(d.f) == EOF && rc == MF_OK) rc = MF_ERR_ARGUMENT;
 	return rc;
 }
 
@@ -249,55 +393,6 @@ static void die(const char *error)
 {
 	fprintf(stderr, "Error: %s\n", error);
 	exit(-1);
-}
-
-/* MATFACT_BIAS: a copy of `p` with K = F + 2 and every value centred with `mu` (one rounding each); NULL when out of memory */
-static mf_entry *centred_entries(const mf_problem *p, double mu)
-{
-	mf_entry *e = malloc(sizeof(mf_entry) * (size_t) (p->nnz ? p->nnz : 1));
-	for (int64_t n = 0; e && n < p->nnz; n++) {
-		e[n] = p->entries[n];
-		e[n].value = p->entries[n].value - mu;
-	}
-	return e;
-}
-
-/*
- * MATFACT_BIAS=1 with MATFACT_LOSS: the monitored loop on the packed plan.  L and R hold the reference's initialisation for
- * K = F; the biases start at 0.0; the held-out values are centred with the TRAINING mean.
- */
-static int run_biased_with_loss(const mf_problem *p, const mf_problem *held, const double *L, const double *R, int32_t *best, int device,
-                                int every, double tol, int rank_cutoff, int regularised, double lambda_users, double lambda_items)
-{
-	const int32_t F = p->features, K = F + 2;
-	double mu = 0.0;
-	double *val = malloc(sizeof(double) * (size_t) (p->nnz ? p->nnz : 1));
-	double *Lp = malloc(sizeof(double) * ((size_t) p->users * (size_t) K + 1));
-	double *Rp = malloc(sizeof(double) * ((size_t) p->items * (size_t) K + 1));
-	if (!val || !Lp || !Rp) return MF_ERR_NO_MEMORY;
-	for (int64_t n = 0; n < p->nnz; n++) val[n] = p->entries[n].value;
-	int rc = mf_backend_bias_mean(val, p->nnz, &mu);
-	free(val);
-	mf_problem q = *p, h;
-	q.features = K;
-	mf_entry *qe = centred_entries(p, mu), *he = NULL;
-	q.entries = qe;
-	if (held) {
-		h = *held;
-		h.features = K;
-		he = centred_entries(held, mu);
-		h.entries = he;
-	}
-	if (!qe || (held && !he)) rc = MF_ERR_NO_MEMORY;
-	if (rc == MF_OK) rc = mf_backend_bias_pack(L, NULL, p->users, F, 1, Lp);
-	if (rc == MF_OK) rc = mf_backend_bias_pack(R, NULL, p->items, F, 0, Rp);
-	if (rc == MF_OK)
-		rc = run_with_loss(&q, held ? &h : NULL, Lp, Rp, best, device, every, tol, rank_cutoff, regularised, lambda_users, lambda_items, 1, mu);
-	free(qe);
-	free(he);
-	free(Lp);
-	free(Rp);
-	return rc;
 }
 
 static double now(void)
@@ -313,110 +408,19 @@ int main(int argc, char **argv)
 		fprintf(stderr, "Run ./matFact.out file");   /* matFact.c:65 */
 		die("Missing input file name.");
 	}
-	/* MATFACT_TOPN=N (1..MF_TOPN_MAX): N items per user on one line each instead of one (mf_host_write_topn); the single-GPU
-	 * default path only.  Checked before the input is read: a bad value prints nothing. */
-	int topn = 0;
-	const char *topn_env = getenv("MATFACT_TOPN");
-	if (topn_env) {
-		char *stop;
-		const long v = strtol(topn_env, &stop, 10);
-		if (stop == topn_env || *stop || v < 1 || v > MF_TOPN_MAX) die("MATFACT_TOPN: expected a whole number from 1 to 32.");
-		if (getenv("MATFACT_DEVICES") || getenv("MATFACT_MATS") || getenv("MATFACT_CHECKPOINT") || getenv("MATFACT_RESUME"))
-			die("MATFACT_TOPN works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT and MATFACT_RESUME.");
-		topn = (int) v;
-	}
-	/* MATFACT_LOSS=every[,tol]: training (and, with MATFACT_HELDOUT=<file.in>, held-out) RMSE every `every` iterations on
-	 * stderr; with tol the run stops by the rule of mf_plan_iterate_monitored.  The single-GPU default path only. */
-	int loss_every = 0;
-	double loss_tol = 0.0;
-	const char *loss_env = getenv("MATFACT_LOSS");
-	if (loss_env) {
-		char *stop;
-		const long v = strtol(loss_env, &stop, 10);
-		if (stop == loss_env || v < 1 || v > 2147483647L || (*stop && *stop != ',')) die("MATFACT_LOSS: expected every[,tol] with every a whole number >= 1.");
-		if (*stop == ',') {
-			char *stop2;
-			loss_tol = strtod(stop + 1, &stop2);
-			if (stop2 == stop + 1 || *stop2) die("MATFACT_LOSS: expected every[,tol] with tol a number.");
-		}
-		if (getenv("MATFACT_DEVICES") || getenv("MATFACT_MATS") || getenv("MATFACT_CHECKPOINT") || getenv("MATFACT_RESUME") || topn)
-			die("MATFACT_LOSS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME and MATFACT_TOPN.");
-		loss_every = (int) v;
-	} else if (getenv("MATFACT_HELDOUT"))
-		die("MATFACT_HELDOUT needs MATFACT_LOSS=every[,tol].");
-	/* MATFACT_RANK=N (N >= 1) with MATFACT_LOSS and MATFACT_HELDOUT: after the monitored loop one more stderr line with the
-	 * hit rate, MRR and NDCG at N of the held-out entries' ranks (mf_plan_rank_heldout, mf_backend_rank_metrics) */
-	int rank_cutoff = 0;
-	const char *rank_env = getenv("MATFACT_RANK");
-	if (rank_env) {
-		char *stop;
-		const long v = strtol(rank_env, &stop, 10);
-		if (stop == rank_env || *stop || v < 1 || v > 2147483647L) die("MATFACT_RANK: expected a whole number >= 1.");
-		if (!loss_every || !getenv("MATFACT_HELDOUT")) die("MATFACT_RANK needs MATFACT_HELDOUT=<file.in>.");
-		rank_cutoff = (int) v;
-	}
-	/* MATFACT_SIMILAR=N[,dot|cosine] (1..MF_TOPN_MAX, default cosine) with MATFACT_SIMILAR_OUT=<path>: the N nearest other
-	 * items of every item, one line per item, to <path>; stdout is unchanged.  The single-GPU default path only. */
-	int similar = 0, similar_metric = MF_SIMILAR_COSINE;
-	const char *similar_env = getenv("MATFACT_SIMILAR");
-	if (similar_env) {
-		char *stop;
-		const long v = strtol(similar_env, &stop, 10);
-		if (stop == similar_env || v < 1 || v > MF_TOPN_MAX || (*stop && *stop != ','))
-			die("MATFACT_SIMILAR: expected N[,dot|cosine] with N a whole number from 1 to 32.");
-		if (*stop == ',') {
-			if (!strcmp(stop + 1, "dot")) similar_metric = MF_SIMILAR_DOT;
-			else if (strcmp(stop + 1, "cosine")) die("MATFACT_SIMILAR: expected N[,dot|cosine] with N a whole number from 1 to 32.");
-		}
-		if (!getenv("MATFACT_SIMILAR_OUT") || !*getenv("MATFACT_SIMILAR_OUT")) die("MATFACT_SIMILAR needs MATFACT_SIMILAR_OUT=<path>.");
-		if (getenv("MATFACT_DEVICES") || getenv("MATFACT_MATS") || getenv("MATFACT_CHECKPOINT") || getenv("MATFACT_RESUME"))
-			die("MATFACT_SIMILAR works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT and MATFACT_RESUME.");
-		if (topn || loss_every) die("MATFACT_SIMILAR cannot be combined with MATFACT_TOPN or MATFACT_LOSS.");
-		similar = (int) v;
-	} else if (getenv("MATFACT_SIMILAR_OUT"))
-		die("MATFACT_SIMILAR_OUT needs MATFACT_SIMILAR=N[,dot|cosine].");
-	/* MATFACT_LAMBDA=l[,li]: L2 regularisation, one number for both sides or users,items (mf_plan_set_regularization's
-	 * rule: finite and >= 0).  The single-GPU default path (mf_backend_run_reg) and the MATFACT_LOSS path only. */
-	int regularised = 0;
-	double lambda_users = 0.0, lambda_items = 0.0;
-	const char *lambda_env = getenv("MATFACT_LAMBDA");
-	if (lambda_env) {
-		char *stop;
-		lambda_users = lambda_items = strtod(lambda_env, &stop);
-		if (stop == lambda_env || (*stop && *stop != ',')) die("MATFACT_LAMBDA: expected l[,li] with l and li numbers >= 0.");
-		if (*stop == ',') {
-			char *stop2;
-			lambda_items = strtod(stop + 1, &stop2);
-			if (stop2 == stop + 1 || *stop2) die("MATFACT_LAMBDA: expected l[,li] with l and li numbers >= 0.");
-		}
-		if (!isfinite(lambda_users) || !isfinite(lambda_items) || lambda_users < 0.0 || lambda_items < 0.0)
-			die("MATFACT_LAMBDA: expected l[,li] with l and li numbers >= 0.");
-		if (getenv("MATFACT_DEVICES") || getenv("MATFACT_MATS") || getenv("MATFACT_CHECKPOINT") || getenv("MATFACT_RESUME") || topn || similar)
-			die("MATFACT_LAMBDA works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR.");
-		regularised = 1;
-	}
-	/* MATFACT_BIAS=1: the biased model a ~ mu + b_user + b_item + l.r on frozen columns (mf_backend_run_biased); the file's K
-	 * is the latent count F.  The single-GPU default path and the MATFACT_LOSS path only, with or without MATFACT_LAMBDA. */
-	int biased = 0;
-	const char *bias_env = getenv("MATFACT_BIAS");
-	if (bias_env) {
-		if (strcmp(bias_env, "1")) die("MATFACT_BIAS: expected 1.");
-		if (getenv("MATFACT_DEVICES") || getenv("MATFACT_MATS") || getenv("MATFACT_CHECKPOINT") || getenv("MATFACT_RESUME") || topn || similar)
-			die("MATFACT_BIAS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR.");
-		biased = 1;
-	}
+	/* every option is checked before the input is read: a refused run prints nothing on stdout */
+	struct cli_options o;
+	const char *refusal = cli_parse(&o);
+	if (refusal) die(refusal);
 	const double t0 = now();
 
-	mf_problem prob;
-	/* MATFACT_CACHE=<dir>: binary cache of parsed inputs keyed by the file's content (util.c:30-34 re-parses every
-	 * run); unset: the plain parser */
+	mf_problem prob, held;
 	int cache_hit = 0;
-	const int prc = mf_host_parse_file_cached(argv[1], getenv("MATFACT_CACHE"), &prob, &cache_hit);
+	const int prc = mf_host_parse_file_cached(argv[1], o.value[V_CACHE], &prob, &cache_hit);
 	if (prc != MF_PARSE_OK) die(mf_host_parse_strerror(prc));
-	mf_problem held;
-	const int have_held = loss_every && getenv("MATFACT_HELDOUT");
+	const int have_held = o.value[V_HELDOUT] != NULL;
 	if (have_held) {
-		const int hrc = mf_host_parse_file(getenv("MATFACT_HELDOUT"), &held);
+		const int hrc = mf_host_parse_file(o.value[V_HELDOUT], &held);
 		if (hrc != MF_PARSE_OK) die(mf_host_parse_strerror(hrc));
 		if (held.users != prob.users || held.items != prob.items) die(mf_host_parse_strerror(MF_PARSE_THREE_INTS));
 	}
@@ -424,81 +428,62 @@ int main(int argc, char **argv)
 
 	const size_t nl = (size_t) prob.users * (size_t) prob.features;
 	const size_t nr = (size_t) prob.items * (size_t) prob.features;
+	const size_t nu = (size_t) (prob.users > 0 ? prob.users : 1), ni = (size_t) (prob.items > 0 ? prob.items : 1);
 	double *L = malloc(sizeof(double) * (nl ? nl : 1));
 	double *R = malloc(sizeof(double) * (nr ? nr : 1));
-	int32_t *best = malloc(sizeof(int32_t) * (size_t) (prob.users > 0 ? prob.users : 1));
+	int32_t *best = malloc(sizeof(int32_t) * nu);
 	if (!L || !R || !best) die("Out of memory.");
 	mf_host_init_factors(prob.users, prob.items, prob.features, L, R);
 	const double t2 = now();
 
-	int32_t *topn_items = NULL;
-	if (topn) {
-		topn_items = malloc(sizeof(int32_t) * (size_t) (prob.users > 0 ? prob.users : 1) * (size_t) topn);
-		if (!topn_items) die("Out of memory.");
-	}
-
-	int device = 0;
-	if (getenv("MATFACT_DEVICE")) device = atoi(getenv("MATFACT_DEVICE"));
-	const char *mats = getenv("MATFACT_MATS");
-	const char *devlist = getenv("MATFACT_DEVICES");   /* e.g. "0,1,2,3,4,5,6,7": row-shard over these GPUs */
+	int32_t *topn_items = o.topn ? malloc(sizeof(int32_t) * nu * (size_t) o.topn) : NULL;
+	if (o.topn && !topn_items) die("Out of memory.");
 	int rc, start_iter = 0;
-	if (getenv("MATFACT_RESUME")) {
-		if (mf_host_checkpoint_read(getenv("MATFACT_RESUME"), &prob, &start_iter, L, R) != 0)
-			die("MATFACT_RESUME: cannot read the checkpoint or it belongs to another instance.");
-	}
-	if (biased && loss_every) {
-		rc = run_biased_with_loss(&prob, have_held ? &held : NULL, L, R, best, device, loss_every, loss_tol, rank_cutoff, regularised,
-		                          lambda_users, lambda_items);
-	} else if (biased) {
+	if (o.value[V_RESUME] && mf_host_checkpoint_read(o.value[V_RESUME], &prob, &start_iter, L, R) != 0)
+		die("MATFACT_RESUME: cannot read the checkpoint or it belongs to another instance.");
+	/*
+	 * The rules of cli_parse leave mode options or path options, never both.  Among the path options the priority is silent:
+	 * MATFACT_CHECKPOINT / MATFACT_RESUME win over MATFACT_MATS, which wins over MATFACT_DEVICES (and MATFACT_RESUME is read
+	 * above whenever it is set).  MATFACT_LOSS, MATFACT_SIMILAR, the checkpoints and the dump need a resident plan and run as
+	 * a session, which splits the entries once; the rest goes through the level-1 calls, which take the entries as they are.
+	 */
+	if (o.loss_every || o.similar || o.value[V_CHECKPOINT] || o.value[V_RESUME]) {
+		rc = run_session(&o, &prob, have_held ? &held : NULL, L, R, best, start_iter, NULL);
+	} else if (o.biased) {
 		/* biases start at 0.0; L and R took the reference's random() stream for K = F above */
 		double mu = 0.0;
-		double *bu = calloc((size_t) (prob.users > 0 ? prob.users : 1), sizeof(double));
-		double *bi = calloc((size_t) (prob.items > 0 ? prob.items : 1), sizeof(double));
+		double *bu = calloc(nu, sizeof(double)), *bi = calloc(ni, sizeof(double));
 		if (!bu || !bi) die("Out of memory.");
-		rc = mf_backend_run_biased(&prob, L, R, bu, bi, &mu, best, lambda_users, lambda_items, device);
+		rc = mf_backend_run_biased(&prob, L, R, bu, bi, &mu, best, o.lambda_users, o.lambda_items, o.device);
 		free(bu);
 		free(bi);
-	} else if (loss_every) {
-		rc = run_with_loss(&prob, have_held ? &held : NULL, L, R, best, device, loss_every, loss_tol, rank_cutoff, regularised,
-		                   lambda_users, lambda_items, 0, 0.0);
-	} else if (regularised) {
-		rc = mf_backend_run_reg(&prob, L, R, best, lambda_users, lambda_items, device);
-	} else if (topn) {
-		rc = mf_backend_run_topn(&prob, L, R, topn, topn_items, NULL, device);
-	} else if (similar) {
-		rc = run_with_similar(&prob, L, R, best, device, similar, similar_metric, getenv("MATFACT_SIMILAR_OUT"));
-	} else if (getenv("MATFACT_CHECKPOINT") || getenv("MATFACT_RESUME")) {
-		rc = run_with_checkpoints(&prob, L, R, best, device, start_iter);
-	} else if (mats) {
-		rc = run_with_mats(mats, &prob, L, R, best, device);
-	} else if (devlist) {
-		int devs[16], nd = 0;
-		for (const char *c = devlist; *c && nd < 16;) {
-			char *stop;
-			devs[nd++] = (int) strtol(c, &stop, 10);
-			if (stop == c) die("MATFACT_DEVICES: expected a comma-separated list of device ordinals.");
-			c = *stop == ',' ? stop + 1 : stop;
-		}
-		rc = mf_backend_run_multi(&prob, L, R, best, devs, nd);
+	} else if (o.regularised) {
+		rc = mf_backend_run_reg(&prob, L, R, best, o.lambda_users, o.lambda_items, o.device);
+	} else if (o.topn) {
+		rc = mf_backend_run_topn(&prob, L, R, o.topn, topn_items, NULL, o.device);
+	} else if (o.value[V_MATS]) {
+		rc = run_with_mats(&o, &prob, L, R, best);
+	} else if (o.value[V_DEVICES]) {
+		if (o.devices_error) die(o.devices_error);
+		rc = mf_backend_run_multi(&prob, L, R, best, o.devs, o.ndev);
 	} else {
-		rc = mf_backend_run_top1(&prob, L, R, best, device);   /* only the list is printed: no copy-back of L and R */
+		rc = mf_backend_run_top1(&prob, L, R, best, o.device);   /* only the list is printed: no copy-back of L and R */
 	}
 	if (rc != MF_OK) {
-		fprintf(stderr, "matFact (hip backend): %s %s\n", mf_backend_strerror(rc),
-		        rc == MF_ERR_HIP ? mf_backend_last_hip_error() : "");
+		fprintf(stderr, "matFact (hip backend): %s %s\n", mf_backend_strerror(rc), rc == MF_ERR_HIP ? mf_backend_last_hip_error() : "");
 		die("GPU backend failed.");
 	}
 	const double t3 = now();
 
-	if (topn)
-		mf_host_write_topn(stdout, topn_items, prob.users, topn);
+	if (o.topn)
+		mf_host_write_topn(stdout, topn_items, prob.users, o.topn);
 	else
 		mf_host_write_out(stdout, best, prob.users);
 	fflush(stdout);
 
-	if (getenv("MATFACT_TIMING"))
-		fprintf(stderr, "parse%s %.6f init %.6f gpu(run) %.6f total %.6f\n", cache_hit ? "(cache)" : "", t1 - t0, t2 - t1,
-		        t3 - t2, now() - t0);
+	if (o.value[V_TIMING])
+		fprintf(stderr, "parse%s %.6f init %.6f gpu(run) %.6f total %.6f\n", cache_hit ? "(cache)" : "", t1 - t0, t2 - t1, t3 - t2,
+		        now() - t0);
 	free(best);
 	free(topn_items);
 	free(L);

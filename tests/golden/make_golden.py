@@ -12,6 +12,8 @@ by oracle/Makefile).  Run in the build container only -- the reference does not 
   reference_special.npz signed ratings, three diverging step sizes and one that converges: the reference's L, R, B
                         after 1, 2, 3, 5, 6, 7 and 8 iterations (inf and NaN included)
   instDiverge.in/.out   one of the diverging instances as an input file, and the reference binary's stdout on it
+  cli_matrix.json       what this project's own command line answers to every combination of its MATFACT_* rule variables
+                        (`make_golden.py cli_matrix <matFact>`; needs no reference)
 
 Fixtures are data only (inputs and expected outputs); no reference source text is stored.
 """
@@ -146,8 +148,66 @@ def reference_special():
         f.write(O.ref_cli(path, "serial"))
 
 
+# the command line's option rules (tests/test_cli.py): every MATFACT_* variable that takes part in a rule, with a valid value
+CLI_VALID = [("MATFACT_TOPN", "3"), ("MATFACT_LOSS", "5"), ("MATFACT_HELDOUT", "held.in"), ("MATFACT_RANK", "10"),
+             ("MATFACT_SIMILAR", "3"), ("MATFACT_SIMILAR_OUT", "s.txt"), ("MATFACT_LAMBDA", "0.1"), ("MATFACT_BIAS", "1"),
+             ("MATFACT_DEVICES", "0"), ("MATFACT_MATS", "/dev/null"), ("MATFACT_CHECKPOINT", "x.ck"), ("MATFACT_RESUME", "x.ck")]
+# the malformed values of the per-feature refusal tests (test_topn, test_loss, test_rank, test_similar, BAD_LAMBDA of
+# test_regularised, BAD_BIAS of test_frozen) as (variable, values, the companions those tests set next to it)
+CLI_MALFORMED = [
+    ("MATFACT_TOPN", ["0", "33", "ten", "3x", ""], {}),
+    ("MATFACT_LOSS", ["0", "-3", "five", "", "5x", "5,", "5,abc"], {}),
+    ("MATFACT_RANK", ["0", "-2", "ten", "3x", ""], {"MATFACT_LOSS": "5", "MATFACT_HELDOUT": "held.in"}),
+    ("MATFACT_SIMILAR", ["0", "33", "ten", "3x", "", "3,", "3,euclid", "3,cosine,dot"], {}),
+    ("MATFACT_SIMILAR", ["3,dot"], {"MATFACT_SIMILAR_OUT": ""}),
+    ("MATFACT_SIMILAR", ["3"], {"MATFACT_SIMILAR_OUT": "s.txt", "MATFACT_LOSS": "1"}),
+    ("MATFACT_LAMBDA", ["", "abc", "-1", "-0.5,0.1", "0.1,-2", "nan", "inf", "1e999", "0.1,", "0.1,x", "0.1x", "0.1,0.2,0.3",
+                        ",0.1"], {}),
+    ("MATFACT_BIAS", ["", "0", "2", "yes", "1 ", "11", "-1", "true"], {}),
+]
+
+
+def cli_matrix_envs():
+    """The environments of cli_matrix.json: every subset of at most three of CLI_VALID (299), then CLI_MALFORMED."""
+    import itertools
+    envs = [dict(c) for k in range(4) for c in itertools.combinations(CLI_VALID, k)]
+    return envs + [dict(companions, **{name: v}) for name, values, companions in CLI_MALFORMED for v in values]
+
+
+def cli_run(cli, env, cwd):
+    """(returncode, stdout, stderr) of `cli missing.in` in the directory `cwd` with exactly `env` of the MATFACT_* variables set:
+    option and parse errors come before any GPU call, so the run ends the same way with or without a GPU"""
+    import subprocess
+    base = {k: v for k, v in os.environ.items() if not k.startswith("MATFACT_")}
+    r = subprocess.run([cli, "missing.in"], capture_output=True, cwd=cwd, env=dict(base, **env))
+    return r.returncode, r.stdout.decode(), r.stderr.decode()
+
+
+def cli_matrix(cli):
+    """cli_matrix.json: what the command line at `cli` answers to every environment of cli_matrix_envs() -- the refusal's
+    message, or the parser's on the missing input where the combination is accepted.  Each distinct stderr text is stored once."""
+    import json
+    import tempfile
+    messages, runs = [], []
+    with tempfile.TemporaryDirectory() as cwd:
+        for env in cli_matrix_envs():
+            code, out, err = cli_run(os.path.abspath(cli), env, cwd)
+            if err not in messages:
+                messages.append(err)
+            runs.append({"env": env, "returncode": code, "stdout": out, "stderr": messages.index(err)})
+        assert not os.listdir(cwd), os.listdir(cwd)
+    with open(os.path.join(HERE, "cli_matrix.json"), "w") as f:
+        f.write('{"stderr": %s,\n"runs": [\n%s\n]}\n' % (json.dumps(messages, indent=0),   # one run per line
+                                                     ",\n".join(json.dumps(r, sort_keys=True) for r in runs)))
+    print("cli_matrix.json: %d runs, %d distinct stderr texts" % (len(runs), len(messages)))
+
+
 if __name__ == "__main__":
-    # no argument: every fixture; otherwise only the parts named (main, large_inputs, reference_random, reference_special)
+    # no argument: every fixture; otherwise only the parts named (main, large_inputs, reference_random, reference_special),
+    # or `cli_matrix <path of the matFact to record from>`
+    if sys.argv[1:2] == ["cli_matrix"]:
+        cli_matrix(sys.argv[2])
+        sys.exit(0)
     for part in sys.argv[1:] or ["main"]:
         {"main": main, "large_inputs": large_inputs, "reference_random": reference_random,
          "reference_special": reference_special}[part]()
