@@ -123,7 +123,31 @@ int mf_backend_run_topn(const mf_problem *p, const double *L0, const double *R0,
  * MF_MULTI_REDUCE=rccl uses ncclAllReduce(ncclDouble, ncclSum) on a communicator made by ncclCommInitAll (needs
  * distinct devices).  The reduce runs on its own stream beside the user sweep.  devices[] lists HIP ordinals; with
  * the peer reducer an ordinal may repeat (several shards on one GPU -- how the path is tested on a one-GPU box).
- * ndev <= 16. */
+ * ndev <= 16.
+ *
+ * The result, bit for bit (peer reducer; tests/test_multi_shards.py holds the run to a numpy model of these lines):
+ *   - The cut side "A" is the users when users >= items, else the items; "B" is the other factor.  With the items cut
+ *     the roles of (row, L) and (col, R) are exchanged and nothing else changes: file order is untouched.
+ *   - Blocks.  cnt[k] = entries whose A key is < k (cnt[nkeys] = nnz).  begin[0] = 0, begin[ndev] = nkeys and, for
+ *     g = 1 .. ndev-1 in turn with ONE cursor u that starts at 0 and only moves forward: target = cnt[nkeys] * g / ndev
+ *     (integer division); while u < nkeys and cnt[u] < target, ++u; begin[g] = u.  Shard g owns the keys
+ *     [begin[g], begin[g+1]) and their entries, in file order (a stable bucketing when the file is not sorted by the A
+ *     key).  A block may be empty (begin[g] == begin[g+1]: a few heavy rows hold the entries, or nnz = 0, when every key
+ *     goes to the last shard); such a shard still sweeps, seeds if it is shard 0 and takes part in the sum.
+ *   - One iteration.  Every shard g forms, from the old A block and the old B, the new rows of its A block and its
+ *     partial P_g of B exactly as the serial program forms them over the shard's entries in file order; P_0 starts
+ *     from the old B (shard 0 seeds, whether or not it owns entries), every other P_g from +0.0.
+ *   - B_new = (((P_0 + P_1) + P_2) + ... + P_{ndev-1}), element by element in double precision, left to right in shard
+ *     order, as IEEE 754 defines the sum: NaN and infinities propagate (+inf + -inf = NaN, sign and payload of a NaN
+ *     unspecified).  The device buffers are summed whole, row padding included (the padding is +0.0 in every shard and
+ *     is not returned).  One shard adds nothing: its result is that of mf_backend_run.
+ *   - Hence, with two or more shards, an element of B that receives no entry keeps its old value -- except a -0.0,
+ *     which comes back as +0.0 ((-0.0) + 0.0); with one shard it stays -0.0.
+ *   - best[] is mf_backend_recommend of the factors this call returns, not of the serial program's: a near-tie can
+ *     resolve differently.  The result does not depend on MF_MULTI_THREADS.
+ * Errors.  ndev outside 1..16, a NULL pointer, a negative size and an entry with row outside [0, users) or col outside
+ * [0, items) give MF_ERR_ARGUMENT before the first HIP call (on a machine without a GPU too), L, R and best untouched;
+ * then a device ordinal that does not exist gives MF_ERR_NO_DEVICE.  A call after a refused one is not affected by it. */
 int mf_backend_run_multi(const mf_problem *p, double *L, double *R, int32_t *best, const int *devices, int ndev);
 /* Host wall-clock of the last mf_backend_run_multi of this process: set-up (bucketing + plan builds + uploads),
  * iterations, recommendations; info[0] = shards, info[1] = reducer (0 peer, 1 rccl), info[2] = 1 when the shards

@@ -409,16 +409,33 @@ int mf_backend_run_multi(const mf_problem *pr, double *L, double *R, int32_t *be
 		return MF_ERR_ARGUMENT;
 	const mf_config cfg = mf_config::from_env();
 	if (ndev == 1 && !cfg.multi_force) return   /* MF_MULTI_FORCE=1: the sharded path even for one shard (tests) */ mf_backend_run(pr, L, R, best, devices[0]);
+	const bool use_rccl = cfg.multi_rccl;   // MF_MULTI_REDUCE=peer (default) | rccl
+	const int U = pr->users, I = pr->items, K = pr->features;
+	const double t_count = now_s();
+	g_multi_timing = MultiTiming();
+	g_multi_timing.shards = ndev;
+	g_multi_timing.reducer = use_rccl ? 1 : 0;
+	// ---- which factor is cut?  The one with MORE rows stays private, the smaller one is replicated and summed:
+	// users >= items -> cut the users (8x1 grid); items > users -> cut the items (1x8 grid) -- the aspect-ratio
+	// rule of create_balanced_grid (mpiutil.c:54-88) and of matFact-omp's reduce_L (matFact-omp.c:44).  Cutting the
+	// items is the same computation with the roles of (row, L) and (col, R) exchanged (the plan reads the structs
+	// with row and col swapped); file order is untouched, so every per-row and per-column summation order is too.
+	const bool cut_items = I > U;
+	const int nrows_a = cut_items ? I : U, nrows_b = cut_items ? U : I;
+	double *A = cut_items ? R : L, *B = cut_items ? L : R;
+	// the counting pass is also the range check of the entries: it runs before the first HIP call, so an entry outside
+	// the matrix is MF_ERR_ARGUMENT on any machine, like the checks above
+	std::vector<int64_t> cnt;
+	std::vector<int> begin;
+	bool sorted = true;
+	int rc = count_entries(pr, cut_items, cnt, sorted);
+	if (rc != MF_OK) return rc;
+	const double counted_s = now_s() - t_count;
 	const int total = mf_backend_device_count();
 	if (total <= 0) return MF_ERR_NO_DEVICE;
 	for (int g = 0; g < ndev; ++g)
 		if (devices[g] < 0 || devices[g] >= total) return MF_ERR_NO_DEVICE;
-	const bool use_rccl = cfg.multi_rccl;   // MF_MULTI_REDUCE=peer (default) | rccl
-	const int U = pr->users, I = pr->items, K = pr->features;
-	const double t_start = now_s();
-	g_multi_timing = MultiTiming();
-	g_multi_timing.shards = ndev;
-	g_multi_timing.reducer = use_rccl ? 1 : 0;
+	const double t_start = now_s() - counted_s;   // set-up time: the counting pass and what follows the device query
 	bool distinct = true;
 	for (int g = 0; g < ndev; ++g)
 		for (int h = 0; h < g; ++h) distinct = distinct && devices[g] != devices[h];
@@ -440,19 +457,6 @@ int mf_backend_run_multi(const mf_problem *pr, double *L, double *R, int32_t *be
 					if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) MF_HIP(e);
 					(void) hipGetLastError();
 				}
-	// ---- which factor is cut?  The one with MORE rows stays private, the smaller one is replicated and summed:
-	// users >= items -> cut the users (8x1 grid); items > users -> cut the items (1x8 grid) -- the aspect-ratio
-	// rule of create_balanced_grid (mpiutil.c:54-88) and of matFact-omp's reduce_L (matFact-omp.c:44).  Cutting the
-	// items is the same computation with the roles of (row, L) and (col, R) exchanged (the plan reads the structs
-	// with row and col swapped); file order is untouched, so every per-row and per-column summation order is too.
-	const bool cut_items = I > U;
-	const int nrows_a = cut_items ? I : U, nrows_b = cut_items ? U : I;
-	double *A = cut_items ? R : L, *B = cut_items ? L : R;
-	std::vector<int64_t> cnt;
-	std::vector<int> begin;
-	bool sorted = true;
-	int rc = count_entries(pr, cut_items, cnt, sorted);
-	if (rc != MF_OK) return rc;
 	balance_blocks(cnt, ndev, begin);
 	ShardSlices sl;
 	rc = slice_entries(pr->entries, pr->nnz, cut_items, sorted, cnt, begin, sl);
