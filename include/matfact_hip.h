@@ -48,7 +48,9 @@ extern "C" {
                                           mf_plan_penalty, mf_backend_run_reg);
                                           frozen factor columns and biases (mf_plan_set_frozen_columns,
                                           mf_plan_get_frozen_columns, mf_backend_bias_mean, mf_backend_bias_pack,
-                                          mf_backend_bias_unpack, mf_backend_run_biased) */
+                                          mf_backend_bias_unpack, mf_backend_run_biased);
+                                          heavy-ball momentum (mf_plan_set_momentum, mf_plan_get_momentum,
+                                          mf_plan_upload_previous, mf_plan_download_previous, mf_backend_run_momentum) */
 
 /* == non_zero_entry, datatypes.h:10-15: the (user, item, rating) triple, 16 bytes, array-of-structs */
 typedef struct mf_entry {
@@ -432,6 +434,44 @@ int mf_backend_bias_unpack(const double *in, int32_t rows, int32_t F, int side, 
  * the largest supported K (4096) -> MF_ERR_UNSUPPORTED. */
 int mf_backend_run_biased(const mf_problem *p, double *L, double *R, double *user_bias, double *item_bias, double *mu,
                           int32_t *best, double lambda_users, double lambda_items, int device);
+
+/* ---- Heavy-ball momentum: the step of a side also carries beta times its previous step.  An extension (the reference
+ * has none), so the definition is this library's; it fixes every rounding.  Per side, beta is finite and >= 0 and defaults
+ * to 0.  For a seeded sweep of side X with beta != 0, for every row r of the launch and every column k that is not the
+ * side's frozen column:
+ *   v    = X_old[r][k] - X_prev[r][k]          one rounded subtraction
+ *   m    = beta * v                            one rounded multiply
+ *   seed = (X_old[r][k] * d) + m               the decay's multiply, then one rounded add; nothing fused
+ *   X_new[r][k] = (...((seed + e_0*Y[idx_0][k]) + e_1*Y[idx_1][k]) + ...)      unchanged
+ * e_n and dot_n are unchanged: they see X_old and Y_old only.  A frozen column keeps X_old's bits (0.0 unseeded): neither
+ * decay nor momentum reaches it.  An unseeded sweep starts from 0.0 and takes no momentum: in a sharded or tiled run the
+ * root that seeds applies it once, like the decay.  With beta == 0 the term is absent -- not "+ 0.0": the bits are those
+ * without momentum, and a plan with both betas at 0 launches the same kernels as before.  Nothing is special-cased:
+ * inf - inf is NaN, subnormals and signed zeros follow IEEE 754.  One consequence: a -0.0 element that moves under momentum
+ * from rest comes out of the seed as +0.0, because (-0.0 * d) + (+0.0) is +0.0.
+ *
+ * X_prev is the side's history: the content of the side's next-generation buffer (mf_plan_users_next / mf_plan_items_next)
+ * at launch -- after a seeded sweep and a flip, the generation before X_old.  The exception is a side AT REST: there
+ * X_prev = X_old by definition, so v = x - x.  A side is at rest after mf_plan_upload_factors, and after
+ * mf_plan_set_momentum changes its beta from 0 to non-zero (a plain run maintains no history); it leaves rest with its first
+ * seeded momentum sweep (the library then copies current -> next in front of the launch) or with mf_plan_upload_previous.
+ * A change between two non-zero betas keeps the history.  beta >= 1 is the caller's business, like a negative d.
+ * mf_plan_set_momentum: NaN, infinite or negative beta -> MF_ERR_ARGUMENT before any HIP call and nothing changes; legal
+ * at any time, before the upload too; read at every launch, for every way the plan iterates (mf_plan_iterate,
+ * mf_plan_iterate_monitored, mf_plan_sweep_items, mf_plan_sweep_users[_seeded]).  mf_backend_run_multi does not use
+ * momentum.  mf_plan_describe appends momentum=<users>/<items> when either is non-zero. */
+int mf_plan_set_momentum(mf_plan *plan, double beta_users, double beta_items);
+int mf_plan_get_momentum(mf_plan *plan, double *beta_users, double *beta_items);   /* either may be NULL */
+/* The previous generation, host <-> the next-generation buffers, on the plan's stream, rows K doubles apart on the host
+ * like mf_plan_upload_factors.  Upload: either pointer may be NULL, which leaves that side alone; a side given is no
+ * longer at rest.  Download: the inverse; a side at rest returns its current factors; either pointer may be NULL.  No
+ * factors: MF_ERR_STATE.  With the two, a momentum run resumes bit for bit: download the current and the previous
+ * generation, and later upload both into a plan with the same betas. */
+int mf_plan_upload_previous(mf_plan *plan, const double *L_prev_block, const double *R_prev);
+int mf_plan_download_previous(mf_plan *plan, double *L_prev_block, double *R_prev);
+/* level 1: mf_backend_run_reg with momentum, from rest.  A bad lambda or beta -> MF_ERR_ARGUMENT before any HIP call. */
+int mf_backend_run_momentum(const mf_problem *p, double *L, double *R, int32_t *best, double lambda_users, double lambda_items,
+                            double beta_users, double beta_items, int device);
 
 /* ---- Ranks of the held-out entries: where each held-out item lands in its user's recommendation order, for the plan's
  * current factors.  An extension (the reference ranks nothing), so the definition is this library's.  For held-out entry

@@ -48,6 +48,8 @@ HIP_SYMBOLS = [
     "mf_plan_set_regularization", "mf_plan_get_regularization", "mf_plan_penalty", "mf_backend_run_reg",
     "mf_plan_set_frozen_columns", "mf_plan_get_frozen_columns", "mf_backend_bias_mean", "mf_backend_bias_pack",
     "mf_backend_bias_unpack", "mf_backend_run_biased",
+    "mf_plan_set_momentum", "mf_plan_get_momentum", "mf_plan_upload_previous", "mf_plan_download_previous",
+    "mf_backend_run_momentum",
 ]
 HOST_SYMBOLS = [
     "mf_host_parse_strerror", "mf_host_parse_file", "mf_host_parse_buffer", "mf_host_free_problem",
@@ -205,6 +207,12 @@ def hip():
         lib.mf_backend_bias_unpack.argtypes = [P, C.c_int32, C.c_int32, C.c_int, P, P]
         lib.mf_backend_run_biased.argtypes = [C.POINTER(Problem), _f64p, _f64p, _f64p, _f64p, C.POINTER(C.c_double), P,
                                               C.c_double, C.c_double, C.c_int]
+        lib.mf_plan_set_momentum.argtypes = [P, C.c_double, C.c_double]
+        lib.mf_plan_get_momentum.argtypes = [P, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        lib.mf_plan_upload_previous.argtypes = [P, P, P]
+        lib.mf_plan_download_previous.argtypes = [P, P, P]
+        lib.mf_backend_run_momentum.argtypes = [C.POINTER(Problem), _f64p, _f64p, P, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                C.c_int]
         _hip = lib
     return _hip
 
@@ -435,6 +443,20 @@ def backend_run_reg(inst, L, R, lambda_users, lambda_items=None, iters=None, dev
     _check(hip().mf_backend_run_reg(C.byref(p), L, R, best.ctypes.data if recommend else None, float(lambda_users), float(li),
                                     device), "mf_backend_run_reg")
     return best
+
+
+def backend_run_momentum(inst, L, R, lambda_users, lambda_items, beta_users, beta_items=None, iters=None, device=0, recommend=True):
+    """mf_backend_run_momentum: backend_run_reg with heavy-ball momentum from rest (one beta means both sides); L, R updated
+    in place, returns best[users], or None with recommend=False."""
+    p, keep = _problem(inst, iters)
+    bi = beta_users if beta_items is None else beta_items
+    best = np.empty(inst.users, np.int32) if recommend else None
+    _check(hip().mf_backend_run_momentum(C.byref(p), L, R, best.ctypes.data if recommend else None, float(lambda_users),
+                                         float(lambda_items), float(beta_users), float(bi), device), "mf_backend_run_momentum")
+    return best
+
+
+run_momentum = backend_run_momentum
 
 
 def bias_mean(val):
@@ -686,6 +708,35 @@ class Plan:
         u, i = C.c_double(), C.c_double()
         _check(hip().mf_plan_get_regularization(self._h, C.byref(u), C.byref(i)), "mf_plan_get_regularization")
         return u.value, i.value
+
+    def set_momentum(self, users, items=None):
+        """mf_plan_set_momentum: heavy-ball beta of the user and the item side (one value means both), read at every launch.
+        A side whose beta leaves 0 is at rest: its first step sees X_prev = X_old."""
+        _check(hip().mf_plan_set_momentum(self._h, float(users), float(users if items is None else items)), "mf_plan_set_momentum")
+
+    def momentum(self):
+        """(beta_users, beta_items) in force"""
+        u, i = C.c_double(), C.c_double()
+        _check(hip().mf_plan_get_momentum(self._h, C.byref(u), C.byref(i)), "mf_plan_get_momentum")
+        return u.value, i.value
+
+    def upload_previous(self, L_prev_block=None, R_prev=None):
+        """mf_plan_upload_previous: the generation before the current one, into the next-generation buffers; None leaves
+        that side alone.  A side given is no longer at rest."""
+        Lp = None if L_prev_block is None else np.ascontiguousarray(L_prev_block, np.float64)
+        Rp = None if R_prev is None else np.ascontiguousarray(R_prev, np.float64)
+        assert Lp is None or Lp.shape == (self.user_count, self.feats)
+        assert Rp is None or Rp.shape == (self.items, self.feats)
+        _check(hip().mf_plan_upload_previous(self._h, None if Lp is None else Lp.ctypes.data, None if Rp is None else Rp.ctypes.data),
+               "mf_plan_upload_previous")
+
+    def download_previous(self, want_l=True, want_r=True):
+        """mf_plan_download_previous: (L_prev_block, R_prev); a side at rest returns its current factors"""
+        Lb = np.empty((self.user_count, self.feats), np.float64) if want_l else None
+        R = np.empty((self.items, self.feats), np.float64) if want_r else None
+        _check(hip().mf_plan_download_previous(self._h, Lb.ctypes.data if want_l else None, R.ctypes.data if want_r else None),
+               "mf_plan_download_previous")
+        return Lb, R
 
     def set_frozen_columns(self, users, items):
         """mf_plan_set_frozen_columns: the column of L and of R that the sweeps leave alone (-1: none), in force from the

@@ -428,6 +428,7 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 	if (s.coop.nch) {
 		p->coop = SweepForm{p->sweep.coop, s.coop.nch, s.coop.lds, mf::kCoopWaves * mf::kWave};
 		MF_HIP(raise_lds_limit((const void *) p->coop.fn, p->coop.lds));
+		if (p->sweep.coop_mom) MF_HIP(raise_lds_limit((const void *) p->sweep.coop_mom, p->coop.lds));
 	}
 	if (s.extreme) {
 		p->prod = SweepForm{p->sweep.prod, s.prod_nch, s.prod_lds, mf::kWave};
@@ -489,6 +490,7 @@ int plan_es_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vector
 	if (p->res_nwg > 0) {
 		MF_TRY(upload(p, p->res_wg, wgs));
 		MF_HIP(raise_lds_limit(stream_resident_fn(p->res_sw), p->res_lds));
+		MF_HIP(raise_lds_limit(stream_resident_fn(p->res_sw, true), p->res_lds));
 	}
 	p->es_mode = true;
 	return MF_OK;

@@ -230,6 +230,42 @@ int mf_plan_upload_factors(mf_plan *p, const double *L_block, const double *R)
 		                        hipMemcpyHostToDevice, p->stream));
 	MF_HIP(hipStreamSynchronize(p->stream));
 	p->have_factors = true;
+	p->at_rest[0] = p->at_rest[1] = true;   // new factors have no history
+	return MF_OK;
+}
+
+int mf_plan_upload_previous(mf_plan *p, const double *L_prev_block, const double *R_prev)
+{
+	if (!p) return MF_ERR_ARGUMENT;
+	if (!p->have_factors) return MF_ERR_STATE;
+	MF_HIP(hipSetDevice(p->device));
+	const size_t w = (size_t) p->K * sizeof(double);
+	if (L_prev_block && p->uc)
+		MF_HIP(hipMemcpy2DAsync(p->Lbuf[p->cur ^ 1], (size_t) p->ldl * sizeof(double), L_prev_block, w, w, (size_t) p->uc,
+		                        hipMemcpyHostToDevice, p->stream));
+	if (R_prev && p->items)
+		MF_HIP(hipMemcpy2DAsync(p->Rbuf[p->cur ^ 1], (size_t) p->ldr * sizeof(double), R_prev, w, w, (size_t) p->items,
+		                        hipMemcpyHostToDevice, p->stream));
+	MF_HIP(hipStreamSynchronize(p->stream));
+	if (L_prev_block) p->at_rest[1] = false;
+	if (R_prev) p->at_rest[0] = false;
+	return MF_OK;
+}
+
+int mf_plan_download_previous(mf_plan *p, double *L_prev_block, double *R_prev)
+{
+	if (!p) return MF_ERR_ARGUMENT;
+	if (!p->have_factors) return MF_ERR_STATE;
+	MF_HIP(hipSetDevice(p->device));
+	const size_t w = (size_t) p->K * sizeof(double);
+	// a side at rest has no history of its own: X_prev = X_old
+	if (L_prev_block && p->uc)
+		MF_HIP(hipMemcpy2DAsync(L_prev_block, w, p->Lbuf[p->at_rest[1] ? p->cur : p->cur ^ 1], (size_t) p->ldl * sizeof(double), w,
+		                        (size_t) p->uc, hipMemcpyDeviceToHost, p->stream));
+	if (R_prev && p->items)
+		MF_HIP(hipMemcpy2DAsync(R_prev, w, p->Rbuf[p->at_rest[0] ? p->cur : p->cur ^ 1], (size_t) p->ldr * sizeof(double), w,
+		                        (size_t) p->items, hipMemcpyDeviceToHost, p->stream));
+	MF_HIP(hipStreamSynchronize(p->stream));
 	return MF_OK;
 }
 
@@ -311,6 +347,11 @@ int mf_plan_iterate(mf_plan *p, int iters)
 	if (!p || iters < 0) return MF_ERR_ARGUMENT;
 	if (!p->have_factors) return MF_ERR_STATE;
 	MF_HIP(hipSetDevice(p->device));
+	// a momentum side at rest gets its history (X_prev = X_old) here: in front of every launch and outside the capture
+	if (iters > 0) {
+		MF_TRY(leave_rest(p, 0));
+		MF_TRY(leave_rest(p, 1));
+	}
 	// Launch-bound regime (inst1: 100000 iterations of a 13-entry instance, ~4 us per launch): capture an even
 	// number of iterations -- so the ping-pong parity returns to where it started -- into a HIP graph and replay it.
 	// Only for small sweeps; a large sweep is not launch-bound and a graph would pin its arguments for nothing.
@@ -350,12 +391,27 @@ int mf_plan_iterate(mf_plan *p, int iters)
 			ra.L_out = p->Lbuf[fin];
 			ra.R_out = p->Rbuf[fin];
 			ra.nnz = (int) p->nnz;
+			// momentum: the next-generation buffers carry the history in; the generation before the final one goes out to
+			// the buffers the final one does not take
+			ra.beta_users = p->beta[1];
+			ra.beta_items = p->beta[0];
+			ra.L_hist = p->Lbuf[p->cur ^ 1];
+			ra.R_hist = p->Rbuf[p->cur ^ 1];
+			ra.L_prev = p->Lbuf[fin ^ 1];
+			ra.R_prev = p->Rbuf[fin ^ 1];
+			const bool momentum = p->beta[0] != 0.0 || p->beta[1] != 0.0;
 			const int threads = ((p->uc + p->items + 63) / 64) * 64;
 			void (*rfn)(mf::ResidentArgs) = p->K <= 4    ? mf::sweep_resident_kernel<4>
 			                                : p->K <= 16 ? mf::sweep_resident_kernel<16>
 			                                : p->K <= 32 && threads <= mf::resident_max_threads(32)
 			                                    ? mf::sweep_resident_kernel<32>
 			                                    : mf::sweep_resident_kernel<0>;
+			if (momentum)
+				rfn = p->K <= 4    ? mf::sweep_resident_kernel<4, true>
+				      : p->K <= 16 ? mf::sweep_resident_kernel<16, true>
+				      : p->K <= 32 && threads <= mf::resident_max_threads(32)
+				          ? mf::sweep_resident_kernel<32, true>
+				          : mf::sweep_resident_kernel<0, true>;
 			MF_HIP(raise_lds_limit((const void *) rfn, need));
 			hipLaunchKernelGGL(rfn, dim3(1), dim3(threads), need, p->stream, ra);
 			MF_HIP(hipGetLastError());
@@ -411,6 +467,26 @@ int mf_plan_get_regularization(mf_plan *p, double *lambda_users, double *lambda_
 	if (!p) return MF_ERR_ARGUMENT;
 	if (lambda_users) *lambda_users = p->lambda[1];
 	if (lambda_items) *lambda_items = p->lambda[0];
+	return MF_OK;
+}
+
+int mf_plan_set_momentum(mf_plan *p, double beta_users, double beta_items)
+{
+	if (!p || !lambda_ok(beta_users) || !lambda_ok(beta_items)) return MF_ERR_ARGUMENT;   // finite and >= 0, like a weight
+	// read at every launch (the graph path captures per call).  A side whose beta leaves 0 has maintained no history: it
+	// is at rest; a change between two non-zero values keeps the history
+	if (p->beta[1] == 0.0 && beta_users != 0.0) p->at_rest[1] = true;
+	if (p->beta[0] == 0.0 && beta_items != 0.0) p->at_rest[0] = true;
+	p->beta[1] = beta_users;
+	p->beta[0] = beta_items;
+	return MF_OK;
+}
+
+int mf_plan_get_momentum(mf_plan *p, double *beta_users, double *beta_items)
+{
+	if (!p) return MF_ERR_ARGUMENT;
+	if (beta_users) *beta_users = p->beta[1];
+	if (beta_items) *beta_items = p->beta[0];
 	return MF_OK;
 }
 
@@ -712,6 +788,11 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 		const size_t at = strlen(buf);
 		if (at + 1 < (size_t) buflen) snprintf(buf + at, (size_t) buflen - at, " lambda=%g/%g", p->lambda[1], p->lambda[0]);
 	}
+	// the momentum in force, when there is any
+	if (p->beta[0] != 0.0 || p->beta[1] != 0.0) {
+		const size_t at = strlen(buf);
+		if (at + 1 < (size_t) buflen) snprintf(buf + at, (size_t) buflen - at, " momentum=%g/%g", p->beta[1], p->beta[0]);
+	}
 	// the frozen columns in force, when there is one
 	if (p->frozen[0] >= 0 || p->frozen[1] >= 0) {
 		const size_t at = strlen(buf);
@@ -770,6 +851,21 @@ int mf_backend_run_reg(const mf_problem *pr, double *L, double *R, int32_t *best
 	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items)) return MF_ERR_ARGUMENT;
 	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
 		int rc = mf_plan_set_regularization(p, lambda_users, lambda_items);
+		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
+		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
+		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
+		return rc;
+	});
+}
+
+int mf_backend_run_momentum(const mf_problem *pr, double *L, double *R, int32_t *best, double lambda_users, double lambda_items,
+                            double beta_users, double beta_items, int device)
+{
+	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !lambda_ok(beta_users) || !lambda_ok(beta_items))
+		return MF_ERR_ARGUMENT;
+	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
+		int rc = mf_plan_set_regularization(p, lambda_users, lambda_items);
+		if (rc == MF_OK) rc = mf_plan_set_momentum(p, beta_users, beta_items);
 		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
 		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
 		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);

@@ -100,8 +100,10 @@ const void *ordered_sum_fn(const mf_config &cfg)
 {
 	return cfg.os_dpp ? (const void *) mf::ordered_sum_kernel<true> : (const void *) mf::ordered_sum_kernel<false>;
 }
-const void *stream_resident_fn(int sw)
+const void *stream_resident_fn(int sw, bool momentum = false)
 {
+	if (momentum)
+		return sw == 8 ? (const void *) mf::stream_resident_kernel<8, true> : sw == 4 ? (const void *) mf::stream_resident_kernel<4, true> : (const void *) mf::stream_resident_kernel<2, true>;
 	return sw == 8 ? (const void *) mf::stream_resident_kernel<8> : sw == 4 ? (const void *) mf::stream_resident_kernel<4> : (const void *) mf::stream_resident_kernel<2>;
 }
 
@@ -141,6 +143,8 @@ int choose_sweep(mf_plan *p)
 	if (p->sweep.pf) MF_HIP(raise_lds_limit((const void *) p->sweep.pf, std::max(p->single.lds, p->few.lds)));
 	if (p->sweep.fn_decay) MF_HIP(raise_lds_limit((const void *) p->sweep.fn_decay, std::max(p->single.lds, p->few.lds)));
 	if (p->sweep.pf_decay) MF_HIP(raise_lds_limit((const void *) p->sweep.pf_decay, std::max(p->single.lds, p->few.lds)));
+	if (p->sweep.fn_mom) MF_HIP(raise_lds_limit((const void *) p->sweep.fn_mom, std::max(p->single.lds, p->few.lds)));
+	if (p->sweep.pf_mom) MF_HIP(raise_lds_limit((const void *) p->sweep.pf_mom, std::max(p->single.lds, p->few.lds)));
 	// the two-tile forms: `dflt` entries per chunk (MF_SWEEP_NCH overrides) while two tiles stay within half a CU's LDS
 	auto two_tiles = [&](SweepFn fn, int dflt, int block) {
 		int n = p->cfg.sweep_nch ? p->cfg.sweep_nch : dflt;
@@ -152,10 +156,12 @@ int choose_sweep(mf_plan *p)
 		// paid per chunk -- a lone 5993-entry row: 0.526 ms at 16, 0.332 at 32; cfg3 power-law 0.311 / 0.268 / 0.314 at 24 / 32 / 40
 		p->pair = two_tiles(p->sweep.pair, 32, 2 * mf::kWave);
 		MF_HIP(raise_lds_limit((const void *) p->pair.fn, p->pair.lds));
+		if (p->sweep.pair_mom) MF_HIP(raise_lds_limit((const void *) p->sweep.pair_mom, p->pair.lds));
 	}
 	if (p->sweep.db) {   // double-buffered form (few rows per CU: the wave hides its own gather)
 		p->db = two_tiles(p->sweep.db, 16, mf::kWave);
 		MF_HIP(raise_lds_limit((const void *) p->db.fn, p->db.lds));
+		if (p->sweep.db_mom) MF_HIP(raise_lds_limit((const void *) p->sweep.db_mom, p->db.lds));
 	}
 	// ---- errors + streams iteration (mf_stream.hip.h) for instances whose factors stay in L2 / Infinity Cache: the
 	// two sweeps are then bound by the latency of one wave walking a row chunk by chunk, not by bandwidth.  It costs a
@@ -208,9 +214,23 @@ bool single_wave_pipelined(const mf_plan *p, int kind)
 // The form of the main launch of one side (kind 0: items, 1: users): the cooperative launch of a tiny sweep, the
 // double-buffered or the wave-pair form where plan_row_schedule chose one, else the single-wave form -- plain or
 // pipelined by single_wave_pipelined, at the large chunk when `few_rows`.
-SweepForm main_form(const mf_plan *p, int kind, bool few_rows, bool decay)
+// `momentum`: the launch is a seeded sweep of a side with beta != 0 -- every form then runs its momentum instance (null
+// where a K has none: launch_sweep refuses); without it the choice and the kernels are those of a plan without momentum.
+SweepForm main_form(const mf_plan *p, int kind, bool few_rows, bool decay, bool momentum)
 {
 	const SweepSide &sd = p->side[kind];
+	if (momentum) {
+		SweepForm f = main_form(p, kind, few_rows, decay, false);
+		if (sd.coop_all)
+			f.fn = p->sweep.coop_mom;
+		else if (sd.use_db)
+			f.fn = p->sweep.db_mom;
+		else if (sd.use_pair)
+			f.fn = p->sweep.pair_mom;
+		else
+			f.fn = p->sweep.dma && single_wave_pipelined(p, kind) ? p->sweep.pf_mom : p->sweep.fn_mom;
+		return f;
+	}
 	if (sd.coop_all) {
 		// A cooperative launch of kSweepFewRows rows or more runs at the single-wave chunk size with the cooperative LDS request,
 		// as it always has.  Known and left for a change of its own, with a test: at K = 30 and K = 50 that request is sized
@@ -243,6 +263,24 @@ double side_decay(const mf_plan *p, int kind)
 	return 1.0 - t;
 }
 
+// Heavy-ball momentum of a launch (kind 0: items, 1: users): the side's beta for a seeded sweep, 0.0 -- no term, today's
+// kernels -- for an unseeded one.  Read at every launch, like the decay.
+double side_momentum(const mf_plan *p, int kind, int seed) { return seed ? p->beta[kind] : 0.0; }
+
+// A side at rest that is about to run a seeded momentum sweep: X_prev = X_old by definition, literally -- one device copy
+// current -> next over rows x pitch on the plan's stream, and the side has a history.  mf_plan_iterate calls it before it
+// captures or launches anything, so no graph and no kernel sees a special first step.
+int leave_rest(mf_plan *p, int kind)
+{
+	if (!p->at_rest[kind] || p->beta[kind] == 0.0) return MF_OK;
+	const int rows = kind == 0 ? p->items : p->uc, ld = kind == 0 ? p->ldr : p->ldl;
+	double *const *buf = kind == 0 ? p->Rbuf : p->Lbuf;
+	if (rows > 0)
+		MF_HIP(hipMemcpyAsync(buf[p->cur ^ 1], buf[p->cur], (size_t) rows * ld * sizeof(double), hipMemcpyDeviceToDevice, p->stream));
+	p->at_rest[kind] = false;
+	return MF_OK;
+}
+
 // defer_join: leave the ordered sums of the extreme rows running on the side stream when the call returns
 // (p->join_pending); the caller joins before anything reads the new generation.
 int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
@@ -257,6 +295,9 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	a.c2 = p->alpha * 2;
 	a.d = side_decay(p, kind);
 	a.frozen = p->frozen[kind];   // read at every launch, like the decay: a captured graph is built per call
+	a.beta = side_momentum(p, kind, seed);
+	const bool momentum = a.beta != 0.0;
+	if (momentum) MF_TRY(leave_rest(p, kind));
 	a.ldx = x.ldx;
 	a.ldy = x.ldy;
 	a.nrows = sd.nrows;
@@ -275,7 +316,7 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	const bool extreme = sd.n_long > 0;
 	// the large chunk below kSweepFewRows rows.  Never beside the extreme-row path: with the extreme rows gone the
 	// occupancy-friendly chunk size is right again.
-	const SweepForm f = main_form(p, kind, !extreme && a.nrows < kSweepFewRows, a.d != 1.0 || a.frozen >= 0);
+	const SweepForm f = main_form(p, kind, !extreme && a.nrows < kSweepFewRows, a.d != 1.0 || a.frozen >= 0, momentum);
 	if (!f.fn) return MF_ERR_UNSUPPORTED;
 	a.nch = f.nch;
 	TimedLaunch t{};
@@ -323,6 +364,23 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 		MF_HIP(hipEventRecord(p->ev_fork, p->stream));
 		MF_HIP(hipStreamWaitEvent(p->side_stream, p->ev_fork, 0));
 		MF_HIP(hipLaunchKernel((const void *) p->prod.fn, dim3(b.nrows), dim3(p->prod.block), bargs, p->prod.lds, p->side_stream));
+		if (momentum) {
+			// the finished seeds of the extreme rows go into their X_new rows, and the ordered sum starts from those
+			mf::SeedPrepArgs s;
+			s.nrows = sd.n_long;
+			s.K = p->K;
+			s.ldx = a.ldx;
+			s.frozen = a.frozen;
+			s.d = a.d;
+			s.beta = a.beta;
+			s.row = sd.long_rows;
+			s.X_old = a.X_old;
+			s.X_new = a.X_new;
+			void *sargs[] = {&s};
+			MF_HIP(hipLaunchKernel((const void *) mf::momentum_seed_kernel, dim3(s.nrows), dim3(mf::kWave), sargs, 0, p->side_stream));
+			o.X_old = a.X_new;
+			o.d = 1.0;
+		}
 		MF_HIP(hipLaunchKernel(ordered_sum_fn(p->cfg), dim3(o.nrows * o.nslices), dim3(mf::kWave), oargs, p->lds_bytes_osum, p->side_stream));
 		MF_HIP(hipEventRecord(p->ev_join, p->side_stream));
 		a.nrows = sd.n_short;
@@ -384,6 +442,12 @@ int launch_es_iteration(mf_plan *p)
 		ra.ldy[side] = x.ldy;
 		ra.d[side] = side_decay(p, side);
 		ra.frozen[side] = p->frozen[side];
+		ra.beta[side] = p->beta[side];
+	}
+	const bool momentum = ra.beta[0] != 0.0 || ra.beta[1] != 0.0;
+	if (momentum) {
+		MF_TRY(leave_rest(p, 0));
+		MF_TRY(leave_rest(p, 1));
 	}
 	TimedLaunch t0{}, t1{};
 	if (p->timing) {
@@ -400,7 +464,7 @@ int launch_es_iteration(mf_plan *p)
 	if (p->timing) MF_HIP(hipEventRecord(t0.t1, p->stream));
 	{
 		void *rargs[] = {&ra};
-		MF_HIP(hipLaunchKernel(stream_resident_fn(p->res_sw), dim3(p->res_nwg), dim3(mf::kResidentThreads), rargs, p->res_lds, p->stream));
+		MF_HIP(hipLaunchKernel(stream_resident_fn(p->res_sw, momentum), dim3(p->res_nwg), dim3(mf::kResidentThreads), rargs, p->res_lds, p->stream));
 	}
 	if (p->timing) {
 		MF_HIP(hipEventRecord(t1.t1, p->stream));

@@ -39,6 +39,8 @@ struct SweepVariant {
 	SweepFn fn_decay = nullptr, pf_decay = nullptr;   // fn and pf with the seed times the decay factor and the frozen column kept (DMA variants; the other forms do both always)
 	SweepFn pair = nullptr;   // wave-pair form (loader + compute) for launches that end on long rows (64 <= K <= 128, compile-time K)
 	LossFn loss = nullptr;    // row sums of mf_plan_loss in the same geometry (all DMA variants; the others use loss_reg_kernel)
+	// the momentum instances of the forms above (a seeded sweep of a side with beta != 0): each where its plain twin is
+	SweepFn fn_mom = nullptr, pf_mom = nullptr, coop_mom = nullptr, db_mom = nullptr, pair_mom = nullptr;
 };
 
 template <int KT, int KP>
@@ -46,16 +48,17 @@ constexpr SweepVariant variant()
 {
 	SweepVariant v;
 	v.fn = mf::sweep_kernel<KT, KP>;
+	v.fn_mom = mf::sweep_kernel<KT, KP, true>;
 	v.kt = KT;
 	v.kpmax = KP;
 	return v;
 }
 
-template <int KT>
+template <int KT, bool MOM = false>
 constexpr SweepFn pair_fn()
 {
 	if constexpr (mf::DmaGeom<KT>::kOnePassWide)
-		return mf::sweep_pair_kernel<KT, 1>;
+		return mf::sweep_pair_kernel<KT, 1, MOM>;
 	else
 		return nullptr;
 }
@@ -79,6 +82,11 @@ constexpr SweepVariant dma_variant()
 	if constexpr (KT <= 128) v.fn_decay = mf::sweep_dma_kernel<KT, NP, mf::kSweepDecay>;
 	v.pf_decay = mf::sweep_dma_kernel<KT, NP, mf::kSweepDecay, 8>;
 	v.pair = pair_fn<KT>();
+	if constexpr (KT <= 128) v.fn_mom = mf::sweep_dma_kernel<KT, NP, mf::kSweepMomentum>;
+	v.pf_mom = mf::sweep_dma_kernel<KT, NP, mf::kSweepMomentum, 8>;
+	v.coop_mom = mf::sweep_coop_kernel<KT, true>;
+	v.db_mom = mf::sweep_db_kernel<KT, NP, true>;
+	v.pair_mom = pair_fn<KT, true>();
 	v.loss = mf::loss_dma_kernel<KT, NP>;
 	return v;
 }
@@ -95,6 +103,8 @@ constexpr SweepVariant dma_generic_variant()
 	v.errs = mf::sweep_dma_kernel<0, NPASS, mf::kSweepErrors>;
 	v.db = mf::sweep_db_kernel<0, NPASS>;
 	v.fn_decay = mf::sweep_dma_kernel<0, NPASS, mf::kSweepDecay>;
+	v.fn_mom = mf::sweep_dma_kernel<0, NPASS, mf::kSweepMomentum>;
+	v.db_mom = mf::sweep_db_kernel<0, NPASS, true>;
 	v.loss = mf::loss_dma_kernel<0, NPASS>;
 	return v;
 }
@@ -192,6 +202,11 @@ struct mf_plan {
 	double alpha = 0.0;
 	double lambda[2] = {0.0, 0.0};   // L2 regularisation per side (0 = items, 1 = users), mf_plan_set_regularization
 	int frozen[2] = {-1, -1};        // frozen column per side (0 = items, 1 = users) or -1, mf_plan_set_frozen_columns
+	double beta[2] = {0.0, 0.0};     // heavy-ball momentum per side (0 = items, 1 = users), mf_plan_set_momentum
+	// a side at rest has no history: X_prev = X_old by definition.  Set by mf_plan_upload_factors and by a change of the
+	// side's beta from 0; cleared by its first seeded momentum sweep (leave_rest copies current -> next) and by
+	// mf_plan_upload_previous
+	bool at_rest[2] = {true, true};
 	int flags = 0;
 
 	hipStream_t own_stream = nullptr;

@@ -46,6 +46,7 @@ struct SliceArgs {
 	int ldx[2], ldy[2];               // row pitch of X and of Y per side, in doubles (>= K)
 	double d[2];                      // weight decay per side: a row's seed is X_old * d (SweepArgs::d)
 	int frozen[2];                    // frozen column per side, or -1 (SweepArgs::frozen)
+	double beta[2];                   // momentum per side (SweepArgs::beta): read by the momentum instances only
 };
 
 #ifdef MF_STAMPS
@@ -56,7 +57,8 @@ struct SliceArgs {
 __device__ unsigned long long mf_es_stamp_buf[512 * kResidentWaves * 12];
 #endif
 
-template <int SW>
+// MOM: the momentum instances -- a side with beta != 0 takes the term into its seeds in the prologue below.
+template <int SW, bool MOM = false>
 __global__ void __launch_bounds__(kResidentThreads) stream_resident_kernel(SliceArgs a)
 {
 #ifdef MF_STAMPS
@@ -100,9 +102,27 @@ __global__ void __launch_bounds__(kResidentThreads) stream_resident_kernel(Slice
 	// prefetched chunks (s_waitcnt vmcnt(0) at every join of its branch).
 	constexpr int NSEED = kWave / G;
 	double sv[NSEED];
+	if constexpr (MOM) {
+		// momentum: the rows of X_new still hold the generation before X_old; every (row, slice) is read here by the wave
+		// that stores it later.  The loads stand beside the seeds', in front of the stream; the frozen column's lanes, and a
+		// side with beta == 0, skip the term.
+		const double beta = a.beta[side];
+		const bool term = beta != 0.0 && !frz;
 #pragma unroll
-	for (int b = 0; b < NSEED; ++b)
-		sv[b] = rb + b * G + g < re ? sd.X_old[(size_t) (rb + b * G + g) * ldx + col0 + cc] * dl : 0.0;
+		for (int b = 0; b < NSEED; ++b) {
+			sv[b] = 0.0;
+			if (rb + b * G + g < re) {
+				const size_t at = (size_t) (rb + b * G + g) * ldx + col0 + cc;
+				const double x = sd.X_old[at];
+				sv[b] = x * dl;
+				if (term) sv[b] = momentum_seed(x, sd.X_new[at], d, beta);
+			}
+		}
+	} else {
+#pragma unroll
+		for (int b = 0; b < NSEED; ++b)
+			sv[b] = rb + b * G + g < re ? sd.X_old[(size_t) (rb + b * G + g) * ldx + col0 + cc] * dl : 0.0;
+	}
 
 	// ---- the slice of every row of Y -> LDS (16-byte pieces, SW/2 per row).  All of a thread's loads are issued
 	// before the first LDS write (one memory latency for the whole copy, not one per piece): at most kPieces per thread.

@@ -21,7 +21,9 @@ namespace mf {
 //   X_new[r][k] = (...((seed + e_0*Y[idx_0][k]) + e_1*Y[idx_1][k]) + ...)          (matFact.c:47-51)
 // where seed = X_old[r][k] * d (d = 1.0 - c2 * lambda, the side's L2 weight decay: one rounded multiply, unfused with
 // the add that follows; d = 1.0 leaves the bits of X_old), or 0 for the non-root contribution of a sharded item sweep
-// (matFact-mpi.c:187): the decay is applied where the seed is taken, once.  Mapping onto the wave, per chunk of <= nch entries of the row:
+// (matFact-mpi.c:187): the decay is applied where the seed is taken, once.  With heavy-ball momentum (beta != 0 and a
+// seed) the seed is (X_old[r][k] * d) + beta * (X_old[r][k] - X_prev[r][k]), X_prev being what X_new[r][k] holds at launch
+// (momentum_seed below; include/matfact_hip.h has the definition).  Mapping onto the wave, per chunk of <= nch entries of the row:
 //   stage   the nch gathered Y rows are copied, coalesced (16 B per lane), into an LDS tile whose row
 //           stride is odd in doubles, so both access patterns below are bank-conflict-free;
 //   phase A lane n walks row n of the tile and forms dot_n sequentially in k (the serial order) with
@@ -65,7 +67,23 @@ struct SweepArgs {
 	// frozen column of the side, or -1: X_new[r][frozen] = seed ? X_old[r][frozen] : 0.0 whatever was added up -- a select on
 	// the finished row where it is stored, in the instances that multiply by d (main_form picks those for a frozen side too)
 	int frozen;
+	// heavy-ball momentum of the side: read by the momentum instances only, which launch_sweep picks for a seeded sweep
+	// with beta != 0 (X_prev is read through X_new: the owner of a row reads it before it writes it)
+	double beta;
 };
+
+// The seed of one element under momentum: one rounded subtraction, one rounded multiply, the decay's multiply, one rounded
+// add -- nothing fused (the library is built with -ffp-contract=off).
+__device__ __forceinline__ double momentum_seed(double x, double xp, double d, double beta)
+{
+	const double v = x - xp;
+	const double m = beta * v;
+	return (x * d) + m;
+}
+__device__ __forceinline__ double2 momentum_seed(double2 x, double2 xp, double d, double beta)
+{
+	return make_double2(momentum_seed(x.x, xp.x, d, beta), momentum_seed(x.y, xp.y, d, beta));
+}
 
 __device__ __forceinline__ double readlane_f64(double v, int lane)
 {
@@ -77,7 +95,7 @@ __device__ __forceinline__ double readlane_f64(double v, int lane)
 // LDS row stride of the register-staged form in doubles: odd, so both access patterns are bank-conflict-free
 __host__ __device__ constexpr int reg_row_stride(int K) { return K | 1; }
 
-template <int KT, int KPMAX>
+template <int KT, int KPMAX, bool MOM = false>
 __global__ void __launch_bounds__(kWave) sweep_kernel(SweepArgs a)
 {
 	extern __shared__ double tile[];
@@ -95,7 +113,10 @@ __global__ void __launch_bounds__(kWave) sweep_kernel(SweepArgs a)
 #pragma unroll
 		for (int kk = 0; kk < KPMAX; ++kk) {
 			const int k = lane + kWave * kk;
-			acc[kk] = (a.seed && k < K) ? xrow[k] * a.d : 0.0;
+			if constexpr (MOM)
+				acc[kk] = (a.seed && k < K) ? momentum_seed(xrow[k], a.X_new[(size_t) r * a.ldx + k], a.d, a.beta) : 0.0;
+			else
+				acc[kk] = (a.seed && k < K) ? xrow[k] * a.d : 0.0;
 		}
 
 		for (int c = beg; c < end; c += nch) {
@@ -225,6 +246,24 @@ __device__ __forceinline__ void load_x_row(const double2 *__restrict__ xrow2, do
 			xs[q] = v;
 		}
 		acc[p] = seed ? make_double2(v.x * d, v.y * d) : make_double2(0.0, 0.0);
+	}
+}
+
+// The same with momentum: `prev2` is the row of X_new, which holds the generation before X_old until this row is stored.
+template <int NP>
+__device__ __forceinline__ void load_x_row_momentum(const double2 *__restrict__ xrow2, const double2 *prev2, double2 *xs, int lane, int P, int seed,
+                                                    double d, double beta, double2 (&acc)[NP])
+{
+#pragma unroll
+	for (int p = 0; p < NP; ++p) {
+		const int q = lane + kWave * p;
+		double2 v = make_double2(0.0, 0.0), w = make_double2(0.0, 0.0);
+		if (q < P) {
+			v = xrow2[q];
+			w = prev2[q];
+			xs[q] = v;
+		}
+		acc[p] = seed ? momentum_seed(v, w, d, beta) : make_double2(0.0, 0.0);
 	}
 }
 
@@ -548,10 +587,11 @@ __device__ __forceinline__ void phase_b_tail(const char *tb, int S, double e, in
 // MODE: 0 accumulate (the sweep), 1 products (extreme rows), 2 errors (first half of the errors + streams iteration),
 // 3 accumulate with the seed multiplied by the decay factor a.d -- launch_sweep picks it when d != 1.0, so the instances
 // of mode 0, the timed path of an unregularised run, keep their code.  Mode 3 also carries the frozen column (a.frozen):
-// launch_sweep picks it for a frozen side at d = 1.0 too, x * 1.0 being x
+// launch_sweep picks it for a frozen side at d = 1.0 too, x * 1.0 being x; 4 mode 3 with the momentum term added to the
+// seed (a seeded sweep of a side with beta != 0)
 // PF > 0: phases A and B keep their LDS reads in flight and the gather issue is lean.
 // ------------------------------------------------------------------------------------------------
-constexpr int kSweepAccumulate = 0, kSweepProducts = 1, kSweepErrors = 2, kSweepDecay = 3;
+constexpr int kSweepAccumulate = 0, kSweepProducts = 1, kSweepErrors = 2, kSweepDecay = 3, kSweepMomentum = 4;
 #ifdef MF_STAMPS
 // diagnostic build only (tools/stamps.py): shader-clock totals of the phases of the rows of at least 1024 entries --
 // [0] rows, [1] chunks, [2] gather issue, [3] landing wait, [4] phase A, [5] phase B, [6] whole row
@@ -564,7 +604,8 @@ __device__ unsigned long long mf_stamp_buf[8];
 template <int KT, int NPASS, int MODE = kSweepAccumulate, int PF = 0>
 __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 {
-	constexpr bool PRODUCTS = MODE == kSweepProducts, ERRORS = MODE == kSweepErrors, SEGMENTS = PRODUCTS || ERRORS, DECAY = MODE == kSweepDecay;
+	constexpr bool PRODUCTS = MODE == kSweepProducts, ERRORS = MODE == kSweepErrors, SEGMENTS = PRODUCTS || ERRORS, MOMENTUM = MODE == kSweepMomentum,
+	               DECAY = MODE == kSweepDecay || MOMENTUM;
 	const int K = KT > 0 ? KT : a.K;
 	const int P = dma_pieces(K);
 	constexpr int NP = NPASS;                               // DMA instructions per row
@@ -607,7 +648,11 @@ __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 				v = xrow2[q];
 				xs[q] = v;
 			}
-			if constexpr (DECAY)
+			if constexpr (MOMENTUM) {
+				double2 w = make_double2(0.0, 0.0);
+				if (q < P) w = reinterpret_cast<const double2 *>(a.X_new + (size_t) r * a.ldx)[q];
+				acc[p] = a.seed ? momentum_seed(v, w, a.d, a.beta) : make_double2(0.0, 0.0);
+			} else if constexpr (DECAY)
 				acc[p] = a.seed ? make_double2(v.x * a.d, v.y * a.d) : make_double2(0.0, 0.0);
 			else
 				acc[p] = a.seed ? v : make_double2(0.0, 0.0);
@@ -774,7 +819,7 @@ __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 // Same arithmetic in the same order as sweep_dma_kernel: same bits.  Twice the LDS per workgroup, so only chosen where
 // occupancy is not what hides latency (choose_sweep / launch_sweep: few rows per CU).  Accumulate mode only.
 // ------------------------------------------------------------------------------------------------
-template <int KT, int NPASS>
+template <int KT, int NPASS, bool MOM = false>
 __global__ void __launch_bounds__(kWave) sweep_db_kernel(SweepArgs a)
 {
 	const int K = KT > 0 ? KT : a.K;
@@ -814,7 +859,12 @@ __global__ void __launch_bounds__(kWave) sweep_db_kernel(SweepArgs a)
 				v = xrow2[q];
 				xs[q] = v;
 			}
-			acc[p] = a.seed ? make_double2(v.x * a.d, v.y * a.d) : make_double2(0.0, 0.0);
+			if constexpr (MOM) {
+				double2 w = make_double2(0.0, 0.0);
+				if (q < P) w = reinterpret_cast<const double2 *>(a.X_new + (size_t) r * a.ldx)[q];
+				acc[p] = a.seed ? momentum_seed(v, w, a.d, a.beta) : make_double2(0.0, 0.0);
+			} else
+				acc[p] = a.seed ? make_double2(v.x * a.d, v.y * a.d) : make_double2(0.0, 0.0);
 		}
 		// chunk c's (idx, val) in cur_*, chunk c+1's in nx_*; the gather of chunk c is issued one iteration ahead
 		int cur_idx = 0, nx_idx = 0;
@@ -915,7 +965,7 @@ __global__ void __launch_bounds__(kWave) sweep_db_kernel(SweepArgs a)
 // built: a second loader was measured within noise of one (the compute wave is the bound), and so
 // was splitting the compute wave into a phase-A and a phase-B wave (profiles/r03/trio_ab.txt).
 // ------------------------------------------------------------------------------------------------
-template <int KT, int NL = 1>
+template <int KT, int NL = 1, bool MOM = false>
 __global__ void __launch_bounds__((NL + 1) * kWave) sweep_pair_kernel(SweepArgs a)
 {
 	using G = DmaGeom<KT>;
@@ -968,7 +1018,10 @@ __global__ void __launch_bounds__((NL + 1) * kWave) sweep_pair_kernel(SweepArgs 
 				__builtin_amdgcn_s_setprio(0);
 			const double2 *__restrict__ xrow2 = reinterpret_cast<const double2 *>(a.X_old + (size_t) r * a.ldx);
 			double2 acc[1];
-			load_x_row<1>(xrow2, xs, lane, P, a.seed, a.d, acc);
+			if constexpr (MOM)
+				load_x_row_momentum<1>(xrow2, reinterpret_cast<const double2 *>(a.X_new + (size_t) r * a.ldx), xs, lane, P, a.seed, a.d, a.beta, acc);
+			else
+				load_x_row<1>(xrow2, xs, lane, P, a.seed, a.d, acc);
 			double nx_val = 0.0;
 			if (beg + lane < min(end, beg + nch)) nx_val = a.val[beg + lane];
 			const unsigned boff = (unsigned) (lane < P ? lane : 0) * 16u;   // lanes beyond the row re-read piece 0: no branch masks in phase B
@@ -1045,6 +1098,9 @@ struct OrderedSumArgs {
 	const int *__restrict__ cnt;          // entries of the row
 	const double *__restrict__ scratch;   // [slice][entry][kSliceCols], each slice padded by one block
 	size_t scratch_entries;
+	// a seeded momentum sweep passes X_new as X_old as well (the finished seeds are in the X_new rows, momentum_seed_kernel):
+	// the two alias BY DESIGN there.  The seed is read through X_old only by the asm LDS-DMA of ordered_sum_task, which
+	// hipcc neither sees nor moves, and each (row, slice) wave has its seed in LDS before it stores that slice
 	const double *__restrict__ X_old;
 	double *__restrict__ X_new;
 	unsigned long long *stamps;           // probe builds only (tools/micro/osum_probe.hip): 4 clock stamps per task, else null
@@ -1242,6 +1298,31 @@ __device__ __forceinline__ void ordered_sum_task(const char *src, unsigned ring_
 }
 #undef MF_FMAC_BCAST
 
+// Momentum and the ordered sum: the seed of an extreme row travels by LDS-DMA inside the hand-counted region above, where
+// a second load has no place.  A seeded momentum sweep therefore runs this launch on the side stream in front of the
+// ordered sum: it writes the FINISHED seed -- (x * d) + beta * (x - x_prev), the frozen column's x as it is -- over x_prev
+// in the X_new row, and the ordered sum takes its seed from X_new at d = 1.0 (x * 1.0 is x; its frozen read of the seed's
+// slot still yields X_old's bits).  One wave per extreme row.
+struct SeedPrepArgs {
+	int nrows, K, ldx, frozen;
+	double d, beta;
+	const int *__restrict__ row;          // extreme row ids
+	const double *__restrict__ X_old;
+	double *__restrict__ X_new;
+};
+
+__global__ void __launch_bounds__(kWave) momentum_seed_kernel(SeedPrepArgs a)
+{
+	const int r = a.row[blockIdx.x];
+	const double *__restrict__ x = a.X_old + (size_t) r * a.ldx;
+	double *__restrict__ out = a.X_new + (size_t) r * a.ldx;
+	for (int k = threadIdx.x; k < a.K; k += kWave) {
+		const double xv = x[k];
+		const double s = momentum_seed(xv, out[k], a.d, a.beta);
+		out[k] = k == a.frozen ? xv : s;
+	}
+}
+
 template <bool DPP>
 __global__ void __launch_bounds__(kWave) ordered_sum_kernel(OrderedSumArgs a)
 {
@@ -1323,6 +1404,16 @@ struct ResidentArgs {
 	double *__restrict__ L_out;                 // where the generation after `iters` iterations belongs
 	double *__restrict__ R_out;
 	int nnz;
+	// momentum instances only: beta of a user / an item row's seed; the history on the way in -- the next-generation
+	// buffers at launch, the generation before L_in / R_in --, and where the generation before the final one belongs on the
+	// way out: the buffers that L_out / R_out are not.  For an even `iters` the two pairs are the same buffers, for an odd one
+	// L_prev / R_prev are L_in / R_in: no __restrict__ here (every load of the way in is complete, behind a barrier, before
+	// the first store of the way out)
+	double beta_users, beta_items;
+	const double *L_hist;
+	const double *R_hist;
+	double *L_prev;
+	double *R_prev;
 };
 
 constexpr size_t resident_lds_bytes(int users, int items, int K, long long nnz)
@@ -1336,7 +1427,9 @@ constexpr size_t resident_lds_bytes(int users, int items, int K, long long nnz)
 // most 256 threads per workgroup (512 VGPRs per lane and SIMD / one wave per SIMD), so it is bounded -- and chosen --
 // for users + items <= 256; under a 1024-thread bound it spilled to scratch.
 constexpr int resident_max_threads(int kmax) { return kmax == 32 ? 256 : 1024; }
-template <int KMAX>
+// MOM: heavy-ball momentum -- gen1 starts as the generation before gen0 (a thread reads its row of `nxt` before it
+// overwrites it, and nobody else's), a side with beta == 0 adds no term, and both generations are written back.
+template <int KMAX, bool MOM = false>
 __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_kernel(ResidentArgs a)
 {
 	extern __shared__ __attribute__((aligned(16))) char rlds[];
@@ -1349,6 +1442,10 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 	const int t = threadIdx.x, nt = blockDim.x;
 	for (int x = t; x < U * K; x += nt) gen0[x] = a.L_in[(size_t) (x / K) * a.ldl + x % K];
 	for (int x = t; x < I * K; x += nt) gen0[U * K + x] = a.R_in[(size_t) (x / K) * a.ldr + x % K];
+	if constexpr (MOM) {
+		for (int x = t; x < U * K; x += nt) gen1[x] = a.L_hist[(size_t) (x / K) * a.ldl + x % K];
+		for (int x = t; x < I * K; x += nt) gen1[U * K + x] = a.R_hist[(size_t) (x / K) * a.ldr + x % K];
+	}
 	for (int x = t; x < nnz; x += nt) {
 		val[x] = a.csr_val[x];
 		val[nnz + x] = a.csc_val[x];
@@ -1368,6 +1465,7 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 	const int ybase = user ? U * K : 0;         // the other factor inside a generation
 	const double d = user ? a.d_users : a.d_items;
 	const int frozen = user ? a.frozen_users : a.frozen_items;
+	const double beta = MOM ? (user ? a.beta_users : a.beta_items) : 0.0;
 	double *cur = gen0, *nxt = gen1;
 	for (int it = 0; it < a.iters; ++it) {
 		if (owner && KMAX > 0) {
@@ -1377,6 +1475,11 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 			for (int k = 0; k < KM; ++k) {
 				xr[k] = k < K ? cur[xoff + k] : 0.0;
 				acc[k] = xr[k] * d;
+			}
+			if (MOM && beta != 0.0) {
+#pragma unroll
+				for (int k = 0; k < KM; ++k)
+					if (k < K) acc[k] = momentum_seed(xr[k], nxt[xoff + k], d, beta);
 			}
 			// the frozen column's old element, read beside the row (a select over xr[] would keep KMAX lane masks alive
 			// across the iteration loop)
@@ -1402,7 +1505,10 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 		} else if (owner) {
 			const double *x = cur + xoff;
 			double *xn = nxt + xoff;
-			for (int k = 0; k < K; ++k) xn[k] = x[k] * d;
+			if (MOM && beta != 0.0)
+				for (int k = 0; k < K; ++k) xn[k] = momentum_seed(x[k], xn[k], d, beta);
+			else
+				for (int k = 0; k < K; ++k) xn[k] = x[k] * d;
 			for (int n = beg; n < end; ++n) {
 				const double *y = cur + ybase + idx[n] * K;
 				double dot = 0.0;
@@ -1419,6 +1525,10 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 	}
 	for (int x = t; x < U * K; x += nt) a.L_out[(size_t) (x / K) * a.ldl + x % K] = cur[x];
 	for (int x = t; x < I * K; x += nt) a.R_out[(size_t) (x / K) * a.ldr + x % K] = cur[U * K + x];
+	if constexpr (MOM) {
+		for (int x = t; x < U * K; x += nt) a.L_prev[(size_t) (x / K) * a.ldl + x % K] = nxt[x];
+		for (int x = t; x < I * K; x += nt) a.R_prev[(size_t) (x / K) * a.ldr + x % K] = nxt[U * K + x];
+	}
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1435,7 +1545,7 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 constexpr int kCoopWaves = 8;
 constexpr int kCoopProducers = kCoopWaves - 1;
 
-template <int KT>
+template <int KT, bool MOM = false>
 __global__ void __launch_bounds__(kCoopWaves *kWave) sweep_coop_kernel(SweepArgs a)
 {
 	using G = DmaGeom<KT>;
@@ -1464,7 +1574,10 @@ __global__ void __launch_bounds__(kCoopWaves *kWave) sweep_coop_kernel(SweepArgs
 				if (q < P) {
 					const double2 v = xrow2[q];
 					xs[q] = v;
-					if (a.seed) acc[p] = make_double2(v.x * a.d, v.y * a.d);
+					if constexpr (MOM) {
+						if (a.seed) acc[p] = momentum_seed(v, reinterpret_cast<const double2 *>(a.X_new + (size_t) r * a.ldx)[q], a.d, a.beta);
+					} else if (a.seed)
+						acc[p] = make_double2(v.x * a.d, v.y * a.d);
 				}
 			}
 		}

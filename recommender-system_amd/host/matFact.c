@@ -22,11 +22,11 @@
 
 /* Every MATFACT_* variable the program reads: the mode options in the order they are examined, the path options, and the
  * accessories, which take part in no rule. */
-enum { V_TOPN, V_LOSS, V_HELDOUT, V_RANK, V_SIMILAR, V_SIMILAR_OUT, V_LAMBDA, V_BIAS, V_DEVICES, V_MATS, V_CHECKPOINT, V_RESUME,
+enum { V_TOPN, V_LOSS, V_HELDOUT, V_RANK, V_SIMILAR, V_SIMILAR_OUT, V_LAMBDA, V_BIAS, V_MOMENTUM, V_DEVICES, V_MATS, V_CHECKPOINT, V_RESUME,
        V_DEVICE, V_MATS_ITERS, V_CHECKPOINT_EVERY, V_CACHE, V_TIMING, V_COUNT };
 static const char *const cli_names[V_COUNT] = {
 	"MATFACT_TOPN", "MATFACT_LOSS", "MATFACT_HELDOUT", "MATFACT_RANK", "MATFACT_SIMILAR", "MATFACT_SIMILAR_OUT", "MATFACT_LAMBDA",
-	"MATFACT_BIAS", "MATFACT_DEVICES", "MATFACT_MATS", "MATFACT_CHECKPOINT", "MATFACT_RESUME", "MATFACT_DEVICE",
+	"MATFACT_BIAS", "MATFACT_MOMENTUM", "MATFACT_DEVICES", "MATFACT_MATS", "MATFACT_CHECKPOINT", "MATFACT_RESUME", "MATFACT_DEVICE",
 	"MATFACT_MATS_ITERS", "MATFACT_CHECKPOINT_EVERY", "MATFACT_CACHE", "MATFACT_TIMING"};
 
 struct cli_options {
@@ -43,6 +43,8 @@ struct cli_options {
 	int regularised;      /* MATFACT_LAMBDA=l[,li]: L2 regularisation, one number for both sides or users,items (finite, >= 0); */
 	double lambda_users, lambda_items;   /* with MATFACT_LOSS one more stderr line: ||L||^2, ||R||^2, the objective at the end */
 	int biased;           /* MATFACT_BIAS=1: a ~ mu + b_user + b_item + l.r on frozen columns; the file's K is the latent count F */
+	int momentum;         /* MATFACT_MOMENTUM=b[,bi]: heavy-ball momentum, one number for both sides or users,items (finite, >= 0) */
+	double beta_users, beta_items;
 	int device;           /* MATFACT_DEVICE=n: the GPU of a single-GPU run, default 0 */
 	int devs[16], ndev;   /* MATFACT_DEVICES=0,1,...: row-shard over these GPUs of the process, at most 16 */
 	const char *devices_error;   /* a non-number in it: said only where that path runs, after the input was read, as ever */
@@ -96,6 +98,12 @@ static const char *cli_value(int v, const char *s, struct cli_options *o)
 	case V_BIAS:
 		o->biased = !strcmp(s, "1");
 		return o->biased ? NULL : "MATFACT_BIAS: expected 1.";
+	case V_MOMENTUM:
+		ok = number(s, ',', &rest, &o->beta_users);
+		o->beta_items = o->beta_users;
+		if (ok && *rest) ok = number(rest + 1, 0, &rest, &o->beta_items);
+		o->momentum = ok && isfinite(o->beta_users) && isfinite(o->beta_items) && o->beta_users >= 0.0 && o->beta_items >= 0.0;
+		return o->momentum ? NULL : "MATFACT_MOMENTUM: expected b[,bi] with b and bi numbers >= 0.";
 	}
 	return NULL;   /* MATFACT_HELDOUT, MATFACT_SIMILAR_OUT: any text */
 }
@@ -125,6 +133,7 @@ static const struct cli_rule cli_clashes[] = {
 	{V_SIMILAR, BIT(V_TOPN) | BIT(V_LOSS), "MATFACT_SIMILAR cannot be combined with MATFACT_TOPN or MATFACT_LOSS."},
 	{V_LAMBDA, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_LAMBDA works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
 	{V_BIAS, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_BIAS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
+	{V_MOMENTUM, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_MOMENTUM works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
 };
 
 /* Fills `o` from the environment -- it opens no file and makes no GPU call -- and returns NULL, or the message to die with. */
@@ -135,7 +144,7 @@ static const char *cli_parse(struct cli_options *o)
 	for (int v = 0; v < V_COUNT; v++)
 		if ((o->value[v] = getenv(cli_names[v])) != NULL) set |= BIT(v);
 	const unsigned usable = o->value[V_SIMILAR_OUT] && !*o->value[V_SIMILAR_OUT] ? set & ~BIT(V_SIMILAR_OUT) : set;
-	for (int v = V_TOPN; v <= V_BIAS; v++) {
+	for (int v = V_TOPN; v <= V_MOMENTUM; v++) {
 		const char *message = set & BIT(v) ? cli_value(v, o->value[v], o) : NULL;
 		if (message) return message;
 		if (!(set & BIT(v))) continue;
@@ -160,7 +169,7 @@ static const char *cli_parse(struct cli_options *o)
 
 /* One resident single-GPU plan over a whole problem and the host buffers it reads: the only place that splits entries into
  * SoA form, fills an mf_shard and creates a plan.  session_close releases everything, whatever was acquired.
- * MATFACT_BIAS (here always next to MATFACT_LOSS) is a preparation in front of the plan: the values are centred with the
+ * MATFACT_BIAS (here next to MATFACT_LOSS or MATFACT_MOMENTUM) is a preparation in front of the plan: the values are centred with the
  * training mean `mu` (one rounding each; the held-out ones later with the SAME mean), L and R -- the reference's
  * initialisation for K = F -- are packed to K = F + 2 by mf_backend_bias_pack with the biases at 0.0. */
 struct session {
@@ -340,6 +349,7 @@ static int run_session(const struct cli_options *o, const mf_problem *p, const m
 	if (rc == MF_OK && held) rc = mf_plan_set_heldout(s.plan, held->nnz, s.hrow, s.hcol, s.hval);
 	if (rc == MF_OK && o->regularised) rc = mf_plan_set_regularization(s.plan, o->lambda_users, o->lambda_items);
 	if (rc == MF_OK && o->biased) rc = mf_plan_set_frozen_columns(s.plan, p->features + 1, p->features);
+	if (rc == MF_OK && o->momentum) rc = mf_plan_set_momentum(s.plan, o->beta_users, o->beta_items);
 	/* loop */
 	if (rc == MF_OK) {
 		if (o->loss_every) rc = mf_plan_iterate_monitored(s.plan, p->iters, o->loss_every, o->loss_tol, trace, cap, &points, &done);
@@ -347,15 +357,16 @@ static int run_session(const struct cli_options *o, const mf_problem *p, const m
 		else if (d) rc = loop_dumped(s.plan, o, p, L, R, d);
 		else rc = mf_plan_iterate(s.plan, p->iters);
 	}
-	/* report: the rules allow MATFACT_BIAS, MATFACT_LAMBDA and MATFACT_RANK in a session only next to MATFACT_LOSS */
+	/* report, next to MATFACT_LOSS only (MATFACT_RANK needs it by the rules; MATFACT_BIAS with MATFACT_MOMENTUM runs here
+	 * without it and reports nothing) */
 	for (int i = 0; rc == MF_OK && i < points && i < cap; i++) {
 		fprintf(stderr, "iter %d train_rmse %.17g", trace[i].iter,
 		        trace[i].train.count > 0 ? sqrt(trace[i].train.sse / (double) trace[i].train.count) : NAN);
 		if (held && held->nnz > 0) fprintf(stderr, " heldout_rmse %.17g", sqrt(trace[i].heldout.sse / (double) trace[i].heldout.count));
 		fprintf(stderr, "\n");
 	}
-	if (rc == MF_OK && o->biased) fprintf(stderr, "bias mu %.17g\n", s.mu);
-	if (rc == MF_OK && o->regularised) rc = report_penalty(s.plan, o);
+	if (rc == MF_OK && o->biased && o->loss_every) fprintf(stderr, "bias mu %.17g\n", s.mu);
+	if (rc == MF_OK && o->regularised && o->loss_every) rc = report_penalty(s.plan, o);
 	if (rc == MF_OK && o->rank_cutoff) rc = report_ranks(s.plan, o->rank_cutoff, s.hrow, held->nnz);
 	/* outputs */
 	if (rc == MF_OK) rc = mf_plan_recommend(s.plan, best);
@@ -444,10 +455,10 @@ int main(int argc, char **argv)
 	/*
 	 * The rules of cli_parse leave mode options or path options, never both.  Among the path options the priority is silent:
 	 * MATFACT_CHECKPOINT / MATFACT_RESUME win over MATFACT_MATS, which wins over MATFACT_DEVICES (and MATFACT_RESUME is read
-	 * above whenever it is set).  MATFACT_LOSS, MATFACT_SIMILAR, the checkpoints and the dump need a resident plan and run as
+	 * above whenever it is set).  MATFACT_LOSS, MATFACT_SIMILAR, MATFACT_BIAS with MATFACT_MOMENTUM, the checkpoints and the dump need a resident plan and run as
 	 * a session, which splits the entries once; the rest goes through the level-1 calls, which take the entries as they are.
 	 */
-	if (o.loss_every || o.similar || o.value[V_CHECKPOINT] || o.value[V_RESUME]) {
+	if (o.loss_every || o.similar || o.value[V_CHECKPOINT] || o.value[V_RESUME] || (o.momentum && o.biased)) {
 		rc = run_session(&o, &prob, have_held ? &held : NULL, L, R, best, start_iter, NULL);
 	} else if (o.biased) {
 		/* biases start at 0.0; L and R took the reference's random() stream for K = F above */
@@ -457,6 +468,8 @@ int main(int argc, char **argv)
 		rc = mf_backend_run_biased(&prob, L, R, bu, bi, &mu, best, o.lambda_users, o.lambda_items, o.device);
 		free(bu);
 		free(bi);
+	} else if (o.momentum) {
+		rc = mf_backend_run_momentum(&prob, L, R, best, o.lambda_users, o.lambda_items, o.beta_users, o.beta_items, o.device);
 	} else if (o.regularised) {
 		rc = mf_backend_run_reg(&prob, L, R, best, o.lambda_users, o.lambda_items, o.device);
 	} else if (o.topn) {
