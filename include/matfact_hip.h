@@ -50,7 +50,9 @@ extern "C" {
                                           mf_plan_get_frozen_columns, mf_backend_bias_mean, mf_backend_bias_pack,
                                           mf_backend_bias_unpack, mf_backend_run_biased);
                                           heavy-ball momentum (mf_plan_set_momentum, mf_plan_get_momentum,
-                                          mf_plan_upload_previous, mf_plan_download_previous, mf_backend_run_momentum) */
+                                          mf_plan_upload_previous, mf_plan_download_previous, mf_backend_run_momentum);
+                                          per-entry confidence weights (mf_plan_create_weighted, mf_plan_weight_total,
+                                          mf_backend_run_weighted) */
 
 /* == non_zero_entry, datatypes.h:10-15: the (user, item, rating) triple, 16 bytes, array-of-structs */
 typedef struct mf_entry {
@@ -472,6 +474,42 @@ int mf_plan_download_previous(mf_plan *plan, double *L_prev_block, double *R_pre
 /* level 1: mf_backend_run_reg with momentum, from rest.  A bad lambda or beta -> MF_ERR_ARGUMENT before any HIP call. */
 int mf_backend_run_momentum(const mf_problem *p, double *L, double *R, int32_t *best, double lambda_users, double lambda_items,
                             double beta_users, double beta_items, int device);
+
+/* ---- Per-entry confidence weights: the entries are not equally trustworthy (confidence by play count, time decay,
+ * inverse-propensity weights, down-weighted sampled negatives, weight 0 to hold a fold out without rebuilding the problem).
+ * An extension (the reference has none), so the definition is this library's; it fixes every rounding.  A plan may carry
+ * one weight w_n (double) per training entry, given with the entries, in the order of mf_shard.row / col / val.  In every
+ * sweep of either side, for every entry:
+ *   dot_n  unchanged
+ *   e_n  = (c2 * (val_n - dot_n)) * w_n
+ * -- the plain e_n is formed first, then one more rounded multiply follows, unfused.  X_new accumulates e_n * Y[idx_n][k]
+ * exactly as before, from the same seed, in the same order; decay, frozen column and momentum are untouched.  w_n == 1.0
+ * gives the plain bits.  Nothing is special-cased or validated: inf * 0 is NaN, and a negative or NaN weight is the
+ * caller's business, like beta >= 1.  One consequence: a zero weight gives a product e_n * y of +-0.0 -- not "no term" --, so
+ * an accumulator that holds -0.0 comes out +0.0 wherever such a product is +0.0 ((-0.0) + (+0.0)); where no accumulator is
+ * +-0.0, weight 0 is leaving the entry out.  Zero-weight entries stay "rated" for the recommendation mask, the ranks and top-N.
+ *
+ * Training loss.  On a weighted plan MF_LOSS_TRAIN is the weighted objective, the one the sweeps descend: step 2 of the loss
+ * becomes q_n = (d_n * d_n) * w_n, one more rounded multiply; steps 3 to 5 are unchanged and count stays |E|.
+ * mf_plan_iterate_monitored therefore monitors the weighted training RMSE.  The held-out set stays unweighted.  With all
+ * weights 1.0 the loss is the unweighted bits.
+ *
+ * mf_plan_create_weighted: mf_plan_create with `weight`, shard->nnz doubles that are copied (the caller's array is not
+ * needed after the call).  weight == NULL is mf_plan_create in every respect: the same kernels, the same mf_plan_describe.
+ * The weights are fixed for the plan's life.  A weighted plan runs the weighted twins of the kernels of an unweighted one --
+ * the same forms, chosen by the same rules -- and keeps the weights in CSR and in CSC order beside the values (2 x 8 bytes
+ * per entry of device memory); mf_plan_describe appends weighted=1, which means that every sweep and loss kernel the string
+ * names runs as its weighted twin (the names printed are those of the unweighted plan of the same shape).  mf_backend_run_multi does not weight: a sharded caller
+ * of the plan API gives each shard the weights of its own entries.
+ * mf_plan_weight_total: the w_n added per user in entry order from 0.0 (row_w, user_count doubles), the rows then combined
+ * by step 4 of the loss (sum_w) -- mf_backend_loss_total is the host twin --, for a caller that normalises.  Either pointer
+ * may be NULL; an unweighted plan returns MF_ERR_STATE. */
+int mf_plan_create_weighted(mf_plan **out, const mf_shard *shard, const double *weight);
+int mf_plan_weight_total(mf_plan *plan, double *sum_w, double *row_w);
+/* level 1: mf_backend_run_momentum on a weighted plan (weight: p->nnz doubles in the order of p->entries, or NULL).  A bad
+ * lambda or beta, or NULL L / R, -> MF_ERR_ARGUMENT before any HIP call. */
+int mf_backend_run_weighted(const mf_problem *p, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
+                            double lambda_items, double beta_users, double beta_items, int device);
 
 /* ---- Ranks of the held-out entries: where each held-out item lands in its user's recommendation order, for the plan's
  * current factors.  An extension (the reference ranks nothing), so the definition is this library's.  For held-out entry

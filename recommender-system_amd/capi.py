@@ -50,6 +50,7 @@ HIP_SYMBOLS = [
     "mf_backend_bias_unpack", "mf_backend_run_biased",
     "mf_plan_set_momentum", "mf_plan_get_momentum", "mf_plan_upload_previous", "mf_plan_download_previous",
     "mf_backend_run_momentum",
+    "mf_plan_create_weighted", "mf_plan_weight_total", "mf_backend_run_weighted",
 ]
 HOST_SYMBOLS = [
     "mf_host_parse_strerror", "mf_host_parse_file", "mf_host_parse_buffer", "mf_host_free_problem",
@@ -213,6 +214,9 @@ def hip():
         lib.mf_plan_download_previous.argtypes = [P, P, P]
         lib.mf_backend_run_momentum.argtypes = [C.POINTER(Problem), _f64p, _f64p, P, C.c_double, C.c_double, C.c_double, C.c_double,
                                                 C.c_int]
+        lib.mf_plan_create_weighted.argtypes = [C.POINTER(P), C.POINTER(Shard), P]
+        lib.mf_plan_weight_total.argtypes = [P, C.POINTER(C.c_double), P]
+        lib.mf_backend_run_weighted.argtypes = [C.POINTER(Problem), P, P, P, P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int]
         _hip = lib
     return _hip
 
@@ -459,6 +463,27 @@ def backend_run_momentum(inst, L, R, lambda_users, lambda_items, beta_users, bet
 run_momentum = backend_run_momentum
 
 
+def backend_run_weighted(inst, weight, L, R, lambda_users=0.0, lambda_items=None, beta_users=0.0, beta_items=None, iters=None, device=0,
+                         recommend=True):
+    """mf_backend_run_weighted: backend_run_momentum on a plan with one confidence weight per entry (weight: inst.nnz doubles
+    in the entries' order, or None for an unweighted run); L, R updated in place, returns best[users], or None with
+    recommend=False."""
+    p, keep = _problem(inst, iters)
+    w = None if weight is None else np.ascontiguousarray(weight, np.float64)
+    assert w is None or w.shape == (inst.nnz,)
+    li = lambda_users if lambda_items is None else lambda_items
+    bi = beta_users if beta_items is None else beta_items
+    best = np.empty(inst.users, np.int32) if recommend else None
+    assert L.dtype == np.float64 and R.dtype == np.float64 and L.flags.c_contiguous and R.flags.c_contiguous
+    _check(hip().mf_backend_run_weighted(C.byref(p), None if w is None else w.ctypes.data, L.ctypes.data, R.ctypes.data,
+                                         best.ctypes.data if recommend else None,
+                                         float(lambda_users), float(li), float(beta_users), float(bi), device), "mf_backend_run_weighted")
+    return best
+
+
+run_weighted = backend_run_weighted
+
+
 def bias_mean(val):
     """mf_backend_bias_mean: the mean of `val` summed in the given order from 0.0; 0.0 for an empty array."""
     v = np.ascontiguousarray(val, np.float64)
@@ -646,10 +671,11 @@ def backend_similar_items(R, n, metric="cosine", query=None, device=0):
 
 # ------------------------------------------------------------------------------------ level 2
 class Plan:
-    """mf_plan: one shard resident on one GPU."""
+    """mf_plan: one shard resident on one GPU.  weight: one confidence weight per entry, in the order of row / col / val
+    (mf_plan_create_weighted); None: an unweighted plan (mf_plan_create)."""
 
     def __init__(self, users_total, items, feats, alpha, row, col, val, user_begin=0, user_count=None,
-                 device=0, items_ext=None, flags=0, users_ext=None, items_pitch=0, users_pitch=0):
+                 device=0, items_ext=None, flags=0, users_ext=None, items_pitch=0, users_pitch=0, weight=None):
         self.users_total, self.items, self.feats = int(users_total), int(items), int(feats)
         self.user_begin = int(user_begin)
         self.user_count = int(users_total - user_begin if user_count is None else user_count)
@@ -668,7 +694,13 @@ class Plan:
         s.items_pitch, s.users_pitch = int(items_pitch), int(users_pitch)
         self.nnz = s.nnz
         self._h = C.c_void_p()
-        _check(hip().mf_plan_create(C.byref(self._h), C.byref(s)), "mf_plan_create")
+        if weight is None:
+            _check(hip().mf_plan_create(C.byref(self._h), C.byref(s)), "mf_plan_create")
+        else:
+            w = np.ascontiguousarray(weight, np.float64)
+            assert w.shape == (s.nnz,)
+            _check(hip().mf_plan_create_weighted(C.byref(self._h), C.byref(s), w.ctypes.data), "mf_plan_create_weighted")
+        self.weighted = weight is not None
         self._keep = None  # the plan copied everything it needs into HBM
 
     def close(self):
@@ -696,6 +728,14 @@ class Plan:
 
     def iterate(self, iters):
         _check(hip().mf_plan_iterate(self._h, int(iters)), "mf_plan_iterate")
+
+    def weight_total(self, rows=False):
+        """mf_plan_weight_total: the sum of the plan's weights -- per user in entry order, the rows then combined like the
+        loss's row sums; (sum_w, row_w) with rows=True.  An unweighted plan raises MF_ERR_STATE."""
+        total = C.c_double()
+        rw = np.empty(self.user_count, np.float64) if rows else None
+        _check(hip().mf_plan_weight_total(self._h, C.byref(total), rw.ctypes.data if rows else None), "mf_plan_weight_total")
+        return (total.value, rw) if rows else total.value
 
     def set_regularization(self, users, items=None):
         """mf_plan_set_regularization: the L2 weights of the user and the item side (one value means both), in force from

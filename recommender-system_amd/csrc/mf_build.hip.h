@@ -15,11 +15,14 @@ inline hipError_t h2d(mf_plan *p, void *dst, const void *src, size_t bytes)
 }
 
 
-// stable counting sort of the entries by `key` into (ptr, idx, val)
+// stable counting sort of the entries by `key` into (ptr, idx, val); `wgt` (optional): a second per-entry array that
+// travels with val into `w`
 void bucket(int64_t nnz, int nkeys, const int32_t *key, int32_t key_off, const int32_t *other,
             int32_t other_off, const double *val, std::vector<int> &ptr, std::vector<int> &idx,
-            std::vector<double> &v, std::vector<int> *pos_out = nullptr)
+            std::vector<double> &v, std::vector<int> *pos_out = nullptr, const double *wgt = nullptr,
+            std::vector<double> *w = nullptr)
 {
+	if (wgt) w->resize((size_t) nnz);
 	if (pos_out) pos_out->resize((size_t) nnz);
 	ptr.assign((size_t) nkeys + 1, 0);
 	for (int64_t n = 0; n < nnz; ++n) ptr[(size_t) (key[n] - key_off) + 1]++;
@@ -31,6 +34,7 @@ void bucket(int64_t nnz, int nkeys, const int32_t *key, int32_t key_off, const i
 		const int pos = fill[(size_t) (key[n] - key_off)]++;
 		idx[(size_t) pos] = other[n] - other_off;
 		v[(size_t) pos] = val[n];
+		if (wgt) (*w)[(size_t) pos] = wgt[n];
 		if (pos_out) (*pos_out)[(size_t) n] = pos;
 	}
 }
@@ -57,13 +61,15 @@ __global__ void __launch_bounds__(256) prep_keys_kernel(const int *__restrict__ 
 __global__ void __launch_bounds__(256) gather_kernel(const unsigned *__restrict__ perm, int64_t nnz,
                                                      const int *__restrict__ other, int other_off,
                                                      const double *__restrict__ val, int *__restrict__ idx_out,
-                                                     double *__restrict__ val_out)
+                                                     double *__restrict__ val_out, const double *__restrict__ wgt,
+                                                     double *__restrict__ wgt_out)
 {
 	const int64_t n = (int64_t) blockIdx.x * 256 + threadIdx.x;
 	if (n >= nnz) return;
 	const unsigned s = perm[n];
 	idx_out[n] = other[s] - other_off;
 	val_out[n] = val[s];
+	if (wgt) wgt_out[n] = wgt[s];   // weighted plans: the weight follows its entry through the same permutation
 }
 
 // ptr[k] = first position whose (sorted) key is >= k, k = 0..nkeys
@@ -147,7 +153,7 @@ __global__ void __launch_bounds__(256) split_entries_kernel(const mf_entry *__re
 	val[n] = x.value;
 }
 
-int build_on_device(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swap, std::vector<int> &csr_ptr_host,
+int build_on_device(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swap, const double *weight, std::vector<int> &csr_ptr_host,
                     std::vector<int> &csc_ptr_host)
 {
 	const int64_t nnz = s->nnz;
@@ -159,6 +165,10 @@ int build_on_device(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swa
 	MF_TRY(p->csr_val.alloc(nz + 64));
 	MF_TRY(p->csc_idx.alloc(nz + 64));
 	MF_TRY(p->csc_val.alloc(nz + 64));
+	if (weight) {
+		MF_TRY(p->csr_wgt.alloc(nz + 64));
+		MF_TRY(p->csc_wgt.alloc(nz + 64));
+	}
 	csr_ptr_host.assign((size_t) p->uc + 1, 0);
 	csc_ptr_host.assign((size_t) p->items + 1, 0);
 	if (nnz == 0) {
@@ -179,6 +189,7 @@ int build_on_device(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swa
 	// the values land directly in csr_val when the input is row-sorted (the usual case); otherwise csc_val is
 	// used as the staging copy of the file-order values and overwritten last
 	double *d_val = p->csc_val;
+	double *d_wgt = p->csc_wgt;   // the weights take the same way: csr_wgt first, csc_wgt as the staging copy
 	const unsigned grid = (unsigned) ((nnz + 255) / 256);
 	if (aos) {
 		// one upload of the 16-byte structs, split on the device (no host pass over the entries)
@@ -192,6 +203,7 @@ int build_on_device(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swa
 		MF_HIP(hipMemcpyAsync(d_col, s->col, nz * sizeof(int), hipMemcpyHostToDevice, st));
 		MF_HIP(hipMemcpyAsync(p->csr_val, s->val, nz * sizeof(double), hipMemcpyHostToDevice, st));
 	}
+	if (weight) MF_HIP(hipMemcpyAsync(p->csr_wgt, weight, nz * sizeof(double), hipMemcpyHostToDevice, st));
 	MF_HIP(hipMemsetAsync(d_flags, 0, 3 * sizeof(int), st));
 	hipLaunchKernelGGL(prep_keys_kernel, dim3(grid), dim3(256), 0, st, d_row, d_col, nnz, p->u0, p->uc, p->items,
 	                   key_in, perm_in, d_flags);
@@ -210,6 +222,7 @@ int build_on_device(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swa
 	if ((rc = tmp.get((char **) &d_temp, temp_bytes)) != MF_OK) return rc;
 
 	const double *vals_file_order = p->csr_val;   // file-order values currently live here
+	const double *wgts_file_order = weight ? p->csr_wgt.get() : nullptr;
 	if (row_sorted) {
 		// CSR == file order: idx = col, val = val (already in place), ptr from the row keys
 		MF_HIP(hipMemcpyAsync(p->csr_idx, d_col, nz * sizeof(int), hipMemcpyDeviceToDevice, st));
@@ -219,10 +232,14 @@ int build_on_device(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swa
 		// keep a file-order copy of the values, then permute into csr_val
 		MF_HIP(hipMemcpyAsync(d_val, p->csr_val, nz * sizeof(double), hipMemcpyDeviceToDevice, st));
 		vals_file_order = d_val;
+		if (weight) {
+			MF_HIP(hipMemcpyAsync(d_wgt, p->csr_wgt, nz * sizeof(double), hipMemcpyDeviceToDevice, st));
+			wgts_file_order = d_wgt;
+		}
 		MF_HIP(rocprim::radix_sort_pairs(d_temp, temp_bytes, key_in, key_out, perm_in, perm_out, nz, 0,
 		                                 bits_for(p->uc), st));
 		hipLaunchKernelGGL(gather_kernel, dim3(grid), dim3(256), 0, st, perm_out, nnz, d_col, 0, vals_file_order,
-		                   p->csr_idx, p->csr_val);
+		                   p->csr_idx, p->csr_val, wgts_file_order, p->csr_wgt.get());
 		hipLaunchKernelGGL(ptr_kernel, dim3((unsigned) ((p->uc + 256) / 256)), dim3(256), 0, st, key_out, nnz, p->uc,
 		                   p->csr_ptr);
 		if (p->want_map) {
@@ -236,14 +253,16 @@ int build_on_device(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swa
 	                                 bits_for(p->items), st));
 	if (row_sorted) {
 		hipLaunchKernelGGL(gather_kernel, dim3(grid), dim3(256), 0, st, perm_out, nnz, d_row, p->u0, vals_file_order,
-		                   p->csc_idx, p->csc_val);
+		                   p->csc_idx, p->csc_val, wgts_file_order, p->csc_wgt.get());
 	} else {
-		// vals_file_order aliases csc_val: gather into a temporary, then copy
-		double *d_val2 = nullptr;
+		// vals_file_order aliases csc_val (and the weights' csc_wgt): gather into a temporary, then copy
+		double *d_val2 = nullptr, *d_wgt2 = nullptr;
 		if ((rc = tmp.get(&d_val2, nz)) != MF_OK) return rc;
+		if (weight && (rc = tmp.get(&d_wgt2, nz)) != MF_OK) return rc;
 		hipLaunchKernelGGL(gather_kernel, dim3(grid), dim3(256), 0, st, perm_out, nnz, d_row, p->u0, vals_file_order,
-		                   p->csc_idx, d_val2);
+		                   p->csc_idx, d_val2, wgts_file_order, d_wgt2);
 		MF_HIP(hipMemcpyAsync(p->csc_val, d_val2, nz * sizeof(double), hipMemcpyDeviceToDevice, st));
+		if (weight) MF_HIP(hipMemcpyAsync(p->csc_wgt, d_wgt2, nz * sizeof(double), hipMemcpyDeviceToDevice, st));
 	}
 	hipLaunchKernelGGL(ptr_kernel, dim3((unsigned) ((p->items + 256) / 256)), dim3(256), 0, st, key_out, nnz, p->items,
 	                   p->csc_ptr);
@@ -277,7 +296,7 @@ int build_on_device(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swa
 
 // CSR over the shard's users and CSC over the items, on the device (default) or bucketed on the host
 // (MF_BUILD=host, kept for A/B tests); rptr / cptr return the two row-pointer arrays for the schedule decisions.
-int build_sparse(mf_plan *p, const mf_shard *s_in, const mf_entry *aos, bool swap, std::vector<int> &rptr,
+int build_sparse(mf_plan *p, const mf_shard *s_in, const mf_entry *aos, bool swap, const double *weight, std::vector<int> &rptr,
                  std::vector<int> &cptr)
 {
 	if (p->cfg.build_host) {   // MF_BUILD=host
@@ -308,10 +327,10 @@ int build_sparse(mf_plan *p, const mf_shard *s_in, const mf_entry *aos, bool swa
 			    s->col[n] >= s->items)
 				return MF_ERR_ARGUMENT;
 		std::vector<int> idx, pos_r, pos_c;
-		std::vector<double> val;
+		std::vector<double> val, wgt;
 		const size_t nz = (size_t) s->nnz;
 		try {
-			bucket(s->nnz, p->uc, s->row, p->u0, s->col, 0, s->val, rptr, idx, val, p->want_map ? &pos_r : nullptr);
+			bucket(s->nnz, p->uc, s->row, p->u0, s->col, 0, s->val, rptr, idx, val, p->want_map ? &pos_r : nullptr, weight, &wgt);
 		} catch (const std::bad_alloc &) {
 			return MF_ERR_NO_MEMORY;
 		}
@@ -335,8 +354,12 @@ int build_sparse(mf_plan *p, const mf_shard *s_in, const mf_entry *aos, bool swa
 			MF_HIP(h2d(p, p->csr_idx, idx.data(), nz * sizeof(int)));
 			MF_HIP(h2d(p, p->csr_val, val.data(), nz * sizeof(double)));
 		}
+		if (weight) {
+			MF_TRY(p->csr_wgt.alloc(nz + 64));
+			if (nz) MF_HIP(h2d(p, p->csr_wgt, wgt.data(), nz * sizeof(double)));
+		}
 		try {
-			bucket(s->nnz, p->items, s->col, 0, s->row, p->u0, s->val, cptr, idx, val, p->want_map ? &pos_c : nullptr);
+			bucket(s->nnz, p->items, s->col, 0, s->row, p->u0, s->val, cptr, idx, val, p->want_map ? &pos_c : nullptr, weight, &wgt);
 		} catch (const std::bad_alloc &) {
 			return MF_ERR_NO_MEMORY;
 		}
@@ -348,6 +371,10 @@ int build_sparse(mf_plan *p, const mf_shard *s_in, const mf_entry *aos, bool swa
 			MF_HIP(h2d(p, p->csc_idx, idx.data(), nz * sizeof(int)));
 			MF_HIP(h2d(p, p->csc_val, val.data(), nz * sizeof(double)));
 		}
+		if (weight) {
+			MF_TRY(p->csc_wgt.alloc(nz + 64));
+			if (nz) MF_HIP(h2d(p, p->csc_wgt, wgt.data(), nz * sizeof(double)));
+		}
 		if (p->want_map) {
 			std::vector<int> map(nz + 1);
 			for (size_t n = 0; n < nz; ++n) map[(size_t) pos_r[n]] = pos_c[n];
@@ -355,7 +382,7 @@ int build_sparse(mf_plan *p, const mf_shard *s_in, const mf_entry *aos, bool swa
 			if (nz) MF_HIP(h2d(p, p->csr2csc, map.data(), nz * sizeof(int)));
 		}
 	} else {
-		MF_TRY(build_on_device(p, s_in, aos, swap, rptr, cptr));
+		MF_TRY(build_on_device(p, s_in, aos, swap, weight, rptr, cptr));
 	}
 	return MF_OK;
 }
@@ -429,9 +456,12 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 		p->coop = SweepForm{p->sweep.coop, s.coop.nch, s.coop.lds, mf::kCoopWaves * mf::kWave};
 		MF_HIP(raise_lds_limit((const void *) p->coop.fn, p->coop.lds));
 		if (p->sweep.coop_mom) MF_HIP(raise_lds_limit((const void *) p->sweep.coop_mom, p->coop.lds));
+		if (p->weighted)
+			for (SweepFn fn : {p->sweep.coop_wd, p->sweep.coop_wm})
+				if (fn) MF_HIP(raise_lds_limit((const void *) fn, p->coop.lds));
 	}
 	if (s.extreme) {
-		p->prod = SweepForm{p->sweep.prod, s.prod_nch, s.prod_lds, mf::kWave};
+		p->prod = SweepForm{p->weighted ? p->sweep.prod_w : p->sweep.prod, s.prod_nch, s.prod_lds, mf::kWave};
 		p->lds_bytes_osum = mf::kOrderedSumLds;
 		MF_HIP(raise_lds_limit((const void *) p->prod.fn, p->prod.lds));
 		MF_HIP(raise_lds_limit(ordered_sum_fn(p->cfg), p->lds_bytes_osum));
@@ -476,7 +506,7 @@ int plan_es_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vector
 		MF_HIP(hipGetLastError());
 		MF_HIP(hipStreamSynchronize(p->stream));
 	}
-	MF_HIP(raise_lds_limit((const void *) p->sweep.errs, p->es_lds_errors));
+	MF_HIP(raise_lds_limit((const void *) (p->weighted ? p->sweep.errs_w : p->sweep.errs), p->es_lds_errors));
 	// ---- LDS-resident streams (mf_resident.hip.h): ~one workgroup per CU
 	int ncu = 256;
 	{

@@ -85,7 +85,7 @@ static int factor_buffers(mf_plan *p, void *const ext[2], int ext_pitch, int own
 }
 
 // everything of a new plan that can fail: the caller destroys the plan when it does
-static int plan_fill(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swap)
+static int plan_fill(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool swap, const double *weight)
 {
 	MF_TRY(choose_sweep(p));
 	MF_TRY(choose_loss(p));
@@ -93,7 +93,7 @@ static int plan_fill(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool sw
 	p->stream = p->own_stream;
 	{
 		std::vector<int> rptr, cptr;
-		MF_TRY(build_sparse(p, s, aos, swap, rptr, cptr));
+		MF_TRY(build_sparse(p, s, aos, swap, weight, rptr, cptr));
 		MF_TRY(plan_row_schedule(p, rptr, cptr));
 		MF_TRY(plan_es_schedule(p, rptr, cptr));
 	}
@@ -112,7 +112,8 @@ static int plan_fill(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool sw
 // `aos` (optional): the entries as the reference's array of (row, col, value) structs; they are then uploaded as they
 // are and split into the three arrays on the device (the level-1 entry points: no host-side copy of 1e8 entries).
 // `swap`: read the structs with row and col exchanged (the item-cut form of mf_backend_run_multi).
-static int plan_create_impl(mf_plan **out, const mf_shard *s, const mf_entry *aos, bool swap = false)
+// `weight` (optional): one confidence weight per entry, in the entries' order; null makes the plan of today in every respect.
+static int plan_create_impl(mf_plan **out, const mf_shard *s, const mf_entry *aos, bool swap = false, const double *weight = nullptr)
 {
 	if (!out) return MF_ERR_ARGUMENT;
 	*out = nullptr;
@@ -149,7 +150,8 @@ static int plan_create_impl(mf_plan **out, const mf_shard *s, const mf_entry *ao
 	p->alpha = s->alpha;
 	p->flags = s->flags;
 	p->cfg = mf_config::from_env();
-	const int rc = plan_fill(p, s, aos, swap);
+	p->weighted = weight != nullptr;   // in front of choose_sweep: it picks the launch limits of the weighted twins
+	const int rc = plan_fill(p, s, aos, swap, weight);
 	if (rc != MF_OK) {
 		mf_plan_destroy(p);
 		return rc;
@@ -175,6 +177,18 @@ static mf_shard whole_shard(int32_t users, int32_t items, int32_t features, int6
 extern "C" {
 
 int mf_plan_create(mf_plan **out, const mf_shard *s) { return plan_create_impl(out, s, nullptr); }
+
+int mf_plan_create_weighted(mf_plan **out, const mf_shard *s, const double *weight)
+{
+	return plan_create_impl(out, s, nullptr, false, weight);
+}
+
+int mf_plan_weight_total(mf_plan *p, double *sum_w, double *row_w)
+{
+	if (!p) return MF_ERR_ARGUMENT;
+	if (!p->weighted) return MF_ERR_STATE;
+	return weight_total_eval(p, sum_w, row_w);
+}
 
 int mf_backend_row_pitch(int features)
 {
@@ -361,7 +375,9 @@ int mf_plan_iterate(mf_plan *p, int iters)
 	// 0.70 -> 0.33 s and inst2 0.47 -> 0.21 s, but inst30-40 (170 entries x K=10) 0.32 -> 0.39 s -- one workgroup
 	// on an otherwise idle chip runs slowly, and two graph-replayed launches per iteration win again.
 	{
-		const size_t need = mf::resident_lds_bytes(p->uc, p->items, p->K, p->nnz);
+		// (the rule looks at the unweighted footprint: weights do not alter which form a plan takes; the request below holds them --
+		// 16 bytes per entry, at most 2 KiB where the footprint is near its bound, since nnz * K <= 512: never above 64 KiB)
+		size_t need = mf::resident_lds_bytes(p->uc, p->items, p->K, p->nnz);
 		const bool toy = p->uc == p->users_total && p->u0 == 0 && p->uc + p->items <= 1024 && p->uc + p->items > 0 &&
 		                 need <= 60 * 1024 && (double) p->nnz * p->K <= 512.0 && !p->timing && iters >= 8 &&
 		                 p->cfg.resident;
@@ -399,6 +415,9 @@ int mf_plan_iterate(mf_plan *p, int iters)
 			ra.R_hist = p->Rbuf[p->cur ^ 1];
 			ra.L_prev = p->Lbuf[fin ^ 1];
 			ra.R_prev = p->Rbuf[fin ^ 1];
+			ra.csr_wgt = p->csr_wgt;
+			ra.csc_wgt = p->csc_wgt;
+			if (p->weighted) need = mf::resident_lds_bytes(p->uc, p->items, p->K, p->nnz, true);
 			const bool momentum = p->beta[0] != 0.0 || p->beta[1] != 0.0;
 			const int threads = ((p->uc + p->items + 63) / 64) * 64;
 			void (*rfn)(mf::ResidentArgs) = p->K <= 4    ? mf::sweep_resident_kernel<4>
@@ -412,6 +431,18 @@ int mf_plan_iterate(mf_plan *p, int iters)
 				      : p->K <= 32 && threads <= mf::resident_max_threads(32)
 				          ? mf::sweep_resident_kernel<32, true>
 				          : mf::sweep_resident_kernel<0, true>;
+			if (p->weighted && !momentum)
+				rfn = p->K <= 4    ? mf::sweep_resident_kernel<4, false, true>
+				      : p->K <= 16 ? mf::sweep_resident_kernel<16, false, true>
+				      : p->K <= 32 && threads <= mf::resident_max_threads(32)
+				          ? mf::sweep_resident_kernel<32, false, true>
+				          : mf::sweep_resident_kernel<0, false, true>;
+			if (p->weighted && momentum)
+				rfn = p->K <= 4    ? mf::sweep_resident_kernel<4, true, true>
+				      : p->K <= 16 ? mf::sweep_resident_kernel<16, true, true>
+				      : p->K <= 32 && threads <= mf::resident_max_threads(32)
+				          ? mf::sweep_resident_kernel<32, true, true>
+				          : mf::sweep_resident_kernel<0, true, true>;
 			MF_HIP(raise_lds_limit((const void *) rfn, need));
 			hipLaunchKernelGGL(rfn, dim3(1), dim3(threads), need, p->stream, ra);
 			MF_HIP(hipGetLastError());
@@ -798,6 +829,11 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 		const size_t at = strlen(buf);
 		if (at + 1 < (size_t) buflen) snprintf(buf + at, (size_t) buflen - at, " frozen=%d/%d", p->frozen[1], p->frozen[0]);
 	}
+	// per-entry weights, when the plan was created with them
+	if (p->weighted) {
+		const size_t at = strlen(buf);
+		if (at + 1 < (size_t) buflen) snprintf(buf + at, (size_t) buflen - at, " weighted=1");
+	}
 	// the environment switches this plan was created under, when any differs from its default (mf_config.hip.h)
 	const std::string cfg = p->cfg.describe();
 	const size_t used = strlen(buf);
@@ -809,22 +845,22 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 
 /* ---------------------------------------------------------------------------------------- LEVEL 1 */
 
-static int make_single_plan(const mf_problem *pr, int device, mf_plan **out)
+static int make_single_plan(const mf_problem *pr, int device, mf_plan **out, const double *weight = nullptr)
 {
 	if (!pr || pr->users < 0 || pr->items < 0 || pr->features < 1 || pr->nnz < 0 || pr->iters < 0 ||
 	    (pr->nnz > 0 && !pr->entries))
 		return MF_ERR_ARGUMENT;
 	const mf_shard s = whole_shard(pr->users, pr->items, pr->features, pr->nnz, pr->alpha, device);
-	return plan_create_impl(out, &s, pr->entries);
+	return plan_create_impl(out, &s, pr->entries, false, weight);
 }
 
 // The level-1 sequence: a plan over the whole problem, the factors up, `work(plan)`, the plan destroyed.  Every entry
 // point checks its own arguments first.
 template <class Work>
-static int with_single_plan(const mf_problem *pr, int device, const double *L, const double *R, Work work)
+static int with_single_plan(const mf_problem *pr, int device, const double *L, const double *R, Work work, const double *weight = nullptr)
 {
 	mf_plan *p = nullptr;
-	int rc = make_single_plan(pr, device, &p);
+	int rc = make_single_plan(pr, device, &p, weight);
 	if (rc != MF_OK) return rc;
 	rc = mf_plan_upload_factors(p, L, R);
 	if (rc == MF_OK) rc = work(p);
@@ -871,6 +907,21 @@ int mf_backend_run_momentum(const mf_problem *pr, double *L, double *R, int32_t 
 		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
 		return rc;
 	});
+}
+
+int mf_backend_run_weighted(const mf_problem *pr, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
+                            double lambda_items, double beta_users, double beta_items, int device)
+{
+	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !lambda_ok(beta_users) || !lambda_ok(beta_items))
+		return MF_ERR_ARGUMENT;
+	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
+		int rc = mf_plan_set_regularization(p, lambda_users, lambda_items);
+		if (rc == MF_OK) rc = mf_plan_set_momentum(p, beta_users, beta_items);
+		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
+		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
+		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
+		return rc;
+	}, weight);
 }
 
 // ---- biases on frozen columns: a ~ mu + b_user + b_item + l.r as the K = F + 2 product of

@@ -81,6 +81,7 @@ size_t tile_head_bytes(const mf_plan *p) { return p->sweep.dma ? (size_t) p->swe
 struct SideOperands {
 	const int *ptr, *idx;
 	const double *val;
+	const double *wgt;          // the entries' weights in the order of (idx, val); null on an unweighted plan
 	const mf::StreamRec *rec;   // the side's {idx, e_n} records (errors + streams iteration)
 	const double *X_old, *Y_old;
 	double *X_new;
@@ -91,8 +92,8 @@ SideOperands side_operands(const mf_plan *p, int kind)
 {
 	const int cur = p->cur, nxt = p->cur ^ 1;
 	if (kind == 0)
-		return {p->csc_ptr, p->csc_idx, p->csc_val, p->rec_csc, p->Rbuf[cur], p->Lbuf[cur], p->Rbuf[nxt], p->ldr, p->ldl, p->uc};
-	return {p->csr_ptr, p->csr_idx, p->csr_val, p->rec_csr, p->Lbuf[cur], p->Rbuf[cur], p->Lbuf[nxt], p->ldl, p->ldr, p->items};
+		return {p->csc_ptr, p->csc_idx, p->csc_val, p->csc_wgt, p->rec_csc, p->Rbuf[cur], p->Lbuf[cur], p->Rbuf[nxt], p->ldr, p->ldl, p->uc};
+	return {p->csr_ptr, p->csr_idx, p->csr_val, p->csr_wgt, p->rec_csr, p->Lbuf[cur], p->Rbuf[cur], p->Lbuf[nxt], p->ldl, p->ldr, p->items};
 }
 
 // the ordered-sum kernel (MF_OS_DPP) and the resident streams kernel of a slice width
@@ -145,6 +146,9 @@ int choose_sweep(mf_plan *p)
 	if (p->sweep.pf_decay) MF_HIP(raise_lds_limit((const void *) p->sweep.pf_decay, std::max(p->single.lds, p->few.lds)));
 	if (p->sweep.fn_mom) MF_HIP(raise_lds_limit((const void *) p->sweep.fn_mom, std::max(p->single.lds, p->few.lds)));
 	if (p->sweep.pf_mom) MF_HIP(raise_lds_limit((const void *) p->sweep.pf_mom, std::max(p->single.lds, p->few.lds)));
+	if (p->weighted)   // the weighted twins, on weighted plans only: an unweighted plan touches none of them
+		for (SweepFn fn : {p->sweep.fn_wd, p->sweep.pf_wd, p->sweep.fn_wm, p->sweep.pf_wm})
+			if (fn) MF_HIP(raise_lds_limit((const void *) fn, std::max(p->single.lds, p->few.lds)));
 	// the two-tile forms: `dflt` entries per chunk (MF_SWEEP_NCH overrides) while two tiles stay within half a CU's LDS
 	auto two_tiles = [&](SweepFn fn, int dflt, int block) {
 		int n = p->cfg.sweep_nch ? p->cfg.sweep_nch : dflt;
@@ -157,11 +161,17 @@ int choose_sweep(mf_plan *p)
 		p->pair = two_tiles(p->sweep.pair, 32, 2 * mf::kWave);
 		MF_HIP(raise_lds_limit((const void *) p->pair.fn, p->pair.lds));
 		if (p->sweep.pair_mom) MF_HIP(raise_lds_limit((const void *) p->sweep.pair_mom, p->pair.lds));
+		if (p->weighted)
+			for (SweepFn fn : {p->sweep.pair_wd, p->sweep.pair_wm})
+				if (fn) MF_HIP(raise_lds_limit((const void *) fn, p->pair.lds));
 	}
 	if (p->sweep.db) {   // double-buffered form (few rows per CU: the wave hides its own gather)
 		p->db = two_tiles(p->sweep.db, 16, mf::kWave);
 		MF_HIP(raise_lds_limit((const void *) p->db.fn, p->db.lds));
 		if (p->sweep.db_mom) MF_HIP(raise_lds_limit((const void *) p->sweep.db_mom, p->db.lds));
+		if (p->weighted)
+			for (SweepFn fn : {p->sweep.db_wd, p->sweep.db_wm})
+				if (fn) MF_HIP(raise_lds_limit((const void *) fn, p->db.lds));
 	}
 	// ---- errors + streams iteration (mf_stream.hip.h) for instances whose factors stay in L2 / Infinity Cache: the
 	// two sweeps are then bound by the latency of one wave walking a row chunk by chunk, not by bandwidth.  It costs a
@@ -194,6 +204,11 @@ int choose_loss(mf_plan *p)
 	p->loss_lds[0] = head + (size_t) cs.nch * row_bytes;
 	p->loss_lds[1] = head + (size_t) cs.nch_few * row_bytes;
 	MF_HIP(raise_lds_limit((const void *) p->loss_fn, std::max(p->loss_lds[0], p->loss_lds[1])));
+	if (p->weighted) {   // the training loss of a weighted plan: the weighted twin in the same geometry
+		p->loss_fn_w = p->sweep.dma ? p->sweep.loss_w : mf::loss_reg_w_kernel;
+		if (!p->loss_fn_w) return MF_ERR_UNSUPPORTED;
+		MF_HIP(raise_lds_limit((const void *) p->loss_fn_w, std::max(p->loss_lds[0], p->loss_lds[1])));
+	}
 	return MF_OK;
 }
 
@@ -216,9 +231,25 @@ bool single_wave_pipelined(const mf_plan *p, int kind)
 // pipelined by single_wave_pipelined, at the large chunk when `few_rows`.
 // `momentum`: the launch is a seeded sweep of a side with beta != 0 -- every form then runs its momentum instance (null
 // where a K has none: launch_sweep refuses); without it the choice and the kernels are those of a plan without momentum.
-SweepForm main_form(const mf_plan *p, int kind, bool few_rows, bool decay, bool momentum)
+// `weighted`: the plan carries per-entry weights -- the same form at the same geometry (weights do not alter which form a
+// side takes) in its weighted twin: of the momentum instance under `momentum`, else of the decay instance, whatever d is.
+SweepForm main_form(const mf_plan *p, int kind, bool few_rows, bool decay, bool momentum, bool weighted = false)
 {
 	const SweepSide &sd = p->side[kind];
+	if (weighted) {
+		SweepForm f = main_form(p, kind, few_rows, decay, false);
+		if (sd.coop_all)
+			f.fn = momentum ? p->sweep.coop_wm : p->sweep.coop_wd;
+		else if (sd.use_db)
+			f.fn = momentum ? p->sweep.db_wm : p->sweep.db_wd;
+		else if (sd.use_pair)
+			f.fn = momentum ? p->sweep.pair_wm : p->sweep.pair_wd;
+		else if (p->sweep.dma && single_wave_pipelined(p, kind))
+			f.fn = momentum ? p->sweep.pf_wm : p->sweep.pf_wd;
+		else
+			f.fn = momentum ? p->sweep.fn_wm : p->sweep.fn_wd;
+		return f;
+	}
 	if (momentum) {
 		SweepForm f = main_form(p, kind, few_rows, decay, false);
 		if (sd.coop_all)
@@ -304,6 +335,7 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	a.ptr = x.ptr;
 	a.idx = x.idx;
 	a.val = x.val;
+	a.wgt = x.wgt;
 	a.X_old = x.X_old;
 	a.Y_old = x.Y_old;
 	a.X_new = x.X_new;
@@ -316,7 +348,7 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	const bool extreme = sd.n_long > 0;
 	// the large chunk below kSweepFewRows rows.  Never beside the extreme-row path: with the extreme rows gone the
 	// occupancy-friendly chunk size is right again.
-	const SweepForm f = main_form(p, kind, !extreme && a.nrows < kSweepFewRows, a.d != 1.0 || a.frozen >= 0, momentum);
+	const SweepForm f = main_form(p, kind, !extreme && a.nrows < kSweepFewRows, a.d != 1.0 || a.frozen >= 0, momentum, p->weighted);
 	if (!f.fn) return MF_ERR_UNSUPPORTED;
 	a.nch = f.nch;
 	TimedLaunch t{};
@@ -421,6 +453,7 @@ int launch_es_iteration(mf_plan *p)
 	a.ptr = users.ptr;
 	a.idx = users.idx;
 	a.val = users.val;
+	a.wgt = users.wgt;   // folded into e_n by the errors launch: the records and the streams launch need nothing new
 	a.X_old = users.X_old;
 	a.Y_old = users.Y_old;
 	a.X_new = nullptr;
@@ -459,7 +492,7 @@ int launch_es_iteration(mf_plan *p)
 		MF_HIP(hipEventRecord(t0.t0, p->stream));
 	}
 	void *eargs[] = {&a};
-	MF_HIP(hipLaunchKernel((const void *) p->sweep.errs, dim3(p->es_nseg), dim3(mf::kWave), eargs, p->es_lds_errors,
+	MF_HIP(hipLaunchKernel((const void *) (p->weighted ? p->sweep.errs_w : p->sweep.errs), dim3(p->es_nseg), dim3(mf::kWave), eargs, p->es_lds_errors,
 	                       p->stream));
 	if (p->timing) MF_HIP(hipEventRecord(t0.t1, p->stream));
 	{

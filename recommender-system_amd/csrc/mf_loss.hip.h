@@ -1,7 +1,8 @@
 // mf_loss.hip.h -- squared error of L * R^T over an entry set (the training entries or a held-out set), in a fixed
 // order of every floating-point operation (include/matfact_hip.h, mf_plan_loss):
 //   p_n = dot(L[i_n], R[j_n])      sequential k from 0.0, multiply and add unfused  (mat2d.c:126-139, as phase A of the sweeps)
-//   q_n = (a_n - p_n) * (a_n - p_n)
+//   q_n = (a_n - p_n) * (a_n - p_n)                  times w_n, one more rounded multiply, in the weighted instances (the
+//                                                    training loss of a plan created with per-entry weights)
 //   s_i = ((0.0 + q_n0) + q_n1) + ...   over the entries of user i in the order of the CSR (the caller's order)
 //   T_b = the s_i of the users [1024 b, 1024 (b + 1)) (GLOBAL user ids) added in ascending i from 0.0
 //   SSE = the T_b added in ascending b from 0.0
@@ -28,6 +29,7 @@ struct LossArgs {
 	const double *__restrict__ R;
 	double *__restrict__ row_sse;
 	const int *__restrict__ rowlist;   // optional: the order in which the workgroups take the rows (all of them)
+	const double *__restrict__ wgt;    // weighted instances only: the entries' weights in the order of (idx, val)
 };
 
 // q = (a - p) * (a - p), formed as (p - a) * (p - a): the same bits for every a and p that are not NaN (IEEE subtraction is
@@ -148,6 +150,98 @@ __global__ void __launch_bounds__(kWave) loss_dma_kernel(LossArgs a)
 	}
 }
 
+// The weighted twin: the kernel above with q_n * w_n, the weight loaded where val is (a name of its own: the unweighted
+// instances are counted by name, and their code stays exactly what it was).
+template <int KT, int NPASS>
+__global__ void __launch_bounds__(kWave) loss_dma_w_kernel(LossArgs a)
+{
+	const int K = KT > 0 ? KT : a.K;
+	const int P = dma_pieces(K);
+	constexpr int NP = NPASS;
+	const int S = dma_row_stride(K);
+	const int xs_bytes = dma_xs_bytes(K);
+	extern __shared__ __attribute__((aligned(16))) char lds[];
+	double2 *xs = reinterpret_cast<double2 *>(lds);
+	char *tile = lds + xs_bytes;
+	const int nch = a.nch;
+	const int lane = threadIdx.x;
+	const unsigned voff = (unsigned) lane * 16u;
+	const unsigned long long ybase = (unsigned long long) a.R;
+	const size_t ybytes = (size_t) a.ldr * 8;   // bytes between rows of R
+
+	for (int it = blockIdx.x; it < a.nrows; it += gridDim.x) {
+		const int r = a.rowlist ? a.rowlist[it] : it;
+		const int beg = a.ptr[r], end = a.ptr[r + 1];
+		const double2 *__restrict__ xrow2 = reinterpret_cast<const double2 *>(a.L + (size_t) r * a.ldl);
+#pragma unroll
+		for (int p = 0; p < NP; ++p) {
+			const int q = lane + kWave * p;
+			if (q < P) xs[q] = xrow2[q];
+		}
+
+		double s = 0.0;
+		// (idx, val) of a chunk are loaded one chunk ahead, so the gather of chunk c never waits on them
+		int nx_idx = 0;
+		double nx_val = 0.0;
+		double nx_wgt = 0.0;
+		if (beg + lane < min(end, beg + nch)) {
+			nx_idx = a.idx[beg + lane];
+			nx_val = a.val[beg + lane];
+			nx_wgt = a.wgt[beg + lane];
+		}
+		for (int c = beg; c < end; c += nch) {
+			const int cnt = min(nch, end - c);
+			const int my_idx = nx_idx;
+			const double my_val = nx_val;
+			const double my_wgt = nx_wgt;
+			if (c + nch + lane < min(end, c + 2 * nch)) {
+				nx_idx = a.idx[c + nch + lane];
+				nx_val = a.val[c + nch + lane];
+				nx_wgt = a.wgt[c + nch + lane];
+			}
+			// ---- stage (as sweep_dma_kernel): short rows several per instruction, the others one instruction per row and pass
+			if constexpr (KT > 0 && dma_multi_row(KT))
+				gather_multi_row<KT>(ybase, ybytes, my_idx, cnt, lane, tile);
+			else
+				gather_rows<NP>(ybase, ybytes, my_idx, cnt, lane, voff, P, S, tile);
+			__syncthreads();   // single-wave workgroup: this is the vmcnt(0)/lgkmcnt(0) that retires the DMA
+			// ---- phase A (lanes beyond the tile re-read row 0; lanes >= cnt produce garbage that never enters the chain)
+			const double2 *t2 = reinterpret_cast<const double2 *>(tile + (lane < nch ? lane : 0) * S);
+			double dot = 0.0;
+			if constexpr (KT > 0) {
+				dot = phase_a_dot<KT>(t2, xs);
+			} else {
+				int i = 0;
+				for (; i + 4 <= P; i += 4) {
+					double2 t[4], x[4];
+#pragma unroll
+					for (int u = 0; u < 4; ++u) {
+						t[u] = t2[i + u];
+						x[u] = xs[i + u];
+					}
+#pragma unroll
+					for (int u = 0; u < 4; ++u) {
+						dot = dot + x[u].x * t[u].x;
+						dot = dot + x[u].y * t[u].y;
+					}
+				}
+				for (; i < P; ++i) {
+					const double2 t = t2[i];
+					const double2 x = xs[i];
+					dot = dot + x.x * t.x;
+					dot = dot + x.y * t.y;
+				}
+			}
+			double q = loss_square(my_val, dot);
+			q = q * my_wgt;
+			s = loss_chain(s, q, cnt);
+			__syncthreads();   // tile is overwritten by the next chunk's DMA
+		}
+		if (lane == 0) a.row_sse[r] = s;
+		__syncthreads();   // xs is overwritten by the next row
+	}
+}
+
 // ------------------------------------------------------------------------------------------------
 // Row sums, register-staged form (odd K, K beyond the LDS-DMA geometry, MF_SWEEP_IMPL=reg): stage and phase A of
 // sweep_kernel.  It keeps no accumulators, so one instance serves every K.
@@ -190,6 +284,70 @@ __global__ void __launch_bounds__(kWave) loss_reg_kernel(LossArgs a)
 			__syncthreads();
 		}
 		if (lane == 0) a.row_sse[r] = s;
+	}
+}
+
+// the weighted twin of loss_reg_kernel: q_n * w_n
+__global__ void __launch_bounds__(kWave) loss_reg_w_kernel(LossArgs a)
+{
+	extern __shared__ double loss_tile[];
+	const int K = a.K;
+	const int stride = a.stride;
+	const int nch = a.nch;
+	const int lane = threadIdx.x;
+
+	for (int it = blockIdx.x; it < a.nrows; it += gridDim.x) {
+		const int r = a.rowlist ? a.rowlist[it] : it;
+		const int beg = a.ptr[r], end = a.ptr[r + 1];
+		const double *__restrict__ xrow = a.L + (size_t) r * a.ldl;
+		double s = 0.0;
+		for (int c = beg; c < end; c += nch) {
+			const int cnt = min(nch, end - c);
+			int my_idx = 0;
+			double my_val = 0.0;
+			double my_wgt = 0.0;
+			if (lane < cnt) {
+				my_idx = a.idx[c + lane];
+				my_val = a.val[c + lane];
+				my_wgt = a.wgt[c + lane];
+			}
+			for (int n = 0; n < cnt; ++n) {
+				const int j = __builtin_amdgcn_readlane(my_idx, n);
+				const double *__restrict__ yrow = a.R + (size_t) j * a.ldr;
+				double *trow = loss_tile + n * stride;
+				for (int k = lane; k < K; k += kWave)
+					trow[k] = yrow[k];
+			}
+			__syncthreads();
+			const double *t = loss_tile + (lane < nch ? lane : 0) * stride;   // lanes beyond the tile re-read row 0
+			double dot = 0.0;
+#pragma unroll 8
+			for (int k = 0; k < K; ++k)
+				dot = dot + xrow[k] * t[k];
+			double q = loss_square(my_val, dot);
+			q = q * my_wgt;
+			s = loss_chain(s, q, cnt);
+			__syncthreads();
+		}
+		if (lane == 0) a.row_sse[r] = s;
+	}
+}
+
+// Row sums of the weights (mf_plan_weight_total): s_i = ((0.0 + w_n0) + w_n1) + ... over the entries of user i in the order
+// of the CSR, one wave per user; loss_block_kernel and loss_total_kernel then add the rows up (step 4 of the loss).
+__global__ void __launch_bounds__(kWave) weight_rows_kernel(const int *__restrict__ ptr, const double *__restrict__ wgt, int nrows,
+                                                             double *__restrict__ row_w)
+{
+	const int lane = threadIdx.x;
+	for (int r = blockIdx.x; r < nrows; r += gridDim.x) {
+		const int beg = ptr[r], end = ptr[r + 1];
+		double s = 0.0;
+		for (int c = beg; c < end; c += kWave) {
+			const int cnt = min(kWave, end - c);
+			const double v = lane < cnt ? wgt[c + lane] : 0.0;
+			s = loss_chain(s, v, cnt);
+		}
+		if (lane == 0) row_w[r] = s;
 	}
 }
 

@@ -9,20 +9,24 @@ int blocks_touched(int begin, int rows)
 	return rows > 0 ? (int) (((long long) begin + rows - 1) / mf::kLossBlock - begin / mf::kLossBlock + 1) : 0;
 }
 
+// the row sums, block sums and total of an evaluation, allocated on first use
+int loss_buffers(mf_plan *p)
+{
+	if (p->row_sse) return MF_OK;   // the three are allocated together; row_sse marks them
+	int rc = p->row_sse.alloc((size_t) p->uc);
+	if (rc == MF_OK) rc = p->loss_blocks.alloc((size_t) blocks_touched(p->u0, p->uc));
+	if (rc == MF_OK) rc = p->loss_total.alloc(1);
+	if (rc != MF_OK) p->row_sse.reset();
+	return rc;
+}
+
 // Row sums of one entry set (CSR over the plan's users) into p->row_sse, then the block sums and the total, all on the
-// plan's stream.  `order`: optional list of all rows in the order the workgroups take them.
-int launch_loss(mf_plan *p, const int *ptr, const int *idx, const double *val, const int *order)
+// plan's stream.  `order`: optional list of all rows in the order the workgroups take them.  `wgt`: the entries' weights
+// (the training set of a weighted plan: q_n * w_n, in the weighted twin of the row-sum kernel) or null.
+int launch_loss(mf_plan *p, const int *ptr, const int *idx, const double *val, const int *order, const double *wgt = nullptr)
 {
 	const int nblocks = blocks_touched(p->u0, p->uc);
-	if (!p->row_sse) {   // the three are allocated together; row_sse marks them
-		int rc = p->row_sse.alloc((size_t) p->uc);
-		if (rc == MF_OK) rc = p->loss_blocks.alloc((size_t) nblocks);
-		if (rc == MF_OK) rc = p->loss_total.alloc(1);
-		if (rc != MF_OK) {
-			p->row_sse.reset();
-			return rc;
-		}
-	}
+	MF_TRY(loss_buffers(p));
 	if (p->uc > 0) {
 		mf::LossArgs a;
 		a.nrows = p->uc;
@@ -37,10 +41,11 @@ int launch_loss(mf_plan *p, const int *ptr, const int *idx, const double *val, c
 		a.R = p->Rbuf[p->cur];
 		a.row_sse = p->row_sse;
 		a.rowlist = order;
+		a.wgt = wgt;
 		const int few = a.nrows < kSweepFewRows ? 1 : 0;
 		a.nch = p->loss_nch[few];
 		void *args[] = {&a};
-		MF_HIP(hipLaunchKernel((const void *) p->loss_fn, dim3(std::min(a.nrows, 1 << 20)), dim3(mf::kWave), args, p->loss_lds[few],
+		MF_HIP(hipLaunchKernel((const void *) (wgt ? p->loss_fn_w : p->loss_fn), dim3(std::min(a.nrows, 1 << 20)), dim3(mf::kWave), args, p->loss_lds[few],
 		                       p->stream));
 		hipLaunchKernelGGL(mf::loss_block_kernel, dim3(nblocks), dim3(mf::kWave), 0, p->stream, p->row_sse, p->u0, p->uc, nblocks,
 		                   p->loss_blocks);
@@ -56,8 +61,8 @@ int loss_eval(mf_plan *p, int which, mf_loss *out, double *row_sse)
 {
 	MF_HIP(hipSetDevice(p->device));
 	const bool train = which == MF_LOSS_TRAIN;
-	const int rc = train ? launch_loss(p, p->csr_ptr, p->csr_idx, p->csr_val, p->side[1].lpt ? p->side[1].short_rows.get() : nullptr)
-	                     : launch_loss(p, p->ho_ptr, p->ho_idx, p->ho_val, nullptr);
+	const int rc = train ? launch_loss(p, p->csr_ptr, p->csr_idx, p->csr_val, p->side[1].lpt ? p->side[1].short_rows.get() : nullptr, p->csr_wgt)
+	                     : launch_loss(p, p->ho_ptr, p->ho_idx, p->ho_val, nullptr);   // the held-out set stays unweighted
 	if (rc != MF_OK) return rc;
 	double sse = 0.0;
 	MF_HIP(hipMemcpyAsync(&sse, p->loss_total, sizeof(double), hipMemcpyDeviceToHost, p->stream));
@@ -66,6 +71,31 @@ int loss_eval(mf_plan *p, int which, mf_loss *out, double *row_sse)
 	MF_HIP(hipStreamSynchronize(p->stream));
 	out->sse = sse;
 	out->count = train ? p->nnz : p->ho_nnz;
+	return MF_OK;
+}
+
+// The weights of a weighted plan added up: row sums per user in entry order, then step 4 of the loss, in the loss's
+// buffers; the total (and the row sums when asked for) back to the host, complete on return.
+int weight_total_eval(mf_plan *p, double *sum_w, double *row_w)
+{
+	MF_HIP(hipSetDevice(p->device));
+	const int nblocks = blocks_touched(p->u0, p->uc);
+	MF_TRY(loss_buffers(p));
+	if (p->uc > 0) {
+		hipLaunchKernelGGL(mf::weight_rows_kernel, dim3(std::min(p->uc, 1 << 20)), dim3(mf::kWave), 0, p->stream, p->csr_ptr.get(),
+		                   p->csr_wgt.get(), p->uc, p->row_sse.get());
+		MF_HIP(hipGetLastError());
+		hipLaunchKernelGGL(mf::loss_block_kernel, dim3(nblocks), dim3(mf::kWave), 0, p->stream, p->row_sse, p->u0, p->uc, nblocks,
+		                   p->loss_blocks);
+		MF_HIP(hipGetLastError());
+	}
+	hipLaunchKernelGGL(mf::loss_total_kernel, dim3(1), dim3(mf::kWave), 0, p->stream, p->loss_blocks, nblocks, p->loss_total);
+	MF_HIP(hipGetLastError());
+	double total = 0.0;
+	MF_HIP(hipMemcpyAsync(&total, p->loss_total, sizeof(double), hipMemcpyDeviceToHost, p->stream));
+	if (row_w && p->uc > 0) MF_HIP(hipMemcpyAsync(row_w, p->row_sse, (size_t) p->uc * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+	MF_HIP(hipStreamSynchronize(p->stream));
+	if (sum_w) *sum_w = total;
 	return MF_OK;
 }
 

@@ -41,6 +41,13 @@ struct SweepVariant {
 	LossFn loss = nullptr;    // row sums of mf_plan_loss in the same geometry (all DMA variants; the others use loss_reg_kernel)
 	// the momentum instances of the forms above (a seeded sweep of a side with beta != 0): each where its plain twin is
 	SweepFn fn_mom = nullptr, pf_mom = nullptr, coop_mom = nullptr, db_mom = nullptr, pair_mom = nullptr;
+	// the weighted twins (a plan created with per-entry weights): of the decay instances -- also what lambda = 0, beta = 0
+	// runs, at d = 1.0 -- and of the momentum instances, per form; weighted products and errors; the weighted row sums of
+	// the training loss
+	SweepFn fn_wd = nullptr, pf_wd = nullptr, coop_wd = nullptr, db_wd = nullptr, pair_wd = nullptr;
+	SweepFn fn_wm = nullptr, pf_wm = nullptr, coop_wm = nullptr, db_wm = nullptr, pair_wm = nullptr;
+	SweepFn prod_w = nullptr, errs_w = nullptr;
+	LossFn loss_w = nullptr;
 };
 
 template <int KT, int KP>
@@ -49,16 +56,18 @@ constexpr SweepVariant variant()
 	SweepVariant v;
 	v.fn = mf::sweep_kernel<KT, KP>;
 	v.fn_mom = mf::sweep_kernel<KT, KP, true>;
+	v.fn_wd = mf::sweep_kernel<KT, KP, false, true>;
+	v.fn_wm = mf::sweep_kernel<KT, KP, true, true>;
 	v.kt = KT;
 	v.kpmax = KP;
 	return v;
 }
 
-template <int KT, bool MOM = false>
+template <int KT, bool MOM = false, bool WGT = false>
 constexpr SweepFn pair_fn()
 {
 	if constexpr (mf::DmaGeom<KT>::kOnePassWide)
-		return mf::sweep_pair_kernel<KT, 1, MOM>;
+		return mf::sweep_pair_kernel<KT, 1, MOM, WGT>;
 	else
 		return nullptr;
 }
@@ -88,6 +97,19 @@ constexpr SweepVariant dma_variant()
 	v.db_mom = mf::sweep_db_kernel<KT, NP, true>;
 	v.pair_mom = pair_fn<KT, true>();
 	v.loss = mf::loss_dma_kernel<KT, NP>;
+	if constexpr (KT <= 128) v.fn_wd = mf::sweep_dma_kernel<KT, NP, mf::kSweepDecayW>;
+	v.pf_wd = mf::sweep_dma_kernel<KT, NP, mf::kSweepDecayW, 8>;
+	if constexpr (KT <= 128) v.fn_wm = mf::sweep_dma_kernel<KT, NP, mf::kSweepMomentumW>;
+	v.pf_wm = mf::sweep_dma_kernel<KT, NP, mf::kSweepMomentumW, 8>;
+	v.coop_wd = mf::sweep_coop_kernel<KT, false, true>;
+	v.coop_wm = mf::sweep_coop_kernel<KT, true, true>;
+	v.db_wd = mf::sweep_db_kernel<KT, NP, false, true>;
+	v.db_wm = mf::sweep_db_kernel<KT, NP, true, true>;
+	v.pair_wd = pair_fn<KT, false, true>();
+	v.pair_wm = pair_fn<KT, true, true>();
+	v.prod_w = mf::sweep_dma_kernel<KT, NP, mf::kSweepProductsW>;
+	v.errs_w = mf::sweep_dma_kernel<KT, NP, mf::kSweepErrorsW>;
+	v.loss_w = mf::loss_dma_w_kernel<KT, NP>;
 	return v;
 }
 
@@ -106,6 +128,13 @@ constexpr SweepVariant dma_generic_variant()
 	v.fn_mom = mf::sweep_dma_kernel<0, NPASS, mf::kSweepMomentum>;
 	v.db_mom = mf::sweep_db_kernel<0, NPASS, true>;
 	v.loss = mf::loss_dma_kernel<0, NPASS>;
+	v.fn_wd = mf::sweep_dma_kernel<0, NPASS, mf::kSweepDecayW>;
+	v.fn_wm = mf::sweep_dma_kernel<0, NPASS, mf::kSweepMomentumW>;
+	v.db_wd = mf::sweep_db_kernel<0, NPASS, false, true>;
+	v.db_wm = mf::sweep_db_kernel<0, NPASS, true, true>;
+	v.prod_w = mf::sweep_dma_kernel<0, NPASS, mf::kSweepProductsW>;
+	v.errs_w = mf::sweep_dma_kernel<0, NPASS, mf::kSweepErrorsW>;
+	v.loss_w = mf::loss_dma_w_kernel<0, NPASS>;
 	return v;
 }
 
@@ -217,6 +246,10 @@ struct mf_plan {
 	dev_buf<double> csr_val;
 	dev_buf<int> csc_ptr, csc_idx;
 	dev_buf<double> csc_val;
+	// per-entry confidence weights (mf_plan_create_weighted), in CSR and in CSC order beside the values; a plan created
+	// without weights allocates neither and launches the unweighted kernels
+	bool weighted = false;
+	dev_buf<double> csr_wgt, csc_wgt;
 	dev_buf<int> mask_idx;   // item ids ascending inside every user's row, only when the file order is not (recommend mask)
 	// errors + streams iteration (mf_stream.hip.h): CSR position -> CSC position, the {idx, e_n} records in both orders, the segment table
 	// of the errors launch and the task list (both factors' rows, longest first) of the streams launch
@@ -262,6 +295,7 @@ struct mf_plan {
 	// loss (mf_plan_loss, mf_loss.hip.h): row sums, block sums and total, allocated on first use; the held-out set as a
 	// second CSR over the shard's users (entries of a user in the caller's order)
 	LossFn loss_fn = nullptr;
+	LossFn loss_fn_w = nullptr;      // its weighted twin (the training loss of a weighted plan)
 	int loss_nch[2] = {0, 0};        // chunk size of the row-sum launch: [0] ordinary, [1] fewer rows than fill the chip
 	size_t loss_lds[2] = {0, 0};     // its LDS request (the L row + ONE tile)
 	dev_buf<double> row_sse, loss_blocks, loss_total;

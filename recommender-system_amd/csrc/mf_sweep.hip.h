@@ -23,7 +23,9 @@ namespace mf {
 // the add that follows; d = 1.0 leaves the bits of X_old), or 0 for the non-root contribution of a sharded item sweep
 // (matFact-mpi.c:187): the decay is applied where the seed is taken, once.  With heavy-ball momentum (beta != 0 and a
 // seed) the seed is (X_old[r][k] * d) + beta * (X_old[r][k] - X_prev[r][k]), X_prev being what X_new[r][k] holds at launch
-// (momentum_seed below; include/matfact_hip.h has the definition).  Mapping onto the wave, per chunk of <= nch entries of the row:
+// (momentum_seed below; include/matfact_hip.h has the definition).  On a plan created with per-entry weights e_n is
+// (c2 * (val_n - dot_n)) * wgt_n -- one more rounded multiply where e_n is formed, in kernel instances of their own (WGT /
+// the weighted modes of sweep_dma_kernel); everything behind e_n is unchanged.  Mapping onto the wave, per chunk of <= nch entries of the row:
 //   stage   the nch gathered Y rows are copied, coalesced (16 B per lane), into an LDS tile whose row
 //           stride is odd in doubles, so both access patterns below are bank-conflict-free;
 //   phase A lane n walks row n of the tile and forms dot_n sequentially in k (the serial order) with
@@ -70,6 +72,9 @@ struct SweepArgs {
 	// heavy-ball momentum of the side: read by the momentum instances only, which launch_sweep picks for a seeded sweep
 	// with beta != 0 (X_prev is read through X_new: the owner of a row reads it before it writes it)
 	double beta;
+	// per-entry confidence weights in the order of (idx, val), or null: read by the weighted instances only, which the launch
+	// picks for a plan created with weights -- e_n = (c2 * (val_n - dot_n)) * wgt_n, one more rounded multiply, unfused
+	const double *__restrict__ wgt;
 };
 
 // The seed of one element under momentum: one rounded subtraction, one rounded multiply, the decay's multiply, one rounded
@@ -95,7 +100,7 @@ __device__ __forceinline__ double readlane_f64(double v, int lane)
 // LDS row stride of the register-staged form in doubles: odd, so both access patterns are bank-conflict-free
 __host__ __device__ constexpr int reg_row_stride(int K) { return K | 1; }
 
-template <int KT, int KPMAX, bool MOM = false>
+template <int KT, int KPMAX, bool MOM = false, bool WGT = false>
 __global__ void __launch_bounds__(kWave) sweep_kernel(SweepArgs a)
 {
 	extern __shared__ double tile[];
@@ -123,9 +128,11 @@ __global__ void __launch_bounds__(kWave) sweep_kernel(SweepArgs a)
 			const int cnt = min(nch, end - c);
 			int my_idx = 0;
 			double my_val = 0.0;
+			[[maybe_unused]] double my_wgt = 0.0;
 			if (lane < cnt) {
 				my_idx = a.idx[c + lane];
 				my_val = a.val[c + lane];
+				if constexpr (WGT) my_wgt = a.wgt[c + lane];
 			}
 			// ---- stage: gathered rows -> LDS tile (row n of the tile = Y_old[idx_n][:])
 			for (int n = 0; n < cnt; ++n) {
@@ -154,6 +161,7 @@ __global__ void __launch_bounds__(kWave) sweep_kernel(SweepArgs a)
 				for (int k = 0; k < K; ++k)
 					dot = dot + xrow[k] * t[k];
 				e = a.c2 * (my_val - dot);
+				if constexpr (WGT) e = e * my_wgt;
 			}
 			// ---- phase B: lane l -> columns l, l+64, ...; entries in order
 			for (int n = 0; n < cnt; ++n) {
@@ -588,10 +596,13 @@ __device__ __forceinline__ void phase_b_tail(const char *tb, int S, double e, in
 // 3 accumulate with the seed multiplied by the decay factor a.d -- launch_sweep picks it when d != 1.0, so the instances
 // of mode 0, the timed path of an unregularised run, keep their code.  Mode 3 also carries the frozen column (a.frozen):
 // launch_sweep picks it for a frozen side at d = 1.0 too, x * 1.0 being x; 4 mode 3 with the momentum term added to the
-// seed (a seeded sweep of a side with beta != 0)
+// seed (a seeded sweep of a side with beta != 0); 5 .. 8 the weighted twins of modes 3, 4, 1 and 2 -- e_n times the entry's
+// weight a.wgt[n], loaded where val is -- which a plan created with weights launches in their place (at d = 1.0 and beta = 0
+// mode 5: a weighted plan has no twin of mode 0)
 // PF > 0: phases A and B keep their LDS reads in flight and the gather issue is lean.
 // ------------------------------------------------------------------------------------------------
 constexpr int kSweepAccumulate = 0, kSweepProducts = 1, kSweepErrors = 2, kSweepDecay = 3, kSweepMomentum = 4;
+constexpr int kSweepDecayW = 5, kSweepMomentumW = 6, kSweepProductsW = 7, kSweepErrorsW = 8;
 #ifdef MF_STAMPS
 // diagnostic build only (tools/stamps.py): shader-clock totals of the phases of the rows of at least 1024 entries --
 // [0] rows, [1] chunks, [2] gather issue, [3] landing wait, [4] phase A, [5] phase B, [6] whole row
@@ -604,8 +615,10 @@ __device__ unsigned long long mf_stamp_buf[8];
 template <int KT, int NPASS, int MODE = kSweepAccumulate, int PF = 0>
 __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 {
-	constexpr bool PRODUCTS = MODE == kSweepProducts, ERRORS = MODE == kSweepErrors, SEGMENTS = PRODUCTS || ERRORS, MOMENTUM = MODE == kSweepMomentum,
-	               DECAY = MODE == kSweepDecay || MOMENTUM;
+	constexpr bool WGT = MODE >= kSweepDecayW;
+	constexpr bool PRODUCTS = MODE == kSweepProducts || MODE == kSweepProductsW, ERRORS = MODE == kSweepErrors || MODE == kSweepErrorsW,
+	               SEGMENTS = PRODUCTS || ERRORS, MOMENTUM = MODE == kSweepMomentum || MODE == kSweepMomentumW,
+	               DECAY = MODE == kSweepDecay || MODE == kSweepDecayW || MOMENTUM;
 	const int K = KT > 0 ? KT : a.K;
 	const int P = dma_pieces(K);
 	constexpr int NP = NPASS;                               // DMA instructions per row
@@ -661,9 +674,11 @@ __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 		// (idx, val) of a chunk are loaded one chunk ahead, so the gather of chunk c never waits on them
 		int nx_idx = 0, nx_map = 0;
 		double nx_val = 0.0;
+		[[maybe_unused]] double nx_wgt = 0.0;
 		if (beg + lane < min(end, beg + nch)) {
 			nx_idx = a.idx[beg + lane];
 			nx_val = a.val[beg + lane];
+			if constexpr (WGT) nx_wgt = a.wgt[beg + lane];
 			if (ERRORS) nx_map = a.map[beg + lane];
 		}
 		for (int c = beg; c < end; c += nch) {
@@ -671,9 +686,11 @@ __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 			const int my_idx = nx_idx;
 			const int my_map = nx_map;
 			const double my_val = nx_val;
+			[[maybe_unused]] const double my_wgt = nx_wgt;
 			if (c + nch + lane < min(end, c + 2 * nch)) {
 				nx_idx = a.idx[c + nch + lane];
 				nx_val = a.val[c + nch + lane];
+				if constexpr (WGT) nx_wgt = a.wgt[c + nch + lane];
 				if (ERRORS) nx_map = a.map[c + nch + lane];
 			}
 			// ---- stage: short rows several per instruction, K <= 128 and K = 256 with PF by the lean issue, the others one
@@ -733,6 +750,7 @@ __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 					}
 				}
 				e = a.c2 * (my_val - dot);
+				if constexpr (WGT) e = e * my_wgt;
 			}
 #ifdef MF_STAMPS
 			asm volatile("" : "+v"(e));
@@ -819,7 +837,7 @@ __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 // Same arithmetic in the same order as sweep_dma_kernel: same bits.  Twice the LDS per workgroup, so only chosen where
 // occupancy is not what hides latency (choose_sweep / launch_sweep: few rows per CU).  Accumulate mode only.
 // ------------------------------------------------------------------------------------------------
-template <int KT, int NPASS, bool MOM = false>
+template <int KT, int NPASS, bool MOM = false, bool WGT = false>
 __global__ void __launch_bounds__(kWave) sweep_db_kernel(SweepArgs a)
 {
 	const int K = KT > 0 ? KT : a.K;
@@ -882,20 +900,38 @@ __global__ void __launch_bounds__(kWave) sweep_db_kernel(SweepArgs a)
 		asm volatile("" : "+v"(cur_idx));
 		if (beg < end) stage(cur_idx, min(nch, end - beg), 0);
 		int buf = 0;
+		// the weights of chunks c and c+1 (weighted instances).  Declared HERE, behind everything else the row declares: the
+		// same dead declaration beside cur_val changed what hipcc emits for the unweighted <20 | 30 | 50, 1, momentum>
+		// instances (two adjacent s_waitcnt merged into one), and an unweighted plan runs the code it ran before.  Their
+		// first loads go out behind the first gather; the vmcnt(0) at the top of the chunk loop retires them with it
+		[[maybe_unused]] double cur_wgt = 0.0, nx_wgt = 0.0;
+		if constexpr (WGT) {
+			if (beg + lane < min(end, beg + nch)) cur_wgt = a.wgt[beg + lane];
+			if (beg + nch + lane < min(end, beg + 2 * nch)) nx_wgt = a.wgt[beg + nch + lane];
+		}
 		for (int c = beg; c < end; c += nch, buf ^= 1) {
 			const int cnt = min(nch, end - c);
 			const double my_val = cur_val;
+			[[maybe_unused]] const double my_wgt = cur_wgt;
 			// everything in flight has arrived: the tile of chunk c, and (idx, val) of chunk c+1
-			asm volatile("s_waitcnt vmcnt(0)" : "+v"(nx_idx), "+v"(nx_val), "+v"(cur_val)::"memory");
+			if constexpr (WGT)
+				asm volatile("s_waitcnt vmcnt(0)" : "+v"(nx_idx), "+v"(nx_val), "+v"(cur_val), "+v"(nx_wgt), "+v"(cur_wgt)::"memory");
+			else
+				asm volatile("s_waitcnt vmcnt(0)" : "+v"(nx_idx), "+v"(nx_val), "+v"(cur_val)::"memory");
 			// the other tile was last read by phase B of chunk c-1 (its reads are complete: their results were consumed)
 			if (c + nch < end) stage(nx_idx, min(nch, end - (c + nch)), buf ^ 1);
 			cur_idx = nx_idx;
 			cur_val = nx_val;
 			nx_idx = 0;
 			nx_val = 0.0;
+			if constexpr (WGT) {
+				cur_wgt = nx_wgt;
+				nx_wgt = 0.0;
+			}
 			if (c + 2 * nch + lane < min(end, c + 3 * nch)) {
 				nx_idx = a.idx[c + 2 * nch + lane];
 				nx_val = a.val[c + 2 * nch + lane];
+				if constexpr (WGT) nx_wgt = a.wgt[c + 2 * nch + lane];
 			}
 			const char *tile = tile0 + buf * tile_bytes;
 			// ---- phase A
@@ -928,6 +964,7 @@ __global__ void __launch_bounds__(kWave) sweep_db_kernel(SweepArgs a)
 					}
 				}
 				e = a.c2 * (my_val - dot);
+				if constexpr (WGT) e = e * my_wgt;
 			}
 			// ---- phase B
 			const char *tb = tile + voff;
@@ -965,7 +1002,7 @@ __global__ void __launch_bounds__(kWave) sweep_db_kernel(SweepArgs a)
 // built: a second loader was measured within noise of one (the compute wave is the bound), and so
 // was splitting the compute wave into a phase-A and a phase-B wave (profiles/r03/trio_ab.txt).
 // ------------------------------------------------------------------------------------------------
-template <int KT, int NL = 1, bool MOM = false>
+template <int KT, int NL = 1, bool MOM = false, bool WGT = false>
 __global__ void __launch_bounds__((NL + 1) * kWave) sweep_pair_kernel(SweepArgs a)
 {
 	using G = DmaGeom<KT>;
@@ -1023,18 +1060,31 @@ __global__ void __launch_bounds__((NL + 1) * kWave) sweep_pair_kernel(SweepArgs 
 			else
 				load_x_row<1>(xrow2, xs, lane, P, a.seed, a.d, acc);
 			double nx_val = 0.0;
-			if (beg + lane < min(end, beg + nch)) nx_val = a.val[beg + lane];
+			[[maybe_unused]] double nx_wgt = 0.0;
+			if (beg + lane < min(end, beg + nch)) {
+				nx_val = a.val[beg + lane];
+				if constexpr (WGT) nx_wgt = a.wgt[beg + lane];
+			}
 			const unsigned boff = (unsigned) (lane < P ? lane : 0) * 16u;   // lanes beyond the row re-read piece 0: no branch masks in phase B
 			int buf = 0;
 			for (int c = beg; c < end; c += nch, buf ^= 1) {
 				const int cnt = min(nch, end - c);
 				double my_val = nx_val;
+				[[maybe_unused]] double my_wgt = nx_wgt;
 				nx_val = 0.0;
-				if (c + nch + lane < min(end, c + 2 * nch)) nx_val = a.val[c + nch + lane];
-				asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : "+v"(my_val)::"memory");   // chunk c has landed
+				if constexpr (WGT) nx_wgt = 0.0;
+				if (c + nch + lane < min(end, c + 2 * nch)) {
+					nx_val = a.val[c + nch + lane];
+					if constexpr (WGT) nx_wgt = a.wgt[c + nch + lane];
+				}
+				if constexpr (WGT)
+					asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : "+v"(my_val), "+v"(my_wgt)::"memory");   // chunk c has landed
+				else
+					asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : "+v"(my_val)::"memory");   // chunk c has landed
 				const char *tile = tile0 + buf * tile_bytes;
 				const double2 *t2 = reinterpret_cast<const double2 *>(tile + (lane < nch ? lane : 0) * S);
-				const double e = a.c2 * (my_val - phase_a_dot<KT, 8, true>(t2, xs));
+				double e = a.c2 * (my_val - phase_a_dot<KT, 8, true>(t2, xs));
+				if constexpr (WGT) e = e * my_wgt;
 				const char *tb = tile + boff;
 				const int n = phase_b_sixteen<false>(tb, S, e, 0, cnt, true, acc[0]);
 				phase_b_tail<1, false>(tb, S, e, n, cnt, lane, P, acc);
@@ -1414,11 +1464,14 @@ struct ResidentArgs {
 	const double *R_hist;
 	double *L_prev;
 	double *R_prev;
+	// weighted instances only: the entries' weights in CSR and in CSC order (SweepArgs::wgt)
+	const double *__restrict__ csr_wgt;
+	const double *__restrict__ csc_wgt;
 };
 
-constexpr size_t resident_lds_bytes(int users, int items, int K, long long nnz)
+constexpr size_t resident_lds_bytes(int users, int items, int K, long long nnz, bool weighted = false)
 {
-	return (size_t) 2 * (size_t) (users + items) * K * 8 + (size_t) nnz * 2 * 12 + (size_t) (users + items + 2) * 4 + 64;
+	return (size_t) 2 * (size_t) (users + items) * K * 8 + (size_t) nnz * 2 * (weighted ? 20 : 12) + (size_t) (users + items + 2) * 4 + 64;
 }
 
 // KMAX > 0: K <= KMAX and the owner keeps its old row and its accumulators in registers (loops fully unrolled, the
@@ -1429,7 +1482,8 @@ constexpr size_t resident_lds_bytes(int users, int items, int K, long long nnz)
 constexpr int resident_max_threads(int kmax) { return kmax == 32 ? 256 : 1024; }
 // MOM: heavy-ball momentum -- gen1 starts as the generation before gen0 (a thread reads its row of `nxt` before it
 // overwrites it, and nobody else's), a side with beta == 0 adds no term, and both generations are written back.
-template <int KMAX, bool MOM = false>
+// WGT: the entries' weights sit in LDS behind their values, and e_n is multiplied by its own.
+template <int KMAX, bool MOM = false, bool WGT = false>
 __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_kernel(ResidentArgs a)
 {
 	extern __shared__ __attribute__((aligned(16))) char rlds[];
@@ -1437,7 +1491,8 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 	const int nf = (U + I) * K;                 // doubles per generation: L rows, then R rows
 	double *gen0 = reinterpret_cast<double *>(rlds), *gen1 = gen0 + nf;
 	double *val = gen1 + nf;                    // [csr values | csc values]
-	int *idx = reinterpret_cast<int *>(val + 2 * (size_t) nnz);   // [csr idx | csc idx]
+	double *wgt = val + 2 * (size_t) nnz;       // [csr weights | csc weights] (weighted instances)
+	int *idx = reinterpret_cast<int *>(wgt + (WGT ? 2 * (size_t) nnz : 0));   // [csr idx | csc idx]
 	int *ptr = idx + 2 * (size_t) nnz;          // [csr_ptr (U+1) | csc_ptr (I+1)]
 	const int t = threadIdx.x, nt = blockDim.x;
 	for (int x = t; x < U * K; x += nt) gen0[x] = a.L_in[(size_t) (x / K) * a.ldl + x % K];
@@ -1451,6 +1506,10 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 		val[nnz + x] = a.csc_val[x];
 		idx[x] = a.csr_idx[x];
 		idx[nnz + x] = a.csc_idx[x];
+		if constexpr (WGT) {
+			wgt[x] = a.csr_wgt[x];
+			wgt[nnz + x] = a.csc_wgt[x];
+		}
 	}
 	for (int x = t; x <= U; x += nt) ptr[x] = a.csr_ptr[x];
 	for (int x = t; x <= I; x += nt) ptr[U + 1 + x] = a.csc_ptr[x];
@@ -1493,7 +1552,8 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 #pragma unroll
 				for (int k = 0; k < KM; ++k)
 					if (k < K) dot = dot + xr[k] * yr[k];
-				const double e = a.c2 * (val[n] - dot);
+				double e = a.c2 * (val[n] - dot);
+				if constexpr (WGT) e = e * wgt[n];
 #pragma unroll
 				for (int k = 0; k < KM; ++k)
 					if (k < K) acc[k] = acc[k] + e * yr[k];
@@ -1513,7 +1573,8 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 				const double *y = cur + ybase + idx[n] * K;
 				double dot = 0.0;
 				for (int k = 0; k < K; ++k) dot = dot + x[k] * y[k];
-				const double e = a.c2 * (val[n] - dot);
+				double e = a.c2 * (val[n] - dot);
+				if constexpr (WGT) e = e * wgt[n];
 				for (int k = 0; k < K; ++k) xn[k] = xn[k] + e * y[k];
 			}
 			if (frozen >= 0) xn[frozen] = x[frozen];
@@ -1545,7 +1606,7 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 constexpr int kCoopWaves = 8;
 constexpr int kCoopProducers = kCoopWaves - 1;
 
-template <int KT, bool MOM = false>
+template <int KT, bool MOM = false, bool WGT = false>
 __global__ void __launch_bounds__(kCoopWaves *kWave) sweep_coop_kernel(SweepArgs a)
 {
 	using G = DmaGeom<KT>;
@@ -1592,16 +1653,19 @@ __global__ void __launch_bounds__(kCoopWaves *kWave) sweep_coop_kernel(SweepArgs
 					char *tile = tiles + ((round & 1) * kCoopProducers + (wave - 1)) * tile_bytes;
 					int my_idx = 0;
 					double my_val = 0.0;
+					[[maybe_unused]] double my_wgt = 0.0;
 					if (lane < cnt) {
 						my_idx = a.idx[c + lane];
 						my_val = a.val[c + lane];
+						if constexpr (WGT) my_wgt = a.wgt[c + lane];
 					}
 					gather_rows<NP>(ybase, (unsigned long long) a.ldy * 8ull, my_idx, cnt, lane, voff, P, S, tile);
 					__builtin_amdgcn_s_waitcnt(0);          // vmcnt(0): the DMA has landed (single wave owns the tile)
 					__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 					// lanes beyond the tile re-read row 0
 					const double2 *t2 = reinterpret_cast<const double2 *>(tile + (lane < nch ? lane : 0) * S);
-					const double e = a.c2 * (my_val - phase_a_dot<KT>(t2, xs));
+					double e = a.c2 * (my_val - phase_a_dot<KT>(t2, xs));
+					if constexpr (WGT) e = e * my_wgt;
 					// scale in place: p_n[k] = e_n * y_n[k]
 					char *tb = tile + voff;
 					for (int n = 0; n < cnt; ++n) {

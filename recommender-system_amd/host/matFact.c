@@ -22,16 +22,17 @@
 
 /* Every MATFACT_* variable the program reads: the mode options in the order they are examined, the path options, and the
  * accessories, which take part in no rule. */
-enum { V_TOPN, V_LOSS, V_HELDOUT, V_RANK, V_SIMILAR, V_SIMILAR_OUT, V_LAMBDA, V_BIAS, V_MOMENTUM, V_DEVICES, V_MATS, V_CHECKPOINT, V_RESUME,
+enum { V_TOPN, V_LOSS, V_HELDOUT, V_RANK, V_SIMILAR, V_SIMILAR_OUT, V_LAMBDA, V_BIAS, V_MOMENTUM, V_WEIGHTS, V_DEVICES, V_MATS, V_CHECKPOINT, V_RESUME,
        V_DEVICE, V_MATS_ITERS, V_CHECKPOINT_EVERY, V_CACHE, V_TIMING, V_COUNT };
 static const char *const cli_names[V_COUNT] = {
 	"MATFACT_TOPN", "MATFACT_LOSS", "MATFACT_HELDOUT", "MATFACT_RANK", "MATFACT_SIMILAR", "MATFACT_SIMILAR_OUT", "MATFACT_LAMBDA",
-	"MATFACT_BIAS", "MATFACT_MOMENTUM", "MATFACT_DEVICES", "MATFACT_MATS", "MATFACT_CHECKPOINT", "MATFACT_RESUME", "MATFACT_DEVICE",
+	"MATFACT_BIAS", "MATFACT_MOMENTUM", "MATFACT_WEIGHTS", "MATFACT_DEVICES", "MATFACT_MATS", "MATFACT_CHECKPOINT", "MATFACT_RESUME", "MATFACT_DEVICE",
 	"MATFACT_MATS_ITERS", "MATFACT_CHECKPOINT_EVERY", "MATFACT_CACHE", "MATFACT_TIMING"};
 
 struct cli_options {
 	/* the variable's text, NULL when unset.  Used as they are: the paths MATFACT_HELDOUT=<file.in> (a second file with the
-	 * same users and items), _SIMILAR_OUT, _MATS, _CHECKPOINT, _RESUME, and _CACHE=<dir> (binary cache of parsed inputs keyed
+	 * same users and items), MATFACT_WEIGHTS=<file.in> (a second file with the same users, items and (row, col) pairs in the
+	 * same order, whose values are the entries' confidence weights), _SIMILAR_OUT, _MATS, _CHECKPOINT, _RESUME, and _CACHE=<dir> (binary cache of parsed inputs keyed
 	 * by the file's content; util.c:30-34 re-parses every run); MATFACT_TIMING only has to be set */
 	const char *value[V_COUNT];
 	int topn;             /* MATFACT_TOPN=N (1..MF_TOPN_MAX): N items per user on one line each instead of one (mf_host_write_topn) */
@@ -105,7 +106,7 @@ static const char *cli_value(int v, const char *s, struct cli_options *o)
 		o->momentum = ok && isfinite(o->beta_users) && isfinite(o->beta_items) && o->beta_users >= 0.0 && o->beta_items >= 0.0;
 		return o->momentum ? NULL : "MATFACT_MOMENTUM: expected b[,bi] with b and bi numbers >= 0.";
 	}
-	return NULL;   /* MATFACT_HELDOUT, MATFACT_SIMILAR_OUT: any text */
+	return NULL;   /* MATFACT_HELDOUT, MATFACT_SIMILAR_OUT, MATFACT_WEIGHTS: any text */
 }
 
 /* The combination rules.  A mode option is examined only when it is set, in the order of the enum: its value format first,
@@ -134,6 +135,7 @@ static const struct cli_rule cli_clashes[] = {
 	{V_LAMBDA, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_LAMBDA works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
 	{V_BIAS, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_BIAS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
 	{V_MOMENTUM, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_MOMENTUM works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
+	{V_WEIGHTS, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_WEIGHTS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
 };
 
 /* Fills `o` from the environment -- it opens no file and makes no GPU call -- and returns NULL, or the message to die with. */
@@ -144,7 +146,7 @@ static const char *cli_parse(struct cli_options *o)
 	for (int v = 0; v < V_COUNT; v++)
 		if ((o->value[v] = getenv(cli_names[v])) != NULL) set |= BIT(v);
 	const unsigned usable = o->value[V_SIMILAR_OUT] && !*o->value[V_SIMILAR_OUT] ? set & ~BIT(V_SIMILAR_OUT) : set;
-	for (int v = V_TOPN; v <= V_MOMENTUM; v++) {
+	for (int v = V_TOPN; v <= V_WEIGHTS; v++) {
 		const char *message = set & BIT(v) ? cli_value(v, o->value[v], o) : NULL;
 		if (message) return message;
 		if (!(set & BIT(v))) continue;
@@ -171,11 +173,12 @@ static const char *cli_parse(struct cli_options *o)
  * SoA form, fills an mf_shard and creates a plan.  session_close releases everything, whatever was acquired.
  * MATFACT_BIAS (here next to MATFACT_LOSS or MATFACT_MOMENTUM) is a preparation in front of the plan: the values are centred with the
  * training mean `mu` (one rounding each; the held-out ones later with the SAME mean), L and R -- the reference's
- * initialisation for K = F -- are packed to K = F + 2 by mf_backend_bias_pack with the biases at 0.0. */
+ * initialisation for K = F -- are packed to K = F + 2 by mf_backend_bias_pack with the biases at 0.0.  MATFACT_WEIGHTS makes
+ * the plan a weighted one (mf_plan_create_weighted); `mu` stays the unweighted mean of the values. */
 struct session {
 	mf_plan *plan;
 	int32_t *row, *col, *hrow, *hcol;   /* the training entries; the held-out ones, in buffers of their own */
-	double *val, *hval;
+	double *val, *hval, *wgt;           /* wgt: the entries' weights of MATFACT_WEIGHTS */
 	double *Lp, *Rp, mu;                /* MATFACT_BIAS: the packed initial factors and the mean */
 };
 
@@ -190,7 +193,8 @@ static int split_entries(const mf_problem *p, int32_t **row, int32_t **col, doub
 	return MF_OK;
 }
 
-static int session_open(struct session *s, const struct cli_options *o, const mf_problem *p, const double *L, const double *R)
+static int session_open(struct session *s, const struct cli_options *o, const mf_problem *p, const mf_problem *wts, const double *L,
+                        const double *R)
 {
 	const int32_t F = p->features, K = o->biased ? F + 2 : F;
 	memset(s, 0, sizeof(*s));
@@ -206,14 +210,19 @@ static int session_open(struct session *s, const struct cli_options *o, const mf
 	const mf_shard shard = {.users_total = p->users, .items = p->items, .features = K, .user_begin = 0, .user_count = p->users,
 	                        .nnz = p->nnz, .row = s->row, .col = s->col, .val = s->val, .alpha = p->alpha, .device = o->device,
 	                        .flags = MF_PLAN_DEFAULT};
-	if (rc == MF_OK) rc = mf_plan_create(&s->plan, &shard);
+	if (rc == MF_OK && wts) {
+		s->wgt = malloc(sizeof(double) * (size_t) (p->nnz ? p->nnz : 1));
+		for (int64_t i = 0; s->wgt && i < p->nnz; i++) s->wgt[i] = wts->entries[i].value;
+		if (!s->wgt) rc = MF_ERR_NO_MEMORY;
+	}
+	if (rc == MF_OK) rc = mf_plan_create_weighted(&s->plan, &shard, s->wgt);   /* no weights: mf_plan_create in every respect */
 	if (rc == MF_OK) rc = mf_plan_upload_factors(s->plan, o->biased ? s->Lp : L, o->biased ? s->Rp : R);
 	return rc;
 }
 
 static void session_close(struct session *s)
 {
-	void *const owned[] = {s->row, s->col, s->val, s->hrow, s->hcol, s->hval, s->Lp, s->Rp};
+	void *const owned[] = {s->row, s->col, s->val, s->hrow, s->hcol, s->hval, s->wgt, s->Lp, s->Rp};
 	mf_plan_destroy(s->plan);
 	for (size_t i = 0; i < COUNT(owned); i++) free(owned[i]);
 }
@@ -333,15 +342,15 @@ static int write_similar(mf_plan *plan, const struct cli_options *o, int32_t ite
 
 /* Every mode that needs a resident plan, as stages over one session: configure, exactly one loop, the reports on stderr,
  * the outputs.  `d` is the open dump of MATFACT_MATS or NULL; `done` counts the iterations a checkpoint already holds. */
-static int run_session(const struct cli_options *o, const mf_problem *p, const mf_problem *held, double *L, double *R, int32_t *best,
-                       int done, const struct dump *d)
+static int run_session(const struct cli_options *o, const mf_problem *p, const mf_problem *held, const mf_problem *wts, double *L, double *R,
+                       int32_t *best, int done, const struct dump *d)
 {
 	struct session s;
 	const int cap = o->loss_every ? p->iters / o->loss_every + 2 : 0;
 	mf_loss_point *trace = cap ? malloc(sizeof(mf_loss_point) * (size_t) cap) : NULL;
 	const int checkpointed = o->value[V_CHECKPOINT] || o->value[V_RESUME];
 	int points = 0;
-	int rc = session_open(&s, o, p, L, R);
+	int rc = session_open(&s, o, p, wts, L, R);
 	if (rc == MF_OK && cap && !trace) rc = MF_ERR_NO_MEMORY;
 	/* configure: the held-out set, regularisation, the frozen columns of the biases */
 	if (rc == MF_OK && held) rc = split_entries(held, &s.hrow, &s.hcol, &s.hval);
@@ -392,7 +401,7 @@ static int run_with_mats(const struct cli_options *o, const mf_problem *p, doubl
 	if (rc == MF_OK) {
 		for (int64_t n = 0; n < p->nnz; n++) d.B[(size_t) p->entries[n].row * p->items + p->entries[n].col] = p->entries[n].value;
 		mats_matrix(d.f, "Initial matrix A", d.B, p->users, p->items, 0);
-		rc = run_session(o, p, NULL, L, R, best, 0, &d);
+		rc = run_session(o, p, NULL, NULL, L, R, best, 0, &d);
 	}
 	free(d.B);
 	if (d.f && fclose(d.f) == EOF && rc == MF_OK) rc = MF_ERR_ARGUMENT;
@@ -425,7 +434,7 @@ int main(int argc, char **argv)
 	if (refusal) die(refusal);
 	const double t0 = now();
 
-	mf_problem prob, held;
+	mf_problem prob, held, wts;
 	int cache_hit = 0;
 	const int prc = mf_host_parse_file_cached(argv[1], o.value[V_CACHE], &prob, &cache_hit);
 	if (prc != MF_PARSE_OK) die(mf_host_parse_strerror(prc));
@@ -434,6 +443,16 @@ int main(int argc, char **argv)
 		const int hrc = mf_host_parse_file(o.value[V_HELDOUT], &held);
 		if (hrc != MF_PARSE_OK) die(mf_host_parse_strerror(hrc));
 		if (held.users != prob.users || held.items != prob.items) die(mf_host_parse_strerror(MF_PARSE_THREE_INTS));
+	}
+	/* MATFACT_WEIGHTS: the same grammar; its values are the weights of the input's entries, pair by pair */
+	const int have_wts = o.value[V_WEIGHTS] != NULL;
+	if (have_wts) {
+		const int wrc = mf_host_parse_file(o.value[V_WEIGHTS], &wts);
+		if (wrc != MF_PARSE_OK) die(mf_host_parse_strerror(wrc));
+		int same = wts.users == prob.users && wts.items == prob.items && wts.nnz == prob.nnz;
+		for (int64_t n = 0; same && n < prob.nnz; n++)
+			same = wts.entries[n].row == prob.entries[n].row && wts.entries[n].col == prob.entries[n].col;
+		if (!same) die("MATFACT_WEIGHTS: the file must hold the input's users, items and (row, col) pairs, in the input's order.");
 	}
 	const double t1 = now();
 
@@ -455,11 +474,11 @@ int main(int argc, char **argv)
 	/*
 	 * The rules of cli_parse leave mode options or path options, never both.  Among the path options the priority is silent:
 	 * MATFACT_CHECKPOINT / MATFACT_RESUME win over MATFACT_MATS, which wins over MATFACT_DEVICES (and MATFACT_RESUME is read
-	 * above whenever it is set).  MATFACT_LOSS, MATFACT_SIMILAR, MATFACT_BIAS with MATFACT_MOMENTUM, the checkpoints and the dump need a resident plan and run as
+	 * above whenever it is set).  MATFACT_LOSS, MATFACT_SIMILAR, MATFACT_WEIGHTS, MATFACT_BIAS with MATFACT_MOMENTUM, the checkpoints and the dump need a resident plan and run as
 	 * a session, which splits the entries once; the rest goes through the level-1 calls, which take the entries as they are.
 	 */
-	if (o.loss_every || o.similar || o.value[V_CHECKPOINT] || o.value[V_RESUME] || (o.momentum && o.biased)) {
-		rc = run_session(&o, &prob, have_held ? &held : NULL, L, R, best, start_iter, NULL);
+	if (o.loss_every || o.similar || have_wts || o.value[V_CHECKPOINT] || o.value[V_RESUME] || (o.momentum && o.biased)) {
+		rc = run_session(&o, &prob, have_held ? &held : NULL, have_wts ? &wts : NULL, L, R, best, start_iter, NULL);
 	} else if (o.biased) {
 		/* biases start at 0.0; L and R took the reference's random() stream for K = F above */
 		double mu = 0.0;
@@ -502,6 +521,7 @@ int main(int argc, char **argv)
 	free(L);
 	free(R);
 	if (have_held) mf_host_free_problem(&held);
+	if (have_wts) mf_host_free_problem(&wts);
 	mf_host_free_problem(&prob);
 	return 0;
 }
