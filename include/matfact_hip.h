@@ -52,7 +52,9 @@ extern "C" {
                                           heavy-ball momentum (mf_plan_set_momentum, mf_plan_get_momentum,
                                           mf_plan_upload_previous, mf_plan_download_previous, mf_backend_run_momentum);
                                           per-entry confidence weights (mf_plan_create_weighted, mf_plan_weight_total,
-                                          mf_backend_run_weighted) */
+                                          mf_backend_run_weighted);
+                                          box-constrained factors (mf_bounds, mf_plan_set_bounds, mf_plan_get_bounds,
+                                          mf_plan_project, mf_plan_bounds_active, mf_backend_run_bounded) */
 
 /* == non_zero_entry, datatypes.h:10-15: the (user, item, rating) triple, 16 bytes, array-of-structs */
 typedef struct mf_entry {
@@ -510,6 +512,51 @@ int mf_plan_weight_total(mf_plan *plan, double *sum_w, double *row_w);
  * lambda or beta, or NULL L / R, -> MF_ERR_ARGUMENT before any HIP call. */
 int mf_backend_run_weighted(const mf_problem *p, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
                             double lambda_items, double beta_users, double beta_items, int device);
+
+/* ---- Box-constrained factors: projected gradient descent onto [lo, hi], of which non-negative factorisation (NMF) is the
+ * lo = 0, hi = +inf case; an upper bound keeps a diverging run finite.  An extension (the reference has none), so the
+ * definition is this library's.  Each side (0 = items, 1 = users) has lo, hi and columns; the default is -inf, +inf, -1.
+ * columns == -1 means all K columns; otherwise 0 <= columns <= K and the columns k < columns are bounded -- a leading range,
+ * so that the bias columns of the layout [ L | b_user | 1.0 ] stay free at columns = F.
+ *
+ * A SEEDED sweep of side X finishes each row exactly as without bounds -- seed, decay, momentum, every e_n * Y in order --
+ * and then, for every bounded column k that is not the side's frozen column:
+ *   y = X_new[r][k];   if (y < lo) y = lo;   if (y > hi) y = hi;   X_new[r][k] = y;
+ * with IEEE 754 comparisons and selects, never a max/min instruction (those return the operand that is not NaN).  So a NaN
+ * stays the same NaN (both comparisons are false), -inf becomes lo and +inf becomes hi, -0.0 under lo = 0.0 stays -0.0, and
+ * a value equal to a bound keeps its own bits.  The frozen column keeps X_old's bits whatever `columns` is: frozen wins.
+ * Rows without entries are projected too; the padding of a row is never touched.  With the default bounds -- and with any
+ * two infinite bounds -- every result keeps the bits it has without this section.  e_n, dot_n, the loss, the penalty and every L R^T pass are
+ * unchanged; under momentum X_prev and X_old are projected values, and the definition of v does not change.
+ *
+ * An UNSEEDED sweep (seed_from_old = 0) does not project: a partial sum must not be clamped.  A sharded caller of the plan API
+ * therefore leaves the summed side unbounded on every shard, sums, and calls mf_plan_project on that side's
+ * next-generation buffer; the private side is bounded in its sweep.  mf_backend_run_multi does not bound.
+ *
+ * mf_plan_set_bounds: legal at any time, before the upload too; read at every launch, like the decay, for every way the plan
+ * iterates.  A NaN bound, lo > hi, columns < -1, columns > K or an unknown side -> MF_ERR_ARGUMENT before any HIP call,
+ * with nothing changed.  mf_plan_get_bounds is its inverse (any pointer may be NULL).
+ * mf_plan_project: the clamp above, in place, on the side's current (generation 0) or next (generation 1) buffer: the
+ * bounded, non-frozen columns of every row, on the plan's stream -- for the sharded caller after its sum, and for a caller
+ * who wants uploaded factors made feasible.  Without factors MF_ERR_STATE.
+ * mf_plan_bounds_active: over the bounded non-frozen columns of the side's current factor, at_lo = elements == lo, at_hi =
+ * elements == hi, inside = elements strictly between -- IEEE comparisons, so a NaN is in none of the three and -0.0 is
+ * at lo = 0.0: the sparsity an NMF user looks at.  Complete on return; any pointer may be NULL.
+ * mf_plan_describe appends bounds=<users>/<items> when either side has a finite bound over at least one column: a side as
+ * [lo,hi]x<columns> (the bounds in %.17g, the columns counted, K for -1), or - for a side without. */
+typedef struct mf_bounds {
+	double lo, hi;
+	int32_t columns;
+} mf_bounds;
+int mf_plan_set_bounds(mf_plan *plan, int side, double lo, double hi, int32_t columns);
+int mf_plan_get_bounds(mf_plan *plan, int side, double *lo, double *hi, int32_t *columns);
+int mf_plan_project(mf_plan *plan, int side, int generation);
+int mf_plan_bounds_active(mf_plan *plan, int side, int64_t *at_lo, int64_t *at_hi, int64_t *inside);
+/* level 1: mf_backend_run_weighted plus one record per side (NULL: unbounded).  A bad record (as mf_plan_set_bounds, with
+ * K = p->features), a bad lambda or beta, or NULL L / R -> MF_ERR_ARGUMENT before any HIP call. */
+int mf_backend_run_bounded(const mf_problem *p, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
+                           double lambda_items, double beta_users, double beta_items, const mf_bounds *bounds_users,
+                           const mf_bounds *bounds_items, int device);
 
 /* ---- Ranks of the held-out entries: where each held-out item lands in its user's recommendation order, for the plan's
  * current factors.  An extension (the reference ranks nothing), so the definition is this library's.  For held-out entry

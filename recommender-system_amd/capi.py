@@ -51,6 +51,7 @@ HIP_SYMBOLS = [
     "mf_plan_set_momentum", "mf_plan_get_momentum", "mf_plan_upload_previous", "mf_plan_download_previous",
     "mf_backend_run_momentum",
     "mf_plan_create_weighted", "mf_plan_weight_total", "mf_backend_run_weighted",
+    "mf_plan_set_bounds", "mf_plan_get_bounds", "mf_plan_project", "mf_plan_bounds_active", "mf_backend_run_bounded",
 ]
 HOST_SYMBOLS = [
     "mf_host_parse_strerror", "mf_host_parse_file", "mf_host_parse_buffer", "mf_host_free_problem",
@@ -92,6 +93,10 @@ class Shard(C.Structure):  # mf_shard
 FILTER_DTYPE = np.dtype([("best", np.float64), ("second", np.float64), ("arg", np.int32), ("nonfinite", np.int32)])
 CANDIDATE_DTYPE = np.dtype([("score", np.float64), ("best", np.int32), ("first", np.int32),
                             ("first_nan", np.int32), ("reserved", np.int32)])
+
+
+class Bounds(C.Structure):  # mf_bounds
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("columns", C.c_int32)]
 
 
 class Loss(C.Structure):  # mf_loss
@@ -217,6 +222,12 @@ def hip():
         lib.mf_plan_create_weighted.argtypes = [C.POINTER(P), C.POINTER(Shard), P]
         lib.mf_plan_weight_total.argtypes = [P, C.POINTER(C.c_double), P]
         lib.mf_backend_run_weighted.argtypes = [C.POINTER(Problem), P, P, P, P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int]
+        lib.mf_plan_set_bounds.argtypes = [P, C.c_int, C.c_double, C.c_double, C.c_int32]
+        lib.mf_plan_get_bounds.argtypes = [P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+        lib.mf_plan_project.argtypes = [P, C.c_int, C.c_int]
+        lib.mf_plan_bounds_active.argtypes = [P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        lib.mf_backend_run_bounded.argtypes = [C.POINTER(Problem), P, P, P, P, C.c_double, C.c_double, C.c_double, C.c_double,
+                                               C.POINTER(Bounds), C.POINTER(Bounds), C.c_int]
         _hip = lib
     return _hip
 
@@ -482,6 +493,41 @@ def backend_run_weighted(inst, weight, L, R, lambda_users=0.0, lambda_items=None
 
 
 run_weighted = backend_run_weighted
+
+SIDES = {"items": 0, "users": 1, 0: 0, 1: 1}
+GENERATIONS = {"current": 0, "next": 1, 0: 0, 1: 1}
+
+
+def _bounds_record(b):
+    """mf_bounds from None (unbounded), (lo, hi) or (lo, hi, columns)"""
+    if b is None:
+        return None
+    lo, hi = float(b[0]), float(b[1])
+    return Bounds(lo, hi, int(b[2]) if len(b) > 2 else -1)
+
+
+def backend_run_bounded(inst, L, R, bounds_users=None, bounds_items=None, weight=None, lambda_users=0.0, lambda_items=None,
+                        beta_users=0.0, beta_items=None, iters=None, device=0, recommend=True):
+    """mf_backend_run_bounded: backend_run_weighted with a box per side -- None (unbounded), (lo, hi) over all columns or
+    (lo, hi, columns) over the leading `columns`; a finished row is projected onto it in every seeded sweep.  L, R updated in
+    place, returns best[users], or None with recommend=False."""
+    p, keep = _problem(inst, iters)
+    w = None if weight is None else np.ascontiguousarray(weight, np.float64)
+    assert w is None or w.shape == (inst.nnz,)
+    li = lambda_users if lambda_items is None else lambda_items
+    bi = beta_users if beta_items is None else beta_items
+    bu, bit = _bounds_record(bounds_users), _bounds_record(bounds_items)
+    best = np.empty(inst.users, np.int32) if recommend else None
+    assert L.dtype == np.float64 and R.dtype == np.float64 and L.flags.c_contiguous and R.flags.c_contiguous
+    _check(hip().mf_backend_run_bounded(C.byref(p), None if w is None else w.ctypes.data, L.ctypes.data, R.ctypes.data,
+                                        best.ctypes.data if recommend else None,
+                                        float(lambda_users), float(li), float(beta_users), float(bi),
+                                        None if bu is None else C.byref(bu), None if bit is None else C.byref(bit), device),
+           "mf_backend_run_bounded")
+    return best
+
+
+run_bounded = backend_run_bounded
 
 
 def bias_mean(val):
@@ -788,6 +834,27 @@ class Plan:
         u, i = C.c_int32(), C.c_int32()
         _check(hip().mf_plan_get_frozen_columns(self._h, C.byref(u), C.byref(i)), "mf_plan_get_frozen_columns")
         return u.value, i.value
+
+    def set_bounds(self, side, lo=-np.inf, hi=np.inf, columns=-1):
+        """mf_plan_set_bounds: the box [lo, hi] over the leading `columns` columns (-1: all) of a side ("items" / 0 or
+        "users" / 1), in force from the next launch; a seeded sweep projects every finished row onto it."""
+        _check(hip().mf_plan_set_bounds(self._h, SIDES[side], float(lo), float(hi), int(columns)), "mf_plan_set_bounds")
+
+    def bounds(self, side):
+        """mf_plan_get_bounds: (lo, hi, columns) of a side"""
+        lo, hi, n = C.c_double(), C.c_double(), C.c_int32()
+        _check(hip().mf_plan_get_bounds(self._h, SIDES[side], C.byref(lo), C.byref(hi), C.byref(n)), "mf_plan_get_bounds")
+        return lo.value, hi.value, n.value
+
+    def project(self, side, generation="current"):
+        """mf_plan_project: the side's current or next buffer projected onto its box in place (bounded, non-frozen columns)"""
+        _check(hip().mf_plan_project(self._h, SIDES[side], GENERATIONS[generation]), "mf_plan_project")
+
+    def bounds_active(self, side):
+        """mf_plan_bounds_active: (at_lo, at_hi, inside) of the side's current factor over its bounded, non-frozen columns"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(hip().mf_plan_bounds_active(self._h, SIDES[side], C.byref(a), C.byref(b), C.byref(c)), "mf_plan_bounds_active")
+        return a.value, b.value, c.value
 
     def penalty(self, rows=False):
         """mf_plan_penalty: (||L_block||^2, ||R||^2) of the current factors; with rows=True also the user_count and the

@@ -394,6 +394,8 @@ int mf_plan_iterate(mf_plan *p, int iters)
 			ra.d_items = side_decay(p, 0);
 			ra.frozen_users = p->frozen[1];
 			ra.frozen_items = p->frozen[0];
+			ra.box_users = mf::Box{p->box_lo[1], p->box_hi[1], side_columns(p, 1, 1)};
+			ra.box_items = mf::Box{p->box_lo[0], p->box_hi[0], side_columns(p, 0, 1)};
 			ra.csr_ptr = p->csr_ptr;
 			ra.csr_idx = p->csr_idx;
 			ra.csr_val = p->csr_val;
@@ -535,6 +537,80 @@ int mf_plan_get_frozen_columns(mf_plan *p, int32_t *users_col, int32_t *items_co
 	if (!p) return MF_ERR_ARGUMENT;
 	if (users_col) *users_col = p->frozen[1];
 	if (items_col) *items_col = p->frozen[0];
+	return MF_OK;
+}
+
+// a box [lo, hi] over a leading range of columns: no NaN bound, lo <= hi, columns >= -1 (K is checked where it is known)
+static bool bounds_ok(double lo, double hi, int32_t columns) { return !std::isnan(lo) && !std::isnan(hi) && !(lo > hi) && columns >= -1; }
+
+int mf_plan_set_bounds(mf_plan *p, int side, double lo, double hi, int32_t columns)
+{
+	// the plan is looked at last: everything else is refused without it
+	if (!p || (side != 0 && side != 1) || !bounds_ok(lo, hi, columns) || columns > p->K) return MF_ERR_ARGUMENT;
+	// read at every launch, like the decay: the graph path captures per call, so no replay sees an earlier value
+	p->box_lo[side] = lo;
+	p->box_hi[side] = hi;
+	p->box_columns[side] = columns;
+	return MF_OK;
+}
+
+int mf_plan_get_bounds(mf_plan *p, int side, double *lo, double *hi, int32_t *columns)
+{
+	if (!p || (side != 0 && side != 1)) return MF_ERR_ARGUMENT;
+	if (lo) *lo = p->box_lo[side];
+	if (hi) *hi = p->box_hi[side];
+	if (columns) *columns = p->box_columns[side];
+	return MF_OK;
+}
+
+// the arguments of the two box passes over one buffer of a side: every row, the bounded columns but the frozen one
+static mf::BoxArgs box_args(mf_plan *p, int side, int generation)
+{
+	mf::BoxArgs a;
+	a.X = side == 0 ? p->Rbuf[p->cur ^ generation] : p->Lbuf[p->cur ^ generation];
+	a.rows = side == 0 ? p->items : p->uc;
+	a.ld = side == 0 ? p->ldr : p->ldl;
+	a.columns = p->box_columns[side] < 0 ? p->K : p->box_columns[side];
+	a.frozen = p->frozen[side];
+	a.lo = p->box_lo[side];
+	a.hi = p->box_hi[side];
+	a.counts = nullptr;
+	return a;
+}
+
+static int box_grid(const mf::BoxArgs &a) { return std::min((a.rows + mf::kBoxRows - 1) / mf::kBoxRows, 1 << 16); }
+
+int mf_plan_project(mf_plan *p, int side, int generation)
+{
+	if (!p || (side != 0 && side != 1) || (generation != 0 && generation != 1)) return MF_ERR_ARGUMENT;
+	if (!p->have_factors) return MF_ERR_STATE;
+	MF_HIP(hipSetDevice(p->device));
+	const mf::BoxArgs a = box_args(p, side, generation);
+	if (a.rows <= 0 || a.columns <= 0 || !a.X) return MF_OK;
+	hipLaunchKernelGGL(mf::box_project_kernel, dim3(box_grid(a)), dim3(mf::kBoxThreads), 0, p->stream, a);
+	MF_HIP(hipGetLastError());
+	return MF_OK;
+}
+
+int mf_plan_bounds_active(mf_plan *p, int side, int64_t *at_lo, int64_t *at_hi, int64_t *inside)
+{
+	if (!p || (side != 0 && side != 1)) return MF_ERR_ARGUMENT;
+	if (!p->have_factors) return MF_ERR_STATE;
+	MF_HIP(hipSetDevice(p->device));
+	unsigned long long c[3] = {0, 0, 0};
+	mf::BoxArgs a = box_args(p, side, 0);
+	if (a.rows > 0 && a.columns > 0) {
+		if (!p->box_counts) MF_TRY(p->box_counts.alloc(3));
+		a.counts = p->box_counts;
+		MF_HIP(hipMemsetAsync(a.counts, 0, sizeof c, p->stream));
+		hipLaunchKernelGGL(mf::box_count_kernel, dim3(box_grid(a)), dim3(mf::kBoxThreads), 0, p->stream, a);
+		MF_HIP(hipGetLastError());
+		MF_HIP(hipMemcpyAsync(c, a.counts, sizeof c, hipMemcpyDeviceToHost, p->stream));
+		MF_HIP(hipStreamSynchronize(p->stream));
+	}
+	if (at_lo) *at_lo = (int64_t) c[0];
+	if (at_hi) *at_hi = (int64_t) c[1];
+	if (inside) *inside = (int64_t) c[2];
 	return MF_OK;
 }
 
@@ -829,6 +905,19 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 		const size_t at = strlen(buf);
 		if (at + 1 < (size_t) buflen) snprintf(buf + at, (size_t) buflen - at, " frozen=%d/%d", p->frozen[1], p->frozen[0]);
 	}
+	// the box constraints in force, when a side has one: bounds=<users>/<items>, a side as [lo,hi]x<columns> with the bounds
+	// in %.17g (they read back exactly) and the columns counted (-1 told: K), or - for a side without
+	if (side_columns(p, 0, 1) > 0 || side_columns(p, 1, 1) > 0) {
+		char sd[2][96];
+		for (int k = 0; k < 2; ++k) {
+			if (side_columns(p, k, 1) > 0)
+				snprintf(sd[k], sizeof sd[k], "[%.17g,%.17g]x%d", p->box_lo[k], p->box_hi[k], side_columns(p, k, 1));
+			else
+				snprintf(sd[k], sizeof sd[k], "-");
+		}
+		const size_t at = strlen(buf);
+		if (at + 1 < (size_t) buflen) snprintf(buf + at, (size_t) buflen - at, " bounds=%s/%s", sd[1], sd[0]);
+	}
 	// per-entry weights, when the plan was created with them
 	if (p->weighted) {
 		const size_t at = strlen(buf);
@@ -917,6 +1006,28 @@ int mf_backend_run_weighted(const mf_problem *pr, const double *weight, double *
 	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
 		int rc = mf_plan_set_regularization(p, lambda_users, lambda_items);
 		if (rc == MF_OK) rc = mf_plan_set_momentum(p, beta_users, beta_items);
+		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
+		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
+		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
+		return rc;
+	}, weight);
+}
+
+// a level-1 bounds record: NULL (no bounds) or a box that mf_plan_set_bounds would take at this K
+static bool bounds_record_ok(const mf_bounds *b, int K) { return !b || (bounds_ok(b->lo, b->hi, b->columns) && b->columns <= K); }
+
+int mf_backend_run_bounded(const mf_problem *pr, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
+                           double lambda_items, double beta_users, double beta_items, const mf_bounds *bounds_users,
+                           const mf_bounds *bounds_items, int device)
+{
+	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !lambda_ok(beta_users) || !lambda_ok(beta_items) ||
+	    !bounds_record_ok(bounds_users, pr->features) || !bounds_record_ok(bounds_items, pr->features))
+		return MF_ERR_ARGUMENT;
+	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
+		int rc = mf_plan_set_regularization(p, lambda_users, lambda_items);
+		if (rc == MF_OK) rc = mf_plan_set_momentum(p, beta_users, beta_items);
+		if (rc == MF_OK && bounds_users) rc = mf_plan_set_bounds(p, 1, bounds_users->lo, bounds_users->hi, bounds_users->columns);
+		if (rc == MF_OK && bounds_items) rc = mf_plan_set_bounds(p, 0, bounds_items->lo, bounds_items->hi, bounds_items->columns);
 		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
 		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
 		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);

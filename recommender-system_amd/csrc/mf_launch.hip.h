@@ -274,8 +274,8 @@ SweepForm main_form(const mf_plan *p, int kind, bool few_rows, bool decay, bool 
 	if (sd.use_pair) return p->pair;
 	SweepForm f = few_rows ? p->few : p->single;
 	// the LDS-DMA single-wave form multiplies the seed, and keeps a frozen column, only in its decay instances (the
-	// register-staged form always does) -- `decay` is "d != 1.0 or the side has a frozen column", x * 1.0 being x; a
-	// missing one leaves fn null and launch_sweep refuses, rather than run without the decay or the frozen column
+	// register-staged form always does) -- `decay` is "d != 1.0, or the side has a frozen column or a box constraint", x * 1.0 being x; a
+	// missing one leaves fn null and launch_sweep refuses, rather than run without the decay, the frozen column or the clamp
 	const bool pf = single_wave_pipelined(p, kind);
 	if (decay && p->sweep.dma)
 		f.fn = pf ? p->sweep.pf_decay : p->sweep.fn_decay;
@@ -297,6 +297,16 @@ double side_decay(const mf_plan *p, int kind)
 // Heavy-ball momentum of a launch (kind 0: items, 1: users): the side's beta for a seeded sweep, 0.0 -- no term, today's
 // kernels -- for an unseeded one.  Read at every launch, like the decay.
 double side_momentum(const mf_plan *p, int kind, int seed) { return seed ? p->beta[kind] : 0.0; }
+
+// Box constraint of a launch (kind 0: items, 1: users): how many leading columns of a finished row are projected onto
+// [lo, hi] -- the side's `columns` (-1: all K) for a seeded sweep of a side with a finite bound, 0 for an unseeded one (a
+// partial sum is not clamped) and for a side whose bounds are both infinite (the clamp would change no bit: the launch
+// is then today's).  Read at every launch, like the decay.
+int side_columns(const mf_plan *p, int kind, int seed)
+{
+	if (!seed || (p->box_lo[kind] == -INFINITY && p->box_hi[kind] == INFINITY)) return 0;
+	return p->box_columns[kind] < 0 ? p->K : p->box_columns[kind];
+}
 
 // A side at rest that is about to run a seeded momentum sweep: X_prev = X_old by definition, literally -- one device copy
 // current -> next over rows x pitch on the plan's stream, and the side has a history.  mf_plan_iterate calls it before it
@@ -327,6 +337,7 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	a.d = side_decay(p, kind);
 	a.frozen = p->frozen[kind];   // read at every launch, like the decay: a captured graph is built per call
 	a.beta = side_momentum(p, kind, seed);
+	a.box = mf::Box{p->box_lo[kind], p->box_hi[kind], side_columns(p, kind, seed)};
 	const bool momentum = a.beta != 0.0;
 	if (momentum) MF_TRY(leave_rest(p, kind));
 	a.ldx = x.ldx;
@@ -348,7 +359,7 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	const bool extreme = sd.n_long > 0;
 	// the large chunk below kSweepFewRows rows.  Never beside the extreme-row path: with the extreme rows gone the
 	// occupancy-friendly chunk size is right again.
-	const SweepForm f = main_form(p, kind, !extreme && a.nrows < kSweepFewRows, a.d != 1.0 || a.frozen >= 0, momentum, p->weighted);
+	const SweepForm f = main_form(p, kind, !extreme && a.nrows < kSweepFewRows, a.d != 1.0 || a.frozen >= 0 || a.box.columns > 0, momentum, p->weighted);
 	if (!f.fn) return MF_ERR_UNSUPPORTED;
 	a.nch = f.nch;
 	TimedLaunch t{};
@@ -381,6 +392,7 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 		o.seed = seed;
 		o.d = a.d;
 		o.frozen = a.frozen;
+		o.box = a.box;
 		o.nslices = (int) mf_sched::slice_count(p->K, mf::kSliceCols);
 		o.row = sd.long_rows;
 		o.sbeg = sd.lr_sbeg;
@@ -450,6 +462,7 @@ int launch_es_iteration(mf_plan *p)
 	a.c2 = p->alpha * 2;
 	a.d = 1.0;           // the errors launch seeds nothing: e_n does not see the decay
 	a.frozen = -1;       // and stores no factor row
+	a.box = mf::Box{-INFINITY, INFINITY, 0};   // nor projects one
 	a.ptr = users.ptr;
 	a.idx = users.idx;
 	a.val = users.val;
@@ -476,6 +489,7 @@ int launch_es_iteration(mf_plan *p)
 		ra.d[side] = side_decay(p, side);
 		ra.frozen[side] = p->frozen[side];
 		ra.beta[side] = p->beta[side];
+		ra.box[side] = mf::Box{p->box_lo[side], p->box_hi[side], side_columns(p, side, 1)};
 	}
 	const bool momentum = ra.beta[0] != 0.0 || ra.beta[1] != 0.0;
 	if (momentum) {

@@ -420,4 +420,63 @@ __global__ void __launch_bounds__(kWave) penalty_rows_kernel(const double *__res
 	if (lane < n) row_sq[r0 + lane] = s;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Box constraint outside a sweep (mf_plan_project, mf_plan_bounds_active): one pass over the bounded columns k < columns,
+// k != frozen, of every row of a factor.  A workgroup takes kBoxRows rows at a time, its threads the elements of those
+// rows' leading `columns` columns; rows use the plan's pitch `ld`, and nothing at or beyond column `columns` (<= K) -- the
+// unbounded columns, the padding -- is read or written.
+//   box_project_kernel   X[r][k] = box_clamp(X[r][k]) in place: the projection a seeded sweep applies (mf_sweep.hip.h)
+//   box_count_kernel     counts[0] += elements == lo, [1] += elements == hi, [2] += elements strictly between: IEEE
+//                        comparisons, so a NaN is in none; integers, so the order of the count is free (atomic adds)
+// ------------------------------------------------------------------------------------------------
+constexpr int kBoxRows = 64;       // rows of a workgroup per step
+constexpr int kBoxThreads = 256;
+
+struct BoxArgs {
+	double *X;
+	int rows, ld, columns, frozen;
+	double lo, hi;
+	unsigned long long *counts;   // box_count_kernel: at_lo, at_hi, inside
+};
+
+__global__ void __launch_bounds__(kBoxThreads) box_project_kernel(BoxArgs a)
+{
+	for (int r0 = blockIdx.x * kBoxRows; r0 < a.rows; r0 += gridDim.x * kBoxRows) {
+		const int n = min(kBoxRows, a.rows - r0) * a.columns;   // <= 64 K
+		for (int e = threadIdx.x; e < n; e += kBoxThreads) {
+			const int r = e / a.columns, k = e - r * a.columns;
+			if (k == a.frozen) continue;
+			double *x = a.X + (size_t) (r0 + r) * a.ld + k;
+			*x = box_clamp(*x, a.lo, a.hi);
+		}
+	}
+}
+
+__global__ void __launch_bounds__(kBoxThreads) box_count_kernel(BoxArgs a)
+{
+	unsigned long long at_lo = 0, at_hi = 0, inside = 0;
+	for (int r0 = blockIdx.x * kBoxRows; r0 < a.rows; r0 += gridDim.x * kBoxRows) {
+		const int n = min(kBoxRows, a.rows - r0) * a.columns;
+		for (int e = threadIdx.x; e < n; e += kBoxThreads) {
+			const int r = e / a.columns, k = e - r * a.columns;
+			if (k == a.frozen) continue;
+			const double x = a.X[(size_t) (r0 + r) * a.ld + k];
+			at_lo += x == a.lo ? 1 : 0;
+			at_hi += x == a.hi ? 1 : 0;
+			inside += (x > a.lo && x < a.hi) ? 1 : 0;
+		}
+	}
+#pragma unroll
+	for (int off = kWave / 2; off > 0; off >>= 1) {
+		at_lo += __shfl_xor(at_lo, off);
+		at_hi += __shfl_xor(at_hi, off);
+		inside += __shfl_xor(inside, off);
+	}
+	if ((threadIdx.x & (kWave - 1)) == 0) {
+		if (at_lo) atomicAdd(a.counts + 0, at_lo);
+		if (at_hi) atomicAdd(a.counts + 1, at_hi);
+		if (inside) atomicAdd(a.counts + 2, inside);
+	}
+}
+
 }  // namespace mf

@@ -232,6 +232,10 @@ struct mf_plan {
 	double lambda[2] = {0.0, 0.0};   // L2 regularisation per side (0 = items, 1 = users), mf_plan_set_regularization
 	int frozen[2] = {-1, -1};        // frozen column per side (0 = items, 1 = users) or -1, mf_plan_set_frozen_columns
 	double beta[2] = {0.0, 0.0};     // heavy-ball momentum per side (0 = items, 1 = users), mf_plan_set_momentum
+	// box constraint per side (0 = items, 1 = users), mf_plan_set_bounds: columns k < box_columns (-1: all K) of a finished
+	// row are projected onto [box_lo, box_hi]
+	double box_lo[2] = {-INFINITY, -INFINITY}, box_hi[2] = {INFINITY, INFINITY};
+	int box_columns[2] = {-1, -1};
 	// a side at rest has no history: X_prev = X_old by definition.  Set by mf_plan_upload_factors and by a change of the
 	// side's beta from 0; cleared by its first seeded momentum sweep (leave_rest copies current -> next) and by
 	// mf_plan_upload_previous
@@ -302,6 +306,8 @@ struct mf_plan {
 	// penalty (mf_plan_penalty), allocated on first use: the row sums of squares [users | items], their block sums
 	// [user blocks | item blocks] and the two totals
 	dev_buf<double> pen_rows, pen_blocks, pen_total;
+	// the three counts of mf_plan_bounds_active (at_lo, at_hi, inside), allocated on first use
+	dev_buf<unsigned long long> box_counts;
 	dev_buf<int> ho_ptr, ho_idx;
 	dev_buf<double> ho_val;
 	int64_t ho_nnz = 0;

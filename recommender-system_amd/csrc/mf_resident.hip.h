@@ -47,6 +47,8 @@ struct SliceArgs {
 	double d[2];                      // weight decay per side: a row's seed is X_old * d (SweepArgs::d)
 	int frozen[2];                    // frozen column per side, or -1 (SweepArgs::frozen)
 	double beta[2];                   // momentum per side (SweepArgs::beta): read by the momentum instances only
+	Box box[2];                       // box constraint per side (SweepArgs::box): the bounded columns of a closed row are
+	                                  // projected in front of the frozen select
 };
 
 #ifdef MF_STAMPS
@@ -86,6 +88,9 @@ __global__ void __launch_bounds__(kResidentThreads) stream_resident_kernel(Slice
 	// the lanes of the side's frozen column: their seeds stay unshrunk (x * 1.0 is x) and a closed row stores its seed
 	const bool frz = c < ncol && col0 + c == a.frozen[side];
 	const double dl = frz ? 1.0 : d;
+	// the lanes of the side's bounded columns (a frozen one stores its seed: frozen wins)
+	const bool bnd = c < ncol && col0 + c < a.box[side].columns;
+	const double blo = a.box[side].lo, bhi = a.box[side].hi;
 
 	const int rb = me.row_beg[wave], re = me.row_beg[wave + 1];
 	const int eb = me.ent_beg[wave], ee = me.ent_beg[wave + 1];
@@ -188,7 +193,8 @@ __global__ void __launch_bounds__(kResidentThreads) stream_resident_kernel(Slice
 		while (pos == row_end && cur < re) {
 			if (g == 0 && c < ncol) {
 				double *dst = sd.X_new + (size_t) cur * ldx + col0 + c;
-				const double out = frz ? sc : acc;   // a select on the result: no e_n reaches the frozen column
+				double out = bnd ? box_clamp(acc, blo, bhi) : acc;   // the projection of the finished element
+				out = frz ? sc : out;                  // a select on the result: no e_n reaches the frozen column
 				asm volatile("global_store_dwordx2 %0, %1, off" ::"v"(dst), "v"(out) : "memory");
 			}
 			++cur;

@@ -34,6 +34,13 @@ namespace mf {
 //           broadcast by v_readlane -> the serial accumulation order into X[r][k].
 // Algorithmic HBM bytes per entry and sweep: 8K (the gathered row) + 12 (idx, val).
 // ------------------------------------------------------------------------------------------------
+// Box constraint of one side: columns k < columns of a finished row are projected onto [lo, hi] (box_clamp below); columns = 0
+// projects nothing
+struct Box {
+	double lo, hi;
+	int columns;
+};
+
 struct SweepArgs {
 	int nrows;
 	int K;
@@ -75,7 +82,40 @@ struct SweepArgs {
 	// per-entry confidence weights in the order of (idx, val), or null: read by the weighted instances only, which the launch
 	// picks for a plan created with weights -- e_n = (c2 * (val_n - dot_n)) * wgt_n, one more rounded multiply, unfused
 	const double *__restrict__ wgt;
+	// box constraint of the side: columns k < box.columns of a finished row are projected onto [box.lo, box.hi] -- a compare and
+	// a select per bound (box_clamp below), straight before the frozen select, in the instances that multiply by d.
+	// launch_sweep passes columns = 0 for an unseeded sweep (a partial sum is not clamped) and for a side without bounds.
+	// The kernels read it through load_box, not as a.box
+	Box box;
 };
+
+// Projection of one element onto [lo, hi]: IEEE comparisons and selects, so a NaN stays the NaN it is (both comparisons are
+// false), -0.0 stays under lo = 0.0 and a value equal to a bound keeps its own bits.  Never a max/min instruction: those
+// return the operand that is not NaN.
+__device__ __forceinline__ double box_clamp(double y, double lo, double hi)
+{
+	y = y < lo ? lo : y;
+	y = y > hi ? hi : y;
+	return y;
+}
+
+// The box of a launch, read where a finished row is stored: a scalar load from the kernel's argument segment (its one argument
+// starts at offset 0; `offset` is offsetof(Args, box)) through a pointer hipcc cannot see through.  Read as a.box the five
+// scalar registers -- and the four vector ones hipcc copies the bounds into for the selects -- are live across the whole row
+// loop, which cost the instances that multiply by d two vector registers and some of them scalar spills.
+__device__ __forceinline__ Box load_box(size_t offset)
+{
+	typedef __attribute__((address_space(4))) const char karg;
+	karg *p = (karg *) __builtin_amdgcn_kernarg_segment_ptr();
+	asm volatile("" : "+s"(p));
+	typedef __attribute__((address_space(4))) const double karg_f64;
+	typedef __attribute__((address_space(4))) const int karg_i32;
+	Box b;
+	b.lo = *reinterpret_cast<karg_f64 *>(p + offset + offsetof(Box, lo));
+	b.hi = *reinterpret_cast<karg_f64 *>(p + offset + offsetof(Box, hi));
+	b.columns = *reinterpret_cast<karg_i32 *>(p + offset + offsetof(Box, columns));
+	return b;
+}
 
 // The seed of one element under momentum: one rounded subtraction, one rounded multiply, the decay's multiply, one rounded
 // add -- nothing fused (the library is built with -ffp-contract=off).
@@ -182,10 +222,12 @@ __global__ void __launch_bounds__(kWave) sweep_kernel(SweepArgs a)
 		int fk = a.frozen >> 6;
 		asm volatile("" : "+s"(fk));
 		const bool flane = lane == (a.frozen & (kWave - 1));
+		const Box box = load_box(offsetof(SweepArgs, box));   // the bounded columns of the row: projected first, so the frozen column wins
 #pragma unroll
 		for (int kk = 0; kk < KPMAX; ++kk) {
 			const int k = lane + kWave * kk;
 			if (k < K) {
+				if (lane < box.columns - kWave * kk) acc[kk] = box_clamp(acc[kk], box.lo, box.hi);   // k < columns, against a scalar
 				if (kk == fk && flane) acc[kk] = a.seed ? xrow[k] : 0.0;
 				a.X_new[(size_t) r * a.ldx + k] = acc[kk];
 			}
@@ -272,6 +314,23 @@ __device__ __forceinline__ void load_x_row_momentum(const double2 *__restrict__ 
 			xs[q] = v;
 		}
 		acc[p] = seed ? momentum_seed(v, w, d, beta) : make_double2(0.0, 0.0);
+	}
+}
+
+// Box constraint of a finished row: lane l holds columns 2l, 2l+1 (+128 per pass); those below box.columns are projected onto
+// [box.lo, box.hi] (box_clamp).  It stands straight before freeze_column, so the frozen column keeps its old bits whatever
+// the bounds are; columns = 0 touches nothing, and the lanes beyond the row hold columns >= K >= box.columns.  The box is
+// loaded per row (load_box), like fq below: neither it nor lane masks are held across the row loop.
+template <int NP>
+__device__ __forceinline__ void project_row(int lane, double2 (&acc)[NP])
+{
+	const Box box = load_box(offsetof(SweepArgs, box));
+	// pieces whose first / second column is bounded: 2q < columns and 2q + 1 < columns, as scalars the lane is compared with
+	const int nx = (box.columns + 1) >> 1, ny = box.columns >> 1;
+#pragma unroll
+	for (int p = 0; p < NP; ++p) {
+		if (lane < nx - kWave * p) acc[p].x = box_clamp(acc[p].x, box.lo, box.hi);
+		if (lane < ny - kWave * p) acc[p].y = box_clamp(acc[p].y, box.lo, box.hi);
 	}
 }
 
@@ -812,7 +871,10 @@ __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 		}
 #endif
 		if (!SEGMENTS) {
-			if constexpr (DECAY) freeze_column<NP>(xs, lane, a.seed, a.frozen, acc);
+			if constexpr (DECAY) {
+				project_row<NP>(lane, acc);
+				freeze_column<NP>(xs, lane, a.seed, a.frozen, acc);
+			}
 			double2 *__restrict__ out2 = reinterpret_cast<double2 *>(a.X_new + (size_t) r * a.ldx);
 #pragma unroll
 			for (int p = 0; p < NP; ++p) {
@@ -976,6 +1038,7 @@ __global__ void __launch_bounds__(kWave) sweep_db_kernel(SweepArgs a)
 			asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 		}
 		{
+			project_row<NP>(lane, acc);
 			freeze_column<NP>(xs, lane, a.seed, a.frozen, acc);
 			double2 *__restrict__ out2 = reinterpret_cast<double2 *>(a.X_new + (size_t) r * a.ldx);
 #pragma unroll
@@ -1089,6 +1152,7 @@ __global__ void __launch_bounds__((NL + 1) * kWave) sweep_pair_kernel(SweepArgs 
 				const int n = phase_b_sixteen<false>(tb, S, e, 0, cnt, true, acc[0]);
 				phase_b_tail<1, false>(tb, S, e, n, cnt, lane, P, acc);
 			}
+			project_row<1>(lane, acc);
 			freeze_column<1>(xs, lane, a.seed, a.frozen, acc);
 			store_x_row<1>(reinterpret_cast<double2 *>(a.X_new + (size_t) r * a.ldx), lane, P, acc);
 			// row end: every read of the last tile and of xs is complete before the loader refills / xs is rewritten
@@ -1143,6 +1207,7 @@ struct OrderedSumArgs {
 	int max_cnt;                          // entries of the longest row of the launch
 	double d;                             // weight decay of the seed (SweepArgs::d)
 	int frozen;                           // frozen column or -1 (SweepArgs::frozen)
+	Box box;                              // box constraint of the finished row (SweepArgs::box), read through load_box
 	const int *__restrict__ row;          // extreme row ids
 	const long long *__restrict__ sbeg;   // first scratch entry of the row
 	const int *__restrict__ cnt;          // entries of the row
@@ -1407,6 +1472,12 @@ __global__ void __launch_bounds__(kWave) ordered_sum_kernel(OrderedSumArgs a)
 			ordered_sum_task<kRing / 2, DPP>(src, ring_base, my, cnt, seed_ptr, a.d, ax, ay, one, t_issued);
 		else
 			ordered_sum_task<kRing / 4, DPP>(src, ring_base, my, cnt, seed_ptr, a.d, ax, ay, one, t_issued);
+		// the box constraint of the finished row, in front of the frozen select (columns = 0: nothing)
+		{
+			const Box box = load_box(offsetof(OrderedSumArgs, box));
+			if (k0 < box.columns) ax = box_clamp(ax, box.lo, box.hi);
+			if (k0 + 1 < box.columns) ay = box_clamp(ay, box.lo, box.hi);
+		}
 		// the frozen column: its two-column piece takes the element back from the seed's slot -- landed with block 0 and
 		// rewritten by no block -- or 0.0 without a seed; read and waited for in one statement like every read of the ring
 		if (live && (a.frozen >> 1 << 1) == k0) {
@@ -1443,6 +1514,7 @@ struct ResidentArgs {
 	double c2;                                  // alpha * 2
 	double d_users, d_items;                    // weight decay of a user / an item row's seed (SweepArgs::d)
 	int frozen_users, frozen_items;             // frozen column of a user / an item row, or -1 (SweepArgs::frozen)
+	Box box_users, box_items;                   // box constraint of a user / an item row (SweepArgs::box)
 	const int *__restrict__ csr_ptr;            // users + 1
 	const int *__restrict__ csr_idx;            // item ids
 	const double *__restrict__ csr_val;
@@ -1524,6 +1596,8 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 	const int ybase = user ? U * K : 0;         // the other factor inside a generation
 	const double d = user ? a.d_users : a.d_items;
 	const int frozen = user ? a.frozen_users : a.frozen_items;
+	const int ncl = user ? a.box_users.columns : a.box_items.columns;
+	const double lo = user ? a.box_users.lo : a.box_items.lo, hi = user ? a.box_users.hi : a.box_items.hi;
 	const double beta = MOM ? (user ? a.beta_users : a.beta_items) : 0.0;
 	double *cur = gen0, *nxt = gen1;
 	for (int it = 0; it < a.iters; ++it) {
@@ -1558,9 +1632,13 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 				for (int k = 0; k < KM; ++k)
 					if (k < K) acc[k] = acc[k] + e * yr[k];
 			}
+			// the box, in front of the frozen store; its column count is taken per iteration, or KMAX lane masks stay alive
+			// across the iteration loop
+			int nc = ncl;
+			asm volatile("" : "+v"(nc));
 #pragma unroll
 			for (int k = 0; k < KM; ++k)
-				if (k < K) nxt[xoff + k] = acc[k];
+				if (k < K) nxt[xoff + k] = k < nc ? box_clamp(acc[k], lo, hi) : acc[k];
 			if (frozen >= 0) nxt[xoff + frozen] = fold;   // whatever was added: no e_n reaches the frozen column
 		} else if (owner) {
 			const double *x = cur + xoff;
@@ -1577,6 +1655,7 @@ __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_ker
 				if constexpr (WGT) e = e * wgt[n];
 				for (int k = 0; k < K; ++k) xn[k] = xn[k] + e * y[k];
 			}
+			for (int k = 0; k < ncl; ++k) xn[k] = box_clamp(xn[k], lo, hi);
 			if (frozen >= 0) xn[frozen] = x[frozen];
 		}
 		__syncthreads();
@@ -1719,6 +1798,7 @@ __global__ void __launch_bounds__(kCoopWaves *kWave) sweep_coop_kernel(SweepArgs
 			__syncthreads();
 		}
 		if (wave == 0) {
+			project_row<NP>(lane, acc);
 			freeze_column<NP>(xs, lane, a.seed, a.frozen, acc);
 			double2 *__restrict__ out2 = reinterpret_cast<double2 *>(a.X_new + (size_t) r * a.ldx);
 #pragma unroll

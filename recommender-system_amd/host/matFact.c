@@ -22,11 +22,11 @@
 
 /* Every MATFACT_* variable the program reads: the mode options in the order they are examined, the path options, and the
  * accessories, which take part in no rule. */
-enum { V_TOPN, V_LOSS, V_HELDOUT, V_RANK, V_SIMILAR, V_SIMILAR_OUT, V_LAMBDA, V_BIAS, V_MOMENTUM, V_WEIGHTS, V_DEVICES, V_MATS, V_CHECKPOINT, V_RESUME,
+enum { V_TOPN, V_LOSS, V_HELDOUT, V_RANK, V_SIMILAR, V_SIMILAR_OUT, V_LAMBDA, V_BIAS, V_MOMENTUM, V_WEIGHTS, V_BOUNDS, V_DEVICES, V_MATS, V_CHECKPOINT, V_RESUME,
        V_DEVICE, V_MATS_ITERS, V_CHECKPOINT_EVERY, V_CACHE, V_TIMING, V_COUNT };
 static const char *const cli_names[V_COUNT] = {
 	"MATFACT_TOPN", "MATFACT_LOSS", "MATFACT_HELDOUT", "MATFACT_RANK", "MATFACT_SIMILAR", "MATFACT_SIMILAR_OUT", "MATFACT_LAMBDA",
-	"MATFACT_BIAS", "MATFACT_MOMENTUM", "MATFACT_WEIGHTS", "MATFACT_DEVICES", "MATFACT_MATS", "MATFACT_CHECKPOINT", "MATFACT_RESUME", "MATFACT_DEVICE",
+	"MATFACT_BIAS", "MATFACT_MOMENTUM", "MATFACT_WEIGHTS", "MATFACT_BOUNDS", "MATFACT_DEVICES", "MATFACT_MATS", "MATFACT_CHECKPOINT", "MATFACT_RESUME", "MATFACT_DEVICE",
 	"MATFACT_MATS_ITERS", "MATFACT_CHECKPOINT_EVERY", "MATFACT_CACHE", "MATFACT_TIMING"};
 
 struct cli_options {
@@ -46,6 +46,8 @@ struct cli_options {
 	int biased;           /* MATFACT_BIAS=1: a ~ mu + b_user + b_item + l.r on frozen columns; the file's K is the latent count F */
 	int momentum;         /* MATFACT_MOMENTUM=b[,bi]: heavy-ball momentum, one number for both sides or users,items (finite, >= 0) */
 	double beta_users, beta_items;
+	int bounded;          /* MATFACT_BOUNDS=lo,hi[,lo_items,hi_items]: every finished row projected onto [lo, hi] (0,inf: non-negative */
+	double lo_users, hi_users, lo_items, hi_items;   /* factors); one pair for both sides or users then items; the bias columns stay free */
 	int device;           /* MATFACT_DEVICE=n: the GPU of a single-GPU run, default 0 */
 	int devs[16], ndev;   /* MATFACT_DEVICES=0,1,...: row-shard over these GPUs of the process, at most 16 */
 	const char *devices_error;   /* a non-number in it: said only where that path runs, after the input was read, as ever */
@@ -105,6 +107,14 @@ static const char *cli_value(int v, const char *s, struct cli_options *o)
 		if (ok && *rest) ok = number(rest + 1, 0, &rest, &o->beta_items);
 		o->momentum = ok && isfinite(o->beta_users) && isfinite(o->beta_items) && o->beta_users >= 0.0 && o->beta_items >= 0.0;
 		return o->momentum ? NULL : "MATFACT_MOMENTUM: expected b[,bi] with b and bi numbers >= 0.";
+	case V_BOUNDS:
+		ok = number(s, ',', &rest, &o->lo_users) && *rest && number(rest + 1, ',', &rest, &o->hi_users);
+		o->lo_items = o->lo_users;
+		o->hi_items = o->hi_users;
+		if (ok && *rest) ok = number(rest + 1, ',', &rest, &o->lo_items) && *rest && number(rest + 1, 0, &rest, &o->hi_items);
+		/* a NaN fails every comparison */
+		o->bounded = ok && o->lo_users <= o->hi_users && o->lo_items <= o->hi_items;
+		return o->bounded ? NULL : "MATFACT_BOUNDS: expected lo,hi[,lo_items,hi_items] with numbers lo <= hi.";
 	}
 	return NULL;   /* MATFACT_HELDOUT, MATFACT_SIMILAR_OUT, MATFACT_WEIGHTS: any text */
 }
@@ -136,6 +146,7 @@ static const struct cli_rule cli_clashes[] = {
 	{V_BIAS, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_BIAS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
 	{V_MOMENTUM, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_MOMENTUM works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
 	{V_WEIGHTS, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_WEIGHTS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
+	{V_BOUNDS, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_BOUNDS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
 };
 
 /* Fills `o` from the environment -- it opens no file and makes no GPU call -- and returns NULL, or the message to die with. */
@@ -146,7 +157,7 @@ static const char *cli_parse(struct cli_options *o)
 	for (int v = 0; v < V_COUNT; v++)
 		if ((o->value[v] = getenv(cli_names[v])) != NULL) set |= BIT(v);
 	const unsigned usable = o->value[V_SIMILAR_OUT] && !*o->value[V_SIMILAR_OUT] ? set & ~BIT(V_SIMILAR_OUT) : set;
-	for (int v = V_TOPN; v <= V_WEIGHTS; v++) {
+	for (int v = V_TOPN; v <= V_BOUNDS; v++) {
 		const char *message = set & BIT(v) ? cli_value(v, o->value[v], o) : NULL;
 		if (message) return message;
 		if (!(set & BIT(v))) continue;
@@ -352,13 +363,16 @@ static int run_session(const struct cli_options *o, const mf_problem *p, const m
 	int points = 0;
 	int rc = session_open(&s, o, p, wts, L, R);
 	if (rc == MF_OK && cap && !trace) rc = MF_ERR_NO_MEMORY;
-	/* configure: the held-out set, regularisation, the frozen columns of the biases */
+	/* configure: the held-out set, regularisation, the frozen columns of the biases, momentum, the box */
 	if (rc == MF_OK && held) rc = split_entries(held, &s.hrow, &s.hcol, &s.hval);
 	for (int64_t i = 0; rc == MF_OK && held && o->biased && i < held->nnz; i++) s.hval[i] -= s.mu;
 	if (rc == MF_OK && held) rc = mf_plan_set_heldout(s.plan, held->nnz, s.hrow, s.hcol, s.hval);
 	if (rc == MF_OK && o->regularised) rc = mf_plan_set_regularization(s.plan, o->lambda_users, o->lambda_items);
 	if (rc == MF_OK && o->biased) rc = mf_plan_set_frozen_columns(s.plan, p->features + 1, p->features);
 	if (rc == MF_OK && o->momentum) rc = mf_plan_set_momentum(s.plan, o->beta_users, o->beta_items);
+	/* the box covers the file's K columns: all of them, or with MATFACT_BIAS the latent F in front of the two bias columns */
+	if (rc == MF_OK && o->bounded) rc = mf_plan_set_bounds(s.plan, 1, o->lo_users, o->hi_users, p->features);
+	if (rc == MF_OK && o->bounded) rc = mf_plan_set_bounds(s.plan, 0, o->lo_items, o->hi_items, p->features);
 	/* loop */
 	if (rc == MF_OK) {
 		if (o->loss_every) rc = mf_plan_iterate_monitored(s.plan, p->iters, o->loss_every, o->loss_tol, trace, cap, &points, &done);
@@ -474,10 +488,10 @@ int main(int argc, char **argv)
 	/*
 	 * The rules of cli_parse leave mode options or path options, never both.  Among the path options the priority is silent:
 	 * MATFACT_CHECKPOINT / MATFACT_RESUME win over MATFACT_MATS, which wins over MATFACT_DEVICES (and MATFACT_RESUME is read
-	 * above whenever it is set).  MATFACT_LOSS, MATFACT_SIMILAR, MATFACT_WEIGHTS, MATFACT_BIAS with MATFACT_MOMENTUM, the checkpoints and the dump need a resident plan and run as
+	 * above whenever it is set).  MATFACT_LOSS, MATFACT_SIMILAR, MATFACT_WEIGHTS, MATFACT_BOUNDS, MATFACT_BIAS with MATFACT_MOMENTUM, the checkpoints and the dump need a resident plan and run as
 	 * a session, which splits the entries once; the rest goes through the level-1 calls, which take the entries as they are.
 	 */
-	if (o.loss_every || o.similar || have_wts || o.value[V_CHECKPOINT] || o.value[V_RESUME] || (o.momentum && o.biased)) {
+	if (o.loss_every || o.similar || have_wts || o.bounded || o.value[V_CHECKPOINT] || o.value[V_RESUME] || (o.momentum && o.biased)) {
 		rc = run_session(&o, &prob, have_held ? &held : NULL, have_wts ? &wts : NULL, L, R, best, start_iter, NULL);
 	} else if (o.biased) {
 		/* biases start at 0.0; L and R took the reference's random() stream for K = F above */

@@ -86,6 +86,7 @@ int main(int argc, char **argv)
 	o.seed = 1;
 	o.d = 1.0;
 	o.frozen = -1;
+	o.box = mf::Box{0.0, 0.0, 0};   // no box constraint
 	o.nslices = nsl;
 	o.ldx = ld;
 	o.row = drow;
