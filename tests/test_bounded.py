@@ -19,7 +19,7 @@ import pytest
 from conftest import GOLDEN, ROOT, golden_in
 from test_frozen import pack, seq_mean
 from test_momentum import BETA, MModel
-from test_regularised import CASES, LAM_I, LAM_U, LARGE, ZERO_FORMS, _case_id, _pick, _small, _step, _toy, differs, fast_dot
+from test_regularised import CASES, LAM_I, LAM_U, LARGE, WIDE, ZERO_FORMS, _case_id, _pick, _small, _step, _toy, differs, fast_dot
 from test_regularised import expected as reg_expected
 from test_sweep_edges import (CLASSES, GRID_CAP, PF_ROWS, SWITCHES, _single_wave, assert_same_bits, cls_signed, is_negzero, pattern,
                               seq_dot, signed_inputs)
@@ -335,7 +335,7 @@ def test_bounded_sweeps_through_every_form(device, switches, case):
 
 
 COLUMN_FORMS = [("reg", 3), ("reg", 129), ("dma-ct", 100), ("dma-ct", 256), ("dma-rt", 6), ("db", 64), ("pair", 100), ("long", 30),
-                ("long-nodpp", 30), ("coop", 10), ("es-sw8", 64), ("es-sw4", 10)]
+                ("long-nodpp", 30), ("coop", 10), ("es-sw8", 64), ("es-sw4", 10)] + WIDE
 
 
 @gpu
@@ -426,7 +426,7 @@ def test_project_on_the_hand_made_matrix(device, switches, lo, hi):
 
 
 MOMENTUM_FORMS = [("reg", 3), ("dma-ct", 30), ("dma-ct", 100), ("db", 64), ("pair", 100), ("long", 30), ("long-nodpp", 30), ("coop", 10),
-                  ("es-sw4", 10)]
+                  ("es-sw4", 10)] + WIDE
 
 
 @gpu

@@ -40,7 +40,13 @@ from test_topn import assert_same, model_topn  # noqa: E402
 
 USERS, ITEMS = 200, 517              # four 64-user (two 128-user) blocks, the last partial; five tiles, the last of 5 items
 KS_FORMS = [16, 20, 32, 40, 48, 60, 64, 66, 70, 72, 80, 90, 96, 98, 100, 104, 112, 128, 256]   # test_recommend_every_chunk_depth_and_staging_form's
-KS = KS_FORMS + [2, 4, 6, 17, 33]
+# Above K = 256 every plan takes recommend_mfma_kernel with both operands staged through registers, 128 users a workgroup
+# (the resident-L image ends at K = 100 and the 64-user kernels at 256; MF_RECOMMEND_BDMA / _HALF then change nothing, the
+# four FORMS run the same kernel, and the plan's description has no entry for the top-1 pass that a test could read: the
+# form follows from launch_recommend's rule alone): the first even and the first odd K of that range -- the odd one takes the non-vector
+# instance --, a K of 32 chunks less one (1000 = 31 x 32 + 8) and the largest K, whose margin is 16 times that of 256.
+KS_WIDE = [258, 301, 1000, 4096]
+KS = KS_FORMS + [2, 4, 6, 17, 33] + KS_WIDE
 KS_SPLIT_MATRIX = (100, 48, 256, 17)
 KS_GRID = (100, 48, 256, 17, 30)
 FORMS = [("1", "1"), ("1", "all"), ("1", "0"), ("0", "0")]      # (MF_RECOMMEND_BDMA, MF_RECOMMEND_HALF)

@@ -376,7 +376,13 @@ POSITIONS = [("dma-ct", 256, 128, 255),   # the first piece of the second pass; 
              ("es-sw2", 6, 5, 4),         # the last slice
              ("es-sw8", 10, 9, 8),        # the last, partly filled slice
              ("coop", 30, 0, 0),
-             ("long", 30, 0, 29)]         # the extreme rows are items: their last piece's .y, in the partly filled slice
+             ("long", 30, 0, 29),         # the extreme rows are items: their last piece's .y, in the partly filled slice
+             # the wide rows (the table of every form has the bias layout: 4094 / 4093 are lanes 62 and 61 of register 63)
+             ("reg-wide", 4095, 4032, 0),       # lane 0 of register 63; lane 0 of register 0
+             ("reg-wide", 4095, 0, 4032),
+             ("reg-wide", 513, 512, 511),       # the lone lane of the ninth register; lane 63 of the eighth
+             ("dma-rt", 1024, 1023, 512),       # the .y of the last piece of the eighth pass; the first piece of the fifth
+             ("dma-rt", 1024, 0, 1023)]
 
 
 @gpu

@@ -282,7 +282,12 @@ def test_cli_heldout_needs_loss_and_a_matching_header(capi, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-KS = [1, 2, 7, 10, 20, 30, 50, 62, 64, 100, 128, 130, 256, 300]
+KS = [1, 2, 7, 10, 20, 30, 50, 62, 64, 100, 128, 130, 256, 300, 511, 513, 1024, 1026, 4095]
+
+
+def loss_shape(K):
+    """users x items of the every-K instance: 1100 x 260, and 100 x 100 where a factor row is 32 KiB"""
+    return (1100, 260) if K <= 2048 else (100, 100)
 
 
 @pytest.fixture(scope="module")
@@ -297,17 +302,23 @@ def gpu(capi):
 @pytest.mark.parametrize("K", KS)
 def test_loss_every_k_equals_the_model(gpu, K, impl, monkeypatch):
     """1100 users (not a multiple of 1024) x 260 items: users 0 and 5 empty, user 3 rated everything (260 entries: more
-    than 64 * 3, so the chain crosses chunks at every chunk size)."""
+    than 64 * 3, so the chain crosses chunks at every chunk size).  Above K = 300: the last odd and the first odd K of two
+    register counts (511, 513), the eight full passes of the run-time-K LDS-DMA row sums (1024), the first even K past them
+    (1026) and the plan at the edge of a CU's LDS (4095, on 100 x 100: user 3 has 100 entries, 20 chunks of five)."""
     capi = gpu
     if impl == "reg":
         monkeypatch.setenv("MF_SWEEP_IMPL", "reg")
-    row, col, val, L, R = instance(K, 1100, 260, K)
-    plan = _plan(capi, 1100, 260, K, row, col, val, L, R)
+    U, I = loss_shape(K)
+    row, col, val, L, R = instance(K, U, I, K)
+    plan = _plan(capi, U, I, K, row, col, val, L, R)
     desc = plan.describe()
-    assert ("loss=loss_dma_kernel(" if impl == "dma" and K % 2 == 0 else "loss=loss_reg_kernel(") in desc, desc
+    assert ("loss=loss_dma_kernel(" if impl == "dma" and K % 2 == 0 and K <= 1024 else "loss=loss_reg_kernel(") in desc, desc
+    if K > 300:
+        assert desc.startswith("sweep_dma_kernel<KT=0,NPASS=8> " if "loss=loss_dma_kernel(" in desc else
+                               "sweep_kernel<KT=0,KPMAX=%d> " % next(kp for kp in (8, 16, 32, 64) if K <= 64 * kp)), desc
     ms = check_loss(plan, L, R, row, col, val, where="K=%d %s" % (K, impl))
     assert ms[0] == 0.0 and ms[5] == 0.0 and bits(ms[0]) == 0
-    out = capi.backend_loss(capi.Instance(1, 0.01, K, 1100, 260, row, col, val), L, R)
+    out = capi.backend_loss(capi.Instance(1, 0.01, K, U, I, row, col, val), L, R)
     assert_bits(out.sse, model_total(ms))
     assert out.count == len(row)
     assert out.rmse == float(np.sqrt(out.sse / out.count))
@@ -356,7 +367,7 @@ def test_loss_row_sum_follows_the_file_order(gpu, K):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("K", [7, 30, 100])
+@pytest.mark.parametrize("K", [7, 30, 100, 513, 1024])
 def test_heldout_sets(gpu, K):
     capi = gpu
     U, I = 1500, 240

@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, golden_in
-from test_regularised import CASES, LAM_I, LAM_U, ZERO_FORMS, Model, Side, _case_id, _pick, _small, _toy, decay, differs, fast_dot, model_sweep
+from test_regularised import CASES, LAM_I, LAM_U, WIDE, ZERO_FORMS, Model, Side, _case_id, _pick, _small, _toy, decay, differs, fast_dot, model_sweep
 from test_sweep_edges import (CLASSES, FORMS, PF_ROWS, SWEEPS, SWITCHES, _single_wave, assert_same_bits, cls_signed, is_negzero, pattern,
                               pattern_both_large, seq_dot, signed_inputs)
 
@@ -234,8 +234,9 @@ def switches(monkeypatch):
 
 def test_every_form_is_in_the_table():
     names = {c["name"] for c in CASES}
-    assert names == {"reg", "dma-ct", "dma-rt", "db", "pair", "long", "long-nodpp", "coop", "es-sw8", "es-sw4", "es-sw2"}
-    assert len(CASES) == 2 * 2 * len(names)
+    assert names == {"reg", "reg-wide", "dma-ct", "dma-rt", "db", "pair", "long", "long-nodpp", "coop", "es-sw8", "es-sw4", "es-sw2"}
+    assert len(CASES) == 2 * 2 * (len(names) - 1) + 2 * len(WIDE)      # both ends of every narrow row, and the wide rows
+    assert {(c["name"], c["K"]) for c in CASES if c["pat"] == "wide"} == {("reg-wide", 513), ("reg-wide", 4095), ("dma-rt", 1024)}
 
 
 def _plan(capi, x, K, lam=LAM, beta=BETA):

@@ -283,7 +283,8 @@ def test_cli_rank_bad_values_die_with_empty_stdout(capi, env, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-KS = [8, 20, 30, 64, 100, 112, 128, 256]
+EXACT_KS = [8, 30, 301, 1024]      # no matrix-core shape: the exact pass for every entry; 301 and 1024 lie above every shape
+KS = [8, 20, 30, 64, 100, 112, 128, 256, 301, 1024]
 
 
 @pytest.fixture(scope="module")
@@ -335,7 +336,7 @@ def test_rank_every_k_equals_the_model(gpu, orc, K, impl, split, monkeypatch):
     got = plan.rank_heldout()
     assert got.dtype == np.int32 and np.array_equal(got, want), (K, impl, split, np.flatnonzero(got != want)[:8])
     exact_entries, form = plan.rank_heldout_info()
-    if impl == "exact" or K in (8, 30):
+    if impl == "exact" or K in EXACT_KS:
         assert exact_entries == -1 and form == 0
     else:
         special = int(np.count_nonzero(((hrow == 3) | (hrow == 4)) & (want != -1)))

@@ -61,8 +61,9 @@ def model_sweep(X_old, Y_old, e, side, other, d, seeded):
     start = X_old * d if seeded else np.zeros_like(X_old)
     if side.maxlen == 0:
         return start
-    if side.pad.size * X_old.shape[1] > 40_000_000:
-        # many rows, most of them short: entry j of every row that has one, j ascending (the same sums, no padded array)
+    if side.pad.size * X_old.shape[1] > 20_000_000:
+        # many rows, most of them short, or rows of a few thousand columns: entry j of every row that has one, j ascending
+        # (the same sums, no padded array)
         acc = start
         for j in range(side.maxlen):
             has = np.flatnonzero(side.lens > j)
@@ -234,14 +235,22 @@ def switches(monkeypatch):
 
 
 def _ends(forms):
-    """the smallest and the largest K of every row of the table"""
+    """the smallest and the largest K of every row of the table (its rows of wide K apart: WIDE below picks among those)"""
+    forms = [f for f in forms if not f.get("wide")]
     ks = {}
     for f in forms:
         ks.setdefault(f["name"], []).append(f["K"])
     return [f for f in forms if f["K"] in (min(ks[f["name"]]), max(ks[f["name"]]))]
 
 
-CASES = [dict(f, nch=nch) for f in _ends(FORMS) for nch in (None, "5")]
+def _pick(name, K):
+    return next(f for f in FORMS if f["name"] == name and f["K"] == K)
+
+
+# The extensions at wide K, on the "wide" pattern: the register-staged form with lane 0 of its ninth register alone (513)
+# and with all 64 registers at the edge of a CU's LDS (4095), and the eight full passes of the run-time-K LDS-DMA form.
+WIDE = [("reg-wide", 513), ("reg-wide", 4095), ("dma-rt", 1024)]
+CASES = [dict(f, nch=nch) for f in _ends(FORMS) + [_pick(*w) for w in WIDE] for nch in (None, "5")]
 
 
 def _case_id(c):
@@ -250,8 +259,9 @@ def _case_id(c):
 
 def test_every_form_is_in_the_table():
     names = {c["name"] for c in CASES}
-    assert names == {"reg", "dma-ct", "dma-rt", "db", "pair", "long", "long-nodpp", "coop", "es-sw8", "es-sw4", "es-sw2"}
-    assert len(CASES) == 2 * 2 * len(names)
+    assert names == {"reg", "reg-wide", "dma-ct", "dma-rt", "db", "pair", "long", "long-nodpp", "coop", "es-sw8", "es-sw4", "es-sw2"}
+    assert len(CASES) == 2 * 2 * (len(names) - 1) + 2 * len(WIDE)
+    assert {(c["name"], c["K"]) for c in CASES if c["pat"] == "wide"} == set(WIDE)
 
 
 def _step(plan, L0, R0, seed_items, seed_users):
@@ -343,12 +353,8 @@ def test_plain_decay_instances_above_262144_rows(device, switches, name):
         plan.close()
 
 
-def _pick(name, K):
-    return next(f for f in FORMS if f["name"] == name and f["K"] == K)
-
-
 ZERO_FORMS = [("reg", 3), ("dma-ct", 100), ("dma-rt", 6), ("db", 64), ("pair", 100), ("long", 30), ("long-nodpp", 30), ("coop", 10),
-              ("es-sw4", 10)]
+              ("es-sw4", 10)] + WIDE
 
 
 @gpu

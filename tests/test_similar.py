@@ -233,7 +233,7 @@ def test_model_masks_the_query_itself_and_pads_the_tail(orc):
 
 # ------------------------------------------------------------------------------------------------ GPU
 MATRIX_KS = [20, 100, 48, 96, 112, 128, 256]
-EXACT_KS = [30, 10]
+EXACT_KS = [30, 10, 301, 1024]     # 301 and 1024: above every matrix-core shape, the normalisation chunked over K
 ITEM_COUNTS = [1, 2, 5, 63, 64, 65, 127, 128, 129, 300]
 NS = [1, 10, 32]
 SHAPES = [(300, K) for K in MATRIX_KS + EXACT_KS] + [(i, K) for K in (100, 48) for i in ITEM_COUNTS if i != 300]

@@ -4,7 +4,9 @@ Every other sweep test feeds init_factors (positive, uniform in [0, 1/K)), ratin
 np.array_equal -- which calls -0.0 and +0.0 equal and any result holding a NaN different.  Here:
 
 A  six value classes (signed, wide exponent range, signed zeros, subnormal users / items, inf and NaN) go through every
-   sweep form the library ships, each forced with the documented switches and confirmed through Plan.describe();
+   sweep form the library ships, each forced with the documented switches and confirmed through Plan.describe() -- every
+   instance of the kernel tables at both ends of its range of K, up to K = 4096, the largest the library accepts
+   (WIDE_FORMS; tests/test_wide_k.py checks the table against mf_plan.hip.h);
 B  launches just above 262144 rows (where the plain accumulate form replaces the pipelined one) and just above 2^20 rows
    (where the row loop of a workgroup makes a second trip);
 C  the oracle is pinned to the reference's own results on signed ratings and on runs that diverge to inf and NaN.
@@ -112,15 +114,16 @@ class Pattern:
 PLANTED = 12
 
 
-def _plant(name, users, items, row, col, seed, first_user=0):
+def _plant(name, users, items, row, col, seed, first_user=0, items_below=None):
     """PLANTED more users and PLANTED more items with one or two entries each (against the original rows, users from
-    first_user on): the short rows on which all products of a sum can be -0.0 and on which the non-finite plants sit."""
+    first_user on, items below items_below): the short rows on which all products of a sum can be -0.0 and on which the
+    non-finite plants sit."""
     rng = np.random.default_rng(seed)
     rows, cols = [np.asarray(row, np.int64)], [np.asarray(col, np.int64)]
     for t in range(PLANTED):
         n = 1 + t % 2
         rows.append(np.full(n, users + t))
-        cols.append(np.sort(rng.choice(items, n, replace=False)))
+        cols.append(np.sort(rng.choice(items if items_below is None else items_below, n, replace=False)))
         cols.append(np.full(n, items + t))
         rows.append(np.sort(rng.choice(np.arange(first_user, users), n, replace=False)))
     return Pattern(name, users + PLANTED, items + PLANTED, np.concatenate(rows), np.concatenate(cols),
@@ -161,7 +164,21 @@ def pattern(name):
         mask[5, :] = False
         row, col = np.nonzero(mask)
         return _plant(name, 150, 700, row, col, 501)
+    if name == "wide":
+        # the rows of K up to 4096 (a factor row is 32 KiB there): the block-diagonal [[A, 0], [0, A^T]], A = 38 x 65 with rows
+        # of WIDE_LENS entries -- users 0..37 and items 65..102 have exactly those lengths (the planted rows stay off them):
+        # n - 1, n, n + 1, 2n, 2n + 1 of every chunk size these plans use (4, 5, 12, 16), about 1600 entries in all
+        rng = np.random.default_rng(1100)
+        na, ma = len(WIDE_LENS), 65
+        arow = np.repeat(np.arange(na), WIDE_LENS)
+        acol = np.concatenate([np.sort(rng.choice(ma, int(n), replace=False)) for n in WIDE_LENS if n])
+        row = np.concatenate([arow, na + acol])
+        col = np.concatenate([acol, ma + arow])
+        return _plant(name, na + ma, ma + na, row, col, 1101, first_user=na, items_below=ma)
     raise KeyError(name)
+
+
+WIDE_LENS = list(range(35)) + [63, 64, 65]
 
 
 def test_patterns_are_the_ones_the_forms_need():
@@ -173,8 +190,15 @@ def test_patterns_are_the_ones_the_forms_need():
     assert q.ilen.max() >= 2600 and (q.ilen[:q.items - PLANTED] >= 20).all() and sorted(set(q.ilen[q.planted_items])) == [1, 2]
     s = pattern("skewed")
     assert (s.ulen[:10] > 500).sum() >= 9 and s.ulen[5] == 0 and (s.ilen[:5] >= 149).all()
-    for x in (p, q, s):
-        key = x.row.astype(np.int64) * x.items + x.col
+    w = pattern("wide")
+    assert (w.users, w.items) == (103 + PLANTED, 103 + PLANTED) and 1500 <= w.nnz <= 1700
+    assert w.ulen[:38].tolist() == WIDE_LENS and w.ilen[65:103].tolist() == WIDE_LENS      # both sides, every length
+    for n in (4, 5, 12, 16):                                                               # the chunk sizes of the wide plans
+        assert {n - 1, n, n + 1, 2 * n, 2 * n + 1} <= set(WIDE_LENS), n
+    assert sorted(set(w.ulen[w.planted_users])) == [1, 2] and sorted(set(w.ilen[w.planted_items])) == [1, 2]
+    assert not ((w.row < 38) & (w.col >= 65)).any() and not ((w.row >= 38) & (w.row < 103) & (w.col < 65)).any()   # block-diagonal
+    for x in (p, q, s, w):
+        key =x.row.astype(np.int64) * x.items + x.col
         assert (np.diff(key) > 0).all(), x.name                                       # sorted, no duplicate entry
 
 
@@ -322,13 +346,15 @@ def expected(pat_name, cls, K):
     return x
 
 
-@pytest.mark.parametrize("K", [3, 6, 100])
-@pytest.mark.parametrize("cls", list(CLASSES))
-@pytest.mark.parametrize("pat_name", ["pair", "long-items", "skewed"])
+GUARDED = ([(p, c, K) for p in ("pair", "long-items", "skewed") for c in CLASSES for K in (3, 6, 100)]
+           + [("wide", c, K) for c in CLASSES for K in (513, 4095)])
+
+
+@pytest.mark.parametrize("pat_name,cls,K", GUARDED, ids=["%s-%s-%d" % g for g in GUARDED])
 def test_value_classes_do_their_job_on_the_oracle(pat_name, cls, K):
     """The guard conditions of every class (no NaN outside "nonfinite"; sums of nothing but -0.0 on both sides and -0.0
     results for "zeros"; a subnormal factor most of whose bits change; NaN in a few rows only and inf without NaN for
-    "nonfinite") hold on the oracle's own results, on every pattern part A uses."""
+    "nonfinite") hold on the oracle's own results, on every pattern part A uses -- the wide one at the K of its rows."""
     x = expected(pat_name, cls, K)
     if cls == "zeros" and pat_name == "pair":
         print("zeros, K=%d: %d -0.0 in the seeded user result, all-(-0.0) sums items/users %s" % (K, x.negzero_seeded, x.negzero_sums))
@@ -337,8 +363,10 @@ def test_value_classes_do_their_job_on_the_oracle(pat_name, cls, K):
 
 
 # ------------------------------------------------------------------------------------------------ A: every sweep form
-def _form(name, env, ks, pat, check, steps=True):
-    return [dict(name=name, env=env, K=k, pat=pat, check=check, steps=steps) for k in ks]
+def _form(name, env, ks, pat, check, steps=True, nchs=(None, "5"), without=()):
+    """rows of the table: `check` confirms the form in Plan.describe(); `nchs`: the chunk sizes a row runs at (the rule's, "5");
+    `without`: value classes a row leaves out"""
+    return [dict(name=name, env=env, K=k, pat=pat, check=check, steps=steps, nchs=nchs, without=without) for k in ks]
 
 
 def _single_wave(desc, K, kt):
@@ -352,8 +380,110 @@ def _slice_width(K, first):
     return next(w for w in (first, 8, 4, 2) if -(-K // w) <= 8)
 
 
+LDS_PER_CU = 160 * 1024
+
+
+def tile_geometry(K, dma):
+    """(bytes in front of the tile, tile row stride in bytes) of a plan's single-wave form: the LDS-DMA forms keep the x
+    row, rounded up to 256 bytes, in front of rows of an odd number of 16-byte pieces; the register-staged form has rows of
+    K | 1 doubles and nothing in front of them."""
+    return (-(-K * 8 // 256) * 256, 16 * ((K >> 1) | 1)) if dma else (0, 8 * (K | 1))
+
+
+def rule_nch(K, dma, forced=None):
+    """Entries per chunk of the ordinary single-wave launch (the nch= of Plan.describe()) as chunk_rule states it: 16, cut to
+    what a sixth of a CU's LDS holds but not below 12, cut to what the whole LDS holds; MF_SWEEP_NCH where that fits."""
+    head, row = tile_geometry(K, dma)
+
+    def fit(budget):
+        return min(64, (budget - head) // row) if budget > head else 0
+    nch = 16
+    if head + nch * row > LDS_PER_CU // 6:
+        nch = max(12, fit(LDS_PER_CU // 6))
+    nch = min(nch, fit(LDS_PER_CU))
+    if forced and head + forced * row <= LDS_PER_CU:
+        nch = forced
+    return nch
+
+
+def generic_width(K, widths):
+    """the first instance of a run-time-K table (64 columns per register, 128 per LDS-DMA pass) that holds K"""
+    return next(w for w in widths if K <= w[1] * w[0])
+
+
+REG_WIDTHS = [(kp, 64) for kp in (1, 2, 4, 8, 16, 32, 64)]
+DMA_WIDTHS = [(np_, 128) for np_ in (1, 2, 4, 8)]
+
+
+def _reg_wide(d, K):
+    """the run-time-K register-staged instance of this K, and the whole LDS request where the rule ends on it"""
+    kp = generic_width(K, REG_WIDTHS)[0]
+    return (d.startswith("sweep_kernel<KT=0,KPMAX=%d> K=%d " % (kp, K)) and "iterate=sweeps" in d
+            and (K != 4095 or " nch=5 stride=4095 lds=163800 " in d) and (K != 4096 or " nch=4 stride=4097 " in d))
+
+
+def _dma_wide(d, K):
+    return _single_wave(d, K, 0) and d.startswith("sweep_dma_kernel<KT=0,NPASS=%d> K=%d " % (generic_width(K, DMA_WIDTHS)[0], K))
+
+
+def _db_wide(d, K):
+    return (d.startswith("sweep_dma_kernel<KT=0,NPASS=%d> K=%d " % (generic_width(K, DMA_WIDTHS)[0], K))
+            and "double_buffered=1/1(" in d and "long_rows=0/0 " in d and "iterate=sweeps" in d)
+
+
+def _long_wide(d, K, dpp):
+    """the extreme-row path beside the instance of this K: compile-time K = 128 (one pass) and 256 (two), else run-time K"""
+    kt = K if K in (128, 256) else 0
+    npass = -(-K // 128) if kt else generic_width(K, DMA_WIDTHS)[0]
+    return (d.startswith("sweep_dma_kernel<KT=%d,NPASS=%d> K=%d " % (kt, npass, K)) and "long_rows=0/" not in d and "long_rows=" in d
+            and ("MF_OS_DPP=0" in d) == (not dpp) and ("MF_OS_DPP" in d) == (not dpp) and "iterate=sweeps" in d)
+
+
+def _reg_rt(d, K):
+    return d.startswith("sweep_kernel<KT=0,KPMAX=%d> K=%d " % (generic_width(K, REG_WIDTHS)[0], K)) and "iterate=sweeps" in d
+
+
+def _coop(d, K):
+    return "long_rows=" in d and "long_rows=0/0 " not in d and "coop_nch=0 " not in d and "iterate=sweeps" in d
+
+
 SWEEPS = {"MF_ITER_MODE": "sweeps"}
 SINGLE = dict(SWEEPS, MF_SWEEP_PAIR="0", MF_SWEEP_DB="0")
+LONG = dict(SWEEPS, MF_SWEEP_LONG="24")
+# The rows of K above the narrow end of every family (the "wide" pattern: a factor row is up to 32 KiB), and the narrow rows
+# the table guard of tests/test_wide_k.py found missing.  All carry wide=True: their description is also checked for the
+# rule's nch, and the per-form tables of the other modules take their ends from the rows above, not from these.
+#   reg-wide   the natural dispatch of an odd K above 256 and of every K above 1024, and MF_SWEEP_IMPL=reg: every KPMAX of
+#              8 .. 64 once with lane 0 of its last register alone (64 * KPMAX / 2 + 1) and once full, the first even K past
+#              the LDS-DMA range (1026) and the two plans at the edge of a CU's LDS (4095: five rows, 163800 bytes; 4096: four)
+#   dma-rt     four passes (258, 512) and eight: one lane of the fifth (514), the seventh (770), the last piece (1022), full
+#   coop       the cooperative form exists for the seven compile-time K.  The rule's 48 KiB budget holds eight entries up
+#              to K = 50 (14 tiles of a row stride each per entry), so K = 100, 128 and 256 are reached through MF_SWEEP_NCH
+#              only -- their rows run at "5" alone
+#   reg-ct     the register-staged instances of a compile-time K, which MF_SWEEP_IMPL=reg picks at the K of the LDS-DMA table
+#   reg, dma-rt (on "pair")   the first and the last K of the narrow run-time-K instances: tests/test_wide_k.py asks for both
+#              ends of every instance's range (64 registers' worth of columns; 126 and 254: the last even K below a
+#              compile-time one).  K = 1 and K = 2 leave the "zeros" class out: its guard -- ten sums of nothing but -0.0 on
+#              each side -- cannot hold on one or two columns of a hundred item rows, and the class reaches both instances
+#              at K = 3 and K = 6
+REG = dict(SWEEPS, MF_SWEEP_IMPL="reg")
+WIDE_FORMS = (
+    _form("reg-ct", REG, [20, 30, 50, 128, 256], "pair",
+          lambda d, K: d.startswith("sweep_kernel<KT=%d,KPMAX=%d> K=%d " % (K, -(-K // 64), K)) and "iterate=sweeps" in d)
+    + _form("reg", REG, [1], "pair", _reg_rt, without=("zeros",))
+    + _form("reg", REG, [64, 127, 255], "pair", _reg_rt)
+    + _form("dma-rt", SINGLE, [2], "pair", _dma_wide, without=("zeros",))
+    + _form("dma-rt", SINGLE, [126, 254], "pair", _dma_wide)
+    + _form("reg-wide", SWEEPS, [257, 513, 1025, 1026, 2049, 4095, 4096], "wide", _reg_wide)
+    + _form("reg-wide", REG, [512, 1024, 2048], "wide", _reg_wide)
+    + _form("dma-rt", SINGLE, [258, 512, 514, 770, 1022, 1024], "wide", _dma_wide)
+    + _form("db", dict(SWEEPS, MF_SWEEP_DB="1"), [130, 300, 1024], "wide", _db_wide)
+    + _form("long", LONG, [64, 128, 130, 256, 300, 1024], "long-items", lambda d, K: _long_wide(d, K, True))
+    + _form("long-nodpp", dict(LONG, MF_OS_DPP="0"), [64, 128, 130, 256, 300, 1024], "long-items", lambda d, K: _long_wide(d, K, False))
+    + _form("coop", SWEEPS, [20], "skewed", lambda d, K: _coop(d, K) and d.startswith("sweep_dma_kernel<KT=20,"))
+    + _form("coop", SWEEPS, [100, 128, 256], "skewed",
+            lambda d, K: _coop(d, K) and d.startswith("sweep_dma_kernel<KT=%d," % K) and " coop_nch=5 " in d, nchs=("5",))
+)
 FORMS = (
     _form("reg", dict(SWEEPS, MF_SWEEP_IMPL="reg"), [3, 7, 10, 65, 100, 129], "pair",
           lambda d, K: d.startswith("sweep_kernel<") and "iterate=sweeps" in d)
@@ -373,23 +503,44 @@ FORMS = (
        for f in _form("es-sw" + sw, {"MF_ITER_MODE": "es", "MF_ES_SW": sw}, [6, 10, 30, 50, 64], "pair",
                       lambda d, K, sw=sw: "iterate=errors+resident-streams(" in d and
                       ", %d-column slices of Y in LDS" % _slice_width(K, int(sw)) in d, steps=False)]
+    + [dict(f, wide=True) for f in WIDE_FORMS]
 )
-CASES = [dict(f, nch=nch) for f in FORMS for nch in (None, "5")]
+CASES = [dict(f, nch=nch) for f in FORMS for nch in f["nchs"]]
 
 
 def _case_id(c):
     return "%s-K%d-nch%s" % (c["name"], c["K"], c["nch"] or "rule")
 
 
+def wide_nch(desc, case):
+    """the nch= of a wide row's description is chunk_rule's for the form the description names"""
+    nch = rule_nch(case["K"], desc.startswith("sweep_dma_kernel<"), int(case["nch"]) if case["nch"] else None)
+    return " K=%d " % case["K"] in desc and " nch=%d " % nch in desc
+
+
 def test_every_form_of_the_issue_is_in_the_table():
     ks = {}
     for c in CASES:
         ks.setdefault(c["name"], set()).add(c["K"])
-    assert ks["reg"] == {3, 7, 10, 65, 100, 129} and ks["dma-ct"] == {10, 20, 30, 50, 100, 128, 256}
-    assert ks["dma-rt"] == {6, 64, 96, 130, 300} and ks["db"] == {64, 100, 256} and ks["pair"] == {100, 128}
-    assert ks["long"] == ks["long-nodpp"] == {6, 30, 100} and ks["coop"] == {10, 30, 50}
+    assert ks["reg"] == {3, 7, 10, 65, 100, 129, 1, 64, 127, 255} and ks["dma-ct"] == {10, 20, 30, 50, 100, 128, 256}
+    assert ks["reg-ct"] == {20, 30, 50, 128, 256} and ks["reg-wide"] == {257, 512, 513, 1024, 1025, 1026, 2048, 2049, 4095, 4096}
+    assert ks["dma-rt"] == {6, 64, 96, 130, 300, 2, 126, 254, 258, 512, 514, 770, 1022, 1024} and ks["db"] == {64, 100, 256, 130, 300, 1024}
+    assert ks["pair"] == {100, 128}
+    assert ks["long"] == ks["long-nodpp"] == {6, 30, 100, 64, 128, 130, 256, 300, 1024} and ks["coop"] == {10, 20, 30, 50, 100, 128, 256}
     assert ks["es-sw8"] == ks["es-sw4"] == ks["es-sw2"] == {6, 10, 30, 50, 64}
-    assert len(CASES) == 2 * len(FORMS) and {c["nch"] for c in CASES} == {None, "5"}
+    assert set(ks) == {"reg", "reg-ct", "reg-wide", "dma-ct", "dma-rt", "db", "pair", "long", "long-nodpp", "coop", "es-sw8", "es-sw4", "es-sw2"}
+    # every row at the rule's chunk size and at 5, but the cooperative rows the rule's budget does not reach: at 5 alone
+    only5 = [f for f in FORMS if f["nchs"] == ("5",)]
+    assert sorted((f["name"], f["K"]) for f in only5) == [("coop", 100), ("coop", 128), ("coop", 256)]
+    assert len(CASES) == 2 * len(FORMS) - len(only5) and {c["nch"] for c in CASES} == {None, "5"}
+    assert len({_case_id(c) for c in CASES}) == len(CASES)
+    # every row runs the six classes, but K = 1 and K = 2 (see WIDE_FORMS): five
+    assert sorted((f["name"], f["K"]) for f in FORMS if f["without"]) == [("dma-rt", 2), ("reg", 1)]
+    assert len(CASES_BY_CLASS) == len(CASES) * len(CLASSES) - 2 * 2
+    # the natural dispatch of the wide register-staged rows sets no MF_SWEEP_IMPL; the full-register ones force it
+    for f in FORMS:
+        if f["name"] == "reg-wide":
+            assert ("MF_SWEEP_IMPL" in f["env"]) == (f["K"] in (512, 1024, 2048)), f["K"]
 
 
 @pytest.fixture(scope="module")
@@ -411,9 +562,11 @@ def switches(monkeypatch):
     return set_all
 
 
+CASES_BY_CLASS = [(c, cls) for c in CASES for cls in CLASSES if cls not in c["without"]]
+
+
 @gpu
-@pytest.mark.parametrize("cls", list(CLASSES))
-@pytest.mark.parametrize("case", CASES, ids=_case_id)
+@pytest.mark.parametrize("case,cls", CASES_BY_CLASS, ids=["%s-%s" % (_case_id(c), cls) for c, cls in CASES_BY_CLASS])
 def test_special_values_through_every_sweep_form(device, switches, case, cls):
     """One value class through one sweep form: both sweeps seeded from the old generation and from zero (orc.tile_step with
     the matching l_is_root / r_is_root), then two whole iterations (orc.factorize) -- NaN in the same places, the same bits
@@ -430,6 +583,8 @@ def test_special_values_through_every_sweep_form(device, switches, case, cls):
         desc = plan.describe()
         assert case["check"](desc, K), desc
         assert ("MF_SWEEP_NCH=5" in desc) == (case["nch"] == "5"), desc
+        if case.get("wide"):
+            assert wide_nch(desc, case), desc
         where = "%s %s K=%d [%s]" % (_case_id(case), cls, K, desc.split(" loss=")[0])
         if case["steps"]:
             for seed, want in ((True, x.seeded), (False, x.unseeded)):

@@ -224,7 +224,8 @@ def test_topn_kernels_isa(capi):
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-KS = [8, 20, 30, 64, 100, 128, 256]
+EXACT_KS = [8, 30, 301, 1024]      # no matrix-core shape: the exact pass for everybody; 301 and 1024 lie above every shape
+KS = [8, 20, 30, 64, 100, 128, 256, 301, 1024]
 NS = [1, 3, 10, 16, 17, 32]
 
 
@@ -256,7 +257,7 @@ def test_topn_every_k_and_n_equals_the_model(gpu, orc, K, impl, split, monkeypat
         assert_same(it, sc, mi[:, :n], ms[:, :n], (K, n, impl))
         assert np.array_equal(it[:, 0], best), (K, n, impl)
         exact_users, form = plan.recommend_topn_info()
-        if impl == "exact" or K in (8, 30):
+        if impl == "exact" or K in EXACT_KS:
             assert exact_users == -1 and form == 0
         else:
             assert form in (1, 2) and exact_users >= 2     # the NaN and the inf user at least

@@ -23,11 +23,12 @@ import pytest
 
 from conftest import GOLDEN, ROOT, golden_in, to_text
 from test_loss import KS as LOSS_KS
+from test_loss import loss_shape
 from test_loss import instance as loss_instance
 from test_loss import model_p, model_total, seq_sum
 from test_momentum import BETA, BETA_I, BETA_U, LAM, MModel, msweep, random_prev
 from test_momentum import expected as momentum_expected
-from test_regularised import CASES, LAM_I, LAM_U, LARGE, ZERO_FORMS, _case_id, _pick, _small, _toy, decay, differs, fast_dot
+from test_regularised import CASES, LAM_I, LAM_U, LARGE, WIDE, ZERO_FORMS, _case_id, _pick, _small, _toy, decay, differs, fast_dot
 from test_sweep_edges import (GRID_CAP, PF_ROWS, SINGLE, SWEEPS, SWITCHES, _single_wave, assert_same_bits, cls_signed, is_negzero, pattern,
                               pattern_both_large, seq_dot, signed_inputs)
 
@@ -368,8 +369,9 @@ def switches(monkeypatch):
 
 def test_every_form_is_in_the_table():
     names = {c["name"] for c in CASES}
-    assert names == {"reg", "dma-ct", "dma-rt", "db", "pair", "long", "long-nodpp", "coop", "es-sw8", "es-sw4", "es-sw2"}
-    assert len(CASES) == 2 * 2 * len(names)
+    assert names == {"reg", "reg-wide", "dma-ct", "dma-rt", "db", "pair", "long", "long-nodpp", "coop", "es-sw8", "es-sw4", "es-sw2"}
+    assert len(CASES) == 2 * 2 * (len(names) - 1) + 2 * len(WIDE)      # both ends of every narrow row, and the wide rows
+    assert {(c["name"], c["K"]) for c in CASES if c["pat"] == "wide"} == {("reg-wide", 513), ("reg-wide", 4095), ("dma-rt", 1024)}
 
 
 def _plan(capi, pat, K, val, alpha, w, lam=LAM, beta=BETA, **kw):
@@ -768,25 +770,26 @@ def test_weighted_training_loss_equals_the_model(device, switches, K):
     the held-out loss on the same plan the unweighted model's, and weights of 1.0 give the unweighted bits."""
     capi = device
     switches({})
-    row, col, val, L, R = loss_instance(K, 1100, 260, K)
+    U, I = loss_shape(K)                       # 100 x 100 at K = 4095, where a factor row is 32 KiB
+    row, col, val, L, R = loss_instance(K, U, I, K)
     w = plain_weights(K, len(row))
     w[:4] = SPECIAL_WEIGHTS
-    plan = capi.Plan(1100, 260, K, 0.01, row, col, val, weight=w)
+    plan = capi.Plan(U, I, K, 0.01, row, col, val, weight=w)
     try:
         desc = plan.describe()
-        assert ("loss=loss_dma_kernel(" if K % 2 == 0 else "loss=loss_reg_kernel(") in desc and " weighted=1" in desc, desc
+        assert ("loss=loss_dma_kernel(" if K % 2 == 0 and K <= 1024 else "loss=loss_reg_kernel(") in desc and " weighted=1" in desc, desc
         plan.upload(L, R)
         ms = _check_weighted_loss(plan, L, R, row, col, val, w, "K=%d" % K)
-        plain = wmodel_rows(L, R, row, col, val, None, 1100)
+        plain = wmodel_rows(L, R, row, col, val, None, U)
         assert differs(ms, plain) > 0.5 and ms[0] == 0.0 and ms[5] == 0.0
         plan.set_heldout(row[::3], col[::3], val[::3] + 0.5)
         out, rs = plan.loss("heldout", rows=True)
-        hs = wmodel_rows(L, R, row[::3], col[::3], val[::3] + 0.5, None, 1100)
+        hs = wmodel_rows(L, R, row[::3], col[::3], val[::3] + 0.5, None, U)
         assert_same_bits(rs, hs, "K=%d: the held-out loss is unweighted" % K)
         assert_same_bits(np.array([out.sse]), np.array([model_total(hs)]), "K=%d: held-out sse" % K)
     finally:
         plan.close()
-    ones = capi.Plan(1100, 260, K, 0.01, row, col, val, weight=np.ones(len(row)))
+    ones = capi.Plan(U, I, K, 0.01, row, col, val, weight=np.ones(len(row)))
     try:
         ones.upload(L, R)
         out, rs = ones.loss("train", rows=True)
