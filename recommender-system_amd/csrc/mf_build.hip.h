@@ -391,7 +391,7 @@ int build_sparse(mf_plan *p, const mf_shard *s_in, const mf_entry *aos, bool swa
 mf_sched::Caps schedule_caps(const mf_plan *p)
 {
 	mf_sched::Caps c;
-	c.prod = p->sweep.prod, c.pf = p->sweep.pf, c.pair = p->sweep.pair, c.coop = p->sweep.coop, c.db = p->sweep.db;
+	c.prod = p->sweep.prod[0] != nullptr, c.pf = p->sweep.has(kPipelined), c.pair = p->sweep.has(kPair), c.coop = p->sweep.has(kCoop), c.db = p->sweep.has(kDb);
 	c.row_bytes = p->sweep.row_bytes, c.xs_bytes = p->sweep.xs_bytes, c.single_nch = p->single.nch;
 	c.coop_producers = mf::kCoopProducers, c.coop_waves = mf::kCoopWaves, c.slice_cols = mf::kSliceCols;
 	c.block_entries = mf::kBlockEntries, c.wave = mf::kWave, c.lds_per_cu = kLdsPerCu;
@@ -453,15 +453,11 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 	}
 	// ---- LDS limits, the scratch, the side stream and its events
 	if (s.coop.nch) {
-		p->coop = SweepForm{p->sweep.coop, s.coop.nch, s.coop.lds, mf::kCoopWaves * mf::kWave};
-		MF_HIP(raise_lds_limit((const void *) p->coop.fn, p->coop.lds));
-		if (p->sweep.coop_mom) MF_HIP(raise_lds_limit((const void *) p->sweep.coop_mom, p->coop.lds));
-		if (p->weighted)
-			for (SweepFn fn : {p->sweep.coop_wd, p->sweep.coop_wm})
-				if (fn) MF_HIP(raise_lds_limit((const void *) fn, p->coop.lds));
+		p->coop = LaunchGeometry{s.coop.nch, s.coop.lds, mf::kCoopWaves * mf::kWave};
+		MF_TRY(raise_form_limits(p, kCoop, p->coop.lds));
 	}
 	if (s.extreme) {
-		p->prod = SweepForm{p->weighted ? p->sweep.prod_w : p->sweep.prod, s.prod_nch, s.prod_lds, mf::kWave};
+		p->prod = SweepForm{{s.prod_nch, s.prod_lds, mf::kWave}, p->sweep.prod[p->weighted]};
 		p->lds_bytes_osum = mf::kOrderedSumLds;
 		MF_HIP(raise_lds_limit((const void *) p->prod.fn, p->prod.lds));
 		MF_HIP(raise_lds_limit(ordered_sum_fn(p->cfg), p->lds_bytes_osum));
@@ -506,7 +502,7 @@ int plan_es_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vector
 		MF_HIP(hipGetLastError());
 		MF_HIP(hipStreamSynchronize(p->stream));
 	}
-	MF_HIP(raise_lds_limit((const void *) (p->weighted ? p->sweep.errs_w : p->sweep.errs), p->es_lds_errors));
+	MF_HIP(raise_lds_limit((const void *) p->sweep.errs[p->weighted], p->es_lds_errors));
 	// ---- LDS-resident streams (mf_resident.hip.h): ~one workgroup per CU
 	int ncu = 256;
 	{

@@ -10,6 +10,8 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
+#include <array>
+#include <cstdarg>
 #include <cstdio>
 #include <cmath>
 #include <cstdlib>
@@ -244,7 +246,7 @@ int mf_plan_upload_factors(mf_plan *p, const double *L_block, const double *R)
 		                        hipMemcpyHostToDevice, p->stream));
 	MF_HIP(hipStreamSynchronize(p->stream));
 	p->have_factors = true;
-	p->at_rest[0] = p->at_rest[1] = true;   // new factors have no history
+	p->rule[0].at_rest = p->rule[1].at_rest = true;   // new factors have no history
 	return MF_OK;
 }
 
@@ -261,8 +263,8 @@ int mf_plan_upload_previous(mf_plan *p, const double *L_prev_block, const double
 		MF_HIP(hipMemcpy2DAsync(p->Rbuf[p->cur ^ 1], (size_t) p->ldr * sizeof(double), R_prev, w, w, (size_t) p->items,
 		                        hipMemcpyHostToDevice, p->stream));
 	MF_HIP(hipStreamSynchronize(p->stream));
-	if (L_prev_block) p->at_rest[1] = false;
-	if (R_prev) p->at_rest[0] = false;
+	if (L_prev_block) p->rule[1].at_rest = false;
+	if (R_prev) p->rule[0].at_rest = false;
 	return MF_OK;
 }
 
@@ -274,10 +276,10 @@ int mf_plan_download_previous(mf_plan *p, double *L_prev_block, double *R_prev)
 	const size_t w = (size_t) p->K * sizeof(double);
 	// a side at rest has no history of its own: X_prev = X_old
 	if (L_prev_block && p->uc)
-		MF_HIP(hipMemcpy2DAsync(L_prev_block, w, p->Lbuf[p->at_rest[1] ? p->cur : p->cur ^ 1], (size_t) p->ldl * sizeof(double), w,
+		MF_HIP(hipMemcpy2DAsync(L_prev_block, w, p->Lbuf[p->rule[1].at_rest ? p->cur : p->cur ^ 1], (size_t) p->ldl * sizeof(double), w,
 		                        (size_t) p->uc, hipMemcpyDeviceToHost, p->stream));
 	if (R_prev && p->items)
-		MF_HIP(hipMemcpy2DAsync(R_prev, w, p->Rbuf[p->at_rest[0] ? p->cur : p->cur ^ 1], (size_t) p->ldr * sizeof(double), w,
+		MF_HIP(hipMemcpy2DAsync(R_prev, w, p->Rbuf[p->rule[0].at_rest ? p->cur : p->cur ^ 1], (size_t) p->ldr * sizeof(double), w,
 		                        (size_t) p->items, hipMemcpyDeviceToHost, p->stream));
 	MF_HIP(hipStreamSynchronize(p->stream));
 	return MF_OK;
@@ -390,12 +392,13 @@ int mf_plan_iterate(mf_plan *p, int iters)
 			ra.ldr = p->ldr;
 			ra.iters = iters;
 			ra.c2 = p->alpha * 2;
-			ra.d_users = side_decay(p, 1);
-			ra.d_items = side_decay(p, 0);
-			ra.frozen_users = p->frozen[1];
-			ra.frozen_items = p->frozen[0];
-			ra.box_users = mf::Box{p->box_lo[1], p->box_hi[1], side_columns(p, 1, 1)};
-			ra.box_items = mf::Box{p->box_lo[0], p->box_hi[0], side_columns(p, 0, 1)};
+			const SideUpdate items = side_update(p, 0, 1), users = side_update(p, 1, 1);
+			ra.d_users = users.d;
+			ra.d_items = items.d;
+			ra.frozen_users = users.frozen;
+			ra.frozen_items = items.frozen;
+			ra.box_users = users.box;
+			ra.box_items = items.box;
 			ra.csr_ptr = p->csr_ptr;
 			ra.csr_idx = p->csr_idx;
 			ra.csr_val = p->csr_val;
@@ -411,8 +414,8 @@ int mf_plan_iterate(mf_plan *p, int iters)
 			ra.nnz = (int) p->nnz;
 			// momentum: the next-generation buffers carry the history in; the generation before the final one goes out to
 			// the buffers the final one does not take
-			ra.beta_users = p->beta[1];
-			ra.beta_items = p->beta[0];
+			ra.beta_users = users.beta;
+			ra.beta_items = items.beta;
 			ra.L_hist = p->Lbuf[p->cur ^ 1];
 			ra.R_hist = p->Rbuf[p->cur ^ 1];
 			ra.L_prev = p->Lbuf[fin ^ 1];
@@ -420,7 +423,7 @@ int mf_plan_iterate(mf_plan *p, int iters)
 			ra.csr_wgt = p->csr_wgt;
 			ra.csc_wgt = p->csc_wgt;
 			if (p->weighted) need = mf::resident_lds_bytes(p->uc, p->items, p->K, p->nnz, true);
-			const bool momentum = p->beta[0] != 0.0 || p->beta[1] != 0.0;
+			const bool momentum = items.beta != 0.0 || users.beta != 0.0;
 			const int threads = ((p->uc + p->items + 63) / 64) * 64;
 			void (*rfn)(mf::ResidentArgs) = p->K <= 4    ? mf::sweep_resident_kernel<4>
 			                                : p->K <= 16 ? mf::sweep_resident_kernel<16>
@@ -489,17 +492,17 @@ static bool lambda_ok(double v) { return std::isfinite(v) && v >= 0.0; }
 int mf_plan_set_regularization(mf_plan *p, double lambda_users, double lambda_items)
 {
 	if (!p || !lambda_ok(lambda_users) || !lambda_ok(lambda_items)) return MF_ERR_ARGUMENT;
-	// read by side_decay at every launch (the graph path captures per call): nothing is cached from an earlier value
-	p->lambda[1] = lambda_users;
-	p->lambda[0] = lambda_items;
+	// read by side_update at every launch (the graph path captures per call): nothing is cached from an earlier value
+	p->rule[1].lambda = lambda_users;
+	p->rule[0].lambda = lambda_items;
 	return MF_OK;
 }
 
 int mf_plan_get_regularization(mf_plan *p, double *lambda_users, double *lambda_items)
 {
 	if (!p) return MF_ERR_ARGUMENT;
-	if (lambda_users) *lambda_users = p->lambda[1];
-	if (lambda_items) *lambda_items = p->lambda[0];
+	if (lambda_users) *lambda_users = p->rule[1].lambda;
+	if (lambda_items) *lambda_items = p->rule[0].lambda;
 	return MF_OK;
 }
 
@@ -508,18 +511,18 @@ int mf_plan_set_momentum(mf_plan *p, double beta_users, double beta_items)
 	if (!p || !lambda_ok(beta_users) || !lambda_ok(beta_items)) return MF_ERR_ARGUMENT;   // finite and >= 0, like a weight
 	// read at every launch (the graph path captures per call).  A side whose beta leaves 0 has maintained no history: it
 	// is at rest; a change between two non-zero values keeps the history
-	if (p->beta[1] == 0.0 && beta_users != 0.0) p->at_rest[1] = true;
-	if (p->beta[0] == 0.0 && beta_items != 0.0) p->at_rest[0] = true;
-	p->beta[1] = beta_users;
-	p->beta[0] = beta_items;
+	if (p->rule[1].beta == 0.0 && beta_users != 0.0) p->rule[1].at_rest = true;
+	if (p->rule[0].beta == 0.0 && beta_items != 0.0) p->rule[0].at_rest = true;
+	p->rule[1].beta = beta_users;
+	p->rule[0].beta = beta_items;
 	return MF_OK;
 }
 
 int mf_plan_get_momentum(mf_plan *p, double *beta_users, double *beta_items)
 {
 	if (!p) return MF_ERR_ARGUMENT;
-	if (beta_users) *beta_users = p->beta[1];
-	if (beta_items) *beta_items = p->beta[0];
+	if (beta_users) *beta_users = p->rule[1].beta;
+	if (beta_items) *beta_items = p->rule[0].beta;
 	return MF_OK;
 }
 
@@ -527,16 +530,16 @@ int mf_plan_set_frozen_columns(mf_plan *p, int32_t users_col, int32_t items_col)
 {
 	if (!p || users_col < -1 || items_col < -1 || users_col >= p->K || items_col >= p->K) return MF_ERR_ARGUMENT;
 	// read at every launch, like the decay: the graph path captures per call, so no replay sees an earlier value
-	p->frozen[1] = users_col;
-	p->frozen[0] = items_col;
+	p->rule[1].frozen = users_col;
+	p->rule[0].frozen = items_col;
 	return MF_OK;
 }
 
 int mf_plan_get_frozen_columns(mf_plan *p, int32_t *users_col, int32_t *items_col)
 {
 	if (!p) return MF_ERR_ARGUMENT;
-	if (users_col) *users_col = p->frozen[1];
-	if (items_col) *items_col = p->frozen[0];
+	if (users_col) *users_col = p->rule[1].frozen;
+	if (items_col) *items_col = p->rule[0].frozen;
 	return MF_OK;
 }
 
@@ -548,18 +551,18 @@ int mf_plan_set_bounds(mf_plan *p, int side, double lo, double hi, int32_t colum
 	// the plan is looked at last: everything else is refused without it
 	if (!p || (side != 0 && side != 1) || !bounds_ok(lo, hi, columns) || columns > p->K) return MF_ERR_ARGUMENT;
 	// read at every launch, like the decay: the graph path captures per call, so no replay sees an earlier value
-	p->box_lo[side] = lo;
-	p->box_hi[side] = hi;
-	p->box_columns[side] = columns;
+	p->rule[side].lo = lo;
+	p->rule[side].hi = hi;
+	p->rule[side].columns = columns;
 	return MF_OK;
 }
 
 int mf_plan_get_bounds(mf_plan *p, int side, double *lo, double *hi, int32_t *columns)
 {
 	if (!p || (side != 0 && side != 1)) return MF_ERR_ARGUMENT;
-	if (lo) *lo = p->box_lo[side];
-	if (hi) *hi = p->box_hi[side];
-	if (columns) *columns = p->box_columns[side];
+	if (lo) *lo = p->rule[side].lo;
+	if (hi) *hi = p->rule[side].hi;
+	if (columns) *columns = p->rule[side].columns;
 	return MF_OK;
 }
 
@@ -570,10 +573,12 @@ static mf::BoxArgs box_args(mf_plan *p, int side, int generation)
 	a.X = side == 0 ? p->Rbuf[p->cur ^ generation] : p->Lbuf[p->cur ^ generation];
 	a.rows = side == 0 ? p->items : p->uc;
 	a.ld = side == 0 ? p->ldr : p->ldl;
-	a.columns = p->box_columns[side] < 0 ? p->K : p->box_columns[side];
-	a.frozen = p->frozen[side];
-	a.lo = p->box_lo[side];
-	a.hi = p->box_hi[side];
+	const SideUpdate u = side_update(p, side, 1);
+	// the side's own column range, whatever its bounds: the count of an unbounded side puts every entry `inside`
+	a.columns = p->rule[side].columns < 0 ? p->K : p->rule[side].columns;
+	a.frozen = u.frozen;
+	a.lo = u.box.lo;
+	a.hi = u.box.hi;
 	a.counts = nullptr;
 	return a;
 }
@@ -856,6 +861,17 @@ int mf_plan_timing_read(mf_plan *p, int64_t *item_launches, double *item_ms, int
 	return MF_OK;
 }
 
+// printf at the end of the text in buf, while there is room for any of it
+__attribute__((format(printf, 3, 4))) static void append(char *buf, int buflen, const char *fmt, ...)
+{
+	const size_t at = strlen(buf);
+	if (at + 1 >= (size_t) buflen) return;
+	va_list ap;
+	va_start(ap, fmt);
+	vsnprintf(buf + at, (size_t) buflen - at, fmt, ap);
+	va_end(ap);
+}
+
 int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 {
 	if (!p || !buf || buflen <= 0) return MF_ERR_ARGUMENT;
@@ -884,49 +900,31 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 			         p->es_nseg, p->es_nch, p->res_sw, p->res_nwg, p->es_lds_errors, p->res_lds);
 	}
 	// the row-sum launch of mf_plan_loss: form, chunk sizes (ordinary / few rows) and LDS requests
-	{
-		const size_t at = strlen(buf);
-		if (at + 1 < (size_t) buflen)
-			snprintf(buf + at, (size_t) buflen - at, " loss=%s(nch=%d/%d lds=%zu/%zu)", p->sweep.dma ? "loss_dma_kernel" : "loss_reg_kernel",
-			         p->loss_nch[0], p->loss_nch[1], p->loss_lds[0], p->loss_lds[1]);
-	}
-	// the regularisation in force, when there is any
-	if (p->lambda[0] != 0.0 || p->lambda[1] != 0.0) {
-		const size_t at = strlen(buf);
-		if (at + 1 < (size_t) buflen) snprintf(buf + at, (size_t) buflen - at, " lambda=%g/%g", p->lambda[1], p->lambda[0]);
-	}
-	// the momentum in force, when there is any
-	if (p->beta[0] != 0.0 || p->beta[1] != 0.0) {
-		const size_t at = strlen(buf);
-		if (at + 1 < (size_t) buflen) snprintf(buf + at, (size_t) buflen - at, " momentum=%g/%g", p->beta[1], p->beta[0]);
-	}
-	// the frozen columns in force, when there is one
-	if (p->frozen[0] >= 0 || p->frozen[1] >= 0) {
-		const size_t at = strlen(buf);
-		if (at + 1 < (size_t) buflen) snprintf(buf + at, (size_t) buflen - at, " frozen=%d/%d", p->frozen[1], p->frozen[0]);
-	}
+	append(buf, buflen, " loss=%s(nch=%d/%d lds=%zu/%zu)", p->sweep.dma ? "loss_dma_kernel" : "loss_reg_kernel", p->loss_nch[0], p->loss_nch[1],
+	       p->loss_lds[0], p->loss_lds[1]);
+	// the update rule in force, users / items, each part when a side has any: regularisation, momentum, frozen columns
+	const SideRule &ri = p->rule[0], &ru = p->rule[1];
+	if (ri.lambda != 0.0 || ru.lambda != 0.0) append(buf, buflen, " lambda=%g/%g", ru.lambda, ri.lambda);
+	if (ri.beta != 0.0 || ru.beta != 0.0) append(buf, buflen, " momentum=%g/%g", ru.beta, ri.beta);
+	if (ri.frozen >= 0 || ru.frozen >= 0) append(buf, buflen, " frozen=%d/%d", ru.frozen, ri.frozen);
 	// the box constraints in force, when a side has one: bounds=<users>/<items>, a side as [lo,hi]x<columns> with the bounds
 	// in %.17g (they read back exactly) and the columns counted (-1 told: K), or - for a side without
-	if (side_columns(p, 0, 1) > 0 || side_columns(p, 1, 1) > 0) {
+	const mf::Box box[2] = {side_update(p, 0, 1).box, side_update(p, 1, 1).box};
+	if (box[0].columns > 0 || box[1].columns > 0) {
 		char sd[2][96];
 		for (int k = 0; k < 2; ++k) {
-			if (side_columns(p, k, 1) > 0)
-				snprintf(sd[k], sizeof sd[k], "[%.17g,%.17g]x%d", p->box_lo[k], p->box_hi[k], side_columns(p, k, 1));
+			if (box[k].columns > 0)
+				snprintf(sd[k], sizeof sd[k], "[%.17g,%.17g]x%d", box[k].lo, box[k].hi, box[k].columns);
 			else
 				snprintf(sd[k], sizeof sd[k], "-");
 		}
-		const size_t at = strlen(buf);
-		if (at + 1 < (size_t) buflen) snprintf(buf + at, (size_t) buflen - at, " bounds=%s/%s", sd[1], sd[0]);
+		append(buf, buflen, " bounds=%s/%s", sd[1], sd[0]);
 	}
 	// per-entry weights, when the plan was created with them
-	if (p->weighted) {
-		const size_t at = strlen(buf);
-		if (at + 1 < (size_t) buflen) snprintf(buf + at, (size_t) buflen - at, " weighted=1");
-	}
+	if (p->weighted) append(buf, buflen, " weighted=1");
 	// the environment switches this plan was created under, when any differs from its default (mf_config.hip.h)
 	const std::string cfg = p->cfg.describe();
-	const size_t used = strlen(buf);
-	if (!cfg.empty() && used + 1 < (size_t) buflen) snprintf(buf + used, (size_t) buflen - used, " config{%s}", cfg.c_str());
+	if (!cfg.empty()) append(buf, buflen, " config{%s}", cfg.c_str());
 	return MF_OK;
 }
 
@@ -957,30 +955,48 @@ static int with_single_plan(const mf_problem *pr, int device, const double *L, c
 	return rc;
 }
 
+// a level-1 bounds record: NULL (no bounds) or a box that mf_plan_set_bounds would take at this K
+static bool bounds_record_ok(const mf_bounds *b, int K) { return !b || (bounds_ok(b->lo, b->hi, b->columns) && b->columns <= K); }
+
+// the update rules of a level-1 run, [0] = items, [1] = users: what the entry point was given, the defaults for the rest
+using RulePair = std::array<SideRule, 2>;
+static RulePair level1_rules(double lambda_users, double lambda_items, double beta_users = 0.0, double beta_items = 0.0,
+                             const mf_bounds *bounds_users = nullptr, const mf_bounds *bounds_items = nullptr)
+{
+	RulePair r;
+	r[1].lambda = lambda_users, r[0].lambda = lambda_items;
+	r[1].beta = beta_users, r[0].beta = beta_items;
+	if (bounds_users) r[1].lo = bounds_users->lo, r[1].hi = bounds_users->hi, r[1].columns = bounds_users->columns;
+	if (bounds_items) r[0].lo = bounds_items->lo, r[0].hi = bounds_items->hi, r[0].columns = bounds_items->columns;
+	return r;
+}
+
+// The level-1 run: a plan over the whole problem (weighted when `weight` is given), the factors up, the update rules the
+// entry point checked, pr->iters iterations, the recommendations when asked for, the factors back into L and R.
+static int run_single_plan(const mf_problem *pr, const double *weight, const RulePair &rule, double *L, double *R, int32_t *best, int device)
+{
+	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
+		p->rule[0] = rule[0], p->rule[1] = rule[1];   // both sides at rest, as the upload left them
+		int rc = mf_plan_iterate(p, pr->iters);
+		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
+		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
+		return rc;
+	}, weight);
+}
+
 extern "C" {
 
 int mf_backend_run(const mf_problem *pr, double *L, double *R, int32_t *best, int device)
 {
 	if (!pr || !L || !R) return MF_ERR_ARGUMENT;   // L and R carry the initial factors in
-	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
-		int rc = mf_plan_iterate(p, pr->iters);
-		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
-		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
-		return rc;
-	});
+	return run_single_plan(pr, nullptr, RulePair{}, L, R, best, device);
 }
 
 int mf_backend_run_reg(const mf_problem *pr, double *L, double *R, int32_t *best, double lambda_users, double lambda_items,
                        int device)
 {
 	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items)) return MF_ERR_ARGUMENT;
-	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
-		int rc = mf_plan_set_regularization(p, lambda_users, lambda_items);
-		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
-		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
-		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
-		return rc;
-	});
+	return run_single_plan(pr, nullptr, level1_rules(lambda_users, lambda_items), L, R, best, device);
 }
 
 int mf_backend_run_momentum(const mf_problem *pr, double *L, double *R, int32_t *best, double lambda_users, double lambda_items,
@@ -988,14 +1004,7 @@ int mf_backend_run_momentum(const mf_problem *pr, double *L, double *R, int32_t 
 {
 	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !lambda_ok(beta_users) || !lambda_ok(beta_items))
 		return MF_ERR_ARGUMENT;
-	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
-		int rc = mf_plan_set_regularization(p, lambda_users, lambda_items);
-		if (rc == MF_OK) rc = mf_plan_set_momentum(p, beta_users, beta_items);
-		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
-		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
-		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
-		return rc;
-	});
+	return run_single_plan(pr, nullptr, level1_rules(lambda_users, lambda_items, beta_users, beta_items), L, R, best, device);
 }
 
 int mf_backend_run_weighted(const mf_problem *pr, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
@@ -1003,18 +1012,8 @@ int mf_backend_run_weighted(const mf_problem *pr, const double *weight, double *
 {
 	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !lambda_ok(beta_users) || !lambda_ok(beta_items))
 		return MF_ERR_ARGUMENT;
-	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
-		int rc = mf_plan_set_regularization(p, lambda_users, lambda_items);
-		if (rc == MF_OK) rc = mf_plan_set_momentum(p, beta_users, beta_items);
-		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
-		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
-		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
-		return rc;
-	}, weight);
+	return run_single_plan(pr, weight, level1_rules(lambda_users, lambda_items, beta_users, beta_items), L, R, best, device);
 }
-
-// a level-1 bounds record: NULL (no bounds) or a box that mf_plan_set_bounds would take at this K
-static bool bounds_record_ok(const mf_bounds *b, int K) { return !b || (bounds_ok(b->lo, b->hi, b->columns) && b->columns <= K); }
 
 int mf_backend_run_bounded(const mf_problem *pr, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
                            double lambda_items, double beta_users, double beta_items, const mf_bounds *bounds_users,
@@ -1023,16 +1022,8 @@ int mf_backend_run_bounded(const mf_problem *pr, const double *weight, double *L
 	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !lambda_ok(beta_users) || !lambda_ok(beta_items) ||
 	    !bounds_record_ok(bounds_users, pr->features) || !bounds_record_ok(bounds_items, pr->features))
 		return MF_ERR_ARGUMENT;
-	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
-		int rc = mf_plan_set_regularization(p, lambda_users, lambda_items);
-		if (rc == MF_OK) rc = mf_plan_set_momentum(p, beta_users, beta_items);
-		if (rc == MF_OK && bounds_users) rc = mf_plan_set_bounds(p, 1, bounds_users->lo, bounds_users->hi, bounds_users->columns);
-		if (rc == MF_OK && bounds_items) rc = mf_plan_set_bounds(p, 0, bounds_items->lo, bounds_items->hi, bounds_items->columns);
-		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
-		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
-		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
-		return rc;
-	}, weight);
+	return run_single_plan(pr, weight, level1_rules(lambda_users, lambda_items, beta_users, beta_items, bounds_users, bounds_items), L, R,
+	                       best, device);
 }
 
 // ---- biases on frozen columns: a ~ mu + b_user + b_item + l.r as the K = F + 2 product of
@@ -1098,14 +1089,9 @@ int mf_backend_run_biased(const mf_problem *pr, double *L, double *R, double *us
 	mf_problem q = *pr;
 	q.features = K;
 	q.entries = ent.data();
-	const int rc = with_single_plan(&q, device, Lp.data(), Rp.data(), [&](mf_plan *p) {
-		int rc = mf_plan_set_regularization(p, lambda_users, lambda_items);
-		if (rc == MF_OK) rc = mf_plan_set_frozen_columns(p, F + 1, F);
-		if (rc == MF_OK) rc = mf_plan_iterate(p, q.iters);
-		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
-		if (rc == MF_OK) rc = mf_plan_download_factors(p, Lp.data(), Rp.data());
-		return rc;
-	});
+	RulePair rule = level1_rules(lambda_users, lambda_items);
+	rule[1].frozen = F + 1, rule[0].frozen = F;
+	const int rc = run_single_plan(&q, nullptr, rule, Lp.data(), Rp.data(), best, device);
 	if (rc != MF_OK) return rc;
 	(void) mf_backend_bias_unpack(Lp.data(), pr->users, F, 1, L, user_bias);
 	(void) mf_backend_bias_unpack(Rp.data(), pr->items, F, 0, R, item_bias);

@@ -1,6 +1,5 @@
 // mf_launch.hip.h -- choice of the sweep kernel variant / chunk size and the launch of one sweep.
 #pragma once
-#include <climits>
 
 namespace {
 
@@ -108,6 +107,17 @@ const void *stream_resident_fn(int sw, bool momentum = false)
 	return sw == 8 ? (const void *) mf::stream_resident_kernel<8> : sw == 4 ? (const void *) mf::stream_resident_kernel<4> : (const void *) mf::stream_resident_kernel<2>;
 }
 
+// Raises the LDS limit of every instance of one form that this plan may launch: the non-null cells of the form's row of
+// the grid -- the unweighted flavours, and on a weighted plan the weighted ones too (an unweighted plan touches none of
+// them).  Called once per form, where the form's geometry is decided.
+int raise_form_limits(const mf_plan *p, Form form, size_t bytes)
+{
+	const int flavours = p->weighted ? (int) kFlavours : mf_sched::kUnweightedFlavours;
+	for (int fl = 0; fl < flavours; ++fl)
+		if (const SweepFn fn = p->sweep.fn[form][fl]) MF_HIP(raise_lds_limit((const void *) fn, bytes));
+	return MF_OK;
+}
+
 int choose_sweep(mf_plan *p)
 {
 	const int K = p->K;
@@ -116,62 +126,47 @@ int choose_sweep(mf_plan *p)
 	if (allow_dma)
 		for (const auto &v : kDma)
 			if (v.kt == K) p->sweep = v;
-	if (!p->sweep.fn && allow_dma && (K & 1) == 0)
+	if (!p->sweep.has(kPlain) && allow_dma && (K & 1) == 0)
 		for (const auto &v : kDmaGeneric)
-			if (K <= 128 * v.kpmax && !p->sweep.fn) {
+			if (K <= 128 * v.kpmax && !p->sweep.has(kPlain)) {
 				p->sweep = v;
 				p->sweep.row_bytes = mf::dma_row_stride(K);
 				p->sweep.xs_bytes = mf::dma_xs_bytes(K);
 			}
-	if (!p->sweep.fn)
+	if (!p->sweep.has(kPlain))
 		for (const auto &v : kSpecialised)
 			if (v.kt == K) p->sweep = v;
-	if (!p->sweep.fn)
+	if (!p->sweep.has(kPlain))
 		for (const auto &v : kGeneric)
 			if (K <= v.kpmax * mf::kWave) {
 				p->sweep = v;
 				break;
 			}
-	if (!p->sweep.fn) return MF_ERR_UNSUPPORTED;
+	if (!p->sweep.has(kPlain)) return MF_ERR_UNSUPPORTED;
 
 	p->stride = mf::reg_row_stride(K);
 	const size_t row_bytes = tile_row_bytes(p), head = tile_head_bytes(p);
 	const ChunkSizes cs = chunk_rule(head, row_bytes, p->cfg);
 	if (cs.nch < 1) return MF_ERR_UNSUPPORTED;
-	p->single = SweepForm{nullptr, cs.nch, head + (size_t) cs.nch * row_bytes, mf::kWave};
-	p->few = SweepForm{nullptr, cs.nch_few, head + (size_t) cs.nch_few * row_bytes, mf::kWave};
-	MF_HIP(raise_lds_limit((const void *) p->sweep.fn, std::max(p->single.lds, p->few.lds)));
-	if (p->sweep.pf) MF_HIP(raise_lds_limit((const void *) p->sweep.pf, std::max(p->single.lds, p->few.lds)));
-	if (p->sweep.fn_decay) MF_HIP(raise_lds_limit((const void *) p->sweep.fn_decay, std::max(p->single.lds, p->few.lds)));
-	if (p->sweep.pf_decay) MF_HIP(raise_lds_limit((const void *) p->sweep.pf_decay, std::max(p->single.lds, p->few.lds)));
-	if (p->sweep.fn_mom) MF_HIP(raise_lds_limit((const void *) p->sweep.fn_mom, std::max(p->single.lds, p->few.lds)));
-	if (p->sweep.pf_mom) MF_HIP(raise_lds_limit((const void *) p->sweep.pf_mom, std::max(p->single.lds, p->few.lds)));
-	if (p->weighted)   // the weighted twins, on weighted plans only: an unweighted plan touches none of them
-		for (SweepFn fn : {p->sweep.fn_wd, p->sweep.pf_wd, p->sweep.fn_wm, p->sweep.pf_wm})
-			if (fn) MF_HIP(raise_lds_limit((const void *) fn, std::max(p->single.lds, p->few.lds)));
+	p->single = LaunchGeometry{cs.nch, head + (size_t) cs.nch * row_bytes, mf::kWave};
+	p->few = LaunchGeometry{cs.nch_few, head + (size_t) cs.nch_few * row_bytes, mf::kWave};
+	MF_TRY(raise_form_limits(p, kPlain, std::max(p->single.lds, p->few.lds)));
+	MF_TRY(raise_form_limits(p, kPipelined, std::max(p->single.lds, p->few.lds)));
 	// the two-tile forms: `dflt` entries per chunk (MF_SWEEP_NCH overrides) while two tiles stay within half a CU's LDS
-	auto two_tiles = [&](SweepFn fn, int dflt, int block) {
+	auto two_tiles = [&](int dflt, int block) {
 		int n = p->cfg.sweep_nch ? p->cfg.sweep_nch : dflt;
 		while (n > 1 && head + 2 * (size_t) n * row_bytes > kLdsPerCu / 2) --n;
-		return SweepForm{fn, n, head + 2 * (size_t) n * row_bytes, block};
+		return LaunchGeometry{n, head + 2 * (size_t) n * row_bytes, block};
 	};
-	if (p->sweep.pair) {   // wave-pair form
+	if (p->sweep.has(kPair)) {   // wave-pair form
 		// 32-entry chunks: the loader's ~90 cycles per gathered row are what a pair is bound by, the K steps of phase A are
 		// paid per chunk -- a lone 5993-entry row: 0.526 ms at 16, 0.332 at 32; cfg3 power-law 0.311 / 0.268 / 0.314 at 24 / 32 / 40
-		p->pair = two_tiles(p->sweep.pair, 32, 2 * mf::kWave);
-		MF_HIP(raise_lds_limit((const void *) p->pair.fn, p->pair.lds));
-		if (p->sweep.pair_mom) MF_HIP(raise_lds_limit((const void *) p->sweep.pair_mom, p->pair.lds));
-		if (p->weighted)
-			for (SweepFn fn : {p->sweep.pair_wd, p->sweep.pair_wm})
-				if (fn) MF_HIP(raise_lds_limit((const void *) fn, p->pair.lds));
+		p->pair = two_tiles(32, 2 * mf::kWave);
+		MF_TRY(raise_form_limits(p, kPair, p->pair.lds));
 	}
-	if (p->sweep.db) {   // double-buffered form (few rows per CU: the wave hides its own gather)
-		p->db = two_tiles(p->sweep.db, 16, mf::kWave);
-		MF_HIP(raise_lds_limit((const void *) p->db.fn, p->db.lds));
-		if (p->sweep.db_mom) MF_HIP(raise_lds_limit((const void *) p->sweep.db_mom, p->db.lds));
-		if (p->weighted)
-			for (SweepFn fn : {p->sweep.db_wd, p->sweep.db_wm})
-				if (fn) MF_HIP(raise_lds_limit((const void *) fn, p->db.lds));
+	if (p->sweep.has(kDb)) {   // double-buffered form (few rows per CU: the wave hides its own gather)
+		p->db = two_tiles(16, mf::kWave);
+		MF_TRY(raise_form_limits(p, kDb, p->db.lds));
 	}
 	// ---- errors + streams iteration (mf_stream.hip.h) for instances whose factors stay in L2 / Infinity Cache: the
 	// two sweeps are then bound by the latency of one wave walking a row chunk by chunk, not by bandwidth.  It costs a
@@ -179,7 +174,7 @@ int choose_sweep(mf_plan *p)
 	// sweeps overrides.
 	p->want_map = false;
 	p->res_sw = resident_slice_width(p->cfg, K, std::max(p->uc, p->items));
-	if (p->sweep.errs && p->nnz > 0) {
+	if (p->sweep.errs[0] && p->nnz > 0) {
 		// Used where the streams launch can keep a slice of Y resident in LDS (mf_resident.hip.h; instML100k 84 -> 39 us
 		// per iteration); MF_ITER_MODE=sweeps keeps the two sweeps, =es asks for it explicitly (same condition).
 		// Not below a few thousand entries: there two graph-replayed single-wave sweeps are quicker than a launch that
@@ -194,8 +189,6 @@ int choose_sweep(mf_plan *p)
 // no second buffer: the request is the L row plus nch gathered rows, at the sweeps' chunk rule (chunk_rule).
 int choose_loss(mf_plan *p)
 {
-	p->loss_fn = p->sweep.dma ? p->sweep.loss : mf::loss_reg_kernel;
-	if (!p->loss_fn) return MF_ERR_UNSUPPORTED;
 	const size_t row_bytes = tile_row_bytes(p), head = tile_head_bytes(p);
 	const ChunkSizes cs = chunk_rule(head, row_bytes, p->cfg);
 	if (cs.nch < 1) return MF_ERR_UNSUPPORTED;
@@ -203,109 +196,63 @@ int choose_loss(mf_plan *p)
 	p->loss_nch[1] = cs.nch_few;
 	p->loss_lds[0] = head + (size_t) cs.nch * row_bytes;
 	p->loss_lds[1] = head + (size_t) cs.nch_few * row_bytes;
-	MF_HIP(raise_lds_limit((const void *) p->loss_fn, std::max(p->loss_lds[0], p->loss_lds[1])));
-	if (p->weighted) {   // the training loss of a weighted plan: the weighted twin in the same geometry
-		p->loss_fn_w = p->sweep.dma ? p->sweep.loss_w : mf::loss_reg_w_kernel;
-		if (!p->loss_fn_w) return MF_ERR_UNSUPPORTED;
-		MF_HIP(raise_lds_limit((const void *) p->loss_fn_w, std::max(p->loss_lds[0], p->loss_lds[1])));
+	const LossFn reg[2] = {mf::loss_reg_kernel, mf::loss_reg_w_kernel};
+	// [1], the training loss of a weighted plan: the weighted twin in the same geometry, on weighted plans only
+	for (int w = 0; w <= (int) p->weighted; ++w) {
+		p->loss_fn[w] = p->sweep.dma ? p->sweep.loss[w] : reg[w];
+		if (!p->loss_fn[w]) return MF_ERR_UNSUPPORTED;
+		MF_HIP(raise_lds_limit((const void *) p->loss_fn[w], std::max(p->loss_lds[0], p->loss_lds[1])));
 	}
 	return MF_OK;
 }
 
-// Accumulate form of the single-wave launch of one side (kind 0: items, 1: users): true for the form with the pipelined
-// phases (sweep.pf), false for the plain one (sweep.fn).  Up to kPfRows rows: the form whose phases keep their LDS reads
-// in flight and whose gather issue is lean -- what a wave walking a long row alone is bound by (cfg3 uniform 0.224 ->
-// 0.201 ms, power-law 0.367 -> 0.350, a lone 5993-entry row 1.02 -> 0.78 ms).  Larger launches of one-pass rows
-// (K <= 128) are never bound by one wave and keep round 2's form (cfg4 user sweep, 1e6 rows: 11.45 vs 11.60 ms).
-// Two-pass rows (K = 256) take it at every size: their phase A is a 256-deep chain per chunk that the six resident
-// workgroups of a CU do not hide, and keeping its LDS reads in flight shortens it (cfg5: 346.6 -> 327.9 ms, 0.745 ->
-// 0.787).  launch_sweep chooses by it and mf_plan_describe prints it (accumulate=<items>/<users>).
+// Accumulate form of a side's single-wave launch, pipelined or plain (mf_schedule.h): main_form's and mf_plan_describe's.
 bool single_wave_pipelined(const mf_plan *p, int kind)
 {
-	const int kPfRows = p->K > 128 ? INT_MAX : 262144;
-	return p->sweep.pf && p->side[kind].n_short <= kPfRows && p->side[kind].nrows <= kPfRows;
+	return mf_sched::single_wave_pipelined(p->sweep.has(kPipelined), p->K, p->side[kind].n_short, p->side[kind].nrows);
 }
 
-// The form of the main launch of one side (kind 0: items, 1: users): the cooperative launch of a tiny sweep, the
-// double-buffered or the wave-pair form where plan_row_schedule chose one, else the single-wave form -- plain or
-// pipelined by single_wave_pipelined, at the large chunk when `few_rows`.
-// `momentum`: the launch is a seeded sweep of a side with beta != 0 -- every form then runs its momentum instance (null
-// where a K has none: launch_sweep refuses); without it the choice and the kernels are those of a plan without momentum.
-// `weighted`: the plan carries per-entry weights -- the same form at the same geometry (weights do not alter which form a
-// side takes) in its weighted twin: of the momentum instance under `momentum`, else of the decay instance, whatever d is.
-SweepForm main_form(const mf_plan *p, int kind, bool few_rows, bool decay, bool momentum, bool weighted = false)
+// The main launch of one side (kind 0: items, 1: users) by the rules of mf_schedule.h: its form, that form's geometry and
+// the instance of `flavour`.  A cell the K does not have leaves fn null: launch_sweep refuses rather than run another.
+SweepForm main_form(const mf_plan *p, int kind, bool few_rows, Flavour flavour)
 {
 	const SweepSide &sd = p->side[kind];
-	if (weighted) {
-		SweepForm f = main_form(p, kind, few_rows, decay, false);
-		if (sd.coop_all)
-			f.fn = momentum ? p->sweep.coop_wm : p->sweep.coop_wd;
-		else if (sd.use_db)
-			f.fn = momentum ? p->sweep.db_wm : p->sweep.db_wd;
-		else if (sd.use_pair)
-			f.fn = momentum ? p->sweep.pair_wm : p->sweep.pair_wd;
-		else if (p->sweep.dma && single_wave_pipelined(p, kind))
-			f.fn = momentum ? p->sweep.pf_wm : p->sweep.pf_wd;
-		else
-			f.fn = momentum ? p->sweep.fn_wm : p->sweep.fn_wd;
-		return f;
+	const Form form = mf_sched::launch_form(sd.coop_all, sd.use_db, sd.use_pair, single_wave_pipelined(p, kind));
+	LaunchGeometry lg = p->coop;
+	switch (mf_sched::launch_geometry(form, few_rows)) {
+	case mf_sched::kGeomSingle: lg = p->single; break;
+	case mf_sched::kGeomFew: lg = p->few; break;
+	case mf_sched::kGeomPair: lg = p->pair; break;
+	case mf_sched::kGeomDb: lg = p->db; break;
+	case mf_sched::kGeomCoop: break;
+	case mf_sched::kGeomCoopSingleNch: lg.nch = p->single.nch; break;
 	}
-	if (momentum) {
-		SweepForm f = main_form(p, kind, few_rows, decay, false);
-		if (sd.coop_all)
-			f.fn = p->sweep.coop_mom;
-		else if (sd.use_db)
-			f.fn = p->sweep.db_mom;
-		else if (sd.use_pair)
-			f.fn = p->sweep.pair_mom;
-		else
-			f.fn = p->sweep.dma && single_wave_pipelined(p, kind) ? p->sweep.pf_mom : p->sweep.fn_mom;
-		return f;
-	}
-	if (sd.coop_all) {
-		// A cooperative launch of kSweepFewRows rows or more runs at the single-wave chunk size with the cooperative LDS request,
-		// as it always has.  Known and left for a change of its own, with a test: at K = 30 and K = 50 that request is sized
-		// for fewer rows (14 and 8) than the 16 of the single-wave chunk.
-		SweepForm f = p->coop;
-		if (!few_rows) f.nch = p->single.nch;
-		return f;
-	}
-	if (sd.use_db) return p->db;
-	if (sd.use_pair) return p->pair;
-	SweepForm f = few_rows ? p->few : p->single;
-	// the LDS-DMA single-wave form multiplies the seed, and keeps a frozen column, only in its decay instances (the
-	// register-staged form always does) -- `decay` is "d != 1.0, or the side has a frozen column or a box constraint", x * 1.0 being x; a
-	// missing one leaves fn null and launch_sweep refuses, rather than run without the decay, the frozen column or the clamp
-	const bool pf = single_wave_pipelined(p, kind);
-	if (decay && p->sweep.dma)
-		f.fn = pf ? p->sweep.pf_decay : p->sweep.fn_decay;
-	else
-		f.fn = pf ? p->sweep.pf : p->sweep.fn;
-	return f;
+	return SweepForm{lg, p->sweep.fn[form][flavour]};
 }
 
-// Weight decay of a side's seed (kind 0: items, 1: users): d = 1.0 - (alpha * 2) * lambda, two roundings in double -- the
-// product, then the subtraction.  Read at every launch, so a change of lambda holds from the next sweep on; lambda = 0
-// is 1.0 whatever alpha is (a non-finite alpha times 0 would be NaN), and x * 1.0 is x bit for bit.
-double side_decay(const mf_plan *p, int kind)
+// The update rule of one launch of a side (kind 0: items, 1: users), from the side's record.  Read at every launch (a
+// captured graph is built per call), so a change holds from the next sweep on.
+//   d: weight decay of the seed, 1.0 - (alpha * 2) * lambda, two roundings in double -- the product, then the subtraction;
+//      lambda = 0 is 1.0 whatever alpha is (a non-finite alpha times 0 would be NaN), and x * 1.0 is x bit for bit.
+//   beta: the side's heavy-ball momentum for a seeded sweep, 0.0 -- no term -- for an unseeded one.
+//   box.columns: how many leading columns of a finished row are projected onto [lo, hi] -- the side's (-1: all K) for a
+//      seeded sweep of a side with a finite bound, 0 for an unseeded one (a partial sum is not clamped) and for a side whose
+//      bounds are both infinite (the clamp would change no bit).
+struct SideUpdate {
+	double d, beta;
+	int frozen;
+	mf::Box box;
+};
+SideUpdate side_update(const mf_plan *p, int kind, int seed)
 {
-	if (p->lambda[kind] == 0.0) return 1.0;
-	const double t = (p->alpha * 2) * p->lambda[kind];
-	return 1.0 - t;
-}
-
-// Heavy-ball momentum of a launch (kind 0: items, 1: users): the side's beta for a seeded sweep, 0.0 -- no term, today's
-// kernels -- for an unseeded one.  Read at every launch, like the decay.
-double side_momentum(const mf_plan *p, int kind, int seed) { return seed ? p->beta[kind] : 0.0; }
-
-// Box constraint of a launch (kind 0: items, 1: users): how many leading columns of a finished row are projected onto
-// [lo, hi] -- the side's `columns` (-1: all K) for a seeded sweep of a side with a finite bound, 0 for an unseeded one (a
-// partial sum is not clamped) and for a side whose bounds are both infinite (the clamp would change no bit: the launch
-// is then today's).  Read at every launch, like the decay.
-int side_columns(const mf_plan *p, int kind, int seed)
-{
-	if (!seed || (p->box_lo[kind] == -INFINITY && p->box_hi[kind] == INFINITY)) return 0;
-	return p->box_columns[kind] < 0 ? p->K : p->box_columns[kind];
+	const SideRule &r = p->rule[kind];
+	SideUpdate u{1.0, seed ? r.beta : 0.0, r.frozen, mf::Box{r.lo, r.hi, 0}};
+	if (r.lambda != 0.0) {
+		const double t = (p->alpha * 2) * r.lambda;
+		u.d = 1.0 - t;
+	}
+	if (seed && !(r.lo == -INFINITY && r.hi == INFINITY)) u.box.columns = r.columns < 0 ? p->K : r.columns;
+	return u;
 }
 
 // A side at rest that is about to run a seeded momentum sweep: X_prev = X_old by definition, literally -- one device copy
@@ -313,12 +260,12 @@ int side_columns(const mf_plan *p, int kind, int seed)
 // captures or launches anything, so no graph and no kernel sees a special first step.
 int leave_rest(mf_plan *p, int kind)
 {
-	if (!p->at_rest[kind] || p->beta[kind] == 0.0) return MF_OK;
+	if (!p->rule[kind].at_rest || p->rule[kind].beta == 0.0) return MF_OK;
 	const int rows = kind == 0 ? p->items : p->uc, ld = kind == 0 ? p->ldr : p->ldl;
 	double *const *buf = kind == 0 ? p->Rbuf : p->Lbuf;
 	if (rows > 0)
 		MF_HIP(hipMemcpyAsync(buf[p->cur ^ 1], buf[p->cur], (size_t) rows * ld * sizeof(double), hipMemcpyDeviceToDevice, p->stream));
-	p->at_rest[kind] = false;
+	p->rule[kind].at_rest = false;
 	return MF_OK;
 }
 
@@ -334,11 +281,12 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	a.seed = seed;
 	a.prio_len = sd.prio_len;
 	a.c2 = p->alpha * 2;
-	a.d = side_decay(p, kind);
-	a.frozen = p->frozen[kind];   // read at every launch, like the decay: a captured graph is built per call
-	a.beta = side_momentum(p, kind, seed);
-	a.box = mf::Box{p->box_lo[kind], p->box_hi[kind], side_columns(p, kind, seed)};
-	const bool momentum = a.beta != 0.0;
+	const SideUpdate u = side_update(p, kind, seed);
+	a.d = u.d;
+	a.frozen = u.frozen;
+	a.beta = u.beta;
+	a.box = u.box;
+	const bool momentum = u.beta != 0.0;
 	if (momentum) MF_TRY(leave_rest(p, kind));
 	a.ldx = x.ldx;
 	a.ldy = x.ldy;
@@ -359,7 +307,8 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	const bool extreme = sd.n_long > 0;
 	// the large chunk below kSweepFewRows rows.  Never beside the extreme-row path: with the extreme rows gone the
 	// occupancy-friendly chunk size is right again.
-	const SweepForm f = main_form(p, kind, !extreme && a.nrows < kSweepFewRows, a.d != 1.0 || a.frozen >= 0 || a.box.columns > 0, momentum, p->weighted);
+	const SweepForm f = main_form(p, kind, !extreme && a.nrows < kSweepFewRows,
+	                              mf_sched::launch_flavour(p->weighted, momentum, u.d != 1.0 || u.frozen >= 0 || u.box.columns > 0));
 	if (!f.fn) return MF_ERR_UNSUPPORTED;
 	a.nch = f.nch;
 	TimedLaunch t{};
@@ -390,9 +339,9 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 		o.K = p->K;
 		o.ldx = a.ldx;
 		o.seed = seed;
-		o.d = a.d;
-		o.frozen = a.frozen;
-		o.box = a.box;
+		o.d = u.d;
+		o.frozen = u.frozen;
+		o.box = u.box;
 		o.nslices = (int) mf_sched::slice_count(p->K, mf::kSliceCols);
 		o.row = sd.long_rows;
 		o.sbeg = sd.lr_sbeg;
@@ -414,9 +363,9 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 			s.nrows = sd.n_long;
 			s.K = p->K;
 			s.ldx = a.ldx;
-			s.frozen = a.frozen;
-			s.d = a.d;
-			s.beta = a.beta;
+			s.frozen = u.frozen;
+			s.d = u.d;
+			s.beta = u.beta;
 			s.row = sd.long_rows;
 			s.X_old = a.X_old;
 			s.X_new = a.X_new;
@@ -486,10 +435,11 @@ int launch_es_iteration(mf_plan *p)
 		ra.yrows[side] = x.yrows;
 		ra.ldx[side] = x.ldx;
 		ra.ldy[side] = x.ldy;
-		ra.d[side] = side_decay(p, side);
-		ra.frozen[side] = p->frozen[side];
-		ra.beta[side] = p->beta[side];
-		ra.box[side] = mf::Box{p->box_lo[side], p->box_hi[side], side_columns(p, side, 1)};
+		const SideUpdate u = side_update(p, side, 1);
+		ra.d[side] = u.d;
+		ra.frozen[side] = u.frozen;
+		ra.beta[side] = u.beta;
+		ra.box[side] = u.box;
 	}
 	const bool momentum = ra.beta[0] != 0.0 || ra.beta[1] != 0.0;
 	if (momentum) {
@@ -506,7 +456,7 @@ int launch_es_iteration(mf_plan *p)
 		MF_HIP(hipEventRecord(t0.t0, p->stream));
 	}
 	void *eargs[] = {&a};
-	MF_HIP(hipLaunchKernel((const void *) (p->weighted ? p->sweep.errs_w : p->sweep.errs), dim3(p->es_nseg), dim3(mf::kWave), eargs, p->es_lds_errors,
+	MF_HIP(hipLaunchKernel((const void *) p->sweep.errs[p->weighted], dim3(p->es_nseg), dim3(mf::kWave), eargs, p->es_lds_errors,
 	                       p->stream));
 	if (p->timing) MF_HIP(hipEventRecord(t0.t1, p->stream));
 	{

@@ -45,7 +45,7 @@ int launch_loss(mf_plan *p, const int *ptr, const int *idx, const double *val, c
 		const int few = a.nrows < kSweepFewRows ? 1 : 0;
 		a.nch = p->loss_nch[few];
 		void *args[] = {&a};
-		MF_HIP(hipLaunchKernel((const void *) (wgt ? p->loss_fn_w : p->loss_fn), dim3(std::min(a.nrows, 1 << 20)), dim3(mf::kWave), args, p->loss_lds[few],
+		MF_HIP(hipLaunchKernel((const void *) p->loss_fn[wgt != nullptr], dim3(std::min(a.nrows, 1 << 20)), dim3(mf::kWave), args, p->loss_lds[few],
 		                       p->stream));
 		hipLaunchKernelGGL(mf::loss_block_kernel, dim3(nblocks), dim3(mf::kWave), 0, p->stream, p->row_sse, p->u0, p->uc, nblocks,
 		                   p->loss_blocks);

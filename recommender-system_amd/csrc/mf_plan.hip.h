@@ -1,6 +1,7 @@
 // mf_plan.hip.h -- kernel variant tables, the buffers and operands of a top-N pass and the resident plan (struct mf_plan).
 // The plan owns its device memory through dev_buf members (mf_device.hip.h): deleting the plan frees it.
 #pragma once
+#include "mf_schedule.h"
 
 namespace {
 
@@ -23,53 +24,75 @@ inline hipError_t raise_lds_limit(const void *fn, size_t bytes)
 	return e;
 }
 
-// One K's kernels.  Filled by name: a form a K does not have stays null.
+using mf_sched::Form, mf_sched::kPlain, mf_sched::kPipelined, mf_sched::kPair, mf_sched::kDb, mf_sched::kCoop, mf_sched::kForms;
+using mf_sched::Flavour, mf_sched::kAccumulate, mf_sched::kDecay, mf_sched::kMomentum, mf_sched::kDecayW, mf_sched::kMomentumW, mf_sched::kFlavours;
+
+// One K's kernels: the grid of the main launch's instances, form by flavour (mf_schedule.h), and the kernels beside it.
+// A cell a K does not have stays null and launch_sweep refuses it.
 struct SweepVariant {
-	SweepFn fn = nullptr;
+	// kPlain: the single-wave form (the register-staged sweep_kernel, or the LDS-DMA sweep_dma_kernel); kPipelined: the
+	// LDS-DMA form with the LDS reads of phases A / B kept in flight (compile-time K); kPair: the wave-pair form (loader +
+	// compute) for launches that end on long rows (64 <= K <= 128, compile-time K); kDb: the intra-wave double-buffered form
+	// for launches of few rows (all DMA variants); kCoop: the row-cooperative form for tiny sweeps (compile-time-K DMA
+	// variants).  The weighted flavours are what a plan created with per-entry weights runs: kDecayW also at lambda = 0,
+	// beta = 0, where d = 1.0.
+	SweepFn fn[kForms][kFlavours] = {};
 	int kt = 0;         // compile-time K, 0 = runtime K
 	int kpmax = 0;      // 64-column groups held in registers (register-staged form) / DMA passes per row (run-time-K DMA form)
 	int dma = 0;        // 1: LDS-DMA form
 	int row_bytes = 0;  // LDS tile row stride in bytes (DMA form)
 	int xs_bytes = 0;   // LDS bytes in front of the tile (DMA form)
-	SweepFn coop = nullptr;   // row-cooperative form for tiny sweeps (compile-time-K DMA variants only)
-	SweepFn prod = nullptr;   // products form for segments of extreme rows (all DMA variants)
-	SweepFn errs = nullptr;   // errors form: e_n per entry of a segment (all DMA variants; mf_stream.hip.h)
-	SweepFn db = nullptr;     // intra-wave double-buffered form for launches of few rows (all DMA variants)
-	SweepFn pf = nullptr;     // accumulate form with the LDS reads of phases A / B kept in flight (compile-time-K DMA variants)
-	SweepFn fn_decay = nullptr, pf_decay = nullptr;   // fn and pf with the seed times the decay factor and the frozen column kept (DMA variants; the other forms do both always)
-	SweepFn pair = nullptr;   // wave-pair form (loader + compute) for launches that end on long rows (64 <= K <= 128, compile-time K)
-	LossFn loss = nullptr;    // row sums of mf_plan_loss in the same geometry (all DMA variants; the others use loss_reg_kernel)
-	// the momentum instances of the forms above (a seeded sweep of a side with beta != 0): each where its plain twin is
-	SweepFn fn_mom = nullptr, pf_mom = nullptr, coop_mom = nullptr, db_mom = nullptr, pair_mom = nullptr;
-	// the weighted twins (a plan created with per-entry weights): of the decay instances -- also what lambda = 0, beta = 0
-	// runs, at d = 1.0 -- and of the momentum instances, per form; weighted products and errors; the weighted row sums of
-	// the training loss
-	SweepFn fn_wd = nullptr, pf_wd = nullptr, coop_wd = nullptr, db_wd = nullptr, pair_wd = nullptr;
-	SweepFn fn_wm = nullptr, pf_wm = nullptr, coop_wm = nullptr, db_wm = nullptr, pair_wm = nullptr;
-	SweepFn prod_w = nullptr, errs_w = nullptr;
-	LossFn loss_w = nullptr;
+	// beside the grid, each [weighted] (all DMA variants): the products form for segments of extreme rows; the errors form,
+	// e_n per entry of a segment (mf_stream.hip.h); the row sums of mf_plan_loss in the same geometry (the others use
+	// loss_reg_kernel)
+	SweepFn prod[2] = {}, errs[2] = {};
+	LossFn loss[2] = {};
+	constexpr bool has(Form form) const { return fn[form][kAccumulate] != nullptr; }
 };
+
+// A form whose one instance always multiplies the seed by d, keeps the frozen column and clamps (the register-staged, db,
+// pair and coop forms): the accumulate and the decay cell are that instance -- x * 1.0 is x bit for bit.
+constexpr void seeded_row(SweepFn *row, SweepFn plain, SweepFn mom, SweepFn wd, SweepFn wm)
+{
+	row[kAccumulate] = row[kDecay] = plain;
+	row[kMomentum] = mom;
+	row[kDecayW] = wd;
+	row[kMomentumW] = wm;
+}
+
+// The LDS-DMA single-wave form multiplies the seed, keeps a frozen column and clamps only in the instances behind its
+// accumulate one: one per flavour, at prefetch depth PF (0: plain, 8: pipelined).
+template <int KT, int NP, int PF>
+constexpr void dma_row(SweepFn *row)
+{
+	row[kDecay] = mf::sweep_dma_kernel<KT, NP, mf::kSweepDecay, PF>;
+	row[kMomentum] = mf::sweep_dma_kernel<KT, NP, mf::kSweepMomentum, PF>;
+	row[kDecayW] = mf::sweep_dma_kernel<KT, NP, mf::kSweepDecayW, PF>;
+	row[kMomentumW] = mf::sweep_dma_kernel<KT, NP, mf::kSweepMomentumW, PF>;
+}
+
+// what all LDS-DMA variants have: the products, errors and loss kernels and the double-buffered form
+template <int KT, int NP>
+constexpr void dma_common(SweepVariant &v)
+{
+	v.dma = 1;
+	v.fn[kPlain][kAccumulate] = mf::sweep_dma_kernel<KT, NP>;
+	seeded_row(v.fn[kDb], mf::sweep_db_kernel<KT, NP>, mf::sweep_db_kernel<KT, NP, true>, mf::sweep_db_kernel<KT, NP, false, true>,
+	           mf::sweep_db_kernel<KT, NP, true, true>);
+	v.prod[0] = mf::sweep_dma_kernel<KT, NP, mf::kSweepProducts>, v.prod[1] = mf::sweep_dma_kernel<KT, NP, mf::kSweepProductsW>;
+	v.errs[0] = mf::sweep_dma_kernel<KT, NP, mf::kSweepErrors>, v.errs[1] = mf::sweep_dma_kernel<KT, NP, mf::kSweepErrorsW>;
+	v.loss[0] = mf::loss_dma_kernel<KT, NP>, v.loss[1] = mf::loss_dma_w_kernel<KT, NP>;
+}
 
 template <int KT, int KP>
 constexpr SweepVariant variant()
 {
 	SweepVariant v;
-	v.fn = mf::sweep_kernel<KT, KP>;
-	v.fn_mom = mf::sweep_kernel<KT, KP, true>;
-	v.fn_wd = mf::sweep_kernel<KT, KP, false, true>;
-	v.fn_wm = mf::sweep_kernel<KT, KP, true, true>;
+	seeded_row(v.fn[kPlain], mf::sweep_kernel<KT, KP>, mf::sweep_kernel<KT, KP, true>, mf::sweep_kernel<KT, KP, false, true>,
+	           mf::sweep_kernel<KT, KP, true, true>);
 	v.kt = KT;
 	v.kpmax = KP;
 	return v;
-}
-
-template <int KT, bool MOM = false, bool WGT = false>
-constexpr SweepFn pair_fn()
-{
-	if constexpr (mf::DmaGeom<KT>::kOnePassWide)
-		return mf::sweep_pair_kernel<KT, 1, MOM, WGT>;
-	else
-		return nullptr;
 }
 
 template <int KT>
@@ -77,39 +100,20 @@ constexpr SweepVariant dma_variant()
 {
 	constexpr int NP = mf::DmaGeom<KT>::kPasses;
 	SweepVariant v;
-	v.fn = mf::sweep_dma_kernel<KT, NP>;
+	dma_common<KT, NP>(v);
 	v.kt = KT;
-	v.dma = 1;
 	v.row_bytes = mf::DmaGeom<KT>::kStride;
 	v.xs_bytes = mf::DmaGeom<KT>::kXsBytes;
-	v.coop = mf::sweep_coop_kernel<KT>;
-	v.prod = mf::sweep_dma_kernel<KT, NP, mf::kSweepProducts>;
-	v.errs = mf::sweep_dma_kernel<KT, NP, mf::kSweepErrors>;
-	v.db = mf::sweep_db_kernel<KT, NP>;
-	v.pf = mf::sweep_dma_kernel<KT, NP, mf::kSweepAccumulate, 8>;
-	// two-pass rows (K = 256) take the pipelined form at every size (single_wave_pipelined): no plain decay instance
-	if constexpr (KT <= 128) v.fn_decay = mf::sweep_dma_kernel<KT, NP, mf::kSweepDecay>;
-	v.pf_decay = mf::sweep_dma_kernel<KT, NP, mf::kSweepDecay, 8>;
-	v.pair = pair_fn<KT>();
-	if constexpr (KT <= 128) v.fn_mom = mf::sweep_dma_kernel<KT, NP, mf::kSweepMomentum>;
-	v.pf_mom = mf::sweep_dma_kernel<KT, NP, mf::kSweepMomentum, 8>;
-	v.coop_mom = mf::sweep_coop_kernel<KT, true>;
-	v.db_mom = mf::sweep_db_kernel<KT, NP, true>;
-	v.pair_mom = pair_fn<KT, true>();
-	v.loss = mf::loss_dma_kernel<KT, NP>;
-	if constexpr (KT <= 128) v.fn_wd = mf::sweep_dma_kernel<KT, NP, mf::kSweepDecayW>;
-	v.pf_wd = mf::sweep_dma_kernel<KT, NP, mf::kSweepDecayW, 8>;
-	if constexpr (KT <= 128) v.fn_wm = mf::sweep_dma_kernel<KT, NP, mf::kSweepMomentumW>;
-	v.pf_wm = mf::sweep_dma_kernel<KT, NP, mf::kSweepMomentumW, 8>;
-	v.coop_wd = mf::sweep_coop_kernel<KT, false, true>;
-	v.coop_wm = mf::sweep_coop_kernel<KT, true, true>;
-	v.db_wd = mf::sweep_db_kernel<KT, NP, false, true>;
-	v.db_wm = mf::sweep_db_kernel<KT, NP, true, true>;
-	v.pair_wd = pair_fn<KT, false, true>();
-	v.pair_wm = pair_fn<KT, true, true>();
-	v.prod_w = mf::sweep_dma_kernel<KT, NP, mf::kSweepProductsW>;
-	v.errs_w = mf::sweep_dma_kernel<KT, NP, mf::kSweepErrorsW>;
-	v.loss_w = mf::loss_dma_w_kernel<KT, NP>;
+	// two-pass rows (K = 256) take the pipelined form at every size (single_wave_pipelined): no plain instance but the
+	// accumulate one
+	if constexpr (KT <= 128) dma_row<KT, NP, 0>(v.fn[kPlain]);
+	v.fn[kPipelined][kAccumulate] = mf::sweep_dma_kernel<KT, NP, mf::kSweepAccumulate, 8>;
+	dma_row<KT, NP, 8>(v.fn[kPipelined]);
+	if constexpr (mf::DmaGeom<KT>::kOnePassWide)
+		seeded_row(v.fn[kPair], mf::sweep_pair_kernel<KT, 1>, mf::sweep_pair_kernel<KT, 1, true>, mf::sweep_pair_kernel<KT, 1, false, true>,
+		           mf::sweep_pair_kernel<KT, 1, true, true>);
+	seeded_row(v.fn[kCoop], mf::sweep_coop_kernel<KT>, mf::sweep_coop_kernel<KT, true>, mf::sweep_coop_kernel<KT, false, true>,
+	           mf::sweep_coop_kernel<KT, true, true>);
 	return v;
 }
 
@@ -118,32 +122,20 @@ template <int NPASS>
 constexpr SweepVariant dma_generic_variant()
 {
 	SweepVariant v;
-	v.fn = mf::sweep_dma_kernel<0, NPASS>;
+	dma_common<0, NPASS>(v);
 	v.kpmax = NPASS;
-	v.dma = 1;
-	v.prod = mf::sweep_dma_kernel<0, NPASS, mf::kSweepProducts>;
-	v.errs = mf::sweep_dma_kernel<0, NPASS, mf::kSweepErrors>;
-	v.db = mf::sweep_db_kernel<0, NPASS>;
-	v.fn_decay = mf::sweep_dma_kernel<0, NPASS, mf::kSweepDecay>;
-	v.fn_mom = mf::sweep_dma_kernel<0, NPASS, mf::kSweepMomentum>;
-	v.db_mom = mf::sweep_db_kernel<0, NPASS, true>;
-	v.loss = mf::loss_dma_kernel<0, NPASS>;
-	v.fn_wd = mf::sweep_dma_kernel<0, NPASS, mf::kSweepDecayW>;
-	v.fn_wm = mf::sweep_dma_kernel<0, NPASS, mf::kSweepMomentumW>;
-	v.db_wd = mf::sweep_db_kernel<0, NPASS, false, true>;
-	v.db_wm = mf::sweep_db_kernel<0, NPASS, true, true>;
-	v.prod_w = mf::sweep_dma_kernel<0, NPASS, mf::kSweepProductsW>;
-	v.errs_w = mf::sweep_dma_kernel<0, NPASS, mf::kSweepErrorsW>;
-	v.loss_w = mf::loss_dma_w_kernel<0, NPASS>;
+	dma_row<0, NPASS, 0>(v.fn[kPlain]);
 	return v;
 }
 
-// One launchable form of a sweep: its kernel, entries per chunk, LDS request and workgroup size.
-struct SweepForm {
-	SweepFn fn = nullptr;
+// The geometry of a launch: entries per chunk, LDS request and workgroup size; and a launchable form, a geometry with its kernel.
+struct LaunchGeometry {
 	int nch = 0;
 	size_t lds = 0;
 	int block = mf::kWave;
+};
+struct SweepForm : LaunchGeometry {
+	SweepFn fn = nullptr;
 };
 
 // K-specialised instances for the K of the bundled samples and of the BASELINE configs, then generic ones.
@@ -220,6 +212,20 @@ struct topn_operands {
 	topn_buffers *out = nullptr;
 };
 
+// How one side's rows are updated: what the setters of the C API write and the getters read.
+struct SideRule {
+	double lambda = 0.0;   // L2 regularisation, mf_plan_set_regularization
+	double beta = 0.0;     // heavy-ball momentum, mf_plan_set_momentum
+	int frozen = -1;       // frozen column or -1, mf_plan_set_frozen_columns
+	// box constraint, mf_plan_set_bounds: columns k < columns (-1: all K) of a finished row are projected onto [lo, hi]
+	double lo = -INFINITY, hi = INFINITY;
+	int columns = -1;
+	// a side at rest has no history: X_prev = X_old by definition.  Set by mf_plan_upload_factors and by a change of the
+	// side's beta from 0; cleared by its first seeded momentum sweep (leave_rest copies current -> next) and by
+	// mf_plan_upload_previous
+	bool at_rest = true;
+};
+
 }  // namespace
 
 struct mf_plan {
@@ -229,17 +235,7 @@ struct mf_plan {
 	int u0 = 0, uc = 0;
 	int64_t nnz = 0;
 	double alpha = 0.0;
-	double lambda[2] = {0.0, 0.0};   // L2 regularisation per side (0 = items, 1 = users), mf_plan_set_regularization
-	int frozen[2] = {-1, -1};        // frozen column per side (0 = items, 1 = users) or -1, mf_plan_set_frozen_columns
-	double beta[2] = {0.0, 0.0};     // heavy-ball momentum per side (0 = items, 1 = users), mf_plan_set_momentum
-	// box constraint per side (0 = items, 1 = users), mf_plan_set_bounds: columns k < box_columns (-1: all K) of a finished
-	// row are projected onto [box_lo, box_hi]
-	double box_lo[2] = {-INFINITY, -INFINITY}, box_hi[2] = {INFINITY, INFINITY};
-	int box_columns[2] = {-1, -1};
-	// a side at rest has no history: X_prev = X_old by definition.  Set by mf_plan_upload_factors and by a change of the
-	// side's beta from 0; cleared by its first seeded momentum sweep (leave_rest copies current -> next) and by
-	// mf_plan_upload_previous
-	bool at_rest[2] = {true, true};
+	SideRule rule[2];   // the update rule per side (0 = items, 1 = users); side_update (mf_launch.hip.h) reads it at every launch
 	int flags = 0;
 
 	hipStream_t own_stream = nullptr;
@@ -298,8 +294,7 @@ struct mf_plan {
 
 	// loss (mf_plan_loss, mf_loss.hip.h): row sums, block sums and total, allocated on first use; the held-out set as a
 	// second CSR over the shard's users (entries of a user in the caller's order)
-	LossFn loss_fn = nullptr;
-	LossFn loss_fn_w = nullptr;      // its weighted twin (the training loss of a weighted plan)
+	LossFn loss_fn[2] = {nullptr, nullptr};   // [1]: the weighted twin (the training loss of a weighted plan)
 	int loss_nch[2] = {0, 0};        // chunk size of the row-sum launch: [0] ordinary, [1] fewer rows than fill the chip
 	size_t loss_lds[2] = {0, 0};     // its LDS request (the L row + ONE tile)
 	dev_buf<double> row_sse, loss_blocks, loss_total;
@@ -324,13 +319,12 @@ struct mf_plan {
 
 	SweepVariant sweep{};
 	int stride = 0;             // register-staged form: LDS row stride in doubles
-	// the forms of a sweep's main launch (launch_sweep: main_form); `single` and `few` leave fn to the side (plain or
-	// pipelined accumulate form, single_wave_pipelined)
-	SweepForm single;           // single-wave form at the chunk size of choose_sweep
-	SweepForm few;              // ... at the chunk size for a sweep of too few rows to fill the chip
-	SweepForm db;               // double-buffered form (two tiles)
-	SweepForm pair;             // wave-pair form (two tiles, two waves per row)
-	SweepForm coop;             // tiny sweeps (a few us of data): ONE cooperative launch over all rows; a fork/join costs more than it saves
+	// the geometries of a sweep's main launch (launch_sweep: main_form adds the instance from the grid)
+	LaunchGeometry single;      // single-wave form at the chunk size of choose_sweep
+	LaunchGeometry few;         // ... at the chunk size for a sweep of too few rows to fill the chip
+	LaunchGeometry db;          // double-buffered form (two tiles)
+	LaunchGeometry pair;        // wave-pair form (two tiles, two waves per row)
+	LaunchGeometry coop;           // tiny sweeps (a few us of data): ONE cooperative launch over all rows; a fork/join costs more than it saves
 	SweepForm prod;             // products launch over the segments of the extreme rows
 	SweepSide side[2];          // 0 = items / CSC, 1 = users / CSR
 	// extreme rows: 64-entry segments -> scaled rows in `scratch` -> ordered sum

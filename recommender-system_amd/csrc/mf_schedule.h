@@ -1,9 +1,11 @@
 // mf_schedule.h -- how the two sweeps of a plan run, decided on the host from the row lengths alone: which rows count as
 // extreme, whether a tiny sweep is ONE cooperative launch, the segment tables of the extreme-row path, the wave
 // priority, the form of the main launch and the dispatch order, and the tables of the errors +
-// streams iteration (5.6).  Pure functions of (row pointers, K, switches, limits): no HIP type, no kernel header, so
-// they compile with any C++17 compiler and tests/test_schedule.py pins them on a CPU.  mf_build.hip.h fills the inputs,
-// calls sweep_schedule / es_errors / es_workgroups, and allocates and uploads what they return.
+// streams iteration (5.6); and the choice made at every launch, the form, flavour and geometry of a main launch (5.8k).
+// Pure functions of (row pointers, K, switches, limits): no HIP type, no kernel header, so they compile with any C++17
+// compiler and tests/test_schedule.py and tests/test_launch_choice.py pin them on a CPU.  mf_build.hip.h fills the inputs,
+// calls sweep_schedule / es_errors / es_workgroups, and allocates and uploads what they return; mf_launch.hip.h makes the
+// launch-time choice.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -305,6 +307,52 @@ inline Sweeps sweep_schedule(const Problem &pb, const Caps &caps, const Switches
 		out.side_low = a.pair || b.pair;
 	}
 	return out;
+}
+
+// ---- the choice of a sweep's main launch, made at every launch (launch_sweep, mf_launch.hip.h): a kernel instance is a
+// cell of the variant's grid fn[form][flavour] (mf_plan.hip.h), launched in the geometry of its form
+enum Form { kPlain, kPipelined, kPair, kDb, kCoop, kForms };
+// What an instance does at the seed and the finished row: kAccumulate seeds with x as it is; kDecay multiplies the seed by d,
+// keeps a frozen column and clamps; kMomentum adds the heavy-ball term; the W twins read per-entry weights, and come last.
+enum Flavour { kAccumulate, kDecay, kMomentum, kDecayW, kMomentumW, kFlavours };
+constexpr int kUnweightedFlavours = kDecayW;
+// Where a launch takes its entries per chunk, LDS request and workgroup size from.
+enum Geometry { kGeomSingle, kGeomFew, kGeomPair, kGeomDb, kGeomCoop, kGeomCoopSingleNch };
+
+// Accumulate form of a single-wave launch: true for the form with the pipelined phases, false for the plain one.  Up to
+// 262144 rows: the form whose phases keep their LDS reads in flight and whose gather issue is lean -- what a wave walking a
+// long row alone is bound by (cfg3 uniform 0.224 -> 0.201 ms, power-law 0.367 -> 0.350, a lone 5993-entry row 1.02 -> 0.78
+// ms).  Larger launches of one-pass rows (K <= 128) are never bound by one wave and keep round 2's form (cfg4 user sweep,
+// 1e6 rows: 11.45 vs 11.60 ms).  Two-pass rows (K = 256) take it at every size: their phase A is a 256-deep chain per chunk
+// that the six resident workgroups of a CU do not hide, and keeping its LDS reads in flight shortens it (cfg5: 346.6 ->
+// 327.9 ms, 0.745 -> 0.787).
+inline bool single_wave_pipelined(bool has_pipelined, int K, int n_short, int nrows)
+{
+	constexpr int kPfRows = 262144;
+	return has_pipelined && (K > 128 || (n_short <= kPfRows && nrows <= kPfRows));
+}
+
+// The form: cooperative, double-buffered or wave-pair where the schedule chose one, else single-wave, pipelined or plain.
+inline Form launch_form(bool coop_all, bool use_db, bool use_pair, bool pipelined)
+{
+	return coop_all ? kCoop : use_db ? kDb : use_pair ? kPair : pipelined ? kPipelined : kPlain;
+}
+
+// The flavour.  `momentum`: a seeded sweep of a side with beta != 0.  `decay`: d != 1.0, or the side has a frozen column or
+// a box constraint (x * 1.0 is x: the rest runs the accumulate instance).  A weighted plan runs kDecayW at d = 1.0 too.
+inline Flavour launch_flavour(bool weighted, bool momentum, bool decay)
+{
+	if (weighted) return momentum ? kMomentumW : kDecayW;
+	return momentum ? kMomentum : decay ? kDecay : kAccumulate;
+}
+
+// The geometry: each form its own; the single-wave forms at the large chunk when `few_rows`.  A cooperative launch that is
+// not one of few rows runs at the single-wave chunk size with the cooperative LDS request, as it always has.  Known and left
+// for a change of its own: at K = 30 and K = 50 that request is sized for fewer rows (14 and 8) than the chunk's 16.
+inline Geometry launch_geometry(Form form, bool few_rows)
+{
+	if (form == kCoop) return few_rows ? kGeomCoop : kGeomCoopSingleNch;
+	return form == kDb ? kGeomDb : form == kPair ? kGeomPair : few_rows ? kGeomFew : kGeomSingle;
 }
 
 // ---- errors + streams iteration (mf_stream.hip.h, mf_resident.hip.h)

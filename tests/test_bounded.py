@@ -408,6 +408,7 @@ def test_project_on_the_hand_made_matrix(device, switches, lo, hi):
         cur_r = next(t for t in rb if t.data_ptr() == plan.items_current_ptr())
         nxt_r = next(t for t in rb if t.data_ptr() == plan.items_next_ptr())
         nxt_r[:, :K] = torch.from_numpy(Rh)
+        torch.cuda.synchronize()   # torch's stream wrote the buffer; the plan's own (non-blocking) stream projects it
         plan.project("users")
         plan.project("items", "next")
         plan.synchronize()
@@ -671,6 +672,7 @@ def test_two_user_shards_on_one_gpu(device, switches):
         for (plan, rb, begin, count, seeded, m), Lm in zip(shards, model_L):
             nxt = next(t for t in rb if t.data_ptr() == plan.items_next_ptr())
             nxt[:, :K] = torch.from_numpy(total).to(dev)
+            torch.cuda.synchronize()   # torch's stream wrote the sum; the plan's own (non-blocking) stream projects it
             plan.set_bounds("items", *BOX)
             plan.project("items", "next")
             plan.flip()
