@@ -211,7 +211,30 @@ int mf_backend_row_pitch(int features);
 int mf_plan_row_pitch(mf_plan *plan, int32_t *users_pitch, int32_t *items_pitch);
 void mf_plan_destroy(mf_plan *plan);
 
-/* hipStream_t as void*; NULL = the plan's own stream.  All plan work is enqueued on it. */
+/* The plan's stream: hipStream_t as void*.  Every launch, copy and memset of every plan entry point is ordered on it, so
+ * a caller that enqueues its own work on the same stream (a collective on mf_plan_items_next(), a copy into the current
+ * buffers) needs no host synchronisation between that work and the plan's (tests/test_stream_order.py holds every line
+ * below on a stream that is busy when the library is called).
+ *   - Entry points that only ENQUEUE and return: mf_plan_iterate (and mf_plan_iterate_monitored between its evaluation
+ *     points), mf_plan_sweep_items, mf_plan_sweep_users, mf_plan_sweep_users_seeded and mf_plan_project.  What they
+ *     write may be read by work enqueued on the stream after the call returns, or by the host after
+ *     mf_plan_synchronize.  A HIP graph that mf_plan_iterate builds is captured on and replayed into this stream.
+ *   - Host only, no device work: mf_plan_flip, the setters and getters of the update rule, the pointer and pitch
+ *     queries, mf_plan_describe.  A setter holds from the next launch that is enqueued.
+ *   - COMPLETE ON RETURN (they enqueue behind whatever the stream holds and wait for it): everything that returns data
+ *     to the host -- mf_plan_download_*, mf_plan_recommend*, mf_plan_rank_heldout, mf_plan_similar_items, mf_plan_loss,
+ *     mf_plan_penalty, mf_plan_weight_total, mf_plan_bounds_active, mf_plan_predict, mf_plan_timing_read, an evaluation
+ *     point of mf_plan_iterate_monitored --, mf_plan_upload_factors, mf_plan_upload_previous, mf_plan_set_heldout,
+ *     mf_plan_synchronize, mf_plan_create*, and mf_plan_destroy, which waits for the stream before it frees anything:
+ *     caller-owned buffers hold the results of all enqueued work when it returns.
+ *   - The side stream of the extreme rows is the plan's own affair: it is forked from and joined to the plan's stream
+ *     inside every call (mf_plan_iterate joins the item sweep's ordered sums behind the user sweep, in front of the
+ *     flip), so nothing is left running beside the plan's stream when a call returns.
+ *   - mf_plan_set_stream waits for the stream it leaves, then switches: work enqueued before the call is complete, work
+ *     after it is ordered on the new stream only.
+ *   - NULL selects the plan's own stream, created non-blocking.  The handle of the legacy default stream is NULL too, so
+ *     that stream cannot be chosen, and the plan's own stream is not ordered against it: a caller whose other work runs
+ *     on the default stream synchronises on the host or passes a stream of its own. */
 int mf_plan_set_stream(mf_plan *plan, void *hip_stream);
 
 /* host -> HBM: this shard's rows of L (user_count x K) and the whole of R (items x K). */
