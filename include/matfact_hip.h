@@ -54,7 +54,11 @@ extern "C" {
                                           per-entry confidence weights (mf_plan_create_weighted, mf_plan_weight_total,
                                           mf_backend_run_weighted);
                                           box-constrained factors (mf_bounds, mf_plan_set_bounds, mf_plan_get_bounds,
-                                          mf_plan_project, mf_plan_bounds_active, mf_backend_run_bounded) */
+                                          mf_plan_project, mf_plan_bounds_active, mf_backend_run_bounded);
+                                          adaptive step sizes (mf_adaptive, mf_plan_set_adaptive, mf_plan_get_adaptive,
+                                          mf_plan_reset_adaptive, mf_plan_adaptive_finish,
+                                          mf_plan_download_adaptive_state, mf_plan_upload_adaptive_state,
+                                          mf_backend_run_adaptive) */
 
 /* == non_zero_entry, datatypes.h:10-15: the (user, item, rating) triple, 16 bytes, array-of-structs */
 typedef struct mf_entry {
@@ -580,6 +584,71 @@ int mf_plan_bounds_active(mf_plan *plan, int side, int64_t *at_lo, int64_t *at_h
 int mf_backend_run_bounded(const mf_problem *p, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
                            double lambda_items, double beta_users, double beta_items, const mf_bounds *bounds_users,
                            const mf_bounds *bounds_items, int device);
+
+/* ---- Adaptive step sizes: AdaGrad, RMSProp and Adam, a per-element step in place of the one global alpha.  An extension
+ * (the reference has none), so the definition is this library's.  Each side (0 = items, 1 = users, as mf_plan_set_bounds
+ * counts them) has its own record; the default kind is MF_OPT_NONE.  eta is finite and > 0; eps is finite and > 0, so a
+ * zero accumulator gives 0 / eps = 0 and never a NaN; beta1 is in [0, 1) and read by ADAM only; beta2 is in [0, 1) -- for
+ * RMSPROP it is its rho, ADAGRAD ignores it.
+ *
+ * A SEEDED sweep of a side X with kind != NONE is defined as follows.  Every operation is rounded once and nothing is
+ * fused; sqrt and / are correctly rounded (IEEE 754).
+ *   1. g[r][k] = the bits an UNSEEDED sweep of that side writes: 0.0 + every e_n * Y in the side's entry order (e_n the
+ *      weighted one on a weighted plan), no decay, no box, 0.0 in the frozen column.
+ *   2. Per side and per step two scalars, 1.0 at rest: with ADAM  p1 = p1 * beta1,  p2 = p2 * beta2  -- sequential
+ *      products, one per seeded adaptive sweep of the side; the other kinds leave them at 1.0 --, then  c1 = 1.0 - p1,
+ *      c2 = 1.0 - p2.  `steps` counts the seeded adaptive sweeps of the side, whatever the kind.
+ *   3. Per element outside the frozen column  q = g * g  and, with ob1 = 1.0 - beta1 and ob2 = 1.0 - beta2 formed once,
+ *        ADAGRAD:  v' = v + q;                                                     mh = g;        vh = v'
+ *        RMSPROP:  v' = (beta2 * v) + (ob2 * q);                                   mh = g;        vh = v'
+ *        ADAM:     m' = (beta1 * m) + (ob1 * g);  v' = (beta2 * v) + (ob2 * q);    mh = m' / c1;  vh = v' / c2
+ *      then for every kind  s = sqrt(vh);  den = s + eps;  u = mh / den;  step = eta * u;  x' = (x * d) + step,  d the
+ *      side's decay exactly as a seeded sweep forms it (1.0 - (alpha * 2) * lambda; 1.0 at lambda = 0).  Then the box
+ *      projection above on the bounded columns, then the frozen select: the frozen column keeps X_old's bits, and its m and
+ *      v keep theirs.
+ *   4. g carries the plain rule's 2 * alpha (e_n = (alpha * 2) * (a_n - dot_n)): the adaptive step is invariant to that
+ *      scale except against eps -- v holds (2 alpha)^2 times the squared gradient, so eps is compared with 2 alpha times
+ *      the gradient's root mean square.  alpha still sets d.
+ * e_n, dot_n, the loss, the penalty and every L R^T pass see nothing new.  Rows without entries take the formula with
+ * g = 0; the padding of a row is never touched.  An UNSEEDED sweep of an adaptive side is the unseeded sweep, untouched.
+ *
+ * State: m (ADAM only) and v per side, rows x K doubles, zero at rest, with steps, p1 and p2.  The state returns to rest on
+ * mf_plan_upload_factors, on a change of the side's kind and on mf_plan_reset_adaptive; a change of eta, beta1, beta2 or
+ * eps alone keeps it.  Momentum: a side cannot have beta != 0 and kind != NONE (X_new carries g, so X_prev is gone) --
+ * whichever of mf_plan_set_momentum / mf_plan_set_adaptive comes second returns MF_ERR_UNSUPPORTED with nothing changed.
+ * While either side is adaptive mf_plan_iterate runs the two sweeps (not the errors + streams iteration, not the toy
+ * loop); with MF_OPT_NONE on both sides the plan launches the kernels and produces the bits it does without this section.
+ *
+ * mf_plan_set_adaptive: NULL or kind NONE turns the rule off.  An unknown side or kind, eta or eps not finite or not > 0, a
+ * beta the kind reads outside [0, 1) -> MF_ERR_ARGUMENT before any HIP call, with nothing changed.  mf_plan_get_adaptive is
+ * its inverse (a side without a rule reads kind NONE and zeros).
+ * mf_plan_adaptive_finish: treats the side's next-generation buffer as g and applies steps 2 - 3 to every row, on the
+ * plan's stream: what a sharded caller of the plan API calls on the summed side after its sum (the sweeps unseeded), as it
+ * calls mf_plan_project for a bounded one.  Without factors, or on a side of kind NONE, MF_ERR_STATE.
+ * mf_plan_download_adaptive_state / mf_plan_upload_adaptive_state: m and v as rows x K doubles (the side's rows: items, or
+ * the shard's users), steps, p1 and p2; any pointer may be NULL; a side at rest downloads zeros, 0 and 1.0, a side that is
+ * not ADAM zeros for m.  With them and the factors a run resumes bit for bit.  Both need factors (MF_ERR_STATE); a side of
+ * kind NONE is at rest and downloads as such, an upload to it is MF_ERR_STATE; an upload of a negative steps or of a p that
+ * is NaN -> MF_ERR_ARGUMENT.  An upload leaves what it is not given as it is.
+ * mf_plan_describe appends adaptive=<users>/<items> when either side has a rule: a side as adam(eta,b1,b2,eps),
+ * rmsprop(eta,rho,eps), adagrad(eta,eps) -- the numbers in %.17g -- or - for a side without. */
+enum { MF_OPT_NONE = 0, MF_OPT_ADAGRAD = 1, MF_OPT_RMSPROP = 2, MF_OPT_ADAM = 3 };
+typedef struct mf_adaptive {
+	int32_t kind;                   /* MF_OPT_NONE | MF_OPT_ADAGRAD | MF_OPT_RMSPROP | MF_OPT_ADAM */
+	double eta, beta1, beta2, eps;
+} mf_adaptive;
+int mf_plan_set_adaptive(mf_plan *plan, int side, const mf_adaptive *rule);
+int mf_plan_get_adaptive(mf_plan *plan, int side, mf_adaptive *rule);
+int mf_plan_reset_adaptive(mf_plan *plan, int side);
+int mf_plan_adaptive_finish(mf_plan *plan, int side);
+int mf_plan_download_adaptive_state(mf_plan *plan, int side, double *m, double *v, int64_t *steps, double *p1, double *p2);
+int mf_plan_upload_adaptive_state(mf_plan *plan, int side, const double *m, const double *v, const int64_t *steps, const double *p1,
+                                  const double *p2);
+/* level 1: mf_backend_run_bounded without the betas, plus one rule per side (NULL: the plain step).  A bad rule, record or
+ * lambda, or NULL L / R -> MF_ERR_ARGUMENT before any HIP call. */
+int mf_backend_run_adaptive(const mf_problem *p, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
+                            double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items,
+                            const mf_adaptive *adaptive_users, const mf_adaptive *adaptive_items, int device);
 
 /* ---- Ranks of the held-out entries: where each held-out item lands in its user's recommendation order, for the plan's
  * current factors.  An extension (the reference ranks nothing), so the definition is this library's.  For held-out entry

@@ -52,6 +52,8 @@ HIP_SYMBOLS = [
     "mf_backend_run_momentum",
     "mf_plan_create_weighted", "mf_plan_weight_total", "mf_backend_run_weighted",
     "mf_plan_set_bounds", "mf_plan_get_bounds", "mf_plan_project", "mf_plan_bounds_active", "mf_backend_run_bounded",
+    "mf_plan_set_adaptive", "mf_plan_get_adaptive", "mf_plan_reset_adaptive", "mf_plan_adaptive_finish",
+    "mf_plan_download_adaptive_state", "mf_plan_upload_adaptive_state", "mf_backend_run_adaptive",
 ]
 HOST_SYMBOLS = [
     "mf_host_parse_strerror", "mf_host_parse_file", "mf_host_parse_buffer", "mf_host_free_problem",
@@ -97,6 +99,16 @@ CANDIDATE_DTYPE = np.dtype([("score", np.float64), ("best", np.int32), ("first",
 
 class Bounds(C.Structure):  # mf_bounds
     _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("columns", C.c_int32)]
+
+
+class Adaptive(C.Structure):  # mf_adaptive
+    _fields_ = [("kind", C.c_int32), ("eta", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
+
+
+# MF_OPT_*: the kinds of an adaptive rule, by number and by name
+MF_OPT_NONE, MF_OPT_ADAGRAD, MF_OPT_RMSPROP, MF_OPT_ADAM = 0, 1, 2, 3
+OPTIMIZERS = {"none": 0, "adagrad": 1, "rmsprop": 2, "adam": 3, None: 0, 0: 0, 1: 1, 2: 2, 3: 3}
+OPTIMIZER_NAMES = ("none", "adagrad", "rmsprop", "adam")
 
 
 class Loss(C.Structure):  # mf_loss
@@ -228,6 +240,14 @@ def hip():
         lib.mf_plan_bounds_active.argtypes = [P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         lib.mf_backend_run_bounded.argtypes = [C.POINTER(Problem), P, P, P, P, C.c_double, C.c_double, C.c_double, C.c_double,
                                                C.POINTER(Bounds), C.POINTER(Bounds), C.c_int]
+        lib.mf_plan_set_adaptive.argtypes = [P, C.c_int, C.POINTER(Adaptive)]
+        lib.mf_plan_get_adaptive.argtypes = [P, C.c_int, C.POINTER(Adaptive)]
+        lib.mf_plan_reset_adaptive.argtypes = [P, C.c_int]
+        lib.mf_plan_adaptive_finish.argtypes = [P, C.c_int]
+        lib.mf_plan_download_adaptive_state.argtypes = [P, C.c_int, P, P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        lib.mf_plan_upload_adaptive_state.argtypes = [P, C.c_int, P, P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        lib.mf_backend_run_adaptive.argtypes = [C.POINTER(Problem), P, P, P, P, C.c_double, C.c_double, C.POINTER(Bounds), C.POINTER(Bounds),
+                                                C.POINTER(Adaptive), C.POINTER(Adaptive), C.c_int]
         _hip = lib
     return _hip
 
@@ -528,6 +548,40 @@ def backend_run_bounded(inst, L, R, bounds_users=None, bounds_items=None, weight
 
 
 run_bounded = backend_run_bounded
+
+
+def _adaptive_record(a):
+    """mf_adaptive from None (the plain step), an Adaptive, or (kind, eta[, beta1, beta2[, eps]]) with the defaults of
+    Plan.set_adaptive"""
+    if a is None or isinstance(a, Adaptive):
+        return a
+    kind, eta = a[0], a[1]
+    b1, b2 = (a[2], a[3]) if len(a) > 3 else (0.9, 0.999)
+    return Adaptive(OPTIMIZERS[kind], float(eta), float(b1), float(b2), float(a[4]) if len(a) > 4 else 1e-8)
+
+
+def backend_run_adaptive(inst, L, R, adaptive_users=None, adaptive_items=None, bounds_users=None, bounds_items=None, weight=None,
+                         lambda_users=0.0, lambda_items=None, iters=None, device=0, recommend=True):
+    """mf_backend_run_adaptive: backend_run_bounded without momentum and with an adaptive rule per side -- None (the plain
+    step) or (kind, eta[, beta1, beta2[, eps]]), kind "adam" | "rmsprop" | "adagrad".  L, R updated in place, returns
+    best[users], or None with recommend=False."""
+    p, keep = _problem(inst, iters)
+    w = None if weight is None else np.ascontiguousarray(weight, np.float64)
+    assert w is None or w.shape == (inst.nnz,)
+    li = lambda_users if lambda_items is None else lambda_items
+    bu, bit = _bounds_record(bounds_users), _bounds_record(bounds_items)
+    au, ai = _adaptive_record(adaptive_users), _adaptive_record(adaptive_items)
+    best = np.empty(inst.users, np.int32) if recommend else None
+    assert L.dtype == np.float64 and R.dtype == np.float64 and L.flags.c_contiguous and R.flags.c_contiguous
+    _check(hip().mf_backend_run_adaptive(C.byref(p), None if w is None else w.ctypes.data, L.ctypes.data, R.ctypes.data,
+                                         best.ctypes.data if recommend else None, float(lambda_users), float(li),
+                                         None if bu is None else C.byref(bu), None if bit is None else C.byref(bit),
+                                         None if au is None else C.byref(au), None if ai is None else C.byref(ai), device),
+           "mf_backend_run_adaptive")
+    return best
+
+
+run_adaptive = backend_run_adaptive
 
 
 def bias_mean(val):
@@ -855,6 +909,53 @@ class Plan:
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
         _check(hip().mf_plan_bounds_active(self._h, SIDES[side], C.byref(a), C.byref(b), C.byref(c)), "mf_plan_bounds_active")
         return a.value, b.value, c.value
+
+    def set_adaptive(self, side, kind, eta=0.0, beta1=0.9, beta2=0.999, eps=1e-8):
+        """mf_plan_set_adaptive: the adaptive rule of a side ("items" / 0 or "users" / 1) -- kind "adam", "rmsprop" (beta2 is
+        its rho), "adagrad", or "none" / None for the plain step --, in force from the next launch.  A change of kind puts
+        the side's accumulators at rest; a change of the numbers alone keeps them."""
+        rec = Adaptive(OPTIMIZERS[kind], float(eta), float(beta1), float(beta2), float(eps))
+        _check(hip().mf_plan_set_adaptive(self._h, SIDES[side], C.byref(rec)), "mf_plan_set_adaptive")
+
+    def adaptive(self, side):
+        """mf_plan_get_adaptive: (kind name, eta, beta1, beta2, eps) of a side; ("none", 0, 0, 0, 0) without a rule"""
+        rec = Adaptive()
+        _check(hip().mf_plan_get_adaptive(self._h, SIDES[side], C.byref(rec)), "mf_plan_get_adaptive")
+        return OPTIMIZER_NAMES[rec.kind], rec.eta, rec.beta1, rec.beta2, rec.eps
+
+    def reset_adaptive(self, side):
+        """mf_plan_reset_adaptive: the side's accumulators back to rest (zeros, 1.0, 0 steps)"""
+        _check(hip().mf_plan_reset_adaptive(self._h, SIDES[side]), "mf_plan_reset_adaptive")
+
+    def adaptive_finish(self, side):
+        """mf_plan_adaptive_finish: the side's next-generation buffer taken as g and finished in place: what a sharded caller
+        runs on the summed side after its sum"""
+        _check(hip().mf_plan_adaptive_finish(self._h, SIDES[side]), "mf_plan_adaptive_finish")
+
+    def _side_shape(self, side):
+        return (self.items if SIDES[side] == 0 else self.user_count, self.feats)
+
+    def download_adaptive_state(self, side):
+        """mf_plan_download_adaptive_state: (m, v, steps, p1, p2) of a side; a side at rest gives zeros, 0, 1.0, 1.0"""
+        m, v = np.empty(self._side_shape(side), np.float64), np.empty(self._side_shape(side), np.float64)
+        steps, p1, p2 = C.c_int64(), C.c_double(), C.c_double()
+        _check(hip().mf_plan_download_adaptive_state(self._h, SIDES[side], m.ctypes.data, v.ctypes.data, C.byref(steps), C.byref(p1),
+                                                     C.byref(p2)), "mf_plan_download_adaptive_state")
+        return m, v, steps.value, p1.value, p2.value
+
+    def upload_adaptive_state(self, side, m=None, v=None, steps=None, p1=None, p2=None):
+        """mf_plan_upload_adaptive_state: what download_adaptive_state returned; None leaves that part as it is"""
+        m = None if m is None else np.ascontiguousarray(m, np.float64)
+        v = None if v is None else np.ascontiguousarray(v, np.float64)
+        assert m is None or m.shape == self._side_shape(side)
+        assert v is None or v.shape == self._side_shape(side)
+        st = None if steps is None else C.c_int64(int(steps))
+        q1 = None if p1 is None else C.c_double(float(p1))
+        q2 = None if p2 is None else C.c_double(float(p2))
+        _check(hip().mf_plan_upload_adaptive_state(self._h, SIDES[side], None if m is None else m.ctypes.data,
+                                                   None if v is None else v.ctypes.data, None if st is None else C.byref(st),
+                                                   None if q1 is None else C.byref(q1), None if q2 is None else C.byref(q2)),
+               "mf_plan_upload_adaptive_state")
 
     def penalty(self, rows=False):
         """mf_plan_penalty: (||L_block||^2, ||R||^2) of the current factors; with rows=True also the user_count and the

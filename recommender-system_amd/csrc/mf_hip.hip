@@ -247,6 +247,7 @@ int mf_plan_upload_factors(mf_plan *p, const double *L_block, const double *R)
 	MF_HIP(hipStreamSynchronize(p->stream));
 	p->have_factors = true;
 	p->rule[0].at_rest = p->rule[1].at_rest = true;   // new factors have no history
+	p->opt[0].rest = p->opt[1].rest = true;            // and no accumulated gradients
 	return MF_OK;
 }
 
@@ -333,7 +334,8 @@ int mf_plan_flip(mf_plan *p)
 
 static int iterate_eager(mf_plan *p, int iters)
 {
-	if (p->es_mode) {
+	// the errors + streams iteration seeds unconditionally: not while a side is adaptive, whose sweep is the unseeded one
+	if (p->es_mode && !adaptive_any(p)) {
 		for (int it = 0; it < iters; ++it) {
 			const int rc = launch_es_iteration(p);
 			if (rc != MF_OK) return rc;
@@ -367,6 +369,9 @@ int mf_plan_iterate(mf_plan *p, int iters)
 	if (iters > 0) {
 		MF_TRY(leave_rest(p, 0));
 		MF_TRY(leave_rest(p, 1));
+		// an adaptive side gets its accumulators here, for the same reason
+		MF_TRY(adaptive_ready(p, 0));
+		MF_TRY(adaptive_ready(p, 1));
 	}
 	// Launch-bound regime (inst1: 100000 iterations of a 13-entry instance, ~4 us per launch): capture an even
 	// number of iterations -- so the ping-pong parity returns to where it started -- into a HIP graph and replay it.
@@ -382,7 +387,7 @@ int mf_plan_iterate(mf_plan *p, int iters)
 		size_t need = mf::resident_lds_bytes(p->uc, p->items, p->K, p->nnz);
 		const bool toy = p->uc == p->users_total && p->u0 == 0 && p->uc + p->items <= 1024 && p->uc + p->items > 0 &&
 		                 need <= 60 * 1024 && (double) p->nnz * p->K <= 512.0 && !p->timing && iters >= 8 &&
-		                 p->cfg.resident;
+		                 p->cfg.resident && !adaptive_any(p);   // the toy loop seeds unconditionally, like errors + streams
 		if (toy) {
 			mf::ResidentArgs ra;
 			ra.users = p->uc;
@@ -509,6 +514,8 @@ int mf_plan_get_regularization(mf_plan *p, double *lambda_users, double *lambda_
 int mf_plan_set_momentum(mf_plan *p, double beta_users, double beta_items)
 {
 	if (!p || !lambda_ok(beta_users) || !lambda_ok(beta_items)) return MF_ERR_ARGUMENT;   // finite and >= 0, like a weight
+	// not on an adaptive side: its X_new carries g, so there is no X_prev
+	if ((beta_users != 0.0 && adaptive_side(p, 1)) || (beta_items != 0.0 && adaptive_side(p, 0))) return MF_ERR_UNSUPPORTED;
 	// read at every launch (the graph path captures per call).  A side whose beta leaves 0 has maintained no history: it
 	// is at rest; a change between two non-zero values keeps the history
 	if (p->rule[1].beta == 0.0 && beta_users != 0.0) p->rule[1].at_rest = true;
@@ -616,6 +623,105 @@ int mf_plan_bounds_active(mf_plan *p, int side, int64_t *at_lo, int64_t *at_hi, 
 	if (at_lo) *at_lo = (int64_t) c[0];
 	if (at_hi) *at_hi = (int64_t) c[1];
 	if (inside) *inside = (int64_t) c[2];
+	return MF_OK;
+}
+
+// an adaptive rule: NULL or kind NONE (no rule), or a known kind with eta and eps finite and > 0 and the betas the kind
+// reads in [0, 1)
+static bool unit_ok(double v) { return v >= 0.0 && v < 1.0; }
+static bool adaptive_ok(const mf_adaptive *o)
+{
+	if (!o || o->kind == MF_OPT_NONE) return true;
+	if (o->kind != MF_OPT_ADAGRAD && o->kind != MF_OPT_RMSPROP && o->kind != MF_OPT_ADAM) return false;
+	if (!std::isfinite(o->eta) || !(o->eta > 0.0) || !std::isfinite(o->eps) || !(o->eps > 0.0)) return false;
+	if (o->kind != MF_OPT_ADAGRAD && !unit_ok(o->beta2)) return false;
+	return o->kind != MF_OPT_ADAM || unit_ok(o->beta1);
+}
+static const mf_adaptive kNoAdaptive = {MF_OPT_NONE, 0.0, 0.0, 0.0, 0.0};
+static mf_adaptive adaptive_rule(const mf_adaptive *o) { return o && o->kind != MF_OPT_NONE ? *o : kNoAdaptive; }
+
+int mf_plan_set_adaptive(mf_plan *p, int side, const mf_adaptive *rule)
+{
+	if (!p || (side != 0 && side != 1) || !adaptive_ok(rule)) return MF_ERR_ARGUMENT;
+	const mf_adaptive o = adaptive_rule(rule);
+	if (o.kind != MF_OPT_NONE && p->rule[side].beta != 0.0) return MF_ERR_UNSUPPORTED;   // momentum came first
+	// read at every launch (the graph path captures per call).  A change of kind puts the side at rest; a change of the
+	// numbers alone keeps what it has accumulated
+	if (o.kind != p->rule[side].opt.kind) p->opt[side].rest = true;
+	p->rule[side].opt = o;
+	return MF_OK;
+}
+
+int mf_plan_get_adaptive(mf_plan *p, int side, mf_adaptive *rule)
+{
+	if (!p || (side != 0 && side != 1)) return MF_ERR_ARGUMENT;
+	if (rule) *rule = p->rule[side].opt;
+	return MF_OK;
+}
+
+int mf_plan_reset_adaptive(mf_plan *p, int side)
+{
+	if (!p || (side != 0 && side != 1)) return MF_ERR_ARGUMENT;
+	p->opt[side].rest = true;
+	return MF_OK;
+}
+
+int mf_plan_adaptive_finish(mf_plan *p, int side)
+{
+	if (!p || (side != 0 && side != 1)) return MF_ERR_ARGUMENT;
+	if (!p->have_factors || !adaptive_side(p, side)) return MF_ERR_STATE;
+	MF_HIP(hipSetDevice(p->device));
+	if (p->side[side].nrows <= 0) return MF_OK;
+	MF_TRY(adaptive_ready(p, side));
+	MF_TRY(launch_adaptive_tick(p, side));
+	return launch_adaptive_finish(p, side, nullptr, p->side[side].nrows, p->stream);
+}
+
+int mf_plan_download_adaptive_state(mf_plan *p, int side, double *m, double *v, int64_t *steps, double *p1, double *p2)
+{
+	if (!p || (side != 0 && side != 1)) return MF_ERR_ARGUMENT;
+	if (!p->have_factors) return MF_ERR_STATE;
+	const AdaptiveState &s = p->opt[side];
+	const int rows = side == 0 ? p->items : p->uc, ld = side == 0 ? p->ldr : p->ldl;
+	const size_t n = (size_t) rows * p->K, w = (size_t) p->K * sizeof(double);
+	const bool rest = !adaptive_side(p, side) || s.rest || !s.step || !s.v;
+	const bool have_m = !rest && p->rule[side].opt.kind == MF_OPT_ADAM && s.m;
+	mf::AdaptiveStep rec{1.0, 1.0, 0.0, 0.0, 0};
+	if (m && !have_m) std::fill(m, m + n, 0.0);
+	if (v && rest) std::fill(v, v + n, 0.0);
+	if (!rest) {
+		MF_HIP(hipSetDevice(p->device));
+		if (m && have_m && rows) MF_HIP(hipMemcpy2DAsync(m, w, s.m, (size_t) ld * sizeof(double), w, (size_t) rows, hipMemcpyDeviceToHost, p->stream));
+		if (v && rows) MF_HIP(hipMemcpy2DAsync(v, w, s.v, (size_t) ld * sizeof(double), w, (size_t) rows, hipMemcpyDeviceToHost, p->stream));
+		MF_HIP(hipMemcpyAsync(&rec, s.step, sizeof rec, hipMemcpyDeviceToHost, p->stream));
+		MF_HIP(hipStreamSynchronize(p->stream));
+	}
+	if (steps) *steps = (int64_t) rec.steps;
+	if (p1) *p1 = rec.p1;
+	if (p2) *p2 = rec.p2;
+	return MF_OK;
+}
+
+int mf_plan_upload_adaptive_state(mf_plan *p, int side, const double *m, const double *v, const int64_t *steps, const double *p1,
+                                  const double *p2)
+{
+	if (!p || (side != 0 && side != 1) || (steps && *steps < 0) || (p1 && std::isnan(*p1)) || (p2 && std::isnan(*p2))) return MF_ERR_ARGUMENT;
+	if (!p->have_factors || !adaptive_side(p, side)) return MF_ERR_STATE;
+	MF_HIP(hipSetDevice(p->device));
+	MF_TRY(adaptive_ready(p, side));   // what is not given starts from rest, or stays as it is
+	AdaptiveState &s = p->opt[side];
+	const int rows = side == 0 ? p->items : p->uc, ld = side == 0 ? p->ldr : p->ldl;
+	const size_t w = (size_t) p->K * sizeof(double);
+	if (m && rows && p->rule[side].opt.kind == MF_OPT_ADAM)
+		MF_HIP(hipMemcpy2DAsync(s.m, (size_t) ld * sizeof(double), m, w, w, (size_t) rows, hipMemcpyHostToDevice, p->stream));
+	if (v && rows) MF_HIP(hipMemcpy2DAsync(s.v, (size_t) ld * sizeof(double), v, w, w, (size_t) rows, hipMemcpyHostToDevice, p->stream));
+	if (steps || p1 || p2) {
+		mf::AdaptiveStep rec;
+		MF_HIP(hipMemcpyAsync(&rec, s.step, sizeof rec, hipMemcpyDeviceToHost, p->stream));
+		MF_HIP(hipStreamSynchronize(p->stream));
+		MF_TRY(adaptive_set_record(p, side, p1 ? *p1 : rec.p1, p2 ? *p2 : rec.p2, steps ? (long long) *steps : rec.steps));
+	}
+	MF_HIP(hipStreamSynchronize(p->stream));
 	return MF_OK;
 }
 
@@ -922,6 +1028,24 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 	}
 	// per-entry weights, when the plan was created with them
 	if (p->weighted) append(buf, buflen, " weighted=1");
+	// the adaptive rules in force, when a side has one: adaptive=<users>/<items>, the numbers in %.17g (they read back
+	// exactly).  While one is, mf_plan_iterate runs the two sweeps whatever iterate= says above: the errors + streams
+	// iteration and the toy loop seed unconditionally
+	if (adaptive_any(p)) {
+		char sd[2][160];
+		for (int k = 0; k < 2; ++k) {
+			const mf_adaptive &o = p->rule[k].opt;
+			if (o.kind == MF_OPT_ADAM)
+				snprintf(sd[k], sizeof sd[k], "adam(%.17g,%.17g,%.17g,%.17g)", o.eta, o.beta1, o.beta2, o.eps);
+			else if (o.kind == MF_OPT_RMSPROP)
+				snprintf(sd[k], sizeof sd[k], "rmsprop(%.17g,%.17g,%.17g)", o.eta, o.beta2, o.eps);
+			else if (o.kind == MF_OPT_ADAGRAD)
+				snprintf(sd[k], sizeof sd[k], "adagrad(%.17g,%.17g)", o.eta, o.eps);
+			else
+				snprintf(sd[k], sizeof sd[k], "-");
+		}
+		append(buf, buflen, " adaptive=%s/%s", sd[1], sd[0]);
+	}
 	// the environment switches this plan was created under, when any differs from its default (mf_config.hip.h)
 	const std::string cfg = p->cfg.describe();
 	if (!cfg.empty()) append(buf, buflen, " config{%s}", cfg.c_str());
@@ -1024,6 +1148,19 @@ int mf_backend_run_bounded(const mf_problem *pr, const double *weight, double *L
 		return MF_ERR_ARGUMENT;
 	return run_single_plan(pr, weight, level1_rules(lambda_users, lambda_items, beta_users, beta_items, bounds_users, bounds_items), L, R,
 	                       best, device);
+}
+
+// the plain rule's betas are absent: a side cannot have momentum and an adaptive kind
+int mf_backend_run_adaptive(const mf_problem *pr, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
+                            double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items,
+                            const mf_adaptive *adaptive_users, const mf_adaptive *adaptive_items, int device)
+{
+	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !bounds_record_ok(bounds_users, pr->features) ||
+	    !bounds_record_ok(bounds_items, pr->features) || !adaptive_ok(adaptive_users) || !adaptive_ok(adaptive_items))
+		return MF_ERR_ARGUMENT;
+	RulePair rule = level1_rules(lambda_users, lambda_items, 0.0, 0.0, bounds_users, bounds_items);
+	rule[1].opt = adaptive_rule(adaptive_users), rule[0].opt = adaptive_rule(adaptive_items);
+	return run_single_plan(pr, weight, rule, L, R, best, device);
 }
 
 // ---- biases on frozen columns: a ~ mu + b_user + b_item + l.r as the K = F + 2 product of

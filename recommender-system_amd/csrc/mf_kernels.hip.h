@@ -9,4 +9,5 @@
 #include "mf_rank.hip.h"
 #include "mf_similar.hip.h"
 #include "mf_loss.hip.h"
+#include "mf_adaptive.hip.h"
 #include "mf_collective.hip.h"

@@ -269,12 +269,107 @@ int leave_rest(mf_plan *p, int kind)
 	return MF_OK;
 }
 
+// ---- adaptive sides (mf_adaptive.hip.h): a seeded sweep is the unseeded one, a tick of the side's step record in front of
+// it and the finishing kernel behind it.
+bool adaptive_side(const mf_plan *p, int kind) { return p->rule[kind].opt.kind != MF_OPT_NONE; }
+bool adaptive_any(const mf_plan *p) { return adaptive_side(p, 0) || adaptive_side(p, 1); }
+
+// elements of a side's accumulators: its rows x its pitch
+size_t adaptive_elements(const mf_plan *p, int kind) { return kind == 0 ? (size_t) p->items * p->ldr : (size_t) p->uc * p->ldl; }
+
+// puts the side's step record at (p1, p2, steps), on the plan's stream
+int adaptive_set_record(mf_plan *p, int kind, double p1, double p2, long long steps)
+{
+	hipLaunchKernelGGL(mf::adaptive_set_kernel, dim3(1), dim3(1), 0, p->stream, p->opt[kind].step.get(), p1, p2, steps);
+	MF_HIP(hipGetLastError());
+	return MF_OK;
+}
+
+// The accumulators of an adaptive side exist and, where the side is at rest, say so: v (and ADAM's m) zeroed with
+// hipMemsetAsync on the plan's stream, the record at 1.0, 1.0, 0.  mf_plan_iterate calls it before it captures or launches
+// anything, so no graph sees an allocation or a special first step; a buffer is only ever new on a side at rest (a change
+// of kind puts the side there).
+int adaptive_ready(mf_plan *p, int kind)
+{
+	const mf_adaptive &o = p->rule[kind].opt;
+	if (o.kind == MF_OPT_NONE) return MF_OK;
+	AdaptiveState &s = p->opt[kind];
+	const size_t n = adaptive_elements(p, kind);
+	if (!s.step || !s.v || (o.kind == MF_OPT_ADAM && !s.m)) s.rest = true;
+	if (!s.step) MF_TRY(s.step.alloc(1));
+	if (!s.v) MF_TRY(s.v.alloc(n));
+	if (o.kind == MF_OPT_ADAM && !s.m) MF_TRY(s.m.alloc(n));
+	if (!s.rest) return MF_OK;
+	if (n) MF_HIP(hipMemsetAsync(s.v, 0, n * sizeof(double), p->stream));
+	if (n && o.kind == MF_OPT_ADAM) MF_HIP(hipMemsetAsync(s.m, 0, n * sizeof(double), p->stream));
+	MF_TRY(adaptive_set_record(p, kind, 1.0, 1.0, 0));
+	s.rest = false;
+	return MF_OK;
+}
+
+// one step of the side's record, on the plan's stream: in front of the sweep's fork, so both streams are behind it
+int launch_adaptive_tick(mf_plan *p, int kind)
+{
+	const mf_adaptive &o = p->rule[kind].opt;
+	hipLaunchKernelGGL(mf::adaptive_tick_kernel, dim3(1), dim3(1), 0, p->stream, p->opt[kind].step.get(), o.beta1, o.beta2,
+	                   (int) (o.kind == MF_OPT_ADAM));
+	MF_HIP(hipGetLastError());
+	return MF_OK;
+}
+
+// The finish of `nrows` rows of the side (rowlist, or rows 0..nrows when null) on `stream`: X_new holds g.  The decay,
+// the frozen column and the box are the seeded sweep's (side_update).
+int launch_adaptive_finish(mf_plan *p, int kind, const int *rowlist, int nrows, hipStream_t stream)
+{
+	if (nrows <= 0) return MF_OK;
+	const mf_adaptive &o = p->rule[kind].opt;
+	const SideOperands x = side_operands(p, kind);
+	const SideUpdate u = side_update(p, kind, 1);
+	mf::AdaptiveArgs a;
+	a.nrows = nrows;
+	a.K = p->K;
+	a.ld = x.ldx;
+	a.frozen = u.frozen;
+	// rows of a workgroup per step: about eight pieces per thread
+	const int per = (a.ld & 1) ? a.K : (a.K >> 1) + (a.K & 1);
+	a.rows_per_step = std::max(1, std::min(mf::kAdaptiveRows, 8 * mf::kAdaptiveThreads / per));
+	a.rowlist = rowlist;
+	a.X_old = x.X_old;
+	a.X_new = x.X_new;
+	a.m = p->opt[kind].m;
+	a.v = p->opt[kind].v;
+	a.step = p->opt[kind].step;
+	a.d = u.d;
+	a.eta = o.eta;
+	a.eps = o.eps;
+	a.beta1 = o.beta1;
+	a.beta2 = o.beta2;
+	a.ob1 = 1.0 - o.beta1;
+	a.ob2 = 1.0 - o.beta2;
+	a.box = u.box;
+	void (*fn)(mf::AdaptiveArgs) = o.kind == MF_OPT_ADAM      ? mf::adaptive_finish_kernel<MF_OPT_ADAM>
+	                               : o.kind == MF_OPT_RMSPROP ? mf::adaptive_finish_kernel<MF_OPT_RMSPROP>
+	                                                          : mf::adaptive_finish_kernel<MF_OPT_ADAGRAD>;
+	const int grid = std::min((nrows + a.rows_per_step - 1) / a.rows_per_step, 1 << 16);
+	hipLaunchKernelGGL(fn, dim3(grid), dim3(mf::kAdaptiveThreads), 0, stream, a);
+	MF_HIP(hipGetLastError());
+	return MF_OK;
+}
+
 // defer_join: leave the ordered sums of the extreme rows running on the side stream when the call returns
 // (p->join_pending); the caller joins before anything reads the new generation.
+// A seeded sweep of an adaptive side launches exactly what the unseeded one does -- the same form and flavour, box columns
+// 0, beta 0 -- with the tick in front and the finish behind: over the short rows (or all rows) on the plan's stream, over
+// the extreme rows behind their ordered sum on the side stream, in front of ev_join.
 int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 {
 	const SweepSide &sd = p->side[kind];
 	const SideOperands x = side_operands(p, kind);
+	const bool adaptive = seed && adaptive_side(p, kind) && sd.nrows > 0;
+	if (adaptive) {
+		MF_TRY(adaptive_ready(p, kind));
+		seed = 0;
+	}
 	mf::SweepArgs a;
 	a.K = p->K;
 	a.stride = p->stride;
@@ -318,6 +413,7 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 		t.kind = kind;
 		MF_HIP(hipEventRecord(t.t0, p->stream));
 	}
+	if (adaptive) MF_TRY(launch_adaptive_tick(p, kind));
 	void *args[] = {&a};
 	if (extreme) {
 		// extreme rows: products kernel over their 64-entry segments -> ordered sum per (row, column slice),
@@ -375,12 +471,14 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 			o.d = 1.0;
 		}
 		MF_HIP(hipLaunchKernel(ordered_sum_fn(p->cfg), dim3(o.nrows * o.nslices), dim3(mf::kWave), oargs, p->lds_bytes_osum, p->side_stream));
+		if (adaptive) MF_TRY(launch_adaptive_finish(p, kind, sd.long_rows, sd.n_long, p->side_stream));
 		MF_HIP(hipEventRecord(p->ev_join, p->side_stream));
 		a.nrows = sd.n_short;
 		a.rowlist = sd.short_rows;
 	}
 	if (a.nrows > 0)
 		MF_HIP(hipLaunchKernel((const void *) f.fn, dim3(std::min(a.nrows, 1 << 20)), dim3(f.block), args, f.lds, p->stream));
+	if (adaptive) MF_TRY(launch_adaptive_finish(p, kind, extreme ? sd.short_rows.get() : nullptr, a.nrows, p->stream));
 	if (extreme) {
 		if (defer_join)
 			p->join_pending = true;

@@ -224,6 +224,17 @@ struct SideRule {
 	// side's beta from 0; cleared by its first seeded momentum sweep (leave_rest copies current -> next) and by
 	// mf_plan_upload_previous
 	bool at_rest = true;
+	// adaptive step size, mf_plan_set_adaptive: kind NONE is the plain step.  A side never has beta != 0 and a kind
+	mf_adaptive opt = {MF_OPT_NONE, 0.0, 0.0, 0.0, 0.0};
+};
+
+// The accumulators of an adaptive side (mf_adaptive.hip.h), allocated when first needed: m (ADAM only) and v, rows x the
+// side's pitch, and the step record.  `rest`: the state is at rest by definition -- zeros, 1.0, 0 steps -- whatever the
+// buffers hold; adaptive_ready (mf_launch.hip.h) makes them say so in front of the side's next adaptive launch.
+struct AdaptiveState {
+	dev_buf<double> m, v;
+	dev_buf<mf::AdaptiveStep> step;
+	bool rest = true;
 };
 
 }  // namespace
@@ -236,6 +247,7 @@ struct mf_plan {
 	int64_t nnz = 0;
 	double alpha = 0.0;
 	SideRule rule[2];   // the update rule per side (0 = items, 1 = users); side_update (mf_launch.hip.h) reads it at every launch
+	AdaptiveState opt[2];   // the accumulators of a side whose rule has an adaptive kind
 	int flags = 0;
 
 	hipStream_t own_stream = nullptr;

@@ -22,11 +22,11 @@
 
 /* Every MATFACT_* variable the program reads: the mode options in the order they are examined, the path options, and the
  * accessories, which take part in no rule. */
-enum { V_TOPN, V_LOSS, V_HELDOUT, V_RANK, V_SIMILAR, V_SIMILAR_OUT, V_LAMBDA, V_BIAS, V_MOMENTUM, V_WEIGHTS, V_BOUNDS, V_DEVICES, V_MATS, V_CHECKPOINT, V_RESUME,
+enum { V_TOPN, V_LOSS, V_HELDOUT, V_RANK, V_SIMILAR, V_SIMILAR_OUT, V_LAMBDA, V_BIAS, V_MOMENTUM, V_WEIGHTS, V_BOUNDS, V_OPTIMIZER, V_DEVICES, V_MATS, V_CHECKPOINT, V_RESUME,
        V_DEVICE, V_MATS_ITERS, V_CHECKPOINT_EVERY, V_CACHE, V_TIMING, V_COUNT };
 static const char *const cli_names[V_COUNT] = {
 	"MATFACT_TOPN", "MATFACT_LOSS", "MATFACT_HELDOUT", "MATFACT_RANK", "MATFACT_SIMILAR", "MATFACT_SIMILAR_OUT", "MATFACT_LAMBDA",
-	"MATFACT_BIAS", "MATFACT_MOMENTUM", "MATFACT_WEIGHTS", "MATFACT_BOUNDS", "MATFACT_DEVICES", "MATFACT_MATS", "MATFACT_CHECKPOINT", "MATFACT_RESUME", "MATFACT_DEVICE",
+	"MATFACT_BIAS", "MATFACT_MOMENTUM", "MATFACT_WEIGHTS", "MATFACT_BOUNDS", "MATFACT_OPTIMIZER", "MATFACT_DEVICES", "MATFACT_MATS", "MATFACT_CHECKPOINT", "MATFACT_RESUME", "MATFACT_DEVICE",
 	"MATFACT_MATS_ITERS", "MATFACT_CHECKPOINT_EVERY", "MATFACT_CACHE", "MATFACT_TIMING"};
 
 struct cli_options {
@@ -48,6 +48,8 @@ struct cli_options {
 	double beta_users, beta_items;
 	int bounded;          /* MATFACT_BOUNDS=lo,hi[,lo_items,hi_items]: every finished row projected onto [lo, hi] (0,inf: non-negative */
 	double lo_users, hi_users, lo_items, hi_items;   /* factors); one pair for both sides or users then items; the bias columns stay free */
+	int adaptive;         /* MATFACT_OPTIMIZER=adam,eta[,beta1,beta2[,eps]] | rmsprop,eta[,rho[,eps]] | adagrad,eta[,eps]: a per-element */
+	mf_adaptive optimizer;   /* adaptive step on both sides (eta, eps > 0; beta1, beta2, rho in [0, 1); defaults 0.9, 0.999, 1e-8) */
 	int device;           /* MATFACT_DEVICE=n: the GPU of a single-GPU run, default 0 */
 	int devs[16], ndev;   /* MATFACT_DEVICES=0,1,...: row-shard over these GPUs of the process, at most 16 */
 	const char *devices_error;   /* a non-number in it: said only where that path runs, after the input was read, as ever */
@@ -115,6 +117,22 @@ static const char *cli_value(int v, const char *s, struct cli_options *o)
 		/* a NaN fails every comparison */
 		o->bounded = ok && o->lo_users <= o->hi_users && o->lo_items <= o->hi_items;
 		return o->bounded ? NULL : "MATFACT_BOUNDS: expected lo,hi[,lo_items,hi_items] with numbers lo <= hi.";
+	case V_OPTIMIZER: {
+		bad = "MATFACT_OPTIMIZER: expected adam,eta[,beta1,beta2[,eps]], rmsprop,eta[,rho[,eps]] or adagrad,eta[,eps] with eta, eps > 0 and beta1, beta2, rho in [0, 1).";
+		mf_adaptive *a = &o->optimizer;
+		const size_t n = strcspn(s, ",");
+		a->kind = n == 4 && !strncmp(s, "adam", n) ? MF_OPT_ADAM : n == 7 && !strncmp(s, "rmsprop", n) ? MF_OPT_RMSPROP : n == 7 && !strncmp(s, "adagrad", n) ? MF_OPT_ADAGRAD : MF_OPT_NONE;
+		a->beta1 = 0.9, a->beta2 = 0.999, a->eps = 1e-8;
+		ok = a->kind != MF_OPT_NONE && s[n] && number(s + n + 1, ',', &rest, &a->eta);
+		/* the betas the kind has: two, one or none, given together */
+		if (ok && *rest && a->kind == MF_OPT_ADAM) ok = number(rest + 1, ',', &rest, &a->beta1) && *rest && number(rest + 1, ',', &rest, &a->beta2);
+		else if (ok && *rest && a->kind == MF_OPT_RMSPROP) ok = number(rest + 1, ',', &rest, &a->beta2);
+		if (ok && *rest) ok = number(rest + 1, 0, &rest, &a->eps);
+		/* a NaN fails every comparison */
+		o->adaptive = ok && isfinite(a->eta) && a->eta > 0.0 && isfinite(a->eps) && a->eps > 0.0 && a->beta1 >= 0.0 && a->beta1 < 1.0 &&
+		              a->beta2 >= 0.0 && a->beta2 < 1.0;
+		return o->adaptive ? NULL : bad;
+	}
 	}
 	return NULL;   /* MATFACT_HELDOUT, MATFACT_SIMILAR_OUT, MATFACT_WEIGHTS: any text */
 }
@@ -147,6 +165,7 @@ static const struct cli_rule cli_clashes[] = {
 	{V_MOMENTUM, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_MOMENTUM works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
 	{V_WEIGHTS, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_WEIGHTS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
 	{V_BOUNDS, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_BOUNDS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
+	{V_OPTIMIZER, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR) | BIT(V_MOMENTUM), "MATFACT_OPTIMIZER works on the single-GPU path only and not with momentum: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN, MATFACT_SIMILAR and MATFACT_MOMENTUM."},
 };
 
 /* Fills `o` from the environment -- it opens no file and makes no GPU call -- and returns NULL, or the message to die with. */
@@ -157,7 +176,7 @@ static const char *cli_parse(struct cli_options *o)
 	for (int v = 0; v < V_COUNT; v++)
 		if ((o->value[v] = getenv(cli_names[v])) != NULL) set |= BIT(v);
 	const unsigned usable = o->value[V_SIMILAR_OUT] && !*o->value[V_SIMILAR_OUT] ? set & ~BIT(V_SIMILAR_OUT) : set;
-	for (int v = V_TOPN; v <= V_BOUNDS; v++) {
+	for (int v = V_TOPN; v <= V_OPTIMIZER; v++) {
 		const char *message = set & BIT(v) ? cli_value(v, o->value[v], o) : NULL;
 		if (message) return message;
 		if (!(set & BIT(v))) continue;
@@ -363,7 +382,7 @@ static int run_session(const struct cli_options *o, const mf_problem *p, const m
 	int points = 0;
 	int rc = session_open(&s, o, p, wts, L, R);
 	if (rc == MF_OK && cap && !trace) rc = MF_ERR_NO_MEMORY;
-	/* configure: the held-out set, regularisation, the frozen columns of the biases, momentum, the box */
+	/* configure: the held-out set, regularisation, the frozen columns of the biases, momentum, the box, the adaptive step */
 	if (rc == MF_OK && held) rc = split_entries(held, &s.hrow, &s.hcol, &s.hval);
 	for (int64_t i = 0; rc == MF_OK && held && o->biased && i < held->nnz; i++) s.hval[i] -= s.mu;
 	if (rc == MF_OK && held) rc = mf_plan_set_heldout(s.plan, held->nnz, s.hrow, s.hcol, s.hval);
@@ -373,6 +392,9 @@ static int run_session(const struct cli_options *o, const mf_problem *p, const m
 	/* the box covers the file's K columns: all of them, or with MATFACT_BIAS the latent F in front of the two bias columns */
 	if (rc == MF_OK && o->bounded) rc = mf_plan_set_bounds(s.plan, 1, o->lo_users, o->hi_users, p->features);
 	if (rc == MF_OK && o->bounded) rc = mf_plan_set_bounds(s.plan, 0, o->lo_items, o->hi_items, p->features);
+	/* the adaptive step, the same rule on both sides */
+	if (rc == MF_OK && o->adaptive) rc = mf_plan_set_adaptive(s.plan, 1, &o->optimizer);
+	if (rc == MF_OK && o->adaptive) rc = mf_plan_set_adaptive(s.plan, 0, &o->optimizer);
 	/* loop */
 	if (rc == MF_OK) {
 		if (o->loss_every) rc = mf_plan_iterate_monitored(s.plan, p->iters, o->loss_every, o->loss_tol, trace, cap, &points, &done);
@@ -488,10 +510,10 @@ int main(int argc, char **argv)
 	/*
 	 * The rules of cli_parse leave mode options or path options, never both.  Among the path options the priority is silent:
 	 * MATFACT_CHECKPOINT / MATFACT_RESUME win over MATFACT_MATS, which wins over MATFACT_DEVICES (and MATFACT_RESUME is read
-	 * above whenever it is set).  MATFACT_LOSS, MATFACT_SIMILAR, MATFACT_WEIGHTS, MATFACT_BOUNDS, MATFACT_BIAS with MATFACT_MOMENTUM, the checkpoints and the dump need a resident plan and run as
+	 * above whenever it is set).  MATFACT_LOSS, MATFACT_SIMILAR, MATFACT_WEIGHTS, MATFACT_BOUNDS, MATFACT_OPTIMIZER, MATFACT_BIAS with MATFACT_MOMENTUM, the checkpoints and the dump need a resident plan and run as
 	 * a session, which splits the entries once; the rest goes through the level-1 calls, which take the entries as they are.
 	 */
-	if (o.loss_every || o.similar || have_wts || o.bounded || o.value[V_CHECKPOINT] || o.value[V_RESUME] || (o.momentum && o.biased)) {
+	if (o.loss_every || o.similar || have_wts || o.bounded || o.adaptive || o.value[V_CHECKPOINT] || o.value[V_RESUME] || (o.momentum && o.biased)) {
 		rc = run_session(&o, &prob, have_held ? &held : NULL, have_wts ? &wts : NULL, L, R, best, start_iter, NULL);
 	} else if (o.biased) {
 		/* biases start at 0.0; L and R took the reference's random() stream for K = F above */
