@@ -220,14 +220,14 @@ void mf_plan_destroy(mf_plan *plan);
  * buffers) needs no host synchronisation between that work and the plan's (tests/test_stream_order.py holds every line
  * below on a stream that is busy when the library is called).
  *   - Entry points that only ENQUEUE and return: mf_plan_iterate (and mf_plan_iterate_monitored between its evaluation
- *     points), mf_plan_sweep_items, mf_plan_sweep_users, mf_plan_sweep_users_seeded and mf_plan_project.  What they
+ *     points), mf_plan_sweep_items, mf_plan_sweep_users, mf_plan_sweep_users_seeded, mf_plan_project and mf_plan_als_solve.  What they
  *     write may be read by work enqueued on the stream after the call returns, or by the host after
  *     mf_plan_synchronize.  A HIP graph that mf_plan_iterate builds is captured on and replayed into this stream.
  *   - Host only, no device work: mf_plan_flip, the setters and getters of the update rule, the pointer and pitch
  *     queries, mf_plan_describe.  A setter holds from the next launch that is enqueued.
  *   - COMPLETE ON RETURN (they enqueue behind whatever the stream holds and wait for it): everything that returns data
  *     to the host -- mf_plan_download_*, mf_plan_recommend*, mf_plan_rank_heldout, mf_plan_similar_items, mf_plan_loss,
- *     mf_plan_penalty, mf_plan_weight_total, mf_plan_bounds_active, mf_plan_predict, mf_plan_timing_read, an evaluation
+ *     mf_plan_penalty, mf_plan_weight_total, mf_plan_bounds_active, mf_plan_als_info, mf_plan_predict, mf_plan_timing_read, an evaluation
  *     point of mf_plan_iterate_monitored --, mf_plan_upload_factors, mf_plan_upload_previous, mf_plan_set_heldout,
  *     mf_plan_synchronize, mf_plan_create*, and mf_plan_destroy, which waits for the stream before it frees anything:
  *     caller-owned buffers hold the results of all enqueued work when it returns.
@@ -649,6 +649,65 @@ int mf_plan_upload_adaptive_state(mf_plan *plan, int side, const double *m, cons
 int mf_backend_run_adaptive(const mf_problem *p, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
                             double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items,
                             const mf_adaptive *adaptive_users, const mf_adaptive *adaptive_items, int device);
+
+/* ---- Alternating least squares: with one side frozen, every row of the other side is the solution of its own K x K ridge
+ * regression.  An extension (the reference has only the gradient step), so the definition is this library's.  Sides are
+ * counted as everywhere: 0 = items, 1 = users.
+ *
+ * mf_plan_als_solve(plan, side, other_generation) computes, for every row r of side X, a new row into X's next-generation
+ * buffer.  It reads Y = the other side's current buffer (other_generation 0) or next buffer (1), X_old = X's current
+ * buffer, and the row's entries n = 0 .. cnt-1 in the side's entry order (CSR order for users, CSC order for items: the
+ * order the sweeps walk): a_n the value, w_n the weight (weighted plan only), y_n the Y row of the entry's other index.
+ * Every operation is rounded once and nothing is fused; sqrt and / are correctly rounded (IEEE 754).
+ *    1. With a frozen column f on this side  xf = X_old[r][f]  and  a'_n = a_n - (xf * y_n[f]);  otherwise a'_n = a_n.
+ *    2. yw_n[q] = y_n[q] * w_n on a weighted plan, yw_n[q] = y_n[q] otherwise.
+ *    3. Lower triangle of the Gram matrix, p >= q: G[p][q] starts at 0.0; for n ascending
+ *       G[p][q] = G[p][q] + (y_n[p] * yw_n[q]).
+ *    4. Right-hand side: b[p] starts at 0.0; for n ascending  b[p] = b[p] + (a'_n * yw_n[p]).
+ *    5. Ridge:  G[p][p] = G[p][p] + ridge,  ridge = lambda_side (MF_ALS_RIDGE) or lambda_side * (double) cnt
+ *       (MF_ALS_RIDGE_COUNT, the "weighted-lambda" ALS of Zhou et al.).
+ *    6. Frozen column f:  G[f][q] = 0.0 for q < f,  G[p][f] = 0.0 for p > f,  G[f][f] = 1.0,  b[f] = xf: the other columns
+ *       then get the bits of the reduced (K-1)-column system.
+ *    7. Cholesky G = C C^T, for j ascending:  s = G[j][j];  for t < j ascending  s = s - (C[j][t] * C[j][t]);  if !(s > 0.0)
+ *       the row is NOT POSITIVE DEFINITE (a NaN fails too);  C[j][j] = sqrt(s);  for each i > j:  s = G[i][j];  for t < j
+ *       ascending  s = s - (C[i][t] * C[j][t]);  C[i][j] = s / C[j][j].  (The kernels are right-looking: column t's rank-1
+ *       update is applied in the order t = 0, 1, ..., which is this chain element by element.)
+ *    8. Forward solve, column-oriented: for j ascending  z[j] = b[j] / C[j][j],  then for every i > j
+ *       b[i] = b[i] - (C[i][j] * z[j]): element i loses its terms one by one, t ascending.
+ *    9. Backward solve, column-oriented: for j descending  x[j] = z[j] / C[j][j],  then for every i < j
+ *       z[i] = z[i] - (C[j][i] * x[j]): element i loses its terms one by one, t descending from K-1.
+ *   10. The box projection of mf_plan_set_bounds on the bounded columns, then the frozen select: the frozen column keeps
+ *       X_old's bits.  A row without entries keeps X_old's bits and is not projected; a row that is not positive definite
+ *       keeps X_old's bits too.  The padding of a row is never touched.
+ * alpha is not read.  lambda, the weights, the frozen columns and the bounds are read at every launch, as the decay is.
+ * The objective a solve cannot increase is mf_plan_loss (training; weighted on a weighted plan) plus lambda times
+ * mf_plan_penalty's squares -- under MF_ALS_RIDGE_COUNT the per-row squares times the row counts.
+ *
+ * mf_plan_set_als: MF_ALS_OFF (the default), MF_ALS_RIDGE or MF_ALS_RIDGE_COUNT; mf_plan_get_als is its inverse.  An unknown
+ * kind -> MF_ERR_ARGUMENT.  K > 128 -> MF_ERR_UNSUPPORTED (the triangle of a row lives in LDS).  Momentum or an adaptive
+ * side together with ALS is refused: whichever of mf_plan_set_momentum / mf_plan_set_adaptive / mf_plan_set_als comes
+ * second returns MF_ERR_UNSUPPORTED with nothing changed.  While the kind is not OFF one iteration of mf_plan_iterate and
+ * of mf_plan_iterate_monitored is  als_solve(users, 0);  als_solve(items, 1);  flip  -- Gauss-Seidel: the item solve reads
+ * the new L -- as eager launches on the plan's stream, no captured graph.  The sweep entry points stay gradient sweeps.
+ * With the kind OFF the plan launches the kernels and produces the bits it does without this section.
+ * mf_plan_als_solve only enqueues.  An unknown side or generation -> MF_ERR_ARGUMENT before any HIP call; without factors,
+ * or with the kind OFF, MF_ERR_STATE.  The user solve works on any shard (rows of L are private); the item solve on a plan
+ * that does not hold all users -- a shard, a 2-D tile -- returns MF_ERR_UNSUPPORTED (an item's Gram matrix is a sum over all
+ * users), and so does mf_plan_iterate under ALS there.
+ * mf_plan_als_info: the rows of the side's last solve that were solved, kept because they have no entries, kept because they
+ * are not positive definite (zeros before the first solve).  Complete on return; any pointer may be NULL.
+ * mf_plan_describe appends als=ridge|ridge-count and als_form=<form>(chunk=<entries per gather chunk>) while the kind is not
+ * OFF.  The forms (MF_ALS_FORM=wg|wave: one 256-thread workgroup per row, any K; one wave per row, K <= 32; by default the
+ * wave form up to K = 16) give the same bits. */
+enum { MF_ALS_OFF = 0, MF_ALS_RIDGE = 1, MF_ALS_RIDGE_COUNT = 2 };
+int mf_plan_set_als(mf_plan *plan, int kind);
+int mf_plan_get_als(mf_plan *plan, int *kind);
+int mf_plan_als_solve(mf_plan *plan, int side, int other_generation);
+int mf_plan_als_info(mf_plan *plan, int side, int64_t *solved, int64_t *kept_empty, int64_t *kept_not_pd);
+/* level 1: pr->iters ALS iterations from the factors in L and R, the plan session above on a whole-problem plan (weighted
+ * when `weight` is given).  A bad kind, record or lambda, or NULL L / R -> MF_ERR_ARGUMENT before any HIP call. */
+int mf_backend_run_als(const mf_problem *p, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
+                       double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, int kind, int device);
 
 /* ---- Ranks of the held-out entries: where each held-out item lands in its user's recommendation order, for the plan's
  * current factors.  An extension (the reference ranks nothing), so the definition is this library's.  For held-out entry

@@ -54,6 +54,7 @@ HIP_SYMBOLS = [
     "mf_plan_set_bounds", "mf_plan_get_bounds", "mf_plan_project", "mf_plan_bounds_active", "mf_backend_run_bounded",
     "mf_plan_set_adaptive", "mf_plan_get_adaptive", "mf_plan_reset_adaptive", "mf_plan_adaptive_finish",
     "mf_plan_download_adaptive_state", "mf_plan_upload_adaptive_state", "mf_backend_run_adaptive",
+    "mf_plan_set_als", "mf_plan_get_als", "mf_plan_als_solve", "mf_plan_als_info", "mf_backend_run_als",
 ]
 HOST_SYMBOLS = [
     "mf_host_parse_strerror", "mf_host_parse_file", "mf_host_parse_buffer", "mf_host_free_problem",
@@ -109,6 +110,11 @@ class Adaptive(C.Structure):  # mf_adaptive
 MF_OPT_NONE, MF_OPT_ADAGRAD, MF_OPT_RMSPROP, MF_OPT_ADAM = 0, 1, 2, 3
 OPTIMIZERS = {"none": 0, "adagrad": 1, "rmsprop": 2, "adam": 3, None: 0, 0: 0, 1: 1, 2: 2, 3: 3}
 OPTIMIZER_NAMES = ("none", "adagrad", "rmsprop", "adam")
+
+# MF_ALS_*: the kinds of the ALS solver, by number and by name
+MF_ALS_OFF, MF_ALS_RIDGE, MF_ALS_RIDGE_COUNT = 0, 1, 2
+ALS_KINDS = {"off": 0, "ridge": 1, "ridge-count": 2, None: 0, 0: 0, 1: 1, 2: 2}
+ALS_KIND_NAMES = ("off", "ridge", "ridge-count")
 
 
 class Loss(C.Structure):  # mf_loss
@@ -248,6 +254,12 @@ def hip():
         lib.mf_plan_upload_adaptive_state.argtypes = [P, C.c_int, P, P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         lib.mf_backend_run_adaptive.argtypes = [C.POINTER(Problem), P, P, P, P, C.c_double, C.c_double, C.POINTER(Bounds), C.POINTER(Bounds),
                                                 C.POINTER(Adaptive), C.POINTER(Adaptive), C.c_int]
+        lib.mf_plan_set_als.argtypes = [P, C.c_int]
+        lib.mf_plan_get_als.argtypes = [P, C.POINTER(C.c_int)]
+        lib.mf_plan_als_solve.argtypes = [P, C.c_int, C.c_int]
+        lib.mf_plan_als_info.argtypes = [P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        lib.mf_backend_run_als.argtypes = [C.POINTER(Problem), P, P, P, P, C.c_double, C.c_double, C.POINTER(Bounds), C.POINTER(Bounds),
+                                           C.c_int, C.c_int]
         _hip = lib
     return _hip
 
@@ -582,6 +594,29 @@ def backend_run_adaptive(inst, L, R, adaptive_users=None, adaptive_items=None, b
 
 
 run_adaptive = backend_run_adaptive
+
+
+def backend_run_als(inst, L, R, kind="ridge", bounds_users=None, bounds_items=None, weight=None, lambda_users=0.0, lambda_items=None,
+                    iters=None, device=0, recommend=True):
+    """mf_backend_run_als: `iters` ALS iterations (kind "ridge" | "ridge-count") from the factors in L and R, with a lambda and
+    a box per side and optional per-entry weights.  L, R updated in place, returns best[users], or None with
+    recommend=False."""
+    p, keep = _problem(inst, iters)
+    w = None if weight is None else np.ascontiguousarray(weight, np.float64)
+    assert w is None or w.shape == (inst.nnz,)
+    li = lambda_users if lambda_items is None else lambda_items
+    bu, bit = _bounds_record(bounds_users), _bounds_record(bounds_items)
+    best = np.empty(inst.users, np.int32) if recommend else None
+    assert L.dtype == np.float64 and R.dtype == np.float64 and L.flags.c_contiguous and R.flags.c_contiguous
+    _check(hip().mf_backend_run_als(C.byref(p), None if w is None else w.ctypes.data, L.ctypes.data, R.ctypes.data,
+                                    best.ctypes.data if recommend else None, float(lambda_users), float(li),
+                                    None if bu is None else C.byref(bu), None if bit is None else C.byref(bit),
+                                    ALS_KINDS.get(kind, kind), device),
+           "mf_backend_run_als")
+    return best
+
+
+run_als = backend_run_als
 
 
 def bias_mean(val):
@@ -931,6 +966,28 @@ class Plan:
         """mf_plan_adaptive_finish: the side's next-generation buffer taken as g and finished in place: what a sharded caller
         runs on the summed side after its sum"""
         _check(hip().mf_plan_adaptive_finish(self._h, SIDES[side]), "mf_plan_adaptive_finish")
+
+    def set_als(self, kind):
+        """mf_plan_set_als: "ridge", "ridge-count", or "off" / None for the gradient step; while it is on, iterate() runs ALS
+        iterations (users against the current R, items against the new L, flip)"""
+        _check(hip().mf_plan_set_als(self._h, ALS_KINDS.get(kind, kind)), "mf_plan_set_als")
+
+    def als(self):
+        """mf_plan_get_als: the kind by name"""
+        k = C.c_int()
+        _check(hip().mf_plan_get_als(self._h, C.byref(k)), "mf_plan_get_als")
+        return ALS_KIND_NAMES[k.value]
+
+    def als_solve(self, side, other="current"):
+        """mf_plan_als_solve: every row of `side` solved against the other side's "current" or "next" buffer, into the side's
+        next buffer; only enqueues"""
+        _check(hip().mf_plan_als_solve(self._h, SIDES.get(side, side), GENERATIONS.get(other, other)), "mf_plan_als_solve")
+
+    def als_info(self, side):
+        """mf_plan_als_info: (solved, kept_empty, kept_not_pd) rows of the side's last solve"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(hip().mf_plan_als_info(self._h, SIDES.get(side, side), C.byref(a), C.byref(b), C.byref(c)), "mf_plan_als_info")
+        return a.value, b.value, c.value
 
     def _side_shape(self, side):
         return (self.items if SIDES[side] == 0 else self.user_count, self.feats)

@@ -34,6 +34,7 @@ struct mf_config {
 	int rec_split = -1;               // MF_RECOMMEND_SPLIT=0|n: item split of small recommendations off / n splits (-1: rule)
 	bool build_host = false;          // MF_BUILD=host: CSR/CSC bucketed on the host
 	bool os_dpp = true;               // MF_OS_DPP=0: ordered sums by plain v_add_f64 (no DPP broadcast)
+	int als_form = -1;                // MF_ALS_FORM=wg|wave: the ALS solve as one workgroup / one wave per row (-1: by K)
 	bool multi_force = false;         // MF_MULTI_FORCE=1: sharded path even with one shard
 	bool multi_rccl = false;          // MF_MULTI_REDUCE=rccl|peer
 	bool multi_threads = true;        // MF_MULTI_THREADS=0: all shards enqueued from the calling thread
@@ -70,6 +71,7 @@ struct mf_config {
 		if ((v = getenv("MF_RECOMMEND_SPLIT"))) c.rec_split = atoi(v);
 		c.build_host = eq(getenv("MF_BUILD"), "host");
 		c.os_dpp = !is0(getenv("MF_OS_DPP"));
+		if ((v = getenv("MF_ALS_FORM"))) c.als_form = eq(v, "wg") ? 0 : eq(v, "wave") ? 1 : -1;
 		c.multi_force = eq(getenv("MF_MULTI_FORCE"), "1");
 		c.multi_rccl = eq(getenv("MF_MULTI_REDUCE"), "rccl");
 		c.multi_threads = !is0(getenv("MF_MULTI_THREADS"));
@@ -101,6 +103,7 @@ struct mf_config {
 		if (rec_split >= 0) add("MF_RECOMMEND_SPLIT", std::to_string(rec_split));
 		if (build_host) add("MF_BUILD", "host");
 		if (!os_dpp) add("MF_OS_DPP", "0");
+		if (als_form >= 0) add("MF_ALS_FORM", als_form ? "wave" : "wg");
 		if (multi_force) add("MF_MULTI_FORCE", "1");
 		if (multi_rccl) add("MF_MULTI_REDUCE", "rccl");
 		if (!multi_threads) add("MF_MULTI_THREADS", "0");

@@ -365,6 +365,16 @@ int mf_plan_iterate(mf_plan *p, int iters)
 	if (!p || iters < 0) return MF_ERR_ARGUMENT;
 	if (!p->have_factors) return MF_ERR_STATE;
 	MF_HIP(hipSetDevice(p->device));
+	// ALS: the users against the current R, the items against the NEW L (Gauss-Seidel), the flip; eager launches, no graph
+	if (p->als_kind != MF_ALS_OFF) {
+		if (iters > 0 && (p->u0 != 0 || p->uc != p->users_total)) return MF_ERR_UNSUPPORTED;   // the item solve of a shard
+		for (int it = 0; it < iters; ++it) {
+			MF_TRY(launch_als(p, 1, 0));
+			MF_TRY(launch_als(p, 0, 1));
+			p->cur ^= 1;
+		}
+		return MF_OK;
+	}
 	// a momentum side at rest gets its history (X_prev = X_old) here: in front of every launch and outside the capture
 	if (iters > 0) {
 		MF_TRY(leave_rest(p, 0));
@@ -516,6 +526,7 @@ int mf_plan_set_momentum(mf_plan *p, double beta_users, double beta_items)
 	if (!p || !lambda_ok(beta_users) || !lambda_ok(beta_items)) return MF_ERR_ARGUMENT;   // finite and >= 0, like a weight
 	// not on an adaptive side: its X_new carries g, so there is no X_prev
 	if ((beta_users != 0.0 && adaptive_side(p, 1)) || (beta_items != 0.0 && adaptive_side(p, 0))) return MF_ERR_UNSUPPORTED;
+	if ((beta_users != 0.0 || beta_items != 0.0) && p->als_kind != MF_ALS_OFF) return MF_ERR_UNSUPPORTED;   // nor under ALS
 	// read at every launch (the graph path captures per call).  A side whose beta leaves 0 has maintained no history: it
 	// is at rest; a change between two non-zero values keeps the history
 	if (p->rule[1].beta == 0.0 && beta_users != 0.0) p->rule[1].at_rest = true;
@@ -645,6 +656,7 @@ int mf_plan_set_adaptive(mf_plan *p, int side, const mf_adaptive *rule)
 	if (!p || (side != 0 && side != 1) || !adaptive_ok(rule)) return MF_ERR_ARGUMENT;
 	const mf_adaptive o = adaptive_rule(rule);
 	if (o.kind != MF_OPT_NONE && p->rule[side].beta != 0.0) return MF_ERR_UNSUPPORTED;   // momentum came first
+	if (o.kind != MF_OPT_NONE && p->als_kind != MF_ALS_OFF) return MF_ERR_UNSUPPORTED;    // ... or ALS did
 	// read at every launch (the graph path captures per call).  A change of kind puts the side at rest; a change of the
 	// numbers alone keeps what it has accumulated
 	if (o.kind != p->rule[side].opt.kind) p->opt[side].rest = true;
@@ -722,6 +734,58 @@ int mf_plan_upload_adaptive_state(mf_plan *p, int side, const double *m, const d
 		MF_TRY(adaptive_set_record(p, side, p1 ? *p1 : rec.p1, p2 ? *p2 : rec.p2, steps ? (long long) *steps : rec.steps));
 	}
 	MF_HIP(hipStreamSynchronize(p->stream));
+	return MF_OK;
+}
+
+static bool als_kind_ok(int kind) { return kind == MF_ALS_OFF || kind == MF_ALS_RIDGE || kind == MF_ALS_RIDGE_COUNT; }
+
+int mf_plan_set_als(mf_plan *p, int kind)
+{
+	if (!p || !als_kind_ok(kind)) return MF_ERR_ARGUMENT;
+	if (kind != MF_ALS_OFF) {
+		if (p->K > mf::kAlsMaxK) return MF_ERR_UNSUPPORTED;   // the triangle of a row lives in LDS
+		// a solve has neither a previous step nor a gradient: momentum or an adaptive side came first
+		if (p->rule[0].beta != 0.0 || p->rule[1].beta != 0.0 || adaptive_any(p)) return MF_ERR_UNSUPPORTED;
+	}
+	// the counters exist from here on: a solve only enqueues and allocates nothing
+	if (kind != MF_ALS_OFF && !p->als_counts) {
+		MF_HIP(hipSetDevice(p->device));
+		MF_TRY(p->als_counts.alloc(6));
+		MF_HIP(hipMemsetAsync(p->als_counts.get(), 0, 6 * sizeof(unsigned long long), p->stream));
+	}
+	p->als_kind = kind;   // read at every launch
+	return MF_OK;
+}
+
+int mf_plan_get_als(mf_plan *p, int *kind)
+{
+	if (!p) return MF_ERR_ARGUMENT;
+	if (kind) *kind = p->als_kind;
+	return MF_OK;
+}
+
+int mf_plan_als_solve(mf_plan *p, int side, int other_generation)
+{
+	if (!p || (side != 0 && side != 1) || (other_generation != 0 && other_generation != 1)) return MF_ERR_ARGUMENT;
+	if (!p->have_factors || p->als_kind == MF_ALS_OFF) return MF_ERR_STATE;
+	// an item's Gram matrix is a sum over ALL users: a plan that holds a block of them (a shard, a 2-D tile) has a part of it
+	if (side == 0 && (p->u0 != 0 || p->uc != p->users_total)) return MF_ERR_UNSUPPORTED;
+	MF_HIP(hipSetDevice(p->device));
+	return launch_als(p, side, other_generation);
+}
+
+int mf_plan_als_info(mf_plan *p, int side, int64_t *solved, int64_t *kept_empty, int64_t *kept_not_pd)
+{
+	if (!p || (side != 0 && side != 1)) return MF_ERR_ARGUMENT;
+	unsigned long long c[3] = {0, 0, 0};
+	if (p->als_counts) {   // no solve yet: zeros
+		MF_HIP(hipSetDevice(p->device));
+		MF_HIP(hipMemcpyAsync(c, p->als_counts.get() + 3 * side, sizeof c, hipMemcpyDeviceToHost, p->stream));
+		MF_HIP(hipStreamSynchronize(p->stream));
+	}
+	if (solved) *solved = (int64_t) c[0];
+	if (kept_empty) *kept_empty = (int64_t) c[1];
+	if (kept_not_pd) *kept_not_pd = (int64_t) c[2];
 	return MF_OK;
 }
 
@@ -1046,6 +1110,11 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 		}
 		append(buf, buflen, " adaptive=%s/%s", sd[1], sd[0]);
 	}
+	// the solver of mf_plan_iterate when it is not the gradient step, and the form its solves launch
+	if (p->als_kind != MF_ALS_OFF) {
+		const AlsForm &form = kAlsForm[als_form(p->K, p->cfg.als_form)];
+		append(buf, buflen, " als=%s als_form=%s(chunk=%d)", p->als_kind == MF_ALS_RIDGE ? "ridge" : "ridge-count", form.name, form.nch);
+	}
 	// the environment switches this plan was created under, when any differs from its default (mf_config.hip.h)
 	const std::string cfg = p->cfg.describe();
 	if (!cfg.empty()) append(buf, buflen, " config{%s}", cfg.c_str());
@@ -1165,6 +1234,24 @@ int mf_backend_run_adaptive(const mf_problem *pr, const double *weight, double *
 
 // ---- biases on frozen columns: a ~ mu + b_user + b_item + l.r as the K = F + 2 product of
 //   L' = [ L | b_user | 1.0 ] (users' column F+1 frozen)  and  R' = [ R | 1.0 | b_item ] (items' column F frozen)
+// the ALS run: the gradient rule's alpha, betas and adaptive kinds have no part in it
+int mf_backend_run_als(const mf_problem *pr, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
+                       double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, int kind, int device)
+{
+	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !bounds_record_ok(bounds_users, pr->features) ||
+	    !bounds_record_ok(bounds_items, pr->features) || !als_kind_ok(kind))
+		return MF_ERR_ARGUMENT;
+	const RulePair rule = level1_rules(lambda_users, lambda_items, 0.0, 0.0, bounds_users, bounds_items);
+	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
+		p->rule[0] = rule[0], p->rule[1] = rule[1];
+		int rc = mf_plan_set_als(p, kind);
+		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
+		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
+		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
+		return rc;
+	}, weight);
+}
+
 int mf_backend_bias_mean(const double *val, int64_t n, double *mu)
 {
 	if (!mu || n < 0 || (n > 0 && !val)) return MF_ERR_ARGUMENT;

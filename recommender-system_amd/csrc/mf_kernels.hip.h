@@ -10,4 +10,5 @@
 #include "mf_similar.hip.h"
 #include "mf_loss.hip.h"
 #include "mf_adaptive.hip.h"
+#include "mf_als.hip.h"
 #include "mf_collective.hip.h"

@@ -571,6 +571,65 @@ int launch_es_iteration(mf_plan *p)
 	return MF_OK;
 }
 
+// ---- alternating least squares (mf_als.hip.h)
+
+// The form of an ALS solve at this K: one wave per row while a row's triangle is a few blocks per lane (K <= 16), one
+// workgroup per row above.  MF_ALS_FORM forces a form where it has this K; every form gives the same bits.
+AlsFormId als_form(int K, int forced)
+{
+	if (forced == kAlsWg) return kAlsWg;
+	if (forced == kAlsWave && K <= kAlsForm[kAlsWave].max_k) return kAlsWave;
+	return K <= 16 ? kAlsWave : kAlsWg;
+}
+
+// One solve of a side (0: items, 1: users) against the other side's current (0) or next (1) buffer, into the side's
+// next buffer: the counters zeroed, then one launch over the side's rows in its dispatch order -- the extreme rows of a
+// split side first, they are its longest.  The rule of the side is read here, at every launch.
+int launch_als(mf_plan *p, int side, int other_generation)
+{
+	const SweepSide &sd = p->side[side];
+	unsigned long long *counts = p->als_counts.get() + 3 * side;
+	MF_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(unsigned long long), p->stream));
+	if (sd.nrows <= 0) return MF_OK;
+	const AlsForm &form = kAlsForm[als_form(p->K, p->cfg.als_form)];
+	const int groups = mf::kAlsThreads / form.threads;
+	const int nb = (mf::als_blocks(p->K, form.bs) + form.threads - 1) / form.threads;
+	const AlsFn fn = form.fn[nb - 1];
+	const size_t lds = (size_t) groups * mf::als_group_doubles(p->K, form.bs, form.nch, p->weighted) * sizeof(double);
+	MF_HIP(raise_lds_limit((const void *) fn, lds));
+
+	const SideUpdate u = side_update(p, side, 1);
+	mf::AlsArgs a;
+	a.K = p->K;
+	a.ldx = side == 0 ? p->ldr : p->ldl;
+	a.ldy = side == 0 ? p->ldl : p->ldr;
+	a.frozen = u.frozen;
+	a.count_scaled = p->als_kind == MF_ALS_RIDGE_COUNT;
+	a.lambda = p->rule[side].lambda;
+	a.ptr = side == 0 ? p->csc_ptr : p->csr_ptr;
+	a.idx = side == 0 ? p->csc_idx : p->csr_idx;
+	a.val = side == 0 ? p->csc_val : p->csr_val;
+	a.wgt = !p->weighted ? nullptr : side == 0 ? p->csc_wgt.get() : p->csr_wgt.get();
+	a.X_old = side == 0 ? p->Rbuf[p->cur] : p->Lbuf[p->cur];
+	a.X_new = side == 0 ? p->Rbuf[p->cur ^ 1] : p->Lbuf[p->cur ^ 1];
+	a.Y = side == 0 ? p->Lbuf[p->cur ^ other_generation] : p->Rbuf[p->cur ^ other_generation];
+	a.counts = counts;
+	a.box = u.box;
+	auto launch = [&](const int *rowlist, int nrows) {
+		if (nrows <= 0) return MF_OK;
+		a.rowlist = rowlist;
+		a.nrows = nrows;
+		hipLaunchKernelGGL(fn, dim3((nrows + groups - 1) / groups), dim3(mf::kAlsThreads), lds, p->stream, a);
+		MF_HIP(hipGetLastError());
+		return MF_OK;
+	};
+	if (sd.n_long > 0) {
+		MF_TRY(launch(sd.long_rows, sd.n_long));
+		return launch(sd.short_rows, sd.n_short);
+	}
+	return launch(sd.lpt ? sd.short_rows.get() : nullptr, sd.nrows);
+}
+
 int drain_timing(mf_plan *p)
 {
 	for (auto &t : p->timed) {

@@ -7,6 +7,7 @@ namespace {
 
 using SweepFn = void (*)(mf::SweepArgs);
 using LossFn = void (*)(mf::LossArgs);
+using AlsFn = void (*)(mf::AlsArgs);
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is per FUNCTION, not per plan: two live plans that share a kernel
 // instance (the run-time-K forms) but need different tile sizes must never lower each other's limit.
@@ -237,6 +238,21 @@ struct AdaptiveState {
 	bool rest = true;
 };
 
+// The forms of the ALS solve (mf_als.hip.h): how many threads own a row, the side of a register block, the entries of a
+// gather chunk, the widest K, and the instances by blocks per thread (NB = 1, 2, 3).  als_form (mf_launch.hip.h) picks one.
+enum AlsFormId { kAlsWg = 0, kAlsWave = 1, kAlsForms = 2 };
+struct AlsForm {
+	const char *name;
+	int threads, bs, nch, max_k;
+	AlsFn fn[3];
+};
+const AlsForm kAlsForm[kAlsForms] = {
+    {"wg", mf::kAlsThreads, 4, mf::kAlsChunkWg, mf::kAlsMaxK,
+     {mf::als_kernel<mf::kAlsThreads, 4, 1>, mf::als_kernel<mf::kAlsThreads, 4, 2>, mf::als_kernel<mf::kAlsThreads, 4, 3>}},
+    {"wave", mf::kWave, 2, mf::kAlsChunkWave, mf::kAlsWaveMaxK,
+     {mf::als_kernel<mf::kWave, 2, 1>, mf::als_kernel<mf::kWave, 2, 2>, mf::als_kernel<mf::kWave, 2, 3>}},
+};
+
 }  // namespace
 
 struct mf_plan {
@@ -248,6 +264,10 @@ struct mf_plan {
 	double alpha = 0.0;
 	SideRule rule[2];   // the update rule per side (0 = items, 1 = users); side_update (mf_launch.hip.h) reads it at every launch
 	AdaptiveState opt[2];   // the accumulators of a side whose rule has an adaptive kind
+	// alternating least squares (mf_als.hip.h): the kind (mf_plan_set_als; OFF: the plan of every other section) and the
+	// three row counts of each side's last solve, [side][solved, kept_empty, kept_not_pd], allocated on first use
+	int als_kind = MF_ALS_OFF;
+	dev_buf<unsigned long long> als_counts;
 	int flags = 0;
 
 	hipStream_t own_stream = nullptr;

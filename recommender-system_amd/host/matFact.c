@@ -22,11 +22,11 @@
 
 /* Every MATFACT_* variable the program reads: the mode options in the order they are examined, the path options, and the
  * accessories, which take part in no rule. */
-enum { V_TOPN, V_LOSS, V_HELDOUT, V_RANK, V_SIMILAR, V_SIMILAR_OUT, V_LAMBDA, V_BIAS, V_MOMENTUM, V_WEIGHTS, V_BOUNDS, V_OPTIMIZER, V_DEVICES, V_MATS, V_CHECKPOINT, V_RESUME,
+enum { V_TOPN, V_LOSS, V_HELDOUT, V_RANK, V_SIMILAR, V_SIMILAR_OUT, V_LAMBDA, V_BIAS, V_MOMENTUM, V_WEIGHTS, V_BOUNDS, V_OPTIMIZER, V_SOLVER, V_DEVICES, V_MATS, V_CHECKPOINT, V_RESUME,
        V_DEVICE, V_MATS_ITERS, V_CHECKPOINT_EVERY, V_CACHE, V_TIMING, V_COUNT };
 static const char *const cli_names[V_COUNT] = {
 	"MATFACT_TOPN", "MATFACT_LOSS", "MATFACT_HELDOUT", "MATFACT_RANK", "MATFACT_SIMILAR", "MATFACT_SIMILAR_OUT", "MATFACT_LAMBDA",
-	"MATFACT_BIAS", "MATFACT_MOMENTUM", "MATFACT_WEIGHTS", "MATFACT_BOUNDS", "MATFACT_OPTIMIZER", "MATFACT_DEVICES", "MATFACT_MATS", "MATFACT_CHECKPOINT", "MATFACT_RESUME", "MATFACT_DEVICE",
+	"MATFACT_BIAS", "MATFACT_MOMENTUM", "MATFACT_WEIGHTS", "MATFACT_BOUNDS", "MATFACT_OPTIMIZER", "MATFACT_SOLVER", "MATFACT_DEVICES", "MATFACT_MATS", "MATFACT_CHECKPOINT", "MATFACT_RESUME", "MATFACT_DEVICE",
 	"MATFACT_MATS_ITERS", "MATFACT_CHECKPOINT_EVERY", "MATFACT_CACHE", "MATFACT_TIMING"};
 
 struct cli_options {
@@ -50,6 +50,8 @@ struct cli_options {
 	double lo_users, hi_users, lo_items, hi_items;   /* factors); one pair for both sides or users then items; the bias columns stay free */
 	int adaptive;         /* MATFACT_OPTIMIZER=adam,eta[,beta1,beta2[,eps]] | rmsprop,eta[,rho[,eps]] | adagrad,eta[,eps]: a per-element */
 	mf_adaptive optimizer;   /* adaptive step on both sides (eta, eps > 0; beta1, beta2, rho in [0, 1); defaults 0.9, 0.999, 1e-8) */
+	int als;              /* MATFACT_SOLVER=als[,count]: the file's iters as ALS iterations (mf_plan_set_als: MF_ALS_RIDGE, or with */
+	                      /* `count` MF_ALS_RIDGE_COUNT) from the reference's initialisation; lambda is MATFACT_LAMBDA's, default 0 */
 	int device;           /* MATFACT_DEVICE=n: the GPU of a single-GPU run, default 0 */
 	int devs[16], ndev;   /* MATFACT_DEVICES=0,1,...: row-shard over these GPUs of the process, at most 16 */
 	const char *devices_error;   /* a non-number in it: said only where that path runs, after the input was read, as ever */
@@ -133,6 +135,9 @@ static const char *cli_value(int v, const char *s, struct cli_options *o)
 		              a->beta2 >= 0.0 && a->beta2 < 1.0;
 		return o->adaptive ? NULL : bad;
 	}
+	case V_SOLVER:
+		o->als = !strcmp(s, "als") ? MF_ALS_RIDGE : !strcmp(s, "als,count") ? MF_ALS_RIDGE_COUNT : MF_ALS_OFF;
+		return o->als ? NULL : "MATFACT_SOLVER: expected als or als,count.";
 	}
 	return NULL;   /* MATFACT_HELDOUT, MATFACT_SIMILAR_OUT, MATFACT_WEIGHTS: any text */
 }
@@ -166,6 +171,7 @@ static const struct cli_rule cli_clashes[] = {
 	{V_WEIGHTS, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_WEIGHTS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
 	{V_BOUNDS, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_BOUNDS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
 	{V_OPTIMIZER, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR) | BIT(V_MOMENTUM), "MATFACT_OPTIMIZER works on the single-GPU path only and not with momentum: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN, MATFACT_SIMILAR and MATFACT_MOMENTUM."},
+	{V_SOLVER, PATHS | BIT(V_SIMILAR) | BIT(V_MOMENTUM) | BIT(V_OPTIMIZER), "MATFACT_SOLVER works on the single-GPU path only and not with momentum or an optimizer: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_SIMILAR, MATFACT_MOMENTUM and MATFACT_OPTIMIZER."},
 };
 
 /* Fills `o` from the environment -- it opens no file and makes no GPU call -- and returns NULL, or the message to die with. */
@@ -176,7 +182,7 @@ static const char *cli_parse(struct cli_options *o)
 	for (int v = 0; v < V_COUNT; v++)
 		if ((o->value[v] = getenv(cli_names[v])) != NULL) set |= BIT(v);
 	const unsigned usable = o->value[V_SIMILAR_OUT] && !*o->value[V_SIMILAR_OUT] ? set & ~BIT(V_SIMILAR_OUT) : set;
-	for (int v = V_TOPN; v <= V_OPTIMIZER; v++) {
+	for (int v = V_TOPN; v <= V_SOLVER; v++) {
 		const char *message = set & BIT(v) ? cli_value(v, o->value[v], o) : NULL;
 		if (message) return message;
 		if (!(set & BIT(v))) continue;
@@ -373,7 +379,7 @@ static int write_similar(mf_plan *plan, const struct cli_options *o, int32_t ite
 /* Every mode that needs a resident plan, as stages over one session: configure, exactly one loop, the reports on stderr,
  * the outputs.  `d` is the open dump of MATFACT_MATS or NULL; `done` counts the iterations a checkpoint already holds. */
 static int run_session(const struct cli_options *o, const mf_problem *p, const mf_problem *held, const mf_problem *wts, double *L, double *R,
-                       int32_t *best, int done, const struct dump *d)
+                       int32_t *best, int32_t *topn_items, int done, const struct dump *d)
 {
 	struct session s;
 	const int cap = o->loss_every ? p->iters / o->loss_every + 2 : 0;
@@ -395,6 +401,8 @@ static int run_session(const struct cli_options *o, const mf_problem *p, const m
 	/* the adaptive step, the same rule on both sides */
 	if (rc == MF_OK && o->adaptive) rc = mf_plan_set_adaptive(s.plan, 1, &o->optimizer);
 	if (rc == MF_OK && o->adaptive) rc = mf_plan_set_adaptive(s.plan, 0, &o->optimizer);
+	/* the solver: ALS in place of the gradient step */
+	if (rc == MF_OK && o->als) rc = mf_plan_set_als(s.plan, o->als);
 	/* loop */
 	if (rc == MF_OK) {
 		if (o->loss_every) rc = mf_plan_iterate_monitored(s.plan, p->iters, o->loss_every, o->loss_tol, trace, cap, &points, &done);
@@ -414,7 +422,7 @@ static int run_session(const struct cli_options *o, const mf_problem *p, const m
 	if (rc == MF_OK && o->regularised && o->loss_every) rc = report_penalty(s.plan, o);
 	if (rc == MF_OK && o->rank_cutoff) rc = report_ranks(s.plan, o->rank_cutoff, s.hrow, held->nnz);
 	/* outputs */
-	if (rc == MF_OK) rc = mf_plan_recommend(s.plan, best);
+	if (rc == MF_OK) rc = o->topn ? mf_plan_recommend_topn(s.plan, o->topn, topn_items, NULL) : mf_plan_recommend(s.plan, best);   /* MATFACT_TOPN comes here with MATFACT_SOLVER only */
 	if (rc == MF_OK && o->similar) rc = write_similar(s.plan, o, p->items);
 	if (rc == MF_OK && checkpointed) rc = mf_plan_download_factors(s.plan, L, R);
 	session_close(&s);
@@ -437,7 +445,7 @@ static int run_with_mats(const struct cli_options *o, const mf_problem *p, doubl
 	if (rc == MF_OK) {
 		for (int64_t n = 0; n < p->nnz; n++) d.B[(size_t) p->entries[n].row * p->items + p->entries[n].col] = p->entries[n].value;
 		mats_matrix(d.f, "Initial matrix A", d.B, p->users, p->items, 0);
-		rc = run_session(o, p, NULL, NULL, L, R, best, 0, &d);
+		rc = run_session(o, p, NULL, NULL, L, R, best, NULL, 0, &d);
 	}
 	free(d.B);
 	if (d.f && fclose(d.f) == EOF && rc == MF_OK) rc = MF_ERR_ARGUMENT;
@@ -510,11 +518,11 @@ int main(int argc, char **argv)
 	/*
 	 * The rules of cli_parse leave mode options or path options, never both.  Among the path options the priority is silent:
 	 * MATFACT_CHECKPOINT / MATFACT_RESUME win over MATFACT_MATS, which wins over MATFACT_DEVICES (and MATFACT_RESUME is read
-	 * above whenever it is set).  MATFACT_LOSS, MATFACT_SIMILAR, MATFACT_WEIGHTS, MATFACT_BOUNDS, MATFACT_OPTIMIZER, MATFACT_BIAS with MATFACT_MOMENTUM, the checkpoints and the dump need a resident plan and run as
+	 * above whenever it is set).  MATFACT_LOSS, MATFACT_SIMILAR, MATFACT_WEIGHTS, MATFACT_BOUNDS, MATFACT_OPTIMIZER, MATFACT_SOLVER, MATFACT_BIAS with MATFACT_MOMENTUM, the checkpoints and the dump need a resident plan and run as
 	 * a session, which splits the entries once; the rest goes through the level-1 calls, which take the entries as they are.
 	 */
-	if (o.loss_every || o.similar || have_wts || o.bounded || o.adaptive || o.value[V_CHECKPOINT] || o.value[V_RESUME] || (o.momentum && o.biased)) {
-		rc = run_session(&o, &prob, have_held ? &held : NULL, have_wts ? &wts : NULL, L, R, best, start_iter, NULL);
+	if (o.loss_every || o.similar || have_wts || o.bounded || o.adaptive || o.als || o.value[V_CHECKPOINT] || o.value[V_RESUME] || (o.momentum && o.biased)) {
+		rc = run_session(&o, &prob, have_held ? &held : NULL, have_wts ? &wts : NULL, L, R, best, topn_items, start_iter, NULL);
 	} else if (o.biased) {
 		/* biases start at 0.0; L and R took the reference's random() stream for K = F above */
 		double mu = 0.0;
