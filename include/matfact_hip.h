@@ -220,14 +220,15 @@ void mf_plan_destroy(mf_plan *plan);
  * buffers) needs no host synchronisation between that work and the plan's (tests/test_stream_order.py holds every line
  * below on a stream that is busy when the library is called).
  *   - Entry points that only ENQUEUE and return: mf_plan_iterate (and mf_plan_iterate_monitored between its evaluation
- *     points), mf_plan_sweep_items, mf_plan_sweep_users, mf_plan_sweep_users_seeded, mf_plan_project and mf_plan_als_solve.  What they
+ *     points), mf_plan_sweep_items, mf_plan_sweep_users, mf_plan_sweep_users_seeded, mf_plan_project, mf_plan_als_solve and
+ *     mf_plan_gram without a host pointer.  What they
  *     write may be read by work enqueued on the stream after the call returns, or by the host after
  *     mf_plan_synchronize.  A HIP graph that mf_plan_iterate builds is captured on and replayed into this stream.
  *   - Host only, no device work: mf_plan_flip, the setters and getters of the update rule, the pointer and pitch
  *     queries, mf_plan_describe.  A setter holds from the next launch that is enqueued.
  *   - COMPLETE ON RETURN (they enqueue behind whatever the stream holds and wait for it): everything that returns data
  *     to the host -- mf_plan_download_*, mf_plan_recommend*, mf_plan_rank_heldout, mf_plan_similar_items, mf_plan_loss,
- *     mf_plan_penalty, mf_plan_weight_total, mf_plan_bounds_active, mf_plan_als_info, mf_plan_predict, mf_plan_timing_read, an evaluation
+ *     mf_plan_penalty, mf_plan_weight_total, mf_plan_bounds_active, mf_plan_als_info, mf_plan_gram with a host pointer, mf_plan_implicit_objective, mf_plan_predict, mf_plan_timing_read, an evaluation
  *     point of mf_plan_iterate_monitored --, mf_plan_upload_factors, mf_plan_upload_previous, mf_plan_set_heldout,
  *     mf_plan_synchronize, mf_plan_create*, and mf_plan_destroy, which waits for the stream before it frees anything:
  *     caller-owned buffers hold the results of all enqueued work when it returns.
@@ -708,6 +709,71 @@ int mf_plan_als_info(mf_plan *plan, int side, int64_t *solved, int64_t *kept_emp
  * when `weight` is given).  A bad kind, record or lambda, or NULL L / R -> MF_ERR_ARGUMENT before any HIP call. */
 int mf_backend_run_als(const mf_problem *p, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
                        double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, int kind, int device);
+
+/* ---- Implicit feedback (Hu, Koren, Volinsky 2008): every user x item pair counts.  A pair that is not an entry is a 0.0 at
+ * confidence 1; entry n is its value a_n at confidence c_n = 1 + conf * w_n (w_n = 1 on a plan without weights).  The model is
+ * this library's definition in every rounding: FP64, every operation rounded once, nothing fused, sqrt and / correctly
+ * rounded, no matrix-core instruction.  Three parts: the Gram matrix of a whole side, the solve, the objective.
+ *
+ * mf_plan_gram(plan, side, generation, triangle): S = X^T X over ALL rows of X = the side's current (generation 0) or next (1)
+ * buffer -- on a shard the plan's own block of the users.  The result is the lower triangle S[p][q], p >= q, packed row by row
+ * (S[p][q] at p (p + 1) / 2 + q), K (K + 1) / 2 doubles.  Order of the sum: the rows are cut into blocks of MF_LOSS_BLOCK
+ * consecutive rows counted from row 0 of the plan's buffer; T_b[p][q] starts at 0.0 and takes T = T + (x_i[p] * x_i[q]) for i
+ * ascending inside block b; S[p][q] is the T_b added in ascending b from 0.0.  A row without entries counts like any other;
+ * the padding of a row is never read.  NaN, infinities and signed zeros follow IEEE 754.  The result does not depend on the
+ * grid or on any switch.  triangle == NULL: the call only enqueues and S stays in a plan-owned buffer (allocated on first
+ * use, with blocks x K (K + 1) / 2 doubles of partial sums); otherwise the call is complete on return.  No factors ->
+ * MF_ERR_STATE; an unknown side or generation -> MF_ERR_ARGUMENT before any HIP call; K > 128 -> MF_ERR_UNSUPPORTED.
+ *
+ * The solve: mf_plan_set_als(plan, MF_ALS_IMPLICIT).  (The kind's number is 4: 3 stays an unknown kind.)  Under it
+ * mf_plan_als_solve(plan, side, other_generation) first enqueues the Gram S of Y = the other side in that generation, then
+ * solves every row of the side by steps 1-10 of the ALS definition above with these changes:
+ *    1, 2. e_n = conf * w_n on a weighted plan and e_n = conf otherwise;  c_n = 1.0 + e_n;  ye_n[q] = y_n[q] * e_n;
+ *          ac_n = a_n * c_n.  A frozen column on the solved side is REFUSED: MF_ERR_UNSUPPORTED from mf_plan_als_solve and from
+ *          mf_plan_iterate*, checked at launch, before any HIP call -- the all-pairs term of a frozen column needs a correction
+ *          (the column's share of S would have to move to the right-hand side) that this library does not define.
+ *    3.    G[p][q] starts at S[p][q], not at 0.0; then G[p][q] = G[p][q] + (y_n[p] * ye_n[q]) for n ascending.
+ *    4.    b[p] starts at 0.0; then b[p] = b[p] + (ac_n * y_n[p]) for n ascending.
+ *    5.    ridge = lambda_side.
+ *    7-10. unchanged: Cholesky, the two solves, the box, the counters.
+ * A row WITHOUT ENTRIES is solved like any other: its sums are empty, G = S + ridge and b = 0, the chain yields +0.0 in every
+ * column, then the box applies (lo under a positive lo).  That is the model's exact minimiser for a cold row.  It is counted
+ * as solved or as not positive definite; kept_empty is 0 under this kind.  A NaN in Y makes S NaN: every row is then not
+ * positive definite and keeps X_old's bits.
+ * conf: mf_plan_set_confidence, default 1.0, read at every launch; not finite or < 0 -> MF_ERR_ARGUMENT, nothing changes.
+ * One iteration of mf_plan_iterate and of mf_plan_iterate_monitored under this kind is  gram(items, current);
+ * als_solve(users, 0);  gram(users, next);  als_solve(items, 1);  flip  -- eager launches on the plan's stream.  Both forms
+ * (MF_ALS_FORM) give the same bits; the LDS of a row is that of a weighted plan's (two tiles, y and ye).  As under the other
+ * kinds: the item solve on a shard or a 2-D tile is MF_ERR_UNSUPPORTED, momentum and adaptive sides are refused, K > 128 is
+ * MF_ERR_UNSUPPORTED.  mf_backend_run_als takes the explicit kinds only.  mf_plan_describe appends
+ * als=implicit conf=<%.17g> als_form=<form>(chunk=<entries>).
+ *
+ * The objective: mf_plan_implicit_objective fills {all_sq, observed, count} for the current factors;
+ *   objective = all_sq + observed + lambda_users * users_sq + lambda_items * items_sq
+ * with mf_plan_penalty's norms, in whatever order the caller chooses.
+ *   all_sq   = sum over ALL pairs of (l_u . r_i)^2 = <L^T L, R^T R>: the two Grams of the current factors (SL of the users, SR of
+ *              the items), then on the host t = 0.0 and t = t + (SL[p][q] * SR[p][q]) over the full K x K matrices, p ascending
+ *              then q ascending, the upper triangle read through symmetry.  mf_backend_gram_dot is that sum (plain C++).
+ *   observed = what the entries add to it: per training entry p_n = mf_plan_predict's bits, d_n = a_n - p_n,
+ *              q_n = (c_n * (d_n * d_n)) - (p_n * p_n), c_n as in the solve; row sums and block totals by steps 3-4 of the loss.
+ *   count    = the training entries.
+ * Complete on return; works with any kind set.  No factors -> MF_ERR_STATE; K > 128 -> MF_ERR_UNSUPPORTED.  On a shard both
+ * parts are those of the plan's own users. */
+enum { MF_ALS_IMPLICIT = 4 };
+typedef struct mf_implicit_objective {
+	double all_sq, observed;
+	int64_t count;
+} mf_implicit_objective;
+int mf_plan_gram(mf_plan *plan, int side, int generation, double *triangle);
+int mf_plan_set_confidence(mf_plan *plan, double conf);
+int mf_plan_get_confidence(mf_plan *plan, double *conf);
+int mf_plan_implicit_objective(mf_plan *plan, mf_implicit_objective *out);
+/* left, right: packed lower triangles of two symmetric K x K matrices (plain C++, no HIP call: works without a GPU) */
+int mf_backend_gram_dot(const double *left, const double *right, int32_t features, double *out);
+/* level 1: mf_backend_run_als under MF_ALS_IMPLICIT with the confidence `conf`.  A bad record, lambda or conf, or NULL L / R ->
+ * MF_ERR_ARGUMENT before any HIP call. */
+int mf_backend_run_implicit(const mf_problem *p, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
+                            double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, double conf, int device);
 
 /* ---- Ranks of the held-out entries: where each held-out item lands in its user's recommendation order, for the plan's
  * current factors.  An extension (the reference ranks nothing), so the definition is this library's.  For held-out entry

@@ -55,6 +55,8 @@ HIP_SYMBOLS = [
     "mf_plan_set_adaptive", "mf_plan_get_adaptive", "mf_plan_reset_adaptive", "mf_plan_adaptive_finish",
     "mf_plan_download_adaptive_state", "mf_plan_upload_adaptive_state", "mf_backend_run_adaptive",
     "mf_plan_set_als", "mf_plan_get_als", "mf_plan_als_solve", "mf_plan_als_info", "mf_backend_run_als",
+    "mf_plan_gram", "mf_plan_set_confidence", "mf_plan_get_confidence", "mf_plan_implicit_objective", "mf_backend_gram_dot",
+    "mf_backend_run_implicit",
 ]
 HOST_SYMBOLS = [
     "mf_host_parse_strerror", "mf_host_parse_file", "mf_host_parse_buffer", "mf_host_free_problem",
@@ -113,8 +115,13 @@ OPTIMIZER_NAMES = ("none", "adagrad", "rmsprop", "adam")
 
 # MF_ALS_*: the kinds of the ALS solver, by number and by name
 MF_ALS_OFF, MF_ALS_RIDGE, MF_ALS_RIDGE_COUNT = 0, 1, 2
-ALS_KINDS = {"off": 0, "ridge": 1, "ridge-count": 2, None: 0, 0: 0, 1: 1, 2: 2}
-ALS_KIND_NAMES = ("off", "ridge", "ridge-count")
+MF_ALS_IMPLICIT = 4   # 3 is not a kind
+ALS_KINDS = {"off": 0, "ridge": 1, "ridge-count": 2, "implicit": 4, None: 0, 0: 0, 1: 1, 2: 2, 4: 4}
+ALS_KIND_NAMES = ("off", "ridge", "ridge-count", None, "implicit")
+
+
+class ImplicitObjective(C.Structure):  # mf_implicit_objective
+    _fields_ = [("all_sq", C.c_double), ("observed", C.c_double), ("count", C.c_int64)]
 
 
 class Loss(C.Structure):  # mf_loss
@@ -260,6 +267,13 @@ def hip():
         lib.mf_plan_als_info.argtypes = [P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         lib.mf_backend_run_als.argtypes = [C.POINTER(Problem), P, P, P, P, C.c_double, C.c_double, C.POINTER(Bounds), C.POINTER(Bounds),
                                            C.c_int, C.c_int]
+        lib.mf_plan_gram.argtypes = [P, C.c_int, C.c_int, P]
+        lib.mf_plan_set_confidence.argtypes = [P, C.c_double]
+        lib.mf_plan_get_confidence.argtypes = [P, C.POINTER(C.c_double)]
+        lib.mf_plan_implicit_objective.argtypes = [P, C.POINTER(ImplicitObjective)]
+        lib.mf_backend_gram_dot.argtypes = [P, P, C.c_int32, C.POINTER(C.c_double)]
+        lib.mf_backend_run_implicit.argtypes = [C.POINTER(Problem), P, P, P, P, C.c_double, C.c_double, C.POINTER(Bounds),
+                                                C.POINTER(Bounds), C.c_double, C.c_int]
         _hip = lib
     return _hip
 
@@ -619,6 +633,40 @@ def backend_run_als(inst, L, R, kind="ridge", bounds_users=None, bounds_items=No
 run_als = backend_run_als
 
 
+def backend_run_implicit(inst, L, R, conf=1.0, bounds_users=None, bounds_items=None, weight=None, lambda_users=0.0, lambda_items=None,
+                         iters=None, device=0, recommend=True):
+    """mf_backend_run_implicit: `iters` implicit-feedback ALS iterations at confidence 1 + conf * w from the factors in L and R,
+    with a lambda and a box per side and optional per-entry weights.  L, R updated in place, returns best[users], or None
+    with recommend=False."""
+    p, keep = _problem(inst, iters)
+    w = None if weight is None else np.ascontiguousarray(weight, np.float64)
+    assert w is None or w.shape == (inst.nnz,)
+    li = lambda_users if lambda_items is None else lambda_items
+    bu, bit = _bounds_record(bounds_users), _bounds_record(bounds_items)
+    best = np.empty(inst.users, np.int32) if recommend else None
+    assert L.dtype == np.float64 and R.dtype == np.float64 and L.flags.c_contiguous and R.flags.c_contiguous
+    _check(hip().mf_backend_run_implicit(C.byref(p), None if w is None else w.ctypes.data, L.ctypes.data, R.ctypes.data,
+                                         best.ctypes.data if recommend else None, float(lambda_users), float(li),
+                                         None if bu is None else C.byref(bu), None if bit is None else C.byref(bit),
+                                         float(conf), device),
+           "mf_backend_run_implicit")
+    return best
+
+
+run_implicit = backend_run_implicit
+
+
+def gram_dot(left, right):
+    """mf_backend_gram_dot: the sum of the elementwise products of two symmetric K x K matrices given as packed lower triangles,
+    over the full matrices, p ascending then q ascending, from 0.0"""
+    left, right = np.ascontiguousarray(left, np.float64), np.ascontiguousarray(right, np.float64)
+    K = int((np.sqrt(8 * left.size + 1) - 1) // 2)
+    assert left.shape == right.shape == (K * (K + 1) // 2,)
+    out = C.c_double()
+    _check(hip().mf_backend_gram_dot(left.ctypes.data, right.ctypes.data, K, C.byref(out)), "mf_backend_gram_dot")
+    return out.value
+
+
 def bias_mean(val):
     """mf_backend_bias_mean: the mean of `val` summed in the given order from 0.0; 0.0 for an empty array."""
     v = np.ascontiguousarray(val, np.float64)
@@ -968,8 +1016,8 @@ class Plan:
         _check(hip().mf_plan_adaptive_finish(self._h, SIDES[side]), "mf_plan_adaptive_finish")
 
     def set_als(self, kind):
-        """mf_plan_set_als: "ridge", "ridge-count", or "off" / None for the gradient step; while it is on, iterate() runs ALS
-        iterations (users against the current R, items against the new L, flip)"""
+        """mf_plan_set_als: "ridge", "ridge-count", "implicit", or "off" / None for the gradient step; while it is on,
+        iterate() runs ALS iterations (users against the current R, items against the new L, flip)"""
         _check(hip().mf_plan_set_als(self._h, ALS_KINDS.get(kind, kind)), "mf_plan_set_als")
 
     def als(self):
@@ -988,6 +1036,30 @@ class Plan:
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
         _check(hip().mf_plan_als_info(self._h, SIDES.get(side, side), C.byref(a), C.byref(b), C.byref(c)), "mf_plan_als_info")
         return a.value, b.value, c.value
+
+    def set_confidence(self, conf):
+        """mf_plan_set_confidence: the scale of the implicit kind's confidences c = 1 + conf * w; read at every launch"""
+        _check(hip().mf_plan_set_confidence(self._h, float(conf)), "mf_plan_set_confidence")
+
+    def confidence(self):
+        """mf_plan_get_confidence"""
+        c = C.c_double()
+        _check(hip().mf_plan_get_confidence(self._h, C.byref(c)), "mf_plan_get_confidence")
+        return c.value
+
+    def gram(self, side, generation="current", download=True):
+        """mf_plan_gram: X^T X over all rows of the side's "current" or "next" buffer as a packed lower triangle (row by row);
+        download=False only enqueues and returns None"""
+        tri = np.empty(self.feats * (self.feats + 1) // 2, np.float64) if download else None
+        _check(hip().mf_plan_gram(self._h, SIDES.get(side, side), GENERATIONS.get(generation, generation),
+                                  tri.ctypes.data if download else None), "mf_plan_gram")
+        return tri
+
+    def implicit_objective(self):
+        """mf_plan_implicit_objective: (all_sq, observed, count) of the current factors"""
+        o = ImplicitObjective()
+        _check(hip().mf_plan_implicit_objective(self._h, C.byref(o)), "mf_plan_implicit_objective")
+        return o.all_sq, o.observed, o.count
 
     def _side_shape(self, side):
         return (self.items if SIDES[side] == 0 else self.user_count, self.feats)

@@ -80,16 +80,31 @@ __device__ __forceinline__ void als_sync()
 
 __device__ __forceinline__ int als_tri(int p, int q) { return p * (p + 1) / 2 + q; }
 
-template <int THREADS, int BS, int NB>
-__global__ void __launch_bounds__(kAlsThreads) als_kernel(AlsArgs a)
+// What the implicit instances take beside AlsArgs (mf_plan_set_als: MF_ALS_IMPLICIT): the Gram of the whole other side
+// (mf_gram.hip.h), a packed lower triangle, and the confidence scale.
+struct AlsImplicit {
+	const double *__restrict__ S;
+	double conf;
+};
+__device__ __forceinline__ AlsImplicit als_implicit_of() { return AlsImplicit{nullptr, 0.0}; }
+__device__ __forceinline__ AlsImplicit als_implicit_of(AlsImplicit im) { return im; }
+
+// als_kernel<THREADS, BS, NB>(AlsArgs) is the explicit solve; als_kernel<THREADS, BS, NB, AlsImplicit>(AlsArgs, AlsImplicit) the
+// implicit one: the same body with steps 1-5 changed as the header states them -- e_n = conf * w_n (conf without weights) is
+// what the second tile is scaled by, a_n goes in as a_n * (1.0 + e_n), the triangle starts at S where it otherwise starts at
+// 0.0, b sums against y_n, not ye_n, and a row without entries is solved like any other (its sums are empty).  No frozen
+// column there: the launch refuses it.
+template <int THREADS, int BS, int NB, class... IM>
+__global__ void __launch_bounds__(kAlsThreads) als_kernel(AlsArgs a, IM... im)
 {
+	constexpr bool IMPLICIT = sizeof...(IM) == 1;
 	constexpr int kGroups = kAlsThreads / THREADS;
 	constexpr int NCH = THREADS == kAlsThreads ? kAlsChunkWg : kAlsChunkWave;
 	constexpr int TD = THREADS == kAlsThreads ? 16 : 8;   // the trailing update walks the triangle as TD x TD threads
 	extern __shared__ double als_lds[];
 
 	const int K = a.K, Kp = als_padded_k(K, BS);
-	const bool weighted = a.wgt != nullptr;
+	const bool weighted = IMPLICIT || a.wgt != nullptr;   // the implicit solve always keeps two tiles, y and ye
 	const int grp = (int) threadIdx.x / THREADS, tid = (int) threadIdx.x % THREADS;
 	const int slot = (int) blockIdx.x * kGroups + grp;
 	if (slot >= a.nrows) return;   // a whole group: the one-wave form has no workgroup barrier, the other one row per workgroup
@@ -106,14 +121,16 @@ __global__ void __launch_bounds__(kAlsThreads) als_kernel(AlsArgs a)
 	double *xs = zs + K;
 
 	const int beg = a.ptr[r], cnt = a.ptr[r + 1] - beg;
-	const int f = a.frozen;
+	const int f = IMPLICIT ? -1 : a.frozen;
 	const size_t xrow = (size_t) r * a.ldx;
 	const double xold = tid < K ? a.X_old[xrow + tid] : 0.0;
 
-	if (cnt <= 0) {   // a row without entries keeps X_old's bits and is not projected
-		if (tid < K) a.X_new[xrow + tid] = xold;
-		if (tid == 0) atomicAdd(&a.counts[1], 1ull);
-		return;
+	if constexpr (!IMPLICIT) {
+		if (cnt <= 0) {   // a row without entries keeps X_old's bits and is not projected
+			if (tid < K) a.X_new[xrow + tid] = xold;
+			if (tid == 0) atomicAdd(&a.counts[1], 1ull);
+			return;
+		}
 	}
 	const double xf = f >= 0 ? a.X_old[xrow + f] : 0.0;
 
@@ -132,7 +149,14 @@ __global__ void __launch_bounds__(kAlsThreads) als_kernel(AlsArgs a)
 #pragma unroll
 		for (int u = 0; u < BS; ++u)
 #pragma unroll
-			for (int v = 0; v < BS; ++v) acc[i][u][v] = 0.0;
+			for (int v = 0; v < BS; ++v) {
+				if constexpr (IMPLICIT) {   // step 3 starts at S[p][q]
+					const int gp = bp[i] + u, gq = bq[i] + v;
+					acc[i][u][v] = e < nblocks && gp < K && gq <= gp ? als_implicit_of(im...).S[als_tri(gp, gq)] : 0.0;
+				} else {
+					acc[i][u][v] = 0.0;
+				}
+			}
 	}
 	double bacc = 0.0;
 
@@ -147,8 +171,16 @@ __global__ void __launch_bounds__(kAlsThreads) als_kernel(AlsArgs a)
 				av = av - t;
 			}
 			ids[tid] = id;
-			ap[tid] = av;
-			wl[tid] = weighted ? a.wgt[e] : 1.0;
+			if constexpr (IMPLICIT) {   // e_n, and ac_n = a_n * c_n with c_n = 1.0 + e_n
+				const double conf = als_implicit_of(im...).conf;
+				const double en = a.wgt ? conf * a.wgt[e] : conf;
+				const double cn = 1.0 + en;
+				ap[tid] = av * cn;
+				wl[tid] = en;
+			} else {
+				ap[tid] = av;
+				wl[tid] = weighted ? a.wgt[e] : 1.0;
+			}
 		}
 		als_sync<THREADS>();
 		// phase 1b: the Y rows of the chunk, zero beyond column K
@@ -183,7 +215,7 @@ __global__ void __launch_bounds__(kAlsThreads) als_kernel(AlsArgs a)
 				}
 			}
 			if (tid < K) {
-				const double t = ap[n] * ywr[tid];
+				const double t = ap[n] * (IMPLICIT ? yr[tid] : ywr[tid]);
 				bacc = bacc + t;
 			}
 		}

@@ -332,6 +332,9 @@ int mf_plan_flip(mf_plan *p)
 	return MF_OK;
 }
 
+// the implicit solve of a side with a frozen column: its all-pairs term needs a correction the header does not define
+static bool implicit_refuses(const mf_plan *p, int side) { return p->als_kind == MF_ALS_IMPLICIT && p->rule[side].frozen >= 0; }
+
 static int iterate_eager(mf_plan *p, int iters)
 {
 	// the errors + streams iteration seeds unconditionally: not while a side is adaptive, whose sweep is the unseeded one
@@ -364,6 +367,7 @@ int mf_plan_iterate(mf_plan *p, int iters)
 {
 	if (!p || iters < 0) return MF_ERR_ARGUMENT;
 	if (!p->have_factors) return MF_ERR_STATE;
+	if (iters > 0 && (implicit_refuses(p, 0) || implicit_refuses(p, 1))) return MF_ERR_UNSUPPORTED;   // before any HIP call
 	MF_HIP(hipSetDevice(p->device));
 	// ALS: the users against the current R, the items against the NEW L (Gauss-Seidel), the flip; eager launches, no graph
 	if (p->als_kind != MF_ALS_OFF) {
@@ -737,11 +741,12 @@ int mf_plan_upload_adaptive_state(mf_plan *p, int side, const double *m, const d
 	return MF_OK;
 }
 
+// the kinds of the explicit solve (mf_backend_run_als takes these); the implicit one comes with a confidence
 static bool als_kind_ok(int kind) { return kind == MF_ALS_OFF || kind == MF_ALS_RIDGE || kind == MF_ALS_RIDGE_COUNT; }
 
 int mf_plan_set_als(mf_plan *p, int kind)
 {
-	if (!p || !als_kind_ok(kind)) return MF_ERR_ARGUMENT;
+	if (!p || !(als_kind_ok(kind) || kind == MF_ALS_IMPLICIT)) return MF_ERR_ARGUMENT;
 	if (kind != MF_ALS_OFF) {
 		if (p->K > mf::kAlsMaxK) return MF_ERR_UNSUPPORTED;   // the triangle of a row lives in LDS
 		// a solve has neither a previous step nor a gradient: momentum or an adaptive side came first
@@ -752,6 +757,10 @@ int mf_plan_set_als(mf_plan *p, int kind)
 		MF_HIP(hipSetDevice(p->device));
 		MF_TRY(p->als_counts.alloc(6));
 		MF_HIP(hipMemsetAsync(p->als_counts.get(), 0, 6 * sizeof(unsigned long long), p->stream));
+	}
+	if (kind == MF_ALS_IMPLICIT) {   // and so do the Gram buffers
+		MF_HIP(hipSetDevice(p->device));
+		MF_TRY(gram_buffers(p));
 	}
 	p->als_kind = kind;   // read at every launch
 	return MF_OK;
@@ -770,8 +779,61 @@ int mf_plan_als_solve(mf_plan *p, int side, int other_generation)
 	if (!p->have_factors || p->als_kind == MF_ALS_OFF) return MF_ERR_STATE;
 	// an item's Gram matrix is a sum over ALL users: a plan that holds a block of them (a shard, a 2-D tile) has a part of it
 	if (side == 0 && (p->u0 != 0 || p->uc != p->users_total)) return MF_ERR_UNSUPPORTED;
+	if (implicit_refuses(p, side)) return MF_ERR_UNSUPPORTED;
 	MF_HIP(hipSetDevice(p->device));
 	return launch_als(p, side, other_generation);
+}
+
+int mf_plan_set_confidence(mf_plan *p, double conf)
+{
+	if (!p || !std::isfinite(conf) || conf < 0.0) return MF_ERR_ARGUMENT;
+	p->confidence = conf;   // read at every launch
+	return MF_OK;
+}
+
+int mf_plan_get_confidence(mf_plan *p, double *conf)
+{
+	if (!p) return MF_ERR_ARGUMENT;
+	if (conf) *conf = p->confidence;
+	return MF_OK;
+}
+
+int mf_plan_gram(mf_plan *p, int side, int generation, double *triangle)
+{
+	if (!p || (side != 0 && side != 1) || (generation != 0 && generation != 1)) return MF_ERR_ARGUMENT;
+	if (!p->have_factors) return MF_ERR_STATE;
+	if (p->K > mf::kAlsMaxK) return MF_ERR_UNSUPPORTED;
+	MF_HIP(hipSetDevice(p->device));
+	MF_TRY(gram_buffers(p));
+	MF_TRY(launch_gram(p, side, generation));
+	if (triangle) {
+		const size_t tri = (size_t) mf::als_triangle(p->K);
+		MF_HIP(hipMemcpyAsync(triangle, p->gram.get() + (size_t) side * tri, tri * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+		MF_HIP(hipStreamSynchronize(p->stream));
+	}
+	return MF_OK;
+}
+
+int mf_backend_gram_dot(const double *left, const double *right, int32_t features, double *out)
+{
+	if (!left || !right || !out || features < 1) return MF_ERR_ARGUMENT;
+	double t = 0.0;
+	for (int p = 0; p < features; ++p)
+		for (int q = 0; q < features; ++q) {
+			const size_t e = p >= q ? (size_t) p * (p + 1) / 2 + q : (size_t) q * (q + 1) / 2 + p;   // the upper triangle by symmetry
+			const double m = left[e] * right[e];
+			t = t + m;
+		}
+	*out = t;
+	return MF_OK;
+}
+
+int mf_plan_implicit_objective(mf_plan *p, mf_implicit_objective *out)
+{
+	if (!p || !out) return MF_ERR_ARGUMENT;
+	if (!p->have_factors) return MF_ERR_STATE;
+	if (p->K > mf::kAlsMaxK) return MF_ERR_UNSUPPORTED;
+	return implicit_objective_eval(p, out);
 }
 
 int mf_plan_als_info(mf_plan *p, int side, int64_t *solved, int64_t *kept_empty, int64_t *kept_not_pd)
@@ -1111,9 +1173,13 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 		append(buf, buflen, " adaptive=%s/%s", sd[1], sd[0]);
 	}
 	// the solver of mf_plan_iterate when it is not the gradient step, and the form its solves launch
-	if (p->als_kind != MF_ALS_OFF) {
+	if (p->als_kind == MF_ALS_RIDGE || p->als_kind == MF_ALS_RIDGE_COUNT) {
 		const AlsForm &form = kAlsForm[als_form(p->K, p->cfg.als_form)];
 		append(buf, buflen, " als=%s als_form=%s(chunk=%d)", p->als_kind == MF_ALS_RIDGE ? "ridge" : "ridge-count", form.name, form.nch);
+	}
+	if (p->als_kind == MF_ALS_IMPLICIT) {
+		const AlsForm &form = kAlsForm[als_form(p->K, p->cfg.als_form)];
+		append(buf, buflen, " als=implicit conf=%.17g als_form=%s(chunk=%d)", p->confidence, form.name, form.nch);
 	}
 	// the environment switches this plan was created under, when any differs from its default (mf_config.hip.h)
 	const std::string cfg = p->cfg.describe();
@@ -1245,6 +1311,25 @@ int mf_backend_run_als(const mf_problem *pr, const double *weight, double *L, do
 	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
 		p->rule[0] = rule[0], p->rule[1] = rule[1];
 		int rc = mf_plan_set_als(p, kind);
+		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
+		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
+		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
+		return rc;
+	}, weight);
+}
+
+// the implicit-feedback run: mf_backend_run_als with the implicit kind and its confidence
+int mf_backend_run_implicit(const mf_problem *pr, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
+                            double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, double conf, int device)
+{
+	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !bounds_record_ok(bounds_users, pr->features) ||
+	    !bounds_record_ok(bounds_items, pr->features) || !std::isfinite(conf) || conf < 0.0)
+		return MF_ERR_ARGUMENT;
+	const RulePair rule = level1_rules(lambda_users, lambda_items, 0.0, 0.0, bounds_users, bounds_items);
+	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
+		p->rule[0] = rule[0], p->rule[1] = rule[1];
+		int rc = mf_plan_set_confidence(p, conf);
+		if (rc == MF_OK) rc = mf_plan_set_als(p, MF_ALS_IMPLICIT);
 		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
 		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
 		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
@@ -1523,6 +1608,7 @@ int mf_plan_iterate_monitored(mf_plan *p, int iters, int every, double tol, mf_l
 {
 	if (!p || iters < 0 || every < 1 || cap < 0 || (cap > 0 && !trace)) return MF_ERR_ARGUMENT;
 	if (!p->have_factors) return MF_ERR_STATE;
+	if (iters > 0 && (implicit_refuses(p, 0) || implicit_refuses(p, 1))) return MF_ERR_UNSUPPORTED;   // before any HIP call
 	int done = 0, npoints = 0;
 	double prev = 0.0;
 	for (;;) {

@@ -582,12 +582,57 @@ AlsFormId als_form(int K, int forced)
 	return K <= 16 ? kAlsWave : kAlsWg;
 }
 
+// ---- the Gram of a whole side (mf_gram.hip.h)
+
+int gram_blocks(int rows) { return (rows + mf::kLossBlock - 1) / mf::kLossBlock; }
+int gram_rows(const mf_plan *p, int side) { return side == 0 ? p->items : p->uc; }
+
+// the two triangles [items | users] and the partials of the longer side, allocated together on first use
+int gram_buffers(mf_plan *p)
+{
+	if (p->gram) return MF_OK;
+	const size_t tri = (size_t) mf::als_triangle(p->K);
+	const size_t blocks = (size_t) std::max(1, std::max(gram_blocks(p->items), gram_blocks(p->uc)));
+	int rc = p->gram_partial.alloc(blocks * tri);
+	if (rc == MF_OK) rc = p->gram.alloc(2 * tri);
+	if (rc != MF_OK) p->gram_partial.reset();
+	return rc;
+}
+
+// S of `side` in its current (0) or next (1) buffer into the side's triangle, on the plan's stream: one workgroup per block
+// of kLossBlock rows, then the sum over the blocks.  The buffers exist (gram_buffers).
+int launch_gram(mf_plan *p, int side, int generation)
+{
+	const int rows = gram_rows(p, side), tri = mf::als_triangle(p->K), blocks = gram_blocks(rows);
+	double *S = p->gram.get() + (size_t) side * tri;
+	if (blocks > 0) {
+		mf::GramArgs a;
+		a.rows = rows;
+		a.K = p->K;
+		a.ld = side == 0 ? p->ldr : p->ldl;
+		a.X = side == 0 ? p->Rbuf[p->cur ^ generation] : p->Lbuf[p->cur ^ generation];
+		a.partial = p->gram_partial;
+		const int nb = (mf::als_blocks(p->K, mf::kGramBS) + mf::kGramThreads - 1) / mf::kGramThreads;
+		const size_t lds = (size_t) mf::kGramChunk * mf::als_padded_k(p->K, mf::kGramBS) * sizeof(double);
+		hipLaunchKernelGGL(kGramFn[nb - 1], dim3(blocks), dim3(mf::kGramThreads), lds, p->stream, a);
+		MF_HIP(hipGetLastError());
+	}
+	hipLaunchKernelGGL(mf::gram_sum_kernel, dim3((tri + mf::kGramThreads - 1) / mf::kGramThreads), dim3(mf::kGramThreads), 0, p->stream,
+	                   (const double *) p->gram_partial.get(), blocks, tri, S);
+	MF_HIP(hipGetLastError());
+	return MF_OK;
+}
+
 // One solve of a side (0: items, 1: users) against the other side's current (0) or next (1) buffer, into the side's
 // next buffer: the counters zeroed, then one launch over the side's rows in its dispatch order -- the extreme rows of a
-// split side first, they are its longest.  The rule of the side is read here, at every launch.
+// split side first, they are its longest.  The rule of the side is read here, at every launch.  Under MF_ALS_IMPLICIT the
+// Gram of the other side in that generation is enqueued first and the implicit instances run (the caller has refused a
+// frozen column).
 int launch_als(mf_plan *p, int side, int other_generation)
 {
 	const SweepSide &sd = p->side[side];
+	const bool implicit = p->als_kind == MF_ALS_IMPLICIT;
+	if (implicit) MF_TRY(launch_gram(p, side ^ 1, other_generation));
 	unsigned long long *counts = p->als_counts.get() + 3 * side;
 	MF_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(unsigned long long), p->stream));
 	if (sd.nrows <= 0) return MF_OK;
@@ -595,8 +640,9 @@ int launch_als(mf_plan *p, int side, int other_generation)
 	const int groups = mf::kAlsThreads / form.threads;
 	const int nb = (mf::als_blocks(p->K, form.bs) + form.threads - 1) / form.threads;
 	const AlsFn fn = form.fn[nb - 1];
-	const size_t lds = (size_t) groups * mf::als_group_doubles(p->K, form.bs, form.nch, p->weighted) * sizeof(double);
-	MF_HIP(raise_lds_limit((const void *) fn, lds));
+	const AlsImplicitFn ifn = form.implicit[nb - 1];
+	const size_t lds = (size_t) groups * mf::als_group_doubles(p->K, form.bs, form.nch, implicit || p->weighted) * sizeof(double);
+	MF_HIP(raise_lds_limit(implicit ? (const void *) ifn : (const void *) fn, lds));
 
 	const SideUpdate u = side_update(p, side, 1);
 	mf::AlsArgs a;
@@ -619,7 +665,11 @@ int launch_als(mf_plan *p, int side, int other_generation)
 		if (nrows <= 0) return MF_OK;
 		a.rowlist = rowlist;
 		a.nrows = nrows;
-		hipLaunchKernelGGL(fn, dim3((nrows + groups - 1) / groups), dim3(mf::kAlsThreads), lds, p->stream, a);
+		if (implicit)
+			hipLaunchKernelGGL(ifn, dim3((nrows + groups - 1) / groups), dim3(mf::kAlsThreads), lds, p->stream, a,
+			                   mf::AlsImplicit{p->gram.get() + (size_t) (side ^ 1) * mf::als_triangle(p->K), p->confidence});
+		else
+			hipLaunchKernelGGL(fn, dim3((nrows + groups - 1) / groups), dim3(mf::kAlsThreads), lds, p->stream, a);
 		MF_HIP(hipGetLastError());
 		return MF_OK;
 	};

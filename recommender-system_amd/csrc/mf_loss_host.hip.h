@@ -99,6 +99,60 @@ int weight_total_eval(mf_plan *p, double *sum_w, double *row_w)
 	return MF_OK;
 }
 
+// The implicit-feedback objective of the current factors (mf_plan_implicit_objective): the two Grams (mf_gram.hip.h) and
+// their elementwise product summed on the host (mf_backend_gram_dot), the observed part as row sums in the loss's buffers
+// followed by step 4 of the loss; complete on return.
+constexpr int kImplicitChunk = 32;   // entries per chunk of implicit_rows_kernel: 32 rows of K | 1 doubles, 33 KiB at K = 128
+
+int implicit_objective_eval(mf_plan *p, mf_implicit_objective *out)
+{
+	MF_HIP(hipSetDevice(p->device));
+	MF_TRY(gram_buffers(p));
+	MF_TRY(loss_buffers(p));
+	MF_TRY(launch_gram(p, 0, 0));
+	MF_TRY(launch_gram(p, 1, 0));
+	const int nblocks = blocks_touched(p->u0, p->uc);
+	if (p->uc > 0) {
+		mf::LossArgs a;
+		a.nrows = p->uc;
+		a.K = p->K;
+		a.nch = kImplicitChunk;
+		a.stride = p->stride;
+		a.ldl = p->ldl;
+		a.ldr = p->ldr;
+		a.ptr = p->csr_ptr;
+		a.idx = p->csr_idx;
+		a.val = p->csr_val;
+		a.L = p->Lbuf[p->cur];
+		a.R = p->Rbuf[p->cur];
+		a.row_sse = p->row_sse;
+		a.rowlist = p->side[1].lpt ? p->side[1].short_rows.get() : nullptr;
+		a.wgt = p->weighted ? p->csr_wgt.get() : nullptr;
+		const size_t lds = (size_t) kImplicitChunk * p->stride * sizeof(double);
+		hipLaunchKernelGGL(mf::implicit_rows_kernel, dim3(std::min(a.nrows, 1 << 20)), dim3(mf::kWave), lds, p->stream, a, p->confidence);
+		MF_HIP(hipGetLastError());
+		hipLaunchKernelGGL(mf::loss_block_kernel, dim3(nblocks), dim3(mf::kWave), 0, p->stream, p->row_sse, p->u0, p->uc, nblocks,
+		                   p->loss_blocks);
+		MF_HIP(hipGetLastError());
+	}
+	hipLaunchKernelGGL(mf::loss_total_kernel, dim3(1), dim3(mf::kWave), 0, p->stream, p->loss_blocks, nblocks, p->loss_total);
+	MF_HIP(hipGetLastError());
+	const size_t tri = (size_t) mf::als_triangle(p->K);
+	std::vector<double> S;
+	try {
+		S.resize(2 * tri);
+	} catch (const std::bad_alloc &) {
+		return MF_ERR_NO_MEMORY;
+	}
+	double observed = 0.0;
+	MF_HIP(hipMemcpyAsync(S.data(), p->gram.get(), 2 * tri * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+	MF_HIP(hipMemcpyAsync(&observed, p->loss_total, sizeof(double), hipMemcpyDeviceToHost, p->stream));
+	MF_HIP(hipStreamSynchronize(p->stream));
+	out->observed = observed;
+	out->count = p->nnz;
+	return mf_backend_gram_dot(S.data() + tri, S.data(), p->K, &out->all_sq);   // users' triangle, items' triangle
+}
+
 // The penalty of one factor: row sums of squares into `rows_out`, block sums (blocks cut at global multiples of
 // kLossBlock counted from `begin`) into `blocks_out`, the total into `total_out`, all on the plan's stream.
 int launch_penalty_side(mf_plan *p, const double *X, int begin, int rows, int ld, double *rows_out, double *blocks_out, double *total_out)

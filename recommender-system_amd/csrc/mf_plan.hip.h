@@ -8,6 +8,8 @@ namespace {
 using SweepFn = void (*)(mf::SweepArgs);
 using LossFn = void (*)(mf::LossArgs);
 using AlsFn = void (*)(mf::AlsArgs);
+using AlsImplicitFn = void (*)(mf::AlsArgs, mf::AlsImplicit);
+using GramFn = void (*)(mf::GramArgs);
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is per FUNCTION, not per plan: two live plans that share a kernel
 // instance (the run-time-K forms) but need different tile sizes must never lower each other's limit.
@@ -245,13 +247,18 @@ struct AlsForm {
 	const char *name;
 	int threads, bs, nch, max_k;
 	AlsFn fn[3];
+	AlsImplicitFn implicit[3];   // the instances of MF_ALS_IMPLICIT: the same forms, S and conf beside the arguments
 };
 const AlsForm kAlsForm[kAlsForms] = {
     {"wg", mf::kAlsThreads, 4, mf::kAlsChunkWg, mf::kAlsMaxK,
-     {mf::als_kernel<mf::kAlsThreads, 4, 1>, mf::als_kernel<mf::kAlsThreads, 4, 2>, mf::als_kernel<mf::kAlsThreads, 4, 3>}},
+     {mf::als_kernel<mf::kAlsThreads, 4, 1>, mf::als_kernel<mf::kAlsThreads, 4, 2>, mf::als_kernel<mf::kAlsThreads, 4, 3>},
+     {mf::als_kernel<mf::kAlsThreads, 4, 1, mf::AlsImplicit>, mf::als_kernel<mf::kAlsThreads, 4, 2, mf::AlsImplicit>, mf::als_kernel<mf::kAlsThreads, 4, 3, mf::AlsImplicit>}},
     {"wave", mf::kWave, 2, mf::kAlsChunkWave, mf::kAlsWaveMaxK,
-     {mf::als_kernel<mf::kWave, 2, 1>, mf::als_kernel<mf::kWave, 2, 2>, mf::als_kernel<mf::kWave, 2, 3>}},
+     {mf::als_kernel<mf::kWave, 2, 1>, mf::als_kernel<mf::kWave, 2, 2>, mf::als_kernel<mf::kWave, 2, 3>},
+     {mf::als_kernel<mf::kWave, 2, 1, mf::AlsImplicit>, mf::als_kernel<mf::kWave, 2, 2, mf::AlsImplicit>, mf::als_kernel<mf::kWave, 2, 3, mf::AlsImplicit>}},
 };
+// the Gram of a whole side (mf_gram.hip.h) by blocks of the triangle per thread, as the workgroup form above
+const GramFn kGramFn[3] = {mf::gram_block_kernel<1>, mf::gram_block_kernel<2>, mf::gram_block_kernel<3>};
 
 }  // namespace
 
@@ -268,6 +275,11 @@ struct mf_plan {
 	// three row counts of each side's last solve, [side][solved, kept_empty, kept_not_pd], allocated on first use
 	int als_kind = MF_ALS_OFF;
 	dev_buf<unsigned long long> als_counts;
+	// implicit feedback: the confidence scale (mf_plan_set_confidence, read at every launch) and the Gram matrices of the two
+	// sides (mf_plan_gram): [items | users], each a packed lower triangle, and the per-block partials they are summed from
+	// (as many blocks as the longer side has), allocated together on first use
+	double confidence = 1.0;
+	dev_buf<double> gram, gram_partial;
 	int flags = 0;
 
 	hipStream_t own_stream = nullptr;

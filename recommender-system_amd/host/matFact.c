@@ -22,11 +22,11 @@
 
 /* Every MATFACT_* variable the program reads: the mode options in the order they are examined, the path options, and the
  * accessories, which take part in no rule. */
-enum { V_TOPN, V_LOSS, V_HELDOUT, V_RANK, V_SIMILAR, V_SIMILAR_OUT, V_LAMBDA, V_BIAS, V_MOMENTUM, V_WEIGHTS, V_BOUNDS, V_OPTIMIZER, V_SOLVER, V_DEVICES, V_MATS, V_CHECKPOINT, V_RESUME,
+enum { V_TOPN, V_LOSS, V_HELDOUT, V_RANK, V_SIMILAR, V_SIMILAR_OUT, V_LAMBDA, V_BIAS, V_MOMENTUM, V_WEIGHTS, V_BOUNDS, V_OPTIMIZER, V_SOLVER, V_IMPLICIT, V_DEVICES, V_MATS, V_CHECKPOINT, V_RESUME,
        V_DEVICE, V_MATS_ITERS, V_CHECKPOINT_EVERY, V_CACHE, V_TIMING, V_COUNT };
 static const char *const cli_names[V_COUNT] = {
 	"MATFACT_TOPN", "MATFACT_LOSS", "MATFACT_HELDOUT", "MATFACT_RANK", "MATFACT_SIMILAR", "MATFACT_SIMILAR_OUT", "MATFACT_LAMBDA",
-	"MATFACT_BIAS", "MATFACT_MOMENTUM", "MATFACT_WEIGHTS", "MATFACT_BOUNDS", "MATFACT_OPTIMIZER", "MATFACT_SOLVER", "MATFACT_DEVICES", "MATFACT_MATS", "MATFACT_CHECKPOINT", "MATFACT_RESUME", "MATFACT_DEVICE",
+	"MATFACT_BIAS", "MATFACT_MOMENTUM", "MATFACT_WEIGHTS", "MATFACT_BOUNDS", "MATFACT_OPTIMIZER", "MATFACT_SOLVER", "MATFACT_IMPLICIT", "MATFACT_DEVICES", "MATFACT_MATS", "MATFACT_CHECKPOINT", "MATFACT_RESUME", "MATFACT_DEVICE",
 	"MATFACT_MATS_ITERS", "MATFACT_CHECKPOINT_EVERY", "MATFACT_CACHE", "MATFACT_TIMING"};
 
 struct cli_options {
@@ -52,6 +52,8 @@ struct cli_options {
 	mf_adaptive optimizer;   /* adaptive step on both sides (eta, eps > 0; beta1, beta2, rho in [0, 1); defaults 0.9, 0.999, 1e-8) */
 	int als;              /* MATFACT_SOLVER=als[,count]: the file's iters as ALS iterations (mf_plan_set_als: MF_ALS_RIDGE, or with */
 	                      /* `count` MF_ALS_RIDGE_COUNT) from the reference's initialisation; lambda is MATFACT_LAMBDA's, default 0 */
+	int implicit;         /* MATFACT_IMPLICIT=conf (finite, >= 0) next to MATFACT_SOLVER=als: the file's iters as implicit-feedback iterations */
+	double conf;          /* (MF_ALS_IMPLICIT) at confidence 1 + conf * weight, and one objective line on stderr at the end */
 	int device;           /* MATFACT_DEVICE=n: the GPU of a single-GPU run, default 0 */
 	int devs[16], ndev;   /* MATFACT_DEVICES=0,1,...: row-shard over these GPUs of the process, at most 16 */
 	const char *devices_error;   /* a non-number in it: said only where that path runs, after the input was read, as ever */
@@ -138,6 +140,12 @@ static const char *cli_value(int v, const char *s, struct cli_options *o)
 	case V_SOLVER:
 		o->als = !strcmp(s, "als") ? MF_ALS_RIDGE : !strcmp(s, "als,count") ? MF_ALS_RIDGE_COUNT : MF_ALS_OFF;
 		return o->als ? NULL : "MATFACT_SOLVER: expected als or als,count.";
+	case V_IMPLICIT:
+		o->implicit = number(s, 0, &rest, &o->conf) && isfinite(o->conf) && o->conf >= 0.0;
+		if (!o->implicit) return "MATFACT_IMPLICIT: expected conf, a number >= 0.";
+		if (o->als == MF_ALS_RIDGE_COUNT) return "MATFACT_IMPLICIT cannot be combined with MATFACT_SOLVER=als,count.";
+		if (o->als == MF_ALS_RIDGE) o->als = MF_ALS_IMPLICIT;   /* unset: the needs row below says so */
+		return NULL;
 	}
 	return NULL;   /* MATFACT_HELDOUT, MATFACT_SIMILAR_OUT, MATFACT_WEIGHTS: any text */
 }
@@ -158,6 +166,7 @@ static const struct cli_rule cli_needs[] = {
 	{V_RANK, BIT(V_LOSS) | BIT(V_HELDOUT), "MATFACT_RANK needs MATFACT_HELDOUT=<file.in>."},
 	{V_SIMILAR, BIT(V_SIMILAR_OUT), "MATFACT_SIMILAR needs MATFACT_SIMILAR_OUT=<path>."},
 	{V_SIMILAR_OUT, BIT(V_SIMILAR), "MATFACT_SIMILAR_OUT needs MATFACT_SIMILAR=N[,dot|cosine]."},
+	{V_IMPLICIT, BIT(V_SOLVER), "MATFACT_IMPLICIT needs MATFACT_SOLVER=als."},
 };
 /* `var` cannot be combined with any one of `others` (MATFACT_SIMILAR has two rows: it says two different things) */
 static const struct cli_rule cli_clashes[] = {
@@ -172,6 +181,7 @@ static const struct cli_rule cli_clashes[] = {
 	{V_BOUNDS, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR), "MATFACT_BOUNDS works on the single-GPU path only: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN and MATFACT_SIMILAR."},
 	{V_OPTIMIZER, PATHS | BIT(V_TOPN) | BIT(V_SIMILAR) | BIT(V_MOMENTUM), "MATFACT_OPTIMIZER works on the single-GPU path only and not with momentum: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_TOPN, MATFACT_SIMILAR and MATFACT_MOMENTUM."},
 	{V_SOLVER, PATHS | BIT(V_SIMILAR) | BIT(V_MOMENTUM) | BIT(V_OPTIMIZER), "MATFACT_SOLVER works on the single-GPU path only and not with momentum or an optimizer: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_SIMILAR, MATFACT_MOMENTUM and MATFACT_OPTIMIZER."},
+	{V_IMPLICIT, BIT(V_BIAS), "MATFACT_IMPLICIT cannot be combined with MATFACT_BIAS: the implicit solve has no frozen columns."},
 };
 
 /* Fills `o` from the environment -- it opens no file and makes no GPU call -- and returns NULL, or the message to die with. */
@@ -182,7 +192,7 @@ static const char *cli_parse(struct cli_options *o)
 	for (int v = 0; v < V_COUNT; v++)
 		if ((o->value[v] = getenv(cli_names[v])) != NULL) set |= BIT(v);
 	const unsigned usable = o->value[V_SIMILAR_OUT] && !*o->value[V_SIMILAR_OUT] ? set & ~BIT(V_SIMILAR_OUT) : set;
-	for (int v = V_TOPN; v <= V_SOLVER; v++) {
+	for (int v = V_TOPN; v <= V_IMPLICIT; v++) {
 		const char *message = set & BIT(v) ? cli_value(v, o->value[v], o) : NULL;
 		if (message) return message;
 		if (!(set & BIT(v))) continue;
@@ -376,6 +386,19 @@ static int write_similar(mf_plan *plan, const struct cli_options *o, int32_t ite
 	return rc;
 }
 
+/* MATFACT_IMPLICIT: the all-pairs objective of the final factors, ((all_sq + observed) + lambda_users ||L||^2) + lambda_items ||R||^2 */
+static int report_implicit(mf_plan *plan, const struct cli_options *o)
+{
+	mf_implicit_objective ob;
+	double us = 0.0, is = 0.0;
+	int rc = mf_plan_implicit_objective(plan, &ob);
+	if (rc == MF_OK) rc = mf_plan_penalty(plan, &us, &is, NULL, NULL);
+	if (rc == MF_OK)
+		fprintf(stderr, "implicit conf %.17g all_sq %.17g observed %.17g users_sq %.17g items_sq %.17g objective %.17g\n", o->conf, ob.all_sq,
+		        ob.observed, us, is, ((ob.all_sq + ob.observed) + o->lambda_users * us) + o->lambda_items * is);
+	return rc;
+}
+
 /* Every mode that needs a resident plan, as stages over one session: configure, exactly one loop, the reports on stderr,
  * the outputs.  `d` is the open dump of MATFACT_MATS or NULL; `done` counts the iterations a checkpoint already holds. */
 static int run_session(const struct cli_options *o, const mf_problem *p, const mf_problem *held, const mf_problem *wts, double *L, double *R,
@@ -402,6 +425,7 @@ static int run_session(const struct cli_options *o, const mf_problem *p, const m
 	if (rc == MF_OK && o->adaptive) rc = mf_plan_set_adaptive(s.plan, 1, &o->optimizer);
 	if (rc == MF_OK && o->adaptive) rc = mf_plan_set_adaptive(s.plan, 0, &o->optimizer);
 	/* the solver: ALS in place of the gradient step */
+	if (rc == MF_OK && o->implicit) rc = mf_plan_set_confidence(s.plan, o->conf);
 	if (rc == MF_OK && o->als) rc = mf_plan_set_als(s.plan, o->als);
 	/* loop */
 	if (rc == MF_OK) {
@@ -421,6 +445,7 @@ static int run_session(const struct cli_options *o, const mf_problem *p, const m
 	if (rc == MF_OK && o->biased && o->loss_every) fprintf(stderr, "bias mu %.17g\n", s.mu);
 	if (rc == MF_OK && o->regularised && o->loss_every) rc = report_penalty(s.plan, o);
 	if (rc == MF_OK && o->rank_cutoff) rc = report_ranks(s.plan, o->rank_cutoff, s.hrow, held->nnz);
+	if (rc == MF_OK && o->implicit) rc = report_implicit(s.plan, o);
 	/* outputs */
 	if (rc == MF_OK) rc = o->topn ? mf_plan_recommend_topn(s.plan, o->topn, topn_items, NULL) : mf_plan_recommend(s.plan, best);   /* MATFACT_TOPN comes here with MATFACT_SOLVER only */
 	if (rc == MF_OK && o->similar) rc = write_similar(s.plan, o, p->items);
