@@ -335,174 +335,32 @@ int mf_plan_flip(mf_plan *p)
 // the implicit solve of a side with a frozen column: its all-pairs term needs a correction the header does not define
 static bool implicit_refuses(const mf_plan *p, int side) { return p->als_kind == MF_ALS_IMPLICIT && p->rule[side].frozen >= 0; }
 
-static int iterate_eager(mf_plan *p, int iters)
-{
-	// the errors + streams iteration seeds unconditionally: not while a side is adaptive, whose sweep is the unseeded one
-	if (p->es_mode && !adaptive_any(p)) {
-		for (int it = 0; it < iters; ++it) {
-			const int rc = launch_es_iteration(p);
-			if (rc != MF_OK) return rc;
-			p->cur ^= 1;
-		}
-		return MF_OK;
-	}
-	for (int it = 0; it < iters; ++it) {
-		// Both sweeps read only the frozen generation (matFact.c:38-39), so the ordered sums of the item sweep's
-		// extreme rows may run on the side stream UNDER the whole user sweep; they are joined before the flip.
-		// Not when the user sweep has extreme rows of its own: it would reuse the scratch buffer.
-		int rc = launch_sweep(p, 0, 1, /*defer_join=*/p->side[1].n_long == 0);
-		if (rc != MF_OK) return rc;
-		rc = launch_sweep(p, 1, 1);
-		if (rc != MF_OK) return rc;
-		if (p->join_pending) {
-			MF_HIP(hipStreamWaitEvent(p->stream, p->ev_join, 0));
-			p->join_pending = false;
-		}
-		p->cur ^= 1;
-	}
-	return MF_OK;
-}
-
 int mf_plan_iterate(mf_plan *p, int iters)
 {
 	if (!p || iters < 0) return MF_ERR_ARGUMENT;
 	if (!p->have_factors) return MF_ERR_STATE;
 	if (iters > 0 && (implicit_refuses(p, 0) || implicit_refuses(p, 1))) return MF_ERR_UNSUPPORTED;   // before any HIP call
 	MF_HIP(hipSetDevice(p->device));
-	// ALS: the users against the current R, the items against the NEW L (Gauss-Seidel), the flip; eager launches, no graph
-	if (p->als_kind != MF_ALS_OFF) {
-		if (iters > 0 && (p->u0 != 0 || p->uc != p->users_total)) return MF_ERR_UNSUPPORTED;   // the item solve of a shard
-		for (int it = 0; it < iters; ++it) {
-			MF_TRY(launch_als(p, 1, 0));
-			MF_TRY(launch_als(p, 0, 1));
-			p->cur ^= 1;
-		}
-		return MF_OK;
-	}
-	// a momentum side at rest gets its history (X_prev = X_old) here: in front of every launch and outside the capture
-	if (iters > 0) {
+	const mf_sched::IterateInput in = iterate_input(p, iters);
+	if (in.als && iters > 0 && !in.whole) return MF_ERR_UNSUPPORTED;   // the item solve of a shard
+	// A momentum side at rest gets its history (X_prev = X_old) and an adaptive side its accumulators here: in front of every
+	// launch and outside any capture.  Not under ALS, which reads neither.
+	if (iters > 0 && !in.als) {
 		MF_TRY(leave_rest(p, 0));
 		MF_TRY(leave_rest(p, 1));
-		// an adaptive side gets its accumulators here, for the same reason
 		MF_TRY(adaptive_ready(p, 0));
 		MF_TRY(adaptive_ready(p, 1));
 	}
-	// Launch-bound regime (inst1: 100000 iterations of a 13-entry instance, ~4 us per launch): capture an even
-	// number of iterations -- so the ping-pong parity returns to where it started -- into a HIP graph and replay it.
-	// Only for small sweeps; a large sweep is not launch-bound and a graph would pin its arguments for nothing.
-	// Toy regime (inst0/1/2: a dozen entries, 1e5 iterations): the whole instance fits the LDS of one workgroup -> one
-	// launch runs all the iterations with a workgroup barrier in between (sweep_resident_kernel).  Whole-instance
-	// plans only, and only while an iteration is a few hundred multiply-adds: measured through the CLI, inst1
-	// 0.70 -> 0.33 s and inst2 0.47 -> 0.21 s, but inst30-40 (170 entries x K=10) 0.32 -> 0.39 s -- one workgroup
-	// on an otherwise idle chip runs slowly, and two graph-replayed launches per iteration win again.
-	{
-		// (the rule looks at the unweighted footprint: weights do not alter which form a plan takes; the request below holds them --
-		// 16 bytes per entry, at most 2 KiB where the footprint is near its bound, since nnz * K <= 512: never above 64 KiB)
-		size_t need = mf::resident_lds_bytes(p->uc, p->items, p->K, p->nnz);
-		const bool toy = p->uc == p->users_total && p->u0 == 0 && p->uc + p->items <= 1024 && p->uc + p->items > 0 &&
-		                 need <= 60 * 1024 && (double) p->nnz * p->K <= 512.0 && !p->timing && iters >= 8 &&
-		                 p->cfg.resident && !adaptive_any(p);   // the toy loop seeds unconditionally, like errors + streams
-		if (toy) {
-			mf::ResidentArgs ra;
-			ra.users = p->uc;
-			ra.items = p->items;
-			ra.K = p->K;
-			ra.ldl = p->ldl;
-			ra.ldr = p->ldr;
-			ra.iters = iters;
-			ra.c2 = p->alpha * 2;
-			const SideUpdate items = side_update(p, 0, 1), users = side_update(p, 1, 1);
-			ra.d_users = users.d;
-			ra.d_items = items.d;
-			ra.frozen_users = users.frozen;
-			ra.frozen_items = items.frozen;
-			ra.box_users = users.box;
-			ra.box_items = items.box;
-			ra.csr_ptr = p->csr_ptr;
-			ra.csr_idx = p->csr_idx;
-			ra.csr_val = p->csr_val;
-			ra.csc_ptr = p->csc_ptr;
-			ra.csc_idx = p->csc_idx;
-			ra.csc_val = p->csc_val;
-			ra.L_in = p->Lbuf[p->cur];
-			ra.R_in = p->Rbuf[p->cur];
-			// the result lands where `iters` flips of the two generations would have left it
-			const int fin = (iters & 1) ? (p->cur ^ 1) : p->cur;
-			ra.L_out = p->Lbuf[fin];
-			ra.R_out = p->Rbuf[fin];
-			ra.nnz = (int) p->nnz;
-			// momentum: the next-generation buffers carry the history in; the generation before the final one goes out to
-			// the buffers the final one does not take
-			ra.beta_users = users.beta;
-			ra.beta_items = items.beta;
-			ra.L_hist = p->Lbuf[p->cur ^ 1];
-			ra.R_hist = p->Rbuf[p->cur ^ 1];
-			ra.L_prev = p->Lbuf[fin ^ 1];
-			ra.R_prev = p->Rbuf[fin ^ 1];
-			ra.csr_wgt = p->csr_wgt;
-			ra.csc_wgt = p->csc_wgt;
-			if (p->weighted) need = mf::resident_lds_bytes(p->uc, p->items, p->K, p->nnz, true);
-			const bool momentum = items.beta != 0.0 || users.beta != 0.0;
-			const int threads = ((p->uc + p->items + 63) / 64) * 64;
-			void (*rfn)(mf::ResidentArgs) = p->K <= 4    ? mf::sweep_resident_kernel<4>
-			                                : p->K <= 16 ? mf::sweep_resident_kernel<16>
-			                                : p->K <= 32 && threads <= mf::resident_max_threads(32)
-			                                    ? mf::sweep_resident_kernel<32>
-			                                    : mf::sweep_resident_kernel<0>;
-			if (momentum)
-				rfn = p->K <= 4    ? mf::sweep_resident_kernel<4, true>
-				      : p->K <= 16 ? mf::sweep_resident_kernel<16, true>
-				      : p->K <= 32 && threads <= mf::resident_max_threads(32)
-				          ? mf::sweep_resident_kernel<32, true>
-				          : mf::sweep_resident_kernel<0, true>;
-			if (p->weighted && !momentum)
-				rfn = p->K <= 4    ? mf::sweep_resident_kernel<4, false, true>
-				      : p->K <= 16 ? mf::sweep_resident_kernel<16, false, true>
-				      : p->K <= 32 && threads <= mf::resident_max_threads(32)
-				          ? mf::sweep_resident_kernel<32, false, true>
-				          : mf::sweep_resident_kernel<0, false, true>;
-			if (p->weighted && momentum)
-				rfn = p->K <= 4    ? mf::sweep_resident_kernel<4, true, true>
-				      : p->K <= 16 ? mf::sweep_resident_kernel<16, true, true>
-				      : p->K <= 32 && threads <= mf::resident_max_threads(32)
-				          ? mf::sweep_resident_kernel<32, true, true>
-				          : mf::sweep_resident_kernel<0, true, true>;
-			MF_HIP(raise_lds_limit((const void *) rfn, need));
-			hipLaunchKernelGGL(rfn, dim3(1), dim3(threads), need, p->stream, ra);
-			MF_HIP(hipGetLastError());
-			p->cur = fin;
-			return MF_OK;
-		}
+	// which loop runs, and how much of it as graph replays: the one rule of mf_schedule.h
+	const mf_sched::IteratePath path = mf_sched::iterate_path(in);
+	switch (path.loop) {
+	case mf_sched::kLoopAls: return iterate_als(p, path.eager);
+	case mf_sched::kLoopToy: return launch_toy_loop(p, path.eager);
+	case mf_sched::kLoopEs:
+	case mf_sched::kLoopSweeps: break;
 	}
-	const bool small = (double) p->nnz * p->K < p->cfg.graph_max && !p->timing && p->side[0].n_long == 0 &&
-	                   p->side[1].n_long == 0;
-	constexpr int kGraphIters = 32;
-	if (small && iters >= 4 * kGraphIters && p->cfg.graph) {
-		hipGraph_t graph = nullptr;
-		hipGraphExec_t exec = nullptr;
-		const int cur0 = p->cur;
-		hipError_t e = hipStreamBeginCapture(p->stream, hipStreamCaptureModeThreadLocal);
-		int rc = MF_OK;
-		if (e == hipSuccess) {
-			rc = iterate_eager(p, kGraphIters);
-			e = hipStreamEndCapture(p->stream, &graph);
-		}
-		if (e == hipSuccess && rc == MF_OK) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-		if (e == hipSuccess && rc == MF_OK) {
-			p->cur = cur0;   // the capture only recorded; kGraphIters is even, so every replay starts from cur0
-			const int replays = iters / kGraphIters;
-			for (int g = 0; g < replays && e == hipSuccess; ++g) e = hipGraphLaunch(exec, p->stream);
-			iters -= replays * kGraphIters;
-		}
-		if (exec) (void) hipGraphExecDestroy(exec);
-		if (graph) (void) hipGraphDestroy(graph);
-		if (rc != MF_OK) return rc;
-		if (e != hipSuccess) {
-			g_last_hip_error = std::string("hip graph path: ") + hipGetErrorString(e);
-			return MF_ERR_HIP;
-		}
-	}
-	return iterate_eager(p, iters);
+	if (path.replays > 0) MF_TRY(replay_graph(p, path.loop, path.replays));
+	return iterate_eager(p, path.loop, path.eager);
 }
 
 // a regularisation weight is finite and >= 0 (a NaN fails both comparisons' complement)
@@ -1155,8 +1013,8 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 	// per-entry weights, when the plan was created with them
 	if (p->weighted) append(buf, buflen, " weighted=1");
 	// the adaptive rules in force, when a side has one: adaptive=<users>/<items>, the numbers in %.17g (they read back
-	// exactly).  While one is, mf_plan_iterate runs the two sweeps whatever iterate= says above: the errors + streams
-	// iteration and the toy loop seed unconditionally
+	// exactly).  What a side with one means for the loop mf_plan_iterate runs, whatever iterate= says above, is
+	// mf_sched::iterate_path's to say (mf_schedule.h)
 	if (adaptive_any(p)) {
 		char sd[2][160];
 		for (int k = 0; k < 2; ++k) {

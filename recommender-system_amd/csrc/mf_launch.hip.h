@@ -1,4 +1,4 @@
-// mf_launch.hip.h -- choice of the sweep kernel variant / chunk size and the launch of one sweep.
+// mf_launch.hip.h -- choice of the sweep kernel variant / chunk size, the launch of one sweep, and the loops of mf_plan_iterate.
 #pragma once
 
 namespace {
@@ -102,9 +102,7 @@ const void *ordered_sum_fn(const mf_config &cfg)
 }
 const void *stream_resident_fn(int sw, bool momentum = false)
 {
-	if (momentum)
-		return sw == 8 ? (const void *) mf::stream_resident_kernel<8, true> : sw == 4 ? (const void *) mf::stream_resident_kernel<4, true> : (const void *) mf::stream_resident_kernel<2, true>;
-	return sw == 8 ? (const void *) mf::stream_resident_kernel<8> : sw == 4 ? (const void *) mf::stream_resident_kernel<4> : (const void *) mf::stream_resident_kernel<2>;
+	return (const void *) kStreamResidentFn[sw == 8 ? 0 : sw == 4 ? 1 : 2][momentum];
 }
 
 // Raises the LDS limit of every instance of one form that this plan may launch: the non-null cells of the form's row of
@@ -609,8 +607,9 @@ int launch_gram(mf_plan *p, int side, int generation)
 		mf::GramArgs a;
 		a.rows = rows;
 		a.K = p->K;
-		a.ld = side == 0 ? p->ldr : p->ldl;
-		a.X = side == 0 ? p->Rbuf[p->cur ^ generation] : p->Lbuf[p->cur ^ generation];
+		const SideOperands x = side_operands(p, side);
+		a.ld = x.ldx;
+		a.X = generation ? x.X_new : x.X_old;
 		a.partial = p->gram_partial;
 		const int nb = (mf::als_blocks(p->K, mf::kGramBS) + mf::kGramThreads - 1) / mf::kGramThreads;
 		const size_t lds = (size_t) mf::kGramChunk * mf::als_padded_k(p->K, mf::kGramBS) * sizeof(double);
@@ -647,18 +646,19 @@ int launch_als(mf_plan *p, int side, int other_generation)
 	const SideUpdate u = side_update(p, side, 1);
 	mf::AlsArgs a;
 	a.K = p->K;
-	a.ldx = side == 0 ? p->ldr : p->ldl;
-	a.ldy = side == 0 ? p->ldl : p->ldr;
+	const SideOperands x = side_operands(p, side);
+	a.ldx = x.ldx;
+	a.ldy = x.ldy;
 	a.frozen = u.frozen;
 	a.count_scaled = p->als_kind == MF_ALS_RIDGE_COUNT;
 	a.lambda = p->rule[side].lambda;
-	a.ptr = side == 0 ? p->csc_ptr : p->csr_ptr;
-	a.idx = side == 0 ? p->csc_idx : p->csr_idx;
-	a.val = side == 0 ? p->csc_val : p->csr_val;
-	a.wgt = !p->weighted ? nullptr : side == 0 ? p->csc_wgt.get() : p->csr_wgt.get();
-	a.X_old = side == 0 ? p->Rbuf[p->cur] : p->Lbuf[p->cur];
-	a.X_new = side == 0 ? p->Rbuf[p->cur ^ 1] : p->Lbuf[p->cur ^ 1];
-	a.Y = side == 0 ? p->Lbuf[p->cur ^ other_generation] : p->Rbuf[p->cur ^ other_generation];
+	a.ptr = x.ptr;
+	a.idx = x.idx;
+	a.val = x.val;
+	a.wgt = x.wgt;
+	a.X_old = x.X_old;
+	a.X_new = x.X_new;
+	a.Y = other_generation ? side_operands(p, side ^ 1).X_new : x.Y_old;   // the other side's next buffer, or its current one
 	a.counts = counts;
 	a.box = u.box;
 	auto launch = [&](const int *rowlist, int nrows) {
@@ -678,6 +678,144 @@ int launch_als(mf_plan *p, int side, int other_generation)
 		return launch(sd.short_rows, sd.n_short);
 	}
 	return launch(sd.lpt ? sd.short_rows.get() : nullptr, sd.nrows);
+}
+
+// ---- the loops of mf_plan_iterate, one per mf_sched::Loop (iterate_path, mf_schedule.h, picks; mf_plan_iterate dispatches)
+
+// what the rule reads of a plan and a call
+mf_sched::IterateInput iterate_input(const mf_plan *p, int iters)
+{
+	mf_sched::IterateInput in;
+	in.als = p->als_kind != MF_ALS_OFF;
+	in.whole = p->u0 == 0 && p->uc == p->users_total;
+	in.rows = (long long) p->uc + p->items;
+	in.toy_bytes = mf_sched::toy_lds_bytes(p->uc, p->items, p->K, p->nnz);
+	in.nnz = p->nnz;
+	in.K = p->K;
+	in.iters = iters;
+	in.timing = p->timing;
+	in.adaptive = adaptive_any(p);
+	in.es_mode = p->es_mode;
+	in.extreme = p->side[0].n_long > 0 || p->side[1].n_long > 0;
+	in.resident = p->cfg.resident;
+	in.graph = p->cfg.graph;
+	in.graph_max = p->cfg.graph_max;
+	return in;
+}
+
+// ALS: the users against the current R, the items against the NEW L (Gauss-Seidel), the flip
+int iterate_als(mf_plan *p, int iters)
+{
+	for (int it = 0; it < iters; ++it) {
+		MF_TRY(launch_als(p, 1, 0));
+		MF_TRY(launch_als(p, 0, 1));
+		p->cur ^= 1;
+	}
+	return MF_OK;
+}
+
+// The toy loop: ONE launch of one workgroup runs all `iters` iterations (sweep_resident_kernel), thread t owning factor row t.
+int launch_toy_loop(mf_plan *p, int iters)
+{
+	const SideOperands items = side_operands(p, 0), users = side_operands(p, 1);
+	const SideUpdate ui = side_update(p, 0, 1), uu = side_update(p, 1, 1);
+	// the result lands where `iters` flips of the two generations would have left it
+	const int fin = (iters & 1) ? (p->cur ^ 1) : p->cur;
+	mf::ResidentArgs ra;
+	ra.users = p->uc;
+	ra.items = p->items;
+	ra.K = p->K;
+	ra.ldl = p->ldl;
+	ra.ldr = p->ldr;
+	ra.iters = iters;
+	ra.c2 = p->alpha * 2;
+	ra.d_users = uu.d;
+	ra.d_items = ui.d;
+	ra.frozen_users = uu.frozen;
+	ra.frozen_items = ui.frozen;
+	ra.box_users = uu.box;
+	ra.box_items = ui.box;
+	ra.csr_ptr = users.ptr;
+	ra.csr_idx = users.idx;
+	ra.csr_val = users.val;
+	ra.csr_wgt = users.wgt;
+	ra.csc_ptr = items.ptr;
+	ra.csc_idx = items.idx;
+	ra.csc_val = items.val;
+	ra.csc_wgt = items.wgt;
+	ra.L_in = users.X_old;
+	ra.R_in = items.X_old;
+	ra.L_out = p->Lbuf[fin];
+	ra.R_out = p->Rbuf[fin];
+	ra.nnz = (int) p->nnz;
+	// momentum: the next-generation buffers carry the history in; the generation before the final one goes out to
+	// the buffers the final one does not take
+	ra.beta_users = uu.beta;
+	ra.beta_items = ui.beta;
+	ra.L_hist = users.X_new;
+	ra.R_hist = items.X_new;
+	ra.L_prev = p->Lbuf[fin ^ 1];
+	ra.R_prev = p->Rbuf[fin ^ 1];
+	const bool momentum = ui.beta != 0.0 || uu.beta != 0.0;
+	const int threads = ((p->uc + p->items + 63) / 64) * 64;
+	const int kmax = mf_sched::toy_kmax(p->K, threads);
+	const ResidentFn rfn = kResidentFn[kmax == 4 ? 0 : kmax == 16 ? 1 : kmax == 32 ? 2 : 3][momentum][p->weighted];
+	const size_t need = mf_sched::toy_lds_bytes(p->uc, p->items, p->K, p->nnz, p->weighted);   // with the weights, where the plan has them
+	MF_HIP(raise_lds_limit((const void *) rfn, need));
+	hipLaunchKernelGGL(rfn, dim3(1), dim3(threads), need, p->stream, ra);
+	MF_HIP(hipGetLastError());
+	p->cur = fin;
+	return MF_OK;
+}
+
+// `iters` iterations of kLoopEs or kLoopSweeps, launched one by one on the plan's stream
+int iterate_eager(mf_plan *p, mf_sched::Loop loop, int iters)
+{
+	for (int it = 0; it < iters; ++it) {
+		if (loop == mf_sched::kLoopEs) {
+			MF_TRY(launch_es_iteration(p));
+		} else {
+			// Both sweeps read only the frozen generation (matFact.c:38-39), so the ordered sums of the item sweep's
+			// extreme rows may run on the side stream UNDER the whole user sweep; they are joined before the flip.
+			// Not when the user sweep has extreme rows of its own: it would reuse the scratch buffer.
+			MF_TRY(launch_sweep(p, 0, 1, /*defer_join=*/p->side[1].n_long == 0));
+			MF_TRY(launch_sweep(p, 1, 1));
+			if (p->join_pending) {
+				MF_HIP(hipStreamWaitEvent(p->stream, p->ev_join, 0));
+				p->join_pending = false;
+			}
+		}
+		p->cur ^= 1;
+	}
+	return MF_OK;
+}
+
+// `replays` replays of kGraphIters iterations of `loop`, captured once from iterate_eager on the plan's stream.  The
+// capture only records, and kGraphIters is even, so every replay starts from the generation the call started in.
+int replay_graph(mf_plan *p, mf_sched::Loop loop, int replays)
+{
+	hipGraph_t graph = nullptr;
+	hipGraphExec_t exec = nullptr;
+	const int cur0 = p->cur;
+	int rc = MF_OK;
+	hipError_t e = hipStreamBeginCapture(p->stream, hipStreamCaptureModeThreadLocal);
+	if (e == hipSuccess) {
+		rc = iterate_eager(p, loop, mf_sched::kGraphIters);
+		e = hipStreamEndCapture(p->stream, &graph);
+	}
+	if (e == hipSuccess && rc == MF_OK) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+	if (e == hipSuccess && rc == MF_OK) {
+		p->cur = cur0;
+		for (int g = 0; g < replays && e == hipSuccess; ++g) e = hipGraphLaunch(exec, p->stream);
+	}
+	if (exec) (void) hipGraphExecDestroy(exec);
+	if (graph) (void) hipGraphDestroy(graph);
+	if (rc != MF_OK) return rc;
+	if (e != hipSuccess) {
+		g_last_hip_error = std::string("hip graph path: ") + hipGetErrorString(e);
+		return MF_ERR_HIP;
+	}
+	return MF_OK;
 }
 
 int drain_timing(mf_plan *p)

@@ -260,6 +260,20 @@ const AlsForm kAlsForm[kAlsForms] = {
 // the Gram of a whole side (mf_gram.hip.h) by blocks of the triangle per thread, as the workgroup form above
 const GramFn kGramFn[3] = {mf::gram_block_kernel<1>, mf::gram_block_kernel<2>, mf::gram_block_kernel<3>};
 
+// the toy loop (sweep_resident_kernel, mf_sweep.hip.h) by [register-row class][momentum][weighted]; the classes are the
+// values of mf_sched::toy_kmax: 4, 16, 32 and, last, 0
+using ResidentFn = void (*)(mf::ResidentArgs);
+#define MF_TOY_ROW(KMAX) \
+	{{mf::sweep_resident_kernel<KMAX, false, false>, mf::sweep_resident_kernel<KMAX, false, true>}, \
+	 {mf::sweep_resident_kernel<KMAX, true, false>, mf::sweep_resident_kernel<KMAX, true, true>}}
+const ResidentFn kResidentFn[4][2][2] = {MF_TOY_ROW(4), MF_TOY_ROW(16), MF_TOY_ROW(32), MF_TOY_ROW(0)};
+#undef MF_TOY_ROW
+// the resident streams launch (mf_resident.hip.h) by [slice width 8, 4, 2][momentum]
+using StreamResidentFn = void (*)(mf::SliceArgs);
+const StreamResidentFn kStreamResidentFn[3][2] = {{mf::stream_resident_kernel<8>, mf::stream_resident_kernel<8, true>},
+                                                  {mf::stream_resident_kernel<4>, mf::stream_resident_kernel<4, true>},
+                                                  {mf::stream_resident_kernel<2>, mf::stream_resident_kernel<2, true>}};
+
 }  // namespace
 
 struct mf_plan {

@@ -1,11 +1,12 @@
 // mf_schedule.h -- how the two sweeps of a plan run, decided on the host from the row lengths alone: which rows count as
 // extreme, whether a tiny sweep is ONE cooperative launch, the segment tables of the extreme-row path, the wave
 // priority, the form of the main launch and the dispatch order, and the tables of the errors +
-// streams iteration (5.6); and the choice made at every launch, the form, flavour and geometry of a main launch (5.8k).
+// streams iteration (5.6); the choice made at every launch, the form, flavour and geometry of a main launch (5.8k); and the
+// choice made at every mf_plan_iterate, the loop an iteration runs in and its graph replays (5.8k2).
 // Pure functions of (row pointers, K, switches, limits): no HIP type, no kernel header, so they compile with any C++17
-// compiler and tests/test_schedule.py and tests/test_launch_choice.py pin them on a CPU.  mf_build.hip.h fills the inputs,
-// calls sweep_schedule / es_errors / es_workgroups, and allocates and uploads what they return; mf_launch.hip.h makes the
-// launch-time choice.
+// compiler and tests/test_schedule.py, tests/test_launch_choice.py and tests/test_iterate_path.py pin them on a CPU.
+// mf_build.hip.h fills the inputs, calls sweep_schedule / es_errors / es_workgroups, and allocates and uploads what they
+// return; mf_launch.hip.h makes the launch-time choice and fills the rule's input for mf_plan_iterate.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -353,6 +354,77 @@ inline Geometry launch_geometry(Form form, bool few_rows)
 {
 	if (form == kCoop) return few_rows ? kGeomCoop : kGeomCoopSingleNch;
 	return form == kDb ? kGeomDb : form == kPair ? kGeomPair : few_rows ? kGeomFew : kGeomSingle;
+}
+
+// ---- how an iteration runs (mf_plan_iterate, mf_hip.hip): one rule picks the loop and how much of it is replayed from a
+// captured graph; mf_plan_iterate only dispatches on the result (tests/test_iterate_path.py)
+
+// LDS bytes of the toy loop (sweep_resident_kernel, mf_sweep.hip.h): both generations of L and R, the entries in CSR and in
+// CSC order -- value and index, 12 bytes, with the weight 20 --, the two row-pointer arrays and 64 bytes of slack.
+constexpr size_t toy_lds_bytes(int users, int items, int K, long long nnz, bool weighted = false)
+{
+	return (size_t) 2 * (size_t) (users + items) * K * 8 + (size_t) nnz * 2 * (weighted ? 20 : 12) + (size_t) (users + items + 2) * 4 + 64;
+}
+
+// Register-row class of sweep_resident_kernel for this K in a workgroup of `threads`: 4, 16 or 32 (K <= class, the owner keeps
+// its row in registers), 0 for the generic instance.  The K <= 32 instance is bounded to 256 threads by its
+// __launch_bounds__, hence the guard.  No toy instance reaches it: more than 256 threads are users + items >= 257, which
+// with K >= 17 need at least 16 * 257 * 17 = 69 904 bytes, over the 60 KiB bound of iterate_path (the test enumerates it).
+constexpr int toy_kmax(int K, int threads) { return K <= 4 ? 4 : K <= 16 ? 16 : K <= 32 && threads <= 256 ? 32 : 0; }
+
+enum Loop { kLoopAls, kLoopToy, kLoopEs, kLoopSweeps };
+// `replays` replays of a captured body of kGraphIters iterations of `loop`, then `eager` iterations launched one by one.
+// An even body, so the ping-pong parity of the generations returns to where it started and every replay starts alike.
+constexpr int kGraphIters = 32;
+struct IteratePath {
+	Loop loop;
+	int replays, eager;
+};
+
+struct IterateInput {
+	bool als = false;          // an ALS kind is set
+	bool whole = false;        // whole-instance plan: u0 == 0 && uc == users_total
+	long long rows = 0;        // uc + items
+	size_t toy_bytes = 0;      // toy_lds_bytes of the plan, unweighted
+	long long nnz = 0;
+	int K = 0, iters = 0;
+	bool timing = false;       // per-launch timing is on
+	bool adaptive = false;     // a side has an adaptive step size
+	bool es_mode = false;      // the plan holds the errors + streams tables
+	bool extreme = false;      // a side has extreme rows (n_long > 0)
+	bool resident = true, graph = true;   // MF_RESIDENT, MF_GRAPH
+	double graph_max = 2e6;               // MF_GRAPH_MAX
+};
+
+inline IteratePath iterate_path(const IterateInput &in)
+{
+	// ALS: eager launches, no graph
+	if (in.als) return {kLoopAls, 0, in.iters};
+	const double work = (double) in.nnz * in.K;   // multiply-adds of a sweep
+	// Toy regime (inst0/1/2: a dozen entries, 1e5 iterations): the whole instance fits the LDS of one workgroup -> one launch
+	// runs all the iterations with a workgroup barrier in between.
+	const bool toy = in.whole &&                            // thread t owns factor row t: every row of both sides
+	                 in.rows > 0 && in.rows <= 1024 &&      // ... one thread each
+	                 // The unweighted footprint: weights do not alter which loop a plan takes.  The request of a weighted plan
+	                 // holds 16 bytes more per entry, at most 2 KiB where the footprint is near its bound, since nnz * K <= 512:
+	                 // never above 64 KiB.
+	                 in.toy_bytes <= 60 * 1024 &&
+	                 // Only while an iteration is a few hundred multiply-adds: measured through the CLI, inst1 0.70 -> 0.33 s and
+	                 // inst2 0.47 -> 0.21 s, but inst30-40 (170 entries x K=10) 0.32 -> 0.39 s -- one workgroup on an otherwise
+	                 // idle chip runs slowly, and two graph-replayed launches per iteration win again.
+	                 work <= 512.0 &&
+	                 !in.timing &&                          // one launch has no per-sweep times
+	                 in.iters >= 8 && in.resident &&
+	                 !in.adaptive;                          // the toy loop seeds unconditionally; an adaptive side's sweep is the unseeded one
+	if (toy) return {kLoopToy, 0, in.iters};
+	// errors + streams seeds unconditionally too: the two sweeps while a side is adaptive, whatever the plan's tables say
+	const Loop loop = in.es_mode && !in.adaptive ? kLoopEs : kLoopSweeps;
+	// Launch-bound regime (inst1: 100000 iterations of a 13-entry instance, ~4 us per launch): capture kGraphIters
+	// iterations into a HIP graph and replay it.  Only for small sweeps -- a large one is not launch-bound and a graph would
+	// pin its arguments for nothing --, never with per-launch timing (its events are host calls), nor beside extreme rows.
+	const bool replay = work < in.graph_max && !in.timing && !in.extreme && in.iters >= 4 * kGraphIters && in.graph;
+	if (!replay) return {loop, 0, in.iters};
+	return {loop, in.iters / kGraphIters, in.iters % kGraphIters};
 }
 
 // ---- errors + streams iteration (mf_stream.hip.h, mf_resident.hip.h)

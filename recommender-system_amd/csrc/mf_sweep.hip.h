@@ -1541,11 +1541,6 @@ struct ResidentArgs {
 	const double *__restrict__ csc_wgt;
 };
 
-constexpr size_t resident_lds_bytes(int users, int items, int K, long long nnz, bool weighted = false)
-{
-	return (size_t) 2 * (size_t) (users + items) * K * 8 + (size_t) nnz * 2 * (weighted ? 20 : 12) + (size_t) (users + items + 2) * 4 + 64;
-}
-
 // KMAX > 0: K <= KMAX and the owner keeps its old row and its accumulators in registers (loops fully unrolled, the
 // K loads of a gathered row issued together: one LDS latency per entry instead of one per element); KMAX == 0: any K.
 // The K <= 32 variant keeps three 32-double arrays (192 VGPRs) per thread: that fits the register file only with at
@@ -1558,7 +1553,7 @@ constexpr int resident_max_threads(int kmax) { return kmax == 32 ? 256 : 1024; }
 template <int KMAX, bool MOM = false, bool WGT = false>
 __global__ void __launch_bounds__(resident_max_threads(KMAX)) sweep_resident_kernel(ResidentArgs a)
 {
-	extern __shared__ __attribute__((aligned(16))) char rlds[];
+	extern __shared__ __attribute__((aligned(16))) char rlds[];   // the layout below in bytes: mf_sched::toy_lds_bytes (mf_schedule.h)
 	const int U = a.users, I = a.items, K = a.K, nnz = a.nnz;
 	const int nf = (U + I) * K;                 // doubles per generation: L rows, then R rows
 	double *gen0 = reinterpret_cast<double *>(rlds), *gen1 = gen0 + nf;

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, golden_in
+from test_iterate_path import path_of_plan
 from test_frozen import pack, seq_mean
 from test_momentum import BETA, MModel
 from test_regularised import CASES, LAM_I, LAM_U, LARGE, WIDE, ZERO_FORMS, _case_id, _pick, _small, _step, _toy, differs, fast_dot
@@ -475,7 +476,6 @@ def test_toy_loop_inside_one_launch(device, switches, K, mode):
     K - 1 on the users, a frozen column inside the items' range."""
     capi = device
     pat, L0, R0, val, alpha = _toy(K)
-    assert pat.users + pat.items <= 1024 and pat.nnz * K <= 512
     beta = BETA if "momentum" in mode else NO_BETA
     w = plain_weights(77 + K, pat.nnz) if "weights" in mode else None
     m = WModel(pat.users, pat.items, pat.row, pat.col, val, alpha, w) if w is not None else MModel(pat.users, pat.items, pat.row, pat.col, val, alpha)
@@ -483,9 +483,12 @@ def test_toy_loop_inside_one_launch(device, switches, K, mode):
     want = brun(m, L0, R0, 9, bounds, LAM, beta, frozen)
     assert differs(want[0], brun(m, L0, R0, 9, (NO_BOX, NO_BOX), LAM, beta, frozen)[0]) > 0.3
     for resident in (None, "0"):
-        switches({} if resident is None else {"MF_RESIDENT": resident})
+        env = {} if resident is None else {"MF_RESIDENT": resident}
+        switches(env)
         plan = _bounded_plan(capi, pat, K, val, alpha, bounds, beta=beta, frozen=frozen, weight=w)
         try:
+            loop = path_of_plan(plan.describe(), pat, K, 9, env, weighted=w is not None)[0]
+            assert loop == ("toy" if resident is None else "sweeps"), (K, mode, resident, loop)
             plan.upload(L0, R0)
             plan.iterate(9)
             L, R = plan.download()

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, golden_in, random_instance, to_text
+from test_iterate_path import described_path_inputs, iterate_path_of
 
 pytestmark = pytest.mark.gpu
 
@@ -778,6 +779,7 @@ def test_randomised_shapes_all_paths_bit_exact(capi, orc, monkeypatch):
     Everything must equal the oracle bit for bit."""
     rng = np.random.default_rng(20261004)
     ks = [1, 2, 3, 6, 10, 14, 20, 30, 31, 50, 64, 66, 100, 128, 130, 200, 256]
+    replayed = set()   # (replays, eager) of the 130-iteration runs
     for case in range(48):
         k = int(ks[case % len(ks)])
         u = int(rng.integers(1, 400))
@@ -788,18 +790,27 @@ def test_randomised_shapes_all_paths_bit_exact(capi, orc, monkeypatch):
             mask[rng.integers(0, u, 2), :] = rng.random((2, i)) < 0.95
             mask[:, rng.integers(0, i, 2)] = rng.random((u, 2)) < 0.95
         row, col = np.nonzero(mask)
-        iters = 130 if case % 8 == 5 else int(rng.integers(1, 4))     # >= 128 iterations: the graph path
+        iters = 130 if case % 8 == 5 else int(rng.integers(1, 4))     # >= 128 iterations: the graph path, asserted below
         d = dict(iters=iters, alpha=1e-3 / max(k, 1), feats=k, users=u, items=i, row=row.astype(np.int32),
                  col=col.astype(np.int32), val=rng.integers(1, 6, len(row)).astype(np.float64))
         if case % 4 == 1:
             monkeypatch.setenv("MF_SWEEP_LONG", "40")   # force the extreme-row path on small instances
         else:
             monkeypatch.delenv("MF_SWEEP_LONG", raising=False)
+        if iters == 130:   # what the rule says of this run, from the description of a plan of the same instance and switches
+            plan = capi.Plan(u, i, k, d["alpha"], d["row"], d["col"], d["val"])
+            try:
+                env = {s: os.environ[s] for s in ("MF_RESIDENT", "MF_GRAPH", "MF_GRAPH_MAX") if s in os.environ}
+                replayed.add(iterate_path_of(u, i, k, len(row), iters, env=env, **described_path_inputs(plan.describe(), u, i))[1:])
+            finally:
+                plan.close()
         L, R = capi.init_factors(u, i, k)
         best = capi.backend_run(_inst(capi, d), L, R)
         Lo, Ro, bo = _oracle_run(orc, d)
         assert np.array_equal(L, Lo) and np.array_equal(R, Ro), (case, u, i, k, dens, iters)
         assert np.array_equal(best, bo), (case, u, i, k)
+    # four replays of the captured graph and two eager iterations; beside the extreme rows MF_SWEEP_LONG makes, 130 eager ones
+    assert replayed == {(4, 2), (0, 130)}, replayed
 
 
 @pytest.mark.parametrize("u,i,k", [(0, 5, 3), (4, 0, 3), (0, 0, 2), (3, 4, 1), (1, 1, 2)])
@@ -1019,7 +1030,6 @@ def test_resident_toy_kernel_bit_exact(capi, orc, shape, monkeypatch):
     one, odd and even iteration counts) against the oracle and against the ordinary two-launch path."""
     u, i, k, dens, iters = shape
     d = random_instance(500 + u + k, u, i, k, density=dens, iters=iters, alpha=0.01)
-    assert len(d["row"]) * k <= 512
     inst = _inst(capi, d)
     L0, R0 = capi.init_factors(u, i, k)
     Lo, Ro = L0.copy(), R0.copy()
@@ -1027,6 +1037,9 @@ def test_resident_toy_kernel_bit_exact(capi, orc, shape, monkeypatch):
     got = {}
     for mode in ("1", "0"):
         monkeypatch.setenv("MF_RESIDENT", mode)
+        # a few dozen entries in rows of a few: the sweeps without extreme rows where the loop is not the toy's
+        loop = iterate_path_of(u, i, k, len(d["row"]), iters, env={"MF_RESIDENT": mode})[0]
+        assert loop == ("toy" if mode == "1" else "sweeps"), (shape, mode, loop)
         L, R = L0.copy(), R0.copy()
         capi.backend_factorize(inst, L, R)
         got[mode] = (L, R)

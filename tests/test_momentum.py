@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, golden_in
+from test_iterate_path import path_of_plan
 from test_regularised import CASES, LAM_I, LAM_U, WIDE, ZERO_FORMS, Model, Side, _case_id, _pick, _small, _toy, decay, differs, fast_dot, model_sweep
 from test_sweep_edges import (CLASSES, FORMS, PF_ROWS, SWEEPS, SWITCHES, _single_wave, assert_same_bits, cls_signed, is_negzero, pattern,
                               pattern_both_large, seq_dot, signed_inputs)
@@ -476,17 +477,20 @@ def test_toy_single_launch_loop(device, switches, K):
     this is the two-launch path carrying its history across calls; test_toy_loop_inside_one_launch has the single launch."""
     capi = device
     pat, L0, R0, val, alpha = _toy(K)
-    assert pat.users + pat.items <= 1024 and pat.nnz * K <= 512
     m = MModel(pat.users, pat.items, pat.row, pat.col, val, alpha)
     for beta in (BETA, (0.0, BETA_I)):
         want = m.run(L0, R0, 9, beta=beta)
         assert differs(want[0], m.run(L0, R0, 9, beta=(0.0, 0.0))[0]) > 0.5
         for mode in (None, "0"):
-            switches({} if mode is None else {"MF_RESIDENT": mode})
+            env = {} if mode is None else {"MF_RESIDENT": mode}
+            switches(env)
             plan = capi.Plan(pat.users, pat.items, K, alpha, pat.row, pat.col, val)
             try:
                 plan.set_regularization(LAM_U, LAM_I)
                 plan.set_momentum(*beta)
+                # a toy instance -- eight iterations would be one launch -- whose calls of five and of four are the sweeps
+                loops = [path_of_plan(plan.describe(), pat, K, n, env)[0] for n in (8, 5, 4)]
+                assert loops == ["toy" if mode is None else "sweeps", "sweeps", "sweeps"], loops
                 plan.upload(L0, R0)
                 plan.iterate(5)
                 plan.iterate(4)
@@ -513,7 +517,6 @@ def test_toy_loop_inside_one_launch(device, switches, K):
     iteration) gives the same bits."""
     capi = device
     pat, L0, R0, val, alpha = _toy(K)
-    assert pat.users + pat.items <= 1024 and pat.nnz * K <= 512
     m = MModel(pat.users, pat.items, pat.row, pat.col, val, alpha)
     Lp, Rp = random_prev(80 + K, L0), random_prev(90 + K, R0)
 
@@ -534,7 +537,8 @@ def test_toy_loop_inside_one_launch(device, switches, K):
     one_side = (0.0, BETA_I)
     o17 = m.run(L0, R0, 17, beta=one_side)
     for mode in (None, "0"):
-        switches({} if mode is None else {"MF_RESIDENT": mode})
+        env = {} if mode is None else {"MF_RESIDENT": mode}
+        switches(env)
         where = "K=%d MF_RESIDENT=%s" % (K, mode)
 
         def fresh(beta=BETA):
@@ -542,6 +546,9 @@ def test_toy_loop_inside_one_launch(device, switches, K):
             p.set_regularization(LAM_U, LAM_I)
             p.set_momentum(*beta)
             p.upload(L0, R0)
+            # every count this test calls with (iterate_monitored(18, every=9) calls with 9): one launch, or the sweeps
+            loops = {path_of_plan(p.describe(), pat, K, n, env)[0] for n in (8, 9)}
+            assert loops == ({"toy"} if mode is None else {"sweeps"}), (where, loops)
             return p
         a, b, c, d, e = fresh(), fresh(), fresh(), fresh(), fresh(one_side)
         try:

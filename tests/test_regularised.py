@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, golden_in
+from test_iterate_path import path_of_plan
 from test_loss import model_total
 from test_sweep_edges import (CLASSES, FORMS, GRID_CAP, PF_ROWS, SINGLE, SWEEPS, SWITCHES, Pattern, _single_wave, assert_same_bits,
                               cls_signed, pattern, pattern_both_large, pattern_one_large, seq_dot, signed_inputs)
@@ -438,19 +439,21 @@ def test_toy_single_launch_loop(device, orc, switches, K):
     path and counts nine launches per side), and at lambda = 0 the oracle's."""
     capi = device
     pat, L0, R0, val, alpha = _toy(K)
-    assert pat.users + pat.items <= 1024 and pat.nnz * K <= 512
     m = Model(pat.users, pat.items, pat.row, pat.col, val, alpha)
     want = m.iterate(L0, R0, 9, LAM_U, LAM_I)
     assert differs(want[0], m.iterate(L0, R0, 9, 0.0, 0.0)[0]) > 0.5
     Lo, Ro = L0.copy(), R0.copy()
     orc.factorize(orc.Instance(9, alpha, K, pat.users, pat.items, pat.row, pat.col, val), Lo, Ro)
     for mode, timed in ((None, False), ("0", False), (None, True)):
-        switches({} if mode is None else {"MF_RESIDENT": mode})
+        env = {} if mode is None else {"MF_RESIDENT": mode}
+        switches(env)
         for lam, (wl, wr) in (((LAM_U, LAM_I), want), ((0.0, 0.0), (Lo, Ro))):
             plan = capi.Plan(pat.users, pat.items, K, alpha, pat.row, pat.col, val)
             try:
                 plan.set_regularization(*lam)
                 plan.timing(timed)
+                loop = path_of_plan(plan.describe(), pat, K, 9, env, timing=timed)[0]
+                assert loop == ("toy" if mode is None and not timed else "sweeps"), (loop, mode, timed)
                 plan.upload(L0, R0)
                 plan.iterate(9)
                 L, R = plan.download()

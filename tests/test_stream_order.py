@@ -37,6 +37,7 @@ import pytest
 import torch
 
 from conftest import random_instance
+from test_iterate_path import iterate_path_of, path_of_plan
 from test_bounded import BOX, NO_BOX, bstep, clip, counts
 from test_loss import model_total
 from test_momentum import BETA as TOY_BETA
@@ -476,8 +477,9 @@ def _weighted_setup(plan):
     plan.set_regularization(*LAM)
 
 
-def _case(name, pat, K, env, check, calls, model, setup=_no_setup, weights=None, timed=False):
-    return dict(name=name, pat=pat, K=K, env=env, check=check, calls=calls, model=model, setup=setup, weights=weights, timed=timed)
+def _case(name, pat, K, env, check, calls, model, setup=_no_setup, weights=None, timed=False, path=None):
+    """path: (iters, (loop, replays, eager)) -- what the rule of mf_plan_iterate (test_iterate_path.py) must say of the case's one call"""
+    return dict(name=name, pat=pat, K=K, env=env, check=check, calls=calls, model=model, setup=setup, weights=weights, timed=timed, path=path)
 
 
 def a_cases():
@@ -500,10 +502,11 @@ def a_cases():
     out += [_case("decay-frozen-box-K30-iterate3", "pair", 30, SWEEPS, _one_kernel(30), _iterate(3),
                   _rule_model(3, bounds=BOXES, lam=LAM, frozen=FROZEN), setup=_composed_setup),
             _case("errors-resident-streams-K30-iterate3", "pair", 30, ES, _es, _iterate(3), _oracle_model(3)),
-            _case("graph-sweeps-K30-iterate130", "pair", 30, SWEEPS, _graphed(_one_kernel(30)), _iterate(130), _oracle_model(130)),
-            _case("graph-es-K30-iterate130", "pair", 30, ES, _graphed(_es), _iterate(130), _oracle_model(130)),
-            _case("toy-loop-in-one-launch-K3-iterate9", "toy", 3, {}, lambda d: True, _iterate(9),
-                  _rule_model(9, lam=TOY_LAM, beta=TOY_BETA), setup=_toy_setup),
+            _case("graph-sweeps-K30-iterate130", "pair", 30, SWEEPS, _graphed(_one_kernel(30)), _iterate(130), _oracle_model(130),
+                  path=(130, ("sweeps", 4, 2))),
+            _case("graph-es-K30-iterate130", "pair", 30, ES, _graphed(_es), _iterate(130), _oracle_model(130), path=(130, ("es", 4, 2))),
+            _case("toy-loop-in-one-launch-K3-iterate9", "toy", 3, {}, lambda d: " iterate=sweeps" in d, _iterate(9),
+                  _rule_model(9, lam=TOY_LAM, beta=TOY_BETA), setup=_toy_setup, path=(9, ("toy", 0, 9))),
             _case("weighted-twins-K30-iterate3", "pair", 30, SWEEPS, lambda d: _one_kernel(30)(d) and " weighted=1" in d, _iterate(3),
                   _rule_model(3, weights=_weights, lam=LAM), setup=_weighted_setup, weights=_weights),
             _case("timed-plan-K30-iterate3", "pair", 30, SWEEPS, _one_kernel(30), _iterate(3), _oracle_model(3), timed=True)]
@@ -520,10 +523,11 @@ def test_every_launch_path_of_the_issue_is_in_the_table():
                  "both-sides", "both-large", "cooperative", "momentum-from-rest-pair-K30-iterate3", "momentum-from-rest-long-items-K30-steps", "decay-frozen-box",
                  "errors-resident-streams", "graph-sweeps", "graph-es", "toy-loop", "weighted-twins", "timed-plan"):
         assert any(part in n for n in names), part
-    toy = source("toy", 3)
-    assert toy.pat.users + toy.pat.items <= 1024 and toy.pat.nnz * 3 <= 512       # one launch runs the loop from eight iterations on
-    pair = source("pair", 30)
-    assert pair.pat.nnz * 30 < 2e6                                                # below MF_GRAPH_MAX's default: iterate(130) captures
+    # the shapes alone, before a plan says the rest: one launch runs the toy's nine iterations, iterate(130) of the pair captures
+    toy, pair = source("toy", 3).pat, source("pair", 30).pat
+    assert iterate_path_of(toy.users, toy.items, 3, toy.nnz, 9) == ("toy", 0, 9)
+    assert iterate_path_of(pair.users, pair.items, 30, pair.nnz, 130) == ("sweeps", 4, 2)
+    assert [c["name"] for c in A_CASES if c["path"]] == ["graph-sweeps-K30-iterate130", "graph-es-K30-iterate130", "toy-loop-in-one-launch-K3-iterate9"]
 
 
 @gpu
@@ -545,6 +549,9 @@ def test_sweep_launch_paths_behind_a_closed_gate(device, switches, gate, case):
         plan.timing(case["timed"])
         desc = plan.describe()
         assert case["check"](desc), desc
+        if case["path"]:
+            iters, want = case["path"]
+            assert path_of_plan(desc, pat, K, iters, case["env"], timing=case["timed"], weighted=w is not None) == want, desc
         plan.set_stream(gate.s.cuda_stream)
         where = "%s [%s]" % (case["name"], desc.split(" loss=")[0])
         got = behind_gate(gate, plan, bufs, src.L0, src.R0, case["calls"], where)

@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, golden_in, to_text
+from test_iterate_path import iterate_path_of, path_of_plan, toy_lds_bytes
 from test_loss import KS as LOSS_KS
 from test_loss import loss_shape
 from test_loss import instance as loss_instance
@@ -661,7 +662,6 @@ def test_toy_loop_inside_one_launch(device, switches, K):
     read their history from the other buffer."""
     capi = device
     pat, L0, R0, val, alpha = _toy(K)
-    assert pat.users + pat.items <= 1024 and pat.nnz * K <= 512
     w = plain_weights(60 + K, pat.nnz)
     w[:2] = [0.0, 1.0]
     m = WModel(pat.users, pat.items, pat.row, pat.col, val, alpha, w)
@@ -669,10 +669,13 @@ def test_toy_loop_inside_one_launch(device, switches, K):
         w9, w18 = m.wrun(L0, R0, 9, beta=beta), m.wrun(L0, R0, 18, beta=beta)
         assert differs(w9[0], MModel(pat.users, pat.items, pat.row, pat.col, val, alpha).run(L0, R0, 9, beta=beta)[0]) > 0.5
         for mode in (None, "0"):
-            switches({} if mode is None else {"MF_RESIDENT": mode})
+            env = {} if mode is None else {"MF_RESIDENT": mode}
+            switches(env)
             plan = _plan(capi, pat, K, val, alpha, w, beta=beta)
             try:
                 where = "K=%d MF_RESIDENT=%s beta=%s" % (K, mode, beta)
+                loop = path_of_plan(plan.describe(), pat, K, 9, env, weighted=True)[0]
+                assert loop == ("toy" if mode is None else "sweeps"), (where, loop)
                 plan.upload(L0, R0)
                 plan.iterate(9)
                 L, R = plan.download()
@@ -690,8 +693,8 @@ def test_toy_loop_inside_one_launch(device, switches, K):
 def test_toy_loop_at_the_edge_of_its_lds_rule(device, switches):
     """The toy rule looks at the unweighted footprint (<= 60 KiB) and the weighted launch asks for 16 bytes more per entry.
     600 users + 424 items at K = 3 with 170 entries: 1024 threads, 57 400 bytes unweighted, 60 120 with the weights -- the
-    largest toy instance there is at this K (entries x K <= 512).  The request cannot pass 64 KiB: 60 KiB + 16 x 512 / K
-    bytes needs (users + items) x K above 3500, so K >= 4 and at most 2 KiB of weights."""
+    largest toy instance there is at this K (the rule bounds entries x K: test_iterate_path.py).  The request cannot pass
+    64 KiB: 60 KiB + 16 x 512 / K bytes needs (users + items) x K above 3500, so K >= 4 and at most 2 KiB of weights."""
     capi = device
     K, U, I, nnz = 3, 600, 424, 170
     rng = np.random.default_rng(321)
@@ -699,15 +702,20 @@ def test_toy_loop_at_the_edge_of_its_lds_rule(device, switches):
     from test_sweep_edges import Pattern
     pat = Pattern("toy-edge", U, I, (cells // I).astype(np.int32), (cells % I).astype(np.int32))
     L0, R0, val, alpha = cls_signed(322, pat, K)
-    plain_need = 2 * (U + I) * K * 8 + nnz * 24 + (U + I + 2) * 4 + 64
-    assert U + I == 1024 and nnz * K <= 512 < (nnz + 1) * K and plain_need == 57400 <= 60 * 1024 and plain_need + 16 * nnz == 60120
+    plain_need, weighted_need = toy_lds_bytes(U, I, K, nnz), toy_lds_bytes(U, I, K, nnz, True)
+    assert U + I == 1024 and plain_need == 57400 <= 60 * 1024 and weighted_need == 60120 == plain_need + 16 * nnz
+    # the largest: one entry more and the rule, asked with every other term as it is, turns the instance away
+    assert iterate_path_of(U, I, K, nnz, 9, weighted=True)[0] == "toy" and iterate_path_of(U, I, K, nnz + 1, 9, weighted=True)[0] == "sweeps"
     w = plain_weights(323, nnz)
     m = WModel(U, I, pat.row, pat.col, val, alpha, w)
     want = m.wrun(L0, R0, 9)
     for mode in (None, "0"):
-        switches({} if mode is None else {"MF_RESIDENT": mode})
+        env = {} if mode is None else {"MF_RESIDENT": mode}
+        switches(env)
         plan = _plan(capi, pat, K, val, alpha, w)
         try:
+            loop = path_of_plan(plan.describe(), pat, K, 9, env, weighted=True)[0]
+            assert loop == ("toy" if mode is None else "sweeps"), (mode, loop)
             plan.upload(L0, R0)
             plan.iterate(9)
             L, R = plan.download()
