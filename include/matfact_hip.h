@@ -775,6 +775,64 @@ int mf_backend_gram_dot(const double *left, const double *right, int32_t feature
 int mf_backend_run_implicit(const mf_problem *p, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
                             double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, double conf, int device);
 
+/* ---- ALS by conjugate gradient: a fixed, small number of conjugate-gradient (CG) steps per row, warm-started from the row's
+ * current value, in place of the direct solve above (Takacs, Pilaszy, Tikk, RecSys 2011).  The Gram matrix of a row is never
+ * formed -- its product with a vector p is  sum_n w_n y_n (y_n . p) + ridge p  -- so K goes up to MF_ALS_CG_MAX_K = 256.
+ *
+ * mf_plan_set_als_cg(plan, steps) / mf_plan_get_als_cg(plan, &steps).  steps = 0, the default, is the direct solve: every
+ * bit and every launched kernel is what it is without this section.  1 <= steps <= MF_ALS_CG_MAX_STEPS switches the solve to
+ * CG: with the kind MF_ALS_RIDGE or MF_ALS_RIDGE_COUNT set, mf_plan_als_solve(plan, side, other_generation) then computes
+ * every row r of side X as below.  The setting is read at every launch.
+ *
+ * Inputs as in steps 1-10 of the direct definition: Y the other side in the named generation, X_old X's current buffer, the
+ * row's entries n = 0 .. cnt-1 in the side's entry order, a_n the value, w_n the weight (weighted plan only), y_n the Y row,
+ * f the side's frozen column or none, ridge = lambda_side or lambda_side * (double) cnt under MF_ALS_RIDGE_COUNT.  FP64
+ * throughout, every operation rounded once, nothing fused, / correctly rounded, no matrix-core instruction.
+ * dot(u, v) is  s = 0.0,  then  s = s + (u[k] * v[k])  for k = 0 .. K-1 ascending.  The padding of a row is never read or
+ * written.
+ *   C0. x = X_old[r][0..K).
+ *   C1. For every entry:  t_n = dot(y_n, x);  d_n = a_n - t_n;  dw_n = d_n * w_n on a weighted plan, dw_n = d_n otherwise.
+ *   C2. g[k] starts at 0.0; for n ascending  g[k] = g[k] + (dw_n * y_n[k]).  Then  r[k] = g[k] - (ridge * x[k]);  with a
+ *       frozen column  r[f] = 0.0.
+ *   C3. p = r;  rs = dot(r, r).
+ *   C4. For s = 1 .. steps:
+ *       a. If rs == 0.0 leave the loop (a NaN is not equal and goes on).
+ *       b. u_n = dot(y_n, p);  uw_n = u_n * w_n on a weighted plan, u_n otherwise.
+ *       c. q[k] starts at 0.0; for n ascending  q[k] = q[k] + (uw_n * y_n[k]).  Then  q[k] = q[k] + (ridge * p[k]);  with a
+ *          frozen column  q[f] = 0.0.
+ *       d. pq = dot(p, q).  If !(pq > 0.0) the row is NOT POSITIVE DEFINITE (a NaN fails too): it keeps X_old's bits, is
+ *          counted as such, and ends here.
+ *       e. alpha = rs / pq;  x[k] = x[k] + (alpha * p[k]);  r[k] = r[k] - (alpha * q[k]).
+ *       f. rn = dot(r, r);  beta = rn / rs;  p[k] = r[k] + (beta * p[k]);  rs = rn.  (After the last step this sub-step does
+ *          not reach the stored row; the kernels skip it.)
+ *   C5. The box projection of mf_plan_set_bounds on the bounded columns, then the frozen select (column f keeps X_old's
+ *       bits), then the store.  The row is counted as solved.
+ * A row without entries keeps X_old's bits, is not projected and is counted kept_empty, as in the direct solve.  Nothing else
+ * is special: infinities, NaN, subnormals and signed zeros follow IEEE 754 through the steps.  alpha of the plan is not read.
+ * The three counters are mf_plan_als_info's, unchanged in meaning, and the objective a step cannot increase in exact
+ * arithmetic is the one the direct definition names.
+ *
+ * Limits and refusals.  1 <= K <= 256 under CG: with the steps set, mf_plan_set_als accepts K up to 256 (a caller at K in
+ * 129..256 sets the steps first); with steps = 0 it refuses K > 128 as before.  mf_plan_set_als_cg returns
+ * MF_ERR_UNSUPPORTED with nothing changed for nonzero steps at K > 256 and for steps = 0 while an ALS kind is on and K > 128;
+ * steps < 0 or > MF_ALS_CG_MAX_STEPS -> MF_ERR_ARGUMENT before any HIP call.  MF_ALS_IMPLICIT together with CG is refused:
+ * whichever of mf_plan_set_als / mf_plan_set_als_cg comes second returns MF_ERR_UNSUPPORTED with nothing changed.  Momentum
+ * and adaptive sides stay refused with ALS, the item solve on a shard or a 2-D tile stays MF_ERR_UNSUPPORTED, the user solve
+ * works on any shard.  mf_plan_als_solve only enqueues on the plan's stream, under CG as without.  One iteration of
+ * mf_plan_iterate / mf_plan_iterate_monitored is the same  als_solve(users, 0);  als_solve(items, 1);  flip.
+ * While CG is on and a kind is set mf_plan_describe appends  als=ridge|ridge-count als_cg=<steps>
+ * als_cg_form=<form>(chunk=<entries>)  without als_form=.  The forms (MF_ALS_CG_FORM=fixed|dma|general: a compile-time K of
+ * the sweeps' list, any even K, any K; by default the first of these that takes the K) give the same bits.
+ * Not part of this: CG under the implicit kind, preconditioning, a residual-based stop, K above 256, sharded item solves. */
+#define MF_ALS_CG_MAX_STEPS 256
+#define MF_ALS_CG_MAX_K     256
+int mf_plan_set_als_cg(mf_plan *plan, int steps);
+int mf_plan_get_als_cg(mf_plan *plan, int *steps);
+/* level 1: mf_backend_run_als with the steps (0: the direct solve).  Bad arguments -> MF_ERR_ARGUMENT before any HIP call. */
+int mf_backend_run_als_cg(const mf_problem *p, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
+                          double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, int kind, int steps,
+                          int device);
+
 /* ---- Ranks of the held-out entries: where each held-out item lands in its user's recommendation order, for the plan's
  * current factors.  An extension (the reference ranks nothing), so the definition is this library's.  For held-out entry
  * n = (i, j, a) -- the rating a plays no part --

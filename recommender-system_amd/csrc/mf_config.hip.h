@@ -35,6 +35,7 @@ struct mf_config {
 	bool build_host = false;          // MF_BUILD=host: CSR/CSC bucketed on the host
 	bool os_dpp = true;               // MF_OS_DPP=0: ordered sums by plain v_add_f64 (no DPP broadcast)
 	int als_form = -1;                // MF_ALS_FORM=wg|wave: the ALS solve as one workgroup / one wave per row (-1: by K)
+	int als_cg_form = -1;             // MF_ALS_CG_FORM=fixed|dma|general: the form of the conjugate-gradient ALS solve (-1: by K)
 	bool multi_force = false;         // MF_MULTI_FORCE=1: sharded path even with one shard
 	bool multi_rccl = false;          // MF_MULTI_REDUCE=rccl|peer
 	bool multi_threads = true;        // MF_MULTI_THREADS=0: all shards enqueued from the calling thread
@@ -72,6 +73,7 @@ struct mf_config {
 		c.build_host = eq(getenv("MF_BUILD"), "host");
 		c.os_dpp = !is0(getenv("MF_OS_DPP"));
 		if ((v = getenv("MF_ALS_FORM"))) c.als_form = eq(v, "wg") ? 0 : eq(v, "wave") ? 1 : -1;
+		if ((v = getenv("MF_ALS_CG_FORM"))) c.als_cg_form = eq(v, "fixed") ? 0 : eq(v, "dma") ? 1 : eq(v, "general") ? 2 : -1;
 		c.multi_force = eq(getenv("MF_MULTI_FORCE"), "1");
 		c.multi_rccl = eq(getenv("MF_MULTI_REDUCE"), "rccl");
 		c.multi_threads = !is0(getenv("MF_MULTI_THREADS"));
@@ -104,6 +106,7 @@ struct mf_config {
 		if (build_host) add("MF_BUILD", "host");
 		if (!os_dpp) add("MF_OS_DPP", "0");
 		if (als_form >= 0) add("MF_ALS_FORM", als_form ? "wave" : "wg");
+		if (als_cg_form >= 0) add("MF_ALS_CG_FORM", als_cg_form == 0 ? "fixed" : als_cg_form == 1 ? "dma" : "general");
 		if (multi_force) add("MF_MULTI_FORCE", "1");
 		if (multi_rccl) add("MF_MULTI_REDUCE", "rccl");
 		if (!multi_threads) add("MF_MULTI_THREADS", "0");

@@ -606,7 +606,9 @@ int mf_plan_set_als(mf_plan *p, int kind)
 {
 	if (!p || !(als_kind_ok(kind) || kind == MF_ALS_IMPLICIT)) return MF_ERR_ARGUMENT;
 	if (kind != MF_ALS_OFF) {
-		if (p->K > mf::kAlsMaxK) return MF_ERR_UNSUPPORTED;   // the triangle of a row lives in LDS
+		// the triangle of a row lives in LDS; the conjugate-gradient solve forms none, and has no implicit kind
+		if (p->K > (p->als_cg > 0 ? mf_sched::kAlsCgMaxK : mf::kAlsMaxK)) return MF_ERR_UNSUPPORTED;
+		if (kind == MF_ALS_IMPLICIT && p->als_cg > 0) return MF_ERR_UNSUPPORTED;
 		// a solve has neither a previous step nor a gradient: momentum or an adaptive side came first
 		if (p->rule[0].beta != 0.0 || p->rule[1].beta != 0.0 || adaptive_any(p)) return MF_ERR_UNSUPPORTED;
 	}
@@ -628,6 +630,22 @@ int mf_plan_get_als(mf_plan *p, int *kind)
 {
 	if (!p) return MF_ERR_ARGUMENT;
 	if (kind) *kind = p->als_kind;
+	return MF_OK;
+}
+
+int mf_plan_set_als_cg(mf_plan *p, int steps)
+{
+	if (!p || steps < 0 || steps > MF_ALS_CG_MAX_STEPS) return MF_ERR_ARGUMENT;
+	if (steps > 0 && (p->K > mf_sched::kAlsCgMaxK || p->als_kind == MF_ALS_IMPLICIT)) return MF_ERR_UNSUPPORTED;
+	if (steps == 0 && p->als_kind != MF_ALS_OFF && p->K > mf::kAlsMaxK) return MF_ERR_UNSUPPORTED;   // the direct solve has no such K
+	p->als_cg = steps;   // read at every launch
+	return MF_OK;
+}
+
+int mf_plan_get_als_cg(mf_plan *p, int *steps)
+{
+	if (!p) return MF_ERR_ARGUMENT;
+	if (steps) *steps = p->als_cg;
 	return MF_OK;
 }
 
@@ -1031,7 +1049,10 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 		append(buf, buflen, " adaptive=%s/%s", sd[1], sd[0]);
 	}
 	// the solver of mf_plan_iterate when it is not the gradient step, and the form its solves launch
-	if (p->als_kind == MF_ALS_RIDGE || p->als_kind == MF_ALS_RIDGE_COUNT) {
+	if ((p->als_kind == MF_ALS_RIDGE || p->als_kind == MF_ALS_RIDGE_COUNT) && p->als_cg > 0) {
+		append(buf, buflen, " als=%s als_cg=%d als_cg_form=%s(chunk=%d)", p->als_kind == MF_ALS_RIDGE ? "ridge" : "ridge-count", p->als_cg,
+		       kAlsCgFormName[als_cg_form(p->K, p->cfg.als_cg_form)], als_cg_chunk(p->K));
+	} else if (p->als_kind == MF_ALS_RIDGE || p->als_kind == MF_ALS_RIDGE_COUNT) {
 		const AlsForm &form = kAlsForm[als_form(p->K, p->cfg.als_form)];
 		append(buf, buflen, " als=%s als_form=%s(chunk=%d)", p->als_kind == MF_ALS_RIDGE ? "ridge" : "ridge-count", form.name, form.nch);
 	}
@@ -1162,13 +1183,22 @@ int mf_backend_run_adaptive(const mf_problem *pr, const double *weight, double *
 int mf_backend_run_als(const mf_problem *pr, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
                        double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, int kind, int device)
 {
+	return mf_backend_run_als_cg(pr, weight, L, R, best, lambda_users, lambda_items, bounds_users, bounds_items, kind, 0, device);
+}
+
+// ... with the steps of the conjugate-gradient solve (0: the direct one), set before the kind: K may lie in 129 .. 256
+int mf_backend_run_als_cg(const mf_problem *pr, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
+                          double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, int kind, int steps,
+                          int device)
+{
 	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !bounds_record_ok(bounds_users, pr->features) ||
-	    !bounds_record_ok(bounds_items, pr->features) || !als_kind_ok(kind))
+	    !bounds_record_ok(bounds_items, pr->features) || !als_kind_ok(kind) || steps < 0 || steps > MF_ALS_CG_MAX_STEPS)
 		return MF_ERR_ARGUMENT;
 	const RulePair rule = level1_rules(lambda_users, lambda_items, 0.0, 0.0, bounds_users, bounds_items);
 	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
 		p->rule[0] = rule[0], p->rule[1] = rule[1];
-		int rc = mf_plan_set_als(p, kind);
+		int rc = mf_plan_set_als_cg(p, steps);
+		if (rc == MF_OK) rc = mf_plan_set_als(p, kind);
 		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
 		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
 		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);

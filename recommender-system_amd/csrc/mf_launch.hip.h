@@ -580,6 +580,11 @@ AlsFormId als_form(int K, int forced)
 	return K <= 16 ? kAlsWave : kAlsWg;
 }
 
+// The form of a conjugate-gradient solve at this K and its entries per chunk: the pure rules of mf_schedule.h, fed with
+// MF_ALS_CG_FORM and the tile geometry of mf_als_cg.hip.h.
+mf_sched::AlsCgFormId als_cg_form(int K, int forced) { return mf_sched::als_cg_form(K, forced); }
+int als_cg_chunk(int K) { return mf_sched::als_cg_chunk(2 * (size_t) mf::als_cg_vec_bytes(K), (size_t) mf::als_cg_row_stride(K), kLdsPerCu); }
+
 // ---- the Gram of a whole side (mf_gram.hip.h)
 
 int gram_blocks(int rows) { return (rows + mf::kLossBlock - 1) / mf::kLossBlock; }
@@ -622,6 +627,51 @@ int launch_gram(mf_plan *p, int side, int generation)
 	return MF_OK;
 }
 
+// The conjugate-gradient solve of a side (mf_plan_set_als_cg with steps > 0; the counters are zeroed): one wave per row, one
+// launch over the side's rows in its dispatch order, as the direct solve below.  The steps and the rule of the side are read
+// here, at every launch.
+int launch_als_cg(mf_plan *p, int side, int other_generation, unsigned long long *counts)
+{
+	const SweepSide &sd = p->side[side];
+	const AlsCgFn fn = als_cg_fn(als_cg_form(p->K, p->cfg.als_cg_form), p->K);
+	if (!fn) return MF_ERR_UNSUPPORTED;   // a missing instance is an error, never another kernel
+	const int nch = als_cg_chunk(p->K);
+	const size_t lds = mf::als_cg_lds_bytes(p->K, nch);
+	MF_HIP(raise_lds_limit((const void *) fn, lds));
+
+	const SideUpdate u = side_update(p, side, 1);
+	const SideOperands x = side_operands(p, side);
+	mf::AlsArgs a;
+	a.K = p->K;
+	a.ldx = x.ldx;
+	a.ldy = x.ldy;
+	a.frozen = u.frozen;
+	a.count_scaled = p->als_kind == MF_ALS_RIDGE_COUNT;
+	a.lambda = p->rule[side].lambda;
+	a.ptr = x.ptr;
+	a.idx = x.idx;
+	a.val = x.val;
+	a.wgt = x.wgt;
+	a.X_old = x.X_old;
+	a.X_new = x.X_new;
+	a.Y = other_generation ? side_operands(p, side ^ 1).X_new : x.Y_old;
+	a.counts = counts;
+	a.box = u.box;
+	auto launch = [&](const int *rowlist, int nrows) {
+		if (nrows <= 0) return MF_OK;
+		a.rowlist = rowlist;
+		a.nrows = nrows;
+		hipLaunchKernelGGL(fn, dim3(nrows), dim3(mf::kWave), lds, p->stream, a, p->als_cg, nch);
+		MF_HIP(hipGetLastError());
+		return MF_OK;
+	};
+	if (sd.n_long > 0) {
+		MF_TRY(launch(sd.long_rows, sd.n_long));
+		return launch(sd.short_rows, sd.n_short);
+	}
+	return launch(sd.lpt ? sd.short_rows.get() : nullptr, sd.nrows);
+}
+
 // One solve of a side (0: items, 1: users) against the other side's current (0) or next (1) buffer, into the side's
 // next buffer: the counters zeroed, then one launch over the side's rows in its dispatch order -- the extreme rows of a
 // split side first, they are its longest.  The rule of the side is read here, at every launch.  Under MF_ALS_IMPLICIT the
@@ -635,6 +685,7 @@ int launch_als(mf_plan *p, int side, int other_generation)
 	unsigned long long *counts = p->als_counts.get() + 3 * side;
 	MF_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(unsigned long long), p->stream));
 	if (sd.nrows <= 0) return MF_OK;
+	if (p->als_cg > 0) return launch_als_cg(p, side, other_generation, counts);
 	const AlsForm &form = kAlsForm[als_form(p->K, p->cfg.als_form)];
 	const int groups = mf::kAlsThreads / form.threads;
 	const int nb = (mf::als_blocks(p->K, form.bs) + form.threads - 1) / form.threads;

@@ -257,6 +257,28 @@ const AlsForm kAlsForm[kAlsForms] = {
      {mf::als_kernel<mf::kWave, 2, 1>, mf::als_kernel<mf::kWave, 2, 2>, mf::als_kernel<mf::kWave, 2, 3>},
      {mf::als_kernel<mf::kWave, 2, 1, mf::AlsImplicit>, mf::als_kernel<mf::kWave, 2, 2, mf::AlsImplicit>, mf::als_kernel<mf::kWave, 2, 3, mf::AlsImplicit>}},
 };
+// The forms of the conjugate-gradient solve (mf_als_cg.hip.h) in the order of mf_sched::AlsCgFormId; als_cg_form (mf_launch.hip.h)
+// picks one, als_cg_fn its instance for a K the form takes.
+using AlsCgFn = void (*)(mf::AlsArgs, int, int);
+const char *const kAlsCgFormName[mf_sched::kAlsCgForms] = {"fixed", "dma", "general"};
+inline AlsCgFn als_cg_fn(int form, int K)
+{
+	if (form == mf_sched::kAlsCgFixed) {
+		switch (K) {
+		case 10: return mf::als_cg_kernel<10, 1, true>;
+		case 20: return mf::als_cg_kernel<20, 1, true>;
+		case 30: return mf::als_cg_kernel<30, 1, true>;
+		case 50: return mf::als_cg_kernel<50, 1, true>;
+		case 100: return mf::als_cg_kernel<100, 1, true>;
+		case 128: return mf::als_cg_kernel<128, 1, true>;
+		case 256: return mf::als_cg_kernel<256, 2, true>;
+		}
+		return nullptr;
+	}
+	const bool two = mf::als_cg_passes(K) == 2;
+	if (form == mf_sched::kAlsCgDma) return two ? mf::als_cg_kernel<0, 2, true> : mf::als_cg_kernel<0, 1, true>;
+	return two ? mf::als_cg_kernel<0, 2, false> : mf::als_cg_kernel<0, 1, false>;
+}
 // the Gram of a whole side (mf_gram.hip.h) by blocks of the triangle per thread, as the workgroup form above
 const GramFn kGramFn[3] = {mf::gram_block_kernel<1>, mf::gram_block_kernel<2>, mf::gram_block_kernel<3>};
 
@@ -288,6 +310,7 @@ struct mf_plan {
 	// alternating least squares (mf_als.hip.h): the kind (mf_plan_set_als; OFF: the plan of every other section) and the
 	// three row counts of each side's last solve, [side][solved, kept_empty, kept_not_pd], allocated on first use
 	int als_kind = MF_ALS_OFF;
+	int als_cg = 0;   // conjugate-gradient steps per row (mf_plan_set_als_cg; 0: the direct solve), read at every launch
 	dev_buf<unsigned long long> als_counts;
 	// implicit feedback: the confidence scale (mf_plan_set_confidence, read at every launch) and the Gram matrices of the two
 	// sides (mf_plan_gram): [items | users], each a packed lower triangle, and the per-block partials they are summed from

@@ -514,4 +514,36 @@ inline size_t es_resident_lds(int yrows_max, int slice_width, int waves, int wav
 	return (size_t) yrows_max * slice_width * 8 + (size_t) waves * wave_lds;
 }
 
+// ---- the form of a conjugate-gradient ALS solve (mf_als_cg.hip.h), chosen at every launch.  Every form gives the same bits.
+//   fixed    compile-time K, LDS-DMA gather: the K the sweeps have instances for;
+//   dma      run-time even K, LDS-DMA gather;
+//   general  any K from 1 to 256, the only form of an odd K: the gathered rows go through registers.
+// The values are the indices of kAlsCgForm (mf_plan.hip.h) and what MF_ALS_CG_FORM=fixed|dma|general stores.
+enum AlsCgFormId { kAlsCgFixed = 0, kAlsCgDma = 1, kAlsCgGeneral = 2, kAlsCgForms = 3 };
+constexpr int kAlsCgMaxK = 256;
+constexpr bool als_cg_fixed_k(int K) { return K == 10 || K == 20 || K == 30 || K == 50 || K == 100 || K == 128 || K == 256; }
+// does `form` take this K?
+constexpr bool als_cg_takes(int form, int K)
+{
+	if (K < 1 || K > kAlsCgMaxK) return false;
+	return form == kAlsCgFixed ? als_cg_fixed_k(K) : form == kAlsCgDma ? (K & 1) == 0 : form == kAlsCgGeneral;
+}
+// The forced form where it takes the K; otherwise the most special form that does: LDS-DMA moves a gathered row without a
+// register or an LDS store, and a compile-time K unrolls phase A with its reads in flight.
+constexpr AlsCgFormId als_cg_form(int K, int forced)
+{
+	if (forced >= 0 && forced < kAlsCgForms && als_cg_takes(forced, K)) return (AlsCgFormId) forced;
+	return als_cg_takes(kAlsCgFixed, K) ? kAlsCgFixed : als_cg_takes(kAlsCgDma, K) ? kAlsCgDma : kAlsCgGeneral;
+}
+// Entries per chunk: the sweeps' rule (chunk_rule, mf_launch.hip.h) -- 16, or what a sixth of a CU's LDS holds behind `head`
+// bytes but at least 12 -- because a wave here alternates "gather a chunk" and "compute on it" exactly as a sweep's does, and
+// the bytes in flight per CU come from the other resident workgroups.
+constexpr int als_cg_chunk(size_t head, size_t row_bytes, size_t lds_per_cu)
+{
+	const size_t budget = lds_per_cu / 6;
+	if (head + 16 * row_bytes <= budget) return 16;
+	const size_t fit = budget > head ? (budget - head) / row_bytes : 0;
+	return fit > 12 ? (int) fit : 12;
+}
+
 }  // namespace mf_sched

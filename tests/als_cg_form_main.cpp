@@ -1,0 +1,20 @@
+// als_cg_form_main -- the form and chunk rules of the conjugate-gradient ALS solve (csrc/mf_schedule.h: als_cg_takes, als_cg_form,
+// als_cg_chunk) on every K from 0 to 257 under every forced form from -1 to 4, and on a grid of tile geometries, one line each
+// (tests/test_als_cg.py):
+//   form K forced : the chosen form, then whether each of the three forms takes the K
+//   chunk head row_bytes : entries per chunk at 160 KiB of LDS per CU
+#include <cstdio>
+
+#include "../recommender-system_amd/csrc/mf_schedule.h"
+
+int main()
+{
+	for (int K = 0; K <= 257; ++K)
+		for (int forced = -1; forced <= 4; ++forced)
+			printf("form %d %d %d %d %d %d\n", K, forced, (int) mf_sched::als_cg_form(K, forced), (int) mf_sched::als_cg_takes(0, K),
+			       (int) mf_sched::als_cg_takes(1, K), (int) mf_sched::als_cg_takes(2, K));
+	for (int head = 512; head <= 4096; head += 512)
+		for (int odd = 1; odd <= 129; odd += 2)
+			printf("chunk %d %d %d\n", head, 16 * odd, mf_sched::als_cg_chunk((size_t) head, (size_t) 16 * odd, (size_t) 160 * 1024));
+	return 0;
+}
