@@ -89,8 +89,10 @@ def gram_rhs(rows, r, val, wgt, Y, xf, frozen, products=plain_products):
     return G, b
 
 
-def cholesky_solve(G, b):
-    """steps 7-9 for a batch: G (B, K, K), b (B, K) -> x (B, K), positive definite (B,)"""
+def cholesky_solve(G, b, observer=None):
+    """steps 7-9 for a batch: G (B, K, K), b (B, K) -> x (B, K), positive definite (B,).  `observer`: called as
+    observer("pivot", j, s, ok) with the values handed to sqrt at column j and observer("divisor", j, d, ok) with the divisors
+    of that column, ok = the rows still positive definite there (a row that is not has left the solve); it only looks"""
     B, K = b.shape
     Ct = np.zeros((K, B, K))   # Ct[t][:, i] = C[i][t] of every row of the batch: column t of the factors, contiguous
     ok = np.ones(B, bool)
@@ -103,6 +105,9 @@ def cholesky_solve(G, b):
         s = chain[-1]
         ok &= s[:, 0] > 0.0
         d = np.sqrt(s[:, 0])
+        if observer is not None:
+            observer("pivot", j, s[:, 0].copy(), ok.copy())
+            observer("divisor", j, d.copy(), ok.copy())
         Ct[j, :, j] = d
         Ct[j, :, j + 1:] = s[:, 1:] / d[:, None]
     bb, z = b.copy(), np.empty_like(b)
@@ -118,9 +123,10 @@ def cholesky_solve(G, b):
     return x, ok
 
 
-def als_solve(rows, val, wgt, X_old, Y, lam, kind, frozen=-1, box=NO_BOX, products=plain_products, grams=None):
+def als_solve(rows, val, wgt, X_old, Y, lam, kind, frozen=-1, box=NO_BOX, products=plain_products, grams=None, observer=None):
     """steps 1-10 for every row of a side -> (X_new, (solved, kept_empty, kept_not_pd)).  `grams`: a dict that keeps steps 1-4
-    of every row for a second solve of the same inputs (the other kind differs from step 5 on)"""
+    of every row for a second solve of the same inputs (the other kind differs from step 5 on).  `observer`: cholesky_solve's,
+    told observer("gram", batch, G, b) first -- the rows of the batch, their matrices with the ridge and right-hand sides"""
     K = X_old.shape[1]
     tp, tq = triangle(K)
     X_new = X_old.copy()
@@ -146,7 +152,9 @@ def als_solve(rows, val, wgt, X_old, Y, lam, kind, frozen=-1, box=NO_BOX, produc
                 G[:, frozen + 1:, frozen] = 0.0
                 G[:, frozen, frozen] = 1.0
                 b[:, frozen] = X_old[batch, frozen]
-            x, ok = cholesky_solve(G, b)
+            if observer is not None:
+                observer("gram", batch.copy(), G.copy(), b.copy())
+            x, ok = cholesky_solve(G, b, observer)
             head = x[:, :ncols]
             head = np.where(head < lo, lo, head)
             head = np.where(head > hi, hi, head)
@@ -164,8 +172,8 @@ class AlsModel:
         self.val = np.asarray(val, np.float64)
         self.wgt = None if weight is None else np.asarray(weight, np.float64)
 
-    def solve(self, side, X_old, Y, lam, kind, frozen=-1, box=NO_BOX, products=plain_products, grams=None):
-        return als_solve(self.side[side], self.val, self.wgt, X_old, Y, lam, kind, frozen, box, products, grams)
+    def solve(self, side, X_old, Y, lam, kind, frozen=-1, box=NO_BOX, products=plain_products, grams=None, observer=None):
+        return als_solve(self.side[side], self.val, self.wgt, X_old, Y, lam, kind, frozen, box, products, grams, observer)
 
     def iteration(self, L, R, lam, kind, frozen=(-1, -1), box=(NO_BOX, NO_BOX)):
         """users against R, items against the NEW L: (L', R', users' counts, items' counts); lam, frozen, box as (users, items)"""

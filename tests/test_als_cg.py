@@ -29,7 +29,9 @@ gpu = pytest.mark.gpu
 MAX_STEPS, MAX_K = 256, 256
 FIXED_K = (10, 20, 30, 50, 100, 128, 256)          # the compile-time K of the sweeps
 FORMS = ("fixed", "dma", "general")                # MF_ALS_CG_FORM, in the order of the rule's enum
-ALL_K = (1, 2, 3, 10, 16, 17, 30, 64, 100, 127, 128, 129, 200, 255, 256)
+# every compile-time K of als_cg_fn and both ends of the range of K of its run-time instances (2 .. 128 and 130 .. 256 under the
+# LDS-DMA gather, 1 .. 128 and 129 .. 256 through registers): tests/test_als_edges.py checks this list against the table
+ALL_K = (1, 2, 3, 10, 16, 17, 20, 30, 50, 64, 100, 127, 128, 129, 130, 200, 255, 256)
 CG_SYMBOLS = ("mf_plan_set_als_cg", "mf_plan_get_als_cg", "mf_backend_run_als_cg")
 LDS_PER_CU = 160 * 1024
 
@@ -78,9 +80,11 @@ def row_product(y, a, w, v, residual):
     return serial_last(e[:, :, None] * y, 1)
 
 
-def cg_side(rows, val, wgt, X_old, Y, lam, kind, steps, frozen=-1, box=NO_BOX, pass_fn=row_product):
+def cg_side(rows, val, wgt, X_old, Y, lam, kind, steps, frozen=-1, box=NO_BOX, pass_fn=row_product, observer=None):
     """C0-C5 for every row of a side.  `steps`: a number, or a tuple of numbers -- then {steps: result}: the row after s steps
-    is an intermediate of every longer run.  result = (X_new, (solved, kept_empty, kept_not_pd))"""
+    is an intermediate of every longer run.  result = (X_new, (solved, kept_empty, kept_not_pd)).  `observer`: called as
+    observer("pq", s, rows, pq) with the divisors of C4e and observer("rs", s, rows, rs) with those of C4f at step s, for the
+    rows that divide there; it only looks"""
     wanted = (steps,) if isinstance(steps, int) else tuple(steps)
     K = X_old.shape[1]
     lo, hi, ncols = box
@@ -126,6 +130,9 @@ def cg_side(rows, val, wgt, X_old, Y, lam, kind, steps, frozen=-1, box=NO_BOX, p
                         bad = ~(pq > 0.0)
                         notpd[i[bad]], active[i[bad]] = True, False
                         i, q, pq = i[~bad], q[~bad], pq[~bad]
+                        if observer is not None:
+                            observer("pq", s, R[i].copy(), pq.copy())
+                            observer("rs", s, R[i].copy(), rs[i].copy())
                         alpha = (rs[i] / pq)[:, None]                                # e
                         x[i] = x[i] + (alpha * p[i])
                         r[i] = r[i] - (alpha * q)
@@ -145,8 +152,8 @@ class CgModel:
         self.val = np.asarray(val, np.float64)
         self.wgt = None if weight is None else np.asarray(weight, np.float64)
 
-    def solve(self, side, X_old, Y, lam, kind, steps, frozen=-1, box=NO_BOX, pass_fn=row_product):
-        return cg_side(self.side[side], self.val, self.wgt, X_old, Y, lam, kind, steps, frozen, box, pass_fn)
+    def solve(self, side, X_old, Y, lam, kind, steps, frozen=-1, box=NO_BOX, pass_fn=row_product, observer=None):
+        return cg_side(self.side[side], self.val, self.wgt, X_old, Y, lam, kind, steps, frozen, box, pass_fn, observer)
 
     def iteration(self, L, R, lam, kind, steps, frozen=(-1, -1), box=(NO_BOX, NO_BOX)):
         """users against R, items against the NEW L: (L', R', users' counts, items' counts); lam, frozen, box as (users, items)"""
