@@ -890,6 +890,14 @@ int mf_plan_timing(mf_plan *plan, int enable);
 int mf_plan_timing_read(mf_plan *plan, int64_t *item_launches, double *item_ms,
                         int64_t *user_launches, double *user_ms);
 
+/* The user sweep in item bands.  A seeded user sweep of the plain rule (no decay, momentum, frozen column, bounds, weights
+ * or adaptive side) may run as several launches on the plan's stream, each walking the entries of every row that fall in
+ * one range of item ids and handing the partial row on through the next-generation buffer -- the same adds in the same
+ * order, so the same bits as one launch.  The library decides when the plan is created (large uniformly rated item factors
+ * and long enough rows; MF_SWEEP_BANDS=<n> sets the count, 0 turns the bands off) and needs rows of ascending item ids.
+ * Per-launch timing counts the sequence as one user launch.  mf_plan_describe appends user_bands=<n> while the next seeded
+ * user sweep would run in n bands; an unseeded sweep always is one launch. */
+
 /* Introspection for tests/bench: name of the sweep kernel variant chosen for this K, LDS bytes, chunk. */
 int mf_plan_describe(mf_plan *plan, char *buf, int buflen);
 

@@ -86,6 +86,18 @@ __global__ void __launch_bounds__(256) ptr_kernel(const unsigned *__restrict__ s
 	ptr[k] = (int) lo;
 }
 
+// The band offset table of the user sweep (mf_schedule.h): off[b * nrows + r] = the first entry of row r whose item id is at
+// least band b's first item, b = 0 .. bands (blockIdx.y); rows of ascending item ids.  Row 0 of the table is ptr[0 .. nrows)
+// and row `bands` is ptr[1 .. nrows].
+__global__ void __launch_bounds__(256) band_offsets_kernel(const int *__restrict__ ptr, const int *__restrict__ idx, int nrows, int items,
+                                                           int bands, int *__restrict__ off)
+{
+	const int r = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+	if (r >= nrows || b > bands) return;
+	const int beg = ptr[r], end = ptr[r + 1];
+	off[(size_t) b * nrows + r] = b == bands ? end : mf_sched::band_cut(idx, beg, end, mf_sched::band_first(b, items, bands));
+}
+
 __global__ void __launch_bounds__(256) copy_keys_kernel(const int *__restrict__ src, int64_t nnz,
                                                         unsigned *__restrict__ key, unsigned *__restrict__ perm)
 {
@@ -469,6 +481,34 @@ int plan_row_schedule(mf_plan *p, const std::vector<int> &rptr, const std::vecto
 		MF_HIP(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
 		MF_HIP(hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming));
 	}
+	return MF_OK;
+}
+
+// Item bands of the user sweep: the count by the rule of mf_schedule.h (band_count), and its offset table cut on the device
+// from the CSR.  After plan_row_schedule (the form of the side's main launch is an input) and the factor buffers (R's pitch).
+int plan_band_tables(mf_plan *p)
+{
+	SweepSide &us = p->side[1];
+	mf_sched::BandInput in;
+	in.user_side = true;
+	in.sorted = !p->mask_idx;
+	in.weighted = p->weighted;
+	in.extreme = us.n_long > 0;
+	in.single_wave = !us.coop_all && !us.use_db && !us.use_pair;
+	in.fixed_k = p->sweep.dma && band_resume_fn(p) != nullptr;
+	in.nrows = us.nrows, in.items = p->items;
+	in.nnz = p->nnz;
+	in.longest_column = p->side[0].max_row_len;
+	in.y_bytes = (size_t) p->items * (size_t) p->ldr * sizeof(double);
+	in.l2_bytes = kChipL2Bytes;
+	in.forced = p->cfg.sweep_bands;
+	us.bands = mf_sched::band_count(in);
+	if (us.bands < 1) return MF_OK;
+	MF_TRY(us.band_off.alloc((size_t) (us.bands + 1) * (size_t) us.nrows));
+	hipLaunchKernelGGL(band_offsets_kernel, dim3((unsigned) ((us.nrows + 255) / 256), (unsigned) (us.bands + 1)), dim3(256), 0, p->stream,
+	                   p->csr_ptr.get(), p->csr_idx.get(), us.nrows, p->items, us.bands, us.band_off.get());
+	MF_HIP(hipGetLastError());
+	MF_HIP(raise_lds_limit((const void *) band_resume_fn(p), std::max(p->single.lds, p->few.lds)));
 	return MF_OK;
 }
 

@@ -21,6 +21,7 @@ struct mf_config {
 	int sweep_nch = 0;                // MF_SWEEP_NCH=<1..64>: entries per chunk (0: the rule of choose_sweep)
 	int sweep_db = -1;                // MF_SWEEP_DB=0|1: intra-wave double-buffered sweep off / forced (-1: by occupancy)
 	int sweep_pair = -1;              // MF_SWEEP_PAIR=0|1: wave-pair sweep (loader + compute wave per row) off / forced (-1: by the plan)
+	int sweep_bands = -1;             // MF_SWEEP_BANDS=<n>: the user sweep in n item bands, 0 off (-1: the rule of mf_schedule.h)
 	int es_sw = 0;                    // MF_ES_SW=8|4|2: slice width of the resident streams launch to try first
 	bool row_pitch = true;            // MF_ROW_PITCH=0: dense device rows
 	bool resident = true;             // MF_RESIDENT=0: no single-launch loop for toy instances
@@ -60,6 +61,7 @@ struct mf_config {
 		}
 		if ((v = getenv("MF_SWEEP_DB"))) c.sweep_db = is0(v) ? 0 : 1;
 		if ((v = getenv("MF_SWEEP_PAIR"))) c.sweep_pair = is0(v) ? 0 : 1;
+		if ((v = getenv("MF_SWEEP_BANDS"))) c.sweep_bands = atoi(v) > 0 ? atoi(v) : 0;
 		if ((v = getenv("MF_ES_SW"))) c.es_sw = atoi(v);
 		c.row_pitch = !is0(getenv("MF_ROW_PITCH"));
 		c.resident = !is0(getenv("MF_RESIDENT"));
@@ -93,6 +95,7 @@ struct mf_config {
 		if (sweep_nch) add("MF_SWEEP_NCH", std::to_string(sweep_nch));
 		if (sweep_db >= 0) add("MF_SWEEP_DB", std::to_string(sweep_db));
 		if (sweep_pair >= 0) add("MF_SWEEP_PAIR", std::to_string(sweep_pair));
+		if (sweep_bands >= 0) add("MF_SWEEP_BANDS", std::to_string(sweep_bands));
 		if (es_sw) add("MF_ES_SW", std::to_string(es_sw));
 		if (!row_pitch) add("MF_ROW_PITCH", "0");
 		if (!resident) add("MF_RESIDENT", "0");

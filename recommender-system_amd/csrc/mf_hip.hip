@@ -102,6 +102,7 @@ static int plan_fill(mf_plan *p, const mf_shard *s, const mf_entry *aos, bool sw
 	const int own = row_pitch(p->cfg, p->K, p->sweep.dma != 0);
 	MF_TRY(factor_buffers(p, s->users_ext, s->users_pitch, own, p->uc, p->Lbuf, p->Lown, &p->ldl, &p->l_external));
 	MF_TRY(factor_buffers(p, s->items_ext, s->items_pitch, own, p->items, p->Rbuf, p->Rown, &p->ldr, &p->r_external));
+	MF_TRY(plan_band_tables(p));
 	MF_HIP(hipStreamSynchronize(p->stream));   // the plan is complete when the call returns
 	MF_TRY(p->best_dev.alloc((size_t) p->uc));
 	MF_TRY(p->lnorm.alloc((size_t) p->uc));
@@ -998,6 +999,17 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 	if (n > 0 && n < buflen)
 		n += snprintf(buf + n, (size_t) (buflen - n), " accumulate=%s/%s", single_wave_pipelined(p, 0) ? "pf" : "plain",
 		              single_wave_pipelined(p, 1) ? "pf" : "plain");
+	// item bands of the user sweep (mf_schedule.h: band_count and bands_at_launch), told only when there are any: what a
+	// seeded sweep would run in now, under the update rule in force
+	int user_bands = 0;
+	if (p->als_kind == MF_ALS_OFF) {
+		const SideUpdate u = side_update(p, 1, 1);
+		const Flavour fl = mf_sched::launch_flavour(p->weighted, u.beta != 0.0, u.d != 1.0 || u.frozen >= 0 || u.box.columns > 0);
+		if (mf_sched::bands_at_launch(us.bands, 1, fl, adaptive_side(p, 1))) user_bands = us.bands;
+		// ... and none where the side's last sweep was launched unseeded (a sharded driver's non-root contribution)
+		if (us.last_unseeded) user_bands = 0;
+	}
+	if (user_bands > 0 && n > 0 && n < buflen) n += snprintf(buf + n, (size_t) (buflen - n), " user_bands=%d", user_bands);
 	// how mf_plan_iterate runs an iteration: the two sweeps above, or errors + streams (mf_stream.hip.h)
 	if (n > 0 && n < buflen) {
 		if (!p->es_mode)

@@ -210,6 +210,9 @@ bool single_wave_pipelined(const mf_plan *p, int kind)
 	return mf_sched::single_wave_pipelined(p->sweep.has(kPipelined), p->K, p->side[kind].n_short, p->side[kind].nrows);
 }
 
+// The resume instance the band launches of the user sweep run: that of its single-wave form, null where the K has none
+SweepFn band_resume_fn(const mf_plan *p) { return p->sweep.resume[single_wave_pipelined(p, 1) ? 1 : 0]; }
+
 // The main launch of one side (kind 0: items, 1: users) by the rules of mf_schedule.h: its form, that form's geometry and
 // the instance of `flavour`.  A cell the K does not have leaves fn null: launch_sweep refuses rather than run another.
 SweepForm main_form(const mf_plan *p, int kind, bool few_rows, Flavour flavour)
@@ -362,6 +365,7 @@ int launch_adaptive_finish(mf_plan *p, int kind, const int *rowlist, int nrows, 
 int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 {
 	const SweepSide &sd = p->side[kind];
+	p->side[kind].last_unseeded = seed == 0;
 	const SideOperands x = side_operands(p, kind);
 	const bool adaptive = seed && adaptive_side(p, kind) && sd.nrows > 0;
 	if (adaptive) {
@@ -400,10 +404,14 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 	const bool extreme = sd.n_long > 0;
 	// the large chunk below kSweepFewRows rows.  Never beside the extreme-row path: with the extreme rows gone the
 	// occupancy-friendly chunk size is right again.
-	const SweepForm f = main_form(p, kind, !extreme && a.nrows < kSweepFewRows,
-	                              mf_sched::launch_flavour(p->weighted, momentum, u.d != 1.0 || u.frozen >= 0 || u.box.columns > 0));
+	const Flavour flavour = mf_sched::launch_flavour(p->weighted, momentum, u.d != 1.0 || u.frozen >= 0 || u.box.columns > 0);
+	const SweepForm f = main_form(p, kind, !extreme && a.nrows < kSweepFewRows, flavour);
 	if (!f.fn) return MF_ERR_UNSUPPORTED;
 	a.nch = f.nch;
+	// the user sweep in item bands (mf_schedule.h): the launches below in place of the one main launch, in the same geometry
+	const int bands = mf_sched::bands_at_launch(sd.bands, seed, flavour, adaptive) ? sd.bands : 0;
+	a.end = nullptr;
+	a.resume = 0;
 	TimedLaunch t{};
 	if (p->timing) {
 		MF_HIP(hipEventCreate(&t.t0));
@@ -474,7 +482,19 @@ int launch_sweep(mf_plan *p, int kind, int seed, bool defer_join = false)
 		a.nrows = sd.n_short;
 		a.rowlist = sd.short_rows;
 	}
-	if (a.nrows > 0)
+	if (bands > 0) {
+		// band b walks the entries [off[b][r], off[b + 1][r]) of every row r, in order on the plan's stream: band 0 seeds with
+		// X_old[r], a later one with the partial row in X_new[r]; every band stores the row.  The arguments are read at the launch.
+		const SweepFn rfn = band_resume_fn(p);
+		if (!rfn) return MF_ERR_UNSUPPORTED;
+		const int *off = sd.band_off;
+		for (int b = 0; b < bands; ++b) {
+			a.ptr = off + (size_t) b * sd.nrows;
+			a.end = off + (size_t) (b + 1) * sd.nrows;
+			a.resume = b > 0;
+			MF_HIP(hipLaunchKernel((const void *) rfn, dim3(std::min(a.nrows, 1 << 20)), dim3(f.block), args, f.lds, p->stream));
+		}
+	} else if (a.nrows > 0)
 		MF_HIP(hipLaunchKernel((const void *) f.fn, dim3(std::min(a.nrows, 1 << 20)), dim3(f.block), args, f.lds, p->stream));
 	if (adaptive) MF_TRY(launch_adaptive_finish(p, kind, extreme ? sd.short_rows.get() : nullptr, a.nrows, p->stream));
 	if (extreme) {

@@ -50,6 +50,9 @@ struct SweepVariant {
 	// loss_reg_kernel)
 	SweepFn prod[2] = {}, errs[2] = {};
 	LossFn loss[2] = {};
+	// the band launches of the user sweep (mf_schedule.h: band_count), [pipelined]: the resume instance of the plain and of
+	// the pipelined single-wave form.  Compile-time-K DMA variants only; a K without them runs no bands.
+	SweepFn resume[2] = {};
 	constexpr bool has(Form form) const { return fn[form][kAccumulate] != nullptr; }
 };
 
@@ -112,6 +115,8 @@ constexpr SweepVariant dma_variant()
 	if constexpr (KT <= 128) dma_row<KT, NP, 0>(v.fn[kPlain]);
 	v.fn[kPipelined][kAccumulate] = mf::sweep_dma_kernel<KT, NP, mf::kSweepAccumulate, 8>;
 	dma_row<KT, NP, 8>(v.fn[kPipelined]);
+	if constexpr (KT <= 128) v.resume[0] = mf::sweep_dma_kernel<KT, NP, mf::kSweepResume, 0>;
+	v.resume[1] = mf::sweep_dma_kernel<KT, NP, mf::kSweepResume, 8>;
 	if constexpr (mf::DmaGeom<KT>::kOnePassWide)
 		seeded_row(v.fn[kPair], mf::sweep_pair_kernel<KT, 1>, mf::sweep_pair_kernel<KT, 1, true>, mf::sweep_pair_kernel<KT, 1, false, true>,
 		           mf::sweep_pair_kernel<KT, 1, true, true>);
@@ -162,6 +167,7 @@ const SweepVariant kGeneric[] = {
 constexpr int kLargestK = 64 * mf::kWave;   // the widest row of kGeneric: choose_sweep refuses a larger K
 
 constexpr size_t kLdsPerCu = 160 * 1024;
+constexpr size_t kChipL2Bytes = (size_t) 32 << 20;   // 8 XCDs x 4 MiB
 
 // One side of an iteration (0 = items / CSC, 1 = users / CSR): its rows and what plan_row_schedule decided for its sweep by
 // the rules of mf_schedule.h.
@@ -182,6 +188,11 @@ struct SweepSide {
 	dev_buf<int> seg_row, seg_beg, seg_end;
 	dev_buf<long long> seg_out, lr_sbeg;
 	dev_buf<int> lr_cnt;
+	// item bands of the user sweep (mf_schedule.h: band_count; 0 on the item side): the count and the entry offsets
+	// [bands + 1][nrows], offset [b][r] = the first entry of row r whose item id is at least band b's first item
+	int bands = 0;
+	dev_buf<int> band_off;
+	bool last_unseeded = false;   // the side's last sweep was launched unseeded, so in one launch: mf_plan_describe tells no bands
 };
 
 struct TimedLaunch {

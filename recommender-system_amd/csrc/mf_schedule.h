@@ -356,6 +356,91 @@ inline Geometry launch_geometry(Form form, bool few_rows)
 	return form == kDb ? kGeomDb : form == kPair ? kGeomPair : few_rows ? kGeomFew : kGeomSingle;
 }
 
+// ---- the user sweep in item bands (profiles/user_bands/README.md): every user's row is walked in `bands`
+// consecutive item ranges, one launch per band, so the table a launch gathers from is 1/bands of Y and an XCD's L2 holds
+// that much more of it.  Band b holds the items [band_first(b), band_first(b + 1)): equal ranges, empty ones where
+// items < bands.  The partial row is handed from launch to launch through X_new; the chain of adds per element is the same
+// chain in the same order, and an FP64 store and load between two adds is exact: the same bits as one launch.
+constexpr int kBandsMax = 4096;                   // largest MF_SWEEP_BANDS
+constexpr long long kBandTableBytes = 1ll << 30;  // ... and no band table above 1 GiB
+constexpr int band_first(int b, int items, int bands) { return (int) ((long long) b * items / bands); }
+
+// The offset cut: the first entry of [beg, end) -- item ids ascending -- whose id is at least first_item (end: none).
+// Entry offsets of row r: off[b][r] = band_cut(idx, ptr[r], ptr[r + 1], band_first(b)), b = 0 .. bands.
+constexpr int band_cut(const int *idx, int beg, int end, int first_item)
+{
+	while (beg < end) {
+		const int mid = beg + ((end - beg) >> 1);
+		if (idx[mid] < first_item)
+			beg = mid + 1;
+		else
+			end = mid;
+	}
+	return beg;
+}
+
+// The band count the size rule picks (0: the rule is off).  Measured on cfg4 (1e6 x 1e5, K = 100, 100 entries per row, R 80
+// MB; two runs each on one MI355X, profiles/user_bands/README.md), user sweep in ms by bands:
+//   1 launch 11.61 | 2: 11.27 | 3: 11.44 | 4: 12.03 | 6: 13.56 | 8: 15.11 | 10: 16.81 | 12: 18.85 | 16: 23.37
+// A band costs every row one more chain of dependent loads in front of its first gather and, on average, one more
+// partly filled chunk -- about 0.85 ms per band on this shape --: two bands gain 0.34 ms, three 0.16, four and more lose.
+// Against the parent commit, three alternating pairs: 23.32 .. 23.34 -> 23.10 .. 23.12 ms per iteration.
+constexpr int kBandsRule = 2;
+// ... and the fewest entries per row and band, on average, at which the rule runs them: two full 16-entry chunks, so that
+// the chunk a band adds stays under a third of its work.  Reasoned from the table above, which still gains at 33 per band
+// (three bands) and loses at 25 (four); no other row length was measured.
+constexpr int kBandFloor = 32;
+// ... and the largest Y, in L2 sizes, for which it does: what a band gains is the part of its table the caches hold, and
+// the one table measured is 2.4 of them (80 MB against 32 MiB); a table many times larger would keep the cost and lose the gain.
+constexpr int kBandYMaxL2 = 4;
+
+struct BandInput {
+	bool user_side = false;     // side 1, the CSR
+	bool sorted = false;        // item ids ascending inside every row (the plan keeps no mask_idx)
+	bool weighted = false;      // plan created with per-entry weights
+	bool extreme = false;       // the side has extreme rows
+	bool single_wave = false;   // the main launch is a single-wave one: not the pair, double-buffered or cooperative form
+	bool fixed_k = false;       // K has a compile-time single-wave LDS-DMA instance
+	int nrows = 0, items = 0;
+	long long nnz = 0;
+	int longest_column = 0;     // entries of the most rated item (the item side's longest row)
+	size_t y_bytes = 0;         // items x pitch x 8
+	size_t l2_bytes = 0;        // the chip's L2, all XCDs
+	int forced = -1;            // MF_SWEEP_BANDS (-1: unset)
+};
+
+// Are the gathers spread evenly over Y?  The longest column under four times the mean one (the skew test of priority_length).
+// Where a few items take most entries their rows of Y are served from L2 as it is, and the bands only cost: cfg4 with Zipf
+// columns, user sweep 9.95 ms in one launch, 10.75 in two bands.
+inline bool band_columns_even(const BandInput &in)
+{
+	return (long long) in.longest_column < 4 * std::max<long long>(in.nnz / std::max(in.items, 1), 1);
+}
+
+// Bands of a side, decided when the plan is created: 0, or the count whose offset table the plan builds.  The form must
+// allow them; then MF_SWEEP_BANDS=n sets the count, and unset the size rule does: Y larger than the chip's L2 but no more than
+// kBandYMaxL2 of them, gathered evenly, and rows long enough.
+inline int band_count(const BandInput &in)
+{
+	if (!in.user_side || !in.sorted || in.weighted || in.extreme || !in.single_wave || !in.fixed_k) return 0;
+	if (in.nrows <= 0 || in.items <= 0 || in.nnz <= 0) return 0;
+	int bands = kBandsRule;
+	if (in.forced >= 0)
+		bands = std::min(in.forced, kBandsMax);
+	else if (bands < 1 || in.y_bytes <= in.l2_bytes || in.y_bytes > kBandYMaxL2 * in.l2_bytes || !band_columns_even(in) || in.nnz / in.nrows / bands < kBandFloor)
+		bands = 0;
+	if ((long long) (bands + 1) * in.nrows * (long long) sizeof(int) > kBandTableBytes) bands = 0;
+	return bands;
+}
+
+// ... and at every launch of the side: the bands run only for a seeded sweep of the plain flavour -- no decay, frozen column
+// or bounds (kDecay), no momentum, no weights -- that is not the unseeded launch of an adaptive side.  An unseeded sweep (the
+// non-root contribution of a sharded driver) keeps its one launch.
+constexpr bool bands_at_launch(int bands, int seed, Flavour flavour, bool adaptive)
+{
+	return bands > 0 && seed == 1 && flavour == kAccumulate && !adaptive;
+}
+
 // ---- how an iteration runs (mf_plan_iterate, mf_hip.hip): one rule picks the loop and how much of it is replayed from a
 // captured graph; mf_plan_iterate only dispatches on the result (tests/test_iterate_path.py)
 

@@ -87,6 +87,11 @@ struct SweepArgs {
 	// launch_sweep passes columns = 0 for an unseeded sweep (a partial sum is not clamped) and for a side without bounds.
 	// The kernels read it through load_box, not as a.box
 	Box box;
+	// band launches of the user sweep (kSweepResume instances only, mf_schedule.h): the launch walks the entries
+	// [ptr[r], end[r]) of row r -- two rows of the plan's band offset table --, and with resume != 0 the accumulators start
+	// from the partial row X_new[r] holds instead of X_old[r]
+	const int *__restrict__ end;
+	int resume;
 };
 
 // Projection of one element onto [lo, hi]: IEEE comparisons and selects, so a NaN stays the NaN it is (both comparisons are
@@ -657,11 +662,12 @@ __device__ __forceinline__ void phase_b_tail(const char *tb, int S, double e, in
 // launch_sweep picks it for a frozen side at d = 1.0 too, x * 1.0 being x; 4 mode 3 with the momentum term added to the
 // seed (a seeded sweep of a side with beta != 0); 5 .. 8 the weighted twins of modes 3, 4, 1 and 2 -- e_n times the entry's
 // weight a.wgt[n], loaded where val is -- which a plan created with weights launches in their place (at d = 1.0 and beta = 0
-// mode 5: a weighted plan has no twin of mode 0)
+// mode 5: a weighted plan has no twin of mode 0); 9 resume: mode 0 over one item band of every row -- the entries
+// [a.ptr[r], a.end[r]) --, seeded with the partial row in X_new where a.resume says so (the band launches of the user sweep)
 // PF > 0: phases A and B keep their LDS reads in flight and the gather issue is lean.
 // ------------------------------------------------------------------------------------------------
 constexpr int kSweepAccumulate = 0, kSweepProducts = 1, kSweepErrors = 2, kSweepDecay = 3, kSweepMomentum = 4;
-constexpr int kSweepDecayW = 5, kSweepMomentumW = 6, kSweepProductsW = 7, kSweepErrorsW = 8;
+constexpr int kSweepDecayW = 5, kSweepMomentumW = 6, kSweepProductsW = 7, kSweepErrorsW = 8, kSweepResume = 9;
 #ifdef MF_STAMPS
 // diagnostic build only (tools/stamps.py): shader-clock totals of the phases of the rows of at least 1024 entries --
 // [0] rows, [1] chunks, [2] gather issue, [3] landing wait, [4] phase A, [5] phase B, [6] whole row
@@ -674,7 +680,7 @@ __device__ unsigned long long mf_stamp_buf[8];
 template <int KT, int NPASS, int MODE = kSweepAccumulate, int PF = 0>
 __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 {
-	constexpr bool WGT = MODE >= kSweepDecayW;
+	constexpr bool WGT = MODE >= kSweepDecayW && MODE <= kSweepErrorsW, RESUME = MODE == kSweepResume;
 	constexpr bool PRODUCTS = MODE == kSweepProducts || MODE == kSweepProductsW, ERRORS = MODE == kSweepErrors || MODE == kSweepErrorsW,
 	               SEGMENTS = PRODUCTS || ERRORS, MOMENTUM = MODE == kSweepMomentum || MODE == kSweepMomentumW,
 	               DECAY = MODE == kSweepDecay || MODE == kSweepDecayW || MOMENTUM;
@@ -695,7 +701,10 @@ __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 	for (int it = blockIdx.x; it < a.nrows; it += gridDim.x) {
 		const int r = SEGMENTS ? a.seg_row[it] : (a.rowlist ? a.rowlist[it] : it);
 		const int beg = SEGMENTS ? a.seg_beg[it] : a.ptr[r];
-		const int end = SEGMENTS ? a.seg_end[it] : a.ptr[r + 1];
+		const int end = SEGMENTS ? a.seg_end[it] : RESUME ? a.end[r] : a.ptr[r + 1];
+		// a later band the row has no entry in: X_new[r] holds the partial row already (band 0 seeds every row)
+		if constexpr (RESUME)
+			if (a.resume && beg == end) continue;
 		const double2 *__restrict__ xrow2 = reinterpret_cast<const double2 *>(a.X_old + (size_t) r * a.ldx);
 		// A wave walking a long row is bound by its own instruction stream and shares its SIMD's issue slots with the
 		// waves of short rows; it is also what the launch ends on.  Rows of at least prio_len entries run at raised
@@ -711,11 +720,33 @@ __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 		unsigned long long st_issue = 0, st_wait = 0, st_a = 0, st_b = 0, st_chunks = 0;
 #endif
 		MF_STAMP(t_row0);
+		// A band launch pays the chain of dependent loads in front of a row's first gather once per band, not once per row: its
+		// first chunk's (idx, val), the old row and the partial row are all issued before any of them is waited for
+		[[maybe_unused]] int first_idx = 0;
+		[[maybe_unused]] double first_val = 0.0;
+		if constexpr (RESUME)
+			if (beg + lane < min(end, beg + nch)) {
+				first_idx = a.idx[beg + lane];
+				first_val = a.val[beg + lane];
+			}
 		double2 acc[NP];
 #pragma unroll
 		for (int p = 0; p < NP; ++p) {
 			const int q = lane + kWave * p;
 			double2 v = make_double2(0.0, 0.0);
+			if constexpr (RESUME) {
+				// band 0 seeds with the old row, a later band with the partial row the band before it stored
+				// (one source pointer, so both loads are issued before either is waited for)
+				const double2 *seed2 = a.resume ? reinterpret_cast<const double2 *>(a.X_new + (size_t) r * a.ldx) : xrow2;
+				double2 w = make_double2(0.0, 0.0);
+				if (q < P) {
+					v = xrow2[q];
+					w = seed2[q];
+					xs[q] = v;
+				}
+				acc[p] = w;
+				continue;
+			}
 			if (q < P) {
 				v = xrow2[q];
 				xs[q] = v;
@@ -734,7 +765,10 @@ __global__ void __launch_bounds__(kWave) sweep_dma_kernel(SweepArgs a)
 		int nx_idx = 0, nx_map = 0;
 		double nx_val = 0.0;
 		[[maybe_unused]] double nx_wgt = 0.0;
-		if (beg + lane < min(end, beg + nch)) {
+		if constexpr (RESUME) {
+			nx_idx = first_idx;
+			nx_val = first_val;
+		} else if (beg + lane < min(end, beg + nch)) {
 			nx_idx = a.idx[beg + lane];
 			nx_val = a.val[beg + lane];
 			if constexpr (WGT) nx_wgt = a.wgt[beg + lane];
