@@ -823,7 +823,8 @@ int mf_backend_run_implicit(const mf_problem *p, const double *weight, double *L
  * While CG is on and a kind is set mf_plan_describe appends  als=ridge|ridge-count als_cg=<steps>
  * als_cg_form=<form>(chunk=<entries>)  without als_form=.  The forms (MF_ALS_CG_FORM=fixed|dma|general: a compile-time K of
  * the sweeps' list, any even K, any K; by default the first of these that takes the K) give the same bits.
- * Not part of this: CG under the implicit kind, preconditioning, a residual-based stop, K above 256, sharded item solves. */
+ * Not part of this: CG under the implicit kind through these two calls (it has a switch of its own: the next section),
+ * preconditioning, a residual-based stop, K above 256, sharded item solves. */
 #define MF_ALS_CG_MAX_STEPS 256
 #define MF_ALS_CG_MAX_K     256
 int mf_plan_set_als_cg(mf_plan *plan, int steps);
@@ -832,6 +833,61 @@ int mf_plan_get_als_cg(mf_plan *plan, int *steps);
 int mf_backend_run_als_cg(const mf_problem *p, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
                           double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, int kind, int steps,
                           int device);
+
+/* ---- Implicit-feedback ALS by conjugate gradient: the CG steps above under MF_ALS_IMPLICIT, warm-started from the row's
+ * current value, in place of the per-row Cholesky (Hu, Koren, Volinsky, ICDM 2008, solved as Takacs, Pilaszy, Tikk do).  The
+ * matrix of a row, S + sum_n e_n y_n y_n^T + ridge I, is never formed: its product with a vector v is
+ * sum_n e_n y_n (y_n . v) + S v + ridge v.
+ *
+ * mf_plan_set_implicit_cg(plan, steps) / mf_plan_get_implicit_cg(plan, &steps).  0 <= steps <= MF_ALS_CG_MAX_STEPS; anything
+ * else -> MF_ERR_ARGUMENT before any HIP call with nothing changed.  The call is accepted under any kind and in any order with
+ * mf_plan_set_als; the value is read at every launch, and only while the kind is MF_ALS_IMPLICIT.  steps = 0, the default, is
+ * the direct implicit solve: every bit and every launched kernel is what it is without this section.  (mf_plan_set_als_cg
+ * together with MF_ALS_IMPLICIT stays refused: that switch belongs to the explicit kinds.)
+ *
+ * With steps > 0 under MF_ALS_IMPLICIT, mf_plan_als_solve(plan, side, other_generation)
+ *   1. enqueues the Gram S of Y = the other side in that generation: mf_plan_gram's bits;
+ *   2. copies the packed triangle into a plan-owned K x K square with an even row stride (an elementwise copy, no arithmetic;
+ *      the pad column of an odd K is +0.0);
+ *   3. computes every row r of the side X by J0 .. J5.
+ * FP64 throughout, every operation rounded once, nothing fused, / correctly rounded, no matrix-core instruction.  dot(u, v) is
+ * the serial chain of the CG section.  S(k, j) is S[max(k,j)][min(k,j)].  ridge = lambda_side.  e_n = conf * w_n on a weighted
+ * plan and e_n = conf otherwise.  The row's entries n = 0 .. cnt-1 come in the side's entry order; a_n is the value, y_n the Y
+ * row.  The padding of a row is never read or written.
+ *   J0. x = X_old[r][0..K).
+ *   J1. For every entry:  c_n = 1.0 + e_n;  ac_n = a_n * c_n;  t_n = dot(y_n, x);  d_n = ac_n - (e_n * t_n).
+ *   J2. g[k] starts at 0.0; for n ascending  g[k] = g[k] + (d_n * y_n[k]).
+ *       sx[k] starts at 0.0; for j = 0 .. K-1 ascending  sx[k] = sx[k] + (S(k, j) * x[j]).
+ *       r[k] = (g[k] - sx[k]) - (ridge * x[k]).
+ *   J3. p = r;  rs = dot(r, r).
+ *   J4. For s = 1 .. steps:
+ *       a. If rs == 0.0 leave the loop (a NaN is not equal and goes on).
+ *       b. u_n = dot(y_n, p);  ue_n = u_n * e_n.
+ *       c. q[k] starts at 0.0; for n ascending  q[k] = q[k] + (ue_n * y_n[k]).
+ *          sp[k] is formed like sx, with p in place of x.
+ *          q[k] = (q[k] + sp[k]) + (ridge * p[k]).
+ *       d, e, f. exactly C4d, C4e and C4f: pq = dot(p, q), NOT POSITIVE DEFINITE when !(pq > 0.0), alpha, x, r, rn, beta, p;
+ *          the last step's f is skipped.
+ *   J5. The box projection of mf_plan_set_bounds on the bounded columns, then the store.  The row is counted as solved.
+ * A row WITHOUT ENTRIES is solved like any other: its entry sums are empty.  kept_empty is 0 under this kind, as in the direct
+ * implicit solve.  A NaN in Y makes S NaN: every row is then not positive definite and keeps X_old's bits.  In exact
+ * arithmetic K steps reach the solution of the direct implicit solve, and no step increases the row's quadratic.
+ *
+ * Limits and refusals are those of the direct implicit kind: a frozen column on the solved side is refused at launch
+ * (MF_ERR_UNSUPPORTED before any HIP call), momentum and adaptive sides are refused, the item solve on a shard or a 2-D tile
+ * is MF_ERR_UNSUPPORTED, K <= 128 (S is mf_plan_gram's).  One iteration of mf_plan_iterate / mf_plan_iterate_monitored keeps
+ * its order:  gram(items, current);  als_solve(users, 0);  gram(users, next);  als_solve(items, 1);  flip.  While the steps
+ * are on and the kind is implicit mf_plan_describe appends  als=implicit conf=<%.17g> implicit_cg=<steps>
+ * als_cg_form=<form>(chunk=<entries>)  without als_form=.  The forms are the CG section's (MF_ALS_CG_FORM) and give the same
+ * bits.
+ * Not part of this: K above 128, a frozen column, preconditioning, a residual-based stop, sharded item solves. */
+int mf_plan_set_implicit_cg(mf_plan *plan, int steps);
+int mf_plan_get_implicit_cg(mf_plan *plan, int *steps);
+/* level 1: mf_backend_run_implicit with the steps (0: the direct solve; mf_backend_run_implicit is this call with 0).  Bad
+ * arguments, the steps among them -> MF_ERR_ARGUMENT before any HIP call, nothing touched. */
+int mf_backend_run_implicit_cg(const mf_problem *p, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
+                               double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, double conf,
+                               int steps, int device);
 
 /* ---- Ranks of the held-out entries: where each held-out item lands in its user's recommendation order, for the plan's
  * current factors.  An extension (the reference ranks nothing), so the definition is this library's.  For held-out entry

@@ -58,6 +58,7 @@ HIP_SYMBOLS = [
     "mf_plan_gram", "mf_plan_set_confidence", "mf_plan_get_confidence", "mf_plan_implicit_objective", "mf_backend_gram_dot",
     "mf_backend_run_implicit",
     "mf_plan_set_als_cg", "mf_plan_get_als_cg", "mf_backend_run_als_cg",
+    "mf_plan_set_implicit_cg", "mf_plan_get_implicit_cg", "mf_backend_run_implicit_cg",
 ]
 HOST_SYMBOLS = [
     "mf_host_parse_strerror", "mf_host_parse_file", "mf_host_parse_buffer", "mf_host_free_problem",
@@ -279,6 +280,10 @@ def hip():
         lib.mf_plan_get_als_cg.argtypes = [P, C.POINTER(C.c_int)]
         lib.mf_backend_run_als_cg.argtypes = [C.POINTER(Problem), P, P, P, P, C.c_double, C.c_double, C.POINTER(Bounds), C.POINTER(Bounds),
                                               C.c_int, C.c_int, C.c_int]
+        lib.mf_plan_set_implicit_cg.argtypes = [P, C.c_int]
+        lib.mf_plan_get_implicit_cg.argtypes = [P, C.POINTER(C.c_int)]
+        lib.mf_backend_run_implicit_cg.argtypes = [C.POINTER(Problem), P, P, P, P, C.c_double, C.c_double, C.POINTER(Bounds),
+                                                   C.POINTER(Bounds), C.c_double, C.c_int, C.c_int]
         _hip = lib
     return _hip
 
@@ -683,6 +688,28 @@ def backend_run_implicit(inst, L, R, conf=1.0, bounds_users=None, bounds_items=N
 run_implicit = backend_run_implicit
 
 
+def backend_run_implicit_cg(inst, L, R, steps, conf=1.0, bounds_users=None, bounds_items=None, weight=None, lambda_users=0.0,
+                            lambda_items=None, iters=None, device=0, recommend=True):
+    """mf_backend_run_implicit_cg: backend_run_implicit with `steps` conjugate-gradient steps per row in place of the direct
+    solve (0: the direct solve)."""
+    p, keep = _problem(inst, iters)
+    w = None if weight is None else np.ascontiguousarray(weight, np.float64)
+    assert w is None or w.shape == (inst.nnz,)
+    li = lambda_users if lambda_items is None else lambda_items
+    bu, bit = _bounds_record(bounds_users), _bounds_record(bounds_items)
+    best = np.empty(inst.users, np.int32) if recommend else None
+    assert L.dtype == np.float64 and R.dtype == np.float64 and L.flags.c_contiguous and R.flags.c_contiguous
+    _check(hip().mf_backend_run_implicit_cg(C.byref(p), None if w is None else w.ctypes.data, L.ctypes.data, R.ctypes.data,
+                                            best.ctypes.data if recommend else None, float(lambda_users), float(li),
+                                            None if bu is None else C.byref(bu), None if bit is None else C.byref(bit),
+                                            float(conf), int(steps), device),
+           "mf_backend_run_implicit_cg")
+    return best
+
+
+run_implicit_cg = backend_run_implicit_cg
+
+
 def gram_dot(left, right):
     """mf_backend_gram_dot: the sum of the elementwise products of two symmetric K x K matrices given as packed lower triangles,
     over the full matrices, p ascending then q ascending, from 0.0"""
@@ -1061,6 +1088,17 @@ class Plan:
         """mf_plan_get_als_cg: the steps"""
         s = C.c_int()
         _check(hip().mf_plan_get_als_cg(self._h, C.byref(s)), "mf_plan_get_als_cg")
+        return s.value
+
+    def set_implicit_cg(self, steps):
+        """mf_plan_set_implicit_cg: conjugate-gradient steps per row of an implicit ALS solve (0: the direct solve); read at every
+        launch, and only under the implicit kind"""
+        _check(hip().mf_plan_set_implicit_cg(self._h, int(steps)), "mf_plan_set_implicit_cg")
+
+    def implicit_cg(self):
+        """mf_plan_get_implicit_cg: the steps"""
+        s = C.c_int()
+        _check(hip().mf_plan_get_implicit_cg(self._h, C.byref(s)), "mf_plan_get_implicit_cg")
         return s.value
 
     def als_solve(self, side, other="current"):

@@ -133,10 +133,11 @@ __device__ __forceinline__ double als_cg_dot(double *pr, int lane, int K, const 
 }
 
 // One pass over the row's entries [beg, beg + cnt): acc[k] = sum_n e_n * y_n[k], n ascending, with t_n = dot(y_n, vs) and
-// e_n = a_n - t_n (RESIDUAL) or t_n, times w_n on a weighted plan.
-template <int KT, int NP, bool DMA, bool RESIDUAL>
+// e_n = a_n - t_n (RESIDUAL) or t_n, times w_n on a weighted plan.  IMPLICIT (mf_als_icg.hip.h) changes the entry's factor
+// alone: with c_n = conf * w_n (conf without weights) it is (a_n * (1.0 + c_n)) - (c_n * t_n) (RESIDUAL) or t_n * c_n.
+template <int KT, int NP, bool DMA, bool RESIDUAL, bool IMPLICIT = false>
 __device__ __forceinline__ void als_cg_pass(const AlsArgs &a, int K, int nch, int beg, int cnt, int lane, const double2 *vs, char *tile,
-                                            double2 (&acc)[NP])
+                                            double2 (&acc)[NP], double conf = 0.0)
 {
 	const int P = als_cg_pieces(K), S = als_cg_row_stride(K);
 	const unsigned voff = (unsigned) lane * 16u;
@@ -152,7 +153,10 @@ __device__ __forceinline__ void als_cg_pass(const AlsArgs &a, int K, int nch, in
 			const int e = beg + c0 + lane;
 			my_idx = a.idx[e];
 			if constexpr (RESIDUAL) my_val = a.val[e];
-			if (a.wgt) my_wgt = a.wgt[e];
+			if constexpr (IMPLICIT)
+				my_wgt = a.wgt ? conf * a.wgt[e] : conf;
+			else if (a.wgt)
+				my_wgt = a.wgt[e];
 		}
 		// ---- the chunk's Y rows into the tile
 		if constexpr (DMA) {
@@ -207,8 +211,18 @@ __device__ __forceinline__ void als_cg_pass(const AlsArgs &a, int K, int nch, in
 					if (K & 1) dot = dot + vs[full].x * t2[full].x;
 				}
 			}
-			e = RESIDUAL ? my_val - dot : dot;
-			if (a.wgt) e = e * my_wgt;
+			if constexpr (IMPLICIT) {
+				if constexpr (RESIDUAL) {
+					const double cn = 1.0 + my_wgt;
+					const double ac = my_val * cn, et = my_wgt * dot;
+					e = ac - et;
+				} else {
+					e = dot * my_wgt;
+				}
+			} else {
+				e = RESIDUAL ? my_val - dot : dot;
+				if (a.wgt) e = e * my_wgt;
+			}
 		}
 		// ---- phase B
 		const char *tb = tile + voff;

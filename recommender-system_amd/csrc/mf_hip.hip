@@ -650,6 +650,20 @@ int mf_plan_get_als_cg(mf_plan *p, int *steps)
 	return MF_OK;
 }
 
+int mf_plan_set_implicit_cg(mf_plan *p, int steps)
+{
+	if (!p || steps < 0 || steps > MF_ALS_CG_MAX_STEPS) return MF_ERR_ARGUMENT;
+	p->implicit_cg = steps;   // read at every launch, and only while the kind is MF_ALS_IMPLICIT
+	return MF_OK;
+}
+
+int mf_plan_get_implicit_cg(mf_plan *p, int *steps)
+{
+	if (!p) return MF_ERR_ARGUMENT;
+	if (steps) *steps = p->implicit_cg;
+	return MF_OK;
+}
+
 int mf_plan_als_solve(mf_plan *p, int side, int other_generation)
 {
 	if (!p || (side != 0 && side != 1) || (other_generation != 0 && other_generation != 1)) return MF_ERR_ARGUMENT;
@@ -1068,7 +1082,10 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 		const AlsForm &form = kAlsForm[als_form(p->K, p->cfg.als_form)];
 		append(buf, buflen, " als=%s als_form=%s(chunk=%d)", p->als_kind == MF_ALS_RIDGE ? "ridge" : "ridge-count", form.name, form.nch);
 	}
-	if (p->als_kind == MF_ALS_IMPLICIT) {
+	if (p->als_kind == MF_ALS_IMPLICIT && p->implicit_cg > 0) {
+		append(buf, buflen, " als=implicit conf=%.17g implicit_cg=%d als_cg_form=%s(chunk=%d)", p->confidence, p->implicit_cg,
+		       kAlsCgFormName[als_cg_form(p->K, p->cfg.als_cg_form)], als_cg_chunk(p->K));
+	} else if (p->als_kind == MF_ALS_IMPLICIT) {
 		const AlsForm &form = kAlsForm[als_form(p->K, p->cfg.als_form)];
 		append(buf, buflen, " als=implicit conf=%.17g als_form=%s(chunk=%d)", p->confidence, form.name, form.nch);
 	}
@@ -1222,13 +1239,22 @@ int mf_backend_run_als_cg(const mf_problem *pr, const double *weight, double *L,
 int mf_backend_run_implicit(const mf_problem *pr, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
                             double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, double conf, int device)
 {
+	return mf_backend_run_implicit_cg(pr, weight, L, R, best, lambda_users, lambda_items, bounds_users, bounds_items, conf, 0, device);
+}
+
+// ... with the steps of its conjugate-gradient solve (0: the direct one)
+int mf_backend_run_implicit_cg(const mf_problem *pr, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
+                               double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, double conf, int steps,
+                               int device)
+{
 	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !bounds_record_ok(bounds_users, pr->features) ||
-	    !bounds_record_ok(bounds_items, pr->features) || !std::isfinite(conf) || conf < 0.0)
+	    !bounds_record_ok(bounds_items, pr->features) || !std::isfinite(conf) || conf < 0.0 || steps < 0 || steps > MF_ALS_CG_MAX_STEPS)
 		return MF_ERR_ARGUMENT;
 	const RulePair rule = level1_rules(lambda_users, lambda_items, 0.0, 0.0, bounds_users, bounds_items);
 	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
 		p->rule[0] = rule[0], p->rule[1] = rule[1];
 		int rc = mf_plan_set_confidence(p, conf);
+		if (rc == MF_OK) rc = mf_plan_set_implicit_cg(p, steps);
 		if (rc == MF_OK) rc = mf_plan_set_als(p, MF_ALS_IMPLICIT);
 		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
 		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);

@@ -618,7 +618,8 @@ int gram_buffers(mf_plan *p)
 	const size_t blocks = (size_t) std::max(1, std::max(gram_blocks(p->items), gram_blocks(p->uc)));
 	int rc = p->gram_partial.alloc(blocks * tri);
 	if (rc == MF_OK) rc = p->gram.alloc(2 * tri);
-	if (rc != MF_OK) p->gram_partial.reset();
+	if (rc == MF_OK) rc = p->gram_square.alloc((size_t) p->K * mf::als_icg_ld(p->K));   // what launch_als_icg reads S from
+	if (rc != MF_OK) p->gram_partial.reset(), p->gram.reset();
 	return rc;
 }
 
@@ -692,6 +693,57 @@ int launch_als_cg(mf_plan *p, int side, int other_generation, unsigned long long
 	return launch(sd.lpt ? sd.short_rows.get() : nullptr, sd.nrows);
 }
 
+// The implicit conjugate-gradient solve of a side (mf_plan_set_implicit_cg with steps > 0 under MF_ALS_IMPLICIT; the Gram of
+// the other side is enqueued and the counters are zeroed): the packed triangle is copied into the plan's square, then one
+// wave per row runs J0 .. J5, one launch over the side's rows in its dispatch order, as launch_als_cg.
+int launch_als_icg(mf_plan *p, int side, int other_generation, unsigned long long *counts)
+{
+	const SweepSide &sd = p->side[side];
+	const AlsIcgFn fn = als_icg_fn(als_cg_form(p->K, p->cfg.als_cg_form), p->K);
+	if (!fn) return MF_ERR_UNSUPPORTED;   // a missing instance is an error, never another kernel
+	const int nch = als_cg_chunk(p->K);
+	const size_t lds = mf::als_cg_lds_bytes(p->K, nch);
+	MF_HIP(raise_lds_limit((const void *) fn, lds));
+
+	const int ld = mf::als_icg_ld(p->K), cells = p->K * ld;
+	hipLaunchKernelGGL(mf::gram_square_kernel, dim3((cells + mf::kGramThreads - 1) / mf::kGramThreads), dim3(mf::kGramThreads), 0, p->stream,
+	                   (const double *) p->gram.get() + (size_t) (side ^ 1) * mf::als_triangle(p->K), p->K, ld, p->gram_square.get());
+	MF_HIP(hipGetLastError());
+
+	const SideUpdate u = side_update(p, side, 1);
+	const SideOperands x = side_operands(p, side);
+	mf::AlsArgs a;
+	a.K = p->K;
+	a.ldx = x.ldx;
+	a.ldy = x.ldy;
+	a.frozen = -1;   // the caller has refused a frozen column
+	a.count_scaled = 0;
+	a.lambda = p->rule[side].lambda;
+	a.ptr = x.ptr;
+	a.idx = x.idx;
+	a.val = x.val;
+	a.wgt = x.wgt;
+	a.X_old = x.X_old;
+	a.X_new = x.X_new;
+	a.Y = other_generation ? side_operands(p, side ^ 1).X_new : x.Y_old;
+	a.counts = counts;
+	a.box = u.box;
+	const mf::AlsImplicit im{p->gram_square.get(), p->confidence};
+	auto launch = [&](const int *rowlist, int nrows) {
+		if (nrows <= 0) return MF_OK;
+		a.rowlist = rowlist;
+		a.nrows = nrows;
+		hipLaunchKernelGGL(fn, dim3(nrows), dim3(mf::kWave), lds, p->stream, a, im, p->implicit_cg, nch);
+		MF_HIP(hipGetLastError());
+		return MF_OK;
+	};
+	if (sd.n_long > 0) {
+		MF_TRY(launch(sd.long_rows, sd.n_long));
+		return launch(sd.short_rows, sd.n_short);
+	}
+	return launch(sd.lpt ? sd.short_rows.get() : nullptr, sd.nrows);
+}
+
 // One solve of a side (0: items, 1: users) against the other side's current (0) or next (1) buffer, into the side's
 // next buffer: the counters zeroed, then one launch over the side's rows in its dispatch order -- the extreme rows of a
 // split side first, they are its longest.  The rule of the side is read here, at every launch.  Under MF_ALS_IMPLICIT the
@@ -706,6 +758,7 @@ int launch_als(mf_plan *p, int side, int other_generation)
 	MF_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(unsigned long long), p->stream));
 	if (sd.nrows <= 0) return MF_OK;
 	if (p->als_cg > 0) return launch_als_cg(p, side, other_generation, counts);
+	if (implicit && p->implicit_cg > 0) return launch_als_icg(p, side, other_generation, counts);
 	const AlsForm &form = kAlsForm[als_form(p->K, p->cfg.als_form)];
 	const int groups = mf::kAlsThreads / form.threads;
 	const int nb = (mf::als_blocks(p->K, form.bs) + form.threads - 1) / form.threads;

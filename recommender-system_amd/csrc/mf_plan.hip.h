@@ -290,6 +290,25 @@ inline AlsCgFn als_cg_fn(int form, int K)
 	if (form == mf_sched::kAlsCgDma) return two ? mf::als_cg_kernel<0, 2, true> : mf::als_cg_kernel<0, 1, true>;
 	return two ? mf::als_cg_kernel<0, 2, false> : mf::als_cg_kernel<0, 1, false>;
 }
+// The instances of the implicit conjugate-gradient solve (mf_als_icg.hip.h) by the same forms: K <= 128, so one piece per lane
+using AlsIcgFn = void (*)(mf::AlsArgs, mf::AlsImplicit, int, int);
+inline AlsIcgFn als_icg_fn(int form, int K)
+{
+	if (K < 1 || K > mf::kAlsMaxK) return nullptr;
+	if (form == mf_sched::kAlsCgFixed) {
+		switch (K) {
+		case 10: return mf::als_icg_kernel<10, 1, true>;
+		case 20: return mf::als_icg_kernel<20, 1, true>;
+		case 30: return mf::als_icg_kernel<30, 1, true>;
+		case 50: return mf::als_icg_kernel<50, 1, true>;
+		case 100: return mf::als_icg_kernel<100, 1, true>;
+		case 128: return mf::als_icg_kernel<128, 1, true>;
+		}
+		return nullptr;
+	}
+	if (form == mf_sched::kAlsCgDma) return (K & 1) ? nullptr : mf::als_icg_kernel<0, 1, true>;
+	return mf::als_icg_kernel<0, 1, false>;
+}
 // the Gram of a whole side (mf_gram.hip.h) by blocks of the triangle per thread, as the workgroup form above
 const GramFn kGramFn[3] = {mf::gram_block_kernel<1>, mf::gram_block_kernel<2>, mf::gram_block_kernel<3>};
 
@@ -328,6 +347,10 @@ struct mf_plan {
 	// (as many blocks as the longer side has), allocated together on first use
 	double confidence = 1.0;
 	dev_buf<double> gram, gram_partial;
+	// conjugate-gradient steps per row under MF_ALS_IMPLICIT (mf_plan_set_implicit_cg; 0: the direct solve), read at every
+	// launch, and the square its kernel reads the other side's Gram from (K rows of an even stride), allocated with the above
+	int implicit_cg = 0;
+	dev_buf<double> gram_square;
 	int flags = 0;
 
 	hipStream_t own_stream = nullptr;
