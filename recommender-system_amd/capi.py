@@ -562,25 +562,32 @@ def _bounds_record(b):
     return Bounds(lo, hi, int(b[2]) if len(b) > 2 else -1)
 
 
+def _run_boxed(name, inst, L, R, weight, lambda_users, lambda_items, bounds_users, bounds_items, iters, device, recommend, *tail,
+               betas=()):
+    """What the level-1 runs with a box per side share: mf_backend_run_<name>(problem, weight, L, R, best, the lambdas (one
+    value means both sides), `betas`, the bounds records, `tail`, device), checked; returns best[users] or None."""
+    p, keep = _problem(inst, iters)
+    w = None if weight is None else np.ascontiguousarray(weight, np.float64)
+    assert w is None or w.shape == (inst.nnz,)
+    li = lambda_users if lambda_items is None else lambda_items
+    bu, bit = _bounds_record(bounds_users), _bounds_record(bounds_items)
+    best = np.empty(inst.users, np.int32) if recommend else None
+    assert L.dtype == np.float64 and R.dtype == np.float64 and L.flags.c_contiguous and R.flags.c_contiguous
+    fn = "mf_backend_run_" + name
+    _check(getattr(hip(), fn)(C.byref(p), None if w is None else w.ctypes.data, L.ctypes.data, R.ctypes.data,
+                              best.ctypes.data if recommend else None, float(lambda_users), float(li), *betas,
+                              None if bu is None else C.byref(bu), None if bit is None else C.byref(bit), *tail, device), fn)
+    return best
+
+
 def backend_run_bounded(inst, L, R, bounds_users=None, bounds_items=None, weight=None, lambda_users=0.0, lambda_items=None,
                         beta_users=0.0, beta_items=None, iters=None, device=0, recommend=True):
     """mf_backend_run_bounded: backend_run_weighted with a box per side -- None (unbounded), (lo, hi) over all columns or
     (lo, hi, columns) over the leading `columns`; a finished row is projected onto it in every seeded sweep.  L, R updated in
     place, returns best[users], or None with recommend=False."""
-    p, keep = _problem(inst, iters)
-    w = None if weight is None else np.ascontiguousarray(weight, np.float64)
-    assert w is None or w.shape == (inst.nnz,)
-    li = lambda_users if lambda_items is None else lambda_items
     bi = beta_users if beta_items is None else beta_items
-    bu, bit = _bounds_record(bounds_users), _bounds_record(bounds_items)
-    best = np.empty(inst.users, np.int32) if recommend else None
-    assert L.dtype == np.float64 and R.dtype == np.float64 and L.flags.c_contiguous and R.flags.c_contiguous
-    _check(hip().mf_backend_run_bounded(C.byref(p), None if w is None else w.ctypes.data, L.ctypes.data, R.ctypes.data,
-                                        best.ctypes.data if recommend else None,
-                                        float(lambda_users), float(li), float(beta_users), float(bi),
-                                        None if bu is None else C.byref(bu), None if bit is None else C.byref(bit), device),
-           "mf_backend_run_bounded")
-    return best
+    return _run_boxed("bounded", inst, L, R, weight, lambda_users, lambda_items, bounds_users, bounds_items, iters, device, recommend,
+                      betas=(float(beta_users), float(bi)))
 
 
 run_bounded = backend_run_bounded
@@ -601,20 +608,9 @@ def backend_run_adaptive(inst, L, R, adaptive_users=None, adaptive_items=None, b
     """mf_backend_run_adaptive: backend_run_bounded without momentum and with an adaptive rule per side -- None (the plain
     step) or (kind, eta[, beta1, beta2[, eps]]), kind "adam" | "rmsprop" | "adagrad".  L, R updated in place, returns
     best[users], or None with recommend=False."""
-    p, keep = _problem(inst, iters)
-    w = None if weight is None else np.ascontiguousarray(weight, np.float64)
-    assert w is None or w.shape == (inst.nnz,)
-    li = lambda_users if lambda_items is None else lambda_items
-    bu, bit = _bounds_record(bounds_users), _bounds_record(bounds_items)
     au, ai = _adaptive_record(adaptive_users), _adaptive_record(adaptive_items)
-    best = np.empty(inst.users, np.int32) if recommend else None
-    assert L.dtype == np.float64 and R.dtype == np.float64 and L.flags.c_contiguous and R.flags.c_contiguous
-    _check(hip().mf_backend_run_adaptive(C.byref(p), None if w is None else w.ctypes.data, L.ctypes.data, R.ctypes.data,
-                                         best.ctypes.data if recommend else None, float(lambda_users), float(li),
-                                         None if bu is None else C.byref(bu), None if bit is None else C.byref(bit),
-                                         None if au is None else C.byref(au), None if ai is None else C.byref(ai), device),
-           "mf_backend_run_adaptive")
-    return best
+    return _run_boxed("adaptive", inst, L, R, weight, lambda_users, lambda_items, bounds_users, bounds_items, iters, device, recommend,
+                      None if au is None else C.byref(au), None if ai is None else C.byref(ai))
 
 
 run_adaptive = backend_run_adaptive
@@ -625,19 +621,8 @@ def backend_run_als(inst, L, R, kind="ridge", bounds_users=None, bounds_items=No
     """mf_backend_run_als: `iters` ALS iterations (kind "ridge" | "ridge-count") from the factors in L and R, with a lambda and
     a box per side and optional per-entry weights.  L, R updated in place, returns best[users], or None with
     recommend=False."""
-    p, keep = _problem(inst, iters)
-    w = None if weight is None else np.ascontiguousarray(weight, np.float64)
-    assert w is None or w.shape == (inst.nnz,)
-    li = lambda_users if lambda_items is None else lambda_items
-    bu, bit = _bounds_record(bounds_users), _bounds_record(bounds_items)
-    best = np.empty(inst.users, np.int32) if recommend else None
-    assert L.dtype == np.float64 and R.dtype == np.float64 and L.flags.c_contiguous and R.flags.c_contiguous
-    _check(hip().mf_backend_run_als(C.byref(p), None if w is None else w.ctypes.data, L.ctypes.data, R.ctypes.data,
-                                    best.ctypes.data if recommend else None, float(lambda_users), float(li),
-                                    None if bu is None else C.byref(bu), None if bit is None else C.byref(bit),
-                                    ALS_KINDS.get(kind, kind), device),
-           "mf_backend_run_als")
-    return best
+    return _run_boxed("als", inst, L, R, weight, lambda_users, lambda_items, bounds_users, bounds_items, iters, device, recommend,
+                      ALS_KINDS.get(kind, kind))
 
 
 run_als = backend_run_als
@@ -647,19 +632,8 @@ def backend_run_als_cg(inst, L, R, steps, kind="ridge", bounds_users=None, bound
                        lambda_items=None, iters=None, device=0, recommend=True):
     """mf_backend_run_als_cg: backend_run_als with `steps` conjugate-gradient steps per row in place of the direct solve (0: the
     direct solve); K up to 256."""
-    p, keep = _problem(inst, iters)
-    w = None if weight is None else np.ascontiguousarray(weight, np.float64)
-    assert w is None or w.shape == (inst.nnz,)
-    li = lambda_users if lambda_items is None else lambda_items
-    bu, bit = _bounds_record(bounds_users), _bounds_record(bounds_items)
-    best = np.empty(inst.users, np.int32) if recommend else None
-    assert L.dtype == np.float64 and R.dtype == np.float64 and L.flags.c_contiguous and R.flags.c_contiguous
-    _check(hip().mf_backend_run_als_cg(C.byref(p), None if w is None else w.ctypes.data, L.ctypes.data, R.ctypes.data,
-                                       best.ctypes.data if recommend else None, float(lambda_users), float(li),
-                                       None if bu is None else C.byref(bu), None if bit is None else C.byref(bit),
-                                       ALS_KINDS.get(kind, kind), int(steps), device),
-           "mf_backend_run_als_cg")
-    return best
+    return _run_boxed("als_cg", inst, L, R, weight, lambda_users, lambda_items, bounds_users, bounds_items, iters, device, recommend,
+                      ALS_KINDS.get(kind, kind), int(steps))
 
 
 run_als_cg = backend_run_als_cg
@@ -670,19 +644,8 @@ def backend_run_implicit(inst, L, R, conf=1.0, bounds_users=None, bounds_items=N
     """mf_backend_run_implicit: `iters` implicit-feedback ALS iterations at confidence 1 + conf * w from the factors in L and R,
     with a lambda and a box per side and optional per-entry weights.  L, R updated in place, returns best[users], or None
     with recommend=False."""
-    p, keep = _problem(inst, iters)
-    w = None if weight is None else np.ascontiguousarray(weight, np.float64)
-    assert w is None or w.shape == (inst.nnz,)
-    li = lambda_users if lambda_items is None else lambda_items
-    bu, bit = _bounds_record(bounds_users), _bounds_record(bounds_items)
-    best = np.empty(inst.users, np.int32) if recommend else None
-    assert L.dtype == np.float64 and R.dtype == np.float64 and L.flags.c_contiguous and R.flags.c_contiguous
-    _check(hip().mf_backend_run_implicit(C.byref(p), None if w is None else w.ctypes.data, L.ctypes.data, R.ctypes.data,
-                                         best.ctypes.data if recommend else None, float(lambda_users), float(li),
-                                         None if bu is None else C.byref(bu), None if bit is None else C.byref(bit),
-                                         float(conf), device),
-           "mf_backend_run_implicit")
-    return best
+    return _run_boxed("implicit", inst, L, R, weight, lambda_users, lambda_items, bounds_users, bounds_items, iters, device, recommend,
+                      float(conf))
 
 
 run_implicit = backend_run_implicit
@@ -692,19 +655,8 @@ def backend_run_implicit_cg(inst, L, R, steps, conf=1.0, bounds_users=None, boun
                             lambda_items=None, iters=None, device=0, recommend=True):
     """mf_backend_run_implicit_cg: backend_run_implicit with `steps` conjugate-gradient steps per row in place of the direct
     solve (0: the direct solve)."""
-    p, keep = _problem(inst, iters)
-    w = None if weight is None else np.ascontiguousarray(weight, np.float64)
-    assert w is None or w.shape == (inst.nnz,)
-    li = lambda_users if lambda_items is None else lambda_items
-    bu, bit = _bounds_record(bounds_users), _bounds_record(bounds_items)
-    best = np.empty(inst.users, np.int32) if recommend else None
-    assert L.dtype == np.float64 and R.dtype == np.float64 and L.flags.c_contiguous and R.flags.c_contiguous
-    _check(hip().mf_backend_run_implicit_cg(C.byref(p), None if w is None else w.ctypes.data, L.ctypes.data, R.ctypes.data,
-                                            best.ctypes.data if recommend else None, float(lambda_users), float(li),
-                                            None if bu is None else C.byref(bu), None if bit is None else C.byref(bit),
-                                            float(conf), int(steps), device),
-           "mf_backend_run_implicit_cg")
-    return best
+    return _run_boxed("implicit_cg", inst, L, R, weight, lambda_users, lambda_items, bounds_users, bounds_items, iters, device, recommend,
+                      float(conf), int(steps))
 
 
 run_implicit_cg = backend_run_implicit_cg

@@ -334,7 +334,7 @@ int mf_plan_flip(mf_plan *p)
 }
 
 // the implicit solve of a side with a frozen column: its all-pairs term needs a correction the header does not define
-static bool implicit_refuses(const mf_plan *p, int side) { return p->als_kind == MF_ALS_IMPLICIT && p->rule[side].frozen >= 0; }
+static bool implicit_refuses(const mf_plan *p, int side) { return als_solver(p).implicit && p->rule[side].frozen >= 0; }
 
 int mf_plan_iterate(mf_plan *p, int iters)
 {
@@ -607,9 +607,9 @@ int mf_plan_set_als(mf_plan *p, int kind)
 {
 	if (!p || !(als_kind_ok(kind) || kind == MF_ALS_IMPLICIT)) return MF_ERR_ARGUMENT;
 	if (kind != MF_ALS_OFF) {
-		// the triangle of a row lives in LDS; the conjugate-gradient solve forms none, and has no implicit kind
-		if (p->K > (p->als_cg > 0 ? mf_sched::kAlsCgMaxK : mf::kAlsMaxK)) return MF_ERR_UNSUPPORTED;
-		if (kind == MF_ALS_IMPLICIT && p->als_cg > 0) return MF_ERR_UNSUPPORTED;
+		// the solve this kind would run (als_solver, mf_schedule.h) takes the plan's K and, under the implicit kind, is implicit
+		const mf_sched::AlsSolver s = mf_sched::als_solver(kind, p->als_cg, p->implicit_cg);
+		if (p->K > s.max_k || (kind == MF_ALS_IMPLICIT && !s.implicit)) return MF_ERR_UNSUPPORTED;
 		// a solve has neither a previous step nor a gradient: momentum or an adaptive side came first
 		if (p->rule[0].beta != 0.0 || p->rule[1].beta != 0.0 || adaptive_any(p)) return MF_ERR_UNSUPPORTED;
 	}
@@ -637,8 +637,10 @@ int mf_plan_get_als(mf_plan *p, int *kind)
 int mf_plan_set_als_cg(mf_plan *p, int steps)
 {
 	if (!p || steps < 0 || steps > MF_ALS_CG_MAX_STEPS) return MF_ERR_ARGUMENT;
-	if (steps > 0 && (p->K > mf_sched::kAlsCgMaxK || p->als_kind == MF_ALS_IMPLICIT)) return MF_ERR_UNSUPPORTED;
-	if (steps == 0 && p->als_kind != MF_ALS_OFF && p->K > mf::kAlsMaxK) return MF_ERR_UNSUPPORTED;   // the direct solve has no such K
+	// the solve these steps would run (als_solver, mf_schedule.h): implicit under the implicit kind, and K within its limit
+	const mf_sched::AlsSolver s = mf_sched::als_solver(p->als_kind, steps, p->implicit_cg);
+	if (p->als_kind == MF_ALS_IMPLICIT && !s.implicit) return MF_ERR_UNSUPPORTED;
+	if (p->K > s.max_k && (s.cg || p->als_kind != MF_ALS_OFF)) return MF_ERR_UNSUPPORTED;
 	p->als_cg = steps;   // read at every launch
 	return MF_OK;
 }
@@ -1075,19 +1077,19 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 		append(buf, buflen, " adaptive=%s/%s", sd[1], sd[0]);
 	}
 	// the solver of mf_plan_iterate when it is not the gradient step, and the form its solves launch
-	if ((p->als_kind == MF_ALS_RIDGE || p->als_kind == MF_ALS_RIDGE_COUNT) && p->als_cg > 0) {
-		append(buf, buflen, " als=%s als_cg=%d als_cg_form=%s(chunk=%d)", p->als_kind == MF_ALS_RIDGE ? "ridge" : "ridge-count", p->als_cg,
-		       kAlsCgFormName[als_cg_form(p->K, p->cfg.als_cg_form)], als_cg_chunk(p->K));
-	} else if (p->als_kind == MF_ALS_RIDGE || p->als_kind == MF_ALS_RIDGE_COUNT) {
-		const AlsForm &form = kAlsForm[als_form(p->K, p->cfg.als_form)];
-		append(buf, buflen, " als=%s als_form=%s(chunk=%d)", p->als_kind == MF_ALS_RIDGE ? "ridge" : "ridge-count", form.name, form.nch);
-	}
-	if (p->als_kind == MF_ALS_IMPLICIT && p->implicit_cg > 0) {
-		append(buf, buflen, " als=implicit conf=%.17g implicit_cg=%d als_cg_form=%s(chunk=%d)", p->confidence, p->implicit_cg,
-		       kAlsCgFormName[als_cg_form(p->K, p->cfg.als_cg_form)], als_cg_chunk(p->K));
-	} else if (p->als_kind == MF_ALS_IMPLICIT) {
-		const AlsForm &form = kAlsForm[als_form(p->K, p->cfg.als_form)];
-		append(buf, buflen, " als=implicit conf=%.17g als_form=%s(chunk=%d)", p->confidence, form.name, form.nch);
+	if (p->als_kind != MF_ALS_OFF) {
+		const mf_sched::AlsSolver s = als_solver(p);
+		if (s.implicit)
+			append(buf, buflen, " als=implicit conf=%.17g", p->confidence);
+		else
+			append(buf, buflen, " als=%s", p->als_kind == MF_ALS_RIDGE ? "ridge" : "ridge-count");
+		if (s.cg) {
+			append(buf, buflen, " %s=%d als_cg_form=%s(chunk=%d)", s.implicit ? "implicit_cg" : "als_cg", s.steps,
+			       kAlsCgFormName[als_cg_form(p->K, p->cfg.als_cg_form)], als_cg_chunk(p->K));
+		} else {
+			const AlsForm &form = kAlsForm[als_form(p->K, p->cfg.als_form)];
+			append(buf, buflen, " als_form=%s(chunk=%d)", form.name, form.nch);
+		}
 	}
 	// the environment switches this plan was created under, when any differs from its default (mf_config.hip.h)
 	const std::string cfg = p->cfg.describe();
@@ -1139,46 +1141,56 @@ static RulePair level1_rules(double lambda_users, double lambda_items, double be
 }
 
 // The level-1 run: a plan over the whole problem (weighted when `weight` is given), the factors up, the update rules the
-// entry point checked, pr->iters iterations, the recommendations when asked for, the factors back into L and R.
-static int run_single_plan(const mf_problem *pr, const double *weight, const RulePair &rule, double *L, double *R, int32_t *best, int device)
+// entry point checked, `setup(plan)` where the entry point has more to set (the ALS runs: their solver), pr->iters
+// iterations, the recommendations when asked for, the factors back into L and R.
+using PlanSetup = std::function<int(mf_plan *)>;
+static int run_single_plan(const mf_problem *pr, const double *weight, const RulePair &rule, double *L, double *R, int32_t *best, int device,
+                           const PlanSetup &setup = nullptr)
 {
 	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
 		p->rule[0] = rule[0], p->rule[1] = rule[1];   // both sides at rest, as the upload left them
-		int rc = mf_plan_iterate(p, pr->iters);
+		int rc = setup ? setup(p) : MF_OK;
+		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
 		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
 		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
 		return rc;
 	}, weight);
 }
 
+// what every mf_backend_run_* checks: the problem, L and R (they carry the initial factors in), its weights, its bounds
+static bool run_args_ok(const mf_problem *pr, const double *L, const double *R, std::initializer_list<double> weights = {},
+                        const mf_bounds *bounds_users = nullptr, const mf_bounds *bounds_items = nullptr)
+{
+	return pr && L && R && std::all_of(weights.begin(), weights.end(), lambda_ok) && bounds_record_ok(bounds_users, pr->features) &&
+	       bounds_record_ok(bounds_items, pr->features);
+}
+
 extern "C" {
 
 int mf_backend_run(const mf_problem *pr, double *L, double *R, int32_t *best, int device)
 {
-	if (!pr || !L || !R) return MF_ERR_ARGUMENT;   // L and R carry the initial factors in
+	if (!run_args_ok(pr, L, R)) return MF_ERR_ARGUMENT;
 	return run_single_plan(pr, nullptr, RulePair{}, L, R, best, device);
 }
 
 int mf_backend_run_reg(const mf_problem *pr, double *L, double *R, int32_t *best, double lambda_users, double lambda_items,
                        int device)
 {
-	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items)) return MF_ERR_ARGUMENT;
+	if (!run_args_ok(pr, L, R, {lambda_users, lambda_items})) return MF_ERR_ARGUMENT;
 	return run_single_plan(pr, nullptr, level1_rules(lambda_users, lambda_items), L, R, best, device);
 }
 
 int mf_backend_run_momentum(const mf_problem *pr, double *L, double *R, int32_t *best, double lambda_users, double lambda_items,
                             double beta_users, double beta_items, int device)
 {
-	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !lambda_ok(beta_users) || !lambda_ok(beta_items))
-		return MF_ERR_ARGUMENT;
+	if (!run_args_ok(pr, L, R, {lambda_users, lambda_items, beta_users, beta_items})) return MF_ERR_ARGUMENT;
 	return run_single_plan(pr, nullptr, level1_rules(lambda_users, lambda_items, beta_users, beta_items), L, R, best, device);
 }
 
 int mf_backend_run_weighted(const mf_problem *pr, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
                             double lambda_items, double beta_users, double beta_items, int device)
 {
-	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !lambda_ok(beta_users) || !lambda_ok(beta_items))
-		return MF_ERR_ARGUMENT;
+	if (!run_args_ok(pr, L, R, {lambda_users, lambda_items, beta_users, beta_items})) return MF_ERR_ARGUMENT;
 	return run_single_plan(pr, weight, level1_rules(lambda_users, lambda_items, beta_users, beta_items), L, R, best, device);
 }
 
@@ -1186,9 +1198,7 @@ int mf_backend_run_bounded(const mf_problem *pr, const double *weight, double *L
                            double lambda_items, double beta_users, double beta_items, const mf_bounds *bounds_users,
                            const mf_bounds *bounds_items, int device)
 {
-	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !lambda_ok(beta_users) || !lambda_ok(beta_items) ||
-	    !bounds_record_ok(bounds_users, pr->features) || !bounds_record_ok(bounds_items, pr->features))
-		return MF_ERR_ARGUMENT;
+	if (!run_args_ok(pr, L, R, {lambda_users, lambda_items, beta_users, beta_items}, bounds_users, bounds_items)) return MF_ERR_ARGUMENT;
 	return run_single_plan(pr, weight, level1_rules(lambda_users, lambda_items, beta_users, beta_items, bounds_users, bounds_items), L, R,
 	                       best, device);
 }
@@ -1198,8 +1208,7 @@ int mf_backend_run_adaptive(const mf_problem *pr, const double *weight, double *
                             double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items,
                             const mf_adaptive *adaptive_users, const mf_adaptive *adaptive_items, int device)
 {
-	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !bounds_record_ok(bounds_users, pr->features) ||
-	    !bounds_record_ok(bounds_items, pr->features) || !adaptive_ok(adaptive_users) || !adaptive_ok(adaptive_items))
+	if (!run_args_ok(pr, L, R, {lambda_users, lambda_items}, bounds_users, bounds_items) || !adaptive_ok(adaptive_users) || !adaptive_ok(adaptive_items))
 		return MF_ERR_ARGUMENT;
 	RulePair rule = level1_rules(lambda_users, lambda_items, 0.0, 0.0, bounds_users, bounds_items);
 	rule[1].opt = adaptive_rule(adaptive_users), rule[0].opt = adaptive_rule(adaptive_items);
@@ -1220,19 +1229,13 @@ int mf_backend_run_als_cg(const mf_problem *pr, const double *weight, double *L,
                           double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, int kind, int steps,
                           int device)
 {
-	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !bounds_record_ok(bounds_users, pr->features) ||
-	    !bounds_record_ok(bounds_items, pr->features) || !als_kind_ok(kind) || steps < 0 || steps > MF_ALS_CG_MAX_STEPS)
+	if (!run_args_ok(pr, L, R, {lambda_users, lambda_items}, bounds_users, bounds_items) || !als_kind_ok(kind) || steps < 0 || steps > MF_ALS_CG_MAX_STEPS)
 		return MF_ERR_ARGUMENT;
 	const RulePair rule = level1_rules(lambda_users, lambda_items, 0.0, 0.0, bounds_users, bounds_items);
-	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
-		p->rule[0] = rule[0], p->rule[1] = rule[1];
-		int rc = mf_plan_set_als_cg(p, steps);
-		if (rc == MF_OK) rc = mf_plan_set_als(p, kind);
-		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
-		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
-		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
-		return rc;
-	}, weight);
+	return run_single_plan(pr, weight, rule, L, R, best, device, [&](mf_plan *p) {
+		const int rc = mf_plan_set_als_cg(p, steps);
+		return rc == MF_OK ? mf_plan_set_als(p, kind) : rc;
+	});
 }
 
 // the implicit-feedback run: mf_backend_run_als with the implicit kind and its confidence
@@ -1247,20 +1250,15 @@ int mf_backend_run_implicit_cg(const mf_problem *pr, const double *weight, doubl
                                double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, double conf, int steps,
                                int device)
 {
-	if (!pr || !L || !R || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) || !bounds_record_ok(bounds_users, pr->features) ||
-	    !bounds_record_ok(bounds_items, pr->features) || !std::isfinite(conf) || conf < 0.0 || steps < 0 || steps > MF_ALS_CG_MAX_STEPS)
+	if (!run_args_ok(pr, L, R, {lambda_users, lambda_items}, bounds_users, bounds_items) || !std::isfinite(conf) || conf < 0.0 || steps < 0 ||
+	    steps > MF_ALS_CG_MAX_STEPS)
 		return MF_ERR_ARGUMENT;
 	const RulePair rule = level1_rules(lambda_users, lambda_items, 0.0, 0.0, bounds_users, bounds_items);
-	return with_single_plan(pr, device, L, R, [&](mf_plan *p) {
-		p->rule[0] = rule[0], p->rule[1] = rule[1];
+	return run_single_plan(pr, weight, rule, L, R, best, device, [&](mf_plan *p) {
 		int rc = mf_plan_set_confidence(p, conf);
 		if (rc == MF_OK) rc = mf_plan_set_implicit_cg(p, steps);
-		if (rc == MF_OK) rc = mf_plan_set_als(p, MF_ALS_IMPLICIT);
-		if (rc == MF_OK) rc = mf_plan_iterate(p, pr->iters);
-		if (rc == MF_OK && best) rc = mf_plan_recommend(p, best);
-		if (rc == MF_OK) rc = mf_plan_download_factors(p, L, R);
-		return rc;
-	}, weight);
+		return rc == MF_OK ? mf_plan_set_als(p, MF_ALS_IMPLICIT) : rc;
+	});
 }
 
 int mf_backend_bias_mean(const double *val, int64_t n, double *mu)
@@ -1302,8 +1300,8 @@ int mf_backend_bias_unpack(const double *in, int32_t rows, int32_t F, int side, 
 int mf_backend_run_biased(const mf_problem *pr, double *L, double *R, double *user_bias, double *item_bias, double *mu,
                           int32_t *best, double lambda_users, double lambda_items, int device)
 {
-	if (!pr || !L || !R || !user_bias || !item_bias || !mu || !lambda_ok(lambda_users) || !lambda_ok(lambda_items) ||
-	    pr->users < 0 || pr->items < 0 || pr->features < 1 || pr->nnz < 0 || pr->iters < 0 || (pr->nnz > 0 && !pr->entries))
+	if (!run_args_ok(pr, L, R, {lambda_users, lambda_items}) || !user_bias || !item_bias || !mu || pr->users < 0 || pr->items < 0 ||
+	    pr->features < 1 || pr->nnz < 0 || pr->iters < 0 || (pr->nnz > 0 && !pr->entries))
 		return MF_ERR_ARGUMENT;
 	if (pr->features > kLargestK - 2) return MF_ERR_UNSUPPORTED;
 	const int32_t F = pr->features, K = F + 2;

@@ -618,7 +618,7 @@ int gram_buffers(mf_plan *p)
 	const size_t blocks = (size_t) std::max(1, std::max(gram_blocks(p->items), gram_blocks(p->uc)));
 	int rc = p->gram_partial.alloc(blocks * tri);
 	if (rc == MF_OK) rc = p->gram.alloc(2 * tri);
-	if (rc == MF_OK) rc = p->gram_square.alloc((size_t) p->K * mf::als_icg_ld(p->K));   // what launch_als_icg reads S from
+	if (rc == MF_OK) rc = p->gram_square.alloc((size_t) p->K * mf::als_icg_ld(p->K));   // what the implicit conjugate-gradient solve reads S from
 	if (rc != MF_OK) p->gram_partial.reset(), p->gram.reset();
 	return rc;
 }
@@ -648,132 +648,19 @@ int launch_gram(mf_plan *p, int side, int generation)
 	return MF_OK;
 }
 
-// The conjugate-gradient solve of a side (mf_plan_set_als_cg with steps > 0; the counters are zeroed): one wave per row, one
-// launch over the side's rows in its dispatch order, as the direct solve below.  The steps and the rule of the side are read
-// here, at every launch.
-int launch_als_cg(mf_plan *p, int side, int other_generation, unsigned long long *counts)
-{
-	const SweepSide &sd = p->side[side];
-	const AlsCgFn fn = als_cg_fn(als_cg_form(p->K, p->cfg.als_cg_form), p->K);
-	if (!fn) return MF_ERR_UNSUPPORTED;   // a missing instance is an error, never another kernel
-	const int nch = als_cg_chunk(p->K);
-	const size_t lds = mf::als_cg_lds_bytes(p->K, nch);
-	MF_HIP(raise_lds_limit((const void *) fn, lds));
+// which solve the plan's next launch runs: the rule of mf_schedule.h on the plan's three fields, read at every launch
+mf_sched::AlsSolver als_solver(const mf_plan *p) { return mf_sched::als_solver(p->als_kind, p->als_cg, p->implicit_cg); }
 
+// the arguments every row solve of a side takes, but the row list (walk_row_lists' caller fills it per launch)
+mf::AlsArgs als_args(const mf_plan *p, int side, int other_generation, unsigned long long *counts)
+{
 	const SideUpdate u = side_update(p, side, 1);
 	const SideOperands x = side_operands(p, side);
 	mf::AlsArgs a;
 	a.K = p->K;
 	a.ldx = x.ldx;
 	a.ldy = x.ldy;
-	a.frozen = u.frozen;
-	a.count_scaled = p->als_kind == MF_ALS_RIDGE_COUNT;
-	a.lambda = p->rule[side].lambda;
-	a.ptr = x.ptr;
-	a.idx = x.idx;
-	a.val = x.val;
-	a.wgt = x.wgt;
-	a.X_old = x.X_old;
-	a.X_new = x.X_new;
-	a.Y = other_generation ? side_operands(p, side ^ 1).X_new : x.Y_old;
-	a.counts = counts;
-	a.box = u.box;
-	auto launch = [&](const int *rowlist, int nrows) {
-		if (nrows <= 0) return MF_OK;
-		a.rowlist = rowlist;
-		a.nrows = nrows;
-		hipLaunchKernelGGL(fn, dim3(nrows), dim3(mf::kWave), lds, p->stream, a, p->als_cg, nch);
-		MF_HIP(hipGetLastError());
-		return MF_OK;
-	};
-	if (sd.n_long > 0) {
-		MF_TRY(launch(sd.long_rows, sd.n_long));
-		return launch(sd.short_rows, sd.n_short);
-	}
-	return launch(sd.lpt ? sd.short_rows.get() : nullptr, sd.nrows);
-}
-
-// The implicit conjugate-gradient solve of a side (mf_plan_set_implicit_cg with steps > 0 under MF_ALS_IMPLICIT; the Gram of
-// the other side is enqueued and the counters are zeroed): the packed triangle is copied into the plan's square, then one
-// wave per row runs J0 .. J5, one launch over the side's rows in its dispatch order, as launch_als_cg.
-int launch_als_icg(mf_plan *p, int side, int other_generation, unsigned long long *counts)
-{
-	const SweepSide &sd = p->side[side];
-	const AlsIcgFn fn = als_icg_fn(als_cg_form(p->K, p->cfg.als_cg_form), p->K);
-	if (!fn) return MF_ERR_UNSUPPORTED;   // a missing instance is an error, never another kernel
-	const int nch = als_cg_chunk(p->K);
-	const size_t lds = mf::als_cg_lds_bytes(p->K, nch);
-	MF_HIP(raise_lds_limit((const void *) fn, lds));
-
-	const int ld = mf::als_icg_ld(p->K), cells = p->K * ld;
-	hipLaunchKernelGGL(mf::gram_square_kernel, dim3((cells + mf::kGramThreads - 1) / mf::kGramThreads), dim3(mf::kGramThreads), 0, p->stream,
-	                   (const double *) p->gram.get() + (size_t) (side ^ 1) * mf::als_triangle(p->K), p->K, ld, p->gram_square.get());
-	MF_HIP(hipGetLastError());
-
-	const SideUpdate u = side_update(p, side, 1);
-	const SideOperands x = side_operands(p, side);
-	mf::AlsArgs a;
-	a.K = p->K;
-	a.ldx = x.ldx;
-	a.ldy = x.ldy;
-	a.frozen = -1;   // the caller has refused a frozen column
-	a.count_scaled = 0;
-	a.lambda = p->rule[side].lambda;
-	a.ptr = x.ptr;
-	a.idx = x.idx;
-	a.val = x.val;
-	a.wgt = x.wgt;
-	a.X_old = x.X_old;
-	a.X_new = x.X_new;
-	a.Y = other_generation ? side_operands(p, side ^ 1).X_new : x.Y_old;
-	a.counts = counts;
-	a.box = u.box;
-	const mf::AlsImplicit im{p->gram_square.get(), p->confidence};
-	auto launch = [&](const int *rowlist, int nrows) {
-		if (nrows <= 0) return MF_OK;
-		a.rowlist = rowlist;
-		a.nrows = nrows;
-		hipLaunchKernelGGL(fn, dim3(nrows), dim3(mf::kWave), lds, p->stream, a, im, p->implicit_cg, nch);
-		MF_HIP(hipGetLastError());
-		return MF_OK;
-	};
-	if (sd.n_long > 0) {
-		MF_TRY(launch(sd.long_rows, sd.n_long));
-		return launch(sd.short_rows, sd.n_short);
-	}
-	return launch(sd.lpt ? sd.short_rows.get() : nullptr, sd.nrows);
-}
-
-// One solve of a side (0: items, 1: users) against the other side's current (0) or next (1) buffer, into the side's
-// next buffer: the counters zeroed, then one launch over the side's rows in its dispatch order -- the extreme rows of a
-// split side first, they are its longest.  The rule of the side is read here, at every launch.  Under MF_ALS_IMPLICIT the
-// Gram of the other side in that generation is enqueued first and the implicit instances run (the caller has refused a
-// frozen column).
-int launch_als(mf_plan *p, int side, int other_generation)
-{
-	const SweepSide &sd = p->side[side];
-	const bool implicit = p->als_kind == MF_ALS_IMPLICIT;
-	if (implicit) MF_TRY(launch_gram(p, side ^ 1, other_generation));
-	unsigned long long *counts = p->als_counts.get() + 3 * side;
-	MF_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(unsigned long long), p->stream));
-	if (sd.nrows <= 0) return MF_OK;
-	if (p->als_cg > 0) return launch_als_cg(p, side, other_generation, counts);
-	if (implicit && p->implicit_cg > 0) return launch_als_icg(p, side, other_generation, counts);
-	const AlsForm &form = kAlsForm[als_form(p->K, p->cfg.als_form)];
-	const int groups = mf::kAlsThreads / form.threads;
-	const int nb = (mf::als_blocks(p->K, form.bs) + form.threads - 1) / form.threads;
-	const AlsFn fn = form.fn[nb - 1];
-	const AlsImplicitFn ifn = form.implicit[nb - 1];
-	const size_t lds = (size_t) groups * mf::als_group_doubles(p->K, form.bs, form.nch, implicit || p->weighted) * sizeof(double);
-	MF_HIP(raise_lds_limit(implicit ? (const void *) ifn : (const void *) fn, lds));
-
-	const SideUpdate u = side_update(p, side, 1);
-	mf::AlsArgs a;
-	a.K = p->K;
-	const SideOperands x = side_operands(p, side);
-	a.ldx = x.ldx;
-	a.ldy = x.ldy;
-	a.frozen = u.frozen;
+	a.frozen = u.frozen;   // -1 under the implicit kind: the caller has refused a frozen column
 	a.count_scaled = p->als_kind == MF_ALS_RIDGE_COUNT;
 	a.lambda = p->rule[side].lambda;
 	a.ptr = x.ptr;
@@ -785,23 +672,73 @@ int launch_als(mf_plan *p, int side, int other_generation)
 	a.Y = other_generation ? side_operands(p, side ^ 1).X_new : x.Y_old;   // the other side's next buffer, or its current one
 	a.counts = counts;
 	a.box = u.box;
-	auto launch = [&](const int *rowlist, int nrows) {
-		if (nrows <= 0) return MF_OK;
+	return a;
+}
+
+// The row lists of a side in its dispatch order, launch(rowlist, nrows) for each that has rows: the extreme rows of a split
+// side first, they are its longest, then the others; a side without extreme rows in one launch, over its LPT list or none.
+template <class Launch>
+int walk_row_lists(const SweepSide &sd, Launch launch)
+{
+	if (sd.n_long > 0) {
+		if (int rc = launch(sd.long_rows.get(), sd.n_long); rc != MF_OK) return rc;
+		return sd.n_short > 0 ? launch(sd.short_rows.get(), sd.n_short) : MF_OK;
+	}
+	return sd.nrows > 0 ? launch(sd.lpt ? sd.short_rows.get() : nullptr, sd.nrows) : MF_OK;
+}
+
+// One solve of a side (0: items, 1: users) against the other side's current (0) or next (1) buffer, into the side's next
+// buffer; the only function that launches a row solve.  The rule (als_solver), the steps and the side's update rule are read
+// here, at every launch.  Under the implicit kind the Gram of the other side in that generation is enqueued first (the caller
+// has refused a frozen column): the direct solve reads it as the packed triangle, the conjugate-gradient one as the plan's
+// square, copied in front of it.  Then the counters zeroed and one launch per row list of the side.
+int launch_als(mf_plan *p, int side, int other_generation)
+{
+	const SweepSide &sd = p->side[side];
+	const mf_sched::AlsSolver s = als_solver(p);
+	if (s.implicit) MF_TRY(launch_gram(p, side ^ 1, other_generation));
+	unsigned long long *counts = p->als_counts.get() + 3 * side;
+	MF_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(unsigned long long), p->stream));
+	if (sd.nrows <= 0) return MF_OK;
+	mf::AlsImplicit im{s.implicit ? p->gram.get() + (size_t) (side ^ 1) * mf::als_triangle(p->K) : nullptr, p->confidence};
+	if (s.implicit && s.cg) {
+		const int ld = mf::als_icg_ld(p->K), cells = p->K * ld;
+		hipLaunchKernelGGL(mf::gram_square_kernel, dim3((cells + mf::kGramThreads - 1) / mf::kGramThreads), dim3(mf::kGramThreads), 0, p->stream,
+		                   im.S, p->K, ld, p->gram_square.get());
+		MF_HIP(hipGetLastError());
+		im.S = p->gram_square.get();
+	}
+	mf::AlsArgs a = als_args(p, side, other_generation, counts);
+
+	// the instance, the rows of a workgroup, its threads and LDS request, and the arguments behind `a` in the kernel's order
+	const void *fn;
+	int rows_per_wg, threads, steps = s.steps, nch = 0;
+	size_t lds;
+	if (s.cg) {
+		const int form = als_cg_form(p->K, p->cfg.als_cg_form);
+		fn = s.implicit ? als_cg_fn<mf::AlsImplicit>(form, p->K) : als_cg_fn<>(form, p->K);
+		nch = als_cg_chunk(p->K);
+		rows_per_wg = 1, threads = mf::kWave, lds = mf::als_cg_lds_bytes(p->K, nch);
+	} else {
+		const AlsForm &form = kAlsForm[als_form(p->K, p->cfg.als_form)];
+		const int nb = (mf::als_blocks(p->K, form.bs) + form.threads - 1) / form.threads;
+		fn = s.implicit ? (const void *) form.implicit[nb - 1] : (const void *) form.fn[nb - 1];
+		rows_per_wg = mf::kAlsThreads / form.threads, threads = mf::kAlsThreads;
+		lds = (size_t) rows_per_wg * mf::als_group_doubles(p->K, form.bs, form.nch, s.implicit || p->weighted) * sizeof(double);
+	}
+	if (!fn) return MF_ERR_UNSUPPORTED;   // a missing instance is an error, never another kernel
+	MF_HIP(raise_lds_limit(fn, lds));
+	void *args[4] = {&a};
+	int nargs = 1;
+	if (s.implicit) args[nargs++] = &im;
+	if (s.cg) args[nargs++] = &steps, args[nargs++] = &nch;
+
+	return walk_row_lists(sd, [&](const int *rowlist, int nrows) {
 		a.rowlist = rowlist;
 		a.nrows = nrows;
-		if (implicit)
-			hipLaunchKernelGGL(ifn, dim3((nrows + groups - 1) / groups), dim3(mf::kAlsThreads), lds, p->stream, a,
-			                   mf::AlsImplicit{p->gram.get() + (size_t) (side ^ 1) * mf::als_triangle(p->K), p->confidence});
-		else
-			hipLaunchKernelGGL(fn, dim3((nrows + groups - 1) / groups), dim3(mf::kAlsThreads), lds, p->stream, a);
-		MF_HIP(hipGetLastError());
+		MF_HIP(hipLaunchKernel(fn, dim3((nrows + rows_per_wg - 1) / rows_per_wg), dim3(threads), args, lds, p->stream));
 		return MF_OK;
-	};
-	if (sd.n_long > 0) {
-		MF_TRY(launch(sd.long_rows, sd.n_long));
-		return launch(sd.short_rows, sd.n_short);
-	}
-	return launch(sd.lpt ? sd.short_rows.get() : nullptr, sd.nrows);
+	});
 }
 
 // ---- the loops of mf_plan_iterate, one per mf_sched::Loop (iterate_path, mf_schedule.h, picks; mf_plan_iterate dispatches)

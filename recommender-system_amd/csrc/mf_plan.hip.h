@@ -268,46 +268,41 @@ const AlsForm kAlsForm[kAlsForms] = {
      {mf::als_kernel<mf::kWave, 2, 1>, mf::als_kernel<mf::kWave, 2, 2>, mf::als_kernel<mf::kWave, 2, 3>},
      {mf::als_kernel<mf::kWave, 2, 1, mf::AlsImplicit>, mf::als_kernel<mf::kWave, 2, 2, mf::AlsImplicit>, mf::als_kernel<mf::kWave, 2, 3, mf::AlsImplicit>}},
 };
-// The forms of the conjugate-gradient solve (mf_als_cg.hip.h) in the order of mf_sched::AlsCgFormId; als_cg_form (mf_launch.hip.h)
-// picks one, als_cg_fn its instance for a K the form takes.
-using AlsCgFn = void (*)(mf::AlsArgs, int, int);
+// The forms of the conjugate-gradient solve in the order of mf_sched::AlsCgFormId; als_cg_form (mf_launch.hip.h) picks one,
+// als_cg_fn<>(form, K) its explicit instance (als_cg_kernel, mf_als_cg.hip.h), als_cg_fn<mf::AlsImplicit>(form, K) its
+// implicit one (als_icg_kernel, mf_als_icg.hip.h): null where the form does not take the K, and for the implicit kind above
+// K = 128 -- it has one piece per lane, so none of the two-pass instances.
 const char *const kAlsCgFormName[mf_sched::kAlsCgForms] = {"fixed", "dma", "general"};
-inline AlsCgFn als_cg_fn(int form, int K)
+static_assert(mf_sched::kAlsImplicitKind == MF_ALS_IMPLICIT && mf_sched::kAlsDirectMaxK == mf::kAlsMaxK, "als_solver (mf_schedule.h) restates both");
+template <int KT, int NP, bool DMA, class... IM>
+inline const void *als_cg_instance()
 {
+	if constexpr (sizeof...(IM) == 0)
+		return (const void *) mf::als_cg_kernel<KT, NP, DMA>;
+	else if constexpr (NP == 1)
+		return (const void *) mf::als_icg_kernel<KT, NP, DMA>;
+	else
+		return nullptr;
+}
+template <class... IM>
+inline const void *als_cg_fn(int form, int K)
+{
+	if (!mf_sched::als_cg_takes(form, K) || (sizeof...(IM) == 1 && K > mf::kAlsMaxK)) return nullptr;
 	if (form == mf_sched::kAlsCgFixed) {
 		switch (K) {
-		case 10: return mf::als_cg_kernel<10, 1, true>;
-		case 20: return mf::als_cg_kernel<20, 1, true>;
-		case 30: return mf::als_cg_kernel<30, 1, true>;
-		case 50: return mf::als_cg_kernel<50, 1, true>;
-		case 100: return mf::als_cg_kernel<100, 1, true>;
-		case 128: return mf::als_cg_kernel<128, 1, true>;
-		case 256: return mf::als_cg_kernel<256, 2, true>;
+		case 10: return als_cg_instance<10, 1, true, IM...>();
+		case 20: return als_cg_instance<20, 1, true, IM...>();
+		case 30: return als_cg_instance<30, 1, true, IM...>();
+		case 50: return als_cg_instance<50, 1, true, IM...>();
+		case 100: return als_cg_instance<100, 1, true, IM...>();
+		case 128: return als_cg_instance<128, 1, true, IM...>();
+		case 256: return als_cg_instance<256, 2, true, IM...>();
 		}
 		return nullptr;
 	}
 	const bool two = mf::als_cg_passes(K) == 2;
-	if (form == mf_sched::kAlsCgDma) return two ? mf::als_cg_kernel<0, 2, true> : mf::als_cg_kernel<0, 1, true>;
-	return two ? mf::als_cg_kernel<0, 2, false> : mf::als_cg_kernel<0, 1, false>;
-}
-// The instances of the implicit conjugate-gradient solve (mf_als_icg.hip.h) by the same forms: K <= 128, so one piece per lane
-using AlsIcgFn = void (*)(mf::AlsArgs, mf::AlsImplicit, int, int);
-inline AlsIcgFn als_icg_fn(int form, int K)
-{
-	if (K < 1 || K > mf::kAlsMaxK) return nullptr;
-	if (form == mf_sched::kAlsCgFixed) {
-		switch (K) {
-		case 10: return mf::als_icg_kernel<10, 1, true>;
-		case 20: return mf::als_icg_kernel<20, 1, true>;
-		case 30: return mf::als_icg_kernel<30, 1, true>;
-		case 50: return mf::als_icg_kernel<50, 1, true>;
-		case 100: return mf::als_icg_kernel<100, 1, true>;
-		case 128: return mf::als_icg_kernel<128, 1, true>;
-		}
-		return nullptr;
-	}
-	if (form == mf_sched::kAlsCgDma) return (K & 1) ? nullptr : mf::als_icg_kernel<0, 1, true>;
-	return mf::als_icg_kernel<0, 1, false>;
+	if (form == mf_sched::kAlsCgDma) return two ? als_cg_instance<0, 2, true, IM...>() : als_cg_instance<0, 1, true, IM...>();
+	return two ? als_cg_instance<0, 2, false, IM...>() : als_cg_instance<0, 1, false, IM...>();
 }
 // the Gram of a whole side (mf_gram.hip.h) by blocks of the triangle per thread, as the workgroup form above
 const GramFn kGramFn[3] = {mf::gram_block_kernel<1>, mf::gram_block_kernel<2>, mf::gram_block_kernel<3>};

@@ -631,4 +631,25 @@ constexpr int als_cg_chunk(size_t head, size_t row_bytes, size_t lds_per_cu)
 	return fit > 12 ? (int) fit : 12;
 }
 
+// ---- which ALS solve a launch runs: the one rule over the plan's kind (mf_plan_set_als; kAlsImplicitKind is the header's
+// MF_ALS_IMPLICIT, mf_plan.hip.h asserts it), the steps of mf_plan_set_als_cg and those of mf_plan_set_implicit_cg.  The steps
+// of the explicit kinds come first and make the solve theirs; the implicit steps count under the implicit kind alone.  The
+// launch, mf_plan_describe and the setters all read it: a setter refuses the state whose solve does not take the plan's K,
+// and the implicit kind where the solve would not be an implicit one.
+constexpr int kAlsImplicitKind = 4;
+constexpr int kAlsDirectMaxK = 128;   // the direct solve keeps a row's triangle in LDS (mf_als.hip.h: kAlsMaxK)
+struct AlsSolver {
+	bool cg;         // conjugate gradient (mf_als_cg.hip.h); otherwise the direct solve (mf_als.hip.h)
+	bool implicit;   // S and the confidence beside the arguments
+	int steps;       // conjugate-gradient steps per row, 0 for the direct solve
+	int max_k;       // the widest K it takes
+};
+constexpr AlsSolver als_solver(int als_kind, int als_cg, int implicit_cg)
+{
+	if (als_cg > 0) return {true, false, als_cg, kAlsCgMaxK};
+	const bool implicit = als_kind == kAlsImplicitKind;
+	if (implicit && implicit_cg > 0) return {true, true, implicit_cg, kAlsDirectMaxK};
+	return {false, implicit, 0, kAlsDirectMaxK};
+}
+
 }  // namespace mf_sched

@@ -3,6 +3,8 @@
 // (tests/test_als_cg.py):
 //   form K forced : the chosen form, then whether each of the three forms takes the K
 //   chunk head row_bytes : entries per chunk at 160 KiB of LDS per CU
+// and the solver rule (als_solver) on every kind x als_cg in {0, 3} x implicit_cg in {0, 3}:
+//   solver kind als_cg implicit_cg : conjugate gradient?, implicit?, steps, widest K
 #include <cstdio>
 
 #include "../recommender-system_amd/csrc/mf_schedule.h"
@@ -16,5 +18,11 @@ int main()
 	for (int head = 512; head <= 4096; head += 512)
 		for (int odd = 1; odd <= 129; odd += 2)
 			printf("chunk %d %d %d\n", head, 16 * odd, mf_sched::als_cg_chunk((size_t) head, (size_t) 16 * odd, (size_t) 160 * 1024));
+	for (int kind : {0, 1, 2, 4})   // MF_ALS_OFF, RIDGE, RIDGE_COUNT, IMPLICIT
+		for (int als_cg : {0, 3})
+			for (int implicit_cg : {0, 3}) {
+				const mf_sched::AlsSolver s = mf_sched::als_solver(kind, als_cg, implicit_cg);
+				printf("solver %d %d %d %d %d %d %d\n", kind, als_cg, implicit_cg, (int) s.cg, (int) s.implicit, s.steps, s.max_k);
+			}
 	return 0;
 }

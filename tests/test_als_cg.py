@@ -375,23 +375,26 @@ def test_cli_cg_refusals_die_with_empty_stdout(capi, env, tmp_path):
 
 @pytest.fixture(scope="module")
 def form_choices(tmp_path_factory):
-    """what tests/als_cg_form_main.cpp prints: {(K, forced): form} and {(head, row): chunk}"""
+    """what tests/als_cg_form_main.cpp prints: {(K, forced): form}, {(head, row): chunk} and {(kind, als_cg, implicit_cg): solver}"""
     exe = str(tmp_path_factory.mktemp("als_cg_form") / "als_cg_form_main")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-o", exe, os.path.join(ROOT, "tests", "als_cg_form_main.cpp")])
-    forms, chunks = {}, {}
+    forms, chunks, solvers = {}, {}, {}
     for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines():
         t = line.split()
         if t[0] == "form":
             forms[(int(t[1]), int(t[2]))] = (int(t[3]), [int(v) for v in t[4:]])
-        else:
+        elif t[0] == "chunk":
             chunks[(int(t[1]), int(t[2]))] = int(t[3])
-    return forms, chunks
+        else:
+            assert t[0] == "solver", line
+            solvers[tuple(int(v) for v in t[1:4])] = tuple(int(v) for v in t[4:])
+    return forms, chunks, solvers
 
 
 def test_form_choice(form_choices):
     """the rule against its truth table, written out here: the forced form where it takes the K, otherwise the first of fixed,
     dma, general that does; and the chunk rule on a grid of geometries, the kernel's among them"""
-    forms, chunks = form_choices
+    forms, chunks, _ = form_choices
     assert len(forms) == 258 * 6
     for (K, forced), (form, taken) in forms.items():
         assert taken == [int(takes(f, K)) for f in FORMS], K
@@ -410,6 +413,31 @@ def test_form_choice(form_choices):
         pieces = (K + 1) // 2
         assert (2 * ((16 * pieces + 255) // 256 * 256), 16 * (pieces | 1)) in chunks, K
     assert [chunk_of(K) for K in (1, 10, 30, 128, 129, 200, 255, 256)] == [16, 16, 16, 16, 16, 14, 12, 12]
+
+
+def solver_of(kind, als_cg, implicit_cg):
+    """which solve a launch runs, as (conjugate gradient?, implicit?, steps, widest K): the steps of mf_plan_set_als_cg come
+    first and make it the explicit CG solve, K to 256; those of mf_plan_set_implicit_cg count under the implicit kind alone;
+    otherwise the direct solve of the kind, K to 128"""
+    if als_cg > 0:
+        return (1, 0, als_cg, MAX_K)
+    if kind == 4 and implicit_cg > 0:
+        return (1, 1, implicit_cg, 128)
+    return (0, int(kind == 4), 0, 128)
+
+
+def test_solver_rule(form_choices, capi):
+    """mf_sched::als_solver on every kind x als_cg x implicit_cg against the restatement above, and what the 16 lines come to"""
+    solvers = form_choices[2]
+    kinds = (capi.ALS_KINDS["off"], capi.ALS_KINDS["ridge"], capi.ALS_KINDS["ridge-count"], capi.ALS_KINDS["implicit"])
+    assert kinds == (0, 1, 2, 4)
+    assert sorted(solvers) == sorted((k, a, i) for k in kinds for a in (0, 3) for i in (0, 3)) and len(solvers) == 16
+    for (kind, als_cg, implicit_cg), got in solvers.items():
+        assert got == solver_of(kind, als_cg, implicit_cg), (kind, als_cg, implicit_cg)
+    # the explicit kinds never read the implicit steps; the implicit kind without explicit steps does
+    assert all(solvers[(k, 0, 3)] == solvers[(k, 0, 0)] == (0, 0, 0, 128) for k in (0, 1, 2))
+    assert all(solvers[(k, 3, i)] == (1, 0, 3, 256) for k in kinds for i in (0, 3))
+    assert solvers[(4, 0, 0)] == (0, 1, 0, 128) and solvers[(4, 0, 3)] == (1, 1, 3, 128)
 
 
 # ------------------------------------------------------------------------------------------------ GPU

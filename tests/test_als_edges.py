@@ -6,10 +6,11 @@ bit; here is what reading the launch code against those modules shows they leave
 A  a guard on the instance tables (CPU): kAlsForm, als_cg_fn and kGramFn of mf_plan.hip.h are read as text, the rule that takes a
    (form, K) to an instance is restated in a few lines -- the blocks per thread NB from als_blocks and the thread count --, and
    the K lists the GPU tests iterate over must reach every instance, both ends of the range of K of every run-time-K instance
-   and every compile-time K of the conjugate-gradient table.  The ends of the NB ranges then run here, on the `pair` pattern
+   and every compile-time K of the conjugate-gradient table, in its explicit and in its implicit instantiation (the instances
+   of one pass, K <= 128; tests/test_implicit_cg.py launches them).  The ends of the NB ranges then run here, on the `pair` pattern
    with random factors (the planted instances of the other modules have R = 2 I or a triangular Y: zero products off the
    diagonal cannot see a wrong block-to-thread mapping);
-B  the split side: MF_SWEEP_LONG=128 on `skewed` gives both sides extreme rows, so launch_als and launch_als_cg launch twice
+B  the split side: MF_SWEEP_LONG=128 on `skewed` gives both sides extreme rows, so launch_als launches every solve twice
    into the same three counters; on `long-items` only the items split.  Dispatch order is no part of the definition: the
    expected bits are those of the models, which know no split;
 C  value classes: range, zeros and nonfinite of tests/test_sweep_edges.py, and scale classes built here -- the signed class
@@ -29,6 +30,7 @@ import pytest
 import test_als as direct_mod
 import test_als_cg as cg_mod
 import test_implicit as implicit_mod
+import test_implicit_cg as icg_mod
 from conftest import ROOT
 from test_als import KINDS, LAM, AlsModel, als_plan, hand_iteration
 from test_als import check_form as direct_check_form
@@ -72,7 +74,7 @@ def _const(text, name):
 
 def als_tables():
     """The instance tables as the launch code indexes them: {"explicit" / "implicit": {form: threads, bs, max_k, nbs},
-    "gram": threads, bs, max_k, nbs, "cg": fixed [(KT, NP)], dma [NP], general [NP]}"""
+    "gram": threads, bs, max_k, nbs, "cg" / "icg": fixed [(KT, NP)], dma [NP], general [NP]}"""
     plan, als, grm = _source("mf_plan.hip.h"), _source("mf_als.hip.h"), _source("mf_gram.hip.h")
     names = {"mf::kAlsThreads": _const(als, "kAlsThreads"), "mf::kWave": _const(_source("mf_common.hip.h"), "kWave"),
              "mf::kAlsMaxK": _const(als, "kAlsMaxK"), "mf::kAlsWaveMaxK": _const(als, "kAlsWaveMaxK")}
@@ -87,13 +89,22 @@ def als_tables():
             tables[kind][name] = dict(threads=names[threads], bs=int(bs), max_k=names[max_k], nbs=[int(nb) for _, _, nb in inst])
     nbs = [int(nb) for nb in re.findall(r"mf::gram_block_kernel<(\d+)>", re.findall(r"const GramFn kGramFn\[\d+\] = \{(.*?)\};", plan)[0])]
     tables["gram"] = dict(threads=_const(grm, "kGramThreads"), bs=_const(grm, "kGramBS"), max_k=names["mf::kAlsMaxK"], nbs=nbs)
-    fn = re.findall(r"inline AlsCgFn als_cg_fn\(int form, int K\)\n\{(.*?)\n\}", plan, re.S)
+    fn = re.findall(r"inline const void \*als_cg_fn\(int form, int K\)\n\{(.*?)\n\}", plan, re.S)
     assert len(fn) == 1
-    fixed = [(int(k), int(kt), int(np_)) for k, kt, np_ in re.findall(r"case (\d+): return mf::als_cg_kernel<(\d+), (\d+), true>;", fn[0])]
+    fixed = [(int(k), int(kt), int(np_)) for k, kt, np_ in re.findall(r"case (\d+): return als_cg_instance<(\d+), (\d+), true, IM\.\.\.>\(\);", fn[0])]
     assert fixed and all(k == kt for k, kt, _ in fixed)
-    run_time = re.findall(r"mf::als_cg_kernel<0, (\d+), (true|false)>", fn[0])
+    run_time = re.findall(r"als_cg_instance<0, (\d+), (true|false), IM\.\.\.>\(\)", fn[0])
     tables["cg"] = dict(fixed=[(kt, np_) for _, kt, np_ in fixed], dma=sorted(int(n) for n, d in run_time if d == "true"),
                         general=sorted(int(n) for n, d in run_time if d == "false"))
+    # the implicit instantiation of the same table: als_cg_instance leaves out what is not of one pass, als_cg_fn every K above
+    # kAlsMaxK
+    inst = re.findall(r"inline const void \*als_cg_instance\(\)\n\{(.*?)\n\}", plan, re.S)
+    assert len(inst) == 1 and re.match(r"\s*if constexpr \(sizeof\.\.\.\(IM\) == 0\)\s*return \(const void \*\) mf::als_cg_kernel<KT, NP, DMA>;"
+                                       r"\s*else if constexpr \(NP == 1\)\s*return \(const void \*\) mf::als_icg_kernel<KT, NP, DMA>;"
+                                       r"\s*else\s*return nullptr;$", inst[0]), inst
+    assert "(sizeof...(IM) == 1 && K > mf::kAlsMaxK)) return nullptr;" in fn[0]
+    tables["icg"] = dict(fixed=[(kt, np_) for kt, np_ in tables["cg"]["fixed"] if np_ == 1], dma=[n for n in tables["cg"]["dma"] if n == 1],
+                         general=[n for n in tables["cg"]["general"] if n == 1], max_k=names["mf::kAlsMaxK"])
     return tables
 
 
@@ -115,8 +126,8 @@ def direct_name(rec, nb, implicit):
     return "als_kernel<%d, %d, %d%s>" % (rec["threads"], rec["bs"], nb, ", AlsImplicit" if implicit else "")
 
 
-def cg_name(kt, np_, dma):
-    return "als_cg_kernel<%d, %d, %s>" % (kt, np_, "true" if dma else "false")
+def cg_name(kt, np_, dma, implicit=False):
+    return "%s<%d, %d, %s>" % ("als_icg_kernel" if implicit else "als_cg_kernel", kt, np_, "true" if dma else "false")
 
 
 def instance_of(tables, table, form, K):
@@ -127,13 +138,14 @@ def instance_of(tables, table, form, K):
     if table == "gram":
         rec = tables["gram"]
         return "gram_block_kernel<%d>" % nb_of(rec, K) if 1 <= K <= rec["max_k"] else None
-    if not 1 <= K <= cg_mod.MAX_K:
+    implicit = table == "icg"
+    if not 1 <= K <= (tables["icg"]["max_k"] if implicit else cg_mod.MAX_K):
         return None
     if form == "fixed":
-        return next((cg_name(kt, np_, True) for kt, np_ in tables["cg"]["fixed"] if kt == K), None)
+        return next((cg_name(kt, np_, True, implicit) for kt, np_ in tables[table]["fixed"] if kt == K), None)
     if form == "dma":
-        return cg_name(0, cg_passes(K), True) if K % 2 == 0 else None
-    return cg_name(0, cg_passes(K), False)
+        return cg_name(0, cg_passes(K), True, implicit) if K % 2 == 0 else None
+    return cg_name(0, cg_passes(K), False, implicit)
 
 
 def all_instances(tables, table):
@@ -141,9 +153,9 @@ def all_instances(tables, table):
         return [(f, direct_name(rec, nb, table == "implicit")) for f, rec in tables[table].items() for nb in rec["nbs"]]
     if table == "gram":
         return [(None, "gram_block_kernel<%d>" % nb) for nb in tables["gram"]["nbs"]]
-    cg = tables["cg"]
-    return ([("fixed", cg_name(kt, np_, True)) for kt, np_ in cg["fixed"]] + [("dma", cg_name(0, n, True)) for n in cg["dma"]]
-            + [("general", cg_name(0, n, False)) for n in cg["general"]])
+    cg, im = tables[table], table == "icg"
+    return ([("fixed", cg_name(kt, np_, True, im)) for kt, np_ in cg["fixed"]] + [("dma", cg_name(0, n, True, im)) for n in cg["dma"]]
+            + [("general", cg_name(0, n, False, im)) for n in cg["general"]])
 
 
 def unreached(tables, table, cases):
@@ -162,7 +174,7 @@ def unreached(tables, table, cases):
         got = reached.get((form, name), set())
         if not got:
             missing.append((name, "no K"))
-        elif "<0," in name or table != "cg":   # a run-time K: both ends of its range
+        elif "<0," in name or table not in ("cg", "icg"):   # a run-time K: both ends of its range
             ends = (min(span[(form, name)]), max(span[(form, name)]))
             missing += [(name, "K=%d" % k) for k in ends if k not in got]
     return missing
@@ -177,11 +189,12 @@ def k_lists(edges=True):
     return {"explicit": [(f, K) for K in direct_mod.ALL_K + extra for f in direct_forms(K)],
             "implicit": [(f, K) for K in implicit_k + extra for f in direct_forms(K)],
             "gram": [(None, K) for K in implicit_mod.GRAM_K + (WG_EDGE_K if edges else ())],
-            "cg": [(f, K) for K in cg_mod.ALL_K if K not in new_cg for f in cg_forms(K)]}
+            "cg": [(f, K) for K in cg_mod.ALL_K if K not in new_cg for f in cg_forms(K)],
+            "icg": [(f, K) for K in icg_mod.ALL_K for f in cg_forms(K)]}
 
 
 def gaps(tables, lists):
-    return {t: unreached(tables, t, lists[t]) for t in ("explicit", "implicit", "gram", "cg")}
+    return {t: unreached(tables, t, lists[t]) for t in ("explicit", "implicit", "gram", "cg", "icg")}
 
 
 def test_every_instance_of_the_als_tables_is_launched_at_both_ends_of_its_range():
@@ -193,6 +206,7 @@ def test_every_instance_of_the_als_tables_is_launched_at_both_ends_of_its_range(
     assert tables["gram"] == dict(threads=256, bs=4, max_k=128, nbs=[1, 2, 3])
     assert [kt for kt, _ in tables["cg"]["fixed"]] == list(cg_mod.FIXED_K) and all(np_ == cg_passes(kt) for kt, np_ in tables["cg"]["fixed"])
     assert tables["cg"]["dma"] == [1, 2] and tables["cg"]["general"] == [1, 2]
+    assert [kt for kt, _ in tables["icg"]["fixed"]] == list(icg_mod.FIXED_K) and tables["icg"]["dma"] == tables["icg"]["general"] == [1]
     wg, wave = tables["explicit"]["wg"], tables["explicit"]["wave"]
     assert [nb_of(wg, K) for K in (1, 88, 89, 124, 125, 128)] == [1, 1, 2, 2, 3, 3]
     assert [nb_of(wave, K) for K in (1, 20, 21, 30, 31, 32)] == [1, 1, 2, 2, 3, 3]
@@ -202,7 +216,7 @@ def test_every_instance_of_the_als_tables_is_launched_at_both_ends_of_its_range(
     found = gaps(tables, lists)
     for t, missing in found.items():
         print(t, missing)
-    assert found == {"explicit": [], "implicit": [], "gram": [], "cg": []}
+    assert found == {"explicit": [], "implicit": [], "gram": [], "cg": [], "icg": []}
     # ... which they did not before this module and the three K added to ALL_K of test_als_cg.py
     before = gaps(tables, k_lists(edges=False))
     for t, missing in before.items():
@@ -213,11 +227,14 @@ def test_every_instance_of_the_als_tables_is_launched_at_both_ends_of_its_range(
     assert before["implicit"] == [(n.replace(">", ", AlsImplicit>"), k) for n, k in before["explicit"]]
     assert before["gram"] == ends("gram_block_kernel<1>", [88]) + ends("gram_block_kernel<2>", [89, 124]) + ends("gram_block_kernel<3>", [125])
     assert before["cg"] == [("als_cg_kernel<20, 1, true>", "no K"), ("als_cg_kernel<50, 1, true>", "no K"), ("als_cg_kernel<0, 2, true>", "K=130")]
+    assert before["icg"] == []   # tests/test_implicit_cg.py came with its list whole
     # a grown table is reported: a ninth fixed K, a fourth NB, a third number of passes
     grown = dict(tables, cg=dict(tables["cg"], fixed=tables["cg"]["fixed"] + [(40, 1)]))
     assert unreached(grown, "cg", lists["cg"]) == [("als_cg_kernel<40, 1, true>", "no K")]
     grown = dict(tables, cg=dict(tables["cg"], general=[1, 2, 3]))
     assert unreached(grown, "cg", lists["cg"]) == [("als_cg_kernel<0, 3, false>", "no K")]
+    grown = dict(tables, icg=dict(tables["icg"], fixed=tables["icg"]["fixed"] + [(40, 1)]))
+    assert unreached(grown, "icg", lists["icg"]) == [("als_icg_kernel<40, 1, true>", "no K")]
     for t in ("explicit", "implicit"):
         grown = dict(tables, **{t: dict(tables[t], wg=dict(tables[t]["wg"], nbs=[1, 2, 3, 4]))})
         assert unreached(grown, t, lists[t]) == [(direct_name(tables[t]["wg"], 4, t == "implicit"), "no K")]

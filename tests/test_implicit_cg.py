@@ -35,8 +35,9 @@ gpu = pytest.mark.gpu
 LAM = (LAM_U, LAM_I)
 CONFS = (0.0, 1.0, 40.0)
 FIXED_K = (10, 20, 30, 50, 100, 128)
-# every compile-time K of als_icg_fn and both ends of the range of K of its run-time instances (2 .. 128 under the LDS-DMA
-# gather, 1 .. 127 through registers; 128 runs there too, forced)
+# every compile-time K of als_cg_fn<mf::AlsImplicit> and both ends of the range of K of its run-time instances (2 .. 128 under
+# the LDS-DMA gather, 1 .. 127 through registers; 128 runs there too, forced): tests/test_als_edges.py checks this list against
+# the table
 ALL_K = (1, 2, 3, 10, 16, 17, 20, 30, 50, 64, 100, 127, 128)
 ICG_SYMBOLS = ("mf_plan_set_implicit_cg", "mf_plan_get_implicit_cg", "mf_backend_run_implicit_cg")
 
@@ -754,7 +755,7 @@ def test_the_padding_of_a_row_is_never_read_or_written(device, switches, K):
 @gpu
 @pytest.mark.parametrize("K", [10, 64, 17])
 def test_split_side_launches_twice(device, switches, K):
-    """MF_SWEEP_LONG=128 on `skewed`: both sides of an even K have extreme rows, so launch_als_icg launches twice into the same
+    """MF_SWEEP_LONG=128 on `skewed`: both sides of an even K have extreme rows, so launch_als launches twice into the same
     three counters; the expected bits are the model's, which knows no split"""
     capi = device
     conf, weighted = _variant("skewed", K)
