@@ -220,8 +220,8 @@ void mf_plan_destroy(mf_plan *plan);
  * buffers) needs no host synchronisation between that work and the plan's (tests/test_stream_order.py holds every line
  * below on a stream that is busy when the library is called).
  *   - Entry points that only ENQUEUE and return: mf_plan_iterate (and mf_plan_iterate_monitored between its evaluation
- *     points), mf_plan_sweep_items, mf_plan_sweep_users, mf_plan_sweep_users_seeded, mf_plan_project, mf_plan_als_solve and
- *     mf_plan_gram without a host pointer.  What they
+ *     points), mf_plan_sweep_items, mf_plan_sweep_users, mf_plan_sweep_users_seeded, mf_plan_project, mf_plan_als_solve,
+ *     mf_plan_als_normal, mf_plan_als_solve_normal and mf_plan_gram without a host pointer.  What they
  *     write may be read by work enqueued on the stream after the call returns, or by the host after
  *     mf_plan_synchronize.  A HIP graph that mf_plan_iterate builds is captured on and replayed into this stream.
  *   - Host only, no device work: mf_plan_flip, the setters and getters of the update rule, the pointer and pitch
@@ -774,6 +774,55 @@ int mf_backend_gram_dot(const double *left, const double *right, int32_t feature
  * MF_ERR_ARGUMENT before any HIP call. */
 int mf_backend_run_implicit(const mf_problem *p, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
                             double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, double conf, int device);
+
+/* ---- ALS on user shards: the solve cut at the normal equations.  An item's Gram matrix is a sum over all users, and a shard
+ * holds a part of it.  The normal equations of a row are linear in its entries, so every shard forms its part, the caller
+ * sums the parts elementwise in FP64 (one collective over one buffer, as it sums mf_plan_items_next()), and every shard solves
+ * the sums redundantly, as it keeps its replica of R.  Sides are 0 = items and 1 = users; T = K (K + 1) / 2.
+ *
+ * The record.  A NORMAL RECORD of a row is `pitch` doubles: N[0 .. T) the packed lower triangle, G[p][q] at p (p + 1) / 2 + q;
+ * N[T .. T + K) is b; N[T + K] is the row's entry count as a double; the remaining slots up to
+ * mf_backend_als_normal_pitch(K) are +0.0 pads.  mf_backend_als_normal_pitch(features) is the smallest even number
+ * >= T + K + 1 (even, so that 16-byte stores work; 0 for features < 1; plain C++, no HIP call).  A caller may pass a larger
+ * even pitch: the doubles of a record beyond the minimum pitch are never read or written.
+ * The buffer.  Caller-owned device memory of (rows + 1) * pitch doubles, 16-byte aligned, rows = the side's row count in the
+ * plan (the items, or the plan's own users).  The plan allocates none of it.
+ *
+ * mf_plan_als_normal(plan, side, other_generation, device_normal, pitch) only enqueues.  For every row r of the side it
+ * writes record r:
+ *   - steps 1-4 of the ALS definition (explicit kinds) or of the implicit kind's steps 1-4, over the plan's OWN entries of
+ *     the row in the side's entry order; the frozen column's a'_n reads X_old as there;
+ *   - the triangle starts at 0.0 under EVERY kind: under MF_ALS_IMPLICIT S is not added here;
+ *   - a row without local entries gets +0.0 in every slot; the count slot is (double) cnt;
+ *   - record `rows` is the GRAM RECORD: under MF_ALS_IMPLICIT its triangle slots hold the bits of
+ *     mf_plan_gram(plan, side ^ 1, other_generation), the Gram of the plan's own block of the other side (enqueued by this
+ *     call, copied on the device), its other slots +0.0; under the explicit kinds the whole record is +0.0.
+ * After the call every double of the buffer up to the minimum pitch of each record is defined: the caller needs no memset.
+ * The caller's sum.  The caller sums the buffers of the plans that partition the OTHER side, elementwise in FP64, in an order
+ * that is its business, exactly as for mf_plan_items_next(), and writes the sum where each plan will read it.
+ *
+ * mf_plan_als_solve_normal(plan, side, device_normal, pitch) only enqueues.  For every row r:  cntd = N[r][T + K];
+ * G[p][q] = N[r][tri] under the explicit kinds and  G[p][q] = N[rows][tri] + N[r][tri]  under MF_ALS_IMPLICIT (one rounded
+ * add, S on the left);  b[p] = N[r][T + p].  Then steps 5-10 of the ALS definition unchanged: ridge = lambda_side or
+ * lambda_side * cntd (MF_ALS_RIDGE_COUNT), the frozen cut with xf = X_old[r][f], Cholesky, the two solves, the box, the
+ * frozen select, into the side's next buffer.  Under the explicit kinds a row with !(cntd > 0.0) keeps X_old's bits and
+ * counts as kept_empty; under MF_ALS_IMPLICIT every row is solved.  mf_plan_als_info(side) then reports this solve.
+ *
+ * What follows from the definition:
+ *   - on a plan that holds all users, under the explicit kinds, als_normal then als_solve_normal gives the bits and the
+ *     counters of mf_plan_als_solve: the chain from 0.0 is the same chain;
+ *   - under MF_ALS_IMPLICIT it does not:  S + (0.0 + t1 + ...)  is not  ((S + t1) + ...).  It is defined by the steps above;
+ *   - on shards, a row that only one shard has entries for gets the single plan's bits under the explicit kinds:
+ *     x + (+0.0) keeps x, and a chain from +0.0 never ends at -0.0.
+ *
+ * Refusals, all before any HIP call and with nothing changed: an unknown side or generation, a NULL or misaligned buffer, an
+ * odd pitch or one below mf_backend_als_normal_pitch(K) -> MF_ERR_ARGUMENT; no factors or the kind MF_ALS_OFF ->
+ * MF_ERR_STATE; conjugate-gradient steps set for the plan's kind (they need a sum per step), K > 128, or a frozen column on
+ * the solved side under MF_ALS_IMPLICIT -> MF_ERR_UNSUPPORTED.  mf_plan_als_solve(items) and mf_plan_iterate stay refused on
+ * a shard.  Both forms (MF_ALS_FORM) give the same bits; the solve needs T + 3 K doubles of LDS per row. */
+int64_t mf_backend_als_normal_pitch(int32_t features);
+int mf_plan_als_normal(mf_plan *plan, int side, int other_generation, void *device_normal, int64_t pitch);
+int mf_plan_als_solve_normal(mf_plan *plan, int side, const void *device_normal, int64_t pitch);
 
 /* ---- ALS by conjugate gradient: a fixed, small number of conjugate-gradient (CG) steps per row, warm-started from the row's
  * current value, in place of the direct solve above (Takacs, Pilaszy, Tikk, RecSys 2011).  The Gram matrix of a row is never

@@ -59,6 +59,7 @@ HIP_SYMBOLS = [
     "mf_backend_run_implicit",
     "mf_plan_set_als_cg", "mf_plan_get_als_cg", "mf_backend_run_als_cg",
     "mf_plan_set_implicit_cg", "mf_plan_get_implicit_cg", "mf_backend_run_implicit_cg",
+    "mf_backend_als_normal_pitch", "mf_plan_als_normal", "mf_plan_als_solve_normal",
 ]
 HOST_SYMBOLS = [
     "mf_host_parse_strerror", "mf_host_parse_file", "mf_host_parse_buffer", "mf_host_free_problem",
@@ -280,6 +281,10 @@ def hip():
         lib.mf_plan_get_als_cg.argtypes = [P, C.POINTER(C.c_int)]
         lib.mf_backend_run_als_cg.argtypes = [C.POINTER(Problem), P, P, P, P, C.c_double, C.c_double, C.POINTER(Bounds), C.POINTER(Bounds),
                                               C.c_int, C.c_int, C.c_int]
+        lib.mf_backend_als_normal_pitch.argtypes = [C.c_int32]
+        lib.mf_backend_als_normal_pitch.restype = C.c_int64
+        lib.mf_plan_als_normal.argtypes = [P, C.c_int, C.c_int, P, C.c_int64]
+        lib.mf_plan_als_solve_normal.argtypes = [P, C.c_int, P, C.c_int64]
         lib.mf_plan_set_implicit_cg.argtypes = [P, C.c_int]
         lib.mf_plan_get_implicit_cg.argtypes = [P, C.POINTER(C.c_int)]
         lib.mf_backend_run_implicit_cg.argtypes = [C.POINTER(Problem), P, P, P, P, C.c_double, C.c_double, C.POINTER(Bounds),
@@ -660,6 +665,11 @@ def backend_run_implicit_cg(inst, L, R, steps, conf=1.0, bounds_users=None, boun
 
 
 run_implicit_cg = backend_run_implicit_cg
+
+
+def als_normal_pitch(feats):
+    """mf_backend_als_normal_pitch: doubles of one normal record, the smallest even number >= K (K + 1) / 2 + K + 1"""
+    return int(hip().mf_backend_als_normal_pitch(int(feats)))
 
 
 def gram_dot(left, right):
@@ -1057,6 +1067,17 @@ class Plan:
         """mf_plan_als_solve: every row of `side` solved against the other side's "current" or "next" buffer, into the side's
         next buffer; only enqueues"""
         _check(hip().mf_plan_als_solve(self._h, SIDES.get(side, side), GENERATIONS.get(other, other)), "mf_plan_als_solve")
+
+    def als_normal(self, side, other, ptr, pitch):
+        """mf_plan_als_normal: the normal records of every row of `side` over the plan's own entries, against the other side's
+        "current" or "next" buffer, and the Gram record behind them, into the device buffer at `ptr` ((rows + 1) x pitch
+        doubles); only enqueues"""
+        _check(hip().mf_plan_als_normal(self._h, SIDES.get(side, side), GENERATIONS.get(other, other), ptr, int(pitch)), "mf_plan_als_normal")
+
+    def als_solve_normal(self, side, ptr, pitch):
+        """mf_plan_als_solve_normal: every row of `side` solved from the (summed) normal records at `ptr` into the side's next
+        buffer; only enqueues"""
+        _check(hip().mf_plan_als_solve_normal(self._h, SIDES.get(side, side), ptr, int(pitch)), "mf_plan_als_solve_normal")
 
     def als_info(self, side):
         """mf_plan_als_info: (solved, kept_empty, kept_not_pd) rows of the side's last solve"""

@@ -89,6 +89,208 @@ struct AlsImplicit {
 __device__ __forceinline__ AlsImplicit als_implicit_of() { return AlsImplicit{nullptr, 0.0}; }
 __device__ __forceinline__ AlsImplicit als_implicit_of(AlsImplicit im) { return im; }
 
+// ---- the phases as functions: als_normal_kernel and als_solve_normal_kernel (mf_als_normal.hip.h) run the two halves of the
+// solve with a record in global memory in between.  They restate the body of als_kernel below statement for statement;
+// als_kernel keeps its own text because calling these functions from it changed the instruction lists of all its twelve
+// instances (integer address arithmetic; profiles/als_shards/kernels_parent_vs_new.txt).  A change of a phase goes into both.
+
+// the LDS slab of one group: als_group_doubles doubles from `base`
+struct AlsSlab {
+	double *ytile, *ywtile, *ap, *wl;
+	int *ids;
+	double *G, *dg, *zs, *xs;
+};
+__device__ __forceinline__ AlsSlab als_slab(double *base, int Kp, int NCH, int K, bool weighted)
+{
+	AlsSlab s;
+	s.ytile = base;
+	s.ywtile = weighted ? s.ytile + NCH * Kp : s.ytile;
+	s.ap = s.ywtile + NCH * Kp;
+	s.wl = s.ap + NCH;
+	s.ids = (int *) (s.wl + NCH);
+	s.G = s.wl + NCH + (NCH + 1) / 2;
+	s.dg = s.G + als_triangle(K);
+	s.zs = s.dg + K;
+	s.xs = s.zs + K;
+	return s;
+}
+
+// the blocks of a thread: block e = tid + i * THREADS of the triangle of blocks, rows bp >= columns bq
+template <int THREADS, int BS, int NB>
+__device__ __forceinline__ void als_own_blocks(int tid, int nblocks, int (&bp)[NB], int (&bq)[NB])
+{
+#pragma unroll
+	for (int i = 0; i < NB; ++i) {
+		const int e = tid + i * THREADS;
+		int p = (int) ((sqrtf(8.0f * (float) e + 1.0f) - 1.0f) * 0.5f);
+		while (p * (p + 1) / 2 > e) --p;
+		while ((p + 1) * (p + 2) / 2 <= e) ++p;
+		bp[i] = e < nblocks ? p * BS : 0;
+		bq[i] = e < nblocks ? (e - p * (p + 1) / 2) * BS : 0;
+	}
+}
+
+// phases 1 and 2 over the row's entries beg .. beg + cnt: every acc[i][u][v] and bacc is one serial chain in entry order
+template <int THREADS, int BS, int NB, bool IMPLICIT>
+__device__ __forceinline__ void als_accumulate(const AlsArgs &a, double conf, int K, int Kp, int tid, int beg, int cnt, int f, double xf,
+                                               bool weighted, int nblocks, double *ytile, double *ywtile, double *ap, double *wl, int *ids,
+                                               const int (&bp)[NB], const int (&bq)[NB], double (&acc)[NB][BS][BS], double &bacc)
+{
+	constexpr int NCH = THREADS == kAlsThreads ? kAlsChunkWg : kAlsChunkWave;
+	for (int c0 = 0; c0 < cnt; c0 += NCH) {
+		const int cc = min(NCH, cnt - c0);
+		// phase 1a: idx, a' and w of the chunk's entries
+		if (tid < cc) {
+			const int e = beg + c0 + tid, id = a.idx[e];
+			double av = a.val[e];
+			if (f >= 0) {
+				const double t = xf * a.Y[(size_t) id * a.ldy + f];
+				av = av - t;
+			}
+			ids[tid] = id;
+			if constexpr (IMPLICIT) {   // e_n, and ac_n = a_n * c_n with c_n = 1.0 + e_n
+				const double en = a.wgt ? conf * a.wgt[e] : conf;
+				const double cn = 1.0 + en;
+				ap[tid] = av * cn;
+				wl[tid] = en;
+			} else {
+				ap[tid] = av;
+				wl[tid] = weighted ? a.wgt[e] : 1.0;
+			}
+		}
+		als_sync<THREADS>();
+		// phase 1b: the Y rows of the chunk, zero beyond column K
+		{
+			int n = tid / Kp, k = tid - n * Kp;
+			const int dn = THREADS / Kp, dk = THREADS - dn * Kp;
+			while (n < cc) {
+				const double y = k < K ? a.Y[(size_t) ids[n] * a.ldy + k] : 0.0;
+				ytile[n * Kp + k] = y;
+				if (weighted) ywtile[n * Kp + k] = y * wl[n];
+				n += dn, k += dk;
+				if (k >= Kp) k -= Kp, ++n;
+			}
+		}
+		als_sync<THREADS>();
+		// phase 2: G[p][q] = G[p][q] + (y_n[p] * yw_n[q]) and b[p] = b[p] + (a'_n * yw_n[p]), n ascending
+		for (int n = 0; n < cc; ++n) {
+			const double *yr = ytile + n * Kp, *ywr = ywtile + n * Kp;
+#pragma unroll
+			for (int i = 0; i < NB; ++i) {
+				if (tid + i * THREADS < nblocks) {
+					double yp[BS], yq[BS];
+#pragma unroll
+					for (int u = 0; u < BS; ++u) yp[u] = yr[bp[i] + u], yq[u] = ywr[bq[i] + u];
+#pragma unroll
+					for (int u = 0; u < BS; ++u)
+#pragma unroll
+						for (int v = 0; v < BS; ++v) {
+							const double t = yp[u] * yq[v];
+							acc[i][u][v] = acc[i][u][v] + t;
+						}
+				}
+			}
+			if (tid < K) {
+				const double t = ap[n] * (IMPLICIT ? yr[tid] : ywr[tid]);
+				bacc = bacc + t;
+			}
+		}
+		als_sync<THREADS>();
+	}
+}
+
+// phase 3, first half: the register blocks into the packed triangle in LDS
+template <int THREADS, int BS, int NB>
+__device__ __forceinline__ void als_blocks_to_lds(int K, int tid, int nblocks, const int (&bp)[NB], const int (&bq)[NB],
+                                                  const double (&acc)[NB][BS][BS], double *G)
+{
+#pragma unroll
+	for (int i = 0; i < NB; ++i) {
+		if (tid + i * THREADS < nblocks) {
+#pragma unroll
+			for (int u = 0; u < BS; ++u)
+#pragma unroll
+				for (int v = 0; v < BS; ++v) {
+					const int p = bp[i] + u, q = bq[i] + v;
+					if (p < K && q <= p) G[als_tri(p, q)] = acc[i][u][v];
+				}
+		}
+	}
+}
+
+// phase 3, second half, to phase 6: the triangle is in G and the group has synchronised; thread p < K holds b[p] in bacc.
+// The ridge (cntd: the row's entry count as a double), the frozen cut, Cholesky, the two solves, the box, the frozen select, the store and the row's counter.
+template <int THREADS>
+__device__ __forceinline__ void als_ridge_solve_store(const AlsArgs &a, int K, int tid, int f, double xf, double xold, size_t xrow, double cntd,
+                                                      double bacc, double *G, double *dg, double *zs, double *xs)
+{
+	constexpr int TD = THREADS == kAlsThreads ? 16 : 8;   // the trailing update walks the triangle as TD x TD threads
+	if (tid < K) {
+		const double ridge = a.count_scaled ? a.lambda * cntd : a.lambda;
+		G[als_tri(tid, tid)] = G[als_tri(tid, tid)] + ridge;
+		if (f >= 0) {
+			if (tid < f) G[als_tri(f, tid)] = 0.0;
+			if (tid > f) G[als_tri(tid, f)] = 0.0;
+			if (tid == f) G[als_tri(f, f)] = 1.0, bacc = xf;
+		}
+	}
+	als_sync<THREADS>();
+
+	// phase 4: Cholesky, right-looking.  Every thread of the group reads the same pivot, so the exit is uniform
+	bool pd = true;
+	const int ti = tid / TD, tq = tid % TD;
+	for (int j = 0; j < K; ++j) {
+		const double s = G[als_tri(j, j)];
+		if (!(s > 0.0)) {
+			pd = false;
+			break;
+		}
+		const double d = sqrt(s);
+		if (tid == 0) dg[j] = d;
+		for (int i = j + 1 + tid; i < K; i += THREADS) G[als_tri(i, j)] = G[als_tri(i, j)] / d;
+		als_sync<THREADS>();
+		for (int i = j + 1 + ti; i < K; i += TD) {
+			const double cij = G[als_tri(i, j)];
+			for (int q = j + 1 + tq; q <= i; q += TD) {
+				const double t = cij * G[als_tri(q, j)];
+				G[als_tri(i, q)] = G[als_tri(i, q)] - t;
+			}
+		}
+		als_sync<THREADS>();
+	}
+
+	double x = xold;
+	if (pd) {
+		// phase 5: C z = b, j ascending; C^T x = z, j descending
+		double bi = bacc;
+		for (int j = 0; j < K; ++j) {
+			if (tid == j) zs[j] = bi / dg[j];
+			als_sync<THREADS>();
+			if (tid > j && tid < K) {
+				const double t = G[als_tri(tid, j)] * zs[j];
+				bi = bi - t;
+			}
+		}
+		double zi = tid < K ? zs[tid] : 0.0;   // its own store
+		for (int j = K - 1; j >= 0; --j) {
+			if (tid == j) xs[j] = zi / dg[j];
+			als_sync<THREADS>();
+			if (tid < j) {
+				const double t = G[als_tri(j, tid)] * xs[j];
+				zi = zi - t;
+			}
+		}
+		// phase 6: the box on the bounded columns, then the frozen select
+		if (tid < K) {
+			x = xs[tid];
+			if (tid < a.box.columns) x = box_clamp(x, a.box.lo, a.box.hi);
+			if (tid == f) x = xold;
+		}
+	}
+	if (tid < K) a.X_new[xrow + tid] = x;
+	if (tid == 0) atomicAdd(&a.counts[pd ? 0 : 2], 1ull);
+}
+
 // als_kernel<THREADS, BS, NB>(AlsArgs) is the explicit solve; als_kernel<THREADS, BS, NB, AlsImplicit>(AlsArgs, AlsImplicit) the
 // implicit one: the same body with steps 1-5 changed as the header states them -- e_n = conf * w_n (conf without weights) is
 // what the second tile is scaled by, a_n goes in as a_n * (1.0 + e_n), the triangle starts at S where it otherwise starts at

@@ -677,6 +677,39 @@ int mf_plan_als_solve(mf_plan *p, int side, int other_generation)
 	return launch_als(p, side, other_generation);
 }
 
+int64_t mf_backend_als_normal_pitch(int32_t features)
+{
+	if (features < 1) return 0;
+	const int64_t K = features;
+	return (K * (K + 1) / 2 + K + 1 + 1) / 2 * 2;   // mf::als_normal_pitch in 64 bits, for any K
+}
+
+// what both halves of the cut solve refuse, before any HIP call
+static int als_normal_check(const mf_plan *p, int side, int other_generation, const void *device_normal, int64_t pitch)
+{
+	if (!p || (side != 0 && side != 1) || (other_generation != 0 && other_generation != 1)) return MF_ERR_ARGUMENT;
+	if (!device_normal || ((uintptr_t) device_normal & 15) != 0 || (pitch & 1) != 0) return MF_ERR_ARGUMENT;
+	if (p->K <= mf::kAlsMaxK && pitch < mf::als_normal_pitch(p->K)) return MF_ERR_ARGUMENT;
+	if (!p->have_factors || p->als_kind == MF_ALS_OFF) return MF_ERR_STATE;
+	if (als_solver(p).cg || p->K > mf::kAlsMaxK) return MF_ERR_UNSUPPORTED;   // CG on shards needs a sum per step
+	if (implicit_refuses(p, side)) return MF_ERR_UNSUPPORTED;
+	return MF_OK;
+}
+
+int mf_plan_als_normal(mf_plan *p, int side, int other_generation, void *device_normal, int64_t pitch)
+{
+	MF_TRY(als_normal_check(p, side, other_generation, device_normal, pitch));
+	MF_HIP(hipSetDevice(p->device));
+	return launch_als_normal(p, side, other_generation, (double *) device_normal, (long long) pitch, false);
+}
+
+int mf_plan_als_solve_normal(mf_plan *p, int side, const void *device_normal, int64_t pitch)
+{
+	MF_TRY(als_normal_check(p, side, 0, device_normal, pitch));
+	MF_HIP(hipSetDevice(p->device));
+	return launch_als_normal(p, side, 0, (double *) const_cast<void *>(device_normal), (long long) pitch, true);
+}
+
 int mf_plan_set_confidence(mf_plan *p, double conf)
 {
 	if (!p || !std::isfinite(conf) || conf < 0.0) return MF_ERR_ARGUMENT;

@@ -741,6 +741,56 @@ int launch_als(mf_plan *p, int side, int other_generation)
 	});
 }
 
+// The solve cut at the normal equations (mf_als_normal.hip.h), the only function that launches either half.  solve == false:
+// the side's normal records over the plan's own entries against the other side in `other_generation`, and record `rows` --
+// under the implicit kind launch_gram of that side and generation first, copied on the device; +0.0 otherwise.
+// solve == true: every row solved from the records into the side's next buffer, the counters zeroed first.  The forms, the
+// row lists and the arguments are launch_als's; the caller has checked the buffer, the pitch and the refusals.
+int launch_als_normal(mf_plan *p, int side, int other_generation, double *N, long long pitch, bool solve)
+{
+	const SweepSide &sd = p->side[side];
+	const mf_sched::AlsSolver s = als_solver(p);
+	const int np = mf::als_normal_pitch(p->K);
+	unsigned long long *counts = p->als_counts.get() + 3 * side;
+	mf::AlsNormal nr{N, pitch, sd.nrows, s.implicit ? 1 : 0};
+	mf::AlsImplicit im{nullptr, p->confidence};
+	if (solve) {
+		MF_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(unsigned long long), p->stream));
+	} else {
+		const double *S = nullptr;
+		if (s.implicit) {
+			MF_TRY(launch_gram(p, side ^ 1, other_generation));
+			S = p->gram.get() + (size_t) (side ^ 1) * mf::als_triangle(p->K);
+		}
+		hipLaunchKernelGGL(mf::als_normal_gram_kernel, dim3((np + mf::kAlsThreads - 1) / mf::kAlsThreads), dim3(mf::kAlsThreads), 0, p->stream, S,
+		                   mf::als_triangle(p->K), np, N + (size_t) sd.nrows * (size_t) pitch);
+		MF_HIP(hipGetLastError());
+	}
+	if (sd.nrows <= 0) return MF_OK;
+	mf::AlsArgs a = als_args(p, side, other_generation, counts);
+
+	const AlsNormalForm &form = kAlsNormalForm[als_form(p->K, p->cfg.als_form)];
+	const int nb = (mf::als_blocks(p->K, form.bs) + form.threads - 1) / form.threads;
+	const int rows_per_wg = mf::kAlsThreads / form.threads;
+	const void *fn = nullptr;
+	if (p->K <= form.max_k && nb >= 1 && nb <= 3)
+		fn = solve ? (const void *) form.solve : s.implicit ? (const void *) form.implicit[nb - 1] : (const void *) form.fn[nb - 1];
+	if (!fn) return MF_ERR_UNSUPPORTED;   // a missing instance is an error, never another kernel
+	const size_t lds = (size_t) rows_per_wg * sizeof(double) *
+	                   (solve ? mf::als_solve_normal_doubles(p->K) : mf::als_group_doubles(p->K, form.bs, form.nch, s.implicit || p->weighted));
+	MF_HIP(raise_lds_limit(fn, lds));
+	void *args[3] = {&a, &nr};
+	int nargs = 2;
+	if (!solve && s.implicit) args[nargs++] = &im;
+
+	return walk_row_lists(sd, [&](const int *rowlist, int nrows) {
+		a.rowlist = rowlist;
+		a.nrows = nrows;
+		MF_HIP(hipLaunchKernel(fn, dim3((nrows + rows_per_wg - 1) / rows_per_wg), dim3(mf::kAlsThreads), args, lds, p->stream));
+		return MF_OK;
+	});
+}
+
 // ---- the loops of mf_plan_iterate, one per mf_sched::Loop (iterate_path, mf_schedule.h, picks; mf_plan_iterate dispatches)
 
 // what the rule reads of a plan and a call

@@ -268,6 +268,27 @@ const AlsForm kAlsForm[kAlsForms] = {
      {mf::als_kernel<mf::kWave, 2, 1>, mf::als_kernel<mf::kWave, 2, 2>, mf::als_kernel<mf::kWave, 2, 3>},
      {mf::als_kernel<mf::kWave, 2, 1, mf::AlsImplicit>, mf::als_kernel<mf::kWave, 2, 2, mf::AlsImplicit>, mf::als_kernel<mf::kWave, 2, 3, mf::AlsImplicit>}},
 };
+// The same forms of the solve cut at the normal equations (mf_als_normal.hip.h), in the order of AlsFormId: the instances
+// that write a side's normal records by blocks per thread, explicit and implicit, and the one that solves from them.
+using AlsNormalFn = void (*)(mf::AlsArgs, mf::AlsNormal);
+using AlsNormalImplicitFn = void (*)(mf::AlsArgs, mf::AlsNormal, mf::AlsImplicit);
+struct AlsNormalForm {
+	const char *name;
+	int threads, bs, nch, max_k;
+	AlsNormalFn fn[3];
+	AlsNormalImplicitFn implicit[3];
+	AlsNormalFn solve;
+};
+const AlsNormalForm kAlsNormalForm[kAlsForms] = {
+    {"wg", mf::kAlsThreads, 4, mf::kAlsChunkWg, mf::kAlsMaxK,
+     {mf::als_normal_kernel<mf::kAlsThreads, 4, 1>, mf::als_normal_kernel<mf::kAlsThreads, 4, 2>, mf::als_normal_kernel<mf::kAlsThreads, 4, 3>},
+     {mf::als_normal_kernel<mf::kAlsThreads, 4, 1, mf::AlsImplicit>, mf::als_normal_kernel<mf::kAlsThreads, 4, 2, mf::AlsImplicit>, mf::als_normal_kernel<mf::kAlsThreads, 4, 3, mf::AlsImplicit>},
+     mf::als_solve_normal_kernel<mf::kAlsThreads>},
+    {"wave", mf::kWave, 2, mf::kAlsChunkWave, mf::kAlsWaveMaxK,
+     {mf::als_normal_kernel<mf::kWave, 2, 1>, mf::als_normal_kernel<mf::kWave, 2, 2>, mf::als_normal_kernel<mf::kWave, 2, 3>},
+     {mf::als_normal_kernel<mf::kWave, 2, 1, mf::AlsImplicit>, mf::als_normal_kernel<mf::kWave, 2, 2, mf::AlsImplicit>, mf::als_normal_kernel<mf::kWave, 2, 3, mf::AlsImplicit>},
+     mf::als_solve_normal_kernel<mf::kWave>},
+};
 // The forms of the conjugate-gradient solve in the order of mf_sched::AlsCgFormId; als_cg_form (mf_launch.hip.h) picks one,
 // als_cg_fn<>(form, K) its explicit instance (als_cg_kernel, mf_als_cg.hip.h), als_cg_fn<mf::AlsImplicit>(form, K) its
 // implicit one (als_icg_kernel, mf_als_icg.hip.h): null where the form does not take the K, and for the implicit kind above

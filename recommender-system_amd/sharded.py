@@ -109,6 +109,58 @@ class ShardedFactorization:
         return out
 
 
+class AlsShardedFactorization:
+    """ALS iterations of one user shard (explicit kinds and MF_ALS_IMPLICIT, direct solves): the users are solved locally,
+    the items from normal records summed over the ranks.  Per iteration
+        user solve  : L_next from R_cur                          (rows of L are private)
+        als_normal  : this shard's part of every item's normal equations against L_next, and its Gram record
+        all-reduce  : `normal` <- SUM over ranks, one FP64 buffer  (the implicit kind's Gram of L rides in it)
+        solve       : every rank solves the summed systems into its R replica
+        flip
+    `normal` is one torch tensor of (items + 1, pitch) float64 on the plan's device, pitch even and at least
+    capi.als_normal_pitch(K).  Conjugate-gradient steps are refused by the library: they need a sum per step."""
+
+    def __init__(self, plan, normal, rank, world, group=None, stream=None):
+        """`stream`: as for ShardedFactorization, a NON-default torch.cuda.Stream for GPU runs, on which the plan's launches
+        and the collective are ordered; None only for CPU stand-in plans (tests)."""
+        if normal.dim() != 2 or normal.dtype != torch.float64 or not normal.is_contiguous():
+            raise ValueError("normal must be a contiguous (items + 1, pitch) float64 tensor")
+        if normal.shape[0] != plan.items + 1 or normal.shape[1] % 2:
+            raise ValueError("normal must have items + 1 rows and an even pitch")
+        self.plan, self.normal, self.rank, self.world, self.group = plan, normal, rank, world, group
+        self.pitch = int(normal.shape[1])
+        self.stream = stream
+        if stream is not None:
+            if int(stream.cuda_stream) == 0:
+                raise ValueError("AlsShardedFactorization needs a non-default CUDA stream")
+            plan.set_stream(int(stream.cuda_stream))
+        elif normal.is_cuda:
+            raise ValueError("GPU buffers need an explicit stream")
+
+    def step(self):
+        if self.stream is not None:
+            with torch.cuda.stream(self.stream):
+                self._step()
+        else:
+            self._step()
+
+    def _step(self):
+        p = self.plan
+        if self.world == 1:
+            p.iterate(1)      # the library's own iteration: user solve, item solve, flip
+            return
+        ptr = int(self.normal.data_ptr())
+        p.als_solve("users", "current")
+        p.als_normal("items", "next", ptr, self.pitch)
+        dist.all_reduce(self.normal, op=dist.ReduceOp.SUM, group=self.group)
+        p.als_solve_normal("items", ptr, self.pitch)
+        p.flip()
+
+    def run(self, iters):
+        for _ in range(iters):
+            self.step()
+
+
 # ------------------------------------------------------------------------------------------------------------
 # 2-D process grid (SURVEY 8f.2): the full decomposition of matFact-mpi.c:155-214.  Rank (gr, gc) of a
 # rows x cols grid (create_balanced_grid, mpiutil.c:54-88 -> capi.balanced_grid; rank = gr*cols + gc, the
