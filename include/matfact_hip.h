@@ -824,6 +824,67 @@ int64_t mf_backend_als_normal_pitch(int32_t features);
 int mf_plan_als_normal(mf_plan *plan, int side, int other_generation, void *device_normal, int64_t pitch);
 int mf_plan_als_solve_normal(mf_plan *plan, int side, const void *device_normal, int64_t pitch);
 
+/* ---- Box-constrained ALS: with a box on a side (mf_plan_set_bounds; lo = 0, hi = inf is non-negative factorisation) the
+ * direct solve above is the unconstrained minimiser, clamped (step 10).  That is not the minimiser of the row's constrained
+ * ridge problem.  With box sweeps set, a row is instead solved by cyclic coordinate descent on its normal equations G x = b,
+ * every coordinate step exact within the box (Hsieh and Dhillon, KDD 2011; the `cd` solver of NMF; HALS).
+ *
+ * mf_plan_set_als_box(plan, sweeps) / mf_plan_get_als_box(plan, &sweeps), 0 <= sweeps <= MF_ALS_BOX_MAX_SWEEPS = 256.
+ * sweeps = 0, the default, is the library without this section, bit for bit and kernel for kernel.  The setting is read at
+ * every launch.  With sweeps > 0 the direct row solve (mf_plan_als_solve, and so mf_plan_iterate*) does steps 1-6 of the ALS
+ * definition unchanged under the plan's kind (MF_ALS_RIDGE, MF_ALS_RIDGE_COUNT), likewise steps 1-5 of MF_ALS_IMPLICIT (its
+ * Gram enqueued first, as there); steps 7-10 are replaced by B0-B4.
+ * Notation: Gs[p][t] is the symmetric read of the packed lower triangle, G[max(p,t)][min(p,t)];  f the side's frozen column or
+ * none;  xf = X_old[r][f];  (lo, hi, columns) the side's box, columns = 0 meaning that no column is bounded (a side whose
+ * bounds are both infinite).  Every operation is rounded once and nothing is fused; / is correctly rounded.  box_clamp is the
+ * projection of mf_plan_set_bounds, two compares and two selects: a NaN stays the NaN it is, -0.0 stays under lo = 0, a value
+ * equal to a bound keeps its bits.
+ *   B0. Diagonal test.  For j ascending: if !(G[j][j] > 0.0) the row is NOT POSITIVE DEFINITE (a NaN fails too): it keeps
+ *       X_old's bits, is not projected and is counted kept_not_pd.  This is WEAKER than Cholesky's test on purpose: a singular G
+ *       with a positive diagonal is a well-defined coordinate-descent problem, is solved, and is counted as solved.
+ *   B1. Start.  x[p] = X_old[r][p];  for p < columns  x[p] = box_clamp(x[p], lo, hi);  x[f] = xf (the frozen column is not
+ *       clamped).
+ *   B2. Residual.  res[p] = b[p];  then for t = 0 .. K-1 ascending  res[p] = res[p] - (Gs[p][t] * x[t]).  All t, f included:
+ *       step 6 has zeroed column f and put 1.0 on its diagonal, nothing is special-cased.
+ *   B3. Sweeps.  For s = 1 .. sweeps, for j = 0 .. K-1 ascending, j != f:
+ *         d = res[j] / G[j][j];  y = x[j] + d;  if j < columns  y = box_clamp(y, lo, hi);  dl = y - x[j];  x[j] = y;
+ *         for every p in 0 .. K-1, j included:  res[p] = res[p] - (Gs[p][j] * dl).
+ *       The update is applied when dl is +-0.0 too (-0.0 - (-0.0) is +0.0: skipping it would change bits).
+ *   B4. Store.  X_new[r][p] = x[p]; column f gets X_old's bits.  The padding of a row is never touched.
+ * The sweep count is fixed, there is no convergence test: the bits are defined.
+ * Rows without entries: under the explicit kinds they keep X_old's bits and count as kept_empty, as in the direct solve.  Under
+ * MF_ALS_IMPLICIT they are solved like any other row: they move towards the minimiser +0.0 but do not reach it in a fixed
+ * number of sweeps -- this DIFFERS from the direct implicit solve, which yields +0.0 (then the box) for a cold row.
+ * With sweeps > 0 mf_plan_als_solve_normal runs its steps 5-6 and then B0-B4 on the summed record; mf_plan_als_normal is
+ * untouched.
+ *
+ * What follows from the definition:
+ *   - on a plan that holds all users, under the explicit kinds, als_normal then als_solve_normal gives the bits and the
+ *     counters of mf_plan_als_solve, as without box sweeps;
+ *   - with lo = hi = c on all columns every solved row is c in every bounded column;
+ *   - both forms (MF_ALS_FORM=wg|wave) give the same bits, and neither needs more LDS than the direct solve: x and res live in
+ *     the 3 K doubles that held the diagonal of C, z and x.
+ *
+ * Refusals, all before any HIP call and with nothing changed: sweeps < 0 or > MF_ALS_BOX_MAX_SWEEPS -> MF_ERR_ARGUMENT.
+ * Conjugate-gradient steps in force (mf_plan_set_als_cg > 0, or mf_plan_set_implicit_cg > 0 under MF_ALS_IMPLICIT) together with
+ * box sweeps -> MF_ERR_UNSUPPORTED: whichever of mf_plan_set_als_box / mf_plan_set_als_cg / mf_plan_set_implicit_cg /
+ * mf_plan_set_als comes second returns it, the way momentum and ALS refuse each other (implicit steps set under another kind
+ * are not in force: it is then mf_plan_set_als(MF_ALS_IMPLICIT) that is refused).  K > 128 with a kind set ->
+ * MF_ERR_UNSUPPORTED.  A frozen column under MF_ALS_IMPLICIT stays refused at launch; momentum and adaptive sides stay refused
+ * under ALS; the item solve on a shard stays MF_ERR_UNSUPPORTED.
+ * mf_plan_describe appends  als_box=<sweeps>  behind als_form=... while a kind is set and sweeps > 0.
+ * Not part of this: coordinate descent without forming G (K > 128), box sweeps combined with CG, a convergence-based stop, a
+ * frozen column under the implicit kind. */
+#define MF_ALS_BOX_MAX_SWEEPS 256
+int mf_plan_set_als_box(mf_plan *plan, int sweeps);
+int mf_plan_get_als_box(mf_plan *plan, int *sweeps);
+/* level 1: pr->iters ALS iterations of `kind` (MF_ALS_RIDGE, MF_ALS_RIDGE_COUNT or MF_ALS_IMPLICIT) with `sweeps` box sweeps per
+ * row (0: the direct solve); conf is read under MF_ALS_IMPLICIT only.  A bad kind, record, lambda, sweep count or (under the
+ * implicit kind) conf, or NULL L / R -> MF_ERR_ARGUMENT before any HIP call. */
+int mf_backend_run_als_box(const mf_problem *p, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
+                           double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, int kind, double conf,
+                           int sweeps, int device);
+
 /* ---- ALS by conjugate gradient: a fixed, small number of conjugate-gradient (CG) steps per row, warm-started from the row's
  * current value, in place of the direct solve above (Takacs, Pilaszy, Tikk, RecSys 2011).  The Gram matrix of a row is never
  * formed -- its product with a vector p is  sum_n w_n y_n (y_n . p) + ridge p  -- so K goes up to MF_ALS_CG_MAX_K = 256.

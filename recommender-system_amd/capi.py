@@ -60,6 +60,7 @@ HIP_SYMBOLS = [
     "mf_plan_set_als_cg", "mf_plan_get_als_cg", "mf_backend_run_als_cg",
     "mf_plan_set_implicit_cg", "mf_plan_get_implicit_cg", "mf_backend_run_implicit_cg",
     "mf_backend_als_normal_pitch", "mf_plan_als_normal", "mf_plan_als_solve_normal",
+    "mf_plan_set_als_box", "mf_plan_get_als_box", "mf_backend_run_als_box",
 ]
 HOST_SYMBOLS = [
     "mf_host_parse_strerror", "mf_host_parse_file", "mf_host_parse_buffer", "mf_host_free_problem",
@@ -289,6 +290,10 @@ def hip():
         lib.mf_plan_get_implicit_cg.argtypes = [P, C.POINTER(C.c_int)]
         lib.mf_backend_run_implicit_cg.argtypes = [C.POINTER(Problem), P, P, P, P, C.c_double, C.c_double, C.POINTER(Bounds),
                                                    C.POINTER(Bounds), C.c_double, C.c_int, C.c_int]
+        lib.mf_plan_set_als_box.argtypes = [P, C.c_int]
+        lib.mf_plan_get_als_box.argtypes = [P, C.POINTER(C.c_int)]
+        lib.mf_backend_run_als_box.argtypes = [C.POINTER(Problem), P, P, P, P, C.c_double, C.c_double, C.POINTER(Bounds), C.POINTER(Bounds),
+                                               C.c_int, C.c_double, C.c_int, C.c_int]
         _hip = lib
     return _hip
 
@@ -665,6 +670,17 @@ def backend_run_implicit_cg(inst, L, R, steps, conf=1.0, bounds_users=None, boun
 
 
 run_implicit_cg = backend_run_implicit_cg
+
+
+def backend_run_als_box(inst, L, R, sweeps, kind="ridge", conf=1.0, bounds_users=None, bounds_items=None, weight=None, lambda_users=0.0,
+                        lambda_items=None, iters=None, device=0, recommend=True):
+    """mf_backend_run_als_box: `iters` ALS iterations of `kind` ("ridge" | "ridge-count" | "implicit", conf read under the last)
+    with `sweeps` coordinate-descent sweeps per row in place of Cholesky and the clamp (0: the direct solve)."""
+    return _run_boxed("als_box", inst, L, R, weight, lambda_users, lambda_items, bounds_users, bounds_items, iters, device, recommend,
+                      ALS_KINDS.get(kind, kind), float(conf), int(sweeps))
+
+
+run_als_box = backend_run_als_box
 
 
 def als_normal_pitch(feats):
@@ -1061,6 +1077,17 @@ class Plan:
         """mf_plan_get_implicit_cg: the steps"""
         s = C.c_int()
         _check(hip().mf_plan_get_implicit_cg(self._h, C.byref(s)), "mf_plan_get_implicit_cg")
+        return s.value
+
+    def set_als_box(self, sweeps):
+        """mf_plan_set_als_box: coordinate-descent sweeps per row of a direct ALS solve, each step exact within the side's box (0:
+        Cholesky, then the clamp); read at every launch"""
+        _check(hip().mf_plan_set_als_box(self._h, int(sweeps)), "mf_plan_set_als_box")
+
+    def als_box(self):
+        """mf_plan_get_als_box: the sweeps"""
+        s = C.c_int()
+        _check(hip().mf_plan_get_als_box(self._h, C.byref(s)), "mf_plan_get_als_box")
         return s.value
 
     def als_solve(self, side, other="current"):

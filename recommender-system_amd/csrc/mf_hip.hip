@@ -608,8 +608,9 @@ int mf_plan_set_als(mf_plan *p, int kind)
 	if (!p || !(als_kind_ok(kind) || kind == MF_ALS_IMPLICIT)) return MF_ERR_ARGUMENT;
 	if (kind != MF_ALS_OFF) {
 		// the solve this kind would run (als_solver, mf_schedule.h) takes the plan's K and, under the implicit kind, is implicit
-		const mf_sched::AlsSolver s = mf_sched::als_solver(kind, p->als_cg, p->implicit_cg);
+		const mf_sched::AlsSolver s = mf_sched::als_solver(kind, p->als_cg, p->implicit_cg, p->als_box);
 		if (p->K > s.max_k || (kind == MF_ALS_IMPLICIT && !s.implicit)) return MF_ERR_UNSUPPORTED;
+		if (s.cg && p->als_box > 0) return MF_ERR_UNSUPPORTED;   // box sweeps and the implicit kind's CG steps, both waiting for it
 		// a solve has neither a previous step nor a gradient: momentum or an adaptive side came first
 		if (p->rule[0].beta != 0.0 || p->rule[1].beta != 0.0 || adaptive_any(p)) return MF_ERR_UNSUPPORTED;
 	}
@@ -640,6 +641,7 @@ int mf_plan_set_als_cg(mf_plan *p, int steps)
 	// the solve these steps would run (als_solver, mf_schedule.h): implicit under the implicit kind, and K within its limit
 	const mf_sched::AlsSolver s = mf_sched::als_solver(p->als_kind, steps, p->implicit_cg);
 	if (p->als_kind == MF_ALS_IMPLICIT && !s.implicit) return MF_ERR_UNSUPPORTED;
+	if (steps > 0 && p->als_box > 0) return MF_ERR_UNSUPPORTED;   // box sweeps came first (mf_plan_set_als_box)
 	if (p->K > s.max_k && (s.cg || p->als_kind != MF_ALS_OFF)) return MF_ERR_UNSUPPORTED;
 	p->als_cg = steps;   // read at every launch
 	return MF_OK;
@@ -655,7 +657,29 @@ int mf_plan_get_als_cg(mf_plan *p, int *steps)
 int mf_plan_set_implicit_cg(mf_plan *p, int steps)
 {
 	if (!p || steps < 0 || steps > MF_ALS_CG_MAX_STEPS) return MF_ERR_ARGUMENT;
+	// under the implicit kind the steps are in force: box sweeps came first (mf_plan_set_als_box)
+	if (steps > 0 && p->als_box > 0 && p->als_kind == MF_ALS_IMPLICIT) return MF_ERR_UNSUPPORTED;
 	p->implicit_cg = steps;   // read at every launch, and only while the kind is MF_ALS_IMPLICIT
+	return MF_OK;
+}
+
+int mf_plan_set_als_box(mf_plan *p, int sweeps)
+{
+	if (!p || sweeps < 0 || sweeps > MF_ALS_BOX_MAX_SWEEPS) return MF_ERR_ARGUMENT;
+	if (sweeps > 0) {
+		// the solve the plan runs without them (als_solver, mf_schedule.h) has to be the direct one, at a K it takes
+		const mf_sched::AlsSolver s = als_solver(p);
+		if (s.cg || p->als_cg > 0) return MF_ERR_UNSUPPORTED;
+		if (p->als_kind != MF_ALS_OFF && p->K > mf_sched::kAlsDirectMaxK) return MF_ERR_UNSUPPORTED;
+	}
+	p->als_box = sweeps;   // read at every launch
+	return MF_OK;
+}
+
+int mf_plan_get_als_box(mf_plan *p, int *sweeps)
+{
+	if (!p) return MF_ERR_ARGUMENT;
+	if (sweeps) *sweeps = p->als_box;
 	return MF_OK;
 }
 
@@ -1122,6 +1146,7 @@ int mf_plan_describe(mf_plan *p, char *buf, int buflen)
 		} else {
 			const AlsForm &form = kAlsForm[als_form(p->K, p->cfg.als_form)];
 			append(buf, buflen, " als_form=%s(chunk=%d)", form.name, form.nch);
+			if (s.box_sweeps > 0) append(buf, buflen, " als_box=%d", s.box_sweeps);
 		}
 	}
 	// the environment switches this plan was created under, when any differs from its default (mf_config.hip.h)
@@ -1291,6 +1316,23 @@ int mf_backend_run_implicit_cg(const mf_problem *pr, const double *weight, doubl
 		int rc = mf_plan_set_confidence(p, conf);
 		if (rc == MF_OK) rc = mf_plan_set_implicit_cg(p, steps);
 		return rc == MF_OK ? mf_plan_set_als(p, MF_ALS_IMPLICIT) : rc;
+	});
+}
+
+// the ALS run of any kind with the box-constrained row solve (0 sweeps: the direct one); conf counts under the implicit kind
+int mf_backend_run_als_box(const mf_problem *pr, const double *weight, double *L, double *R, int32_t *best, double lambda_users,
+                           double lambda_items, const mf_bounds *bounds_users, const mf_bounds *bounds_items, int kind, double conf,
+                           int sweeps, int device)
+{
+	const bool implicit = kind == MF_ALS_IMPLICIT;
+	if (!run_args_ok(pr, L, R, {lambda_users, lambda_items}, bounds_users, bounds_items) || !(als_kind_ok(kind) || implicit) || sweeps < 0 ||
+	    sweeps > MF_ALS_BOX_MAX_SWEEPS || (implicit && (!std::isfinite(conf) || conf < 0.0)))
+		return MF_ERR_ARGUMENT;
+	const RulePair rule = level1_rules(lambda_users, lambda_items, 0.0, 0.0, bounds_users, bounds_items);
+	return run_single_plan(pr, weight, rule, L, R, best, device, [&](mf_plan *p) {
+		int rc = implicit ? mf_plan_set_confidence(p, conf) : MF_OK;
+		if (rc == MF_OK) rc = mf_plan_set_als_box(p, sweeps);
+		return rc == MF_OK ? mf_plan_set_als(p, kind) : rc;
 	});
 }
 

@@ -648,8 +648,8 @@ int launch_gram(mf_plan *p, int side, int generation)
 	return MF_OK;
 }
 
-// which solve the plan's next launch runs: the rule of mf_schedule.h on the plan's three fields, read at every launch
-mf_sched::AlsSolver als_solver(const mf_plan *p) { return mf_sched::als_solver(p->als_kind, p->als_cg, p->implicit_cg); }
+// which solve the plan's next launch runs: the rule of mf_schedule.h on the plan's four fields, read at every launch
+mf_sched::AlsSolver als_solver(const mf_plan *p) { return mf_sched::als_solver(p->als_kind, p->als_cg, p->implicit_cg, p->als_box); }
 
 // the arguments every row solve of a side takes, but the row list (walk_row_lists' caller fills it per launch)
 mf::AlsArgs als_args(const mf_plan *p, int side, int other_generation, unsigned long long *counts)
@@ -712,7 +712,7 @@ int launch_als(mf_plan *p, int side, int other_generation)
 
 	// the instance, the rows of a workgroup, its threads and LDS request, and the arguments behind `a` in the kernel's order
 	const void *fn;
-	int rows_per_wg, threads, steps = s.steps, nch = 0;
+	int rows_per_wg, threads, steps = s.steps, nch = 0, sweeps = s.box_sweeps;
 	size_t lds;
 	if (s.cg) {
 		const int form = als_cg_form(p->K, p->cfg.als_cg_form);
@@ -722,7 +722,12 @@ int launch_als(mf_plan *p, int side, int other_generation)
 	} else {
 		const AlsForm &form = kAlsForm[als_form(p->K, p->cfg.als_form)];
 		const int nb = (mf::als_blocks(p->K, form.bs) + form.threads - 1) / form.threads;
-		fn = s.implicit ? (const void *) form.implicit[nb - 1] : (const void *) form.fn[nb - 1];
+		if (sweeps > 0) {   // the box-constrained solve: the same form, geometry and LDS request
+			const AlsBoxForm &box = kAlsBoxForm[als_form(p->K, p->cfg.als_form)];
+			fn = s.implicit ? (const void *) box.implicit[nb - 1] : (const void *) box.fn[nb - 1];
+		} else {
+			fn = s.implicit ? (const void *) form.implicit[nb - 1] : (const void *) form.fn[nb - 1];
+		}
 		rows_per_wg = mf::kAlsThreads / form.threads, threads = mf::kAlsThreads;
 		lds = (size_t) rows_per_wg * mf::als_group_doubles(p->K, form.bs, form.nch, s.implicit || p->weighted) * sizeof(double);
 	}
@@ -730,6 +735,7 @@ int launch_als(mf_plan *p, int side, int other_generation)
 	MF_HIP(raise_lds_limit(fn, lds));
 	void *args[4] = {&a};
 	int nargs = 1;
+	if (sweeps > 0) args[nargs++] = &sweeps;
 	if (s.implicit) args[nargs++] = &im;
 	if (s.cg) args[nargs++] = &steps, args[nargs++] = &nch;
 
@@ -774,13 +780,16 @@ int launch_als_normal(mf_plan *p, int side, int other_generation, double *N, lon
 	const int rows_per_wg = mf::kAlsThreads / form.threads;
 	const void *fn = nullptr;
 	if (p->K <= form.max_k && nb >= 1 && nb <= 3)
-		fn = solve ? (const void *) form.solve : s.implicit ? (const void *) form.implicit[nb - 1] : (const void *) form.fn[nb - 1];
+		fn = solve ? (s.box_sweeps > 0 ? (const void *) kAlsBoxNormalForm[als_form(p->K, p->cfg.als_form)] : (const void *) form.solve)
+		           : s.implicit ? (const void *) form.implicit[nb - 1] : (const void *) form.fn[nb - 1];
 	if (!fn) return MF_ERR_UNSUPPORTED;   // a missing instance is an error, never another kernel
 	const size_t lds = (size_t) rows_per_wg * sizeof(double) *
 	                   (solve ? mf::als_solve_normal_doubles(p->K) : mf::als_group_doubles(p->K, form.bs, form.nch, s.implicit || p->weighted));
 	MF_HIP(raise_lds_limit(fn, lds));
+	int sweeps = s.box_sweeps;
 	void *args[3] = {&a, &nr};
 	int nargs = 2;
+	if (solve && sweeps > 0) args[nargs++] = &sweeps;   // the box-constrained solve of the records (mf_als_box.hip.h)
 	if (!solve && s.implicit) args[nargs++] = &im;
 
 	return walk_row_lists(sd, [&](const int *rowlist, int nrows) {

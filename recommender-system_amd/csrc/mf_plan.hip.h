@@ -289,6 +289,23 @@ const AlsNormalForm kAlsNormalForm[kAlsForms] = {
      {mf::als_normal_kernel<mf::kWave, 2, 1, mf::AlsImplicit>, mf::als_normal_kernel<mf::kWave, 2, 2, mf::AlsImplicit>, mf::als_normal_kernel<mf::kWave, 2, 3, mf::AlsImplicit>},
      mf::als_solve_normal_kernel<mf::kWave>},
 };
+// The box-constrained solve (mf_als_box.hip.h) in the same forms, in the order of AlsFormId and by blocks per thread: the
+// instances launch_als and launch_als_normal(solve) take where the rule (als_solver) names box sweeps; the geometry and the LDS
+// request of a form are kAlsForm's / kAlsNormalForm's.
+using AlsBoxFn = void (*)(mf::AlsArgs, int);
+using AlsBoxImplicitFn = void (*)(mf::AlsArgs, int, mf::AlsImplicit);
+using AlsBoxNormalFn = void (*)(mf::AlsArgs, mf::AlsNormal, int);
+struct AlsBoxForm {
+	AlsBoxFn fn[3];
+	AlsBoxImplicitFn implicit[3];
+};
+const AlsBoxForm kAlsBoxForm[kAlsForms] = {
+    {{mf::als_box_kernel<mf::kAlsThreads, 4, 1>, mf::als_box_kernel<mf::kAlsThreads, 4, 2>, mf::als_box_kernel<mf::kAlsThreads, 4, 3>},
+     {mf::als_box_kernel<mf::kAlsThreads, 4, 1, mf::AlsImplicit>, mf::als_box_kernel<mf::kAlsThreads, 4, 2, mf::AlsImplicit>, mf::als_box_kernel<mf::kAlsThreads, 4, 3, mf::AlsImplicit>}},
+    {{mf::als_box_kernel<mf::kWave, 2, 1>, mf::als_box_kernel<mf::kWave, 2, 2>, mf::als_box_kernel<mf::kWave, 2, 3>},
+     {mf::als_box_kernel<mf::kWave, 2, 1, mf::AlsImplicit>, mf::als_box_kernel<mf::kWave, 2, 2, mf::AlsImplicit>, mf::als_box_kernel<mf::kWave, 2, 3, mf::AlsImplicit>}},
+};
+const AlsBoxNormalFn kAlsBoxNormalForm[kAlsForms] = {mf::als_box_solve_normal_kernel<mf::kAlsThreads>, mf::als_box_solve_normal_kernel<mf::kWave>};
 // The forms of the conjugate-gradient solve in the order of mf_sched::AlsCgFormId; als_cg_form (mf_launch.hip.h) picks one,
 // als_cg_fn<>(form, K) its explicit instance (als_cg_kernel, mf_als_cg.hip.h), als_cg_fn<mf::AlsImplicit>(form, K) its
 // implicit one (als_icg_kernel, mf_als_icg.hip.h): null where the form does not take the K, and for the implicit kind above
@@ -357,6 +374,7 @@ struct mf_plan {
 	// three row counts of each side's last solve, [side][solved, kept_empty, kept_not_pd], allocated on first use
 	int als_kind = MF_ALS_OFF;
 	int als_cg = 0;   // conjugate-gradient steps per row (mf_plan_set_als_cg; 0: the direct solve), read at every launch
+	int als_box = 0;  // coordinate-descent sweeps per row (mf_plan_set_als_box; 0: Cholesky, then the clamp), read at every launch
 	dev_buf<unsigned long long> als_counts;
 	// implicit feedback: the confidence scale (mf_plan_set_confidence, read at every launch) and the Gram matrices of the two
 	// sides (mf_plan_gram): [items | users], each a packed lower triangle, and the per-block partials they are summed from

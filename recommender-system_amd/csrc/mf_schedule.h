@@ -632,10 +632,12 @@ constexpr int als_cg_chunk(size_t head, size_t row_bytes, size_t lds_per_cu)
 }
 
 // ---- which ALS solve a launch runs: the one rule over the plan's kind (mf_plan_set_als; kAlsImplicitKind is the header's
-// MF_ALS_IMPLICIT, mf_plan.hip.h asserts it), the steps of mf_plan_set_als_cg and those of mf_plan_set_implicit_cg.  The steps
-// of the explicit kinds come first and make the solve theirs; the implicit steps count under the implicit kind alone.  The
-// launch, mf_plan_describe and the setters all read it: a setter refuses the state whose solve does not take the plan's K,
-// and the implicit kind where the solve would not be an implicit one.
+// MF_ALS_IMPLICIT, mf_plan.hip.h asserts it), the steps of mf_plan_set_als_cg, those of mf_plan_set_implicit_cg and the sweeps
+// of mf_plan_set_als_box.  The steps of the explicit kinds come first and make the solve theirs; the implicit steps count under
+// the implicit kind alone; the box sweeps count where no steps are in force (the setters refuse the two together) and turn the
+// direct solve's Cholesky into coordinate descent (mf_als_box.hip.h).  The launch, mf_plan_describe and the setters all read it:
+// a setter refuses the state whose solve does not take the plan's K, and the implicit kind where the solve would not be an
+// implicit one.
 constexpr int kAlsImplicitKind = 4;
 constexpr int kAlsDirectMaxK = 128;   // the direct solve keeps a row's triangle in LDS (mf_als.hip.h: kAlsMaxK)
 struct AlsSolver {
@@ -643,13 +645,14 @@ struct AlsSolver {
 	bool implicit;   // S and the confidence beside the arguments
 	int steps;       // conjugate-gradient steps per row, 0 for the direct solve
 	int max_k;       // the widest K it takes
+	int box_sweeps;  // coordinate-descent sweeps per row of the direct solve (mf_als_box.hip.h), 0 for every other solve
 };
-constexpr AlsSolver als_solver(int als_kind, int als_cg, int implicit_cg)
+constexpr AlsSolver als_solver(int als_kind, int als_cg, int implicit_cg, int als_box = 0)
 {
-	if (als_cg > 0) return {true, false, als_cg, kAlsCgMaxK};
+	if (als_cg > 0) return {true, false, als_cg, kAlsCgMaxK, 0};
 	const bool implicit = als_kind == kAlsImplicitKind;
-	if (implicit && implicit_cg > 0) return {true, true, implicit_cg, kAlsDirectMaxK};
-	return {false, implicit, 0, kAlsDirectMaxK};
+	if (implicit && implicit_cg > 0) return {true, true, implicit_cg, kAlsDirectMaxK, 0};
+	return {false, implicit, 0, kAlsDirectMaxK, als_box > 0 ? als_box : 0};
 }
 
 }  // namespace mf_sched

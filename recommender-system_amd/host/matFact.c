@@ -22,11 +22,11 @@
 
 /* Every MATFACT_* variable the program reads: the mode options in the order they are examined, the path options, and the
  * accessories, which take part in no rule. */
-enum { V_TOPN, V_LOSS, V_HELDOUT, V_RANK, V_SIMILAR, V_SIMILAR_OUT, V_LAMBDA, V_BIAS, V_MOMENTUM, V_WEIGHTS, V_BOUNDS, V_OPTIMIZER, V_SOLVER, V_IMPLICIT, V_ALS_CG, V_IMPLICIT_CG, V_DEVICES, V_MATS, V_CHECKPOINT, V_RESUME,
+enum { V_TOPN, V_LOSS, V_HELDOUT, V_RANK, V_SIMILAR, V_SIMILAR_OUT, V_LAMBDA, V_BIAS, V_MOMENTUM, V_WEIGHTS, V_BOUNDS, V_OPTIMIZER, V_SOLVER, V_IMPLICIT, V_ALS_CG, V_IMPLICIT_CG, V_ALS_BOX, V_DEVICES, V_MATS, V_CHECKPOINT, V_RESUME,
        V_DEVICE, V_MATS_ITERS, V_CHECKPOINT_EVERY, V_CACHE, V_TIMING, V_COUNT };
 static const char *const cli_names[V_COUNT] = {
 	"MATFACT_TOPN", "MATFACT_LOSS", "MATFACT_HELDOUT", "MATFACT_RANK", "MATFACT_SIMILAR", "MATFACT_SIMILAR_OUT", "MATFACT_LAMBDA",
-	"MATFACT_BIAS", "MATFACT_MOMENTUM", "MATFACT_WEIGHTS", "MATFACT_BOUNDS", "MATFACT_OPTIMIZER", "MATFACT_SOLVER", "MATFACT_IMPLICIT", "MATFACT_ALS_CG", "MATFACT_IMPLICIT_CG", "MATFACT_DEVICES", "MATFACT_MATS", "MATFACT_CHECKPOINT", "MATFACT_RESUME", "MATFACT_DEVICE",
+	"MATFACT_BIAS", "MATFACT_MOMENTUM", "MATFACT_WEIGHTS", "MATFACT_BOUNDS", "MATFACT_OPTIMIZER", "MATFACT_SOLVER", "MATFACT_IMPLICIT", "MATFACT_ALS_CG", "MATFACT_IMPLICIT_CG", "MATFACT_ALS_BOX", "MATFACT_DEVICES", "MATFACT_MATS", "MATFACT_CHECKPOINT", "MATFACT_RESUME", "MATFACT_DEVICE",
 	"MATFACT_MATS_ITERS", "MATFACT_CHECKPOINT_EVERY", "MATFACT_CACHE", "MATFACT_TIMING"};
 
 struct cli_options {
@@ -58,6 +58,8 @@ struct cli_options {
 	                      /* gradient steps per solve instead of being solved directly (mf_plan_set_als_cg); K up to 256 */
 	int implicit_cg;      /* MATFACT_IMPLICIT_CG=steps (1..MF_ALS_CG_MAX_STEPS) next to MATFACT_IMPLICIT: the same for the implicit solve */
 	                      /* (mf_plan_set_implicit_cg) */
+	int als_box;          /* MATFACT_ALS_BOX=sweeps (1..MF_ALS_BOX_MAX_SWEEPS) next to MATFACT_SOLVER: every row is solved by that many */
+	                      /* coordinate-descent sweeps inside MATFACT_BOUNDS' box instead of directly and clamped (mf_plan_set_als_box) */
 	int device;           /* MATFACT_DEVICE=n: the GPU of a single-GPU run, default 0 */
 	int devs[16], ndev;   /* MATFACT_DEVICES=0,1,...: row-shard over these GPUs of the process, at most 16 */
 	const char *devices_error;   /* a non-number in it: said only where that path runs, after the input was read, as ever */
@@ -154,6 +156,8 @@ static const char *cli_value(int v, const char *s, struct cli_options *o)
 		return whole(s, MF_ALS_CG_MAX_STEPS, 0, &rest, &o->als_cg) ? NULL : "MATFACT_ALS_CG: expected a whole number from 1 to 256.";
 	case V_IMPLICIT_CG:
 		return whole(s, MF_ALS_CG_MAX_STEPS, 0, &rest, &o->implicit_cg) ? NULL : "MATFACT_IMPLICIT_CG: expected a whole number from 1 to 256.";
+	case V_ALS_BOX:
+		return whole(s, MF_ALS_BOX_MAX_SWEEPS, 0, &rest, &o->als_box) ? NULL : "MATFACT_ALS_BOX: expected a whole number from 1 to 256.";
 	}
 	return NULL;   /* MATFACT_HELDOUT, MATFACT_SIMILAR_OUT, MATFACT_WEIGHTS: any text */
 }
@@ -177,6 +181,7 @@ static const struct cli_rule cli_needs[] = {
 	{V_IMPLICIT, BIT(V_SOLVER), "MATFACT_IMPLICIT needs MATFACT_SOLVER=als."},
 	{V_ALS_CG, BIT(V_SOLVER), "MATFACT_ALS_CG needs MATFACT_SOLVER=als or als,count."},
 	{V_IMPLICIT_CG, BIT(V_IMPLICIT), "MATFACT_IMPLICIT_CG needs MATFACT_IMPLICIT."},
+	{V_ALS_BOX, BIT(V_SOLVER), "MATFACT_ALS_BOX needs MATFACT_SOLVER=als or als,count."},
 };
 /* `var` cannot be combined with any one of `others` (MATFACT_SIMILAR has two rows: it says two different things) */
 static const struct cli_rule cli_clashes[] = {
@@ -193,6 +198,7 @@ static const struct cli_rule cli_clashes[] = {
 	{V_SOLVER, PATHS | BIT(V_SIMILAR) | BIT(V_MOMENTUM) | BIT(V_OPTIMIZER), "MATFACT_SOLVER works on the single-GPU path only and not with momentum or an optimizer: unset MATFACT_DEVICES, MATFACT_MATS, MATFACT_CHECKPOINT, MATFACT_RESUME, MATFACT_SIMILAR, MATFACT_MOMENTUM and MATFACT_OPTIMIZER."},
 	{V_IMPLICIT, BIT(V_BIAS), "MATFACT_IMPLICIT cannot be combined with MATFACT_BIAS: the implicit solve has no frozen columns."},
 	{V_ALS_CG, BIT(V_IMPLICIT), "MATFACT_ALS_CG cannot be combined with MATFACT_IMPLICIT: the implicit solve is the direct one."},
+	{V_ALS_BOX, BIT(V_ALS_CG) | BIT(V_IMPLICIT_CG), "MATFACT_ALS_BOX cannot be combined with MATFACT_ALS_CG or MATFACT_IMPLICIT_CG: the box sweeps replace the direct solve."},
 };
 
 /* Fills `o` from the environment -- it opens no file and makes no GPU call -- and returns NULL, or the message to die with. */
@@ -203,7 +209,7 @@ static const char *cli_parse(struct cli_options *o)
 	for (int v = 0; v < V_COUNT; v++)
 		if ((o->value[v] = getenv(cli_names[v])) != NULL) set |= BIT(v);
 	const unsigned usable = o->value[V_SIMILAR_OUT] && !*o->value[V_SIMILAR_OUT] ? set & ~BIT(V_SIMILAR_OUT) : set;
-	for (int v = V_TOPN; v <= V_IMPLICIT_CG; v++) {
+	for (int v = V_TOPN; v <= V_ALS_BOX; v++) {
 		const char *message = set & BIT(v) ? cli_value(v, o->value[v], o) : NULL;
 		if (message) return message;
 		if (!(set & BIT(v))) continue;
@@ -439,6 +445,7 @@ static int run_session(const struct cli_options *o, const mf_problem *p, const m
 	if (rc == MF_OK && o->implicit) rc = mf_plan_set_confidence(s.plan, o->conf);
 	if (rc == MF_OK && o->als_cg) rc = mf_plan_set_als_cg(s.plan, o->als_cg);   /* first: K may lie in 129 .. 256 */
 	if (rc == MF_OK && o->implicit_cg) rc = mf_plan_set_implicit_cg(s.plan, o->implicit_cg);
+	if (rc == MF_OK && o->als_box) rc = mf_plan_set_als_box(s.plan, o->als_box);
 	if (rc == MF_OK && o->als) rc = mf_plan_set_als(s.plan, o->als);
 	/* loop */
 	if (rc == MF_OK) {

@@ -118,11 +118,13 @@ class AlsShardedFactorization:
         solve       : every rank solves the summed systems into its R replica
         flip
     `normal` is one torch tensor of (items + 1, pitch) float64 on the plan's device, pitch even and at least
-    capi.als_normal_pitch(K).  Conjugate-gradient steps are refused by the library: they need a sum per step."""
+    capi.als_normal_pitch(K).  Conjugate-gradient steps are refused by the library: they need a sum per step.  `box_sweeps` > 0
+    makes every row solve, the users' and the one of the summed records, the box-constrained one (Plan.set_als_box)."""
 
-    def __init__(self, plan, normal, rank, world, group=None, stream=None):
+    def __init__(self, plan, normal, rank, world, group=None, stream=None, box_sweeps=0):
         """`stream`: as for ShardedFactorization, a NON-default torch.cuda.Stream for GPU runs, on which the plan's launches
-        and the collective are ordered; None only for CPU stand-in plans (tests)."""
+        and the collective are ordered; None only for CPU stand-in plans (tests).  `box_sweeps`: set on the plan when it is not
+        what the plan already has (0: the direct solve, the default of a plan)."""
         if normal.dim() != 2 or normal.dtype != torch.float64 or not normal.is_contiguous():
             raise ValueError("normal must be a contiguous (items + 1, pitch) float64 tensor")
         if normal.shape[0] != plan.items + 1 or normal.shape[1] % 2:
@@ -130,6 +132,9 @@ class AlsShardedFactorization:
         self.plan, self.normal, self.rank, self.world, self.group = plan, normal, rank, world, group
         self.pitch = int(normal.shape[1])
         self.stream = stream
+        self.box_sweeps = int(box_sweeps)
+        if self.box_sweeps or hasattr(plan, "set_als_box"):   # a stand-in plan without the setter is a plan at 0
+            plan.set_als_box(self.box_sweeps)
         if stream is not None:
             if int(stream.cuda_stream) == 0:
                 raise ValueError("AlsShardedFactorization needs a non-default CUDA stream")
